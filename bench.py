@@ -29,6 +29,9 @@ collective) => weak scaling; the only torch.distributed use is the barrier and t
 `--global-batch G` instead builds ONE length-varied batch of G utterances, shards it over the ranks (artspeech_amd.shard) and
 checks the merged result against a single-rank run (BASELINE config C4).
 
+--dump-outputs DIR: after the timed steps, what the last timed step of the arrangement that became `value` returned (the mel of its
+batch of 32; seeded inputs, the same from run to run for the same arguments) is written as DIR/<name>.npy, 64 MB at most.
+
 Prints ONE JSON line (rank 0).  Beside the contract's keys:
   roofline       the dominant kernel, the implicit-GEMM conv on the fp16 matrix cores (f16x3 split-operand arithmetic, fp32-accurate):
                  algorithmic flop / its HIP-event time on the launch stream (an instrumented pass of the same step, branches back to back)
@@ -140,6 +143,34 @@ def pack_inputs(host, idx, dev):
     g["ref_lens"] = [host["ref_lens"][i] for i in idx]
     g["frames"] = [host["frames"][i] for i in idx]
     return g
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step, as d/<name>.npy (float32 stays float32,
+    integer arrays become float64: exact).  Over DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded, sorted sample of
+    its columns (last axis) -- the same columns from run to run for the same arguments.  -> {name: shape written}"""
+    arrays = {k: np.asarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)                 # (room for the .npy headers)
+    os.makedirs(d, exist_ok=True)
+    written = {}
+    for k, a in arrays.items():
+        if total > budget and a.ndim:
+            n = a.shape[-1]
+            keep = max(1, int(n * budget / total))
+            a = a[..., np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))]
+        np.save(os.path.join(d, f"{k}.npy"), np.ascontiguousarray(a))
+        written[k] = list(a.shape)
+    return written
+
+
+def host_arrays(out):
+    """the device tensors of a forward result dict (mel, dur_i, frame_off as present) on the host"""
+    torch.cuda.synchronize()
+    return {k: v.detach().cpu().numpy() for k, v in out.items() if isinstance(v, torch.Tensor)}
 
 
 def adjacent_submissions(g, per):
@@ -680,12 +711,13 @@ def merge_hosts(hosts):
     return {k: [v for h in hosts for v in h[k]] for k in hosts[0]}
 
 
-def bench_coalesced(net, hosts, k, n_lanes, steps, warmup, barrier=lambda: None):
+def bench_coalesced(net, hosts, k, n_lanes, steps, warmup, barrier=lambda: None, last=None):
     """The K timed steps as K submissions of ONE 32-utterance batch each through the library's lanes with as_lanes_set_coalesce(k): a lane's k
     consecutive batches live in adjacent column ranges of one block, so the lane launches them as ONE as_forward_test call over 32 k
     utterances, without a copy (wider conv GEMM launches, one fetch of the weights for k batches; models.py:361-362 processes one utterance
     at a time: any grouping is legal).  hosts: k * n_lanes make_inputs host dicts (one per batch).  Every batch's mel is compared with the
-    same batch run ALONE as one merged chain (not bitwise: k times the columns, another GEMM tile)."""
+    same batch run ALONE as one merged chain (not bitwise: k times the columns, another GEMM tile).  last (a dict): receives the host
+    arrays of the last step of the first timed pass (the line's figure) -- what its submitter gets back: the mel of its batch."""
     from artspeech_amd import models
     dev = net.rt.device
     per = len(hosts[0]["frames"])
@@ -725,6 +757,8 @@ def bench_coalesced(net, hosts, k, n_lanes, steps, warmup, barrier=lambda: None)
         barrier()
         torch.cuda.synchronize()
         els.append(time.perf_counter() - t0)
+        if last is not None and len(els) == 1:
+            last.update(host_arrays(order[(steps - 1) % len(order)]["out"]))
         for i in range(steps, (steps // len(order) + 1) * len(order)):   # finish the round: every output block is of ONE launch generation
             submit(i)
         lanes.wait()
@@ -1004,6 +1038,8 @@ def main():
                     "adjacent buffers, no copy); with --in-flight F the library runs F / coalesce lanes.  1 = off")
     ap.add_argument("--lane-branches", action="store_true", help="lanes in flight keep their step's branches on side streams (default: a "
                     "lane in flight is one chain on one stream)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the timed arrangement's last step "
+                    "returned (the mel of its batch; with one batch in flight also dur_i and frame_off) as DIR/<name>.npy, rank 0")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1079,6 +1115,8 @@ def main():
     run = runner.step if args.no_graph else runner.capture()
     elapsed = runner.timed(run, args.steps, args.warmup, barrier)
     single_ms = elapsed / args.steps * 1e3                               # one step at a time: the step's latency
+    # --dump-outputs: the result of the last timed step of whichever arrangement becomes `value` (replaced below when another one does)
+    dump = dict(arrangement="one batch at a time", arrays=host_arrays(runner.out)) if args.dump_outputs else None
     if not args.no_graph:
         torch.cuda.synchronize()
         assert torch.equal(runner.out["mel"], mel_first), "graph replay changed the result"
@@ -1114,7 +1152,9 @@ def main():
         # one chain ALONE (the latency of a batch on a merging serial plan, beside single_ms: the same batch with its branches on side streams)
         with torch.cuda.stream(lanes[0][2]):
             one_chain_ms = lanes[0][0].timed(lanes[0][1], max(args.steps // 4, 5), 3, lambda: None) / max(args.steps // 4, 5) * 1e3
-        it = [0]
+        # the warm-up ends on the last lane: timed step i runs lane i % n_fl, i.e. batch seed DATA_SEED + 100 (i % n_fl) -- the batch the
+        # coalesced arrangement's step i submits too, so that --dump-outputs holds the same batch whichever arrangement is adopted
+        it = [-args.warmup % n_fl]
 
         def run_lanes():
             _, fn, st = lanes[it[0] % n_fl]
@@ -1132,6 +1172,8 @@ def main():
             lanes_ok = bool(int(ok_t.item()))
         if lanes_ok:
             elapsed = elapsed_fl
+            if dump is not None:                             # (every lane verified against its first step: the last timed step's bits)
+                dump = dict(arrangement=f"{n_fl} batches in flight", arrays=host_arrays(lanes[(args.steps - 1) % n_fl][0].out))
         else:
             in_flight_note = "results of the batches in flight differed from the one-at-a-time result: in-flight timing discarded"
             n_fl = 1
@@ -1143,7 +1185,8 @@ def main():
         kc = args.coalesce
         ncl = max(1, n_fl // kc)
         hosts = [host] + [make_inputs(None, seed0=DATA_SEED + 100 * i)[0] for i in range(1, kc * ncl)]
-        coal, coal_first = bench_coalesced(net, hosts, kc, ncl, args.steps, args.warmup, barrier)
+        coal_last = {} if dump is not None else None
+        coal, coal_first = bench_coalesced(net, hosts, kc, ncl, args.steps, args.warmup, barrier, last=coal_last)
         c_el, l_el, c_ok = coal["elapsed_s"], elapsed, coal["results_verified"]
         if world > 1:                                        # ONE decision for all ranks (what follows holds collectives): the slowest rank's times
             cpu = dist.get_backend() == "gloo"
@@ -1154,6 +1197,8 @@ def main():
         if coal["adopted_as_value"]:
             elapsed_lanes32 = elapsed
             elapsed = coal["elapsed_s"]
+            if dump is not None:
+                dump = dict(arrangement=f"coalesced {kc}x32", arrays=coal_last)
     predicted = None
     if coal is not None and rank == 0:
         try:
@@ -1343,6 +1388,9 @@ def main():
             line["parity_coalesced_mel_max_abs_vs_oracle"] = max(
                 float((coal_first[:, fo[b]:fo[b + 1]].cpu() - outs[b]["mel"]).abs().max()) for b in range(min(len(outs), B)))
     line["forward_calls_in_process"] = FORWARD_CALLS[0] if args.no_graph else None      # (what a kernel trace of an eager run holds)
+    if dump is not None and rank == 0:
+        line["dump_outputs"] = dict(dir=args.dump_outputs, arrangement=dump["arrangement"], last_step=args.steps - 1,
+                                    arrays=dump_outputs(args.dump_outputs, dump["arrays"]))
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -57,7 +57,7 @@ def _cases(golden_dir, tag):
 
 @pytest.mark.parametrize("tag", ["tiny", "full"])
 def test_oracle_matches_reference(golden_dir, tag):
-    torch.set_num_threads(max(1, os.cpu_count() or 1))
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
     files = _cases(golden_dir, tag)
     assert files
     for f in files:
@@ -89,7 +89,7 @@ def allin_extractor_weights(gain):
 @pytest.mark.parametrize("tag", ["tiny", "full"])
 def test_oracle_allin_matches_reference(golden_dir, tag):
     """forward(step="test") with the reference's real JDCNet and EMA_Predictor in the loop (models.py:426-449 feeding :356-371)"""
-    torch.set_num_threads(max(1, os.cpu_count() or 1))
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
     files = sorted(glob.glob(os.path.join(golden_dir, f"net_allin_{tag}_*.npz")))
     assert files
     for f in files:
