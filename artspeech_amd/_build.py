@@ -14,8 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libartspeech_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-# AS_BUILD_FLAGS="-DAS_EXPERIMENTS": also compile the tuning variants (other GEMM pipeline shapes, the 256x128 tile) that the
-# shipped library leaves out; AS_TEST_EXPERIMENTS=1 adds their ids to the test matrix
+# AS_BUILD_FLAGS: extra hipcc flags for every source (a change of flags recompiles everything)
 EXTRA = os.environ.get("AS_BUILD_FLAGS", "").split()
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall",
          "-Wno-unused-function", "-I", CSRC, "-I", os.path.join(os.path.dirname(HERE), "include")] + EXTRA

@@ -205,14 +205,6 @@ __global__ void __launch_bounds__(NW * 64)
 relpos_attention_image_kernel(const AttnImageArgs a)
 {
     constexpr int DK = 128, KB = DK / 16, NT = NW * 64, NQ = NW * 32;
-#ifdef ATTN_DBG
-    long long tmark[16];
-    int nmark = 0;
-#define ATTN_MARK() tmark[nmark++] = __builtin_readcyclecounter()
-#else
-#define ATTN_MARK()
-#endif
-    ATTN_MARK();
     const int grp = a.ek2 ? (int)blockIdx.z / a.b_split : 0;
     const float* emb_k = a.ek1 + (ptrdiff_t)grp * (a.ek2 - a.ek1);
     const float* emb_v = a.ev1 + (ptrdiff_t)grp * (a.ev2 - a.ev1);
@@ -300,10 +292,8 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             V2[(((1 * 4 + c) * 2 + gg) * DK + d) * 2 + (ig & 1)] = ll;
         }
     };
-    ATTN_MARK();
     issue_k(0, 0);                                                      // (in flight while the tables are built)
     load_v(0);
-    ATTN_MARK();
     // the two 9-row tables as matrix-core operands: q . Ek[r] is one more "key" block, sum_r p_r Ev[r] one more contraction block.
     // (all loads first, then the conversions: one memory round trip, shared with the K / V tile above)
     {
@@ -324,11 +314,6 @@ relpos_attention_image_kernel(const AttnImageArgs a)
 #pragma unroll
             for (int j = 0; j < 8; ++j) xv[it][j] = emb_v[min(8 * gg + j, nrel - 1) * DK + d];
         }
-        ATTN_MARK();
-#ifdef ATTN_DBG
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        ATTN_MARK();
-#endif
 #pragma unroll
         for (int it = 0; it < EI; ++it) {
             const int idx = tid + it * NT, r = idx & 31, dg = idx >> 5;
@@ -352,9 +337,7 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             EvT[(1 * 2 + gg) * DK + d] = ll;
         }
     }
-    ATTN_MARK();
     __syncthreads();                                                    // the tables are visible
-    ATTN_MARK();
     // q . Ek[r] for the wave's 32 queries: S_rel^T = Ek . Q^T, rows r = 8 (e >> 2) + 4 g + (e & 3)
     {
         f32x16 SR;
@@ -374,7 +357,6 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             if (r < nrel) Rk[ql * MAXREL + r] = SR[e] * cs;
         }
     }
-    ATTN_MARK();
     float m = -INFINITY, lsum = 0.f;
     f32x16 acc[4];
 #pragma unroll
@@ -387,7 +369,6 @@ relpos_attention_image_kernel(const AttnImageArgs a)
         store_v(k0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // this wave's share of the K tile has landed
         __syncthreads();                                                // K tile k0 (DMA) and V tile k0 are in LDS (first time: Rk too)
-        if (k0 == 0) ATTN_MARK();
         if (k0 + FK < N) {
             issue_k(k0 + FK, buf ^ 1);
             load_v(k0 + FK);
@@ -407,7 +388,6 @@ relpos_attention_image_kernel(const AttnImageArgs a)
                 S[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, Qh[kb]), S[sb], 0, 0, 0);
             }
         }
-        if (k0 == 0) ATTN_MARK();
         bool band[2];
         float mx = -INFINITY;
 #pragma unroll
@@ -444,7 +424,6 @@ relpos_attention_image_kernel(const AttnImageArgs a)
                 S[sb][e] = pe;
                 lsum += pe;
             }
-        if (k0 == 0) ATTN_MARK();
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb) {
             if (!band[sb]) continue;
@@ -480,7 +459,6 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             }
             __builtin_amdgcn_wave_barrier();
         }
-        if (k0 == 0) ATTN_MARK();
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float pv[8];
@@ -498,18 +476,8 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             }
         }
         __syncthreads();                                                // everybody is done with Vt and this K buffer
-        if (k0 == 0) ATTN_MARK();
     }
     const float ltot = lsum + __shfl_xor(lsum, 32);
-#ifdef ATTN_DBG
-    __syncthreads();
-    ATTN_MARK();
-    if (a.out && blockIdx.x == 0 && blockIdx.y == 1 && blockIdx.z == 1 && tid == 0) {
-        for (int i = 1; i < nmark; ++i) a.out[(size_t)(DK * 2 - 1) * a.ldo + i] = (float)(tmark[i] - tmark[i - 1]);
-        a.out[(size_t)(DK * 2 - 1) * a.ldo] = (float)nmark;
-        return;
-    }
-#endif
     if (qi < N) {
         const float inv = 1.0f / ltot;
 #pragma unroll

@@ -559,9 +559,9 @@ extern "C" int as_set_range_probe(int on)
 
 static void tile_dims(int choice, int* bm, int* bn)
 {
-    // 42 / 22 / 21 / 12 / 11 / 14 / 2: 256x128, 128x128, 128x64, 64x128, 64x64, 64x256, 32x128 (4 waves each)
-    *bm = choice == 42 ? 256 : (choice == 22 || choice == 21) ? 128 : choice == 2 ? 32 : 64;
-    *bn = choice == 14 ? 256 : (choice == 42 || choice == 22 || choice == 12 || choice == 2) ? 128 : 64;
+    // 22 / 21 / 12 / 11 / 14 / 2: 128x128, 128x64, 64x128, 64x64, 64x256, 32x128 (4 waves each)
+    *bm = (choice == 22 || choice == 21) ? 128 : choice == 2 ? 32 : 64;
+    *bn = choice == 14 ? 256 : (choice == 22 || choice == 12 || choice == 2) ? 128 : 64;
 }
 
 // Tile choice, fitted to sweeps on MI355X (scripts/gemm_bench.py, round 2).  The time of a launch is the time of its busiest CU:
@@ -571,7 +571,7 @@ static void tile_dims(int choice, int* bm, int* bn)
 // (240); M512 N1280 K512 T3: 25.6 / 17.8 / 15.2 us for 40 / 80 / 160 tiles.
 static int gemm_tile_choice(int M, int N, int n_prod, int Kp)
 {
-    const char* env = getenv("AS_GEMM_TILE");           // tuning/experiments only: 42, 22, 21, 12, 11, 14
+    const char* env = getenv("AS_GEMM_TILE");           // tests/tuning only: 22, 21, 12, 11, 14
     if (env && atoi(env) > 0) return atoi(env);
     if (M <= 32 && n_prod == 3) return 2;                              // a 64-row tile would be half empty (HiFi-GAN's last stage: 32 channels, 1.9 M columns)
     // <= 64 output channels over many columns (the towers' first convs, 64 x 509 440): the 64 x 128 tile splits K over wave pairs and
@@ -579,30 +579,18 @@ static int gemm_tile_choice(int M, int N, int n_prod, int Kp)
     // M64 N509440 K64 T9 167 -> 139 us, N128000 41 -> 34, N63680 20.8 -> 19.7; below one round of the chip (N6400: 8.6 -> 10.8) it loses.
     if (M <= 64 && n_prod == 3 && as_cdiv(N, 256) >= 240) return 14;
     const bool tall = M > 64 && (M % 128 == 0 || M % 128 > 64 || M >= 512);   // a 128-row tile is not half empty
-    static const int choices[5] = {42, 22, 21, 12, 11};
-    // 256x128 (a wave owns 128 x 64): a third less LDS traffic per matrix-core product, but 364 registers: ONE workgroup per CU.
-    // Ten identical launches back to back in a hipGraph: M1024 N6400 K1216 T3 127 us against 152 for 128x128, M256 N32000 K256 T9 94
-    // against 106, M512 N19200 105 against 96.  Inside the step the same launches take the same time with either tile (C3: 5.08 against
-    // 5.10 ms of GEMM per step, C5: 8.78 against 8.70), so the default stays with the tiles that share a CU; -DAS_EXPERIMENTS builds
-    // carry it (AS_GEMM_TILE=42 / AS_GEMM_USE42=1).
-    double t1[5] = {1.55, 1.0, 0.78, 0.78, 0.59};
-#ifdef AS_EXPERIMENTS
-    static const bool use42 = getenv("AS_GEMM_USE42") != nullptr;
-    static const double t42 = getenv("AS_GEMM_T42") ? atof(getenv("AS_GEMM_T42")) : 1.55;   // (tuning: the 256 x 128 tile's cost alone on a CU)
-    t1[0] = t42;
-#else
-    constexpr bool use42 = false;
-#endif
+    // (a 256 x 128 tile was measured and removed: faster alone, no gain inside the step -- DESIGN.md section 3.1)
+    static const int choices[4] = {22, 21, 12, 11};
+    static const double t1[4] = {1.0, 0.78, 0.78, 0.59};
     int best = 11;
     double best_cost = 1e30;
-    for (int c = 0; c < 5; ++c) {
+    for (int c = 0; c < 4; ++c) {
         int bm, bn;
         tile_dims(choices[c], &bm, &bn);
         if (bm >= 128 && !tall) continue;
-        if (bm == 256 && (M % 256 != 0 || n_prod != 3 || !use42)) continue;
         const double tiles = (double)as_cdiv(M, bm) * as_cdiv(N, bn);
         const double n = ceil(tiles / 256.0);
-        const double cost = t1[c] * (bm == 256 ? n : (n > 1.0 ? 0.71 * n : 1.0));
+        const double cost = t1[c] * (n > 1.0 ? 0.71 * n : 1.0);
         if (cost < best_cost * 0.97) { best_cost = cost; best = choices[c]; }   // (ties go to the larger tile)
     }
     // An image of <= 32 channels may come from the 32-row tile, which leaves the upper half of the image's 64-row block unwritten (clearing
@@ -634,8 +622,7 @@ static int gemm_ksplit(int M, int N, int Kp, int T, int choice, int K2 = 0)
         // with the reduction pass behind them
         s = 512 / (int)tiles;
     }
-    const int env_min = getenv("AS_GEMM_MINKT") ? atoi(getenv("AS_GEMM_MINKT")) : 0;   // tuning/experiments only
-    const int min_kt = env_min > 0 ? env_min : 24 / wk;   // a slice keeps >= 384 k
+    const int min_kt = 24 / wk;                           // a slice keeps >= 384 k
     if (s > nkt / min_kt) s = nkt / min_kt;
     return s < 1 ? 1 : s;
 }
@@ -656,34 +643,9 @@ static GemmPlan gemm_plan(const ConvGemmArgs& a)
     return p;
 }
 
-// A launch of 1.x rounds of the chip: 513 .. 1024 tiles of 128 x 128 on 512 workgroup slots (the six 1 024-row decoder convs at 64
-// utterances per call: 800 tiles).  Its second round leaves most CUs with one workgroup, at 0.71 of the paired rate.  The last sixth of
-// the columns on 128 x 64 tiles instead -- listed last, so they fill the slots the big tiles leave -- levels it: M1024 N12800 K1024 T3
-// 227 -> 200-203 us with 12-25 % of the columns small, K1216 270 -> 237-240 (scripts/exp/tilemix_bound.py, two free-running launches:
-// the bound; scripts/exp/records/riders_r06.txt).  Launches of one round or less lose (M1024 N6400 + 6 %, M512 N12800 + 4 %): not them.
-// Returns the first small column (a multiple of 128), or 0: no mixing.  Same products, and for the small tile's columns the order of
-// partial sums of the 128 x 64 tile (two K halves summed through LDS).
-// OFF unless AS_GEMM_MIX=1: inside the step the gain is not there -- two coalescing lanes, 40 steps, alternating runs on one box: 3.86-3.87
-// ms per step mixed against 3.82-3.84 unmixed (the conv class by events 0.387-0.389 against 0.384-0.386 of the ceiling: the launches are
-// a little faster, the step is not) -- like every tile experiment before it.  The kernel and the rule stay, tested.
-static int gemm_mix_split(const ConvGemmArgs& a, int choice, int S)
-{
-    const char* on = getenv("AS_GEMM_MIX");                                // (read per call: tests, A/B runs)
-    const bool off = !(on && *on == '1');
-    if (off || choice != 22 || S != 1 || a.n_prod != 3 || a.n_groups > 1 || a.M % 128 != 0 || a.slab_tr) return 0;
-    const int tn = as_cdiv(a.N, 128), tiles = (a.M / 128) * tn;
-    if (tiles <= 512 + 64 || tiles > 1024) return 0;
-    const char* fe = getenv("AS_GEMM_MIX_FRAC");
-    const double frac = fe ? atof(fe) : 0.17;
-    const int small_t = std::max(1, (int)(frac * tn + 0.5));
-    const int split = (tn - small_t) * 128;
-    return split > 0 && split < a.N ? split : 0;
-}
-
 static bool direct_cin1(const ConvGemmArgs& a)
 {
-    return a.K == 1 && !a.K2 && a.W && a.X && (!a.Yh || a.T <= 9) && !a.res && !a.div_sqrt2 && !a.transpose_out && a.ileave_u <= 1 && a.M <= DIRECT_MAX_M && a.n_groups <= 1 &&
-           !getenv("AS_GEMM_NO_DIRECT");
+    return a.K == 1 && !a.K2 && a.W && a.X && (!a.Yh || a.T <= 9) && !a.res && !a.div_sqrt2 && !a.transpose_out && a.ileave_u <= 1 && a.M <= DIRECT_MAX_M && a.n_groups <= 1;
 }
 
 // A conv with an AdaIN / LayerNorm behind it (as_conv_gemm_multi_post_f32) whose output is tiny (batch-1 sizes: <= 1 MB) is cut into TWO K
@@ -972,8 +934,7 @@ static int conv_gemm_one(const ConvGemmArgs* args_host, const AsAdainArgs* post_
     const ConvGemmArgs* one = &a;
     const bool fuse_ln = S > 1 && want_ln && ln_fusable(a, *ln_host);
     norm.slab_tr = fuse_ln ? 1 : 0;                                     // (the slices store time-major for the reduction that normalises columns)
-    const int mix = gemm_mix_split(a, plan.choice, S);
-    const int rc = mix ? as_conv_gemm_h3_launch_mix(one, mix, stream) : as_conv_gemm_h3_launch(&one, &S, 1, plan.choice, stream);
+    const int rc = as_conv_gemm_h3_launch(&one, &S, 1, plan.choice, stream);
     if (rc != AS_OK) return rc;
     if (fuse_ln) {
         const AsAdainArgs* np = nullptr;
@@ -1152,8 +1113,7 @@ static int conv_gemm_multi(const ConvGemmArgs* list_host, const AsAdainArgs* pos
     for (int i = 0; i < m; ++i) {
         const ConvGemmArgs& a = norm[i];
         const int min_kt = std::max(1, 24 / wk);
-        static const double thr = getenv("AS_MULTI_SLICE_THR") ? atof(getenv("AS_MULTI_SLICE_THR")) : 1.5;   // (tuning)
-        int s = nkt[i] > thr * share ? (int)ceil(nkt[i] / share) : 1;
+        int s = nkt[i] > 1.5 * share ? (int)ceil(nkt[i] / share) : 1;
         s = std::min(std::min(s, 16), nkt[i] / min_kt);
         const size_t slab = (size_t)a.M * a.N * sizeof(float);
         if (s > 1 && (!a.ws || a.ws_bytes / slab < (size_t)s)) s = a.ws ? (int)std::min<size_t>(a.ws_bytes / slab, (size_t)s) : 1;

@@ -28,13 +28,6 @@
 #include <cstring>
 #include <type_traits>
 
-// knock-out switches of experiment builds only (scripts/build_exp.sh NAME -DH3_EXP_NOMFMA / _NODMA / _NOFRAG): what bounds the k loop
-#ifdef H3_EXP_NOMFMA
-#define H3_MFMA(A, B, C) (C)
-#else
-#define H3_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B, C, 0, 0, 0)
-#endif
-
 typedef __attribute__((address_space(3))) void lds_void;
 
 template <int I, int N, typename F>
@@ -46,7 +39,7 @@ static __device__ __forceinline__ void h3_for(F&& f)
     }
 }
 
-// TM: 32-row MFMA tiles per wave (2: a wave owns 64 x 64; 4: 128 x 64 -- a third less LDS traffic per matrix-core product)
+// TM: 32-row MFMA tiles per wave (1: a wave owns 32 x 64; 2: 64 x 64)
 template <int WM, int WN, int WK, int KT, int NS, int NP, int TM = 2>
 struct H3Cfg {
     static constexpr int QP = NP == 1 ? 2 : 4;                           // planes staged per k-block (h only / h and l)
@@ -64,9 +57,7 @@ struct H3Cfg {
     static constexpr int NFR = (TM + 2) * (NP == 1 ? 1 : 2);             // fragment reads per k-block
 };
 
-#ifndef H3_OCC
-#define H3_OCC 1
-#endif
+static constexpr int H3_OCC = 1;                                       // workgroups per CU the register budget is fitted to
 // which problem a workgroup belongs to (wave-uniform: scalar compares on the kernel arguments)
 static __device__ __forceinline__ int h3_problem_of(const H3Multi& mm)
 {
@@ -76,8 +67,7 @@ static __device__ __forceinline__ int h3_problem_of(const H3Multi& mm)
     return pi;
 }
 
-// one workgroup's tile of problem `prob` (the whole kernel but for the problem look-up: conv_gemm_h3_kernel runs it for every
-// workgroup, conv_gemm_h3_mix_kernel runs one of two instantiations, by the problem's tile class)
+// one workgroup's tile of problem `prob` (the whole kernel but for the problem look-up)
 template <int WM, int WN, int WK, int KT, int NS, int NP, int TM = 2>
 static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char* smem)
 {
@@ -247,14 +237,14 @@ static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char
         }
     };
     auto dma_a = [&](auto i_, int stage) {
-#if __HIP_DEVICE_COMPILE__ && !defined(H3_EXP_NODMA)   // (device pass only: with this builtin in the body hipcc 7.2's HOST pass drops the kernel's launch stub)
+#if __HIP_DEVICE_COMPILE__   // (device pass only: with this builtin in the body hipcc 7.2's HOST pass drops the kernel's launch stub)
         constexpr int i = decltype(i_)::value;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_void*)(smem + stage * C::STAGE + wave * 1024 + i * (NT * 16)), 16, a_voff[i],
                                                  a_soff, 0, 0);
 #endif
     };
     auto dma_b = [&](auto i_, int stage) {
-#if __HIP_DEVICE_COMPILE__ && !defined(H3_EXP_NODMA)
+#if __HIP_DEVICE_COMPILE__
         constexpr int i = decltype(i_)::value;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsXc, (lds_void*)(smem + stage * C::STAGE + C::A_ST + wave * 1024 + i * (NT * 16)), 16, bv[i],
                                                  b_soff, 0, 0);
@@ -270,9 +260,6 @@ static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char
     const int b_frag = C::A_ST + (wk * KT * QP + lk) * BN * 16 + (wn * 64 + l31) * 16;
     // fragment read q of k-block step s of stage `stage` into register set `set`: q = ab*NFR/2 + p*2 + i
     auto read_frag = [&](auto q_, auto set_, auto s_, int stage) {
-#ifdef H3_EXP_NOFRAG
-        return;
-#endif
         constexpr int q = decltype(q_)::value, set = decltype(set_)::value, s = decltype(s_)::value;
         // in the order the MFMAs first need them: (A h, B l) for h*l, then (A l, B h) for l*h; h*h reuses them
         // reads: TM x A h, 2 x B l, TM x A l, 2 x B h  (NP = 1: TM x A h, 2 x B h)
@@ -318,34 +305,14 @@ static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char
     constexpr int SLOT0 = 0;
     auto stage_micro = [&](auto m_, auto p_) {
         constexpr int Mi = decltype(m_)::value, P = (decltype(p_)::value + L) % NS;
-#if defined(H3_EXP_BSKIP)                                   // knock-out: activations staged for the first tap only (what sharing a tile across taps could save)
-        if constexpr (Mi < ACH) dma_a(std::integral_constant<int, Mi>{}, P);
-        else if constexpr (Mi < M_ADV) { if (s_t == 0) dma_b(std::integral_constant<int, Mi - ACH>{}, P); }
-        else advance();
-#elif defined(H3_EXP_ASKIP)                                 // knock-out: weights staged every other k-block
-        if constexpr (Mi < ACH) { if ((s_kb & 1) == 0) dma_a(std::integral_constant<int, Mi>{}, P); }
-        else if constexpr (Mi < M_ADV) dma_b(std::integral_constant<int, Mi - ACH>{}, P);
-        else advance();
-#else
         if constexpr (Mi < ACH) dma_a(std::integral_constant<int, Mi>{}, P);
         else if constexpr (Mi < M_ADV) dma_b(std::integral_constant<int, Mi - ACH>{}, P);
         else advance();
-#endif
     };
-#ifndef H3_PLAN
-#define H3_PLAN 0
-#endif
-    // H3_PLAN (experiment builds): 0 = staging spread over the whole iteration, interleaved with the fragment reads; 1 = fragment
-    // reads first, staging in the second half; 2 = staging first, fragment reads in the second half
-    auto slot_of_stage = [](int m) constexpr {
-        if (KT == 1 && NP == 3 && H3_PLAN == 1) return 6 + (m * 6) / NMS;
-        if (KT == 1 && NP == 3 && H3_PLAN == 2) return (m * 6) / NMS;
-        return SLOT0 + (m * (NMI - SLOT0)) / NMS;
-    };
+    // staging spread over the whole iteration, interleaved with the fragment reads
+    auto slot_of_stage = [](int m) constexpr { return SLOT0 + (m * (NMI - SLOT0)) / NMS; };
     // slot of fragment read q of step s (reads of the NEXT step): spread over the first NMF - 2 slots of the step
     auto slot_of_frag = [](int s, int q) constexpr {
-        if (KT == 1 && NP == 3 && H3_PLAN == 1) return (q * 6) / C::NFR;
-        if (KT == 1 && NP == 3 && H3_PLAN == 2) return 5 + (q * 6) / C::NFR;
         return s * C::NMF + (q * (C::NMF - 2)) / C::NFR + (C::NMF > 4 ? 1 : 0);
     };
     // MFMA n of a step: groups of four, smallest terms first: (A part, B part) = (h,l) (l,h) (h,h); NP = 1: (h,h)
@@ -354,7 +321,7 @@ static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char
         constexpr int grp_ = Nn / (2 * TM), i = (Nn % (2 * TM)) / 2, jn = Nn % 2;
         constexpr int PA = NP == 1 ? 0 : (grp_ == 1 ? 1 : 0);
         constexpr int PB = NP == 1 ? 0 : (grp_ == 0 ? 1 : 0);
-        acc[i][jn] = H3_MFMA(fa[F][i][PA], fb[F][jn][PB], acc[i][jn]);
+        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[F][i][PA], fb[F][jn][PB], acc[i][jn], 0, 0, 0);
         constexpr int slot = Ss * C::NMF + Nn;
         h3_for<0, NMS>([&](auto m_) {
             if constexpr (slot_of_stage(decltype(m_)::value) == slot) stage_micro(m_, p_);
@@ -370,13 +337,6 @@ static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char
     // end of an iteration: the tile the NEXT iteration reads fragments from has landed (this wave's share) and everybody
     // is done with the stage the next iteration restages.  Not __syncthreads(): its fence waits for vmcnt(0).
     constexpr int PEND = (L - 2) * (ACH + BCH);                          // LDS-DMAs that may stay in flight across the barrier: tiles it + 3 .. it + L
-#if defined(H3_EXP_NOBAR)
-#define H3_END_OF_ITER asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PEND) : "memory");
-#elif defined(H3_EXP_NOVMWAIT)
-#define H3_END_OF_ITER asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-#define H3_END_OF_ITER asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(PEND) : "memory");
-#endif
 #define H3_ITER(U)                                                                                                \
     {                                                                                                             \
         h3_for<0, KT>([&](auto s_) {                                                                              \
@@ -385,7 +345,7 @@ static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char
                      std::integral_constant<int, ((U) * KT + decltype(s_)::value) % 2>{});                        \
             });                                                                                                   \
         });                                                                                                       \
-        H3_END_OF_ITER                                                                                            \
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(PEND) : "memory");                     \
     }
     // stage = it % NS, first register set = (it KT) % 2: period lcm(NS, KT odd ? 2 : 1)
     constexpr int PERIOD = (KT % 2 == 0) ? NS : (NS % 2 == 0 ? NS : 2 * NS);
@@ -438,48 +398,6 @@ conv_gemm_h3_kernel(const H3Multi mm)
     h3_tile<WM, WN, WK, KT, NS, NP, TM>(mm.p[h3_problem_of(mm)], smem);
 }
 
-// ONE conv on two tile shapes (as_conv_gemm_h3_launch_mix): the entries listed first run the 128 x 128 tile, the ones flagged `small`
-// the 128 x 64 tile (four waves as two K halves of two 64 x 64 blocks).  A workgroup runs one of the two bodies; registers and LDS are
-// the larger of the two (the small tile stages two k-blocks per stage: 72 KB, two workgroups per CU as before).
-__global__ void __launch_bounds__(256, H3_OCC)
-conv_gemm_h3_mix_kernel(const H3Multi mm)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // (two entries, constant indices: a dynamic index into the argument struct here made the compiler copy it to scratch)
-    if ((int)blockIdx.x >= mm.p[1].wg0) h3_tile<2, 1, 2, 1, 3, 3>(mm.p[1], smem);
-    else h3_tile<2, 2, 1, 1, 3, 3>(mm.p[0], smem);
-}
-
-int as_conv_gemm_h3_launch_mix(const ConvGemmArgs* a, int col_split, hipStream_t stream)
-{
-    using CB = H3Cfg<2, 2, 1, 1, 3, 3>;
-    using CS = H3Cfg<2, 1, 2, 1, 3, 3>;
-    constexpr int LDS = CB::LDS > CS::LDS ? CB::LDS : CS::LDS;
-    if (!a || a->n_prod != 3 || a->n_groups > 1 || col_split <= 0 || col_split >= a->N || col_split % CB::BN) return AS_EINVAL;
-    if ((double)as_kbx(a->K) * 4.0 * ((a->src_col ? a->N_in : a->N) + 1.0) * 16.0 >= 2147483648.0) return AS_EINVAL;
-    AS_LDS_OPT_IN((&conv_gemm_h3_mix_kernel), LDS);
-    H3Multi mm;
-    memset(&mm, 0, sizeof(mm));
-    mm.n = 2;
-    int wg = 0;
-    for (int i = 0; i < 2; ++i) {
-        H3Prob& p = mm.p[i];
-        p.a = *a;
-        if (h3_pack_taps(p.a, &p.tp) != AS_OK) return AS_EINVAL;
-        p.col0 = i == 0 ? 0 : col_split;
-        p.col1 = i == 0 ? col_split : a->N;
-        p.small = i;
-        p.tiles = as_cdiv(a->M, 128) * as_cdiv(p.col1 - p.col0, i == 0 ? CB::BN : CS::BN);
-        p.S = 1;
-        p.wg0 = wg;
-        p.wgs = (p.tiles + 7) & ~7;
-        wg += p.wgs;
-    }
-    hipLaunchKernelGGL(conv_gemm_h3_mix_kernel, dim3(wg), dim3(256), LDS, stream, mm);
-    AS_CHECK_LAUNCH();
-    return AS_OK;
-}
-
 template <int WM, int WN, int WK, int KT, int NS, int NP, int TM = 2>
 static int launch_h3(const ConvGemmArgs* const* a, const int* S, int n, hipStream_t stream)
 {
@@ -507,26 +425,11 @@ static int launch_h3(const ConvGemmArgs* const* a, const int* S, int n, hipStrea
     return AS_OK;
 }
 
-// Pipeline shape per tile (k-blocks per wave and iteration, LDS stages): AS_H3_KT / AS_H3_NS select the alternatives
-// that are compiled in (tuning runs only)
-#ifndef H3_KT
-#define H3_KT 1
-#endif
+// Pipeline shape of every 4-wave tile: one k-block per wave and iteration, three LDS stages
 template <int WM, int WN, int WK>
 static int launch_h3_tile(const ConvGemmArgs* const* a, const int* S, int n, hipStream_t stream)
 {
     if (a[0]->n_prod == 1) return launch_h3<WM, WN, WK, 1, 3, 1>(a, S, n, stream);
-#ifdef AS_EXPERIMENTS   // (-DAS_EXPERIMENTS builds only: the shipped library carries the one pipeline shape the path launches)
-    const char *ekt = getenv("AS_H3_KT"), *ens = getenv("AS_H3_NS");
-    const int kt = ekt ? atoi(ekt) : H3_KT, ns = ens ? atoi(ens) : 3;
-    if constexpr (H3Cfg<WM, WN, WK, 2, 3, 3>::LDS <= 160 * 1024) {
-        if (kt == 2) return launch_h3<WM, WN, WK, 2, 3, 3>(a, S, n, stream);
-    }
-    if (ns == 2) return launch_h3<WM, WN, WK, 1, 2, 3>(a, S, n, stream);
-    if constexpr (H3Cfg<WM, WN, WK, 1, 4, 3>::LDS <= 160 * 1024) {
-        if (ns == 4) return launch_h3<WM, WN, WK, 1, 4, 3>(a, S, n, stream);
-    }
-#endif
     return launch_h3<WM, WN, WK, 1, 3, 3>(a, S, n, stream);
 }
 
@@ -538,18 +441,9 @@ int as_conv_gemm_h3_launch(const ConvGemmArgs* const* a, const int* S, int n, in
         if ((double)as_kbx(a[i]->K) * 4.0 * ((a[i]->src_col ? a[i]->N_in : a[i]->N) + 1.0) * 16.0 >= 2147483648.0) return AS_EINVAL;   // 32-bit offsets in the descriptor
     }
     switch (choice) {
-#ifdef AS_EXPERIMENTS
-    case 42:                                                            // 256 x 128, a wave owns 128 x 64
-        if (a[0]->n_prod == 1) return AS_EINVAL;
-        return launch_h3<2, 2, 1, 1, 3, 3, 4>(a, S, n, stream);
-#endif
     case 2:                                                             // 32 x 128 (a wave owns 32 x 64): the vocoder's 32-channel stage, M <= 32
         if (a[0]->n_prod == 1) return AS_EINVAL;
-        {
-            static const bool ns3 = getenv("AS_TILE2_NS3") != nullptr;   // (tuning: the three-stage form)
-            if (!ns3) return launch_h3<1, 2, 2, 1, 2, 3, 1>(a, S, n, stream);
-        }
-        return launch_h3<1, 2, 2, 1, 3, 3, 1>(a, S, n, stream);
+        return launch_h3<1, 2, 2, 1, 2, 3, 1>(a, S, n, stream);
     case 22: return launch_h3_tile<2, 2, 1>(a, S, n, stream);
     case 21: return launch_h3_tile<2, 1, 2>(a, S, n, stream);
     case 12: return launch_h3_tile<1, 2, 2>(a, S, n, stream);

@@ -123,9 +123,6 @@ struct as_lanes {
     // hardware queues, and a copy stream per lane put lanes' copies behind other lanes' kernels (measured: + 7-10 % per step where the
     // copies on the lane's own stream cost + 4.7 %)
     hipStream_t h2d = nullptr, d2h = nullptr;
-    bool copy_on_lane = false;                                    // AS_LANES_COPY_ON_LANE=1 (measurements): a lane's copies on its own stream
-    hipStream_t up(const Lane& L) const { return copy_on_lane ? L.stream : h2d; }
-    hipStream_t down(const Lane& L) const { return copy_on_lane ? L.stream : d2h; }
 };
 
 namespace {
@@ -201,7 +198,6 @@ static int lanes_create(const as_model* m, int n_lanes, as_lanes** out)
     if (as_model_get_cfg(m, &q->cfg) != AS_OK) { delete q; return AS_EINVAL; }
     const char* dbg = getenv("AS_DEBUG");
     q->debug = dbg && *dbg && *dbg != '0';
-    q->copy_on_lane = getenv("AS_LANES_COPY_ON_LANE") != nullptr;
     q->lanes.resize(n_lanes);
     for (Lane& L : q->lanes) {
         int rc = as_plan_create(m, &L.plan);
@@ -554,7 +550,7 @@ static int flush_lane(as_lanes* q, int lane)
     const bool host_group = !outs.empty();
     const int bi = L.cur;
     if (host_group) {                                             // the group's kernels start behind its host -> device copies
-        AS_CHECK(hipEventRecord(L.ev_h2d[bi], q->up(L)));
+        AS_CHECK(hipEventRecord(L.ev_h2d[bi], q->h2d));
         AS_CHECK(hipStreamWaitEvent(L.stream, L.ev_h2d[bi], 0));
         L.cur ^= 1;                                               // (the next group of this lane fills the other block)
         L.blk_used[bi] = true;
@@ -567,15 +563,15 @@ static int flush_lane(as_lanes* q, int lane)
         // ... and every submission's mel goes home behind them, on the lane's device -> host stream: the lane's next group computes meanwhile.
         // ev_d2h[bi] is what the block's NEXT group's copies wait for (recorded whatever happened: a block is never left without it)
         hipError_t e = hipEventRecord(L.ev_comp[bi], L.stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(q->down(L), L.ev_comp[bi], 0);
+        if (e == hipSuccess) e = hipStreamWaitEvent(q->d2h, L.ev_comp[bi], 0);
         for (const Out& o : outs) {
             if (rc == AS_OK && e == hipSuccess && o.cols > 0)
                 e = hipMemcpy2DAsync(o.host, (size_t)o.ld * 4, o.dev, (size_t)o.ld_dev * 4, (size_t)o.cols * 4, (size_t)q->cfg.n_mels,
-                                     hipMemcpyDeviceToHost, q->down(L));
+                                     hipMemcpyDeviceToHost, q->d2h);
             if (rc == AS_OK && e == hipSuccess && o.foff_host)
-                e = hipMemcpyAsync(o.foff_host, o.foff_dev, (size_t)o.n_foff * 4, hipMemcpyDeviceToHost, q->down(L));
+                e = hipMemcpyAsync(o.foff_host, o.foff_dev, (size_t)o.n_foff * 4, hipMemcpyDeviceToHost, q->d2h);
         }
-        const hipError_t e2 = hipEventRecord(L.ev_d2h[bi], q->down(L));
+        const hipError_t e2 = hipEventRecord(L.ev_d2h[bi], q->d2h);
         if (rc == AS_OK && (e != hipSuccess || e2 != hipSuccess)) return (int)(e != hipSuccess ? e : e2);
     }
     return rc;
@@ -717,7 +713,7 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
         }
         if (rc != AS_OK) return rc;
         Lane::Block& b = L.blk[L.cur];
-        hipStream_t s = q->up(L);
+        hipStream_t s = q->h2d;
         // the block's previous group (two groups back on this lane) has left it -- its kernels and the copies of its results -- before
         // the first copy of this one lands
         if (L.pend.empty() && L.blk_used[L.cur]) AS_CHECK(hipStreamWaitEvent(s, L.ev_d2h[L.cur], 0));

@@ -150,10 +150,7 @@ template <int H, int KREG, int KLDS>
 __global__ void __launch_bounds__(2 * H)
 bilstm_big_kernel(const LstmJobs jobs, const int* __restrict__ col_off, int B)
 {
-    #ifndef LSTM_SB
-#define LSTM_SB 4
-#endif
-    constexpr int G = 4 * H, NT = 2 * H, KS = H - KREG - KLDS, SB = LSTM_SB;   // SB: streamed rows per batch
+    constexpr int G = 4 * H, NT = 2 * H, KS = H - KREG - KLDS, SB = 4;   // SB: streamed rows per batch
     static_assert(KS >= 0 && KS % SB == 0, "split of the k range");
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* hs = sm;                         // [2][H][NB]
@@ -456,8 +453,8 @@ extern "C" int as_bilstm_f32(const BiLstmJob* jobs_host, int n_jobs, const int32
     const size_t smem = sizeof(float) * ((size_t)2 * H * NB + (size_t)4 * H * NB);
     const dim3 grid(as_cdiv(B, NB), 2, n_jobs), block(4 * H);
     AsProfScope prof__(AS_FILE_CLS, 0, 0, (hipStream_t)stream);
-    // one utterance per workgroup while all the recurrences fit the chip together (AS_LSTM_NB=2 forces the pairs: experiments)
-    const bool single = (H == 64 || H == 128) && (long)n_jobs * 2 * B <= 512 && !getenv("AS_LSTM_NB");
+    // one utterance per workgroup while all the recurrences fit the chip together
+    const bool single = (H == 64 || H == 128) && (long)n_jobs * 2 * B <= 512;
     if (single) {
         const dim3 g1(B, 2, n_jobs);
         if (H == 64) hipLaunchKernelGGL(bilstm_quad1_kernel<64>, g1, block, 0, (hipStream_t)stream, jobs, col_off, B);
@@ -471,14 +468,10 @@ extern "C" int as_bilstm_f32(const BiLstmJob* jobs_host, int n_jobs, const int32
     case 64: hipLaunchKernelGGL(bilstm_quad_kernel<64>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
     case 128: hipLaunchKernelGGL(bilstm_quad_kernel<128>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
     case 256: {
-#ifndef LSTM_KREG
-#define LSTM_KREG 32
-#endif
-        constexpr int KREG = LSTM_KREG, KLDS = 36;                    
+        constexpr int KREG = 32, KLDS = 36;
         const size_t sm_big = smem + sizeof(float) * (size_t)KLDS * 1024;
         AS_LDS_OPT_IN((bilstm_big_kernel<256, KREG, KLDS>), (int)sm_big);   // (+ 16 bytes static: 160 KB would be refused)
-        if (getenv("AS_LSTM_STREAM")) hipLaunchKernelGGL(bilstm_kernel<0>, grid, block, smem, (hipStream_t)stream, jobs, col_off, B, H);
-        else hipLaunchKernelGGL((bilstm_big_kernel<256, KREG, KLDS>), grid, dim3(512), sm_big, (hipStream_t)stream, jobs, col_off, B);
+        hipLaunchKernelGGL((bilstm_big_kernel<256, KREG, KLDS>), grid, dim3(512), sm_big, (hipStream_t)stream, jobs, col_off, B);
         break;
     }
     default: hipLaunchKernelGGL(bilstm_kernel<0>, grid, block, smem, (hipStream_t)stream, jobs, col_off, B, H); break;

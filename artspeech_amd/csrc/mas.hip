@@ -36,16 +36,6 @@
 #define MAS_NEG (-1e32f)
 typedef unsigned long long u64;
 
-#ifdef AS_EXPERIMENTS
-__device__ unsigned long long mas_dbg[8];      // shader / wall clocks at the phase boundaries of block 0 (scripts/exp/mas_clock.py)
-#define MAS_MARK(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) { mas_dbg[2 * (i)] = clock64(); mas_dbg[2 * (i) + 1] = wall_clock64(); } } while (0)
-__device__ unsigned long long mas_dbg2[128];    // wall clock (100 MHz) per (band, wave) of utterance 0: block 0 may start / is done, last block done
-extern "C" int as_mas_debug(unsigned long long* out8) { return (int)hipMemcpyFromSymbol(out8, HIP_SYMBOL(mas_dbg), 64); }
-extern "C" int as_mas_debug2(unsigned long long* out128) { return (int)hipMemcpyFromSymbol(out128, HIP_SYMBOL(mas_dbg2), 1024); }
-#else
-#define MAS_MARK(i)
-#endif
-
 template <int R, int Q, bool VEC4, bool TIE_MOVE, int MAXT>
 __global__ void __launch_bounds__(MAXT)
 mas_kernel(const float* __restrict__ value, const int* __restrict__ t_x, const int* __restrict__ t_y,
@@ -440,16 +430,7 @@ mas_band_kernel(const float* __restrict__ value, const int* __restrict__ t_x, co
     auto lds_addr = [](const void* p) { return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p; };
     static_assert(MAS_NL == 2, "the block's poll reads the two loaders' counters");
     const unsigned a_c0 = lds_addr(&ctr[0]), a_c1 = lds_addr(&ctr[1]), a_cw = from_wave ? lds_addr(&ctr[MAS_NL + w - 1]) : a_c0;
-#ifdef AS_EXPERIMENTS
-    long long c_wait = 0, c_dp = 0, c_all = clock64();
-#define MAS_T(v) const long long v = clock64()
-#define MAS_ACC(acc, a, b_) acc += (b_) - (a)
-#else
-#define MAS_T(v)
-#define MAS_ACC(acc, a, b_)
-#endif
     for (int blk = 0; blk < nblk; ++blk) {
-        MAS_T(t0);
         const float* slot = ring + (blk % MAS_RING) * MAS_SLOT_F(W);
         const float4* rowp = reinterpret_cast<const float4*>(slot + (x_local >> 3) * MAS_CHUNK_F + (x_local & 7) * 32);
         const float4* inp = reinterpret_cast<const float4*>(from_wave ? &outrow[w - 1][blk % MAS_OUT_RING][0] : (from_band ? &uprow[blk & 1][0] : &negrow[0]));
@@ -466,11 +447,6 @@ mas_band_kernel(const float* __restrict__ value, const int* __restrict__ t_x, co
             if (__builtin_amdgcn_readfirstlane(c0) > blk && __builtin_amdgcn_readfirstlane(c1) > blk && __builtin_amdgcn_readfirstlane(c2) > blk) break;
             __builtin_amdgcn_s_sleep(1);
         }
-        MAS_T(t1);
-        MAS_ACC(c_wait, t0, t1);
-#ifdef AS_EXPERIMENTS
-        if (b == 0 && lane == 0 && blk == 0) mas_dbg2[(p * W + w) * 4 + 0] = wall_clock64();
-#endif
         float* lastp = lane == 63 ? &outrow[w][blk % MAS_OUT_RING][0] : &scratch[w][lane * 33];
         unsigned bits = 0u;
         const int ncol = (y_len - blk * MAS_BLK) < MAS_BLK ? (y_len - blk * MAS_BLK) : MAS_BLK;
@@ -483,12 +459,6 @@ mas_band_kernel(const float* __restrict__ value, const int* __restrict__ t_x, co
             const int have = blk == 0 ? ncol - 1 : ncol;   // decisions shifted in (column 0 has none)
             bits = have > 0 ? bits << (MAS_BLK - ncol) : 0u;
         }
-        MAS_T(t3);
-        MAS_ACC(c_dp, t1, t3);
-#ifdef AS_EXPERIMENTS
-        if (b == 0 && lane == 0 && blk == 0) mas_dbg2[(p * W + w) * 4 + 1] = wall_clock64();
-        if (b == 0 && lane == 0 && blk == nblk - 1) mas_dbg2[(p * W + w) * 4 + 2] = wall_clock64();
-#endif
         mo[((size_t)blk * W + w) * 64 + lane] = bits;
         if (to_band && lane < ncol)
             __hip_atomic_store(xo + blk * MAS_BLK + lane, ((u64)1u << 32) | __float_as_uint(outrow[w][blk % MAS_OUT_RING][lane]), __ATOMIC_RELAXED,
@@ -509,11 +479,6 @@ mas_band_kernel(const float* __restrict__ value, const int* __restrict__ t_x, co
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         if (w == 0) mas_backtrack_wave<W>(b, lane, x_len, y_len, Tx, Ty, P, nblk_max, masks, path, dur, rows);
     }
-#ifdef AS_EXPERIMENTS
-    if (b == 0 && p == 0 && tid == 0) {                      // the first wave of the first band of utterance 0
-        mas_dbg[0] = c_wait; mas_dbg[1] = 0; mas_dbg[2] = c_dp; mas_dbg[3] = clock64() - c_all;
-    }
-#endif
 #endif
 }
 
@@ -786,7 +751,7 @@ static MasBands mas_bands(int B, int Tx, int Ty)
     g.nblk = as_cdiv(Ty, MAS_BLK);
     g.xchg_bytes = g.P > 1 ? (((size_t)B * g.P * g.nblk * MAS_BLK * sizeof(u64) + 255) & ~(size_t)255) : 0;
     g.mask_bytes = (((size_t)B * g.P * g.nblk * g.R * 64 * sizeof(unsigned)) + 255) & ~(size_t)255;
-    g.fused = g.P == 1 && (long)Tx * Ty <= MAS_FUSED_CELLS && !getenv("AS_MAS_NO_FUSE");
+    g.fused = g.P == 1 && (long)Tx * Ty <= MAS_FUSED_CELLS;
     g.exs = (Tx + 15) & ~15;
     g.ex_bytes = g.fused ? 0 : (((size_t)B * g.nblk * g.exs) + 255) & ~(size_t)255;       // exit table: a byte per (block, row)
     g.entry_bytes = g.fused ? 0 : (((size_t)B * g.nblk * sizeof(int)) + 255) & ~(size_t)255;

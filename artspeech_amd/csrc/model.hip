@@ -727,50 +727,12 @@ struct Ctx {
     }
 };
 
-#ifdef AS_EXPERIMENTS
-// timing experiments only (results are wrong): AS_EXP_SKIP="avgpool,dwconv" drops the RUN launches whose call text holds one of the words
-static bool exp_skip(const char* call)
-{
-    static const char* e = getenv("AS_EXP_SKIP");
-    if (!e || !*e) return false;
-    std::string words(e);
-    size_t a = 0;
-    while (a <= words.size()) {
-        size_t b = words.find(',', a);
-        if (b == std::string::npos) b = words.size();
-        if (b > a && strstr(call, words.substr(a, b - a).c_str())) return true;
-        a = b + 1;
-    }
-    return false;
-}
-// AS_EXP_DUP="adain": those launches run TWICE (same arguments: results unchanged) -- what a class costs the step at the margin, without
-// the knock-out's side effect on the data the later kernels see
-static bool exp_dup(const char* call)
-{
-    static const char* e = getenv("AS_EXP_DUP");
-    if (!e || !*e) return false;
-    std::string words(e);
-    size_t a = 0;
-    while (a <= words.size()) {
-        size_t b = words.find(',', a);
-        if (b == std::string::npos) b = words.size();
-        if (b > a && strstr(call, words.substr(a, b - a).c_str())) return true;
-        a = b + 1;
-    }
-    return false;
-}
-#define EXP_SKIP(call) exp_skip(#call)
-#define EXP_DUP(call) exp_dup(#call)
-#else
-#define EXP_SKIP(call) false
-#define EXP_DUP(call) false
-#endif
 // (a recorded launch that play() moves to the plan's side stream: Op.side)
 static thread_local hipStream_t tl_stream_override = nullptr;
 // (recorded form: the closure copies what the call names -- argument structs and job arrays included -- and sees the stream as `c.s`)
 #define RUN(c, call)                                   \
     do {                                               \
-        if ((c).go() && !EXP_SKIP(call)) {             \
+        if ((c).go()) {                                \
             if ((c).deferring()) {                     \
                 const hipStream_t s__ = (c).s;         \
                 Op& o__ = (c).push(0);                 \
@@ -778,13 +740,10 @@ static thread_local hipStream_t tl_stream_override = nullptr;
                 o__.fn = [=]() -> int {                \
                     struct { hipStream_t s; } c = {tl_stream_override ? tl_stream_override : s__}; \
                     (void)c;                           \
-                    int r__ = (call);                  \
-                    if (r__ == AS_OK && EXP_DUP(call)) r__ = (call); \
-                    return r__;                        \
+                    return (call);                     \
                 };                                     \
             } else {                                   \
-                int r__ = (call);                      \
-                if (r__ == AS_OK && EXP_DUP(call)) r__ = (call); \
+                const int r__ = (call);                \
                 if (r__ != AS_OK) (c).fail(r__, #call, __LINE__); \
             }                                          \
         }                                              \
@@ -825,7 +784,6 @@ static void play(Ctx& c, Sched& S)
         return any;
     };
     auto fail = [&](int r, const Op& o) { c.fail(r, o.what, o.line); };
-    static const bool no_merge = getenv("AS_NO_MERGE") != nullptr;    // experiments: the recorded order, one launch per conv
     static const bool trace = getenv("AS_DEBUG_SCHED") != nullptr;     // print what goes out, in order
     if (trace) {
         fprintf(stderr, "artspeech_hip: playing %d recorded queues:", nq);
@@ -895,12 +853,7 @@ static void play(Ctx& c, Sched& S)
                     fprintf(stderr, "\n");
                 }
                 const Op& o0 = S.q[dq[0]][head[dq[0]]];
-                const int r = no_merge ? AS_OK : as_down_multi_f32(dl, nd, o0.s);
-                if (no_merge)
-                    for (int i = 0; i < nd && !c.rc; ++i) {
-                        const int r1 = as_down_multi_f32(&dl[i], 1, o0.s);
-                        if (r1 != AS_OK) fail(r1, o0);
-                    }
+                const int r = as_down_multi_f32(dl, nd, o0.s);
                 if (r != AS_OK) { fail(r, o0); return; }
                 if (c.rc) return;
                 for (int i = 0; i < nd; ++i) ++head[dq[i]];
@@ -937,8 +890,8 @@ static void play(Ctx& c, Sched& S)
         // moves on to heads that can.  Otherwise the set = the mergeable heads of the row class that holds the most work.
         int pick[AS_MAX_MULTI], np = 0, lone = -1;
         for (int i = 0; i < nh && lone < 0; ++i)
-            if (no_merge || !gemm_mergeable(S.q[heads[i]][head[heads[i]]].g)) lone = heads[i];
-        if (lone >= 0 && !no_merge && gemm_direct(S.q[lone][head[lone]].g)) {        // the towers' Cin = 1 stems that are ready together: one direct launch
+            if (!gemm_mergeable(S.q[heads[i]][head[heads[i]]].g)) lone = heads[i];
+        if (lone >= 0 && gemm_direct(S.q[lone][head[lone]].g)) {        // the towers' Cin = 1 stems that are ready together: one direct launch
             for (int i = 0; i < nh && np < AS_MAX_MULTI; ++i)
                 if (gemm_direct(S.q[heads[i]][head[heads[i]]].g)) pick[np++] = heads[i];
             if (np < 2) np = 0;
@@ -1207,7 +1160,7 @@ void conv_impl(Ctx& c, const GemmW* w, const float* X, int ldx, const uint16_t* 
         post_mw = o.post_lay->max_w;                                      // (a capacity layout: no utterance is wider than the room)
     }
     if (o.ln.yh && (o.post_yh || !Y)) { c.fail(AS_EINVAL); return; }
-    if (c.deferring() && !EXP_SKIP(as_conv_gemm_f32)) {                  // recorded: it may share its launch with other branches' convs
+    if (c.deferring()) {                  // recorded: it may share its launch with other branches' convs
         Op& op = c.push(1);
         op.g = a;
         op.post = post;
@@ -1908,9 +1861,8 @@ float* duration_tail(Ctx& c, float* d, const float* ds, const Lay* tok, float* d
         RUN(c, as_bilstm_cluster_f32(&job, 1, tok->d_off, tok->B, H, tok->max_w, xchg, xb, c.s));
         // hundreds of tokens: milliseconds on a few dozen workgroups (C5: 1.8 ms on 16) while the text / articulatory encoders' last two
         // layers -- which do not depend on it (models.py:356-360) -- have the chip's worth of GEMMs to run: a recording plan puts the
-        // launch on its side stream (one fork / join pair of event edges: worth it only for a long launch)
-        static const int side_min = getenv("AS_SIDE_LSTM_MIN") ? atoi(getenv("AS_SIDE_LSTM_MIN")) : 200;
-        if (c.deferring() && c.go() && tok->max_w >= side_min && !c.sched->q[c.cur_q].empty()) c.sched->q[c.cur_q].back().side = true;
+        // launch on its side stream (one fork / join pair of event edges: worth it only for a long launch, >= 200 tokens)
+        if (c.deferring() && c.go() && tok->max_w >= 200 && !c.sched->q[c.cur_q].empty()) c.sched->q[c.cur_q].back().side = true;
     }
     float* y = c.f32(Nn);
     if (dst) y = dst;
@@ -2235,77 +2187,54 @@ PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
     // The articulatory + text encoders (twins: one double-width encoder), the mel tower, the duration predictor and the three
     // small towers are mutually independent (models.py:358-360) and individually too small to fill 256 CUs: four concurrent
     // branches (measured in round 1: 3 branches 9.35 ms, these 4 8.89 ms, 5 branches 9.76 ms per step).
-    // (AS_ONLY_BRANCH=k: timing experiments -- only branch k is launched, the others are allocated but skipped; results invalid)
-    const char* only_env = getenv("AS_ONLY_BRANCH");
-    const int only = only_env ? atoi(only_env) : -1;
-    const bool launch0 = c.launch;
-    auto gate = [&](int k) { c.launch = launch0 && (only < 0 || only == k); };
     // Side streams: the mel tower; the small towers; the duration predictor's dur_block.  The calling stream runs the three encoders as one
     // triple-width encoder; when the duration predictor's (2 layers) is finished the third side stream waits for it and runs the
     // predictor's tail while the text / articulatory pair runs its last two layers.  (Every edge is calling stream <-> side stream:
-    // side-to-side edges break hipGraph instantiation.)
-    const bool early = getenv("AS_DUR_EARLY") != nullptr;               // experiment: dur_block from the start on its own stream (slower in a graph)
+    // side-to-side edges break hipGraph instantiation.)  (dur_block from the start on a stream of its own was slower in a graph.)
     // Serial plans that merge (as_plan_set_serial + as_plan_set_merge, the default of a serial plan): the branches are RECORDED (Fork, Op)
     // and played out on the one stream with their ready conv GEMMs sharing launches -- queues cost nothing, so every tower is its own
     // branch and dur_block starts with the others; the predictor's tail joins its queue once the duration encoder is done.  The order of
     // the calls (hence of the workspace allocations) depends on the PLAN's flags only, never on the pass (count / prepare / run).
     const bool rec = c.p.serial && c.p.merge;
-    Fork f(c, rec ? 5 : (early ? 3 : 2), 0);
+    Fork f(c, rec ? 5 : 2, 0);
     f.branch(0);
-    gate(1);
     style_tower(c, 0, si, A.style);
     f.branch(1);
-    gate(3);
     if (rec) {
         style_tower(c, 1, si, A.style);
         f.branch(2);
         style_tower(c, 2, si, A.style);
         f.branch(3);
-        gate(2);
         duration_style(c, A.feat12 ? A.feat12 + (size_t)2 * A.ref->N : nullptr, A.ref->N, A.ref, ds);
         // every AdaIN fc layer of the predictors and the decoder (75 MB of weights streamed for 32 columns: bandwidth-bound) needs the
         // Style vector only -- here it rides along with the encoders' compute-bound convs instead of opening the second half alone
         f.after(4, {0, 1, 2});
         f.branch(4);
-        gate(3);
         A.fc = adain_fc_all(c, "style", style_norms(m), A.style, sd2, sd2, B);
         A.has_fc = true;
     } else {
         for (int t = 1; t <= 3; ++t) style_tower(c, t, si, A.style);
-        if (early) {
-            f.branch(2);
-            gate(2);
-            duration_style(c, A.feat12 ? A.feat12 + (size_t)2 * A.ref->N : nullptr, A.ref->N, A.ref, ds);
-        }
     }
     f.back();
-    gate(0);
     EncOut eo;
     std::unique_ptr<Fork> f2;
     rel_encoder_multi(c, path_encoders(), io->tokens, A.tok, &eo, [&](int g) {
         if (g != ENC_DUR) return;
-        const bool l0 = c.launch;
         if (rec) {
             f.wait_main(3);                                              // the duration encoder's result
             f.branch(3);
-        } else if (early) {
-            f.wait_main(2);
-            f.branch(2);
         } else {
             f2.reset(new Fork(c, 1, 2));
             f2->branch(0);
+            duration_style(c, A.feat12 ? A.feat12 + (size_t)2 * A.ref->N : nullptr, A.ref->N, A.ref, ds);
         }
-        gate(2);
-        if (!early && !rec) duration_style(c, A.feat12 ? A.feat12 + (size_t)2 * A.ref->N : nullptr, A.ref->N, A.ref, ds);
         A.duration = duration_tail(c, eo.y[ENC_DUR], ds, A.tok, io->duration);
         f.back();
-        c.launch = l0;
     });
     A.a_en = eo.y[ENC_ARTS];
     A.t_en = eo.y[ENC_TEXT];
     A.ld_en = eo.ld[ENC_ARTS];
     if (f2) f2->join();
-    c.launch = launch0;
     f.join();
     if (c.go()) c.p.mark(2, c.s);
     // round half even -> clamp(min = 1) (or the forced durations), per-utterance frame offsets (models.py:361-366)

@@ -21,7 +21,7 @@
 // the order of the fp32 partial sums inside a tap differs, so results agree to fp32 rounding, not bit for bit.
 //
 // Measured (scripts/exp/respair_bench.py, 32 x 200 frames): the conv phases run at ~80 % of what the matrix cores sustain on this
-// arithmetic (-DRP_EXP_TIMING: 88 granules of 8 waves in 112 k cycles at C = 64, k = 11); what is left is that a workgroup's fill and
+// arithmetic (cycle counters per phase, since removed: 88 granules of 8 waves in 112 k cycles at C = 64, k = 11); what is left is that a workgroup's fill and
 // epilogue (HBM) and its convs (MFMA) follow each other, and two to four workgroups per CU overlap them only in part: k = 3 steps run
 // at 2.0-2.6 TB/s of x-in + y-out (the residual is read a second time, the halo columns twice), k = 11 ones at 260-320 TFLOP/s.
 // Tried, same times within 3 %: three weight buffers with the DMA two granules ahead and a vmcnt(1) wait before the barrier, fragments
@@ -37,25 +37,7 @@
 
 typedef __attribute__((address_space(3))) void rp_lds_void;
 
-// knock-out switch of experiment builds only (scripts/build_exp.sh NAME -DRP_EXP_NOMFMA): what bounds a step
-#ifdef RP_EXP_NOMFMA
-#define RP_MFMA(A, B, C) (C)
-#else
 #define RP_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B, C, 0, 0, 0)
-#endif
-
-#ifdef RP_EXP_TIMING
-__device__ unsigned long long rp_times[8];     // sum over workgroups (wave 0): fill, conv1, mid, conv2, epilogue, total; [6] = workgroups
-extern "C" int as_respair_debug_times(unsigned long long* out, int reset)
-{
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(rp_times), sizeof(rp_times)) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(rp_times), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#define RP_T(i) const unsigned long long tm##i = __builtin_readcyclecounter();
-#else
-#define RP_T(i)
-#endif
 
 namespace {
 constexpr int RP_ML = 8;         // conv1's lead over the first output column ((k-1)/2 <= 8)
@@ -84,7 +66,6 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
     const int n_lo = a.col_off[b], n_hi = a.col_off[b + 1];
     const int t0 = n_lo + logical_of((int)blockIdx.x, (int)gridDim.x) * RP_OW;
     if (t0 >= n_hi) return;
-    RP_T(0)
     const int half = a.k >> 1, h1 = a.dil * half;
     const int XW = RP_MW + 2 * h1;                                       // columns of the x tile
     const int X0 = t0 - RP_ML - h1;                                      // its first column
@@ -172,7 +153,6 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
         }
     }
     __syncthreads();
-    RP_T(1)
 
     f32x16 acc[MB][2];
     auto zero = [&]() {
@@ -254,7 +234,6 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
     conv(rsW1, 0, tile, XW, wave * 64 + l31 + h1, a.dil);
     __syncthreads();                                                     // every wave is past its last read of the x tile
 
-    RP_T(2)
     // 3. conv1's result as conv2's operand, over the x tile (every wave is past its last read of it)
     {
         const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.b1), 0, a.b1 ? C * 4 : 0, 0x00020000);
@@ -302,12 +281,10 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
         }
     }
     __syncthreads();
-    RP_T(3)
 
     // 4. conv2: output column o of the workgroup reads conv1 tile column o + 8 + shift
     zero();
     conv(rsW2, G, tile, RP_MWP, wave * 64 + l31 + RP_ML, 1);
-    RP_T(4)
     {
         const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.b2), 0, a.b2 ? C * 4 : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y ? (int)((unsigned)C * a.ldy * 4u) : 0, 0x00020000);
@@ -398,14 +375,6 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
             }
         }
     }
-#ifdef RP_EXP_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RP_T(5)
-    if (tid == 0) {
-        atomicAdd(&rp_times[0], tm1 - tm0); atomicAdd(&rp_times[1], tm2 - tm1); atomicAdd(&rp_times[2], tm3 - tm2);
-        atomicAdd(&rp_times[3], tm4 - tm3); atomicAdd(&rp_times[4], tm5 - tm4); atomicAdd(&rp_times[5], tm5 - tm0); atomicAdd(&rp_times[6], 1ull);
-    }
-#endif
 }
 
 template <int C>

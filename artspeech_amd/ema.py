@@ -6,7 +6,7 @@ d_model 256, 4 heads, FFN x4, conv kernel 31, half-step residuals): ``EMA_Predic
 
   encoder1       Linear 82->256 (+BatchNorm folded in) + ReLU                                       conv GEMM
   3 x block      LayerNorm -> Linear 256->1024 (Swish epilogue) -> Linear 1024->256 (x0.5 folded in, residual)    x2
-                 LayerNorm -> fused q/k/v GEMM, pos_proj(PE) GEMM -> as_xl_attention_f32 -> out_proj (residual)
+                 LayerNorm -> fused q/k/v GEMM, pos_proj(PE) GEMM -> as_xl_attention_image_f32 -> out_proj (residual)
                  LayerNorm -> pointwise 256->512 -> GLU + depthwise k31 + BatchNorm + Swish (one kernel) -> pointwise (residual)
                  LayerNorm
   decoder2       nn.LSTM without batch_first fed [1, T, 256]: ONE step per frame from the zero state = GEMM + gate kernel
@@ -16,7 +16,6 @@ larger batch (SURVEY.md N1 "batch-axis LSTM quirk"); here a batch is a stack of 
 reference is built but never called by forward.
 """
 import math
-import os
 
 import numpy as np
 import torch
@@ -151,9 +150,7 @@ class EMA_Predictor:
             a = f"{q}.1.module"
             at = a + ".attention"
             blk["att"] = dict(ln=(vec(a + ".layer_norm.weight"), vec(a + ".layer_norm.bias")),
-                              wqkv=gemm(torch.cat([w[f"{at}.{n}_proj.linear.weight"] for n in ("query", "key", "value")], 0)),
-                              bqkv=torch.cat([w[f"{at}.{n}_proj.linear.bias"] for n in ("query", "key", "value")], 0).to(dev),
-                              wpos=gemm(w[at + ".pos_proj.linear.weight"]), u=vec(at + ".u_bias"), v=vec(at + ".v_bias"),
+                              wpos=gemm(w[at + ".pos_proj.linear.weight"]),
                               # matrix-core attention (ops.xl_attention_image): the query rows twice, u_bias / v_bias folded into the bias
                               wqkv4=gemm(torch.cat([w[f"{at}.{n}_proj.linear.weight"] for n in ("query", "query", "key", "value")], 0)),
                               bqkv4=torch.cat([w[f"{at}.query_proj.linear.bias"] + w[at + ".u_bias"].reshape(-1),
@@ -218,8 +215,6 @@ class EMA_Predictor:
         x = mm(W["enc1"][0], x82, bias=W["enc1"][1], act=ACT_RELU)                    # :75
         pos_in = self._pos_inputs(lay)
         inv_scale = 1.0 / math.sqrt(D_MODEL)                                          # attention.py:57: sqrt(d_model), not d_head
-        if os.environ.get("AS_XL_ATTENTION", "image") != "image":
-            return self._forward_exact(x, pos_in, inv_scale, lay)
         # Activations travel between the GEMMs as operand images wherever their only reader is a GEMM: LayerNorm writes the image of the
         # GEMM that follows it, the FFN's first GEMM (Swish) that of the second, the attention that of its out-projection -- 5 split
         # passes per batch instead of 31.  pos = pos_proj(PE[frame index]) does not depend on the input: its image is made once per
@@ -263,31 +258,6 @@ class EMA_Predictor:
             ops._settle(self.device)
             self._pos_cache[key] = ph
         return ph
-
-    def _forward_exact(self, x, pos_in, inv_scale, lay):
-        """the blocks with the exact fp32 attention kernel (AS_XL_ATTENTION=exact): fp32 activations between all launches"""
-        W, N = self.W, lay.N
-        one = [(0, 0)]
-        mm = lambda wt, v, **kw: ops.conv_gemm(wt, v, lay, lay.new(wt.shape[2]), one, **kw)
-        ln = lambda g, v: ops.channel_layernorm(v, N, g[0], g[1], lay.new(v.shape[0]), eps=1e-5)
-        for blk in W["blocks"]:
-            f = blk["ff1"]
-            x = mm(f["w2"], mm(f["w1"], ln(f["ln"], x), bias=f["b1"], act=ACT_SWISH), bias=f["b2"], res=x)
-            a = blk["att"]
-            qkv = mm(a["wqkv"], ln(a["ln"], x), bias=a["bqkv"])
-            pos = mm(a["wpos"], pos_in)
-            ctx = ops.xl_attention(qkv, D_MODEL, HEADS, pos, a["u"], a["v"], inv_scale, lay, lay.new(D_MODEL))
-            x = mm(a["wo"], ctx, bias=a["bo"], res=x)
-            c = blk["conv"]
-            g = ops.glu_dwconv_bn_swish(mm(c["w1"], ln(c["ln"], x), bias=c["b1"]), D_MODEL, c["dw"], c["bn"][0], c["bn"][1], lay,
-                                        lay.new(D_MODEL))
-            x = mm(c["w2"], g, bias=c["b2"], res=x)
-            f = blk["ff2"]
-            x = mm(f["w2"], mm(f["w1"], ln(f["ln"], x), bias=f["b1"], act=ACT_SWISH), bias=f["b2"], res=x)
-            x = ln(blk["ln"], x)
-        h = ops.lstm_step0(mm(W["lstm"][0], x, bias=W["lstm"][1]), D_MODEL, N, lay.new(2 * D_MODEL))   # :79
-        d = mm(W["d3a"][0], h, bias=W["d3a"][1], act=ACT_RELU)                        # :46-51
-        return mm(W["d3b"][0], d, bias=W["d3b"][1])                                   # :53, :80
 
     @torch.no_grad()
     def forward(self, F0, energy, mels=None, lengths=None):

@@ -10,7 +10,6 @@ Everything dense runs through the conv GEMM of the acoustic path (``ops.conv_gem
                          x[q-1], x[q], x[q+1] with a per-phase weight (zero where a phase does not use the tap)
 Activations stay in the packed-frames layout, so a ragged batch costs nothing and every utterance equals its B = 1 result.
 """
-import os
 
 import numpy as np
 import torch
@@ -154,7 +153,7 @@ class Generator:
             lay_up = lay.scaled(u)
             # ConvTranspose1d as one 3-tap conv with (phase, channel) rows: its epilogue stores the rows in time order (ileave) -- the
             # interleave_phases pass over the stage's input is gone -- when the channels are a multiple of 32
-            il = cout % 32 == 0 and os.environ.get("AS_VOC_ILEAVE", "1") != "0"
+            il = cout % 32 == 0
             out = lay_up.new(cout) if il else lay.new(u * cout)
             kw = dict(bias=W[f"ups{i}b"], ileave=u) if il else {}
             if xi is not None:
@@ -163,14 +162,11 @@ class Generator:
             else:
                 z = ops.conv_gemm(wt, x, lay, out, taps_1d(3), in_act=ACT_LRELU, in_slope=LRELU_SLOPE, **kw)
             # 32 / 64 channels: the residual steps are fused launches (below); they address a tensor with 32-bit byte offsets: a batch
-            # beyond 2 GiB per tensor takes the conv GEMM launches.  (They can read the conv's phase-major output in place -- the interleave
-            # as an address computation of their six reads, AS_VOC_FOLD=1 --: measured 14.30 ms per batch against 14.08 with the interleave
-            # kernel: the six strided reads cost more than the 0.28 ms the two passes take.)
-            fused = cout in (32, 64) and nk == 3 and os.environ.get("AS_VOC_FUSED", "1") != "0" and 4 * u * cout * (lay.N + 1) < 2 ** 31
-            if il:
-                x = z
-            else:
-                x = (z, b, u) if fused and os.environ.get("AS_VOC_FOLD", "0") == "1" else ops.interleave_phases(z, b, cout, u, lay.N, lay_up.new(cout))
+            # beyond 2 GiB per tensor takes the conv GEMM launches.  (Reading the conv's phase-major output in place -- the interleave as an
+            # address computation of their six reads, ops.respair's (Z, bias, u) form -- was measured: 14.30 ms per batch against 14.08 with
+            # the interleave kernel: the six strided reads cost more than the 0.28 ms the two passes take.)
+            fused = cout in (32, 64) and nk == 3 and 4 * u * cout * (lay.N + 1) < 2 ** 31
+            x = z if il else ops.interleave_phases(z, b, cout, u, lay.N, lay_up.new(cout))
             lay = lay_up
             outs = []
             # LeakyReLU(x) as an operand image, once for the three residual stacks that start from x; inside a stack every conv hands its
@@ -209,12 +205,12 @@ class Generator:
                 outs.append(y)
             if nk != 3:
                 raise NotImplementedError("three residual stacks per stage (Vocoder/config.json)")
-            if i + 1 < nst and os.environ.get("AS_VOC_FUSED", "1") != "0":
+            if i + 1 < nst:
                 x, xi = None, ops.mean3_image(outs[0], outs[1], outs[2], lay.N, LRELU_SLOPE)
             else:
                 x = ops.mean3(outs[0], outs[1], outs[2], lay.N, lay.new(cout))
         wt, b = W["post"]
-        if W["post32"] is not None and os.environ.get("AS_VOC_FUSED", "1") != "0":
+        if W["post32"] is not None:
             wav = ops.conv_post(x, lay, W["post32"], b, 0.01)
         else:
             wav = ops.conv_gemm(wt, x, lay, lay.new(1), taps_1d(7), bias=b, in_act=ACT_LRELU, in_slope=0.01, act=ACT_TANH)

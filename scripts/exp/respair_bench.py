@@ -34,16 +34,3 @@ for C, k, d in [tuple(int(v) for v in c.split(",")) for c in os.environ.get("CAS
     us = e0.elapsed_time(e1) / (5 * REP) * 1e3
     fl = 2 * 2.0 * C * C * k * lay.N
     print(f"C{C} k{k} d{d} N{lay.N}: {us:7.1f} us  {8.0 * C * lay.N / us / 1e6:5.2f} TB/s (x in, y out)  {fl / us / 1e6:6.1f} TFLOP/s")
-    try:
-        import ctypes
-        from artspeech_amd import _lib
-        L = ctypes.CDLL(os.environ["AS_LIB_PATH"]) if os.environ.get("AS_LIB_PATH") else None
-        if L is not None and hasattr(L, "as_respair_debug_times"):
-            buf = (ctypes.c_ulonglong * 8)()
-            L.as_respair_debug_times(buf, 1)
-            ops.respair(X, lay, w1, b, w2, b, k, d, 0.1, Y=Y); torch.cuda.synchronize()
-            L.as_respair_debug_times(buf, 1)
-            n = max(buf[6], 1)
-            print("   per workgroup (cycles of wave 0): fill %d conv1 %d mid %d conv2 %d epilogue %d total %d  (%d workgroups)" % tuple([buf[i] // n for i in range(6)] + [buf[6]]))
-    except Exception as e:
-        print("timing:", e)

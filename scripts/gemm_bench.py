@@ -1,5 +1,5 @@
-"""Micro-benchmark of the conv GEMM on the path's shapes (tuning aid).  AS_LIB_PATH selects an experiment build.
-usage: gemm_bench.py [M,N,K,T,L ...]   env: PIPES=13,12,23 (KT NS)  TILES=,22,21,12,11  KSPLITS=,1,2,4  SPLIT=0,1
+"""Micro-benchmark of the conv GEMM on the path's shapes (tuning aid).  AS_LIB_PATH selects another build of the library.
+usage: gemm_bench.py [M,N,K,T,L ...]   env: TILES=,22,21,12,11,14  KSPLITS=,1,2,4  SPLIT=0,1
 Every configuration is captured into a hipGraph of REP launches and replayed, so the time is the device's, not the host's.
 SPLIT=1 includes the standalone split of the fp32 activations (what a call without an operand image costs)."""
 import os, sys
@@ -17,7 +17,6 @@ SHAPES = [  # M, N(total cols), K, taps, per-utt length (1-D)
 args = [a for a in sys.argv[1:]]
 if args:
     SHAPES = [tuple(int(v) for v in s.split(",")) for s in args]
-PIPES = os.environ.get("PIPES", "13").split(",")
 TILES = os.environ.get("TILES", "").split(",")
 KSPLITS = os.environ.get("KSPLITS", "").split(",")
 SPLITS = os.environ.get("SPLIT", "0").split(",")
@@ -35,37 +34,35 @@ for (M, N, K, T, L) in SHAPES:
     taps = ops.taps_1d(T)
     xs = ops.split_act(X, lay)
     ref = None
-    for pipe in PIPES:
-        os.environ["AS_H3_KT"], os.environ["AS_H3_NS"] = pipe[0], pipe[1]
-        for tile in TILES:
-            for ks in KSPLITS:
-                for sp in SPLITS:
-                    os.environ.pop("AS_GEMM_TILE", None); os.environ.pop("AS_GEMM_KSPLIT", None)
-                    if tile: os.environ["AS_GEMM_TILE"] = tile
-                    if ks: os.environ["AS_GEMM_KSPLIT"] = ks
-                    Y = lay.new(M)
-                    call = (lambda: ops.conv_gemm(wt, X, lay, Y, taps, bias=b)) if sp == "1" else \
-                           (lambda: ops.conv_gemm(wt, None, lay, Y, taps, bias=b, xs=xs, K=K))
+    for tile in TILES:
+        for ks in KSPLITS:
+            for sp in SPLITS:
+                os.environ.pop("AS_GEMM_TILE", None); os.environ.pop("AS_GEMM_KSPLIT", None)
+                if tile: os.environ["AS_GEMM_TILE"] = tile
+                if ks: os.environ["AS_GEMM_KSPLIT"] = ks
+                Y = lay.new(M)
+                call = (lambda: ops.conv_gemm(wt, X, lay, Y, taps, bias=b)) if sp == "1" else \
+                       (lambda: ops.conv_gemm(wt, None, lay, Y, taps, bias=b, xs=xs, K=K))
+                call()
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                s = torch.cuda.Stream()
+                with torch.cuda.stream(s):
                     call()
                     torch.cuda.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    s = torch.cuda.Stream()
-                    with torch.cuda.stream(s):
-                        call()
-                        torch.cuda.synchronize()
-                        with torch.cuda.graph(graph, stream=s):
-                            for _ in range(REP):
-                                call()
+                    with torch.cuda.graph(graph, stream=s):
+                        for _ in range(REP):
+                            call()
+                graph.replay()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(5):
                     graph.replay()
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(5):
-                        graph.replay()
-                    e1.record(); torch.cuda.synchronize()
-                    ms = e0.elapsed_time(e1) / (5 * REP)
-                    if ref is None:
-                        ref = Y.clone()
-                    d = float((Y - ref).abs().max())
-                    print(f"M{M} N{lay.N} K{K} T{T} kt{pipe[0]}ns{pipe[1]} tile={tile or 'auto':4s} S={ks or 'auto':4s} split={sp}: {ms*1e3:8.1f} us  "
-                          f"{2.0*M*lay.N*K*T/ms/1e9:6.1f} TF/s  maxdiff {d:.1e}", flush=True)
+                e1.record(); torch.cuda.synchronize()
+                ms = e0.elapsed_time(e1) / (5 * REP)
+                if ref is None:
+                    ref = Y.clone()
+                d = float((Y - ref).abs().max())
+                print(f"M{M} N{lay.N} K{K} T{T} tile={tile or 'auto':4s} S={ks or 'auto':4s} split={sp}: {ms*1e3:8.1f} us  "
+                      f"{2.0*M*lay.N*K*T/ms/1e9:6.1f} TF/s  maxdiff {d:.1e}", flush=True)
