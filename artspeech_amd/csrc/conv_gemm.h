@@ -14,6 +14,9 @@ int as_conv_gemm_h3_launch(const ConvGemmArgs* const* a, const int* S, int n, in
 int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, float slope, uint16_t* xh, hipStream_t stream);
 
 static inline __host__ __device__ int as_kbx(int K) { return (((K + 15) >> 4) + 3) & ~3; }      // k-blocks of a split image: a multiple of 4
+// host: M output channels fill a 128-row tile well enough to use one (it is not half empty) -- the tile rules of conv_gemm.hip, and the
+// row classes by which the recorded schedule (model.hip: play) picks the convs that share a launch
+static inline bool as_fills_tall_tile(int M) { return M > 64 && (M % 128 == 0 || M % 128 > 64 || M >= 512); }
 
 // tap offsets packed one byte per tap, (dh+8) << 4 | (dw+8) (|dh|, |dw| <= 7, checked by the host), eight taps per
 // word: the k loop then selects a tap with scalar ALU only (a scalar or scratch load inside it would stall the wave)

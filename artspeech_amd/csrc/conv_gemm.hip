@@ -578,7 +578,7 @@ static int gemm_tile_choice(int M, int N, int n_prod, int Kp)
     // reads six fragments per six products; 64 x 256 gives every wave a 64 x 64 block over the whole k (eight per twelve, like 128 x 128):
     // M64 N509440 K64 T9 167 -> 139 us, N128000 41 -> 34, N63680 20.8 -> 19.7; below one round of the chip (N6400: 8.6 -> 10.8) it loses.
     if (M <= 64 && n_prod == 3 && as_cdiv(N, 256) >= 240) return 14;
-    const bool tall = M > 64 && (M % 128 == 0 || M % 128 > 64 || M >= 512);   // a 128-row tile is not half empty
+    const bool tall = as_fills_tall_tile(M);
     // (a 256 x 128 tile was measured and removed: faster alone, no gain inside the step -- DESIGN.md section 3.1)
     static const int choices[4] = {22, 21, 12, 11};
     static const double t1[4] = {1.0, 0.78, 0.78, 0.59};
@@ -656,6 +656,16 @@ static bool post_slice_ok(const ConvGemmArgs& a)
 {
     return a.Xh && a.ileave_u <= 1 && !a.transpose_out && (size_t)a.M * a.N * sizeof(float) <= kPostSlabMax &&
            a.T * (a.Kp / 16) + as_cdiv(a.K2, 16) >= 8;
+}
+// the K slices of a problem planned at S: two where S = 1, post_slice_ok holds, the workspace has room for two slabs and a reduction can
+// write the LayerNorm (ln) / AdaIN (adain, max_w: its widest utterance) behind it.  Whatever AS_NO_REDUCE_* says -- the switch changes who
+// normalises, never the conv's own arithmetic.  (Two slices always have a k iteration each: the >= 8 k-blocks of post_slice_ok are >= 2
+// iterations of any tile, which splits K over at most 4 waves.)
+static int post_slices(const ConvGemmArgs& a, int S, bool ln, bool adain, int max_w)
+{
+    const bool two = S == 1 && post_slice_ok(a) && a.ws && a.ws_bytes >= 2 * (size_t)a.M * a.N * sizeof(float) &&
+                     ((ln && a.M % 8 == 0 && a.M <= 512 && !a.Yh && a.act <= 2) || (adain && max_w > 0 && max_w <= 256 && a.act <= 2));
+    return two ? 2 : S;
 }
 
 extern "C" size_t as_conv_gemm_workspace_bytes(const ConvGemmArgs* a)
@@ -751,14 +761,6 @@ static double gemm_bytes(const ConvGemmArgs& a)
 {
     return 4.0 * (((double)a.T * a.K + a.K2) * a.M * a.n_groups + ((double)a.K + a.K2) * a.N + (double)a.M * a.N);
 }
-static int launch_reduce(const ConvGemmArgs& a, int S, hipStream_t stream)
-{
-    const int rows = a.Yh ? (16 * as_kbx(a.M) > a.M ? 16 * as_kbx(a.M) : a.M) : a.M;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(as_cdiv(a.N + 1, 256), as_cdiv(rows, 8)), dim3(256), 0, stream, a, S);
-    AS_CHECK_LAUNCH();
-    return AS_OK;
-}
-
 // the fast direct form (T <= 9) for n problems
 static int launch_direct_x4(const ConvGemmArgs* a, int n, hipStream_t stream)
 {
@@ -870,105 +872,36 @@ static int launch_reduce_post(const ConvGemmArgs* const* ptr, const int* So, con
     return AS_OK;
 }
 
-static int conv_gemm_one(const ConvGemmArgs* args_host, const AsAdainArgs* post_host, int post_max_w, const AsLnArgs* ln_host, hipStream_t stream)
+// the reductions of a launch's K-sliced problems ptr[k] (So[k] > 1), one launch: the AdaIN / LayerNorm behind problem k written by it
+// where np[k] / nl[k] is given (launch_reduce_post), else the plain sums -- one problem's kernel, or the list's
+static int launch_reductions(const ConvGemmArgs* const* ptr, const int* So, const AsAdainArgs* const* np, const int* max_w,
+                             const AsLnArgs* const* nl, int m, hipStream_t stream)
 {
-    ConvGemmArgs norm;
-    const int rn = conv_gemm_normalise(args_host, norm);
-    if (rn != AS_OK) return rn;
-    const ConvGemmArgs& a = norm;
-    if (a.N == 0) return AS_OK;
-    AsAdainArgs post;
-    const bool want_post = post_wanted(post_host), want_ln = ln_wanted(ln_host);
-    if (want_post && want_ln) return AS_EINVAL;
-    if (want_post) {
-        const int rp = post_normalise(a, *post_host, post);
-        if (rp != AS_OK) return rp;
-    }
-    if (want_ln) {
-        const int rl = ln_check(a, *ln_host);
-        if (rl != AS_OK) return rl;
-    }
-    bool post_done = false;
-    {
-    const int rc1 = [&]() -> int {
-    if (direct_cin1(a)) {
-        char tag[64];
-        snprintf(tag, sizeof(tag), "M%d N%d K1 T%d direct", a.M, a.N, a.T);
-        AsProfScope prof__(AS_CLS_GEMM, 2.0 * a.M * a.N * (double)a.T, 4.0 * ((double)a.T * a.M + a.N + (double)a.M * a.N), stream, tag);
-        if (a.T <= 9) {
-            const int rd = launch_direct_x4(&a, 1, stream);
-            if (rd != AS_OK) return rd;
-        } else {
-            hipLaunchKernelGGL(conv_direct_cin1_kernel, dim3(as_cdiv(a.N, 256)), dim3(256), 0, stream, a);
+    for (int k = 0; k < m; ++k)
+        if (np[k] || nl[k]) return launch_reduce_post(ptr, So, np, max_w, nl, m, stream);
+    ReduceMulti rm;
+    memset(&rm, 0, sizeof(rm));
+    int rows_max = 0;
+    for (int k = 0; k < m; ++k)
+        if (So[k] > 1) {
+            const ConvGemmArgs& a = *ptr[k];
+            rm.a[rm.n] = a;
+            rm.S[rm.n] = So[k];
+            rm.blk0[rm.n + 1] = rm.blk0[rm.n] + as_cdiv(a.N + 1, 256);
+            rows_max = std::max(rows_max, a.Yh ? std::max(16 * as_kbx(a.M), a.M) : a.M);
+            ++rm.n;
         }
-        AS_CHECK_LAUNCH();
-        return AS_OK;
-    }
-    if (!a.Wh) return AS_EINVAL;
-    GemmPlan plan = gemm_plan(a);
-    if (plan.xh_bytes) {                                   // no operand image from the caller: it needs room in the workspace
-        if (!a.ws || a.ws_bytes < plan.xh_bytes) return AS_EINVAL;
-        if (a.ws_bytes < align256(plan.slab_bytes) + plan.xh_bytes) { plan.S = 1; plan.slab_bytes = 0; }
-    } else if (plan.S > 1 && (!a.ws || a.ws_bytes < plan.slab_bytes)) {
-        plan.S = 1;                                        // no workspace: no K slices
-        plan.slab_bytes = 0;
-    }
-    // (see post_slice_ok: whatever AS_NO_REDUCE_* says -- the switch changes who normalises, never the conv's own arithmetic)
-    int S_ = plan.S;
-    if (S_ == 1 && post_slice_ok(a) && a.ws && a.ws_bytes >= 2 * (size_t)a.M * a.N * sizeof(float) &&
-        ((want_ln && a.M % 8 == 0 && a.M <= 512 && !a.Yh && a.act <= 2) || (want_post && post_max_w > 0 && post_max_w <= 256 && a.act <= 2)))
-        S_ = 2;
-    const int S = S_;
-    char tag[96], shape[64];
-    gemm_tag(a, shape, sizeof(shape));
-    snprintf(tag, sizeof(tag), "%s tile%d S%d%s%s%s", shape, plan.choice, S, a.n_prod == 1 ? " h1" : "", a.Xh ? "" : " +split",
-             a.Yh ? (a.Y ? " y+yh" : " yh") : "");
-    // algorithmic work of this launch: 2*M*N*(K*T + K2) flop; bytes = weights + inputs + output once (4 bytes per element)
-    AsProfScope prof__(AS_CLS_GEMM, gemm_flops(a), gemm_bytes(a), stream, tag);
-    if (!a.Xh) {                                                        // split once, behind the K slabs in the workspace
-        uint16_t* xh = reinterpret_cast<uint16_t*>(reinterpret_cast<unsigned char*>(a.ws) + align256(plan.slab_bytes));
-        const int rc = as_split_f16x2_launch(a.X, a.ldx, a.K, a.N, a.in_act == 2, a.in_slope, xh, stream);
-        if (rc != AS_OK) return rc;
-        norm.Xh = xh;
-    }
-    const ConvGemmArgs* one = &a;
-    const bool fuse_ln = S > 1 && want_ln && ln_fusable(a, *ln_host);
-    norm.slab_tr = fuse_ln ? 1 : 0;                                     // (the slices store time-major for the reduction that normalises columns)
-    const int rc = as_conv_gemm_h3_launch(&one, &S, 1, plan.choice, stream);
-    if (rc != AS_OK) return rc;
-    if (fuse_ln) {
-        const AsAdainArgs* np = nullptr;
-        const AsLnArgs* nl = ln_host;
-        post_done = true;
-        return launch_reduce_post(&one, &S, &np, &post_max_w, &nl, 1, stream);
-    }
-    if (S > 1 && want_post && post_fusable(a, post_max_w)) {
-        const AsAdainArgs* np = &post;
-        post_done = true;
-        return launch_reduce_post(&one, &S, &np, &post_max_w, nullptr, 1, stream);
-    }
-    if (S > 1) return launch_reduce(a, S, stream);
-    return AS_OK;
-    }();
-    if (rc1 != AS_OK) return rc1;
-    }
-    if (want_post && !post_done) return as_adain_image_f32(&post, stream);   // (its own profiling scope, behind the conv's)
-    if (want_ln && !post_done)
-        return as_channel_layernorm_split_f32(a.Y, a.ldy, a.M, a.N, ln_host->gamma, ln_host->beta, ln_host->gamma2, ln_host->beta2, ln_host->n_split,
-                                              ln_host->eps, ln_host->relu, ln_host->yh, stream);
+    if (rm.n == 0) return AS_OK;
+    const dim3 grid(rm.blk0[rm.n], as_cdiv(rows_max, 8));
+    if (rm.n == 1) hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, stream, rm.a[0], rm.S[0]);
+    else hipLaunchKernelGGL(splitk_reduce_multi_kernel, grid, dim3(256), 0, stream, rm);
+    AS_CHECK_LAUNCH();
     return AS_OK;
 }
 
-extern "C" int as_conv_gemm_f32(const ConvGemmArgs* args_host, as_stream_t stream_)
-{
-    return conv_gemm_one(args_host, nullptr, 0, nullptr, static_cast<hipStream_t>(stream_));
-}
-
 // ----------------------------------------------------------------------------------------------------------------
-// Several independent convolutions as ONE launch (include/artspeech_hip.h: as_conv_gemm_multi_f32).
+// One convolution, or several independent ones as ONE launch (include/artspeech_hip.h: as_conv_gemm_f32, as_conv_gemm_multi[_post]_f32).
 // ----------------------------------------------------------------------------------------------------------------
-static bool multi_tall(int M) { return M > 64 && (M % 128 == 0 || M % 128 > 64 || M >= 512); }
-
 // one tile for the whole set: the cost model of gemm_tile_choice on the SUM of the problems' tiles
 static int multi_tile_choice(const ConvGemmArgs* a, int n)
 {
@@ -981,7 +914,7 @@ static int multi_tile_choice(const ConvGemmArgs* a, int n)
     for (int i = 0; i < n; ++i) {
         const double wi = (double)a[i].M * a[i].N * ((double)a[i].K * a[i].T + a[i].K2);
         work += wi;
-        if (multi_tall(a[i].M)) tall_work += wi;
+        if (as_fills_tall_tile(a[i].M)) tall_work += wi;
         all_short = all_short && a[i].M <= 64;
         all_32 = all_32 && a[i].M <= 32;
         small_k = small_k || a[i].Kp <= 32;
@@ -1021,24 +954,25 @@ extern "C" int as_conv_gemm_multi_tile(const ConvGemmArgs* list_host, int n)
     return multi_tile_choice(norm, n);
 }
 
-static int conv_gemm_multi(const ConvGemmArgs* list_host, const AsAdainArgs* post_host, const int32_t* post_max_w, const AsLnArgs* ln_host, int n,
-                           hipStream_t stream)
+// 1 .. AS_MAX_MULTI problems: checks, plan, launch, then the AdaINs / LayerNorms no reduction took along.  ONE problem (after those
+// with N = 0 are dropped) runs by the single launch's rules: gemm_plan, fp32 activations split into the workspace first, the direct
+// Cin = 1 kernel for any T.  Several run as ONE launch by the set's rules -- multi_tile_choice, K slices by share -- from operand images only.
+static int conv_gemm(const ConvGemmArgs* list_host, const AsAdainArgs* post_host, const int32_t* post_max_w, const AsLnArgs* ln_host, int n,
+                     hipStream_t stream)
 {
     if (!list_host || n < 1 || n > AS_MAX_MULTI || (post_host && !post_max_w)) return AS_EINVAL;
     static_assert(AS_MAX_MULTI == H3_MAXP, "header and kernel disagree");
-    if (n == 1) return conv_gemm_one(list_host, post_host, post_host ? post_max_w[0] : 0, ln_host, stream);
     ConvGemmArgs norm[H3_MAXP];
     AsAdainArgs post[H3_MAXP];
     AsLnArgs lnp[H3_MAXP];
     bool has_ln[H3_MAXP];
     bool has_post[H3_MAXP], post_done[H3_MAXP];
-    int pmw[H3_MAXP], src[H3_MAXP];
-    int m = 0, n_direct = 0;
+    int pmw[H3_MAXP];
+    int m = 0;
     for (int i = 0; i < n; ++i) {
         const int r = conv_gemm_normalise(&list_host[i], norm[m]);
         if (r != AS_OK) return r;
         if (norm[m].N == 0) continue;                                    // nothing to do for this one
-        n_direct += direct_cin1(norm[m]) && norm[m].T <= 9 ? 1 : 0;
         has_post[m] = post_host && post_wanted(&post_host[i]);
         has_ln[m] = ln_host && ln_wanted(&ln_host[i]);
         if (has_post[m] && has_ln[m]) return AS_EINVAL;
@@ -1049,7 +983,6 @@ static int conv_gemm_multi(const ConvGemmArgs* list_host, const AsAdainArgs* pos
         }
         post_done[m] = false;
         pmw[m] = has_post[m] ? post_max_w[i] : 0;
-        src[m] = i;
         if (has_post[m]) {
             const int rp = post_normalise(norm[m], post_host[i], post[m]);
             if (rp != AS_OK) return rp;
@@ -1057,13 +990,10 @@ static int conv_gemm_multi(const ConvGemmArgs* list_host, const AsAdainArgs* pos
         ++m;
     }
     if (m == 0) return AS_OK;
-    if (m == 1) return conv_gemm_one(&list_host[src[0]], post_host ? &post_host[src[0]] : nullptr, pmw[0], ln_host ? &ln_host[src[0]] : nullptr, stream);
-    bool any_post = false;
-    for (int i = 0; i < m; ++i) any_post = any_post || has_post[i] || has_ln[i];
     auto finish_posts = [&]() -> int {                                   // the AdaINs / LayerNorms no reduction kernel took along: one launch each, in list order
         for (int i = 0; i < m; ++i) {
             if (has_post[i] && !post_done[i]) {
-                const int r = as_adain_image_f32(&post[i], stream);
+                const int r = as_adain_image_f32(&post[i], stream);     // (its own profiling scope, behind the conv's)
                 if (r != AS_OK) return r;
             }
             if (has_ln[i] && !post_done[i]) {
@@ -1075,7 +1005,9 @@ static int conv_gemm_multi(const ConvGemmArgs* list_host, const AsAdainArgs* pos
         }
         return AS_OK;
     };
-    if (n_direct == m) {                                                 // a set of Cin = 1 stems: the direct kernel, one launch
+    bool direct = true;                                                  // one Cin = 1 conv, or a set of Cin = 1 stems (T <= 9): the direct kernel
+    for (int i = 0; i < m; ++i) direct = direct && direct_cin1(norm[i]) && (m == 1 || norm[i].T <= 9);
+    if (direct) {
         static_assert(DIRECT_MAXP == H3_MAXP, "one list length");
         double fl = 0, by = 0;
         for (int i = 0; i < m; ++i) {
@@ -1083,124 +1015,137 @@ static int conv_gemm_multi(const ConvGemmArgs* list_host, const AsAdainArgs* pos
             by += 4.0 * ((double)norm[i].T * norm[i].M + norm[i].N + (double)norm[i].M * norm[i].N);
         }
         char tag[64];
-        snprintf(tag, sizeof(tag), "multi%d direct: M%d N%d K1 T%d | ...", m, norm[0].M, norm[0].N, norm[0].T);
-        int rd;
+        if (m == 1) snprintf(tag, sizeof(tag), "M%d N%d K1 T%d direct", norm[0].M, norm[0].N, norm[0].T);
+        else snprintf(tag, sizeof(tag), "multi%d direct: M%d N%d K1 T%d | ...", m, norm[0].M, norm[0].N, norm[0].T);
         {
             AsProfScope prof__(AS_CLS_GEMM, fl, by, stream, tag);
-            rd = launch_direct_x4(norm, m, stream);
+            if (norm[0].T > 9) {                                         // (one problem) the general form
+                hipLaunchKernelGGL(conv_direct_cin1_kernel, dim3(as_cdiv(norm[0].N, 256)), dim3(256), 0, stream, norm[0]);
+                AS_CHECK_LAUNCH();
+            } else {
+                const int rd = launch_direct_x4(norm, m, stream);
+                if (rd != AS_OK) return rd;
+            }
         }
-        return rd != AS_OK ? rd : finish_posts();
+        return finish_posts();
     }
-    // otherwise, in one launch only what the tiled kernel runs from operand images with the same arithmetic
+    // the tiled kernel needs a weight image; a set, in one launch, only what it runs from operand images with the same arithmetic
     for (int i = 0; i < m; ++i)
-        if (direct_cin1(norm[i]) || !norm[i].Wh || !norm[i].Xh || norm[i].n_prod != norm[0].n_prod || norm[i].ileave_u > 1) return AS_EINVAL;
-    const int choice = multi_tile_choice(norm, m);
-    int bm, bn;
-    tile_dims(choice, &bm, &bn);
-    // K slices: a launch costs what its longest chain of k iterations on one CU costs.  With W = all problems' tiles x iterations spread
-    // over the chip's 512 workgroup slots, a problem whose tile alone runs longer than that share (the towers' closing 5 x 5 convs: 800
-    // k-blocks on a dozen tiles, beside convs of 30-300) is cut into slices of about that length -- as many as its workspace holds slabs
-    // for, each keeping >= 384 k.  (That is also the rule of the single launch for grids that leave most of the chip idle.)
-    const int wk = choice == 2 ? 2 : bm * bn >= 4 * 64 * 64 ? 1 : 4 * 64 * 64 / (bm * bn);
-    int order[H3_MAXP], S[H3_MAXP], nkt[H3_MAXP];
-    double len[H3_MAXP], W = 0;
-    for (int i = 0; i < m; ++i) {
-        const ConvGemmArgs& a = norm[i];
-        nkt[i] = a.T * as_cdiv(a.Kp / 16, wk) + as_cdiv(as_cdiv(a.K2, 16), wk);
-        W += (double)nkt[i] * as_cdiv(a.M, bm) * (a.n_groups > 1 ? a.n_groups * as_cdiv(a.group_cols, bn) : as_cdiv(a.N, bn));
+        if (direct_cin1(norm[i]) || !norm[i].Wh || (m > 1 && (!norm[i].Xh || norm[i].n_prod != norm[0].n_prod || norm[i].ileave_u > 1)))
+            return AS_EINVAL;
+    int choice, S[H3_MAXP], order[H3_MAXP];
+    size_t xh_off = 0;                                                   // one problem without an operand image: where its split goes
+    for (int i = 0; i < m; ++i) order[i] = i;
+    if (m == 1) {
+        const ConvGemmArgs& a = norm[0];
+        GemmPlan plan = gemm_plan(a);
+        if (plan.xh_bytes) {                                   // no operand image from the caller: it needs room in the workspace
+            if (!a.ws || a.ws_bytes < plan.xh_bytes) return AS_EINVAL;
+            if (a.ws_bytes < align256(plan.slab_bytes) + plan.xh_bytes) { plan.S = 1; plan.slab_bytes = 0; }
+        } else if (plan.S > 1 && (!a.ws || a.ws_bytes < plan.slab_bytes)) {
+            plan.S = 1;                                        // no workspace: no K slices
+            plan.slab_bytes = 0;
+        }
+        choice = plan.choice;
+        S[0] = post_slices(a, plan.S, has_ln[0], has_post[0], pmw[0]);
+        xh_off = align256(plan.slab_bytes);
+    } else {
+        choice = multi_tile_choice(norm, m);
+        int bm, bn;
+        tile_dims(choice, &bm, &bn);
+        // K slices: a launch costs what its longest chain of k iterations on one CU costs.  With W = all problems' tiles x iterations spread
+        // over the chip's 512 workgroup slots, a problem whose tile alone runs longer than that share (the towers' closing 5 x 5 convs: 800
+        // k-blocks on a dozen tiles, beside convs of 30-300) is cut into slices of about that length -- as many as its workspace holds slabs
+        // for, each keeping >= 384 k.  (That is also the rule of the single launch for grids that leave most of the chip idle.)
+        const int wk = choice == 2 ? 2 : bm * bn >= 4 * 64 * 64 ? 1 : 4 * 64 * 64 / (bm * bn);
+        int nkt[H3_MAXP];
+        double len[H3_MAXP], W = 0;
+        for (int i = 0; i < m; ++i) {
+            const ConvGemmArgs& a = norm[i];
+            nkt[i] = a.T * as_cdiv(a.Kp / 16, wk) + as_cdiv(as_cdiv(a.K2, 16), wk);
+            W += (double)nkt[i] * as_cdiv(a.M, bm) * (a.n_groups > 1 ? a.n_groups * as_cdiv(a.group_cols, bn) : as_cdiv(a.N, bn));
+        }
+        const double share = std::max(W / 512.0, 1.0);
+        for (int i = 0; i < m; ++i) {
+            const ConvGemmArgs& a = norm[i];
+            const int min_kt = std::max(1, 24 / wk);
+            int s = nkt[i] > 1.5 * share ? (int)ceil(nkt[i] / share) : 1;
+            s = std::min(std::min(s, 16), nkt[i] / min_kt);
+            const size_t slab = (size_t)a.M * a.N * sizeof(float);
+            if (s > 1 && (!a.ws || a.ws_bytes / slab < (size_t)s)) s = a.ws ? (int)std::min<size_t>(a.ws_bytes / slab, (size_t)s) : 1;
+            S[i] = post_slices(a, s < 1 ? 1 : s, has_ln[i], has_post[i], pmw[i]);
+            len[i] = (double)nkt[i] / S[i];
+        }
+        std::sort(order, order + m, [&](int x, int y) { return len[x] > len[y]; });
     }
-    const double share = std::max(W / 512.0, 1.0);
-    for (int i = 0; i < m; ++i) {
-        const ConvGemmArgs& a = norm[i];
-        const int min_kt = std::max(1, 24 / wk);
-        int s = nkt[i] > 1.5 * share ? (int)ceil(nkt[i] / share) : 1;
-        s = std::min(std::min(s, 16), nkt[i] / min_kt);
-        const size_t slab = (size_t)a.M * a.N * sizeof(float);
-        if (s > 1 && (!a.ws || a.ws_bytes / slab < (size_t)s)) s = a.ws ? (int)std::min<size_t>(a.ws_bytes / slab, (size_t)s) : 1;
-        S[i] = s < 1 ? 1 : s;
-        // (post_slice_ok: a tiny conv with a normalisation behind it is always cut in two -- its reduction replaces the normalisation's launch)
-        if (S[i] == 1 && post_slice_ok(a) && a.ws && a.ws_bytes >= 2 * slab && nkt[i] >= 2 &&
-            ((has_ln[i] && a.M % 8 == 0 && a.M <= 512 && !a.Yh && a.act <= 2) || (has_post[i] && pmw[i] > 0 && pmw[i] <= 256 && a.act <= 2)))
-            S[i] = 2;
-        len[i] = (double)nkt[i] / S[i];
-        order[i] = i;
-    }
-    std::sort(order, order + m, [&](int x, int y) { return len[x] > len[y]; });
     const ConvGemmArgs* ptr[H3_MAXP];
     int So[H3_MAXP];
     double flops = 0, bytes = 0;
-    char tag[160];
-    int at = snprintf(tag, sizeof(tag), "multi%d tile%d:", m, choice);
     for (int k = 0; k < m; ++k) {
         ptr[k] = &norm[order[k]];
         So[k] = S[order[k]];
         flops += gemm_flops(*ptr[k]);
         bytes += gemm_bytes(*ptr[k]);
-        char shape[64], sl[8] = "";
-        gemm_tag(*ptr[k], shape, sizeof(shape));
-        if (So[k] > 1) snprintf(sl, sizeof(sl), " S%d", So[k]);
-        if (at < (int)sizeof(tag) - 1) at += snprintf(tag + at, sizeof(tag) - at, " %s%s%s", shape, sl, k + 1 < m ? " |" : "");
     }
-    // K-sliced problems with a LayerNorm behind them store their slabs time-major (the reduction normalises whole columns)
+    char tag[160], shape[64];
+    if (m == 1) {
+        const ConvGemmArgs& a = norm[0];
+        gemm_tag(a, shape, sizeof(shape));
+        snprintf(tag, sizeof(tag), "%s tile%d S%d%s%s%s", shape, choice, So[0], a.n_prod == 1 ? " h1" : "", a.Xh ? "" : " +split",
+                 a.Yh ? (a.Y ? " y+yh" : " yh") : "");
+    } else {
+        int at = snprintf(tag, sizeof(tag), "multi%d tile%d:", m, choice);
+        for (int k = 0; k < m; ++k) {
+            char sl[8] = "";
+            gemm_tag(*ptr[k], shape, sizeof(shape));
+            if (So[k] > 1) snprintf(sl, sizeof(sl), " S%d", So[k]);
+            if (at < (int)sizeof(tag) - 1) at += snprintf(tag + at, sizeof(tag) - at, " %s%s%s", shape, sl, k + 1 < m ? " |" : "");
+        }
+    }
+    // K-sliced problems whose result is read through a LayerNorm / an AdaIN (few columns: the reduction holds a channel's whole time
+    // axis): the reduction launch writes that image too.  With a LayerNorm the slices store their slabs time-major (it normalises whole columns).
     const AsLnArgs* nl[H3_MAXP];
-    bool any_ln_fused = false;
+    const AsAdainArgs* np[H3_MAXP];
+    int mwo[H3_MAXP];
     for (int k = 0; k < m; ++k) {
         const int i = order[k];
         nl[k] = (has_ln[i] && So[k] > 1 && ln_fusable(norm[i], lnp[i])) ? &lnp[i] : nullptr;
+        np[k] = (has_post[i] && So[k] > 1 && post_fusable(norm[i], pmw[i])) ? &post[i] : nullptr;
         norm[i].slab_tr = nl[k] ? 1 : 0;
-        any_ln_fused = any_ln_fused || nl[k];
+        mwo[k] = pmw[i];
     }
     {
+        // algorithmic work of this launch: 2*M*N*(K*T + K2) flop; bytes = weights + inputs + output once (4 bytes per element)
         AsProfScope prof__(AS_CLS_GEMM, flops, bytes, stream, tag);
+        if (!norm[0].Xh) {                                               // (one problem) split once, behind the K slabs in the workspace
+            ConvGemmArgs& a = norm[0];
+            uint16_t* xh = reinterpret_cast<uint16_t*>(reinterpret_cast<unsigned char*>(a.ws) + xh_off);
+            const int rc = as_split_f16x2_launch(a.X, a.ldx, a.K, a.N, a.in_act == 2, a.in_slope, xh, stream);
+            if (rc != AS_OK) return rc;
+            a.Xh = xh;
+        }
         const int rc = as_conv_gemm_h3_launch(ptr, So, m, choice, stream);
         if (rc != AS_OK) return rc;
-        // K-sliced problems whose result is read through an AdaIN (few columns: the reduction holds a channel's whole time axis): the
-        // reduction launch writes the AdaIN image too
-        bool fused = any_ln_fused;
-        const AsAdainArgs* np[H3_MAXP];
-        for (int k = 0; k < m; ++k) {
-            const int i = order[k];
-            np[k] = (any_post && has_post[i] && So[k] > 1 && post_fusable(*ptr[k], pmw[i])) ? &post[i] : nullptr;
-            fused = fused || np[k];
-        }
-        if (fused) {
-            int mwo[H3_MAXP];
-            for (int k = 0; k < m; ++k) mwo[k] = pmw[order[k]];
-            const int rr = launch_reduce_post(ptr, So, np, mwo, nl, m, stream);
-            if (rr != AS_OK) return rr;
-            for (int k = 0; k < m; ++k)
-                if (np[k] || nl[k]) post_done[order[k]] = true;
-        }
-        ReduceMulti rm;
-        memset(&rm, 0, sizeof(rm));
-        int rows_max = 0;
-        for (int k = 0; k < m && !fused; ++k)
-            if (So[k] > 1) {
-                const ConvGemmArgs& a = *ptr[k];
-                rm.a[rm.n] = a;
-                rm.S[rm.n] = So[k];
-                rm.blk0[rm.n + 1] = rm.blk0[rm.n] + as_cdiv(a.N + 1, 256);
-                rows_max = std::max(rows_max, a.Yh ? std::max(16 * as_kbx(a.M), a.M) : a.M);
-                ++rm.n;
-            }
-        if (rm.n == 1) {
-            const int rr = launch_reduce(rm.a[0], rm.S[0], stream);
-            if (rr != AS_OK) return rr;
-        } else if (rm.n > 1) {
-            hipLaunchKernelGGL(splitk_reduce_multi_kernel, dim3(rm.blk0[rm.n], as_cdiv(rows_max, 8)), dim3(256), 0, stream, rm);
-            AS_CHECK_LAUNCH();
-        }
+        const int rr = launch_reductions(ptr, So, np, mwo, nl, m, stream);
+        if (rr != AS_OK) return rr;
     }
+    for (int k = 0; k < m; ++k)
+        if (np[k] || nl[k]) post_done[order[k]] = true;
     return finish_posts();
+}
+
+extern "C" int as_conv_gemm_f32(const ConvGemmArgs* args_host, as_stream_t stream_)
+{
+    return conv_gemm(args_host, nullptr, nullptr, nullptr, 1, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int as_conv_gemm_multi_f32(const ConvGemmArgs* list_host, int n, as_stream_t stream_)
 {
-    return conv_gemm_multi(list_host, nullptr, nullptr, nullptr, n, static_cast<hipStream_t>(stream_));
+    return conv_gemm(list_host, nullptr, nullptr, nullptr, n, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int as_conv_gemm_multi_post_f32(const ConvGemmArgs* list_host, const AsAdainArgs* post_host, const int32_t* post_max_w,
                                            const AsLnArgs* post_ln_host, int n, as_stream_t stream_)
 {
-    return conv_gemm_multi(list_host, post_host, post_max_w, post_ln_host, n, static_cast<hipStream_t>(stream_));
+    return conv_gemm(list_host, post_host, post_max_w, post_ln_host, n, static_cast<hipStream_t>(stream_));
 }

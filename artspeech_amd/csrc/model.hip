@@ -763,7 +763,6 @@ static bool gemm_direct(const ConvGemmArgs& g)           // the Cin = 1 direct k
     int32_t kind = 1, tile = 0, slices = 0;
     return g.N > 0 && g.T <= 9 && as_conv_gemm_plan(&g, &kind, &tile, &slices) == AS_OK && kind == 0;
 }
-static bool gemm_tall(int M) { return M > 64 && (M % 128 == 0 || M % 128 > 64 || M >= 512); }   // (a 128-row tile is not half empty: conv_gemm.hip)
 
 static void play(Ctx& c, Sched& S)
 {
@@ -900,14 +899,14 @@ static void play(Ctx& c, Sched& S)
             double work[2] = {0, 0};
             for (int i = 0; i < nh; ++i) {
                 const ConvGemmArgs& g = S.q[heads[i]][head[heads[i]]].g;
-                work[gemm_tall(g.M) ? 1 : 0] += (double)g.M * g.N * ((double)g.K * g.T + g.K2);
+                work[as_fills_tall_tile(g.M) ? 1 : 0] += (double)g.M * g.N * ((double)g.K * g.T + g.K2);
             }
             const int cls = work[1] >= work[0] ? 1 : 0;
             // (a 64-channel conv may ride with a set of 128-row problems when it is a small part of the work: as_conv_gemm_multi_tile)
             const bool ride = cls == 1 && work[0] <= 0.1 * work[1];
             for (int i = 0; i < nh && np < AS_MAX_MULTI; ++i) {
                 const ConvGemmArgs& g = S.q[heads[i]][head[heads[i]]].g;
-                if (((gemm_tall(g.M) ? 1 : 0) == cls || ride) && (np == 0 || g.n_prod == S.q[pick[0]][head[pick[0]]].g.n_prod)) pick[np++] = heads[i];
+                if (((as_fills_tall_tile(g.M) ? 1 : 0) == cls || ride) && (np == 0 || g.n_prod == S.q[pick[0]][head[pick[0]]].g.n_prod)) pick[np++] = heads[i];
             }
             if (np < 2) lone = pick[0];
         }
