@@ -740,6 +740,10 @@ static int conv_gemm_normalise(const ConvGemmArgs* args_host, ConvGemmArgs& norm
     if ((a.X && a.ldx < a.N) || (a.Y && a.ldy < (a.transpose_out ? a.M : a.N)) || (a.res && (a.ldr < a.N || a.transpose_out)) ||
         (a.Yh && a.transpose_out))
         return AS_EINVAL;
+    // the time-major store (the LSTM input projection) has bias only: its epilogue holds no division and no activation
+    if (a.transpose_out && (a.act != 0 || a.div_sqrt2)) return AS_EINVAL;
+    // the division by sqrt(2) comes with no activation, ReLU or LeakyReLU only (epilogue_dispatch has no other combination)
+    if (a.div_sqrt2 && a.act > 2) return AS_EINVAL;
     if (((reinterpret_cast<uintptr_t>(a.Wh) | reinterpret_cast<uintptr_t>(a.Xh) | reinterpret_cast<uintptr_t>(a.Yh)) & 15) != 0) return AS_EINVAL;
     // 32-bit byte offsets inside the buffer descriptors
     if (((double)a.T * as_kbx(a.K) + (a.K2 ? as_kbx(a.K2) : 0)) * 64.0 * a.M >= 2147483648.0 || (a.X && (double)a.K * a.ldx * 4.0 + 16.0 >= 4294967296.0)) return AS_EINVAL;

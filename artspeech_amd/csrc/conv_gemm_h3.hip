@@ -3,10 +3,14 @@
 //
 //   Y[m][j] = epilogue( sum_t sum_k  W[t][k][m] * X[k][ j + dh[t]*Wj + dw[t] ] )      m < M, j < N
 //
-//   x = h + l,  h = fp16(x), l = fp16(x - h)  (22 significand bits);   x*w ~= h_x*l_w + l_x*h_w + h_x*h_w
+//   x = h + l,  h = fp16(x), l = fp16(x - h);   x*w ~= h_x*l_w + l_x*h_w + h_x*h_w
 //   on v_mfma_f32_32x32x16_f16 (32 cycles, K = 16), fp32 accumulation, smallest terms first.  The dropped l*l term is below
 //   2^-22 |x w|; weights are pre-scaled by a power of two so their l parts are normal numbers (ConvGemmArgs.acc_scale undoes
-//   it).  scripts/exp/f16x3_numerics.py runs the whole path this way on the CPU: the mel lands 6e-6 from the reference's
+//   it).  Activations are NOT scaled, so the split holds 22 significand bits only above the fp16 subnormals: |x - h - l| <=
+//   max(2^-22 |x|, 2^-25) -- l is subnormal below |x| ~ 2^-3, h below 2^-14.  The envelope an output meets (oracle/gemm_ref.py
+//   derives it; the GPU tests check it per element from 2^-24 to 2^14): |y - y_exact| <= 2^-20 A + 2^-25 F + fp32 accumulation and
+//   epilogue roundings, A = conv(|w|, |x|), F = the sum of |w| over the taps that read a valid column -- relative above the floor,
+//   an ABSOLUTE floor of 2^-25 per unit of weight below it.  scripts/exp/f16x3_numerics.py runs the whole path this way on the CPU: the mel lands 6e-6 from the reference's
 //   golden vectors, where exact fp32 products land 5e-6 (bound 1e-4).  Three matrix-core products per fp32 product instead of
 //   round 1's six bf16 ones (bf16x6), and 4 bytes of operand image per element instead of 6.
 //

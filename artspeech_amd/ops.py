@@ -261,7 +261,7 @@ def project_cols(X, N, w, bias, Y):
 
 def conv_gemm(Wt, X, lay, Y, taps, bias=None, res=None, act=0, div_sqrt2=False, in_act=0, transpose_out=False,
               use_meta=True, in_slope=0.2, act_slope=0.2, xs=None, K=None, group_cols=0, yh=None, yh_lrelu=False, n_prod=None, plan_out=None,
-              x2s=None, K2=0, src_col=None, src_meta=None, N_in=0, defer=None, ileave=0):
+              x2s=None, K2=0, src_col=None, src_meta=None, N_in=0, defer=None, ileave=0, n_valid=None, ws_bytes=None):
     """Y = epi(sum_t Wt[t]^T X shifted by tap t).  defer: a list -- the call is not launched but appended to it (conv_gemm_multi
     launches the whole list as ONE kernel: as_conv_gemm_multi_f32).  Wt: prep_weight(...); X [K][*] fp32 or None with xs= (the split image of
     X: split_act / adain_split / channel_layernorm_split / another conv's yh=) and K=; Y [M][*] (or [N][*] transposed) or None
@@ -270,7 +270,10 @@ def conv_gemm(Wt, X, lay, Y, taps, bias=None, res=None, act=0, div_sqrt2=False, 
     whose 1x1 conv (weights: prep_weight(..., sc=)) is summed into the same accumulators (needs xs=).  src_col / src_meta / N_in: a
     strided or valid conv -- `lay` is the OUTPUT layout, xs an image over N_in input columns, output column j reads input column
     src_col[j] + dh * W_in + dw and src_meta[j] (strided_source) describes that input position.  ileave = u: the M = u C rows are
-    (phase, channel) and Y is [C][u N] with Y[m][u j + r] = row r C + m at column j (ConvGemmArgs.ileave_u; bias per row)."""
+    (phase, channel) and Y is [C][u N] with Y[m][u j + r] = row r C + m at column j (ConvGemmArgs.ileave_u; bias per row).  n_valid: a
+    device int32 tensor, *n_valid = the leading valid columns (of every weight group) of a capacity launch (ConvGemmArgs.n_valid).
+    ws_bytes (tests): the workspace the call gets -- "single" / "multi" (the library's two sizes) or a byte count; None: the size the
+    call needs (the multi one when deferred)."""
     T, Kp, M = Wt.shape
     if X is None:
         if xs is None or K is None:
@@ -297,12 +300,21 @@ def conv_gemm(Wt, X, lay, Y, taps, bias=None, res=None, act=0, div_sqrt2=False, 
         a.src_col, a.N_in, a.meta = _p(src_col), N_in, _p(src_meta)
     a.n_prod = n_prod if n_prod is not None else (1 if GEMM_IMPL == "h1" else 3)
     a.ileave_u = int(ileave)
+    if n_valid is not None:
+        if n_valid.dtype != torch.int32:
+            raise ValueError("conv_gemm: n_valid is a device int32 tensor")
+        a.n_valid = _p(n_valid)
     a.in_slope, a.act_slope = in_slope, act_slope          # used as given (the acoustic path's LeakyReLU slope is 0.2)
     assert len(taps) == T
     for i, (dh, dw) in enumerate(taps):
         a.dh[i], a.dw[i] = dh, dw
     L = _lib.lib()
-    nbytes = (L.as_conv_gemm_multi_workspace_bytes if defer is not None else L.as_conv_gemm_workspace_bytes)(ctypes.byref(a))
+    if ws_bytes is None:
+        ws_bytes = "multi" if defer is not None else "single"
+    if isinstance(ws_bytes, str):
+        nbytes = (L.as_conv_gemm_multi_workspace_bytes if ws_bytes == "multi" else L.as_conv_gemm_workspace_bytes)(ctypes.byref(a))
+    else:
+        nbytes = int(ws_bytes)
     if nbytes:                                       # split-K partial slabs, the split image of X (caller-owned scratch)
         ws = torch.empty(nbytes // 4 + 4, dtype=torch.float32, device=(Y if Y is not None else yh).device)
         a.ws, a.ws_bytes = ws.data_ptr(), nbytes
@@ -311,7 +323,7 @@ def conv_gemm(Wt, X, lay, Y, taps, bias=None, res=None, act=0, div_sqrt2=False, 
         check(L.as_conv_gemm_plan(ctypes.byref(a), ctypes.byref(k), ctypes.byref(t), ctypes.byref(sl)), "as_conv_gemm_plan")
         plan_out.update(kind=k.value, tile=t.value, slices=sl.value)
     if defer is not None:
-        defer.append((a, [Wt, X, xs, Y, yh, bias, res, x2s, src_col, src_meta, lay, (ws if nbytes else None)]))
+        defer.append((a, [Wt, X, xs, Y, yh, bias, res, x2s, src_col, src_meta, lay, (ws if nbytes else None), n_valid]))
         return Y if Y is not None else yh
     check(L.as_conv_gemm_f32(ctypes.byref(a), stream()), "as_conv_gemm_f32")
     return Y if Y is not None else yh

@@ -174,10 +174,10 @@ typedef struct ConvGemmArgs {
     int32_t ldx, ldy, ldr;
     int32_t act;           /* epilogue activation: 0 none, 1 ReLU, 2 LeakyReLU(act_slope), 3 tanh, 4 |x| (Utils/JDC/model.py:137),
                               5 swish x*sigmoid(x) (Utils/EMA/conformer/conformer/activation.py:29) */
-    int32_t div_sqrt2;     /* epilogue: divide by sqrt(2) after bias and residual */
+    int32_t div_sqrt2;     /* epilogue: divide by sqrt(2) after bias and residual (with act 0 - 2 only) */
     int32_t in_act;        /* 2 = LeakyReLU(in_slope) applied to X while it is split (models.py:89,142; Vocoder/vocoder.py:38,102);
                               ignored when Xh is given */
-    int32_t transpose_out; /* 1 = write Y[j][m] (time-major, row stride ldy >= M) */
+    int32_t transpose_out; /* 1 = write Y[j][m] (time-major, row stride ldy >= M); bias only: act 0, no div_sqrt2, res or Yh */
     int32_t yh_lrelu;      /* 1 = the image Yh holds LeakyReLU(in_slope)(y) (the consumer's in_act) while Y stays plain */
     int32_t n_prod;        /* 0 or 3 = f16x3 (fp32-accurate); 1 = h*h only */
     int32_t dh[AS_MAX_TAPS];   /* tap row offsets */
