@@ -6,9 +6,10 @@
 //   as_forward_test   ArtsSpeech.forward(step="test"), models.py:356-371, batched on packed frames
 //
 // This file holds no kernels: it is the host side that orders the launches of the other files of this library, owns the
-// batch geometry tables and hands out workspace memory.  One code path serves three passes over the same function:
-//   prepare (as_model_create: every weight the sequence touches is built and uploaded; nothing launched),
-//   count   (as_module_workspace_bytes: the bump allocator only adds up), and
+// batch geometry tables and hands out workspace memory.  One launch sequence per module serves three passes (Pass):
+//   count   (as_module_workspace_bytes, on placeholder arguments: the bump allocator only adds up; on a model that as_model_create
+//           is preparing, every weight the sequence touches is built and uploaded on the way),
+//   replay  (as_forward_test_finish: the first half's allocations in the caller's workspace, to find its results; nothing launched), and
 //   run     (kernels are enqueued; nothing is allocated, nothing synchronises once the geometry's tables exist).
 #include "common.h"
 #include "conv_gemm.h"
@@ -106,7 +107,7 @@ struct Vec {
 };
 struct LstmW {
     const GemmW* wih = nullptr; // [8H][I] both directions
-    float* bias = nullptr;      // [8H] b_ih + b_hh
+    const float* bias = nullptr; // [8H] b_ih + b_hh
     float* whh_t = nullptr;     // [2][H][4H]
     int H = 0;
 };
@@ -117,63 +118,97 @@ struct as_model {
     as_model_cfg cfg;
     int device = 0;
     std::unordered_map<std::string, HostT> raw;             // folded fp32 host tensors, reference names with plain ".weight"
-    mutable std::unordered_map<std::string, GemmW> gemm;    // filled while !frozen (as_model_create), read-only afterwards
+    struct Proj {                                           // a projection with its bias (and its fp32 matrix)
+        const GemmW* w = nullptr;
+        const float* bias = nullptr;
+        const float* w32 = nullptr;
+    };
+    // Every AdaIN1d fc layer fed by one style vector as ONE weight matrix [Mtot][K] (models.py:237: h = fc(s); gamma, beta =
+    // chunk(h)): row0[name] = a layer's first output row (gamma rows, then beta rows).
+    struct FcAll {
+        const GemmW* w = nullptr;
+        const float* bias = nullptr;
+        std::unordered_map<std::string, int> row0;
+        int Mtot = 0, K = 0;
+    };
+    // the weights laid out for the kernels: filled while !frozen (as_model_create), read-only afterwards
+    mutable std::unordered_map<std::string, GemmW> gemm;
     mutable std::unordered_map<std::string, Vec> vecs;
     mutable std::unordered_map<std::string, LstmW> lstms;
+    mutable std::unordered_map<std::string, Proj> projs;
+    mutable std::unordered_map<std::string, FcAll> fcalls;
     mutable DevPool pool{(size_t)256 << 20};
     mutable bool frozen = false;
     mutable int err = 0;
 
+    void fail_once(int code, const std::string& what = std::string()) const      // the first failure is the one reported
+    {
+        if (err) return;
+        err = code;
+        if (!what.empty()) fprintf(stderr, "artspeech_hip: %s\n", what.c_str());
+    }
+    // the step every getter shares: the entry under `key`; else, while !frozen, the one build(entry) makes, stored if it succeeds
+    template <class T, class F>
+    const T* cached(std::unordered_map<std::string, T>& map, const std::string& key, F&& build) const
+    {
+        auto it = map.find(key);
+        if (it != map.end()) return &it->second;
+        if (frozen) { fail_once(AS_EINVAL, "'" + key + "' was not prepared by as_model_create"); return nullptr; }
+        T v;
+        if (!build(v)) return nullptr;
+        return &(map[key] = std::move(v));
+    }
     bool has(const std::string& n) const { return raw.find(n) != raw.end(); }
     const HostT* host(const std::string& n) const
     {
         auto it = raw.find(n);
-        if (it == raw.end()) { if (!err) { err = AS_EINVAL; fprintf(stderr, "artspeech_hip: checkpoint has no tensor '%s'\n", n.c_str()); } return nullptr; }
+        if (it == raw.end()) { fail_once(AS_EINVAL, "checkpoint has no tensor '" + n + "'"); return nullptr; }
         return &it->second;
     }
     float* upload(const float* h, size_t n) const
     {
         float* d = static_cast<float*>(pool.alloc(n * sizeof(float)));
-        if (!d || hipMemcpy(d, h, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { if (!err) err = (int)hipErrorOutOfMemory; return nullptr; }
+        if (!d || hipMemcpy(d, h, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fail_once((int)hipErrorOutOfMemory); return nullptr; }
         return d;
     }
-    // a weight given as host data [G][Cout][Cin][T]
-    const GemmW* gemm_from(const std::string& key, const float* w, int G, int Cout, int Cin, int T, const float* w2 = nullptr, int Cin2 = 0) const
+    // a weight given as host data [G][Cout][Cin][T] (+ [G][Cout][Cin2] behind the taps), laid out and uploaded into g
+    bool gemm_image(GemmW& g, const float* w, int G, int Cout, int Cin, int T, const float* w2 = nullptr, int Cin2 = 0) const
     {
-        GemmW g;
         g.T = T; g.K = Cin; g.Kp = (Cin + 15) / 16 * 16; g.M = Cout; g.G = G; g.K2 = Cin2;
         const size_t bytes = as_prep_weight_f16x2_sc_bytes(G, Cout, Cin, T, Cin2);
         std::vector<uint16_t> img(bytes / 2);
-        if (as_prep_weight_f16x2_sc_host(w, w2, G, Cout, Cin, T, Cin2, img.data(), &g.scale) != AS_OK) { if (!err) err = AS_EINVAL; return nullptr; }
+        if (as_prep_weight_f16x2_sc_host(w, w2, G, Cout, Cin, T, Cin2, img.data(), &g.scale) != AS_OK) { fail_once(AS_EINVAL); return false; }
         g.wh = static_cast<uint16_t*>(pool.alloc(bytes));
-        if (!g.wh || hipMemcpy(g.wh, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { if (!err) err = (int)hipErrorOutOfMemory; return nullptr; }
+        if (!g.wh || hipMemcpy(g.wh, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { fail_once((int)hipErrorOutOfMemory); return false; }
         if (Cin == 1 && G == 1) {                                          // the direct kernel's fp32 image [T][Kp][M]
             std::vector<float> w32((size_t)T * g.Kp * Cout, 0.f);
             for (int m = 0; m < Cout; ++m)
                 for (int t = 0; t < T; ++t) w32[((size_t)t * g.Kp) * Cout + m] = w[(size_t)m * T + t];
             g.w32 = upload(w32.data(), w32.size());
         }
-        return &(gemm[key] = g);
+        return true;
+    }
+    const GemmW* gemm_at(const std::string& key, const std::vector<float>& w, int G, int Cout, int Cin) const     // (1x1)
+    {
+        return cached(gemm, key, [&](GemmW& g) { return gemm_image(g, w.data(), G, Cout, Cin, 1); });
     }
     // conv weights `names` ([Cout][Cin][k...] each, same shape) stacked as the weight sets of one grouped launch
     const GemmW* conv_stack(const std::vector<std::string>& names) const
     {
         std::string key = names[0];
         for (size_t i = 1; i < names.size(); ++i) key += "|" + names[i];
-        auto it = gemm.find(key);
-        if (it != gemm.end()) return &it->second;
-        if (frozen) { if (!err) { err = AS_EINVAL; fprintf(stderr, "artspeech_hip: '%s' was not prepared by as_model_create\n", key.c_str()); } return nullptr; }
-        const HostT* a = host(names[0] + ".weight");
-        if (!a) return nullptr;
-        const int Cout = a->dim(0), Cin = a->dim(1), T = (int)(a->numel() / ((size_t)Cout * Cin));
-        if (names.size() == 1) return gemm_from(key, a->v.data(), 1, Cout, Cin, T);
-        std::vector<float> w(a->v);
-        for (size_t i = 1; i < names.size(); ++i) {
-            const HostT* b = host(names[i] + ".weight");
-            if (!b || b->dims != a->dims) { if (!err) err = AS_EINVAL; return nullptr; }
-            w.insert(w.end(), b->v.begin(), b->v.end());
-        }
-        return gemm_from(key, w.data(), (int)names.size(), Cout, Cin, T);
+        return cached(gemm, key, [&](GemmW& g) {
+            const HostT* a = host(names[0] + ".weight");
+            if (!a) return false;
+            std::vector<float> w;
+            for (const std::string& n : names) {
+                const HostT* b = host(n + ".weight");
+                if (!b || b->dims != a->dims) { fail_once(AS_EINVAL); return false; }
+                w.insert(w.end(), b->v.begin(), b->v.end());
+            }
+            const int Cout = a->dim(0), Cin = a->dim(1), T = (int)(a->numel() / ((size_t)Cout * Cin));
+            return gemm_image(g, w.data(), (int)names.size(), Cout, Cin, T);
+        });
     }
     // the same with the blocks' learned shortcuts `sc_names` ([Cout][Cin2][1], no bias: models.py:77,123,178) behind the taps of every
     // weight set: the shortcut is evaluated by the launch of the block's last conv (ConvGemmArgs.Xh2 / K2)
@@ -181,23 +216,22 @@ struct as_model {
     {
         std::string key = "FOLD:";
         for (size_t i = 0; i < names.size(); ++i) key += names[i] + "+" + sc_names[i] + "|";
-        auto it = gemm.find(key);
-        if (it != gemm.end()) return &it->second;
-        if (frozen) { if (!err) { err = AS_EINVAL; fprintf(stderr, "artspeech_hip: '%s' was not prepared by as_model_create\n", key.c_str()); } return nullptr; }
-        const HostT *a = host(names[0] + ".weight"), *s0 = host(sc_names[0] + ".weight");
-        if (!a || !s0 || names.size() != sc_names.size()) { if (!err) err = AS_EINVAL; return nullptr; }
-        const int Cout = a->dim(0), Cin = a->dim(1), T = (int)(a->numel() / ((size_t)Cout * Cin)), Cin2 = s0->dim(1);
-        std::vector<float> w, w2;
-        for (size_t i = 0; i < names.size(); ++i) {
-            const HostT *b = host(names[i] + ".weight"), *sc = host(sc_names[i] + ".weight");
-            if (!b || !sc || b->dims != a->dims || sc->dims != s0->dims || sc->dim(0) != Cout || sc->numel() != (size_t)Cout * Cin2) {
-                if (!err) err = AS_EINVAL;
-                return nullptr;
+        return cached(gemm, key, [&](GemmW& g) {
+            const HostT *a = host(names[0] + ".weight"), *s0 = host(sc_names[0] + ".weight");
+            if (!a || !s0 || names.size() != sc_names.size()) { fail_once(AS_EINVAL); return false; }
+            const int Cout = a->dim(0), Cin = a->dim(1), T = (int)(a->numel() / ((size_t)Cout * Cin)), Cin2 = s0->dim(1);
+            std::vector<float> w, w2;
+            for (size_t i = 0; i < names.size(); ++i) {
+                const HostT *b = host(names[i] + ".weight"), *sc = host(sc_names[i] + ".weight");
+                if (!b || !sc || b->dims != a->dims || sc->dims != s0->dims || sc->dim(0) != Cout || sc->numel() != (size_t)Cout * Cin2) {
+                    fail_once(AS_EINVAL);
+                    return false;
+                }
+                w.insert(w.end(), b->v.begin(), b->v.end());
+                w2.insert(w2.end(), sc->v.begin(), sc->v.end());
             }
-            w.insert(w.end(), b->v.begin(), b->v.end());
-            w2.insert(w2.end(), sc->v.begin(), sc->v.end());
-        }
-        return gemm_from(key, w.data(), (int)names.size(), Cout, Cin, T, w2.data(), Cin2);
+            return gemm_image(g, w.data(), (int)names.size(), Cout, Cin, T, w2.data(), Cin2);
+        });
     }
     const GemmW* conv(const std::string& name, const std::string& name2 = std::string()) const
     {
@@ -208,22 +242,20 @@ struct as_model {
     {
         std::string key = names[0];
         for (size_t i = 1; i < names.size(); ++i) key += "|" + names[i];
-        auto it = vecs.find(key);
-        if (it != vecs.end()) return it->second.p;
-        if (frozen) { if (!err) { err = AS_EINVAL; fprintf(stderr, "artspeech_hip: '%s' was not prepared by as_model_create\n", key.c_str()); } return nullptr; }
-        std::vector<float> v;
-        size_t n0 = 0;
-        for (size_t i = 0; i < names.size(); ++i) {
-            const HostT* a = host(names[i]);
-            if (!a || (i && a->numel() != n0)) { if (!err) err = AS_EINVAL; return nullptr; }
-            n0 = a->numel();
-            v.insert(v.end(), a->v.begin(), a->v.end());
-        }
-        Vec d;
-        d.n = v.size();
-        d.p = upload(v.data(), v.size());
-        vecs[key] = d;
-        return d.p;
+        const Vec* r = cached(vecs, key, [&](Vec& d) {
+            std::vector<float> v;
+            size_t n0 = 0;
+            for (size_t i = 0; i < names.size(); ++i) {
+                const HostT* a = host(names[i]);
+                if (!a || (i && a->numel() != n0)) { fail_once(AS_EINVAL); return false; }
+                n0 = a->numel();
+                v.insert(v.end(), a->v.begin(), a->v.end());
+            }
+            d.n = v.size();
+            d.p = upload(v.data(), v.size());
+            return d.p != nullptr;
+        });
+        return r ? r->p : nullptr;
     }
     const float* vec(const std::string& name, const std::string& name2 = std::string()) const
     {
@@ -241,79 +273,47 @@ struct as_model {
         for (auto& x : n) x += ".bias";
         return vec_stack(n);
     }
+    static const GemmW* proj_out(const Proj* r, const float** bias_out, const float** w32_out = nullptr)
+    {
+        if (!r) return nullptr;
+        *bias_out = r->bias;
+        if (w32_out) *w32_out = r->w32;
+        return r->w;
+    }
     // q / k / v projections of one attention layer as one [3C] GEMM (RelTransformerEnc.py:128-133)
     const GemmW* qkv(const std::vector<std::string>& ps, const float** bias_out) const
     {
         std::string key = "QKV:";
         for (const std::string& q : ps) key += q + "|";
-        auto it = gemm.find(key);
-        if (it == gemm.end()) {
-            if (frozen) { if (!err) err = AS_EINVAL; return nullptr; }
+        return proj_out(cached(projs, key, [&](Proj& r) {
             std::vector<float> w, b;
-            int C = 0, G = 0;
-            for (const std::string& q : ps) {
-                ++G;
+            int C = 0;
+            for (const std::string& q : ps)
                 for (const char* n : {"q", "k", "v"}) {
                     const HostT* wt = host(q + ".conv_" + n + ".weight");
                     const HostT* bt = host(q + ".conv_" + n + ".bias");
-                    if (!wt || !bt) return nullptr;
+                    if (!wt || !bt) return false;
                     C = wt->dim(1);
                     w.insert(w.end(), wt->v.begin(), wt->v.end());
                     b.insert(b.end(), bt->v.begin(), bt->v.end());
                 }
-            }
-            if (!gemm_from(key, w.data(), G, 3 * C, C, 1)) return nullptr;
-            Vec d;
-            d.n = b.size();
-            d.p = upload(b.data(), b.size());
-            vecs[key] = d;
-            it = gemm.find(key);
-        }
-        *bias_out = vecs[key].p;
-        return &it->second;
-    }
-    // nn.LSTM(bidirectional): input projection of both directions as one GEMM, biases summed, W_hh transposed (SURVEY.md Appendix B)
-    const LstmW* lstm(const std::string& p) const
-    {
-        auto it = lstms.find(p);
-        if (it != lstms.end()) return &it->second;
-        if (frozen) { if (!err) err = AS_EINVAL; return nullptr; }
-        const HostT *wi = host(p + ".weight_ih_l0"), *wir = host(p + ".weight_ih_l0_reverse"), *wh = host(p + ".weight_hh_l0"),
-                    *whr = host(p + ".weight_hh_l0_reverse"), *bi = host(p + ".bias_ih_l0"), *bh = host(p + ".bias_hh_l0"),
-                    *bir = host(p + ".bias_ih_l0_reverse"), *bhr = host(p + ".bias_hh_l0_reverse");
-        if (!wi || !wir || !wh || !whr || !bi || !bh || !bir || !bhr) return nullptr;
-        LstmW L;
-        L.H = wh->dim(1);
-        const int H = L.H, I = wi->dim(1);
-        std::vector<float> w(wi->v);
-        w.insert(w.end(), wir->v.begin(), wir->v.end());
-        L.wih = gemm_from("LSTM:" + p, w.data(), 1, 8 * H, I, 1);
-        std::vector<float> b(8 * H);
-        for (int i = 0; i < 4 * H; ++i) { b[i] = bi->v[i] + bh->v[i]; b[4 * H + i] = bir->v[i] + bhr->v[i]; }
-        L.bias = upload(b.data(), b.size());
-        std::vector<float> t((size_t)2 * H * 4 * H);
-        for (int d = 0; d < 2; ++d) {
-            const std::vector<float>& src = d ? whr->v : wh->v;                   // [4H][H] -> [H][4H]
-            for (int r = 0; r < 4 * H; ++r)
-                for (int k = 0; k < H; ++k) t[((size_t)d * H + k) * 4 * H + r] = src[(size_t)r * H + k];
-        }
-        L.whh_t = upload(t.data(), t.size());
-        return &(lstms[p] = L);
+            r.w = gemm_at(key, w, (int)ps.size(), 3 * C, C);
+            r.bias = upload(b.data(), b.size());
+            return r.w && r.bias;
+        }), bias_out);
     }
     // input projections of several LSTMs of the same shape as the weight sets of one grouped launch
     const GemmW* lstm_wih_stack(const std::vector<std::string>& names, const float** bias_out) const
     {
         std::string key = "LSTMS:";
         for (const auto& n : names) key += n + "|";
-        auto it = gemm.find(key);
-        if (it == gemm.end()) {
-            if (frozen) { if (!err) err = AS_EINVAL; return nullptr; }
+        return proj_out(cached(projs, key, [&](Proj& r) {
             std::vector<float> w, b;
             int H = 0, I = 0;
             for (const auto& p : names) {
                 const HostT *wi = host(p + ".weight_ih_l0"), *wir = host(p + ".weight_ih_l0_reverse"), *bi = host(p + ".bias_ih_l0"),
                             *bh = host(p + ".bias_hh_l0"), *bir = host(p + ".bias_ih_l0_reverse"), *bhr = host(p + ".bias_hh_l0_reverse");
-                if (!wi || !wir || !bi || !bh || !bir || !bhr) return nullptr;
+                if (!wi || !wir || !bi || !bh || !bir || !bhr) return false;
                 H = wi->dim(0) / 4;
                 I = wi->dim(1);
                 w.insert(w.end(), wi->v.begin(), wi->v.end());
@@ -321,63 +321,63 @@ struct as_model {
                 for (int i = 0; i < 4 * H; ++i) b.push_back(bi->v[i] + bh->v[i]);
                 for (int i = 0; i < 4 * H; ++i) b.push_back(bir->v[i] + bhr->v[i]);
             }
-            if (!gemm_from(key, w.data(), (int)names.size(), 8 * H, I, 1)) return nullptr;
-            Vec d;
-            d.n = b.size();
-            d.p = upload(b.data(), b.size());
-            vecs[key] = d;
-            it = gemm.find(key);
-        }
-        *bias_out = vecs[key].p;
-        return &it->second;
+            r.w = gemm_at(key, w, (int)names.size(), 8 * H, I);
+            r.bias = upload(b.data(), b.size());
+            return r.w && r.bias;
+        }), bias_out);
     }
-    // Every AdaIN1d fc layer fed by one style vector as ONE weight matrix [Mtot][K] (models.py:237: h = fc(s); gamma, beta =
-    // chunk(h)): `norms` = (layer name, first style entry it reads, entries it reads) -- a layer that reads a slice of the style
-    // (models.py:499,597-599) gets zero columns elsewhere.  row0[name] = its first output row (gamma rows, then beta rows).
-    struct FcAll {
-        const GemmW* w = nullptr;
-        const float* bias = nullptr;
-        std::unordered_map<std::string, int> row0;
-        int Mtot = 0, K = 0;
-    };
-    mutable std::unordered_map<std::string, FcAll> fcalls;
+    // nn.LSTM(bidirectional): input projection of both directions as one GEMM, biases summed, W_hh transposed (SURVEY.md Appendix B)
+    const LstmW* lstm(const std::string& p) const
+    {
+        return cached(lstms, p, [&](LstmW& L) {
+            const HostT *wh = host(p + ".weight_hh_l0"), *whr = host(p + ".weight_hh_l0_reverse");
+            L.wih = lstm_wih_stack({p}, &L.bias);
+            if (!wh || !whr || !L.wih) return false;
+            const int H = L.H = wh->dim(1);
+            std::vector<float> t((size_t)2 * H * 4 * H);
+            for (int d = 0; d < 2; ++d) {
+                const std::vector<float>& src = d ? whr->v : wh->v;               // [4H][H] -> [H][4H]
+                for (int r = 0; r < 4 * H; ++r)
+                    for (int k = 0; k < H; ++k) t[((size_t)d * H + k) * 4 * H + r] = src[(size_t)r * H + k];
+            }
+            L.whh_t = upload(t.data(), t.size());
+            return true;
+        });
+    }
+    // `norms` = (layer name, first style entry it reads, entries it reads): a layer that reads a slice of the style
+    // (models.py:499,597-599) gets zero columns elsewhere
     struct NormSpec { std::string name; int off, S; };
     const FcAll* fc_all(const std::string& key, const std::vector<NormSpec>& norms, int K) const
     {
-        auto it = fcalls.find(key);
-        if (it != fcalls.end()) return &it->second;
-        if (frozen) { if (!err) err = AS_EINVAL; return nullptr; }
-        FcAll f;
-        f.K = K;
-        std::vector<float> w, b;
-        for (const auto& n : norms) {
-            const HostT *wt = host(n.name + ".fc.weight"), *bt = host(n.name + ".fc.bias");
-            if (!wt || !bt || wt->dim(1) != n.S || n.off + n.S > K) { if (!err) err = AS_EINVAL; return nullptr; }
-            const int M = wt->dim(0);
-            f.row0[n.name] = f.Mtot;
-            f.Mtot += M;
-            const size_t base = w.size();
-            w.resize(base + (size_t)M * K, 0.f);
-            for (int m = 0; m < M; ++m)
-                for (int k = 0; k < n.S; ++k) w[base + (size_t)m * K + n.off + k] = wt->v[(size_t)m * n.S + k];
-            b.insert(b.end(), bt->v.begin(), bt->v.end());
-        }
-        f.w = gemm_from("FCALL:" + key, w.data(), 1, f.Mtot, K, 1);
-        f.bias = upload(b.data(), b.size());
-        if (!f.w || !f.bias) return nullptr;
-        return &(fcalls[key] = f);
+        return cached(fcalls, key, [&](FcAll& f) {
+            f.K = K;
+            std::vector<float> w, b;
+            for (const auto& n : norms) {
+                const HostT *wt = host(n.name + ".fc.weight"), *bt = host(n.name + ".fc.bias");
+                if (!wt || !bt || wt->dim(1) != n.S || n.off + n.S > K) { fail_once(AS_EINVAL); return false; }
+                const int M = wt->dim(0);
+                f.row0[n.name] = f.Mtot;
+                f.Mtot += M;
+                const size_t base = w.size();
+                w.resize(base + (size_t)M * K, 0.f);
+                for (int m = 0; m < M; ++m)
+                    for (int k = 0; k < n.S; ++k) w[base + (size_t)m * K + n.off + k] = wt->v[(size_t)m * n.S + k];
+                b.insert(b.end(), bt->v.begin(), bt->v.end());
+            }
+            f.w = gemm_at("FCALL:" + key, w, 1, f.Mtot, K);
+            f.bias = upload(b.data(), b.size());
+            return f.w && f.bias;
+        });
     }
     // decoder.F0_conv (1 -> 32), N_conv (1 -> 32), EMA_conv (10 -> 64) (models.py:480-482, 1x1, weight-norm) as ONE block-diagonal
     // 1x1 conv from the stacked [F0; N; EMA] rows (12) to the 128 channels the decoder concatenates (models.py:503-505)
     const GemmW* fne(const float** bias_out, const float** w32_out = nullptr) const
     {
         const std::string key = "FNE:decoder";
-        auto it = gemm.find(key);
-        if (it == gemm.end()) {
-            if (frozen) { if (!err) err = AS_EINVAL; return nullptr; }
+        return proj_out(cached(projs, key, [&](Proj& r) {
             const HostT *f = host("decoder.F0_conv.weight"), *n = host("decoder.N_conv.weight"), *e = host("decoder.EMA_conv.weight");
             const HostT *fb = host("decoder.F0_conv.bias"), *nb = host("decoder.N_conv.bias"), *eb = host("decoder.EMA_conv.bias");
-            if (!f || !n || !e || !fb || !nb || !eb) return nullptr;
+            if (!f || !n || !e || !fb || !nb || !eb) return false;
             const int mf = f->dim(0), mn = n->dim(0), me = e->dim(0), ke = e->dim(1), K = 2 + ke, M = mf + mn + me;
             std::vector<float> w((size_t)M * K, 0.f), b;
             for (int m = 0; m < mf; ++m) w[(size_t)m * K + 0] = f->v[m];
@@ -387,20 +387,11 @@ struct as_model {
             b.insert(b.end(), fb->v.begin(), fb->v.end());
             b.insert(b.end(), nb->v.begin(), nb->v.end());
             b.insert(b.end(), eb->v.begin(), eb->v.end());
-            if (!gemm_from(key, w.data(), 1, M, K, 1)) return nullptr;
-            Vec d;
-            d.n = b.size();
-            d.p = upload(b.data(), b.size());
-            vecs[key] = d;
-            Vec d32;                                                     // the same matrix in fp32 [M][K] (as_pointwise_small_f32)
-            d32.n = w.size();
-            d32.p = upload(w.data(), w.size());
-            vecs[key + ":w32"] = d32;
-            it = gemm.find(key);
-        }
-        *bias_out = vecs[key].p;
-        if (w32_out) *w32_out = vecs[key + ":w32"].p;
-        return &it->second;
+            r.w = gemm_at(key, w, 1, M, K);
+            r.bias = upload(b.data(), b.size());
+            r.w32 = upload(w.data(), w.size());                          // the same matrix in fp32 [M][K] (as_pointwise_small_f32)
+            return r.w && r.bias && r.w32;
+        }), bias_out, w32_out);
     }
 };
 
@@ -539,14 +530,21 @@ struct Sched {
     int new_queue() { q.emplace_back(); return (int)q.size() - 1; }
 };
 
+// The passes over a launch sequence (see the top of this file)
+enum class Pass {
+    Count,                        // nothing behind the arena, geometry tables stay on the host, nothing launched
+    Replay,                       // the caller's workspace, nothing launched (as_forward_test_finish: where the first half left its results)
+    Run,                          // kernels are enqueued
+};
+const char* pass_name(Pass p) { return p == Pass::Count ? "count" : (p == Pass::Run ? "run" : "replay"); }
+
 struct Ctx {
     const as_model& m;
     as_plan& p;
     hipStream_t s;                // the stream launches go to (a side stream inside a Fork)
     char* base;                   // workspace (nullptr when counting)
     size_t cap, off = 0;
-    bool launch;                  // false: allocate only (count pass; prepare pass; the first half of as_forward_test_finish)
-    bool count;                   // true: nothing behind the arena, geometry tables stay on the host
+    Pass pass;
     int rc = 0;
     std::shared_ptr<Sched> sched; // launches are being recorded (inside a Fork of a serial, merging plan)
     int cur_q = -1;
@@ -568,8 +566,8 @@ struct Ctx {
         else as_prof_hint(f, b);
     }
 
-    Ctx(const as_model& m_, as_plan& p_, hipStream_t s_, void* ws, size_t ws_bytes, bool launch_, bool count_)
-        : m(m_), p(p_), s(s_), base(static_cast<char*>(ws)), cap(ws_bytes), launch(launch_), count(count_) {}
+    Ctx(const as_model& m_, as_plan& p_, hipStream_t s_, void* ws, size_t ws_bytes, Pass pass_)
+        : m(m_), p(p_), s(s_), base(static_cast<char*>(ws)), cap(ws_bytes), pass(pass_) {}
     void fail(int r, const char* what = nullptr, int line = 0)
     {
         if (!rc) {
@@ -581,90 +579,85 @@ struct Ctx {
     {
         const size_t o = off;
         off += align256(bytes ? bytes : 1);
-        if (launch && !count && getenv("AS_DEBUG_ALLOC")) fprintf(stderr, "artspeech_hip: arena %p + %zu : %zu bytes\n", (void*)base, o, bytes);
+        if (pass == Pass::Run && getenv("AS_DEBUG_ALLOC")) fprintf(stderr, "artspeech_hip: arena %p + %zu : %zu bytes\n", (void*)base, o, bytes);
         // counting: a non-null placeholder (never dereferenced: nothing launches), so that code which branches on "is there an operand
         // image" takes the branch the run takes (their workspace needs differ)
-        if (count) return reinterpret_cast<void*>((size_t)1 << 20) ;
+        if (pass == Pass::Count) return reinterpret_cast<void*>((size_t)1 << 20);
         if (off > cap) { fail(AS_ENOSPC); return nullptr; }
         return base + o;
     }
     float* f32(size_t n) { return static_cast<float*>(raw_alloc(n * sizeof(float))); }
     int32_t* i32(size_t n) { return static_cast<int32_t*>(raw_alloc(n * sizeof(int32_t))); }
     uint16_t* image(int K, int N) { return static_cast<uint16_t*>(raw_alloc(as_split_f16x2_bytes(K, N > 0 ? N : 1))); }
-    bool go() const { return launch && rc == 0 && m.err == 0; }
+    bool go() const { return pass == Pass::Run && rc == 0 && m.err == 0; }
 
-    // geometry (cached in the plan; device tables created on first real use: a blocking upload)
-    const Lay* lay(const std::vector<int>& widths, int H = 1)
+    // geometry (cached in the plan; device tables created on first real use: a blocking upload).  init fills a new layout (false: bad
+    // geometry); a layout is never evicted inside a call (as_plan::trim runs between calls)
+    template <class F>
+    const Lay* lay_at(std::pair<std::vector<int>, int> key, F&& init)
     {
-        auto key = std::make_pair(widths, H);
         auto it = p.lays.find(key);
-        Lay* L;
         if (it == p.lays.end()) {
             auto u = std::make_unique<Lay>();
-            L = u.get();
-            L->B = (int)widths.size();
-            L->H = H;
-            L->w = widths;
-            L->off.resize(L->B + 1);
-            L->off[0] = 0;
-            for (int b = 0; b < L->B; ++b) {
-                if (widths[b] < 0 || widths[b] > AS_META_MAX_W || H > AS_META_MAX_H) { fail(AS_EINVAL); return nullptr; }
-                L->off[b + 1] = L->off[b] + H * widths[b];
-                L->max_w = std::max(L->max_w, widths[b]);
-            }
-            L->N = L->off[L->B];
-            p.lays[key] = std::move(u);                        // (never evicted inside a call: as_plan::trim runs between calls)
-        } else {
-            L = it->second.get();
+            if (!init(*u)) { fail(AS_EINVAL); return nullptr; }
+            it = p.lays.emplace(std::move(key), std::move(u)).first;
         }
-        if (!count && launch && !L->d_off) {
-            L->d_w = static_cast<int32_t*>(p.pool.alloc((L->B + 1) * sizeof(int32_t)));
-            L->d_off = static_cast<int32_t*>(p.pool.alloc((L->B + 1) * sizeof(int32_t)));
-            if (!L->d_w || !L->d_off || hipMemcpy(L->d_w, L->w.data(), L->B * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(L->d_off, L->off.data(), (L->B + 1) * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-                fail((int)hipErrorOutOfMemory);
-                return nullptr;
+        return tables(it->second.get()) ? it->second.get() : nullptr;
+    }
+    const Lay* lay(const std::vector<int>& widths, int H = 1)
+    {
+        return lay_at({widths, H}, [&](Lay& L) {
+            L.B = (int)widths.size();
+            L.H = H;
+            L.w = widths;
+            L.off.assign(L.B + 1, 0);
+            for (int b = 0; b < L.B; ++b) {
+                if (widths[b] < 0 || widths[b] > AS_META_MAX_W || H > AS_META_MAX_H) return false;
+                L.off[b + 1] = L.off[b] + H * widths[b];
+                L.max_w = std::max(L.max_w, widths[b]);
             }
-        }
-        return L;
+            L.N = L.off[L.B];
+            return true;
+        });
     }
     // capacity layout `kind` (AsDynGeo: 0 half rate, 1 mel rate, 2 / 3 the batch three times) of B utterances in cap1 half-rate columns
     const Lay* dyn_lay(int kind, int B, int cap1)
     {
         if (kind < 0 || kind > 3 || B < 1 || cap1 < 1 || (double)cap1 * 6.0 > (double)AS_META_MAX_W) { fail(AS_EINVAL); return nullptr; }
-        auto key = std::make_pair(std::vector<int>{-1 - kind, B, cap1}, 1);
-        auto it = p.lays.find(key);
-        Lay* L;
-        if (it == p.lays.end()) {
-            auto u = std::make_unique<Lay>();
-            L = u.get();
-            L->dyn = true; L->dyn_kind = kind; L->dyn_B = B; L->cap1 = cap1;
-            L->B = kind < 2 ? B : 3 * B;
-            L->H = 1;
-            L->max_w = cap1 * ((kind & 1) ? 2 : 1);
-            L->N = L->max_w * (kind < 2 ? 1 : 3);
-            p.lays[key] = std::move(u);
-        } else {
-            L = it->second.get();
-        }
-        if (!count && launch && !L->d_off) {
-            L->d_w = static_cast<int32_t*>(p.pool.alloc((L->B + 1) * sizeof(int32_t)));
-            L->d_off = static_cast<int32_t*>(p.pool.alloc((L->B + 1) * sizeof(int32_t)));
+        return lay_at({{-1 - kind, B, cap1}, 1}, [&](Lay& L) {
+            L.dyn = true; L.dyn_kind = kind; L.dyn_B = B; L.cap1 = cap1;
+            L.B = kind < 2 ? B : 3 * B;
+            L.max_w = cap1 * ((kind & 1) ? 2 : 1);
+            L.N = L.max_w * (kind < 2 ? 1 : 3);
+            return true;
+        });
+    }
+    // L's device tables, made on the first run that uses L: d_w and d_off (B + 1 entries), uploaded at once (a blocking copy); a
+    // capacity layout's instead hold what every call's as_dyn_geometry_launch writes, with d_meta, d_nvalid and (kind 2) src3
+    bool tables(Lay* L)
+    {
+        if (pass != Pass::Run || L->d_off) return true;
+        const auto i32 = [&](size_t n) { return static_cast<int32_t*>(p.pool.alloc(n * sizeof(int32_t))); };
+        int32_t *d_w = i32(L->B + 1), *d_off = i32(L->B + 1);
+        bool ok = d_w && d_off;
+        if (ok && L->dyn) {
             L->d_meta = static_cast<uint64_t*>(p.pool.alloc((size_t)L->N * sizeof(uint64_t)));
-            L->d_nvalid = static_cast<int32_t*>(p.pool.alloc(sizeof(int32_t)));
-            int32_t* src3 = kind == 2 ? static_cast<int32_t*>(p.pool.alloc((size_t)L->B * sizeof(int32_t))) : nullptr;
-            if (!L->d_w || !L->d_off || !L->d_meta || !L->d_nvalid || (kind == 2 && !src3)) {
-                L->d_off = nullptr;
-                fail((int)hipErrorOutOfMemory);
-                return nullptr;
-            }
-            if (src3) L->tabs["src3"] = src3;
+            L->d_nvalid = i32(1);
+            int32_t* src3 = L->dyn_kind == 2 ? i32(L->B) : nullptr;
+            ok = L->d_meta && L->d_nvalid && (L->dyn_kind != 2 || src3);
+            if (ok && src3) L->tabs["src3"] = src3;
+        } else if (ok) {
+            ok = hipMemcpy(d_w, L->w.data(), L->B * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess &&
+                 hipMemcpy(d_off, L->off.data(), (L->B + 1) * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
         }
-        return L;
+        if (!ok) { fail((int)hipErrorOutOfMemory); return false; }
+        L->d_w = d_w;
+        L->d_off = d_off;
+        return true;
     }
     const uint64_t* meta(const Lay* L)
     {
-        if (!L || count || !launch) return nullptr;
+        if (!L || pass != Pass::Run) return nullptr;
         if (L->dyn) return L->d_meta;                              // (written by the call's as_dyn_geometry_launch)
         Lay* M = const_cast<Lay*>(L);
         if (!M->d_meta) {
@@ -679,7 +672,7 @@ struct Ctx {
     template <typename F>
     const int32_t* itable(const Lay* L, const std::string& key, F&& build)
     {
-        if (!L || count || !launch) return nullptr;
+        if (!L || pass != Pass::Run) return nullptr;
         Lay* M = const_cast<Lay*>(L);
         auto it = M->tabs.find(key);
         if (it != M->tabs.end()) return it->second;
@@ -692,7 +685,7 @@ struct Ctx {
     void* lstm_xchg(int n_jobs, int B, size_t* bytes)
     {
         *bytes = 0;
-        if (count || !launch) return nullptr;
+        if (pass != Pass::Run) return nullptr;
         const size_t need = as_bilstm_cluster_bytes(n_jobs, B);
         if (p.lstm_xchg_bytes < need) {
             void* d = p.pool.alloc(need);
@@ -1139,8 +1132,8 @@ void conv_impl(Ctx& c, const GemmW* w, const float* X, int ldx, const uint16_t* 
     q.Xh2 = o.K2 ? reinterpret_cast<const uint16_t*>(16) : nullptr;
     const size_t wsb = rec ? as_conv_gemm_multi_workspace_bytes(&q) : as_conv_gemm_workspace_bytes(&q);
     if (getenv("AS_DEBUG_ALLOC"))
-        fprintf(stderr, "artspeech_hip: conv %s M%d N%d K%d T%d G%d img%d -> ws %zu (arena at %zu)\n", c.count ? "count" : (c.launch ? "run" : "replay"), a.M,
-                a.N, a.K, a.T, a.n_groups, (int)in_image, wsb, c.off);
+        fprintf(stderr, "artspeech_hip: conv %s M%d N%d K%d T%d G%d img%d -> ws %zu (arena at %zu)\n", pass_name(c.pass), a.M, a.N, a.K, a.T,
+                a.n_groups, (int)in_image, wsb, c.off);
     a.ws = wsb ? c.raw_alloc(wsb) : nullptr;
     a.ws_bytes = wsb;
     if (!c.go()) return;
@@ -1210,7 +1203,7 @@ struct FcOut {
     const as_model::FcAll* f = nullptr;
     float* gbT = nullptr;
     int B = 0;
-    Norm norm(const std::string& name, int group_stride_rows = 0, const int32_t* gb_off = nullptr) const
+    Norm norm(const std::string& name, const int32_t* gb_off = nullptr) const
     {
         Norm n;
         auto it = f ? f->row0.find(name) : decltype(f->row0.begin())();
@@ -1218,7 +1211,6 @@ struct FcOut {
         n.gb = gbT ? gbT + (size_t)it->second * B : nullptr;
         n.gb_off = gb_off;
         n.gb_sc = B;
-        (void)group_stride_rows;
         return n;
     }
 };
@@ -2159,7 +2151,7 @@ PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
 {
     const as_model& m = c.m;
     PhaseA A;
-    const int C = m.cfg.hidden_dim, B = batch->B, n_mels = m.cfg.n_mels, sd2 = 2 * m.cfg.style_dim;
+    const int B = batch->B, n_mels = m.cfg.n_mels, sd2 = 2 * m.cfg.style_dim;
     A.tok = c.lay(vec_of(batch->tok_lens, B));
     A.ref = c.lay(vec_of(batch->ref_lens, B));
     if (!A.tok || !A.ref) return A;
@@ -2240,7 +2232,6 @@ PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
     // (with the frame counts given nobody reads this half's copy: the second half computes durations, offsets and the frame -> token map)
     // (... and so does a call under a frame capacity, as_forward_io.frame_cap)
     if (!batch->frames && io->frame_cap <= 0) RUN(c, as_durations_f32(A.duration, io->forced_dur, A.tok->d_off, B, A.dur_i, A.frame_off, nullptr, 0, c.s));
-    (void)C;
     return A;
 }
 
@@ -2353,22 +2344,190 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
         if (io->N) copy_rows(c, io->N, io->ld_pred, fne + (size_t)N2, N2, 1, N2);
         if (io->EMA) copy_rows(c, io->EMA, io->ld_pred, fne + (size_t)2 * N2, N2, 10, N2);
     }
-    (void)n_mels;
 }
 
-void outputs_a(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_io* io)
+void outputs_a(Ctx& c, const PhaseA& A, const as_forward_io* io)
 {
     if (!c.go()) return;
     const int C = c.m.cfg.hidden_dim, Nt = A.tok->N, Nr = A.ref->N;
     if (io->feat12) copy_rows(c, io->feat12, io->ld_feat, A.feat12, Nr, 12, Nr);
     if (io->t_en) copy_rows(c, io->t_en, io->ld_en, A.t_en, A.ld_en, C, Nt);
     if (io->a_en) copy_rows(c, io->a_en, io->ld_en, A.a_en, A.ld_en, C, Nt);
-    (void)batch;
 }
 
 bool io_ok(const as_forward_io* io, bool need_out)
 {
     return io && io->tokens && io->mel && io->f0_raw && io->ema_raw && (!need_out || io->mel_out);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// the module entry points' launch sequences: one function both sizes the workspace (as_module_workspace_bytes: placeholder
+// arguments, ANY / ANY_LD) and runs.  A returned AS_EINVAL: an argument is wrong, nothing was launched.
+// ------------------------------------------------------------------------------------------------------------------
+// (count pass) never dereferenced, non-null and of unbounded leading dimension, so that every branch the run takes is taken
+struct Any {
+    template <class T> operator T*() const { return reinterpret_cast<T*>(16); }
+};
+constexpr Any ANY;
+constexpr int ANY_LD = 1 << 30;
+
+int encoder_module(Ctx& c, const as_batch* batch, int which, const int32_t* tokens, float* out, int ldo)
+{
+    const Lay* lay = c.lay(vec_of(batch->tok_lens, batch->B));
+    if (!lay || ldo < lay->N) return AS_EINVAL;
+    // the three encoders exist as ONE stacked weight set (they always run together in the path): a single one is asked for by
+    // running all of them and returning its columns
+    EncOut eo;
+    rel_encoder_multi(c, path_encoders(), tokens, lay, &eo, [](int) {});
+    const int g = which == 0 ? ENC_TEXT : (which == 1 ? ENC_ARTS : ENC_DUR);
+    copy_rows(c, out, ldo, eo.y[g], eo.ld[g], c.m.cfg.hidden_dim, lay->N);
+    return AS_OK;
+}
+
+int style_module(Ctx& c, const as_batch* batch, const float* mel, int ldm, const float* f0_raw, const float* ema_raw, int lde, float* feat12,
+                 int ldf, float* style)
+{
+    const Lay* ref = c.lay(vec_of(batch->ref_lens, batch->B));
+    if (!ref || ldm < ref->N || lde < ref->N || ldf < ref->N) return AS_EINVAL;
+    const float* stats = c.m.vec("__stats24");
+    const int n_mels = c.m.cfg.n_mels;
+    RUN(c, as_ref_features_f32(mel, ldm, n_mels, f0_raw, ema_raw, lde, ref->N, stats, feat12, ldf, c.s));
+    const StyleIn si = style_inputs(c, feat12, ldf, mel, ldm, ref);
+    if (si.l1) for (int t = 0; t < 4; ++t) style_tower(c, t, si, style);
+    return AS_OK;
+}
+
+int duration_module(Ctx& c, const as_batch* batch, const int32_t* tokens, const float* ema_ext, int lde, float* duration)
+{
+    const Lay *tok = c.lay(vec_of(batch->tok_lens, batch->B)), *ref = c.lay(vec_of(batch->ref_lens, batch->B));
+    if (!tok || !ref || lde < ref->N) return AS_EINVAL;
+    float* ds = c.f32((size_t)batch->B * (c.m.cfg.style_dim / 4));
+    duration_style(c, ema_ext, lde, ref, ds);
+    EncOut eo;
+    rel_encoder_multi(c, path_encoders(), tokens, tok, &eo, [](int) {});
+    duration_tail(c, eo.y[ENC_DUR], ds, tok, duration);
+    return AS_OK;
+}
+
+int arts_module(Ctx& c, const as_batch* batch, const float* a_ens, int lda, const float* style, float* F0, float* N, float* EMA, int ldp)
+{
+    const Lay* lay = c.lay(vec_of(batch->frames, batch->B));
+    if (!lay || lda < lay->N || ldp < 2 * lay->N) return AS_EINVAL;
+    const int N2 = 2 * lay->N, sd2 = 2 * c.m.cfg.style_dim;
+    const FcOut fc = adain_fc_all(c, "style", style_norms(c.m), style, sd2, sd2, batch->B);
+    float* fne = c.f32((size_t)12 * std::max(N2, 1));
+    arts_predictor(c, a_ens, lda, lay, fc, fne, N2);
+    copy_rows(c, F0, ldp, fne, N2, 1, N2);
+    copy_rows(c, N, ldp, fne + (size_t)N2, N2, 1, N2);
+    copy_rows(c, EMA, ldp, fne + (size_t)2 * N2, N2, 10, N2);
+    return AS_OK;
+}
+
+int decoder_module(Ctx& c, const as_batch* batch, const float* asr, int lda, const float* style, const float* F0, const float* N,
+                   const float* EMA, int ldp, float* mel, int ldo)
+{
+    const Lay* lay = c.lay(vec_of(batch->frames, batch->B));
+    if (!lay) return AS_EINVAL;
+    const Lay* lay2 = c.scaled(lay, 2);
+    if (!lay2 || lda < lay->N || ldp < lay2->N || ldo < lay2->N) return AS_EINVAL;
+    // nearest x2 of the text encoding (models.py:500) = a column gather with every frame as its own token
+    int32_t* ident = c.i32((size_t)std::max(lay->N, 1));
+    if (c.go() && lay->N > 0) {
+        std::vector<int32_t> h(lay->N);
+        for (int i = 0; i < lay->N; ++i) h[i] = i;
+        if (hipMemcpyAsync(ident, h.data(), (size_t)lay->N * 4, hipMemcpyHostToDevice, c.s) != hipSuccess || hipStreamSynchronize(c.s) != hipSuccess)
+            c.fail((int)hipErrorUnknown);
+    }
+    const int C = c.m.cfg.hidden_dim, N2 = lay2->N, sd2 = 2 * c.m.cfg.style_dim;
+    float* x0 = c.f32((size_t)(C + 128) * std::max(N2, 1));
+    RUN(c, as_expand_f32(asr, lda, C, ident, lay->N, 2, x0, N2, c.s));
+    float* fne = c.f32((size_t)12 * std::max(N2, 1));
+    copy_rows(c, fne, N2, F0, ldp, 1, N2);
+    copy_rows(c, fne + (size_t)N2, N2, N, ldp, 1, N2);
+    copy_rows(c, fne + (size_t)2 * N2, N2, EMA, ldp, 10, N2);
+    const FcOut fc = adain_fc_all(c, "style", style_norms(c.m), style, sd2, sd2, batch->B);
+    decoder(c, decoder_pre(c, x0, lay2), x0, lay2, fne, N2, fc, mel, ldo);
+    return AS_OK;
+}
+
+const as_forward_io* dummy_io()
+{
+    static const as_forward_io io = [] {
+        as_forward_io d;
+        memset(&d, 0, sizeof(d));
+        d.tokens = ANY;
+        d.mel = d.f0_raw = d.ema_raw = ANY;
+        d.mel_out = ANY;
+        d.ld_mel = d.ld_ema = d.ld_out = d.ld_pred = ANY_LD;
+        return d;
+    }();
+    return &io;
+}
+
+// the sequence of one module with nothing behind it: workspace bytes (and, on a model being created, the weights it touches)
+size_t count_module(const as_model* m, as_plan* p, int module, const as_batch* batch)
+{
+    // the batch fields every module reads: tok_lens, ref_lens, frames (AS_MOD_FORWARD_B_CAP: capacities)
+    static const bool need[8][3] = {{1, 1, 0}, {1, 1, 1}, {1, 0, 0}, {0, 1, 0}, {1, 1, 0}, {0, 0, 1}, {0, 0, 1}, {1, 1, 1}};
+    if (module < 0 || module > AS_MOD_FORWARD_B_CAP || !batch_ok(batch, need[module][0], need[module][1], need[module][2])) return 0;
+    Ctx c(*m, *p, nullptr, nullptr, 0, Pass::Count);
+    int rc = AS_OK;
+    switch (module) {
+    case AS_MOD_ENCODER: rc = encoder_module(c, batch, 0, ANY, ANY, ANY_LD); break;
+    case AS_MOD_STYLE: rc = style_module(c, batch, ANY, ANY_LD, ANY, ANY, ANY_LD, ANY, ANY_LD, ANY); break;
+    case AS_MOD_DURATION: rc = duration_module(c, batch, ANY, ANY, ANY_LD, ANY); break;
+    case AS_MOD_ARTS: rc = arts_module(c, batch, ANY, ANY_LD, ANY, ANY, ANY, ANY, ANY_LD); break;
+    case AS_MOD_DECODER: rc = decoder_module(c, batch, ANY, ANY_LD, ANY, ANY, ANY, ANY, ANY_LD, ANY, ANY_LD); break;
+    case AS_MOD_FORWARD_A: forward_a(c, batch, dummy_io()); break;
+    default: {                                                           // workspace B: the second half, behind a first half in workspace A
+        as_forward_io io = *dummy_io();
+        as_batch b = *batch;
+        if (module == AS_MOD_FORWARD_B_CAP) {                            // batch->frames = capacities: their sum is the call's frame_cap
+            long cap = 0;
+            for (int i = 0; i < b.B; ++i) cap += std::max(b.frames[i], 0);
+            if (cap < 1 || cap > (1 << 28)) return 0;
+            io.frame_cap = (int32_t)cap;
+            b.frames = nullptr;
+        }
+        Ctx ca(*m, *p, nullptr, nullptr, 0, Pass::Count);
+        const PhaseA A = forward_a(ca, &b, &io);
+        if (ca.rc || !A.tok) return 0;
+        forward_b(c, A, &b, &io);
+    }
+    }
+    return rc || c.rc ? 0 : c.off + 256;
+}
+
+bool misaligned(const void* ws) { return (reinterpret_cast<uintptr_t>(ws) & 255) != 0; }
+
+struct Call {                     // common prologue of the entry points; `trim`: as_plan::trim may drop layouts first
+    Ctx c;
+    Call(const as_model* m, as_plan* p, void* ws, size_t bytes, as_stream_t stream, Pass pass, bool trim)
+        : c(*m, *p, static_cast<hipStream_t>(stream), ws, bytes, pass)
+    {
+        if (pass == Pass::Run) {
+            p->next_event = 0;
+            const int t = trim ? p->trim(static_cast<hipStream_t>(stream)) : AS_OK;
+            if (t != AS_OK) c.fail(t);
+            p->note_stream(static_cast<hipStream_t>(stream));
+            if (as_status_peek()) c.fail(AS_EDEVICE);      // a kernel of earlier work reported a failure: sticky until as_device_status(1)
+        }
+        if (misaligned(ws)) c.fail(AS_EINVAL);
+    }
+    int done(int r = AS_OK) const { return r ? r : (c.rc ? c.rc : c.m.err); }     // r: what the sequence returned
+};
+
+// nothing may unwind through the C boundary
+template <class F>
+int abi(F&& f)
+{
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return (int)hipErrorOutOfMemory;
+    } catch (...) {
+        return AS_EINVAL;
+    }
 }
 
 }  // namespace
@@ -2494,8 +2653,6 @@ bool fold(const std::unordered_map<std::string, HostT>& in, std::unordered_map<s
     return true;
 }
 
-size_t count_module(const as_model* m, as_plan* p, int module, const as_batch* batch, bool prepare);
-
 }  // namespace
 
 namespace {
@@ -2592,7 +2749,7 @@ static int model_create(const void* blob_host, size_t blob_bytes, const as_model
     if (rc != AS_OK) return rc;
     const int32_t tl[1] = {8}, rl[1] = {96}, fr[1] = {12};
     as_batch b = {1, tl, rl, fr};
-    for (int mod : {AS_MOD_FORWARD_A, AS_MOD_FORWARD_B}) count_module(m, plan, mod, &b, true);
+    for (int mod : {AS_MOD_FORWARD_A, AS_MOD_FORWARD_B}) count_module(m, plan, mod, &b);
     as_plan_destroy(plan);
     if (m->err) return m->err;
     m->frozen = true;
@@ -2606,13 +2763,7 @@ extern "C" int as_model_create(const void* blob_host, size_t blob_bytes, const a
     if (!blob_host || !cfg || !out || cfg->hidden_dim <= 0 || cfg->hidden_dim % 16 || cfg->dim_in <= 0 || cfg->style_dim <= 0 || cfg->style_dim % 4 ||
         cfg->n_mels <= 0)
         return AS_EINVAL;
-    try {                                                                // nothing may unwind through the C boundary
-        return model_create(blob_host, blob_bytes, cfg, out);
-    } catch (const std::bad_alloc&) {
-        return (int)hipErrorOutOfMemory;
-    } catch (...) {
-        return AS_EINVAL;
-    }
+    return abi([&] { return model_create(blob_host, blob_bytes, cfg, out); });
 }
 
 extern "C" int as_model_destroy(as_model* m)
@@ -2691,134 +2842,11 @@ extern "C" int as_plan_phase_ms(as_plan* p, float* ms, int n)
     return AS_OK;
 }
 
-namespace {
-
-const as_forward_io* dummy_io()
-{
-    static as_forward_io io;
-    static bool init = false;
-    if (!init) {
-        memset(&io, 0, sizeof(io));
-        io.tokens = reinterpret_cast<const int32_t*>(16);
-        io.mel = io.f0_raw = io.ema_raw = reinterpret_cast<const float*>(16);
-        io.mel_out = reinterpret_cast<float*>(16);
-        io.ld_mel = io.ld_ema = io.ld_out = io.ld_pred = 1 << 30;
-        init = true;
-    }
-    return &io;
-}
-
-// the sequence of one module with nothing behind it: workspace bytes (and, for as_model_create, the weights it touches)
-size_t count_module(const as_model* m, as_plan* p, int module, const as_batch* batch, bool prepare)
-{
-    Ctx c(*m, *p, nullptr, nullptr, 0, false, true);
-    (void)prepare;
-    const as_forward_io* io = dummy_io();
-    const int B = batch->B, C = m->cfg.hidden_dim;
-    switch (module) {
-    case AS_MOD_FORWARD_A:
-        if (!batch_ok(batch, true, true, false)) return 0;
-        forward_a(c, batch, io);
-        break;
-    case AS_MOD_FORWARD_B: {
-        if (!batch_ok(batch, true, true, true)) return 0;
-        Ctx ca(*m, *p, nullptr, nullptr, 0, false, true);
-        const PhaseA A = forward_a(ca, batch, io);
-        if (ca.rc || !A.tok) return 0;
-        forward_b(c, A, batch, io);
-        break;
-    }
-    case AS_MOD_FORWARD_B_CAP: {                                         // batch->frames = capacities: their sum is the call's frame_cap
-        if (!batch_ok(batch, true, true, true)) return 0;
-        long cap = 0;
-        for (int b = 0; b < B; ++b) cap += std::max(batch->frames[b], 0);
-        if (cap < 1 || cap > (1 << 28)) return 0;
-        as_forward_io ioc = *io;
-        ioc.frame_cap = (int32_t)cap;
-        as_batch b2 = *batch;
-        b2.frames = nullptr;
-        Ctx ca(*m, *p, nullptr, nullptr, 0, false, true);
-        const PhaseA A = forward_a(ca, &b2, &ioc);
-        if (ca.rc || !A.tok) return 0;
-        forward_b(c, A, &b2, &ioc);
-        break;
-    }
-    case AS_MOD_ENCODER: {
-        if (!batch_ok(batch, true, false, false)) return 0;
-        const Lay* lay = c.lay(vec_of(batch->tok_lens, B));
-        EncOut eo;
-        if (lay) rel_encoder_multi(c, path_encoders(), io->tokens, lay, &eo, [](int) {});
-        break;
-    }
-    case AS_MOD_STYLE: {
-        if (!batch_ok(batch, false, true, false)) return 0;
-        const Lay* ref = c.lay(vec_of(batch->ref_lens, B));
-        if (!ref) return 0;
-        const StyleIn si = style_inputs(c, nullptr, ref->N, nullptr, ref->N, ref);
-        if (si.l1) for (int t = 0; t < 4; ++t) style_tower(c, t, si, nullptr);
-        break;
-    }
-    case AS_MOD_DURATION: {
-        if (!batch_ok(batch, true, true, false)) return 0;
-        const Lay *tok = c.lay(vec_of(batch->tok_lens, B)), *ref = c.lay(vec_of(batch->ref_lens, B));
-        if (!tok || !ref) return 0;
-        float* ds = c.f32((size_t)B * (m->cfg.style_dim / 4));
-        duration_style(c, nullptr, ref->N, ref, ds);
-        EncOut eo;
-        rel_encoder_multi(c, path_encoders(), io->tokens, tok, &eo, [](int) {});
-        duration_tail(c, eo.y[ENC_DUR], ds, tok);
-        break;
-    }
-    case AS_MOD_ARTS: {
-        if (!batch_ok(batch, false, false, true)) return 0;
-        const Lay* lay = c.lay(vec_of(batch->frames, B));
-        if (!lay) return 0;
-        const FcOut fc = adain_fc_all(c, "style", style_norms(*m), nullptr, 2 * m->cfg.style_dim, 2 * m->cfg.style_dim, B);
-        float* fne = c.f32((size_t)12 * std::max(2 * lay->N, 1));
-        arts_predictor(c, nullptr, lay->N, lay, fc, fne, 2 * lay->N);
-        break;
-    }
-    case AS_MOD_DECODER: {
-        if (!batch_ok(batch, false, false, true)) return 0;
-        const Lay* lay = c.lay(vec_of(batch->frames, B));
-        if (!lay) return 0;
-        const Lay* lay2 = c.scaled(lay, 2);
-        c.i32((size_t)std::max(lay->N, 1));
-        float* x0 = c.f32((size_t)(C + 128) * std::max(lay2->N, 1));
-        float* fne = c.f32((size_t)12 * std::max(lay2->N, 1));
-        const FcOut fc = adain_fc_all(c, "style", style_norms(*m), nullptr, 2 * m->cfg.style_dim, 2 * m->cfg.style_dim, B);
-        decoder(c, decoder_pre(c, x0, lay2), x0, lay2, fne, lay2->N, fc, nullptr, lay2->N);
-        break;
-    }
-    default: return 0;
-    }
-    return c.rc ? 0 : c.off + 256;
-}
-
-struct Call {                     // common prologue of the run entry points
-    Ctx c;
-    Call(const as_model* m, as_plan* p, void* ws, size_t bytes, as_stream_t stream, bool launch = true, bool first = true)
-        : c(*m, *p, static_cast<hipStream_t>(stream), ws, bytes, launch, false)
-    {
-        if (launch) {
-            p->next_event = 0;
-            const int t = first ? p->trim(static_cast<hipStream_t>(stream)) : AS_OK;   // (as_forward_test_finish continues _begin's call: it needs _begin's layouts)
-            if (t != AS_OK) c.fail(t);
-            p->note_stream(static_cast<hipStream_t>(stream));
-            if (as_status_peek()) c.fail(AS_EDEVICE);      // a kernel of earlier work reported a failure: sticky until as_device_status(1)
-        }
-        if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) c.fail(AS_EINVAL);
-    }
-    int done() const { return c.rc ? c.rc : c.m.err; }
-};
-
-}  // namespace
-
 extern "C" size_t as_module_workspace_bytes(const as_model* m, as_plan* p, int module, const as_batch* batch)
 {
     if (!m || !p || !batch) return 0;
     // (no trim here: a caller asks for workspace B's size between as_forward_test_begin and _finish, which share layouts)
-    return count_module(m, p, module, batch, false);
+    return count_module(m, p, module, batch);
 }
 
 extern "C" int as_plan_set_layout_cap(as_plan* p, int max_layouts)
@@ -2839,190 +2867,114 @@ extern "C" int as_plan_reset_layouts(as_plan* p)
 
 extern "C" int as_encoder_forward(const as_model* m, as_plan* p, int which, const as_batch* batch, const int32_t* tokens, float* out, int ldo,
                                   void* ws, size_t ws_bytes, as_stream_t stream)
-try {                                                                    // nothing may unwind through the C boundary
-    if (!m || !p || !batch_ok(batch, true, false, false) || !tokens || !out || which < 0 || which > 2) return AS_EINVAL;
-    Call k(m, p, ws, ws_bytes, stream);
-    Ctx& c = k.c;
-    const Lay* lay = c.lay(vec_of(batch->tok_lens, batch->B));
-    if (!lay || ldo < lay->N) return AS_EINVAL;
-    // the three encoders exist as ONE stacked weight set (they always run together in the path): a single one is asked for by
-    // running all of them and returning its columns
-    EncOut eo;
-    rel_encoder_multi(c, path_encoders(), tokens, lay, &eo, [](int) {});
-    const int g = which == 0 ? ENC_TEXT : (which == 1 ? ENC_ARTS : ENC_DUR);
-    copy_rows(c, out, ldo, eo.y[g], eo.ld[g], m->cfg.hidden_dim, lay->N);
-    return k.done();
-} catch (const std::bad_alloc&) {
-    return (int)hipErrorOutOfMemory;
-} catch (...) {
-    return AS_EINVAL;
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, true, false, false) || !tokens || !out || which < 0 || which > 2) return AS_EINVAL;
+        Call k(m, p, ws, ws_bytes, stream, Pass::Run, true);
+        return k.done(encoder_module(k.c, batch, which, tokens, out, ldo));
+    });
 }
 
 extern "C" int as_style_forward(const as_model* m, as_plan* p, const as_batch* batch, const float* mel, int ldm, const float* f0_raw,
                                 const float* ema_raw, int lde, float* feat12, int ldf, float* style, void* ws, size_t ws_bytes, as_stream_t stream)
-try {                                                                    // nothing may unwind through the C boundary
-    if (!m || !p || !batch_ok(batch, false, true, false) || !mel || !f0_raw || !ema_raw || !feat12 || !style) return AS_EINVAL;
-    Call k(m, p, ws, ws_bytes, stream);
-    Ctx& c = k.c;
-    const Lay* ref = c.lay(vec_of(batch->ref_lens, batch->B));
-    if (!ref || ldm < ref->N || lde < ref->N || ldf < ref->N) return AS_EINVAL;
-    const float* stats = m->vec("__stats24");
-    RUN(c, as_ref_features_f32(mel, ldm, m->cfg.n_mels, f0_raw, ema_raw, lde, ref->N, stats, feat12, ldf, c.s));
-    const StyleIn si = style_inputs(c, feat12, ldf, mel, ldm, ref);
-    if (si.l1) for (int t = 0; t < 4; ++t) style_tower(c, t, si, style);
-    return k.done();
-} catch (const std::bad_alloc&) {
-    return (int)hipErrorOutOfMemory;
-} catch (...) {
-    return AS_EINVAL;
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, false, true, false) || !mel || !f0_raw || !ema_raw || !feat12 || !style) return AS_EINVAL;
+        Call k(m, p, ws, ws_bytes, stream, Pass::Run, true);
+        return k.done(style_module(k.c, batch, mel, ldm, f0_raw, ema_raw, lde, feat12, ldf, style));
+    });
 }
 
 extern "C" int as_duration_forward(const as_model* m, as_plan* p, const as_batch* batch, const int32_t* tokens, const float* ema_ext, int lde,
                                    float* duration, void* ws, size_t ws_bytes, as_stream_t stream)
-try {                                                                    // nothing may unwind through the C boundary
-    if (!m || !p || !batch_ok(batch, true, true, false) || !tokens || !ema_ext || !duration) return AS_EINVAL;
-    Call k(m, p, ws, ws_bytes, stream);
-    Ctx& c = k.c;
-    const Lay *tok = c.lay(vec_of(batch->tok_lens, batch->B)), *ref = c.lay(vec_of(batch->ref_lens, batch->B));
-    if (!tok || !ref || lde < ref->N) return AS_EINVAL;
-    float* ds = c.f32((size_t)batch->B * (m->cfg.style_dim / 4));
-    duration_style(c, ema_ext, lde, ref, ds);
-    EncOut eo;
-    rel_encoder_multi(c, path_encoders(), tokens, tok, &eo, [](int) {});
-    duration_tail(c, eo.y[ENC_DUR], ds, tok, duration);
-    return k.done();
-} catch (const std::bad_alloc&) {
-    return (int)hipErrorOutOfMemory;
-} catch (...) {
-    return AS_EINVAL;
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, true, true, false) || !tokens || !ema_ext || !duration) return AS_EINVAL;
+        Call k(m, p, ws, ws_bytes, stream, Pass::Run, true);
+        return k.done(duration_module(k.c, batch, tokens, ema_ext, lde, duration));
+    });
 }
 
 extern "C" int as_arts_forward(const as_model* m, as_plan* p, const as_batch* batch, const float* a_ens, int lda, const float* style, float* F0,
                                float* N, float* EMA, int ldp, void* ws, size_t ws_bytes, as_stream_t stream)
-try {                                                                    // nothing may unwind through the C boundary
-    if (!m || !p || !batch_ok(batch, false, false, true) || !a_ens || !style || !F0 || !N || !EMA) return AS_EINVAL;
-    Call k(m, p, ws, ws_bytes, stream);
-    Ctx& c = k.c;
-    const Lay* lay = c.lay(vec_of(batch->frames, batch->B));
-    if (!lay || lda < lay->N || ldp < 2 * lay->N) return AS_EINVAL;
-    const int N2 = 2 * lay->N, sd2 = 2 * m->cfg.style_dim;
-    const FcOut fc = adain_fc_all(c, "style", style_norms(*m), style, sd2, sd2, batch->B);
-    float* fne = c.f32((size_t)12 * std::max(N2, 1));
-    arts_predictor(c, a_ens, lda, lay, fc, fne, N2);
-    copy_rows(c, F0, ldp, fne, N2, 1, N2);
-    copy_rows(c, N, ldp, fne + (size_t)N2, N2, 1, N2);
-    copy_rows(c, EMA, ldp, fne + (size_t)2 * N2, N2, 10, N2);
-    return k.done();
-} catch (const std::bad_alloc&) {
-    return (int)hipErrorOutOfMemory;
-} catch (...) {
-    return AS_EINVAL;
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, false, false, true) || !a_ens || !style || !F0 || !N || !EMA) return AS_EINVAL;
+        Call k(m, p, ws, ws_bytes, stream, Pass::Run, true);
+        return k.done(arts_module(k.c, batch, a_ens, lda, style, F0, N, EMA, ldp));
+    });
 }
 
 extern "C" int as_decoder_forward(const as_model* m, as_plan* p, const as_batch* batch, const float* asr, int lda, const float* style,
                                   const float* F0, const float* N, const float* EMA, int ldp, float* mel, int ldo, void* ws, size_t ws_bytes,
                                   as_stream_t stream)
-try {                                                                    // nothing may unwind through the C boundary
-    if (!m || !p || !batch_ok(batch, false, false, true) || !asr || !style || !F0 || !N || !EMA || !mel) return AS_EINVAL;
-    Call k(m, p, ws, ws_bytes, stream);
-    Ctx& c = k.c;
-    const Lay* lay = c.lay(vec_of(batch->frames, batch->B));
-    if (!lay) return AS_EINVAL;
-    const Lay* lay2 = c.scaled(lay, 2);
-    if (!lay2 || lda < lay->N || ldp < lay2->N || ldo < lay2->N) return AS_EINVAL;
-    // nearest x2 of the text encoding (models.py:500) = a column gather with every frame as its own token
-    int32_t* ident = c.i32((size_t)std::max(lay->N, 1));
-    if (c.go() && lay->N > 0) {
-        std::vector<int32_t> h(lay->N);
-        for (int i = 0; i < lay->N; ++i) h[i] = i;
-        if (hipMemcpyAsync(ident, h.data(), (size_t)lay->N * 4, hipMemcpyHostToDevice, c.s) != hipSuccess || hipStreamSynchronize(c.s) != hipSuccess)
-            c.fail((int)hipErrorUnknown);
-    }
-    const int C = m->cfg.hidden_dim;
-    float* x0 = c.f32((size_t)(C + 128) * std::max(lay2->N, 1));
-    RUN(c, as_expand_f32(asr, lda, C, ident, lay->N, 2, x0, lay2->N, c.s));
-    float* fne = c.f32((size_t)12 * std::max(lay2->N, 1));
-    copy_rows(c, fne, lay2->N, F0, ldp, 1, lay2->N);
-    copy_rows(c, fne + (size_t)lay2->N, lay2->N, N, ldp, 1, lay2->N);
-    copy_rows(c, fne + (size_t)2 * lay2->N, lay2->N, EMA, ldp, 10, lay2->N);
-    const int sd2 = 2 * m->cfg.style_dim;
-    const FcOut fc = adain_fc_all(c, "style", style_norms(*m), style, sd2, sd2, batch->B);
-    decoder(c, decoder_pre(c, x0, lay2), x0, lay2, fne, lay2->N, fc, mel, ldo);
-    return k.done();
-} catch (const std::bad_alloc&) {
-    return (int)hipErrorOutOfMemory;
-} catch (...) {
-    return AS_EINVAL;
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, false, false, true) || !asr || !style || !F0 || !N || !EMA || !mel) return AS_EINVAL;
+        Call k(m, p, ws, ws_bytes, stream, Pass::Run, true);
+        return k.done(decoder_module(k.c, batch, asr, lda, style, F0, N, EMA, ldp, mel, ldo));
+    });
 }
 
 extern "C" int as_forward_test_begin(const as_model* m, as_plan* p, const as_batch* batch, const as_forward_io* io, void* ws_a, size_t ws_a_bytes,
                                      as_stream_t stream)
-try {                                                                    // nothing may unwind through the C boundary
-    if (!m || !p || !batch_ok(batch, true, true, false) || !io_ok(io, false)) return AS_EINVAL;
-    Call k(m, p, ws_a, ws_a_bytes, stream);
-    const PhaseA A = forward_a(k.c, batch, io);
-    if (A.tok && A.ref) outputs_a(k.c, A, batch, io);
-    return k.done();
-} catch (const std::bad_alloc&) {
-    return (int)hipErrorOutOfMemory;
-} catch (...) {
-    return AS_EINVAL;
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, true, true, false) || !io_ok(io, false)) return AS_EINVAL;
+        Call k(m, p, ws_a, ws_a_bytes, stream, Pass::Run, true);
+        const PhaseA A = forward_a(k.c, batch, io);
+        if (A.tok && A.ref) outputs_a(k.c, A, io);
+        return k.done();
+    });
 }
 
 extern "C" int as_forward_test_finish(const as_model* m, as_plan* p, const as_batch* batch, const as_forward_io* io, void* ws_a, size_t ws_a_bytes,
                                       void* ws_b, size_t ws_b_bytes, as_stream_t stream)
-try {                                                                    // nothing may unwind through the C boundary
-    if (!m || !p || !batch_ok(batch, true, true, true) || !io_ok(io, true)) return AS_EINVAL;
-    // recover where the first half left its results: the same allocation sequence, nothing launched
-    Call ka(m, p, ws_a, ws_a_bytes, stream, false);
-    const PhaseA A = forward_a(ka.c, batch, io);
-    if (ka.done() || !A.tok || !A.ref) return ka.done() ? ka.done() : AS_EINVAL;
-    Call kb(m, p, ws_b, ws_b_bytes, stream, true, false);
-    forward_b(kb.c, A, batch, io);
-    return kb.done();
-} catch (const std::bad_alloc&) {
-    return (int)hipErrorOutOfMemory;
-} catch (...) {
-    return AS_EINVAL;
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, true, true, true) || !io_ok(io, true)) return AS_EINVAL;
+        // recover where the first half left its results: the same allocation sequence, nothing launched (_begin's layouts: no trim)
+        Call ka(m, p, ws_a, ws_a_bytes, stream, Pass::Replay, false);
+        const PhaseA A = forward_a(ka.c, batch, io);
+        if (ka.done() || !A.tok || !A.ref) return ka.done() ? ka.done() : AS_EINVAL;
+        Call kb(m, p, ws_b, ws_b_bytes, stream, Pass::Run, false);
+        forward_b(kb.c, A, batch, io);
+        return kb.done();
+    });
 }
 
 extern "C" int as_forward_test(const as_model* m, as_plan* p, const as_batch* batch, const as_forward_io* io, void* ws_a, size_t ws_a_bytes,
                                void* ws_b, size_t ws_b_bytes, int32_t* frames_host_out, as_stream_t stream)
-try {                                                                    // nothing may unwind through the C boundary
-    if (!m || !p || !batch_ok(batch, true, true, false) || !io_ok(io, true)) return AS_EINVAL;
-    Call ka(m, p, ws_a, ws_a_bytes, stream);
-    const PhaseA A = forward_a(ka.c, batch, io);
-    if (ka.done() || !A.tok || !A.ref) return ka.done() ? ka.done() : AS_EINVAL;
-    if (!batch->frames && io->frame_cap > 0) {
-        // predicted durations under a frame capacity: the second half is sized by the capacity and finds the utterances' extents on the
-        // device -- no read-back, nothing here waits for the stream, the whole call is capturable
-        if (io->forced_dur) return AS_EINVAL;                               // (forced durations are host data: their sums are batch->frames)
-        outputs_a(ka.c, A, batch, io);
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, true, true, false) || !io_ok(io, true)) return AS_EINVAL;
+        Call ka(m, p, ws_a, ws_a_bytes, stream, Pass::Run, true);
+        const PhaseA A = forward_a(ka.c, batch, io);
+        if (ka.done() || !A.tok || !A.ref) return ka.done() ? ka.done() : AS_EINVAL;
+        const hipStream_t s = static_cast<hipStream_t>(stream);
+        as_batch b2 = *batch;
+        if (!batch->frames && io->frame_cap > 0) {
+            // predicted durations under a frame capacity: the second half is sized by the capacity and finds the utterances' extents on the
+            // device -- no read-back, nothing here waits for the stream, the whole call is capturable
+            if (io->forced_dur) return AS_EINVAL;                           // (forced durations are host data: their sums are batch->frames)
+        } else {
+            if (!batch->frames) {                                           // the one device -> host read of the path
+                std::vector<int32_t> off(batch->B + 1);
+                AS_CHECK(hipMemcpyAsync(off.data(), A.frame_off, off.size() * 4, hipMemcpyDeviceToHost, s));
+                AS_CHECK(hipStreamSynchronize(s));
+                if (as_status_peek()) return AS_EDEVICE;                    // e.g. the duration predictor's recurrence timed out
+                p->frames_host.resize(batch->B);
+                for (int i = 0; i < batch->B; ++i) p->frames_host[i] = off[i + 1] - off[i];
+                b2.frames = p->frames_host.data();
+            }
+            if (frames_host_out) memcpy(frames_host_out, b2.frames, (size_t)batch->B * 4);
+        }
+        outputs_a(ka.c, A, io);
         if (ka.done()) return ka.done();
-        Ctx cb(*m, *p, static_cast<hipStream_t>(stream), ws_b, ws_b_bytes, true, false);
-        if ((reinterpret_cast<uintptr_t>(ws_b) & 255) != 0) return AS_EINVAL;
-        forward_b(cb, A, batch, io);
+        // the second half of the same call: its events follow the first half's, layouts and device status were seen to above
+        if (misaligned(ws_b)) return AS_EINVAL;
+        Ctx cb(*m, *p, s, ws_b, ws_b_bytes, Pass::Run);
+        forward_b(cb, A, &b2, io);
         return cb.rc ? cb.rc : m->err;
-    }
-    as_batch b2 = *batch;
-    if (!batch->frames) {                                                   // the one device -> host read of the path
-        std::vector<int32_t> off(batch->B + 1);
-        AS_CHECK(hipMemcpyAsync(off.data(), A.frame_off, off.size() * 4, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
-        AS_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-        if (as_status_peek()) return AS_EDEVICE;                            // e.g. the duration predictor's recurrence timed out
-        p->frames_host.resize(batch->B);
-        for (int i = 0; i < batch->B; ++i) p->frames_host[i] = off[i + 1] - off[i];
-        b2.frames = p->frames_host.data();
-    }
-    if (frames_host_out) memcpy(frames_host_out, b2.frames, (size_t)batch->B * 4);
-    outputs_a(ka.c, A, &b2, io);
-    if (ka.done()) return ka.done();
-    Ctx cb(*m, *p, static_cast<hipStream_t>(stream), ws_b, ws_b_bytes, true, false);
-    if ((reinterpret_cast<uintptr_t>(ws_b) & 255) != 0) return AS_EINVAL;
-    forward_b(cb, A, &b2, io);
-    return cb.rc ? cb.rc : m->err;
-} catch (const std::bad_alloc&) {
-    return (int)hipErrorOutOfMemory;
-} catch (...) {
-    return AS_EINVAL;
+    });
 }

@@ -382,6 +382,105 @@ def test_c_abi_forward_on_full_goldens(cuda, golden_dir):
         L.as_model_destroy(model)
 
 
+def test_module_workspace_bytes_are_exact(cuda, golden_dir):
+    """as_module_workspace_bytes is exactly what each module entry point allocates: with that many bytes the call succeeds, with 512
+    fewer (still 256-aligned) it returns AS_ENOSPC -- an undercount fails the first check, an overcount the second.  Every module a
+    caller can size, on the tiny goldens' geometry as one ragged batch of four utterances."""
+    import ctypes
+    from artspeech_amd.blob import state_dict_to_blob
+    L = _lib.lib()
+    files = sorted(glob.glob(os.path.join(golden_dir, "net_tiny_*.npz")))
+    gs = [np.load(f) for f in files]
+    hd, di = int(gs[0]["hidden_dim"]), int(gs[0]["dim_in"])
+    blob = state_dict_to_blob(synth.synth_state_dict(hd, di, seed=int(gs[0]["weight_seed"])))
+    cfg = _lib.ModelCfg()
+    cfg.hidden_dim, cfg.dim_in, cfg.style_dim, cfg.n_mels, cfg.n_token = hd, di, 256, 80, 178
+    for i, v in enumerate(models.stats_floats(load_distribution(DEFAULT_STATS))):
+        cfg.stats[i] = v
+    torch.cuda.set_device(cuda)
+    model, plan = ctypes.c_void_p(), ctypes.c_void_p()
+    assert L.as_model_create(blob, len(blob), ctypes.byref(cfg), ctypes.byref(model)) == 0
+    assert L.as_plan_create(model, ctypes.byref(plan)) == 0
+    I32P = ctypes.POINTER(ctypes.c_int32)
+    AS_ENOSPC = -2
+    keep = []                                     # the host arrays the batches point to
+
+    def arr(v):
+        keep.append((ctypes.c_int32 * len(v))(*v))
+        return keep[-1]
+
+    def batch(frames):
+        return _lib.Batch(len(gs), ctypes.cast(tl, I32P), ctypes.cast(rl, I32P), ctypes.cast(arr(frames), I32P) if frames else None)
+
+    def fp(*shape):
+        return (0.1 * torch.randn(*shape, generator=gen, device=cuda)).contiguous()
+
+    def check(module, b, call):
+        n = L.as_module_workspace_bytes(model, plan, module, ctypes.byref(b))
+        assert n > 512 and n % 256 == 0, (module, n)
+        ws = torch.empty(n, dtype=torch.uint8, device=cuda)
+        assert call(ws.data_ptr(), n - 512) == AS_ENOSPC, (module, n)
+        assert call(ws.data_ptr(), n) == 0, (module, n)
+        torch.cuda.synchronize()
+        assert L.as_device_status(0) == 0, module
+        return ws, n
+
+    try:
+        tl, rl = arr([len(g["tokens"]) for g in gs]), arr([int(g["t_ref"]) for g in gs])
+        frames = [int(g["ref/pred_dur"].sum()) for g in gs]
+        Nt, Nr, N1 = sum(tl), sum(rl), sum(frames)
+        b_tok, b_fr = batch(None), batch(frames)
+        gen = torch.Generator(device=cuda).manual_seed(0)
+        s = torch.cuda.current_stream().cuda_stream
+        tokens = torch.from_numpy(np.concatenate([g["tokens"] for g in gs]).astype(np.int32)).to(cuda)
+        feats = [raw_features(int(g["t_ref"]), int(g["seed"])) for g in gs]
+        mel, f0_raw, ema_raw = (torch.from_numpy(np.concatenate([f[i] for f in feats], axis=-1)).to(cuda).contiguous() for i in range(3))
+        style = fp(len(gs), 512)
+
+        enc = torch.empty(hd, Nt, device=cuda)
+        check(_lib.AS_MOD_ENCODER, b_tok, lambda ws, n: L.as_encoder_forward(model, plan, 0, ctypes.byref(b_tok), tokens.data_ptr(),
+                                                                             enc.data_ptr(), Nt, ws, n, s))
+        feat12 = torch.empty(12, Nr, device=cuda)
+        check(_lib.AS_MOD_STYLE, b_tok, lambda ws, n: L.as_style_forward(model, plan, ctypes.byref(b_tok), mel.data_ptr(), Nr,
+                                                                         f0_raw.data_ptr(), ema_raw.data_ptr(), Nr, feat12.data_ptr(), Nr,
+                                                                         style.data_ptr(), ws, n, s))
+        dur = torch.empty(Nt, device=cuda)
+        check(_lib.AS_MOD_DURATION, b_tok, lambda ws, n: L.as_duration_forward(model, plan, ctypes.byref(b_tok), tokens.data_ptr(),
+                                                                               feat12[2:].data_ptr(), Nr, dur.data_ptr(), ws, n, s))
+        a_en, pred = fp(hd, N1), torch.empty(12, 2 * N1, device=cuda)
+        check(_lib.AS_MOD_ARTS, b_fr, lambda ws, n: L.as_arts_forward(model, plan, ctypes.byref(b_fr), a_en.data_ptr(), N1,
+                                                                      style.data_ptr(), pred[0].data_ptr(), pred[1].data_ptr(),
+                                                                      pred[2:].data_ptr(), 2 * N1, ws, n, s))
+        out = torch.empty(80, 2 * N1 + 64, device=cuda)
+        check(_lib.AS_MOD_DECODER, b_fr, lambda ws, n: L.as_decoder_forward(model, plan, ctypes.byref(b_fr), a_en.data_ptr(), N1,
+                                                                            style.data_ptr(), pred[0].data_ptr(), pred[1].data_ptr(),
+                                                                            pred[2:].data_ptr(), 2 * N1, out.data_ptr(), out.shape[1],
+                                                                            ws, n, s))
+        # the whole path: the first half (predicted durations, read back through frame_off), the second on the frames it predicted,
+        # and the one-call form under a frame capacity (each utterance gets 8 frames of room more than it needs)
+        f_off = torch.zeros(len(gs) + 1, dtype=torch.int32, device=cuda)
+        io = _lib.ForwardIO()
+        io.tokens, io.mel, io.ld_mel, io.f0_raw, io.ema_raw, io.ld_ema = (tokens.data_ptr(), mel.data_ptr(), Nr, f0_raw.data_ptr(),
+                                                                          ema_raw.data_ptr(), Nr)
+        io.mel_out, io.ld_out, io.frame_off = out.data_ptr(), out.shape[1], f_off.data_ptr()
+        ws_a, na = check(_lib.AS_MOD_FORWARD_A, b_tok, lambda ws, n: L.as_forward_test_begin(model, plan, ctypes.byref(b_tok),
+                                                                                             ctypes.byref(io), ws, n, s))
+        off = f_off.cpu().tolist()
+        pred_frames = [off[i + 1] - off[i] for i in range(len(gs))]
+        assert min(pred_frames) >= 1 and 2 * off[-1] <= out.shape[1] - 64, pred_frames
+        b_pred = batch(pred_frames)
+        check(_lib.AS_MOD_FORWARD_B, b_pred, lambda ws, n: L.as_forward_test_finish(model, plan, ctypes.byref(b_pred), ctypes.byref(io),
+                                                                                    ws_a.data_ptr(), na, ws, n, s))
+        room = [f + 8 for f in pred_frames]
+        b_room = batch(room)
+        io.frame_cap = sum(room)
+        check(_lib.AS_MOD_FORWARD_B_CAP, b_room, lambda ws, n: L.as_forward_test(model, plan, ctypes.byref(b_tok), ctypes.byref(io),
+                                                                                 ws_a.data_ptr(), na, ws, n, None, s))
+    finally:
+        L.as_plan_destroy(plan)
+        L.as_model_destroy(model)
+
+
 @pytest.mark.parametrize("arrangement", ["side_streams", "merged_chain"])
 def test_c3_full_config_ragged_batch_vs_oracle(cuda, arrangement):
     """BASELINE config C3 at full size: 32 utterances of VARIED lengths through one as_forward_test call, every utterance against the
