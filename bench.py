@@ -11,8 +11,8 @@ duration predictor + integer alignment expansion + F0/energy/TV predictors + Ada
 batch of 32 synthetic utterances (config C3 of SURVEY.md section 8: N = 40 tokens, forced integer durations
 summing to M = 100 => 200 mel frames per utterance, T_ref = 200; full-size model, seeded synthetic weights),
 as ONE call of the library's as_forward_test (csrc/model.hip) captured into a hipGraph and replayed.
-`value` is measured with the inputs resident in HBM when the timed region starts (the contract of this benchmark); the SAME K steps are
-then timed again with the host <-> device copies inside the region ("transfers": as_lanes_submit_host -- the library copies a submission's
+`value` is measured with the inputs resident in HBM when the timed region starts (the contract of this benchmark); with `--full` the SAME
+K steps are then timed again with the host <-> device copies inside the region ("transfers": as_lanes_submit_host -- the library copies a submission's
 pinned host arrays into the lane's device block, launches the group and copies the mel back: the reference's test.py:96-113 boundary, in
 the arrangement `value` reports) -- the two differ by 2-3 per cent because the copies run beside the lanes' kernels.
 Consecutive steps are independent batches: by default FOUR are kept in flight per GPU (`--in-flight 4`: each lane its own plan +
@@ -26,16 +26,21 @@ eager step and lane 0's with the one-at-a-time run; if a lane ever differed the 
 one-at-a-time number (`in_flight_note`).
 With N > 1 every rank runs its own 32-utterance batch on its own GPU (utterance batches shard embarrassingly; no data-path
 collective) => weak scaling; the only torch.distributed use is the barrier and the max-over-ranks of the elapsed time.
-`--global-batch G` instead builds ONE length-varied batch of G utterances, shards it over the ranks (artspeech_amd.shard) and
-checks the merged result against a single-rank run (BASELINE config C4).
+`--global-batch G` instead builds ONE length-varied batch of G utterances and shards it over the ranks (artspeech_amd.shard); with
+`--full` the merged result is checked against a single-rank run (BASELINE config C4).
 
 --dump-outputs DIR: after the timed steps, what the last timed step of the arrangement that became `value` returned (the mel of its
 batch of 32; seeded inputs, the same from run to run for the same arguments) is written as DIR/<name>.npy, 64 MB at most.
 
-Prints ONE JSON line (rank 0).  Beside the contract's keys:
+Prints ONE JSON line (rank 0).  A plain run does only what `value` needs: the setup, the arrangements above, each warmed up and timed (the
+faster verified one is `value`), --dump-outputs, the line -- the contract's keys and what those timed passes give on the way
+(`ms_per_step_repeats`, `ms_per_step_one_in_flight`, `coalesced`, `ms_per_step_lanes_of_32`).  `--full` adds everything else:
+  ms_per_step_one_chain_alone   one lane's chain alone, timed on its own
+  c4_shard_check (--global-batch) the merged shards against rank 0 running the whole batch alone
   roofline       the dominant kernel, the implicit-GEMM conv on the fp16 matrix cores (f16x3 split-operand arithmetic, fp32-accurate):
                  algorithmic flop / its HIP-event time on the launch stream (an instrumented pass of the same step, branches back to back)
   roofline_hbm   the bandwidth-bound group (AdaIN, LayerNorm, pooling / expansion / image writers): algorithmic bytes / event time / 8 TB/s
+  kernel_classes, launches_per_step, phase_ms_eager   what those two are computed from; the phases of one eager step
   mas            monotonic alignment search (K1) at [32,40,100] and [8,1024,2000]: cells/s, us/column, GB/s, bit-exactness against the
                  reference-generated golden paths
   configs        C2 (batch 1, 150 frames: latency; also in the 16-bit-operand mode with its measured error) and C5 (long form)
@@ -44,7 +49,8 @@ Prints ONE JSON line (rank 0).  Beside the contract's keys:
   transfers      the headline arrangement with HOST buffers at the boundary (as_lanes_submit_host: the library's copies inside the timed
                  region); `lanes_of_32`: copies around the replays of 32-utterance graphs on this script's own streams
   lanes_native   the same K steps through the library's own lanes (as_lanes_submit: plans, streams, workspaces, hipGraphs kept in C++)
-  cpu_baseline   the oracle's CPU restatement timed on this box's host cores on a bounded sample of the same workload
+  cpu_baseline   the oracle's CPU restatement timed on the host's cores on a bounded sample of the same workload, and the mel's
+                 parity against it
 """
 import argparse
 import ctypes
@@ -711,13 +717,14 @@ def merge_hosts(hosts):
     return {k: [v for h in hosts for v in h[k]] for k in hosts[0]}
 
 
-def bench_coalesced(net, hosts, k, n_lanes, steps, warmup, barrier=lambda: None, last=None):
+def bench_coalesced(net, hosts, k, n_lanes, steps, warmup, barrier=lambda: None, last=None, with_host=False):
     """The K timed steps as K submissions of ONE 32-utterance batch each through the library's lanes with as_lanes_set_coalesce(k): a lane's k
     consecutive batches live in adjacent column ranges of one block, so the lane launches them as ONE as_forward_test call over 32 k
     utterances, without a copy (wider conv GEMM launches, one fetch of the weights for k batches; models.py:361-362 processes one utterance
     at a time: any grouping is legal).  hosts: k * n_lanes make_inputs host dicts (one per batch).  Every batch's mel is compared with the
     same batch run ALONE as one merged chain (not bitwise: k times the columns, another GEMM tile).  last (a dict): receives the host
-    arrays of the last step of the first timed pass (the line's figure) -- what its submitter gets back: the mel of its batch."""
+    arrays of the last step of the first timed pass (the line's figure) -- what its submitter gets back: the mel of its batch.
+    with_host: `host_boundary` also times the same submissions from host buffers (coalesced_host_boundary)."""
     from artspeech_amd import models
     dev = net.rt.device
     per = len(hosts[0]["frames"])
@@ -769,6 +776,18 @@ def bench_coalesced(net, hosts, k, n_lanes, steps, warmup, barrier=lambda: None,
     st = lanes.stats(0)
     first = order[0]["out"]["mel"].clone()
     lanes.close()
+    host_boundary = coalesced_host_boundary(net, hosts, order, k, n_lanes, steps, warmup, barrier, els) if with_host else None
+    return dict(elapsed_s=el, ms_per_step=el / steps * 1e3, ms_per_step_repeats=[e / steps * 1e3 for e in els], coalesce=k, lanes=n_lanes,
+                utterances_per_call=per * k, merged_calls=merged,
+                graph_launches_lane0=st["graph_launches"], max_abs_vs_each_batch_alone=worst, results_verified=bool(worst <= 3e-5),
+                host_boundary=host_boundary,
+                note="as_lanes_submit per 32-utterance batch; a lane launches its k adjacent batches as one as_forward_test call"), first
+
+
+def coalesced_host_boundary(net, hosts, order, k, n_lanes, steps, warmup, barrier, els):
+    """bench_coalesced's K submissions (order: its submissions, els: its elapsed seconds) again with host buffers at the boundary"""
+    from artspeech_amd import models
+    per = len(hosts[0]["frames"])
     # The SAME K submissions with HOST buffers at the boundary (SURVEY.md D2; /root/reference/test.py:96-113 moves tokens / mel to the device
     # inside `synthesis`): as_lanes_submit_host -- per submission the pinned host -> device copies into the lane's own block, the group's
     # launch, the device -> host copy of every submission's mel, all issued by the library (the copies on its two copy streams, ordered against
@@ -819,11 +838,7 @@ def bench_coalesced(net, hosts, k, n_lanes, steps, warmup, barrier=lambda: None,
                               "all issued by the library (copies on its two copy streams, events against the lane's kernels); results bitwise equal to the "
                               "device-buffer submissions")
     lanes.close()
-    return dict(elapsed_s=el, ms_per_step=el / steps * 1e3, ms_per_step_repeats=[e / steps * 1e3 for e in els], coalesce=k, lanes=n_lanes,
-                utterances_per_call=per * k, merged_calls=merged,
-                graph_launches_lane0=st["graph_launches"], max_abs_vs_each_batch_alone=worst, results_verified=bool(worst <= 3e-5),
-                host_boundary=host_boundary,
-                note="as_lanes_submit per 32-utterance batch; a lane launches its k adjacent batches as one as_forward_test call"), first
+    return host_boundary
 
 
 def bench_predicted(net, hosts, k, n_lanes, steps, warmup, barrier=lambda: None):
@@ -996,6 +1011,94 @@ def c4_check(net, host, mel_mine, mine, world, rank, dev, dist, dump=None):
                 note="not bitwise: the GEMM's tile choice depends on a shard's total column count (bound 5e-5)")
 
 
+def kernel_figures(net, g, g_roof, per_call, args):
+    """--full: the line's objects of kernel classes -- the phase times of one eager step of g, the kernel classes of one call of g_roof
+    (per_call batches of 32: as the timed region launches them) and the rooflines of the conv GEMM and of the bandwidth-bound group"""
+    # ---- phase times of one eager step with the branches concurrent (HIP events between the phases, on the calling stream)
+    prunner = Runner(net, g)
+    phase = [net.rt.phase_ms(prunner.step) for _ in range(3)][-1]
+    kern = profile_classes(net, Runner(net, g_roof))
+    net.rt.set_serial(args.no_concurrency)
+    gemm_tflops, gemm_peak = gemm_roofline(kern, 3)
+    k0 = kern["conv_gemm"]
+    hbm_ms = sum(kern[c]["ms_per_step"] for c in HBM_GROUP if c in kern)
+    hbm_gb = sum(kern[c]["gbyte_per_step"] for c in HBM_GROUP if c in kern)
+
+    # HBM traffic of the dominant kernel cannot be read live (PMC needs rocprofv3): it comes from the committed counter pass of this
+    # same command (profiles/latest_pmc_traffic.json, scripts/gpu_profile.sh), and only when that pass was taken from THIS build
+    traffic, traffic_src = None, "no PMC profile of this build (profiles/latest_pmc_traffic.json was taken from other kernel sources)"
+    try:
+        pj = json.load(open(os.path.join(ROOT, "profiles", "latest_pmc_traffic.json")))
+        if pj.get("source_id") == source_id() and pj.get("batches_per_call", 1) == per_call:
+            traffic, traffic_src = pj["conv_gemm_hbm_bytes_per_launch"], pj["source"]
+    except Exception:
+        pass
+
+    sus_reg, sus_lds = mfma_sustained()
+    # The roofline fractions are reported from the committed rocprofv3 kernel trace of THIS build when there is one
+    # (profiles/latest_trace_classes.json: sum of kernel durations per class and step, scripts/make_profiles.py) -- a trace counts a kernel's
+    # own duration, nothing of the brackets around it -- and from this run's HIP events otherwise; the event figures stay beside them.
+    trace_cls, trace_src = None, "no kernel trace of this build under profiles/ (HIP events of this run, bracket cost removed)"
+    try:
+        tj = json.load(open(os.path.join(ROOT, "profiles", "latest_trace_classes.json")))
+        if tj.get("source_id") == source_id() and args.config == "C3" and not args.global_batch and tj.get("batches_per_call", 1) == per_call:
+            trace_cls, trace_src = tj["classes"], f"{tj['file']} ({tj['command']}; {tj['steps_in_trace']} steps in the trace)"
+    except Exception:
+        pass
+    gemm_tflops_ev = gemm_tflops
+    hbm_ms_ev = hbm_ms
+    tc_ms = None
+    if trace_cls:                                                  # (both sides per CALL of per_call batches)
+        try:
+            tc_ms = lambda c: trace_cls[c].get("ms_per_call", trace_cls[c]["ms_per_step"] * per_call)   # (files of rounds 1-4: per step = per call)
+            gemm_tflops = k0["gflop_per_step"] / tc_ms("conv_gemm")
+            hbm_ms = sum(tc_ms(c) for c in HBM_GROUP if c in trace_cls)
+        except Exception:                                          # (a committed summary this script cannot read never costs the line)
+            trace_cls, trace_src, gemm_tflops, hbm_ms = None, "the committed kernel-trace summary is unreadable (HIP events of this run)", gemm_tflops_ev, hbm_ms_ev
+    return {
+        "roofline": {"bound": "mfma",
+                     "kernel": "conv_gemm_h3_kernel (implicit-GEMM conv, fp16 matrix cores, two-way split operands h + l, 3 products per fp32 "
+                               "product, fp32 accumulate; both operands staged by LDS-DMA from producer-written images)",
+                     "achieved": gemm_tflops, "peak": gemm_peak, "unit": "TFLOP/s", "frac": gemm_tflops / gemm_peak,
+                     # where `achieved` / `frac` come from: "committed_trace" = the rocprofv3 kernel trace of THIS build committed under
+                     # profiles/ (matched by the kernel sources' id; not measured by this run), "events_this_run" = HIP events of this run
+                     "frac_source": "committed_trace" if trace_cls else "events_this_run",
+                     "time_source": trace_src,
+                     "achieved_by_events": gemm_tflops_ev, "frac_by_events": gemm_tflops_ev / gemm_peak,      # (always this run's)
+                     # the launches the fraction is about: one as_forward_test call over `batches_per_call` batches of 32 (the timed region's)
+                     "batches_per_call": per_call, "utterances_per_call": len(g_roof["frames"]),
+                     "gemm_ms_per_step_by_trace": tc_ms("conv_gemm") / per_call if trace_cls else None,
+                     "gemm_ms_per_step_by_events": k0["ms_per_step"] / per_call,
+                     "peak_basis": "dense fp16 MFMA 2516.6 TFLOP/s / 3 matrix-core products per fp32 product (achieved = algorithmic fp32 flop); "
+                                   "round 1 ran six bf16 products per fp32 product (ceiling 419.4)",
+                     # measured live on this device: a bare loop of the kernel's own MFMA pattern on random operands (no memory traffic, no
+                     # barriers).  The chip lowers its clock under matrix-core load on non-trivial data: `peak` above is the data sheet's.
+                     "sustained_on_random_operands": {
+                         "mfma_f16_tflops_operands_in_registers": sus_reg, "mfma_f16_tflops_operands_from_lds": sus_lds,
+                         "as_f16x3_tflops_from_lds": sus_lds / 3.0, "frac_of_nominal_peak": sus_lds / PEAK_F16_MFMA_TFLOPS,
+                         "kernel_frac_of_sustained": gemm_tflops / (sus_lds / 3.0)},
+                     "frac_of_fp32_mfma_peak": gemm_tflops / PEAK_F32_MFMA_TFLOPS,
+                     "frac_of_round1_bf16x6_ceiling": gemm_tflops / PEAK_X6_TFLOPS,
+                     "traffic": traffic, "traffic_source": traffic_src,
+                     "avg_launch_ms": k0["ms_per_step"] / max(k0["launches_per_step"], 1), "launches_per_step": k0["launches_per_step"],
+                     "event_bracket_overhead_us": bracket_overhead_ms() * 1e3,
+                     "achieved_with_bracket_overhead": k0["gflop_per_step"] / k0["ms_per_step_bracketed"],
+                     "algorithmic_gflop_per_step": k0["gflop_per_step"] / per_call},
+        "roofline_hbm": {"bound": "hbm", "kernels": "AdaIN / LayerNorm operand-image writers, pooling, expansion, im2col, reference features "
+                                                    "(classes adain + layernorm + other of the event profiler)",
+                         "achieved": hbm_gb / hbm_ms if hbm_ms else None, "peak": PEAK_HBM_TBS, "unit": "TB/s",
+                         "frac": hbm_gb / hbm_ms / PEAK_HBM_TBS if hbm_ms else None,
+                         "frac_source": "committed_trace" if trace_cls else "events_this_run",
+                         "batches_per_call": per_call,
+                         "algorithmic_gbyte_per_step": hbm_gb / per_call, "ms_per_step": hbm_ms / per_call, "time_source": trace_src,
+                         "ms_per_step_by_events": hbm_ms_ev / per_call, "frac_by_events": hbm_gb / hbm_ms_ev / PEAK_HBM_TBS if hbm_ms_ev else None,
+                         "launches_per_step": sum(kern[c]["launches_per_step"] for c in HBM_GROUP if c in kern)},
+        "launches_per_step": {c: kern[c]["launches_per_step"] for c in kern},       # (per call of `roofline.batches_per_call` batches, like kernel_classes)
+        "kernel_classes": kern,
+        "phase_ms_eager": dict(zip(["features", "encoders_towers_duration", "predictors", "decoder"], [round(v, 3) for v in phase])),
+    }
+
+
 def self_launch(n):
     """`python3 bench.py --gpus N` without a launcher around it: start `python -m torch.distributed.run --nproc-per-node N bench.py <the
     same arguments>` as a child process (rendezvous on 127.0.0.1, a free port), pass rank 0's JSON line through, return the launcher's
@@ -1022,14 +1125,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--cpu-utts", type=int, default=96, help="utterances in the CPU-baseline sample, capped at ~20 s (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, everything else the line can hold: the other "
+                    "arrangements' and configs' figures, the host boundary, kernel classes and rooflines, MAS, the test.py chain, "
+                    "the CPU baseline and the checks against it and against one rank")
+    ap.add_argument("--cpu-utts", type=int, default=96, help="with --full: utterances in the CPU-baseline sample, capped at ~20 s (0 = skip)")
     ap.add_argument("--no-graph", action="store_true", help="launch kernels eagerly instead of replaying a hipGraph")
     ap.add_argument("--no-concurrency", action="store_true", help="run the independent branches back to back (profiling)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the MAS / C2 / C5 / transfer / surface lines (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the MAS / C2 / C5 / transfer / surface lines (profiling runs)")
     ap.add_argument("--surface-only", action="store_true", help="print only the `surface` object (the test.py chain around the path): profiling runs")
     ap.add_argument("--config", default="C3", choices=["C3", "C5", "C2"], help="workload of the timed region (profiling runs; the headline is C3)")
     ap.add_argument("--global-batch", type=int, default=0, help="C4: ONE ragged batch of this many utterances sharded over the ranks")
-    ap.add_argument("--c4-dump", default=None, help="with --global-batch: .npz for the merged mel of three utterances (tests hold them against the oracle)")
+    ap.add_argument("--c4-dump", default=None, help="with --global-batch --full: .npz for the merged mel of three utterances (tests hold them against "
+                    "the oracle)")
     ap.add_argument("--in-flight", type=int, default=4, help="batches in flight per GPU: consecutive steps are replayed on this many HIP streams "
                     "(each with its own plan and workspaces on the same weights); 1 = one step at a time (the step's latency)")
     ap.add_argument("--call-batches", type=int, default=1, help="profiling runs (C3): a step = ONE as_forward_test call over this many batches of 32 "
@@ -1041,6 +1148,8 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the timed arrangement's last step "
                     "returned (the mel of its batch; with one batch in flight also dur_i and frame_off) as DIR/<name>.npy, rank 0")
     args = ap.parse_args()
+    if args.c4_dump and not (args.global_batch and args.full):
+        ap.error("--c4-dump needs --global-batch and --full (the merged shards are checked by --full runs only)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python3 bench.py --gpus N` on its own: this process has not touched the GPU (importing torch does not), so it starts the N
@@ -1150,8 +1259,9 @@ def main():
         chain_vs_side = float((firsts[0] - mel_first).abs().max())
         assert chain_vs_side <= 3e-5, f"a step as one chain and the step with its branches on side streams differ by {chain_vs_side}"
         # one chain ALONE (the latency of a batch on a merging serial plan, beside single_ms: the same batch with its branches on side streams)
-        with torch.cuda.stream(lanes[0][2]):
-            one_chain_ms = lanes[0][0].timed(lanes[0][1], max(args.steps // 4, 5), 3, lambda: None) / max(args.steps // 4, 5) * 1e3
+        if args.full:
+            with torch.cuda.stream(lanes[0][2]):
+                one_chain_ms = lanes[0][0].timed(lanes[0][1], max(args.steps // 4, 5), 3, lambda: None) / max(args.steps // 4, 5) * 1e3
         # the warm-up ends on the last lane: timed step i runs lane i % n_fl, i.e. batch seed DATA_SEED + 100 (i % n_fl) -- the batch the
         # coalesced arrangement's step i submits too, so that --dump-outputs holds the same batch whichever arrangement is adopted
         it = [-args.warmup % n_fl]
@@ -1186,7 +1296,7 @@ def main():
         ncl = max(1, n_fl // kc)
         hosts = [host] + [make_inputs(None, seed0=DATA_SEED + 100 * i)[0] for i in range(1, kc * ncl)]
         coal_last = {} if dump is not None else None
-        coal, coal_first = bench_coalesced(net, hosts, kc, ncl, args.steps, args.warmup, barrier, last=coal_last)
+        coal, coal_first = bench_coalesced(net, hosts, kc, ncl, args.steps, args.warmup, barrier, last=coal_last, with_host=args.full)
         c_el, l_el, c_ok = coal["elapsed_s"], elapsed, coal["results_verified"]
         if world > 1:                                        # ONE decision for all ranks (what follows holds collectives): the slowest rank's times
             cpu = dist.get_backend() == "gloo"
@@ -1200,7 +1310,7 @@ def main():
             if dump is not None:
                 dump = dict(arrangement=f"coalesced {kc}x32", arrays=coal_last)
     predicted = None
-    if coal is not None and rank == 0:
+    if coal is not None and rank == 0 and args.full:
         try:
             predicted = bench_predicted(net, hosts, kc, ncl, args.steps, args.warmup)
             # per mel frame against the line's value (the predicted durations of these inputs do not add up to the forced 100 frames per utterance)
@@ -1208,11 +1318,11 @@ def main():
         except Exception as e:                               # (an extra: never costs the headline line)
             predicted = {"error": repr(e)[:300]}
     native = None
-    if n_fl > 1 and rank == 0 and not args.no_extras:
+    if n_fl > 1 and rank == 0 and args.full and not args.no_extras:
         native = bench_native_lanes(net, [r.g for r, _, _ in lanes], firsts, args.steps, args.warmup)
     # the same K steps with the host <-> device copies inside the timed region (every rank; max over ranks like the headline)
     transfers = None
-    if not args.no_graph and not args.global_batch and not args.no_extras:
+    if not args.no_graph and not args.global_batch and args.full and not args.no_extras:
         transfers = bench_transfers(lanes, args.steps, min(args.warmup, 10), barrier)
     if world > 1:
         t = torch.tensor([elapsed, transfers["elapsed_s"] if transfers else 0.0], dtype=torch.float64,
@@ -1228,7 +1338,7 @@ def main():
         #  resident-input time, which is `elapsed` unless the coalesced lanes' figure became the line's value)
         transfers["vs_resident_inputs"] = transfers["elapsed_s"] / (elapsed_lanes32 or elapsed)
         transfers["arrangement"] = "batches of 32, one hipGraph replay each (ms_per_step_lanes_of_32)" if elapsed_lanes32 else "as the line's value"
-    if coal and coal["adopted_as_value"]:
+    if coal and coal["adopted_as_value"] and args.full:
         # the line's value is the coalesced arrangement: its copy-inclusive figure is the library's own host boundary (as_lanes_submit_host),
         # the K steps with the copies inside the timed region; the 4 x 32 arrangement's figure stays beside it
         hbnd = dict(coal["host_boundary"])
@@ -1241,57 +1351,10 @@ def main():
         hbnd["frames_per_s_including_transfers"] = frames_total * args.steps / hbnd["elapsed_s"]
         hbnd["lanes_of_32"] = transfers
         transfers = hbnd
-    if args.global_batch:
+    if args.global_batch and args.full:
         c4 = c4_check(net, host, runner.out["mel"], mine, world, rank, dev, dist, dump=args.c4_dump)
 
-    # ---- phase times of one eager step with the branches concurrent (HIP events between the phases, on the calling stream)
-    prunner = Runner(net, g)
-    phase = [net.rt.phase_ms(prunner.step) for _ in range(3)][-1]
-    # the kernel classes AS THE TIMED REGION LAUNCHES THEM: with the coalesced arrangement adopted, one call over its 32 k utterances
-    per_call = args.call_batches
-    g_roof = g
-    if coal and coal["adopted_as_value"]:
-        per_call = coal["coalesce"]
-        g_roof = pack_inputs(merge_hosts(hosts[:per_call]), list(range(per_call * len(host["frames"]))), dev)
-    kern = profile_classes(net, Runner(net, g_roof))
-    net.rt.set_serial(args.no_concurrency)
-    gemm_tflops, gemm_peak = gemm_roofline(kern, 3)
-    k0 = kern["conv_gemm"]
-    hbm_ms = sum(kern[c]["ms_per_step"] for c in HBM_GROUP if c in kern)
-    hbm_gb = sum(kern[c]["gbyte_per_step"] for c in HBM_GROUP if c in kern)
-
-    # HBM traffic of the dominant kernel cannot be read live (PMC needs rocprofv3): it comes from the committed counter pass of this
-    # same command (profiles/latest_pmc_traffic.json, scripts/gpu_profile.sh), and only when that pass was taken from THIS build
-    traffic, traffic_src = None, "no PMC profile of this build (profiles/latest_pmc_traffic.json was taken from other kernel sources)"
-    try:
-        pj = json.load(open(os.path.join(ROOT, "profiles", "latest_pmc_traffic.json")))
-        if pj.get("source_id") == source_id() and pj.get("batches_per_call", 1) == per_call:
-            traffic, traffic_src = pj["conv_gemm_hbm_bytes_per_launch"], pj["source"]
-    except Exception:
-        pass
-
-    sus_reg, sus_lds = mfma_sustained()
     ms_per_step = elapsed / args.steps * 1e3
-    # The roofline fractions are reported from the committed rocprofv3 kernel trace of THIS build when there is one
-    # (profiles/latest_trace_classes.json: sum of kernel durations per class and step, scripts/make_profiles.py) -- a trace counts a kernel's
-    # own duration, nothing of the brackets around it -- and from this run's HIP events otherwise; the event figures stay beside them.
-    trace_cls, trace_src = None, "no kernel trace of this build under profiles/ (HIP events of this run, bracket cost removed)"
-    try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", "latest_trace_classes.json")))
-        if tj.get("source_id") == source_id() and args.config == "C3" and not args.global_batch and tj.get("batches_per_call", 1) == per_call:
-            trace_cls, trace_src = tj["classes"], f"{tj['file']} ({tj['command']}; {tj['steps_in_trace']} steps in the trace)"
-    except Exception:
-        pass
-    gemm_tflops_ev = gemm_tflops
-    hbm_ms_ev = hbm_ms
-    tc_ms = None
-    if trace_cls:                                                  # (both sides per CALL of per_call batches)
-        try:
-            tc_ms = lambda c: trace_cls[c].get("ms_per_call", trace_cls[c]["ms_per_step"] * per_call)   # (files of rounds 1-4: per step = per call)
-            gemm_tflops = k0["gflop_per_step"] / tc_ms("conv_gemm")
-            hbm_ms = sum(tc_ms(c) for c in HBM_GROUP if c in trace_cls)
-        except Exception:                                          # (a committed summary this script cannot read never costs the line)
-            trace_cls, trace_src, gemm_tflops, hbm_ms = None, "the committed kernel-trace summary is unreadable (HIP events of this run)", gemm_tflops_ev, hbm_ms_ev
     value = frames_total * args.steps / elapsed
     # the K steps of the arrangement that became `value`, timed REPEATS times back to back inside this run (rank-local; `ms_per_step` is
     # the first of them, max over ranks): min / median / max say what a 20-step measurement is worth
@@ -1319,51 +1382,18 @@ def main():
         "in_flight_note": in_flight_note,
         "rtf": (elapsed / args.steps) / (frames_total * FRAME_SEC),
         "x_realtime_per_gpu": (value / world) * FRAME_SEC,
-        "roofline": {"bound": "mfma",
-                     "kernel": "conv_gemm_h3_kernel (implicit-GEMM conv, fp16 matrix cores, two-way split operands h + l, 3 products per fp32 "
-                               "product, fp32 accumulate; both operands staged by LDS-DMA from producer-written images)",
-                     "achieved": gemm_tflops, "peak": gemm_peak, "unit": "TFLOP/s", "frac": gemm_tflops / gemm_peak,
-                     # where `achieved` / `frac` come from: "committed_trace" = the rocprofv3 kernel trace of THIS build committed under
-                     # profiles/ (matched by the kernel sources' id; not measured by this run), "events_this_run" = HIP events of this run
-                     "frac_source": "committed_trace" if trace_cls else "events_this_run",
-                     "time_source": trace_src,
-                     "achieved_by_events": gemm_tflops_ev, "frac_by_events": gemm_tflops_ev / gemm_peak,      # (always this run's)
-                     # the launches the fraction is about: one as_forward_test call over `batches_per_call` batches of 32 (the timed region's)
-                     "batches_per_call": per_call, "utterances_per_call": len(g_roof["frames"]),
-                     "gemm_ms_per_step_by_trace": tc_ms("conv_gemm") / per_call if trace_cls else None,
-                     "gemm_ms_per_step_by_events": k0["ms_per_step"] / per_call,
-                     "peak_basis": "dense fp16 MFMA 2516.6 TFLOP/s / 3 matrix-core products per fp32 product (achieved = algorithmic fp32 flop); "
-                                   "round 1 ran six bf16 products per fp32 product (ceiling 419.4)",
-                     # measured live on this device: a bare loop of the kernel's own MFMA pattern on random operands (no memory traffic, no
-                     # barriers).  The chip lowers its clock under matrix-core load on non-trivial data: `peak` above is the data sheet's.
-                     "sustained_on_random_operands": {
-                         "mfma_f16_tflops_operands_in_registers": sus_reg, "mfma_f16_tflops_operands_from_lds": sus_lds,
-                         "as_f16x3_tflops_from_lds": sus_lds / 3.0, "frac_of_nominal_peak": sus_lds / PEAK_F16_MFMA_TFLOPS,
-                         "kernel_frac_of_sustained": gemm_tflops / (sus_lds / 3.0)},
-                     "frac_of_fp32_mfma_peak": gemm_tflops / PEAK_F32_MFMA_TFLOPS,
-                     "frac_of_round1_bf16x6_ceiling": gemm_tflops / PEAK_X6_TFLOPS,
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "avg_launch_ms": k0["ms_per_step"] / max(k0["launches_per_step"], 1), "launches_per_step": k0["launches_per_step"],
-                     "event_bracket_overhead_us": bracket_overhead_ms() * 1e3,
-                     "achieved_with_bracket_overhead": k0["gflop_per_step"] / k0["ms_per_step_bracketed"],
-                     "algorithmic_gflop_per_step": k0["gflop_per_step"] / per_call},
-        "roofline_hbm": {"bound": "hbm", "kernels": "AdaIN / LayerNorm operand-image writers, pooling, expansion, im2col, reference features "
-                                                    "(classes adain + layernorm + other of the event profiler)",
-                         "achieved": hbm_gb / hbm_ms if hbm_ms else None, "peak": PEAK_HBM_TBS, "unit": "TB/s",
-                         "frac": hbm_gb / hbm_ms / PEAK_HBM_TBS if hbm_ms else None,
-                         "frac_source": "committed_trace" if trace_cls else "events_this_run",
-                         "batches_per_call": per_call,
-                         "algorithmic_gbyte_per_step": hbm_gb / per_call, "ms_per_step": hbm_ms / per_call, "time_source": trace_src,
-                         "ms_per_step_by_events": hbm_ms_ev / per_call, "frac_by_events": hbm_gb / hbm_ms_ev / PEAK_HBM_TBS if hbm_ms_ev else None,
-                         "launches_per_step": sum(kern[c]["launches_per_step"] for c in HBM_GROUP if c in kern)},
-        "launches_per_step": {c: kern[c]["launches_per_step"] for c in kern},       # (per call of `roofline.batches_per_call` batches, like kernel_classes)
-        "forward_calls_in_process": None,
-        "kernel_classes": kern,
-        "phase_ms_eager": dict(zip(["features", "encoders_towers_duration", "predictors", "decoder"], [round(v, 3) for v in phase])),
     }
+    if args.full:
+        # the kernel classes AS THE TIMED REGION LAUNCHES THEM: with the coalesced arrangement adopted, one call over its 32 k utterances
+        per_call = args.call_batches
+        g_roof = g
+        if coal and coal["adopted_as_value"]:
+            per_call = coal["coalesce"]
+            g_roof = pack_inputs(merge_hosts(hosts[:per_call]), list(range(per_call * len(host["frames"]))), dev)
+        line.update(kernel_figures(net, g, g_roof, per_call, args))
     if c4 is not None:
         line["c4_shard_check"] = c4
-    extras = rank == 0 and not args.no_extras and not args.global_batch and args.config == "C3"
+    extras = args.full and rank == 0 and not args.no_extras and not args.global_batch and args.config == "C3"
     if transfers:
         line["transfers"] = transfers
     if native:
@@ -1378,7 +1408,7 @@ def main():
             line["surface"] = bench_surface(net, dev)
         except Exception as e:                          # (an extra: never costs the headline line)
             line["surface"] = {"error": repr(e)[:300]}
-    if rank == 0 and args.cpu_utts > 0 and not args.global_batch and args.config == "C3":
+    if args.full and rank == 0 and args.cpu_utts > 0 and not args.global_batch and args.config == "C3":
         cb, outs = cpu_baseline(host, sd, args.cpu_utts)
         line["cpu_baseline"] = cb
         fo = np.concatenate([[0], np.cumsum([2 * f for f in g["frames"]])])

@@ -68,7 +68,7 @@ def trace_classes(stats_csv, bench_line_json, out_json, tag):
     m = re.search(r"ONE call over (\d+) batches", line["config"]["workload"])
     bpc = int(m.group(1)) if m else 1                                   # batches of 32 per traced call (bench.py --call-batches)
     out = dict(source_id=source_id(), steps_in_trace=steps, batches_per_call=bpc, file=f"profiles/{tag}_kernel_stats.csv",
-               command="rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --no-graph --no-concurrency --cpu-utts 0 --no-extras"
+               command="rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 2 --no-graph --no-concurrency --cpu-utts 0 --no-extras"
                        + (f" --call-batches {bpc}" if bpc > 1 else ""),
                classes={c: dict(ms_per_call=v[0] / steps, ms_per_step=v[0] / steps / bpc, launches_per_call=v[1] / steps) for c, v in agg.items()})
     json.dump(out, open(out_json, "w"), indent=1)

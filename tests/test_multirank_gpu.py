@@ -67,7 +67,7 @@ def test_two_ranks_c4_global_batch_sharded(cuda, tmp_path):
     from artspeech_amd.weights import DEFAULT_STATS, fold_state_dict, load_distribution
     from oracle import acoustic
     dump = str(tmp_path / "c4.npz")
-    line = launch(["--steps", "3", "--warmup", "1", "--global-batch", "256", "--c4-dump", dump])
+    line = launch(["--steps", "3", "--warmup", "1", "--global-batch", "256", "--full", "--c4-dump", dump])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     c4 = line["c4_shard_check"]
     assert c4["utterances"] == 256 and c4["shards"] == 2
