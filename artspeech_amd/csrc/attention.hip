@@ -17,6 +17,11 @@
 //                                  (K tile rows padded to 65 floats -> conflict-free), softmax statistics by wave shuffles; PV: lane = channel.
 //   relpos_attention_image_kernel  the path (128-channel heads): matrix cores, operands straight from the q/k/v GEMM's operand image
 //                                  (as_relpos_attention_image_f32; described above the kernel).
+// Envelope (oracle/attn_ref.py derives it per element; tests/test_attn_bound_gpu.py checks it from a flat to a one-hot softmax, V over
+// 2^-24 .. 2^14): the exact kernel is off by fp32 roundings only, relative to sum_j p_ij |v'_j| and to the logits' sizes.  The image
+// kernel adds 2^-20 of the same relative terms and ABSOLUTE floors: 2^-25 per unit of |q|, |k|, |Ek| in every logit, and -- P is split
+// without a scale, so its l part is an fp16 subnormal below p = 2^-3 -- up to 2^-25 |v'_j| per key in the output: N 2^-25 max |v| / l
+// at worst (flat weights below 2^-3 over N keys), not 22 bits of the output.
 #include <cstring>
 #include "common.h"
 #include "artspeech_hip.h"

@@ -20,6 +20,8 @@
 // operand of O^T += V^T . P^T by the v_permlane32_swap that conv_gemm.h's yh_store_tile uses.  V^T rows (8 consecutive keys of a
 // channel) come from the fp32 copy of the projection.  u and v are folded into the projection's bias (ema.py stacks the query weights
 // twice: rows q + u, q + v, k, v), so (q + u) . k is computed as the reference computes it.  No barrier: waves are independent.
+// Envelope (oracle/attn_ref.py, checked by tests/test_attn_bound_gpu.py): 2^-20 relative in every product, with ABSOLUTE floors of
+// 2^-25 per unit of |q + u|, |k|, |q + v|, |p| in every logit, and up to 2^-25 |v_j| per key in the output (P is split unscaled).
 #include "conv_gemm.h"
 #define AS_FILE_CLS AS_CLS_ATTN
 
@@ -51,6 +53,10 @@ __global__ void __launch_bounds__(256) xl_attention_mfma_kernel(const XlArgs a)
     const int b = blockIdx.z, h = blockIdx.y;
     const int o0 = a.col_off[b], T = a.col_off[b + 1] - o0;
     const int i0 = 31 * ((int)blockIdx.x * 4 + wave);
+    if (a.oh && b == 0 && blockIdx.x == 0 && wave == 0 && lane < 16) {  // the image's zero column: this head's 4 k-blocks x 4 planes,
+        const size_t pz = (size_t)(h * 16 + lane);                        // written before any wave leaves (utterance 0 may be empty)
+        reinterpret_cast<u32x4_t*>(a.oh)[pz * ((size_t)a.N + 1) + a.N] = u32x4_t{0u, 0u, 0u, 0u};
+    }
     if (i0 >= T) return;                                                 // (no barrier below: a wave leaves alone)
     float* sc = xsm + wave * (64 * 32);                                  // this wave's shift scratch [64][32]
     const unsigned NX = (unsigned)a.N + 1u;                              // columns of an image plane (the last one is zero)
@@ -219,7 +225,6 @@ __global__ void __launch_bounds__(256) xl_attention_mfma_kernel(const XlArgs a)
     if (a.oh) {                                                          // 16-byte rows of 8 consecutive channels (conv_gemm.h yh_store_tile)
         const __amdgpu_buffer_rsrc_t rsO =
             __builtin_amdgcn_make_buffer_rsrc(a.oh, 0, (int)((unsigned)as_kbx(a.C) * 4u * NX * 16u), 0x00020000);
-        const u32x4_t z = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -239,10 +244,6 @@ __global__ void __launch_bounds__(256) xl_attention_mfma_kernel(const XlArgs a)
                 const unsigned off = mine ? (pl * NX + (unsigned)(o0 + i)) * 16u : OOBH;
                 __builtin_amdgcn_raw_buffer_store_b128(hh, rsO, off, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b128(ll, rsO, off + 2u * NX * 16u, 0, 0);
-                if (b == 0 && i == 0) {                                  // the image's zero column, once per (channel group, part)
-                    __builtin_amdgcn_raw_buffer_store_b128(z, rsO, (pl * NX + zc) * 16u, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(z, rsO, ((pl + 2u) * NX + zc) * 16u, 0, 0);
-                }
             }
     }
 }
