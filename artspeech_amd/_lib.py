@@ -32,7 +32,7 @@ _SIGNATURES = {
 }
 
 AS_MAX_TAPS = 25
-AS_ABI_VERSION = 8          # include/artspeech_hip.h
+AS_ABI_VERSION = 9          # include/artspeech_hip.h
 
 
 class ConvGemmArgs(ctypes.Structure):
@@ -149,15 +149,18 @@ class ForwardIO(ctypes.Structure):
     _fields_ = [("tokens", c_p), ("mel", c_p), ("ld_mel", ctypes.c_int32), ("f0_raw", c_p), ("ema_raw", c_p), ("ld_ema", ctypes.c_int32),
                 ("forced_dur", c_p), ("mel_out", c_p), ("ld_out", ctypes.c_int32), ("duration", c_p), ("dur_i", c_p), ("frame_off", c_p),
                 ("style", c_p), ("feat12", c_p), ("ld_feat", ctypes.c_int32), ("t_en", c_p), ("a_en", c_p), ("ld_en", ctypes.c_int32),
-                ("F0", c_p), ("N", c_p), ("EMA", c_p), ("ld_pred", ctypes.c_int32), ("frame_cap", ctypes.c_int32), ("segs", c_p)]
+                ("F0", c_p), ("N", c_p), ("EMA", c_p), ("ld_pred", ctypes.c_int32), ("frame_cap", ctypes.c_int32), ("segs", c_p),
+                ("voices", c_p), ("ld_voice", ctypes.c_int32), ("n_voices", ctypes.c_int32), ("voice_idx", c_p)]
 
 
 class HostIO(ctypes.Structure):                 # as_host_io: HOST pointers (as_lanes_submit_host)
     _fields_ = [("tokens", c_p), ("mel", c_p), ("ld_mel", ctypes.c_int32), ("f0_raw", c_p), ("ema_raw", c_p), ("ld_ema", ctypes.c_int32),
-                ("forced_dur", c_p), ("mel_out", c_p), ("ld_out", ctypes.c_int32), ("frame_cap", ctypes.c_int32), ("frame_off", c_p)]
+                ("forced_dur", c_p), ("mel_out", c_p), ("ld_out", ctypes.c_int32), ("frame_cap", ctypes.c_int32), ("frame_off", c_p),
+                ("voices", c_p), ("ld_voice", ctypes.c_int32), ("n_voices", ctypes.c_int32), ("voice_idx", c_p)]   # voices: DEVICE, voice_idx: HOST
 
 
-AS_MOD_FORWARD_A, AS_MOD_FORWARD_B, AS_MOD_ENCODER, AS_MOD_STYLE, AS_MOD_DURATION, AS_MOD_ARTS, AS_MOD_DECODER, AS_MOD_FORWARD_B_CAP = range(8)
+(AS_MOD_FORWARD_A, AS_MOD_FORWARD_B, AS_MOD_ENCODER, AS_MOD_STYLE, AS_MOD_DURATION, AS_MOD_ARTS, AS_MOD_DECODER, AS_MOD_FORWARD_B_CAP,
+ AS_MOD_VOICE, AS_MOD_FORWARD_A_VOICE) = range(10)
 _pB, _pIO = ctypes.POINTER(Batch), ctypes.POINTER(ForwardIO)
 _SIGNATURES.update({
     "as_adain_image_f32": (c_i, [ctypes.POINTER(AdainArgs), c_p]),
@@ -189,6 +192,8 @@ _SIGNATURES.update({
     "as_encoder_forward": (c_i, [c_p, c_p, c_i, _pB, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "as_style_forward": (c_i, [c_p, c_p, _pB, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
     "as_duration_forward": (c_i, [c_p, c_p, _pB, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "as_voice_dim": (c_i, [c_p]),
+    "as_voice_forward": (c_i, [c_p, c_p, _pB, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_sz, c_p]),
     "as_arts_forward": (c_i, [c_p, c_p, _pB, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "as_decoder_forward": (c_i, [c_p, c_p, _pB, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_sz, c_p]),
     "as_forward_test_begin": (c_i, [c_p, c_p, _pB, _pIO, c_p, c_sz, c_p]),
@@ -253,7 +258,8 @@ STATUS_NAMES = ("clustered LSTM hand-over timed out", "MAS band hand-over timed 
                 "non-finite accumulator (an operand beyond fp16's range, or a non-finite input)",
                 "a layout the kernels cannot serve: an utterance wider than the column descriptors (AS_META_MAX_W) or than its caller said, "
                 "or (as_lanes debug mode) device buffers that changed while their submission was waiting for its group",
-                "the predicted durations add up to more frames than the capacity the caller named (as_forward_io.frame_cap)")
+                "the predicted durations add up to more frames than the capacity the caller named (as_forward_io.frame_cap)",
+                "a voice index outside [0, n_voices) (as_forward_io.voice_idx): that utterance got a zero voice")
 
 
 def device_status(clear=False):

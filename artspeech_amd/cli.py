@@ -7,6 +7,10 @@ stage on the HIP path (log-mel front end, JDCNet, EMA_Predictor, acoustic model,
 What test.py does and this does not: espeak phonemisation (pass the phoneme string the phonemizer prints, test.py:95), and
 librosa's load / trim / resample (the wave must already be 24 kHz mono PCM; it is read with the standard library).
 ``--synthetic`` replaces every checkpoint by the seeded synthetic weights the tests use (the reference ships no weights).
+
+One voice, many sentences: ``--save-voice voice.npz`` (with ``--ref-wav``) also writes the voice computed from the reference, and
+``--voice voice.npz`` replaces ``--ref-wav`` in later runs -- the reference is not processed again.  Exactly one of ``--ref-wav`` and
+``--voice`` is given.
 """
 import argparse
 import json
@@ -40,11 +44,14 @@ def write_wav(path, x, sr=24000):
         f.writeframes((pcm * 32767.0).astype(np.int16).tobytes())
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", help="Configs/config.yaml of the reference (model_params, stats_path, pretrained_model)")
     ap.add_argument("--phonemes", required=True, help="the phoneme string espeak produces for the text (test.py:94-95)")
-    ap.add_argument("--ref-wav", required=True, help="reference utterance, 24 kHz mono PCM wav")
+    ref = ap.add_mutually_exclusive_group(required=True)
+    ref.add_argument("--ref-wav", help="reference utterance, 24 kHz mono PCM wav")
+    ref.add_argument("--voice", help="a voice saved with --save-voice (in place of --ref-wav)")
+    ap.add_argument("--save-voice", metavar="PATH", help="with --ref-wav: also write the voice computed from it (.npz)")
     ap.add_argument("--out", default="output.wav")
     ap.add_argument("--jdc", help="Utils/JDC/bst.t7")
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
@@ -52,7 +59,19 @@ def main(argv=None):
     ap.add_argument("--vocoder", help="Vocoder/g_00935000")
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights instead of checkpoints (smoke / demo)")
     ap.add_argument("--tiny", action="store_true", help="with --synthetic: the small test configuration")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
+    if a.save_voice and not a.ref_wav:
+        ap.error("--save-voice needs --ref-wav (the voice is computed from it)")
+    return ap, a
+
+
+def main(argv=None):
+    ap, a = parse_args(argv)
 
     from . import ema as E, jdc as J, synth, vocoder as V
     from .pipeline import ArtSpeech
@@ -73,7 +92,15 @@ def main(argv=None):
         tts.attach_ema_extractor(a.ema)
         h = json.load(open(a.vocoder_config)) if a.vocoder_config else None
         tts.attach_vocoder(h, a.vocoder)
-    audio = tts.synthesis_from_wave(a.phonemes, read_wav(a.ref_wav))
+    if a.voice:
+        from .pipeline import Voice
+        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts))
+    else:
+        wave_in = read_wav(a.ref_wav)
+        if a.save_voice:
+            tts.voice_from_wave(wave_in).save(a.save_voice)
+            print(f"{a.save_voice}: voice of {a.ref_wav}")
+        audio = tts.synthesis_from_wave(a.phonemes, wave_in)
     write_wav(a.out, audio.cpu().numpy())
     print(f"{a.out}: {audio.numel() / 24000.0:.2f} s of audio from {tts._last_frames[0]} mel frames")
     return 0

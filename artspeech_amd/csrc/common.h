@@ -83,6 +83,10 @@ struct AsSegScatter {
     float* dst[16]; int32_t ld_dst[16];
 };
 int as_seg_scatter_launch(const AsSegScatter& a, hipStream_t stream);
+// voice mode (voice.hip): utterance b's Style [n_style] and dur_style [n_dur] from row idx[b] (NULL: b) of voices [n_voices][ld_voice];
+// an index outside [0, n_voices) writes zeros and raises AS_STATUS_BAD_VOICE
+int as_voice_gather_launch(const float* voices, int ld_voice, int n_voices, const int32_t* idx, int B, int n_style, int n_dur, float* style,
+                           int ld_style, float* ds, int ld_ds, hipStream_t stream);
 
 // kernel classes for the optional event profiler (prof.hip)
 enum { AS_CLS_GEMM = 0, AS_CLS_ADAIN = 1, AS_CLS_LN = 2, AS_CLS_ATTN = 3, AS_CLS_LSTM = 4, AS_CLS_MAS = 5, AS_CLS_OTHER = 6, AS_N_CLS = 7 };

@@ -60,7 +60,9 @@ struct Lane {
         size_t bytes = 0;
         int cap_tok = 0, cap_ref = 0, cap_out = 0, cap_utt = 0;  // tokens / reference frames / mel frames (columns) / utterances the block holds
         int used_tok = 0, used_ref = 0, used_out = 0, used_utt = 0;   // ... of which the group that is being filled has taken
+        int used_vid = 0;                                         // voice indices taken (one per utterance: a group's indices lie back to back)
         int32_t *tokens = nullptr, *forced = nullptr, *foff = nullptr;   // (foff: frame offsets of submissions under a frame capacity, [utterances + 1] each)
+        int32_t* vidx = nullptr;                                  // voice indices of voice-mode submissions [utterances]
         float *f0 = nullptr, *ema = nullptr, *mel = nullptr, *out = nullptr;
     } blk[2];                                                     // two, alternating from group to group: the next group's copies run under this group's kernels
     int cur = 0;                                                  // the block the group that is being filled lives in
@@ -93,13 +95,14 @@ std::string key_of(const as_batch* b, const as_forward_io* io)
     std::string k;
     put(k, b->B);
     k.append(reinterpret_cast<const char*>(b->tok_lens), sizeof(int32_t) * b->B);
-    k.append(reinterpret_cast<const char*>(b->ref_lens), sizeof(int32_t) * b->B);
+    if (b->ref_lens) k.append(reinterpret_cast<const char*>(b->ref_lens), sizeof(int32_t) * b->B);
     if (b->frames) k.append(reinterpret_cast<const char*>(b->frames), sizeof(int32_t) * b->B);
     put(k, io->tokens); put(k, io->mel); put(k, io->ld_mel); put(k, io->f0_raw); put(k, io->ema_raw); put(k, io->ld_ema);
     put(k, io->forced_dur); put(k, io->mel_out); put(k, io->ld_out); put(k, io->duration); put(k, io->dur_i); put(k, io->frame_off);
     put(k, io->style); put(k, io->feat12); put(k, io->ld_feat); put(k, io->t_en); put(k, io->a_en); put(k, io->ld_en);
     put(k, io->F0); put(k, io->N); put(k, io->EMA); put(k, io->ld_pred);
     put(k, io->frame_cap);
+    put(k, io->voices); put(k, io->ld_voice); put(k, io->n_voices); put(k, io->voice_idx);   // (the indices' CONTENTS are read at replay)
     if (io->segs) {
         const as_segments& g = *io->segs;
         put(k, g.n);
@@ -309,7 +312,7 @@ static int lane_run(as_lanes* q, const as_batch* batch, const as_forward_io* io,
     // the lane's previous batch has left its workspaces (and the caller's buffers of that lane)
     if (hipStreamSynchronize(L.stream) != hipSuccess) return (int)hipErrorUnknown;
     // (sizes come from the eager plan: a count pass adds host-side layout entries, which that plan may flush; the graph plan stays small)
-    const size_t na = as_module_workspace_bytes(q->m, L.plan, AS_MOD_FORWARD_A, batch);
+    const size_t na = as_module_workspace_bytes(q->m, L.plan, io->voices ? AS_MOD_FORWARD_A_VOICE : AS_MOD_FORWARD_A, batch);
     if (!na) return AS_EINVAL;
     // workspace B depends on the frame counts: known (forced durations / a second pass), a capacity the caller named (frame_cap: the call
     // then runs like one with known counts -- eager, captured, replayed), or sized for what the output buffer can hold
@@ -415,6 +418,17 @@ static bool plain_io(const as_forward_io* io)                     // only the me
 {
     return !io->duration && !io->dur_i && !io->frame_off && !io->style && !io->feat12 && !io->t_en && !io->a_en && !io->F0 && !io->N && !io->EMA;
 }
+// Voice mode (as_forward_io.voices): the voice of utterance b of the merged call must still be utterance b's -- indices that continue where
+// the previous submission's end, into the same table; or no indices (row b) and the rows continuing where the previous submission's end (a
+// table of at least its own rows: with fewer it raises AS_STATUS_BAD_VOICE alone and is not merged).  Never with a reference submission.
+static bool voices_adjacent(const as_forward_io& a, long prev_B, const as_forward_io* io)
+{
+    if ((io->voices != nullptr) != (a.voices != nullptr)) return false;
+    if (!io->voices) return true;
+    if (io->voice_idx && a.voice_idx)
+        return io->voices == a.voices && io->ld_voice == a.ld_voice && io->n_voices == a.n_voices && io->voice_idx == a.voice_idx + prev_B;
+    return !io->voice_idx && !a.voice_idx && io->ld_voice == a.ld_voice && a.n_voices >= prev_B && io->voices == a.voices + prev_B * a.ld_voice;
+}
 static bool adjacent(const Lane::Pending& p, const as_forward_io* io, bool cap_mode)
 {
     long nt = 0, nr = 0, nf = 0;
@@ -423,8 +437,10 @@ static bool adjacent(const Lane::Pending& p, const as_forward_io* io, bool cap_m
     for (int32_t v : p.frames) nf += v;
     const as_forward_io& a = p.io;
     if (cap_mode != (p.frames.empty() && a.frame_cap > 0)) return false;   // (a group is of one kind)
-    const bool in = io->tokens == a.tokens + nt && io->mel == a.mel + nr && io->ld_mel == a.ld_mel && io->f0_raw == a.f0_raw + nr &&
-                    io->ema_raw == a.ema_raw + nr && io->ld_ema == a.ld_ema;
+    if (!voices_adjacent(a, (long)p.tok_lens.size(), io)) return false;
+    const bool in = io->tokens == a.tokens + nt &&
+                    (io->voices || (io->mel == a.mel + nr && io->ld_mel == a.ld_mel && io->f0_raw == a.f0_raw + nr && io->ema_raw == a.ema_raw + nr &&
+                                    io->ld_ema == a.ld_ema));
     // under a frame capacity every submission keeps its own output buffer (as_segments: the merged call's mel is dealt out to them)
     if (cap_mode) return in && !io->forced_dur && !a.forced_dur;
     return in && ((!io->forced_dur && !a.forced_dur) || (io->forced_dur && a.forced_dur && io->forced_dur == a.forced_dur + nt)) &&
@@ -439,7 +455,7 @@ static bool plain_cap_io(const as_forward_io* io)
 // ---- debug mode (as_lanes_set_debug, AS_DEBUG=1) -------------------------------------------------------------------------------------
 // Under coalescing a submission's device buffers are read when its GROUP is launched, not when it is submitted: a caller that refills them
 // in between corrupts a batch without any sign.  Debug mode makes that loud: the inputs of a held-back submission (tokens, forced
-// durations, f0, the EMA and mel rows) are checksummed on the lane's stream when it is submitted -- the call then WAITS for that stream,
+// durations, f0, the EMA and mel rows; in voice mode the voice indices) are checksummed on the lane's stream when it is submitted -- the call then WAITS for that stream,
 // so the sum is of the data the caller handed over -- and again when the group goes out; a difference raises AS_STATUS_BAD_LAYOUT (the
 // group's launch returns AS_EDEVICE, as every entry point does while a bit is set).  Costs a stream synchronisation per submission.
 __global__ void __launch_bounds__(256)
@@ -474,9 +490,13 @@ static int inputs_sum(as_lanes* q, Lane& L, const std::vector<int32_t>& tok_lens
     };
     add(io.tokens, nt, 1, nt, 0x100000000ull);
     add(io.forced_dur, nt, 1, nt, 0x200000000ull);
-    add(io.f0_raw, nr, 1, nr, 0x300000000ull);
-    add(io.ema_raw, nr, 10, io.ld_ema, 0x400000000ull);
-    add(io.mel, nr, q->cfg.n_mels, io.ld_mel, 0x500000000ull);
+    if (io.voices) {
+        add(io.voice_idx, (long)tok_lens.size(), 1, (long)tok_lens.size(), 0x600000000ull);
+    } else {
+        add(io.f0_raw, nr, 1, nr, 0x300000000ull);
+        add(io.ema_raw, nr, 10, io.ld_ema, 0x400000000ull);
+        add(io.mel, nr, q->cfg.n_mels, io.ld_mel, 0x500000000ull);
+    }
     AS_CHECK_LAUNCH();
     AS_CHECK(hipMemcpyAsync(sum, L.dbg, sizeof(unsigned long long), hipMemcpyDeviceToHost, L.stream));
     AS_CHECK(hipStreamSynchronize(L.stream));
@@ -510,6 +530,14 @@ static int flush_lane(as_lanes* q, int lane)
     b.B = (int32_t)tl.size();
     b.tok_lens = tl.data(); b.ref_lens = rl.data(); b.frames = fr.data();
     as_forward_io io = L.pend.front().io;
+    if (io.voices) {
+        b.ref_lens = nullptr;                                     // (voice mode reads no reference lengths)
+        if (!io.voice_idx && L.pend.size() > 1) {                 // rows b of the merged call: the last submission's table bounds the group's
+            long rows = 0;
+            for (size_t i = 0; i + 1 < L.pend.size(); ++i) rows += (long)L.pend[i].tok_lens.size();
+            io.n_voices = (int32_t)std::min<long>(INT_MAX, rows + L.pend.back().io.n_voices);
+        }
+    }
     as_segments segs;
     if (fr.empty()) {                                             // submissions under a frame capacity: the merged call deals its mel out to them
         b.frames = nullptr;
@@ -580,7 +608,7 @@ static int flush_lane(as_lanes* q, int lane)
 static int lanes_submit(as_lanes* q, const as_batch* batch, const as_forward_io* io, int32_t* frames_host_out, int32_t* lane_out,
                         float* out_host = nullptr, int32_t ld_out_host = 0, int32_t* foff_host = nullptr)
 {
-    if (!q || !batch || !io || batch->B <= 0 || !batch->tok_lens || !batch->ref_lens) return AS_EINVAL;
+    if (!q || !batch || !io || batch->B <= 0 || !batch->tok_lens || (!batch->ref_lens && !io->voices)) return AS_EINVAL;
     Lane& L = q->lanes[q->next];
     // (a host submission always joins the group of its lane's block -- a group of one when coalescing is off)
     const bool cap_mode = !batch->frames && io->frame_cap > 0;
@@ -598,7 +626,7 @@ static int lanes_submit(as_lanes* q, const as_batch* batch, const as_forward_io*
     Lane& L2 = q->lanes[q->next];
     Lane::Pending p;
     p.tok_lens.assign(batch->tok_lens, batch->tok_lens + batch->B);
-    p.ref_lens.assign(batch->ref_lens, batch->ref_lens + batch->B);
+    if (!io->voices) p.ref_lens.assign(batch->ref_lens, batch->ref_lens + batch->B);
     if (batch->frames) p.frames.assign(batch->frames, batch->frames + batch->B);
     p.io = *io;
     p.out_host = out_host;
@@ -648,7 +676,7 @@ static int block_fit(as_lanes* q, Lane& L, long nt, long nr, long nf2, int n_utt
                 return (int)hipErrorOutOfMemory;
     }
     Lane::Block& b = L.blk[L.cur];
-    if (L.pend.empty()) b.used_tok = b.used_ref = b.used_out = b.used_utt = 0;   // a new group starts at the block's first column
+    if (L.pend.empty()) b.used_tok = b.used_ref = b.used_out = b.used_utt = b.used_vid = 0;   // a new group starts at the block's first column
     if (b.dev && b.used_tok + nt <= b.cap_tok && b.used_ref + nr <= b.cap_ref && b.used_out + nf2 <= b.cap_out &&
         b.used_utt + n_utt + 1 <= b.cap_utt)
         return AS_OK;
@@ -657,7 +685,7 @@ static int block_fit(as_lanes* q, Lane& L, long nt, long nr, long nf2, int n_utt
     const int ct = std::max(b.cap_tok, grow_to(nt, k)), cr = std::max(b.cap_ref, grow_to(nr, k)), co = std::max(b.cap_out, grow_to(nf2, k));
     const int cu = std::max(b.cap_utt, grow_to(n_utt + 1, k));
     const int n_mels = q->cfg.n_mels;
-    const size_t bytes = 2 * up256((size_t)ct * 4) + up256((size_t)cu * 4) + up256((size_t)cr * 4) + up256((size_t)10 * cr * 4) +
+    const size_t bytes = 2 * up256((size_t)ct * 4) + 2 * up256((size_t)cu * 4) + up256((size_t)cr * 4) + up256((size_t)10 * cr * 4) +
                          up256((size_t)n_mels * cr * 4) + up256((size_t)n_mels * co * 4);
     AS_CHECK(hipStreamSynchronize(L.stream));                     // the groups that used the old block have left it: kernels ...
     AS_CHECK(hipStreamSynchronize(q->d2h));                       // ... and the copies of their results
@@ -675,6 +703,7 @@ static int block_fit(as_lanes* q, Lane& L, long nt, long nr, long nf2, int n_utt
     b.tokens = reinterpret_cast<int32_t*>(c); c += up256((size_t)ct * 4);
     b.forced = reinterpret_cast<int32_t*>(c); c += up256((size_t)ct * 4);
     b.foff = reinterpret_cast<int32_t*>(c); c += up256((size_t)cu * 4);
+    b.vidx = reinterpret_cast<int32_t*>(c); c += up256((size_t)cu * 4);
     b.f0 = reinterpret_cast<float*>(c); c += up256((size_t)cr * 4);
     b.ema = reinterpret_cast<float*>(c); c += up256((size_t)10 * cr * 4);
     b.mel = reinterpret_cast<float*>(c); c += up256((size_t)n_mels * cr * 4);
@@ -684,27 +713,38 @@ static int block_fit(as_lanes* q, Lane& L, long nt, long nr, long nf2, int n_utt
 
 static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_io* h, int32_t* lane_out)
 {
-    if (!q || !batch || !h || batch->B <= 0 || !batch->tok_lens || !batch->ref_lens) return AS_EINVAL;
-    if (!h->tokens || !h->mel || !h->f0_raw || !h->ema_raw || !h->mel_out) return AS_EINVAL;
+    if (!q || !batch || !h || batch->B <= 0 || !batch->tok_lens || (!batch->ref_lens && !h->voices)) return AS_EINVAL;
+    if (!h->tokens || !h->mel_out || (!h->voices && (!h->mel || !h->f0_raw || !h->ema_raw))) return AS_EINVAL;
+    const bool voice = h->voices != nullptr;                      // (voice mode: the table stays where it is, the indices travel with the tokens)
     // frame counts from the caller, or a capacity (durations predicted on the device: the frame offsets come back with the mel)
     const bool cap_mode = !batch->frames;
     if (cap_mode && (h->frame_cap < 1 || !h->frame_off || h->forced_dur)) return AS_EINVAL;
     long nt = 0, nr = 0, nf = 0;
     for (int b = 0; b < batch->B; ++b) {
-        if (batch->tok_lens[b] < 0 || batch->ref_lens[b] < 0 || (!cap_mode && batch->frames[b] < 0)) return AS_EINVAL;
-        nt += batch->tok_lens[b]; nr += batch->ref_lens[b]; nf += cap_mode ? 0 : batch->frames[b];
+        if (batch->tok_lens[b] < 0 || (!voice && batch->ref_lens[b] < 0) || (!cap_mode && batch->frames[b] < 0)) return AS_EINVAL;
+        nt += batch->tok_lens[b]; nr += voice ? 0 : batch->ref_lens[b]; nf += cap_mode ? 0 : batch->frames[b];
     }
     if (cap_mode) nf = h->frame_cap;
-    if (h->ld_mel < nr || h->ld_ema < nr || h->ld_out < 2 * nf) return AS_EINVAL;
+    if ((!voice && (h->ld_mel < nr || h->ld_ema < nr)) || h->ld_out < 2 * nf) return AS_EINVAL;
     const int n_mels = q->cfg.n_mels;
     for (int attempt = 0;; ++attempt) {
         Lane& L = q->lanes[q->next];
         // what waits on this lane came with device buffers of the caller's, or the block is full: that group goes out first
         size_t waiting = 0;
         for (const Lane::Pending& p : L.pend) waiting += p.tok_lens.size();
+        // (voice mode: the group's indices lie back to back in the block, so indexed submissions of one table always continue each other)
+        bool voice_fits = true;
+        if (!L.pend.empty()) {
+            const as_forward_io& a = L.pend.back().io;
+            const long prev_B = (long)L.pend.back().tok_lens.size();
+            voice_fits = (a.voices != nullptr) == voice &&
+                         (!voice || (h->voice_idx ? (a.voice_idx && a.voices == h->voices && a.ld_voice == h->ld_voice && a.n_voices == h->n_voices)
+                                                  : (!a.voice_idx && a.ld_voice == h->ld_voice && a.n_voices >= prev_B &&
+                                                     h->voices == a.voices + prev_B * a.ld_voice)));
+        }
         const bool foreign = !L.pend.empty() && (!L.pend.back().out_host || (L.pend.back().io.forced_dur != nullptr) != (h->forced_dur != nullptr) ||
                                                  waiting + (size_t)batch->B > 1024 || L.pend.back().frames.empty() != cap_mode ||
-                                                 (cap_mode && L.pend.size() >= (size_t)AS_MAX_SEGMENTS));
+                                                 (cap_mode && L.pend.size() >= (size_t)AS_MAX_SEGMENTS) || !voice_fits);
         int rc = foreign ? AS_ENOSPC : block_fit(q, L, nt, nr, 2 * nf, batch->B, std::max(q->coalesce, 1));
         if (rc == AS_ENOSPC && attempt <= (int)q->lanes.size()) {
             rc = flush_lane(q, q->next);                          // (the turn passes on: the submission opens the next lane's group)
@@ -719,7 +759,8 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
         if (L.pend.empty() && L.blk_used[L.cur]) AS_CHECK(hipStreamWaitEvent(s, L.ev_d2h[L.cur], 0));
         AS_CHECK(hipMemcpyAsync(b.tokens + b.used_tok, h->tokens, (size_t)nt * 4, hipMemcpyHostToDevice, s));
         if (h->forced_dur) AS_CHECK(hipMemcpyAsync(b.forced + b.used_tok, h->forced_dur, (size_t)nt * 4, hipMemcpyHostToDevice, s));
-        AS_CHECK(hipMemcpyAsync(b.f0 + b.used_ref, h->f0_raw, (size_t)nr * 4, hipMemcpyHostToDevice, s));
+        if (voice && h->voice_idx) AS_CHECK(hipMemcpyAsync(b.vidx + b.used_vid, h->voice_idx, (size_t)batch->B * 4, hipMemcpyHostToDevice, s));
+        if (!voice) AS_CHECK(hipMemcpyAsync(b.f0 + b.used_ref, h->f0_raw, (size_t)nr * 4, hipMemcpyHostToDevice, s));
         if (nr > 0) {
             AS_CHECK(hipMemcpy2DAsync(b.ema + b.used_ref, (size_t)b.cap_ref * 4, h->ema_raw, (size_t)h->ld_ema * 4, (size_t)nr * 4, 10, hipMemcpyHostToDevice, s));
             AS_CHECK(hipMemcpy2DAsync(b.mel + b.used_ref, (size_t)b.cap_ref * 4, h->mel, (size_t)h->ld_mel * 4, (size_t)nr * 4, (size_t)n_mels,
@@ -728,9 +769,14 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
         as_forward_io io;
         memset(&io, 0, sizeof(io));
         io.tokens = b.tokens + b.used_tok;
-        io.mel = b.mel + b.used_ref; io.ld_mel = b.cap_ref;
-        io.f0_raw = b.f0 + b.used_ref;
-        io.ema_raw = b.ema + b.used_ref; io.ld_ema = b.cap_ref;
+        if (voice) {
+            io.voices = h->voices; io.ld_voice = h->ld_voice; io.n_voices = h->n_voices;
+            io.voice_idx = h->voice_idx ? b.vidx + b.used_vid : nullptr;
+        } else {
+            io.mel = b.mel + b.used_ref; io.ld_mel = b.cap_ref;
+            io.f0_raw = b.f0 + b.used_ref;
+            io.ema_raw = b.ema + b.used_ref; io.ld_ema = b.cap_ref;
+        }
         io.forced_dur = h->forced_dur ? b.forced + b.used_tok : nullptr;
         io.mel_out = b.out + b.used_out; io.ld_out = b.cap_out;
         if (cap_mode) {
@@ -738,7 +784,7 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
             io.frame_off = b.foff + b.used_utt;
         }
         // (a group mixes forced and predicted-from-known-frames submissions only if all or none bring forced durations: `adjacent` says no otherwise)
-        b.used_tok += (int)nt; b.used_ref += (int)nr; b.used_out += (int)(2 * nf); b.used_utt += batch->B + 1;
+        b.used_tok += (int)nt; b.used_ref += (int)nr; b.used_out += (int)(2 * nf); b.used_utt += batch->B + 1; b.used_vid += batch->B;
         return lanes_submit(q, batch, &io, nullptr, lane_out, h->mel_out, h->ld_out, cap_mode ? h->frame_off : nullptr);
     }
 }

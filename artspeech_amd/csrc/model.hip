@@ -1788,11 +1788,12 @@ StyleIn style_inputs(Ctx& c, const float* feat12, int ldf, const float* mel, int
     return s;
 }
 
-// one of the four towers of StyleEncoder.style_extractor (models.py:417-424) -> its slice of Style [B][2 * style_dim]
-void style_tower(Ctx& c, int which, const StyleIn& s, float* style)
+// one of the four towers of StyleEncoder.style_extractor (models.py:417-424) -> its slice of Style [B][lds] (lds 0: 2 * style_dim)
+void style_tower(Ctx& c, int which, const StyleIn& s, float* style, int lds = 0)
 {
     const std::string p = "style_encoder";
-    const int sd = c.m.cfg.style_dim, lds = 2 * sd;
+    const int sd = c.m.cfg.style_dim;
+    if (lds <= 0) lds = 2 * sd;
     if (which == 0) tower2d(c, p + ".Mel_block", s.mel_img, s.lm, {true, true, true, true}, 6, 1, p + ".Mellinear", style, lds);
     else if (which == 1) tower2d(c, p + ".EMA_block", s.ema_img, s.le, {false, false, true}, 5, 2, p + ".EMAlinear", style ? style + sd : nullptr, lds);
     // energy (crop row 0) and F0 (row 1) towers: twins merged at load (merge_twin_towers) into one tower on the two-row input; its Linear
@@ -1801,7 +1802,7 @@ void style_tower(Ctx& c, int which, const StyleIn& s, float* style)
 }
 
 // DurationPredictor (models.py:540-566) in three pieces
-void duration_style(Ctx& c, const float* ema_ext, int lde, const Lay* ref, float* ds /* [B][style_dim / 4] */)
+void duration_style(Ctx& c, const float* ema_ext, int lde, const Lay* ref, float* ds /* [B][ldd] */, int ldd = 0 /* 0: style_dim / 4 */)
 {
     // dur_block + dur_linear on the FULL-length TV track (models.py:543-546)
     const std::string p = "durationPredictor";
@@ -1809,7 +1810,7 @@ void duration_style(Ctx& c, const float* ema_ext, int lde, const Lay* ref, float
     if (!limg) return;
     float* img = c.f32((size_t)std::max(limg->N, 1));
     RUN(c, as_rows_to_images_f32(ema_ext, lde, ref->d_off, 0, 10, img, limg->d_off, ref->B, ref->max_cols(), c.s));
-    tower2d(c, p + ".dur_block", img, limg, {false, false, true}, 5, 2, p + ".dur_linear", ds, c.m.cfg.style_dim / 4);
+    tower2d(c, p + ".dur_block", img, limg, {false, false, true}, 5, 2, p + ".dur_linear", ds, ldd > 0 ? ldd : c.m.cfg.style_dim / 4);
 }
 
 // 3 x AdainResBlk1d -> BiLSTM -> duration_proj -> [1][N] (into `dst`, the caller's buffer, when given)
@@ -2139,6 +2140,8 @@ struct PhaseA {                   // what the first half leaves in workspace A f
     int ld_en = 0;
     int32_t *dur_i = nullptr, *frame_off = nullptr;
     const Lay *tok = nullptr, *ref = nullptr;
+    bool voice = false;           // voice mode (as_forward_io.voices): no reference layout, no feat12
+    bool ok() const { return tok && (ref || voice); }
 };
 
 bool batch_ok(const as_batch* b, bool tok, bool ref, bool frames)
@@ -2146,8 +2149,9 @@ bool batch_ok(const as_batch* b, bool tok, bool ref, bool frames)
     return b && b->B > 0 && (!tok || b->tok_lens) && (!ref || b->ref_lens) && (!frames || b->frames);
 }
 std::vector<int> vec_of(const int32_t* p, int n) { return std::vector<int>(p, p + n); }
+int voice_dim(const as_model& m) { return 2 * m.cfg.style_dim + m.cfg.style_dim / 4; }
 
-PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
+PhaseA forward_a_full(Ctx& c, const as_batch* batch, const as_forward_io* io)
 {
     const as_model& m = c.m;
     PhaseA A;
@@ -2233,6 +2237,59 @@ PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
     // (... and so does a call under a frame capacity, as_forward_io.frame_cap)
     if (!batch->frames && io->frame_cap <= 0) RUN(c, as_durations_f32(A.duration, io->forced_dur, A.tok->d_off, B, A.dur_i, A.frame_off, nullptr, 0, c.s));
     return A;
+}
+
+// The first half in voice mode (as_forward_io.voices): Style and dur_style are gathered from the caller's voice table (as_voice_forward's
+// rows) -- the reference features, the style towers and dur_block do not run.  What is left beside the encoders: the AdaIN fc GEMM of the
+// predictors and the decoder, which needs the Style rows only and so starts at once (branch 0), and the duration predictor's tail (branch 1),
+// which joins after the duration encoder as in the full sequence.  Side-stream plans put the two branches on side streams 0 and 1 (every
+// edge calling stream <-> side stream); recording plans record them as queues.  forward_b is the same for both modes.
+PhaseA forward_a_voice(Ctx& c, const as_batch* batch, const as_forward_io* io)
+{
+    const as_model& m = c.m;
+    PhaseA A;
+    A.voice = true;
+    const int B = batch->B, sd2 = 2 * m.cfg.style_dim, S = m.cfg.style_dim / 4;
+    A.tok = c.lay(vec_of(batch->tok_lens, B));
+    if (!A.tok) return A;
+    const int Nt = std::max(A.tok->N, 1);
+    A.style = c.f32((size_t)B * sd2);
+    if (io->style) A.style = io->style;
+    A.dur_i = c.i32(Nt);
+    A.frame_off = c.i32(B + 1);
+    if (!batch->frames) {
+        if (io->dur_i) A.dur_i = io->dur_i;
+        if (io->frame_off) A.frame_off = io->frame_off;
+    }
+    float* ds = c.f32((size_t)B * S);
+    if (c.go()) c.p.mark(0, c.s);
+    RUN(c, as_voice_gather_launch(io->voices, io->ld_voice, io->n_voices, io->voice_idx, B, sd2, S, A.style, sd2, ds, S, c.s));
+    if (c.go()) c.p.mark(1, c.s);
+    Fork f(c, 2, 0);
+    f.branch(0);
+    A.fc = adain_fc_all(c, "style", style_norms(m), A.style, sd2, sd2, B);
+    A.has_fc = true;
+    f.back();
+    EncOut eo;
+    rel_encoder_multi(c, path_encoders(), io->tokens, A.tok, &eo, [&](int g) {
+        if (g != ENC_DUR) return;
+        f.wait_main(1);                                                  // the duration encoder's result
+        f.branch(1);
+        A.duration = duration_tail(c, eo.y[ENC_DUR], ds, A.tok, io->duration);
+        f.back();
+    });
+    A.a_en = eo.y[ENC_ARTS];
+    A.t_en = eo.y[ENC_TEXT];
+    A.ld_en = eo.ld[ENC_ARTS];
+    f.join();
+    if (c.go()) c.p.mark(2, c.s);
+    if (!batch->frames && io->frame_cap <= 0) RUN(c, as_durations_f32(A.duration, io->forced_dur, A.tok->d_off, B, A.dur_i, A.frame_off, nullptr, 0, c.s));
+    return A;
+}
+
+PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
+{
+    return io->voices ? forward_a_voice(c, batch, io) : forward_a_full(c, batch, io);
 }
 
 void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_io* io)
@@ -2349,8 +2406,8 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
 void outputs_a(Ctx& c, const PhaseA& A, const as_forward_io* io)
 {
     if (!c.go()) return;
-    const int C = c.m.cfg.hidden_dim, Nt = A.tok->N, Nr = A.ref->N;
-    if (io->feat12) copy_rows(c, io->feat12, io->ld_feat, A.feat12, Nr, 12, Nr);
+    const int C = c.m.cfg.hidden_dim, Nt = A.tok->N, Nr = A.ref ? A.ref->N : 0;
+    if (io->feat12 && A.ref) copy_rows(c, io->feat12, io->ld_feat, A.feat12, Nr, 12, Nr);
     if (io->t_en) copy_rows(c, io->t_en, io->ld_en, A.t_en, A.ld_en, C, Nt);
     if (io->a_en) copy_rows(c, io->a_en, io->ld_en, A.a_en, A.ld_en, C, Nt);
 }
@@ -2358,6 +2415,14 @@ void outputs_a(Ctx& c, const PhaseA& A, const as_forward_io* io)
 bool io_ok(const as_forward_io* io, bool need_out)
 {
     return io && io->tokens && io->mel && io->f0_raw && io->ema_raw && (!need_out || io->mel_out);
+}
+// the batch and io of a forward entry point, full or voice mode (voice mode: no reference lengths, a table of at least one voice row,
+// no feat12 -- it has no meaning without a reference)
+bool forward_ok(const as_model* m, const as_batch* batch, const as_forward_io* io, bool need_out, bool frames)
+{
+    if (!io || !batch_ok(batch, true, !io->voices, frames)) return false;
+    if (!io->voices) return io_ok(io, need_out);
+    return io->tokens && (!need_out || io->mel_out) && io->ld_voice >= voice_dim(*m) && io->n_voices >= 1 && !io->feat12;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2394,6 +2459,23 @@ int style_module(Ctx& c, const as_batch* batch, const float* mel, int ldm, const
     RUN(c, as_ref_features_f32(mel, ldm, n_mels, f0_raw, ema_raw, lde, ref->N, stats, feat12, ldf, c.s));
     const StyleIn si = style_inputs(c, feat12, ldf, mel, ldm, ref);
     if (si.l1) for (int t = 0; t < 4; ++t) style_tower(c, t, si, style);
+    return AS_OK;
+}
+
+// the voices of B reference utterances (as_voice_forward): Style (the towers on the T - 1 crop) and dur_style (dur_block on the full-length TV
+// track) into the rows of voice [B][ldv] -- the launches the full forward makes for them, one after the other on the calling stream
+int voice_module(Ctx& c, const as_batch* batch, const float* mel, int ldm, const float* f0_raw, const float* ema_raw, int lde, float* voice, int ldv)
+{
+    const Lay* ref = c.lay(vec_of(batch->ref_lens, batch->B));
+    if (!ref || ldm < ref->N || lde < ref->N || ldv < voice_dim(c.m)) return AS_EINVAL;
+    const int n_mels = c.m.cfg.n_mels, sd2 = 2 * c.m.cfg.style_dim;
+    float* feat12 = c.f32((size_t)12 * std::max(ref->N, 1));
+    const float* stats = c.m.vec("__stats24");
+    RUN(c, as_ref_features_f32(mel, ldm, n_mels, f0_raw, ema_raw, lde, ref->N, stats, feat12, ref->N, c.s));
+    const StyleIn si = style_inputs(c, feat12, ref->N, mel, ldm, ref);
+    if (!si.l1) return AS_OK;
+    for (int t = 0; t < 3; ++t) style_tower(c, t, si, voice, ldv);
+    duration_style(c, feat12 ? feat12 + (size_t)2 * ref->N : nullptr, ref->N, ref, voice ? voice + sd2 : nullptr, ldv);
     return AS_OK;
 }
 
@@ -2463,13 +2545,26 @@ const as_forward_io* dummy_io()
     }();
     return &io;
 }
+const as_forward_io* dummy_voice_io()
+{
+    static const as_forward_io io = [] {
+        as_forward_io d = *dummy_io();
+        d.mel = d.f0_raw = d.ema_raw = nullptr;
+        d.voices = ANY;
+        d.ld_voice = ANY_LD;
+        d.n_voices = 1;
+        return d;
+    }();
+    return &io;
+}
 
 // the sequence of one module with nothing behind it: workspace bytes (and, on a model being created, the weights it touches)
 size_t count_module(const as_model* m, as_plan* p, int module, const as_batch* batch)
 {
-    // the batch fields every module reads: tok_lens, ref_lens, frames (AS_MOD_FORWARD_B_CAP: capacities)
-    static const bool need[8][3] = {{1, 1, 0}, {1, 1, 1}, {1, 0, 0}, {0, 1, 0}, {1, 1, 0}, {0, 0, 1}, {0, 0, 1}, {1, 1, 1}};
-    if (module < 0 || module > AS_MOD_FORWARD_B_CAP || !batch_ok(batch, need[module][0], need[module][1], need[module][2])) return 0;
+    // the batch fields every module reads: tok_lens, ref_lens, frames (AS_MOD_FORWARD_B_CAP: capacities).  Workspace B is counted behind a
+    // voice-mode first half when ref_lens is NULL (a voice-mode caller has no reference lengths)
+    static const bool need[10][3] = {{1, 1, 0}, {1, 0, 1}, {1, 0, 0}, {0, 1, 0}, {1, 1, 0}, {0, 0, 1}, {0, 0, 1}, {1, 0, 1}, {0, 1, 0}, {1, 0, 0}};
+    if (module < 0 || module > AS_MOD_FORWARD_A_VOICE || !batch_ok(batch, need[module][0], need[module][1], need[module][2])) return 0;
     Ctx c(*m, *p, nullptr, nullptr, 0, Pass::Count);
     int rc = AS_OK;
     switch (module) {
@@ -2479,8 +2574,10 @@ size_t count_module(const as_model* m, as_plan* p, int module, const as_batch* b
     case AS_MOD_ARTS: rc = arts_module(c, batch, ANY, ANY_LD, ANY, ANY, ANY, ANY, ANY_LD); break;
     case AS_MOD_DECODER: rc = decoder_module(c, batch, ANY, ANY_LD, ANY, ANY, ANY, ANY, ANY_LD, ANY, ANY_LD); break;
     case AS_MOD_FORWARD_A: forward_a(c, batch, dummy_io()); break;
+    case AS_MOD_VOICE: rc = voice_module(c, batch, ANY, ANY_LD, ANY, ANY, ANY_LD, ANY, ANY_LD); break;
+    case AS_MOD_FORWARD_A_VOICE: forward_a(c, batch, dummy_voice_io()); break;
     default: {                                                           // workspace B: the second half, behind a first half in workspace A
-        as_forward_io io = *dummy_io();
+        as_forward_io io = batch->ref_lens ? *dummy_io() : *dummy_voice_io();
         as_batch b = *batch;
         if (module == AS_MOD_FORWARD_B_CAP) {                            // batch->frames = capacities: their sum is the call's frame_cap
             long cap = 0;
@@ -2491,7 +2588,7 @@ size_t count_module(const as_model* m, as_plan* p, int module, const as_batch* b
         }
         Ctx ca(*m, *p, nullptr, nullptr, 0, Pass::Count);
         const PhaseA A = forward_a(ca, &b, &io);
-        if (ca.rc || !A.tok) return 0;
+        if (ca.rc || !A.ok()) return 0;
         forward_b(c, A, &b, &io);
     }
     }
@@ -2885,6 +2982,18 @@ extern "C" int as_style_forward(const as_model* m, as_plan* p, const as_batch* b
     });
 }
 
+extern "C" int as_voice_dim(const as_model* m) { return m ? voice_dim(*m) : AS_EINVAL; }
+
+extern "C" int as_voice_forward(const as_model* m, as_plan* p, const as_batch* batch, const float* mel, int ldm, const float* f0_raw,
+                                const float* ema_raw, int lde, float* voice, int ld_voice, void* ws, size_t ws_bytes, as_stream_t stream)
+{
+    return abi([&] {
+        if (!m || !p || !batch_ok(batch, false, true, false) || !mel || !f0_raw || !ema_raw || !voice) return AS_EINVAL;
+        Call k(m, p, ws, ws_bytes, stream, Pass::Run, true);
+        return k.done(voice_module(k.c, batch, mel, ldm, f0_raw, ema_raw, lde, voice, ld_voice));
+    });
+}
+
 extern "C" int as_duration_forward(const as_model* m, as_plan* p, const as_batch* batch, const int32_t* tokens, const float* ema_ext, int lde,
                                    float* duration, void* ws, size_t ws_bytes, as_stream_t stream)
 {
@@ -2920,10 +3029,10 @@ extern "C" int as_forward_test_begin(const as_model* m, as_plan* p, const as_bat
                                      as_stream_t stream)
 {
     return abi([&] {
-        if (!m || !p || !batch_ok(batch, true, true, false) || !io_ok(io, false)) return AS_EINVAL;
+        if (!m || !p || !forward_ok(m, batch, io, false, false)) return AS_EINVAL;
         Call k(m, p, ws_a, ws_a_bytes, stream, Pass::Run, true);
         const PhaseA A = forward_a(k.c, batch, io);
-        if (A.tok && A.ref) outputs_a(k.c, A, io);
+        if (A.ok()) outputs_a(k.c, A, io);
         return k.done();
     });
 }
@@ -2932,11 +3041,11 @@ extern "C" int as_forward_test_finish(const as_model* m, as_plan* p, const as_ba
                                       void* ws_b, size_t ws_b_bytes, as_stream_t stream)
 {
     return abi([&] {
-        if (!m || !p || !batch_ok(batch, true, true, true) || !io_ok(io, true)) return AS_EINVAL;
+        if (!m || !p || !forward_ok(m, batch, io, true, true)) return AS_EINVAL;
         // recover where the first half left its results: the same allocation sequence, nothing launched (_begin's layouts: no trim)
         Call ka(m, p, ws_a, ws_a_bytes, stream, Pass::Replay, false);
         const PhaseA A = forward_a(ka.c, batch, io);
-        if (ka.done() || !A.tok || !A.ref) return ka.done() ? ka.done() : AS_EINVAL;
+        if (ka.done() || !A.ok()) return ka.done() ? ka.done() : AS_EINVAL;
         Call kb(m, p, ws_b, ws_b_bytes, stream, Pass::Run, false);
         forward_b(kb.c, A, batch, io);
         return kb.done();
@@ -2947,10 +3056,10 @@ extern "C" int as_forward_test(const as_model* m, as_plan* p, const as_batch* ba
                                void* ws_b, size_t ws_b_bytes, int32_t* frames_host_out, as_stream_t stream)
 {
     return abi([&] {
-        if (!m || !p || !batch_ok(batch, true, true, false) || !io_ok(io, true)) return AS_EINVAL;
+        if (!m || !p || !forward_ok(m, batch, io, true, false)) return AS_EINVAL;
         Call ka(m, p, ws_a, ws_a_bytes, stream, Pass::Run, true);
         const PhaseA A = forward_a(ka.c, batch, io);
-        if (ka.done() || !A.tok || !A.ref) return ka.done() ? ka.done() : AS_EINVAL;
+        if (ka.done() || !A.ok()) return ka.done() ? ka.done() : AS_EINVAL;
         const hipStream_t s = static_cast<hipStream_t>(stream);
         as_batch b2 = *batch;
         if (!batch->frames && io->frame_cap > 0) {

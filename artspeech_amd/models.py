@@ -10,8 +10,14 @@ frames only.
 The two frozen feature extractors are pluggable: their OUTPUTS are inputs of this path.
 Pass ``features=(f0_raw, ema_raw)`` or attach modules as ``style_encoder.pitch_extractor`` (artspeech_amd.jdc.JDCNet is
 the HIP one) / ``style_encoder.ema_extractor``.
+
+Voices: everything forward(step="test") takes from the reference reduces to Style [2 style_dim] and dur_style [style_dim / 4] per speaker.
+``ArtsSpeech.compute_voice`` computes them once (as_voice_forward: one row of ``voice_dim`` floats per reference, Style first); ``forward`` /
+``forward_packed`` / ``Lanes.submit`` with ``voice=`` (a [V, voice_dim] table) and ``voice_idx=`` (row per utterance, None = row b) then
+skip the reference features, the style towers and dur_block.
 """
 import ctypes
+import hashlib
 
 import torch
 
@@ -32,6 +38,15 @@ def stats_floats(distribution):
     vals = [d["energy_mean"].reshape(1), d["energy_std"].reshape(1), d["pitch_mean"].reshape(1), d["pitch_std"].reshape(1),
             d["EMA_mean"].reshape(10), d["EMA_std"].reshape(10)]
     return torch.cat([v.detach().float().cpu() for v in vals]).tolist()
+
+
+def weights_fingerprint(blob, cfg):
+    """A short hex digest of the serialised weights (blob.state_dict_to_blob) and the as_model_cfg they are created with: a voice
+    (pipeline.Voice) is only valid for the model it was computed on."""
+    h = hashlib.blake2b(digest_size=16)
+    h.update(bytes(blob))
+    h.update(bytes(cfg))
+    return h.hexdigest()
 
 
 def _i32(values):
@@ -57,18 +72,21 @@ class Runtime:
             cfg.stats[i] = v
         self.cfg = cfg
         blob = state_dict_to_blob(state_dict)
+        self.fingerprint = weights_fingerprint(blob, cfg)
         with torch.cuda.device(self.device):
             check(L.as_model_create(blob, len(blob), ctypes.byref(cfg), ctypes.byref(self.model)), "as_model_create")
             check(L.as_plan_create(self.model, ctypes.byref(self.plan)), "as_plan_create")
         self._ws = {}
         self._retired = []
         self._parent = None
+        self.voice_dim = int(L.as_voice_dim(self.model))
 
     def fork(self):
         """A second caller of the SAME weights: its own as_plan (geometry tables, side streams) and workspaces, so that its forwards can
         be in flight on another stream while this runtime's run (include/artspeech_hip.h: one model per GPU, one plan per stream)."""
         rt = Runtime.__new__(Runtime)
-        rt.model, rt.plan, rt.device, rt.cfg = self.model, ctypes.c_void_p(), self.device, self.cfg
+        rt.model, rt.plan, rt.device, rt.cfg, rt.voice_dim = self.model, ctypes.c_void_p(), self.device, self.cfg, self.voice_dim
+        rt.fingerprint = self.fingerprint
         rt._ws, rt._retired, rt._parent = {}, [], self                  # (keeps the owner of the model alive)
         with torch.cuda.device(self.device):
             check(_lib.lib().as_plan_create(self.model, ctypes.byref(rt.plan)), "as_plan_create")
@@ -147,6 +165,29 @@ def _dev(t, device, dtype=torch.float32):
 
 def _p(t):
     return t.data_ptr() if t is not None else None
+
+
+def _voice_args(rt, voice, voice_idx, B, device_idx=True):
+    """(voice, voice_idx) -> the as_forward_io / as_host_io voice fields (voices, ld_voice, n_voices, voice_idx) and the tensors to keep alive.
+    voice: device fp32 [V, >= voice_dim] (rows dense; a row range of a wider table is fine); voice_idx: None (utterance b speaks in row b)
+    or [B] integers -- on the model's device (device_idx) or on the host (as_lanes_submit_host), converted to int32 if they are not."""
+    if voice.dim() != 2 or voice.shape[1] < rt.voice_dim or voice.dtype != torch.float32:
+        raise ValueError(f"voice: expected a float32 [V, {rt.voice_dim}] table, got {tuple(voice.shape)} {voice.dtype}")
+    if not voice.is_cuda or voice.device != rt.device or voice.stride(-1) != 1:
+        raise _lib.HipLibraryError("voice: expected a table on the model's GPU with dense rows")
+    idx = None
+    if voice_idx is not None:
+        idx = torch.as_tensor(voice_idx)
+        if idx.numel() != B:
+            raise ValueError(f"voice_idx: {idx.numel()} entries for {B} utterances")
+        idx = idx.to(device=rt.device if device_idx else "cpu", dtype=torch.int32).reshape(-1)
+        if not idx.is_contiguous():
+            idx = idx.contiguous()
+    return (voice.data_ptr(), voice.stride(0), voice.shape[0], idx.data_ptr() if idx is not None else None), (voice, idx)
+
+
+def _set_voice(io, fields):
+    io.voices, io.ld_voice, io.n_voices, io.voice_idx = fields
 
 
 def _pack_tokens(x, lens, n_token):
@@ -332,8 +373,37 @@ class ArtsSpeech(_Module):
         self.decoder = Decoder(rt)
         return self
 
+    def compute_voice(self, mels, mel_input_length, features=None):
+        """The voices of B reference utterances (as_voice_forward) -> device fp32 [B, voice_dim]: row b = Style (StyleEncoder on the T - 1
+        crop, models.py:459-471) then dur_style (dur_linear(dur_block(ema_ext)), models.py:541-546) -- what forward(step="test") computes
+        from the reference, once.  mels / features / attached extractors exactly as in `forward`."""
+        if self.rt is None:
+            raise RuntimeError("no weights loaded: call load_checkpoint / load_state_dict first")
+        ml = [int(v) for v in mel_input_length]
+        B = len(ml)
+        f0_raw, ema_raw = self.style_encoder._extract(mels, features, ml)
+        with torch.cuda.device(self.device):
+            mel_p = pack(mels.to(self.device), ml)
+            f0_p = pack(f0_raw.to(self.device).reshape(B, 1, -1), ml)
+            ema_p = pack(ema_raw.to(self.device), ml)
+            return self.compute_voice_packed(mel_p, f0_p, ema_p, ml)
+
+    def compute_voice_packed(self, mel_p, f0_p, ema_p, ref_lens):
+        """compute_voice on packed reference features (mel [n_mels][>= N], f0 [1][N], ema [10][>= N]) -> [B, voice_dim]"""
+        rt, L = self.rt, _lib.lib()
+        ref_lens = [int(v) for v in ref_lens]
+        with torch.cuda.device(rt.device):
+            b = rt.batch(ref_lens=ref_lens)
+            v = torch.empty((len(ref_lens), rt.voice_dim), dtype=torch.float32, device=rt.device)
+            ws, nb = rt.workspace("v", _lib.AS_MOD_VOICE, b)
+            check(L.as_voice_forward(rt.model, rt.plan, ctypes.byref(b), _p(mel_p), mel_p.stride(0), _p(f0_p), _p(ema_p), ema_p.stride(0), _p(v),
+                                     v.stride(0), _p(ws), nb, rt.stream()), "as_voice_forward")
+        return v
+
     def forward(self, batch, s2s_attn=None, s2s_attn_mono=None, step="test", mode="train", epoch=0, features=None,
-                forced_durations=None, return_aux=False):
+                forced_durations=None, return_aux=False, voice=None, voice_idx=None):
+        """voice: a [V, voice_dim] table of compute_voice rows -- utterance b then speaks in row voice_idx[b] (None: row b), and the batch's
+        mels / mel_input_length are not read (they may be None)."""
         if step != "test":
             raise NotImplementedError("training branches (step='first'/'second') are out of scope (SURVEY.md section 2)")
         if self.rt is None:
@@ -341,42 +411,55 @@ class ArtsSpeech(_Module):
         texts, input_lengths, mels, mel_input_length = batch[0], batch[1], batch[2], batch[3]   # 7- or 4-tuple (B1)
         dev = self.device
         tl = [int(v) for v in input_lengths]
-        ml = [int(v) for v in mel_input_length]
         B = len(tl)
-        f0_raw, ema_raw = self.style_encoder._extract(mels, features, ml)
+        if voice is not None:
+            ml, mel_p, f0_p, ema_p = None, None, None, None
+        else:
+            ml = [int(v) for v in mel_input_length]
+            f0_raw, ema_raw = self.style_encoder._extract(mels, features, ml)
         with torch.cuda.device(dev):
             tok = _dev(_pack_tokens(texts, tl, self.rt.cfg.n_token), dev, torch.int32)
-            mel_p = pack(mels.to(dev), ml)
-            f0_p = pack(f0_raw.to(dev).reshape(B, 1, -1), ml)
-            ema_p = pack(ema_raw.to(dev), ml)
+            if voice is None:
+                mel_p = pack(mels.to(dev), ml)
+                f0_p = pack(f0_raw.to(dev).reshape(B, 1, -1), ml)
+                ema_p = pack(ema_raw.to(dev), ml)
             forced, frames = None, None
             if forced_durations is not None:
                 fd = [torch.as_tensor(forced_durations[b])[: tl[b]].reshape(-1) for b in range(B)]
                 forced = torch.cat(fd).to(device=dev, dtype=torch.int32)
                 frames = [int(f.sum()) for f in fd]
-            out = self.forward_packed(tok, tl, mel_p, f0_p, ema_p, ml, forced=forced, frames_hint=frames, aux=return_aux)
+            out = self.forward_packed(tok, tl, mel_p, f0_p, ema_p, ml, forced=forced, frames_hint=frames, aux=return_aux, voice=voice,
+                                      voice_idx=voice_idx)
             mel = unpack(out["mel"], layout(out["frames2"], dev))
         if return_aux:
             return mel, out
         return mel
 
-    def forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None):
+    def forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None,
+                       voice=None, voice_idx=None):
         """The whole hot path on packed tensors (what bench.py times): one call of as_forward_test when the integer frame
         counts are known (forced durations), else as_forward_test_begin -> one device->host read of B + 1 integers ->
         as_forward_test_finish.  `out`: the dict of a previous call with the same geometry (its tensors are reused).
         frame_cap (predicted durations only): the half-rate frames to make room for, all utterances together -- ONE as_forward_test call
         with no read-back (capturable); the result's `frame_off` (device, [B + 1]) says where each utterance's frames lie in `mel`
-        [n_mels][2 frame_cap], `frames` is None; more frames than room raises the AS_STATUS_CAPACITY bit (as_device_status)."""
+        [n_mels][2 frame_cap], `frames` is None; more frames than room raises the AS_STATUS_CAPACITY bit (as_device_status).
+        voice / voice_idx: voice mode (see `forward`); mel_p / f0_p / ema_p / ref_lens are then not read (None)."""
         if frame_cap is not None:
-            return self._forward_packed_cap(tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, int(frame_cap), aux, out)
+            return self._forward_packed_cap(tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, int(frame_cap), aux, out, voice, voice_idx)
         rt, L = self.rt, _lib.lib()
         dev = rt.device
-        tok_lens, ref_lens = [int(v) for v in tok_lens], [int(v) for v in ref_lens]
-        B, Nt, Nr, C = len(tok_lens), sum(tok_lens), sum(ref_lens), rt.cfg.hidden_dim
+        tok_lens = [int(v) for v in tok_lens]
+        ref_lens = None if voice is not None else [int(v) for v in ref_lens]
+        B, Nt, Nr, C = len(tok_lens), sum(tok_lens), sum(ref_lens or []), rt.cfg.hidden_dim
         with torch.cuda.device(dev):
             io = _lib.ForwardIO()
-            io.tokens, io.mel, io.ld_mel = _p(tok), _p(mel_p), mel_p.stride(0)
-            io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
+            io.tokens = _p(tok)
+            if voice is not None:
+                fields, keep_voice = _voice_args(rt, voice, voice_idx, B)
+                _set_voice(io, fields)
+            else:
+                io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
+                io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
             io.forced_dur = _p(forced)
             res = out if out is not None else {}
 
@@ -392,10 +475,11 @@ class ArtsSpeech(_Module):
             if aux:
                 io.duration = _p(new("duration", (1, max(Nt, 1))))
                 io.style = _p(new("style", (B, 2 * rt.cfg.style_dim)))
-                io.feat12, io.ld_feat = _p(new("feat12", (12, max(Nr, 1)))), max(Nr, 1)
+                if voice is None:                                                # (no reference features in voice mode)
+                    io.feat12, io.ld_feat = _p(new("feat12", (12, max(Nr, 1)))), max(Nr, 1)
                 io.t_en, io.a_en, io.ld_en = _p(new("t_en", (C, max(Nt, 1)))), _p(new("a_en", (C, max(Nt, 1)))), max(Nt, 1)
             ba = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=frames_hint)
-            ws_a, na = rt.workspace("a", _lib.AS_MOD_FORWARD_A, ba)
+            ws_a, na = rt.workspace("a", _lib.AS_MOD_FORWARD_A_VOICE if voice is not None else _lib.AS_MOD_FORWARD_A, ba)
             s = rt.stream()
             frames = frames_hint
             if frames is None:
@@ -420,15 +504,21 @@ class ArtsSpeech(_Module):
         return res
 
 
-def _forward_packed_cap(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, frame_cap, aux, out):
+def _forward_packed_cap(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, frame_cap, aux, out, voice=None, voice_idx=None):
     rt, L = self.rt, _lib.lib()
     dev = rt.device
-    tok_lens, ref_lens = [int(v) for v in tok_lens], [int(v) for v in ref_lens]
-    B, Nt, Nr, C = len(tok_lens), sum(tok_lens), sum(ref_lens), rt.cfg.hidden_dim
+    tok_lens = [int(v) for v in tok_lens]
+    ref_lens = None if voice is not None else [int(v) for v in ref_lens]
+    B, Nt, Nr, C = len(tok_lens), sum(tok_lens), sum(ref_lens or []), rt.cfg.hidden_dim
     with torch.cuda.device(dev):
         io = _lib.ForwardIO()
-        io.tokens, io.mel, io.ld_mel = _p(tok), _p(mel_p), mel_p.stride(0)
-        io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
+        io.tokens = _p(tok)
+        if voice is not None:
+            fields, keep_voice = _voice_args(rt, voice, voice_idx, B)
+            _set_voice(io, fields)
+        else:
+            io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
+            io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
         io.frame_cap = frame_cap
         res = out if out is not None else {}
 
@@ -443,12 +533,13 @@ def _forward_packed_cap(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, frame
         if aux:
             io.duration = _p(new("duration", (1, max(Nt, 1))))
             io.style = _p(new("style", (B, 2 * rt.cfg.style_dim)))
-            io.feat12, io.ld_feat = _p(new("feat12", (12, max(Nr, 1)))), max(Nr, 1)
+            if voice is None:
+                io.feat12, io.ld_feat = _p(new("feat12", (12, max(Nr, 1)))), max(Nr, 1)
             io.t_en, io.a_en, io.ld_en = _p(new("t_en", (C, max(Nt, 1)))), _p(new("a_en", (C, max(Nt, 1)))), max(Nt, 1)
             io.F0, io.N, io.EMA = _p(new("F0", (1, n2))), _p(new("N", (1, n2))), _p(new("EMA", (10, n2)))
             io.ld_pred = n2
         ba = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens)
-        ws_a, na = rt.workspace("a", _lib.AS_MOD_FORWARD_A, ba)
+        ws_a, na = rt.workspace("a", _lib.AS_MOD_FORWARD_A_VOICE if voice is not None else _lib.AS_MOD_FORWARD_A, ba)
         bc = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=[frame_cap] + [0] * (B - 1))     # (only the sum counts)
         ws_b, nb = rt.workspace("b", _lib.AS_MOD_FORWARD_B_CAP, bc)
         check(L.as_forward_test(rt.model, rt.plan, ctypes.byref(ba), ctypes.byref(io), _p(ws_a), na, _p(ws_b), nb, None, rt.stream()),
@@ -496,12 +587,16 @@ class Lanes:
     def merged_calls(self, lane):
         return int(_lib.lib().as_lanes_merged_calls(self.h, int(lane)))
 
-    def submit(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames=None, out=None, capacity=None, frame_cap=None):
+    def submit(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames=None, out=None, capacity=None, frame_cap=None, voice=None,
+               voice_idx=None):
         """-> (lane, dict with the output tensors).  frames (per-utterance half-rate frame counts) known: graph-replayed from the second
         submit of the same tensors on a lane; None: predicted durations, `capacity` = the mel frames the output buffer is made for (eager,
         one read-back per call) -- or frame_cap = the half-rate frames to make room for (as_forward_io.frame_cap: no read-back, replayed
         from hipGraphs and coalesced like a submission with known counts; `frame_off` of the result says where the utterances lie).
-        2-D tensors may be column ranges of a wider block (row stride = the block's width)."""
+        2-D tensors may be column ranges of a wider block (row stride = the block's width).
+        voice / voice_idx: voice mode (ArtsSpeech.forward); voice_idx a DEVICE int32 [B] tensor (read when the group runs: rewriting it
+        changes what a replayed graph computes) or None = row b of `voice` (then a row range of a wider table); mel_p / f0_p / ema_p /
+        ref_lens are not read (None).  Adjacent: indices that continue each other in one table, or row ranges that do."""
         def _p(t):                                                  # (rows of a wider block: only the last axis has to be dense)
             if t is None:
                 return None
@@ -512,13 +607,22 @@ class Lanes:
             return t.data_ptr()
         rt, L = self.rt, _lib.lib()
         dev = rt.device
-        tok_lens, ref_lens = [int(v) for v in tok_lens], [int(v) for v in ref_lens]
+        tok_lens = [int(v) for v in tok_lens]
+        ref_lens = None if voice is not None else [int(v) for v in ref_lens]
         B, Nt = len(tok_lens), sum(tok_lens)
         res = out if out is not None else {}
         with torch.cuda.device(dev):
             io = _lib.ForwardIO()
-            io.tokens, io.mel, io.ld_mel = _p(tok), _p(mel_p), mel_p.stride(0)
-            io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
+            io.tokens = _p(tok)
+            keep_voice = None
+            if voice is not None:
+                if voice_idx is not None and (not torch.is_tensor(voice_idx) or voice_idx.dtype != torch.int32 or voice_idx.device != dev):
+                    raise _lib.HipLibraryError("voice_idx: expected an int32 tensor on the model's GPU (it is read when the group runs)")
+                fields, keep_voice = _voice_args(rt, voice, voice_idx, B)
+                _set_voice(io, fields)
+            else:
+                io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
+                io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
             io.forced_dur = _p(forced)
             n2 = 2 * sum(int(f) for f in frames) if frames is not None else (2 * int(frame_cap) if frame_cap is not None else int(capacity))
             if frame_cap is not None:
@@ -546,39 +650,49 @@ class Lanes:
             res["frames"] = None if frame_cap is not None else ([int(v) for v in fr] if frames is None else [int(f) for f in frames])
             # (a lane's last group of submissions stays referenced: its launch may still be reading them)
             prev = self._keep[lane.value] or []
-            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, res)])[-2 * max(self.coalesce, 1):]
+            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, res, keep_voice)])[-2 * max(self.coalesce, 1):]
         return lane.value, res
 
     def set_debug(self, on=True):
         """as_lanes_set_debug: the device inputs of a held-back submission are checksummed at submit and at its group's launch"""
         check(_lib.lib().as_lanes_set_debug(self.h, int(bool(on))), "as_lanes_set_debug")
 
-    def submit_host(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames, out_mel, frame_cap=None, frame_off=None):
+    def submit_host(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames, out_mel, frame_cap=None, frame_off=None, voice=None,
+                    voice_idx=None):
         """as_lanes_submit_host: HOST tensors in (pinned: `.pin_memory()`), the mel back into the host tensor `out_mel` [n_mels][>= 2 sum
         frames]; the lane owns the device side (its block, the copies, the group's launch).  -> lane.  Keep the tensors alive and unchanged
         until `wait(lane)`; `out_mel` is valid after it.  Predicted durations: frames=None, forced=None, frame_cap = the half-rate frames
-        there is room for (out_mel [n_mels][>= 2 frame_cap]) and frame_off = a host int32 tensor [B + 1] that receives the offsets."""
+        there is room for (out_mel [n_mels][>= 2 frame_cap]) and frame_off = a host int32 tensor [B + 1] that receives the offsets.
+        voice: a DEVICE table that stays resident (keep it unchanged until `wait`); voice_idx: HOST integers [B] (copied into the lane's
+        block with the tokens) or None = row b; mel_p / f0_p / ema_p / ref_lens are then not read."""
         def _h(t):
             if t is None:
                 return None
             if t.is_cuda or t.stride(-1) != 1:
                 raise _lib.HipLibraryError("expected a host tensor whose rows are dense")
             return t.data_ptr()
-        tok_lens, ref_lens = [int(v) for v in tok_lens], [int(v) for v in ref_lens]
+        tok_lens = [int(v) for v in tok_lens]
+        ref_lens = None if voice is not None else [int(v) for v in ref_lens]
         frames = [int(v) for v in frames] if frames is not None else None
         with torch.cuda.device(self.rt.device):
             io = _lib.HostIO()
             if frames is None:
                 io.frame_cap, io.frame_off = int(frame_cap), _h(frame_off)
-            io.tokens, io.mel, io.ld_mel = _h(tok), _h(mel_p), mel_p.stride(0)
-            io.f0_raw, io.ema_raw, io.ld_ema = _h(f0_p), _h(ema_p), ema_p.stride(0)
+            io.tokens = _h(tok)
+            keep_voice = None
+            if voice is not None:
+                fields, keep_voice = _voice_args(self.rt, voice, voice_idx, len(tok_lens), device_idx=False)
+                _set_voice(io, fields)
+            else:
+                io.mel, io.ld_mel = _h(mel_p), mel_p.stride(0)
+                io.f0_raw, io.ema_raw, io.ld_ema = _h(f0_p), _h(ema_p), ema_p.stride(0)
             io.forced_dur = _h(forced)
             io.mel_out, io.ld_out = _h(out_mel), out_mel.stride(0)
             ba = self.rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=frames)
             lane = ctypes.c_int32(-1)
             check(_lib.lib().as_lanes_submit_host(self.h, ctypes.byref(ba), ctypes.byref(io), ctypes.byref(lane)), "as_lanes_submit_host")
             prev = self._keep[lane.value] or []
-            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, out_mel, frame_off)])[-2 * max(self.coalesce, 1):]
+            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, out_mel, frame_off, keep_voice)])[-2 * max(self.coalesce, 1):]
         return lane.value
 
     def wait(self, lane=-1):

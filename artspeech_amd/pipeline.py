@@ -5,14 +5,64 @@ The phonemizer and the wav/mel front end are outside this path (SURVEY.md sectio
 test.py:75-88 (distribution, build_model, load_checkpoint), test.py:96-113 (ids, tensor packing, the model call) and
 test.py:115-125 (the generator, SURVEY.md section 8(f) N2: artspeech_amd/vocoder.py), so that a caller with phonemes and a
 reference mel gets the mel -- and, with a vocoder attached, the waveform -- the reference would produce.
+
+One voice, many sentences: ``voice_from_mel`` / ``voice_from_wave`` compute what the model takes from a reference utterance once (a
+``Voice``: Style and dur_style, models.ArtsSpeech.compute_voice); ``synthesis_mel(phonemes, voice=v)`` then skips the reference
+features, the style towers and dur_block.  ``Voice.save`` / ``Voice.load`` keep it as a small .npz, bound to the weights it came from.
 """
 import json
 
+import numpy as np
 import torch
 
 from . import models
 from .text import TextCleaner
 from .weights import DEFAULT_STATS, load_distribution
+
+
+class Voice:
+    """A speaker's voice for one model: vector fp32 [2 * style_dim + style_dim / 4] (Style, then dur_style), the model's style_dim and
+    the fingerprint of the weights and configuration it was computed with (models.weights_fingerprint)."""
+
+    def __init__(self, vector, style_dim, fingerprint):
+        self.vector = torch.as_tensor(vector, dtype=torch.float32).detach().cpu().reshape(-1).clone()
+        self.style_dim = int(style_dim)
+        self.fingerprint = str(fingerprint)
+        if self.vector.numel() != 2 * self.style_dim + self.style_dim // 4:
+            raise ValueError(f"a voice of style_dim {self.style_dim} has {2 * self.style_dim + self.style_dim // 4} entries, not {self.vector.numel()}")
+
+    @property
+    def style(self):
+        """Style [2 * style_dim]: timbre, TV, F0 and energy slices (models.py:417-424)"""
+        return self.vector[: 2 * self.style_dim]
+
+    @property
+    def dur_style(self):
+        """dur_style [style_dim / 4] (models.py:541-546)"""
+        return self.vector[2 * self.style_dim:]
+
+    def save(self, path):
+        """.npz with `vector`, `style_dim` and `fingerprint` (no pickled objects).  Writes exactly `path`."""
+        with open(path, "wb") as f:
+            np.savez(f, vector=self.vector.numpy(), style_dim=np.int32(self.style_dim), fingerprint=np.array(self.fingerprint))
+
+    @classmethod
+    def load(cls, path, model=None):
+        """A voice saved by `save`.  model (an ArtSpeech, an ArtsSpeech or a models.Runtime): checked against it at once (`check`)."""
+        with np.load(path, allow_pickle=False) as z:
+            v = cls(z["vector"], int(z["style_dim"]), str(z["fingerprint"]))
+        if model is not None:
+            rt = model.model.ArtsSpeech.rt if isinstance(model, ArtSpeech) else getattr(model, "rt", model)
+            v.check(rt.fingerprint, int(rt.cfg.style_dim))
+        return v
+
+    def check(self, fingerprint, style_dim):
+        """ValueError unless this voice was computed by a model of these weights and this configuration"""
+        if int(style_dim) != self.style_dim:
+            raise ValueError(f"the voice was computed with style_dim {self.style_dim}, this model has {int(style_dim)}")
+        if str(fingerprint) != self.fingerprint:
+            raise ValueError("the voice was computed with other weights or another configuration than this model's "
+                             f"(fingerprint {self.fingerprint} vs {fingerprint})")
 
 
 class ArtSpeech:
@@ -69,6 +119,46 @@ class ArtSpeech:
         return self.frontend
 
     @torch.no_grad()
+    def voice_from_mel(self, ref_mel, features=None):
+        """The Voice of one reference utterance: normalised log-mel [80, T] (test.py:43-47); features = (f0_raw, ema_raw) [or
+        (None, ema_raw)] when the extractors are not attached -- as `synthesis_mel` takes them for one utterance."""
+        net = self.model.ArtsSpeech
+        mel = torch.as_tensor(ref_mel, dtype=torch.float32)
+        feats = None
+        if features is not None:
+            f, e = features
+            feats = (None if f is None else torch.as_tensor(f, dtype=torch.float32).reshape(1, 1, -1),
+                     torch.as_tensor(e, dtype=torch.float32).reshape(1, 10, -1))
+        v = net.compute_voice(mel[None], torch.LongTensor([mel.shape[-1]]), features=feats)
+        return Voice(v[0].cpu(), net.rt.cfg.style_dim, net.rt.fingerprint)
+
+    @torch.no_grad()
+    def voice_from_wave(self, ref_wave):
+        """The Voice of a reference wave (24 kHz, already loaded / trimmed): the log-mel front end, the attached extractors, the voice"""
+        if getattr(self, "frontend", None) is None:
+            self.attach_frontend()
+        return self.voice_from_mel(self.frontend(ref_wave)[0])
+
+    def _voice_table(self, voice, B):
+        """one Voice (every utterance) or a list of B -> (device table [V, voice_dim], indices [B]); each voice checked against the model"""
+        rt = self.model.ArtsSpeech.rt
+        voices = [voice] * B if isinstance(voice, Voice) else list(voice)
+        if len(voices) != B:
+            raise ValueError(f"{len(voices)} voices for {B} utterances")
+        rows, idx = [], []
+        for v in voices:
+            if not isinstance(v, Voice):
+                raise TypeError("voice: expected a pipeline.Voice (voice_from_mel / voice_from_wave / Voice.load) or a list of them")
+            v.check(rt.fingerprint, int(rt.cfg.style_dim))
+            k = next((i for i, u in enumerate(rows) if u is v), None)
+            if k is None:
+                rows.append(v)
+                k = len(rows) - 1
+            idx.append(k)
+        table = torch.stack([v.vector for v in rows]).to(rt.device)
+        return table, torch.tensor(idx, dtype=torch.int32)
+
+    @torch.no_grad()
     def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed, 24 kHz) reference wave on: log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator.  Returns the samples (mel frames if no vocoder is attached).
@@ -97,26 +187,29 @@ class ArtSpeech:
         return self.generator
 
     @torch.no_grad()
-    def synthesis_wav(self, phonemes, ref_mel, features=None, forced_durations=None):
+    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised."""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         single = isinstance(phonemes, str)
-        mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations)
+        mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice)
         lens = self._last_frames
         wav = self.generator(mel, lengths=lens)[:, 0]
         return wav[0] if single else wav
 
     @torch.no_grad()
-    def synthesis_mel(self, phonemes, ref_mel, features=None, forced_durations=None, world=1, rank=0):
+    def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None):
         """phonemes: the string the phonemizer returns (test.py:94-96) or a list of such strings; ref_mel: normalised
         log-mel [80,T] (test.py:43-47) or a list; features: (f0_raw, ema_raw) per utterance when no extractor modules
         are attached; (None, ema_raw) with a pitch extractor attached (attach_pitch_extractor).  Returns mel [B,80,2*max M] (what test.py:115 hands to the vocoder).
         world / rank: BASELINE config C4 -- the batch is one GLOBAL batch, this process (one per GPU, torch.distributed initialised by
         the caller) synthesises its length-sorted round-robin shard (artspeech_amd.shard: no data-path collective) and rank 0 gets the
-        whole batch back in the caller's order (other ranks: None)."""
+        whole batch back in the caller's order (other ranks: None).
+        voice: a Voice (every utterance) or a list of them, in place of ref_mel / features: the reference is not processed again."""
+        if (voice is None) == (ref_mel is None):
+            raise ValueError("synthesis needs exactly one of ref_mel and voice")
         if world > 1 and not isinstance(phonemes, str):
             from . import shard
             lens = [len(p) for p in phonemes]
@@ -124,9 +217,10 @@ class ArtSpeech:
             def step(idx):
                 if not idx:
                     return []
-                sub = self.synthesis_mel([phonemes[i] for i in idx], [ref_mel[i] for i in idx],
+                sub = self.synthesis_mel([phonemes[i] for i in idx], None if ref_mel is None else [ref_mel[i] for i in idx],
                                          features=None if features is None else [features[i] for i in idx],
-                                         forced_durations=None if forced_durations is None else [forced_durations[i] for i in idx])
+                                         forced_durations=None if forced_durations is None else [forced_durations[i] for i in idx],
+                                         voice=voice if voice is None or isinstance(voice, Voice) else [voice[i] for i in idx])
                 return [sub[k, :, : self._last_frames[k]].cpu() for k in range(len(idx))]
 
             parts = shard.sharded_forward(step, lens, world, rank)
@@ -138,11 +232,21 @@ class ArtSpeech:
                 out[b, :, : p.shape[1]] = p
             return out
         if isinstance(phonemes, str):
-            phonemes, ref_mel = [phonemes], [ref_mel]
+            phonemes, ref_mel = [phonemes], None if ref_mel is None else [ref_mel]
             if features is not None:
                 features = [features]
         ids = [torch.LongTensor(self.textcleaner(p)) for p in phonemes]               # test.py:96-97
         B = len(ids)
+        if voice is not None:
+            table, vidx = self._voice_table(voice, B)
+            nmax = max(len(i) for i in ids)
+            text = torch.zeros(B, nmax, dtype=torch.long)
+            for b in range(B):
+                text[b, : len(ids[b])] = ids[b]
+            mel, aux = self.model.ArtsSpeech([text, torch.LongTensor([len(i) for i in ids]), None, None], None, None, step="test",
+                                             forced_durations=forced_durations, return_aux=True, voice=table, voice_idx=vidx)
+            self._last_frames = list(aux["frames2"])
+            return mel
         nmax, tmax = max(len(i) for i in ids), max(m.shape[-1] for m in ref_mel)
         text = torch.zeros(B, nmax, dtype=torch.long)
         mels = torch.zeros(B, ref_mel[0].shape[0], tmax)

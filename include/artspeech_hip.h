@@ -28,7 +28,7 @@ typedef void* as_stream_t; /* hipStream_t */
 /* library/ABI version; bumped on any change of a signature or of a struct's layout (never held back for anything outside this header:
  * bench.py's source id of the kernel sources leaves version.hip out).  as_abi_version() returns the AS_ABI_VERSION the library was built
  * from: a caller compiled against another header must not go on (artspeech_amd/_lib.py refuses to). */
-#define AS_ABI_VERSION 8
+#define AS_ABI_VERSION 9
 int as_abi_version(void);
 
 /* Device-side status.  The reference's operators cannot return silently stale results: nn.Embedding raises on an id >= n_token
@@ -51,12 +51,14 @@ int as_abi_version(void);
  *                               the capacity its caller named (as_forward_io.frame_cap): what was computed was cut at the capacity --
  *                               nothing was written out of bounds, the mel is void; run it again with more room (the counterpart of
  *                               AS_ENOSPC where no host read-back tells the host in time)
+ *   bit AS_STATUS_BAD_VOICE     a voice index outside [0, n_voices) reached a voice-mode forward (as_forward_io.voice_idx): that
+ *                               utterance's Style and dur_style were set to zeros -- nothing was read out of bounds, its mel is void
  * as_device_status returns the bits raised on the current HIP device since the last clear (0 = healthy) without synchronising; it is
  * final for work whose stream has been synchronised.  The module-level entry points (as_*_forward, as_forward_test*) return
  * AS_EDEVICE while any bit is set: results computed since it was raised are invalid; clear it to go on. */
 #define AS_EDEVICE (-3)
 enum { AS_STATUS_LSTM_TIMEOUT = 0, AS_STATUS_MAS_TIMEOUT = 1, AS_STATUS_BAD_TOKEN = 2, AS_STATUS_F16_RANGE = 3, AS_STATUS_BAD_LAYOUT = 4,
-       AS_STATUS_CAPACITY = 5, AS_STATUS_KINDS = 6 };
+       AS_STATUS_CAPACITY = 5, AS_STATUS_BAD_VOICE = 6, AS_STATUS_KINDS = 7 };
 int as_device_status(int clear);
 /* test hook: raise `kind` from a kernel on `stream`, exactly as a failing kernel would */
 int as_device_status_raise_for_test(int kind, as_stream_t stream);
@@ -642,9 +644,11 @@ typedef struct as_batch {
 } as_batch;
 
 enum { AS_MOD_FORWARD_A = 0, AS_MOD_FORWARD_B = 1, AS_MOD_ENCODER = 2, AS_MOD_STYLE = 3, AS_MOD_DURATION = 4, AS_MOD_ARTS = 5,
-       AS_MOD_DECODER = 6, AS_MOD_FORWARD_B_CAP = 7 };
+       AS_MOD_DECODER = 6, AS_MOD_FORWARD_B_CAP = 7, AS_MOD_VOICE = 8, AS_MOD_FORWARD_A_VOICE = 9 };
 /* workspace bytes of one module call for this geometry (AS_MOD_FORWARD_A / _B: the two workspaces of as_forward_test; AS_MOD_FORWARD_B_CAP:
- * workspace B of a call with as_forward_io.frame_cap = the SUM of batch->frames, whose entries are then capacities, not counts) */
+ * workspace B of a call with as_forward_io.frame_cap = the SUM of batch->frames, whose entries are then capacities, not counts;
+ * AS_MOD_VOICE: as_voice_forward; AS_MOD_FORWARD_A_VOICE: workspace A of a voice-mode forward (as_forward_io.voices), batch->ref_lens is not
+ * read.  Workspace B of a voice-mode forward is AS_MOD_FORWARD_B / _B_CAP; with batch->ref_lens NULL they are counted for voice mode) */
 size_t as_module_workspace_bytes(const as_model* m, as_plan* p, int module, const as_batch* batch);
 
 /* RelTransformerEncoder.forward (RelTransformerEnc.py:371-380).  which: 0 text_encoder, 1 arts_encoder, 2 the duration
@@ -669,6 +673,18 @@ int as_arts_forward(const as_model* m, as_plan* p, const as_batch* batch, const 
 int as_decoder_forward(const as_model* m, as_plan* p, const as_batch* batch, const float* asr, int lda, const float* style,
                        const float* F0, const float* N, const float* EMA, int ldp, float* mel, int ldo, void* ws, size_t ws_bytes,
                        as_stream_t stream);
+
+/* Voices: everything forward(step="test") takes from the reference utterance reduces to two vectors per speaker -- Style [2 * style_dim]
+ * (StyleEncoder.style_extractor on the T - 1 crop of the reference features, models.py:459-471; slices timbre [0, style_dim), TV
+ * [style_dim, 3/2 style_dim), F0 and energy the two quarters behind) and dur_style [style_dim / 4] (dur_linear(dur_block(ema_ext)) on the
+ * full-length TV track, models.py:541-546).  A voice is the two back to back: as_voice_dim(m) = 2 * style_dim + style_dim / 4 fp32,
+ * [0, 2 style_dim) Style, then dur_style.  as_voice_forward computes the voices of B reference utterances (batch->ref_lens; mel / f0_raw /
+ * ema_raw as in as_forward_io) into rows of voice [B][ld_voice >= as_voice_dim] (workspace: AS_MOD_VOICE) -- the same quantities the full
+ * forward computes -- and a forward with as_forward_io.voices set reads them instead of the reference: the style towers, the reference
+ * features and dur_block do not run at all. */
+int as_voice_dim(const as_model* m);
+int as_voice_forward(const as_model* m, as_plan* p, const as_batch* batch, const float* mel, int ldm, const float* f0_raw, const float* ema_raw,
+                     int lde, float* voice, int ld_voice, void* ws, size_t ws_bytes, as_stream_t stream);
 
 /* ArtsSpeech.forward(step="test") (models.py:356-371), batched: every utterance gets exactly its batch-1 result.
  * Two halves sharing workspace A: _begin runs everything up to the integer durations (encoders, style towers, duration
@@ -707,6 +723,13 @@ typedef struct as_forward_io {
      * whose frame_off[s] (optional, [its utterances + 1]) counts from 0 -- every submission is served as if it had been alone.  NULL: the
      * call is one submission (mel_out / frame_off above). */
     const struct as_segments* segs;
+    /* Voice mode (voices != NULL): utterance b speaks in row voice_idx[b] of the DEVICE table voices [n_voices][ld_voice >= as_voice_dim]
+     * (as_voice_forward's rows); voice_idx DEVICE int32 [B], read when the call runs (a replayed graph sees new contents), or NULL = row b.
+     * mel, f0_raw, ema_raw and batch->ref_lens are not read (they may be NULL); feat12 cannot be asked for (AS_EINVAL); `style` gets the
+     * gathered rows.  An index outside [0, n_voices) raises AS_STATUS_BAD_VOICE (that utterance gets a zero voice; nothing is read out of
+     * bounds).  Workspace A: AS_MOD_FORWARD_A_VOICE.  Works with known frames, the read-back, frame_cap and as_forward_test_begin / _finish. */
+    const float* voices; int32_t ld_voice; int32_t n_voices;
+    const int32_t* voice_idx;
 } as_forward_io;
 typedef struct as_segments {
     int32_t n;                      /* 1 .. AS_MAX_SEGMENTS */
@@ -761,7 +784,12 @@ int as_lanes_wait(as_lanes* q, int lane);
  * lane's buffers after as_lanes_wait(q, lane) -- or keep two blocks per lane and alternate.  Re-submitting the SAME unchanged buffers (a
  * benchmark's replay) needs nothing: a group's launch first waits for the lane's previous group.  The turn passes to the next lane when
  * a group is launched; as_lanes_destroy launches what still waits before it tears the lanes down.
- * (models.py:361-362 processes one utterance at a time: any grouping is legal, and every utterance gets its batch-1 result.) */
+ * (models.py:361-362 processes one utterance at a time: any grouping is legal, and every utterance gets its batch-1 result.)
+ * Voice mode (as_forward_io.voices): the tokens (and forced_dur / mel_out as above) are adjacent and the voices continue each other -- both
+ * with indices, the same voices / ld_voice / n_voices and voice_idx = the previous voice_idx + its B; or both without, the same ld_voice and
+ * voices = the previous voices + its B * ld_voice.  A voice submission never joins a group of reference submissions, nor the reverse.  The
+ * graph key holds the voice fields; the indices are device data read at replay.  Debug checksums cover voice_idx instead of the reference
+ * rows. */
 int as_lanes_set_coalesce(as_lanes* q, int k);
 int as_lanes_flush(as_lanes* q);
 /* Debug mode (also switched on by AS_DEBUG=1 in the environment at as_lanes_create).  The buffer rule above is the caller's to keep, and a
@@ -793,6 +821,11 @@ typedef struct as_host_io {
      * ld_out >= 2 * frame_cap and which is copied back whole) */
     int32_t frame_cap;
     int32_t* frame_off;
+    /* voice mode (as_forward_io.voices): voices is a DEVICE table [n_voices][ld_voice] that stays resident (it is not copied: keep it
+     * unchanged until as_lanes_wait); voice_idx is HOST int32 [B] (or NULL = row b), copied into the lane's block like the tokens.  mel,
+     * f0_raw, ema_raw and batch->ref_lens are then not read. */
+    const float* voices; int32_t ld_voice, n_voices;
+    const int32_t* voice_idx;
 } as_host_io;
 int as_lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_io* io, int32_t* lane_out);
 int64_t as_lanes_merged_calls(const as_lanes* q, int lane);   /* as_forward_test calls of this lane that held more than one submission */
