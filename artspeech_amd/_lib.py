@@ -32,7 +32,8 @@ _SIGNATURES = {
 }
 
 AS_MAX_TAPS = 25
-AS_ABI_VERSION = 9          # include/artspeech_hip.h
+AS_ABI_VERSION = 10         # include/artspeech_hip.h
+AS_PROSODY_DIM, AS_PROSODY_TRACKS, AS_PROSODY_DUR, AS_PROSODY_GAIN, AS_PROSODY_OFFSET = 25, 12, 0, 1, 13   # as_forward_io.prosody rows
 
 
 class ConvGemmArgs(ctypes.Structure):
@@ -150,13 +151,15 @@ class ForwardIO(ctypes.Structure):
                 ("forced_dur", c_p), ("mel_out", c_p), ("ld_out", ctypes.c_int32), ("duration", c_p), ("dur_i", c_p), ("frame_off", c_p),
                 ("style", c_p), ("feat12", c_p), ("ld_feat", ctypes.c_int32), ("t_en", c_p), ("a_en", c_p), ("ld_en", ctypes.c_int32),
                 ("F0", c_p), ("N", c_p), ("EMA", c_p), ("ld_pred", ctypes.c_int32), ("frame_cap", ctypes.c_int32), ("segs", c_p),
-                ("voices", c_p), ("ld_voice", ctypes.c_int32), ("n_voices", ctypes.c_int32), ("voice_idx", c_p)]
+                ("voices", c_p), ("ld_voice", ctypes.c_int32), ("n_voices", ctypes.c_int32), ("voice_idx", c_p),
+                ("prosody", c_p), ("ld_prosody", ctypes.c_int32)]
 
 
 class HostIO(ctypes.Structure):                 # as_host_io: HOST pointers (as_lanes_submit_host)
     _fields_ = [("tokens", c_p), ("mel", c_p), ("ld_mel", ctypes.c_int32), ("f0_raw", c_p), ("ema_raw", c_p), ("ld_ema", ctypes.c_int32),
                 ("forced_dur", c_p), ("mel_out", c_p), ("ld_out", ctypes.c_int32), ("frame_cap", ctypes.c_int32), ("frame_off", c_p),
-                ("voices", c_p), ("ld_voice", ctypes.c_int32), ("n_voices", ctypes.c_int32), ("voice_idx", c_p)]   # voices: DEVICE, voice_idx: HOST
+                ("voices", c_p), ("ld_voice", ctypes.c_int32), ("n_voices", ctypes.c_int32), ("voice_idx", c_p),   # voices: DEVICE, voice_idx: HOST
+                ("prosody", c_p), ("ld_prosody", ctypes.c_int32)]                                                    # prosody: HOST
 
 
 (AS_MOD_FORWARD_A, AS_MOD_FORWARD_B, AS_MOD_ENCODER, AS_MOD_STYLE, AS_MOD_DURATION, AS_MOD_ARTS, AS_MOD_DECODER, AS_MOD_FORWARD_B_CAP,

@@ -11,6 +11,8 @@ librosa's load / trim / resample (the wave must already be 24 kHz mono PCM; it i
 One voice, many sentences: ``--save-voice voice.npz`` (with ``--ref-wav``) also writes the voice computed from the reference, and
 ``--voice voice.npz`` replaces ``--ref-wav`` in later runs -- the reference is not processed again.  Exactly one of ``--ref-wav`` and
 ``--voice`` is given.
+
+How it is spoken: ``--speed`` (speaking rate, 1 = as predicted), ``--pitch-semitones`` and ``--energy-db`` (pipeline.Prosody).
 """
 import argparse
 import json
@@ -52,6 +54,9 @@ def build_parser():
     ref.add_argument("--ref-wav", help="reference utterance, 24 kHz mono PCM wav")
     ref.add_argument("--voice", help="a voice saved with --save-voice (in place of --ref-wav)")
     ap.add_argument("--save-voice", metavar="PATH", help="with --ref-wav: also write the voice computed from it (.npz)")
+    ap.add_argument("--speed", type=float, default=1.0, help="speaking rate: 2 = twice as fast (durations halved), in (0, 16]")
+    ap.add_argument("--pitch-semitones", type=float, default=0.0, help="raise (or, negative, lower) the pitch by this many semitones")
+    ap.add_argument("--energy-db", type=float, default=0.0, help="raise (or lower) the frame energy by this many dB")
     ap.add_argument("--out", default="output.wav")
     ap.add_argument("--jdc", help="Utils/JDC/bst.t7")
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
@@ -67,7 +72,19 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.save_voice and not a.ref_wav:
         ap.error("--save-voice needs --ref-wav (the voice is computed from it)")
+    try:
+        a.prosody = prosody_of(a)
+    except ValueError as e:
+        ap.error(str(e))
     return ap, a
+
+
+def prosody_of(a):
+    """the pipeline.Prosody of the parsed arguments, or None when they ask for no control"""
+    from .pipeline import Prosody
+    if a.speed == 1.0 and a.pitch_semitones == 0.0 and a.energy_db == 0.0:
+        return None
+    return Prosody(speed=a.speed, pitch_semitones=a.pitch_semitones, energy_db=a.energy_db)
 
 
 def main(argv=None):
@@ -94,13 +111,13 @@ def main(argv=None):
         tts.attach_vocoder(h, a.vocoder)
     if a.voice:
         from .pipeline import Voice
-        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts))
+        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody)
     else:
         wave_in = read_wav(a.ref_wav)
         if a.save_voice:
             tts.voice_from_wave(wave_in).save(a.save_voice)
             print(f"{a.save_voice}: voice of {a.ref_wav}")
-        audio = tts.synthesis_from_wave(a.phonemes, wave_in)
+        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody)
     write_wav(a.out, audio.cpu().numpy())
     print(f"{a.out}: {audio.numel() / 24000.0:.2f} s of audio from {tts._last_frames[0]} mel frames")
     return 0

@@ -87,6 +87,14 @@ int as_seg_scatter_launch(const AsSegScatter& a, hipStream_t stream);
 // an index outside [0, n_voices) writes zeros and raises AS_STATUS_BAD_VOICE
 int as_voice_gather_launch(const float* voices, int ld_voice, int n_voices, const int32_t* idx, int B, int n_style, int n_dur, float* style,
                            int ld_style, float* ds, int ld_ds, hipStream_t stream);
+// prosody control (as_forward_io.prosody, rows [B][ld_pros >= AS_PROSODY_DIM]; elementwise.hip).  as_durations_f32 with every predicted
+// duration of utterance b multiplied by pros[b][AS_PROSODY_DUR] before it is rounded (pros NULL: as_durations_f32 itself)
+int as_durations_prosody_launch(const float* dur_f32, const int32_t* forced_dur, const int32_t* tok_off, int B, const float* pros, int ld_pros,
+                                int32_t* dur_i32, int32_t* frame_off, int32_t* tok_of_frame, int max_frames, hipStream_t stream);
+// as_project_cols_f32 whose output row m is track track0 + m: column j of utterance b (col_off [B + 1], device) is stored as
+// fmaf(gain[b][track], y, offset[b][track]); columns at or past col_off[B] (a capacity layout's filler) as computed
+int as_project_cols_prosody_launch(const float* x, int ldx, int K, int N, const float* w, const float* bias, int M, float* y, int ldy,
+                                   const float* pros, int ld_pros, const int32_t* col_off, int B, int track0, hipStream_t s);
 
 // kernel classes for the optional event profiler (prof.hip)
 enum { AS_CLS_GEMM = 0, AS_CLS_ADAIN = 1, AS_CLS_LN = 2, AS_CLS_ATTN = 3, AS_CLS_LSTM = 4, AS_CLS_MAS = 5, AS_CLS_OTHER = 6, AS_N_CLS = 7 };

@@ -324,10 +324,15 @@ extern "C" int as_linear_rows_f32(const float* x, int ldx, const float* w, const
 // F0 / energy / TV projections, models.py:565,619-621).  One column per thread: every X row is read once, coalesced;
 // the weights are wave-uniform (scalar loads).
 // ---------------------------------------------------------------------------------------------------
+// Prosody control (pros != NULL; as_project_cols_prosody_launch): output row m is track track0 + m of the AS_PROSODY_DIM-wide rows
+// pros [B][ldr], and column j of utterance b (col_off [B + 1]: the layout's device column offsets) is stored as fmaf(gain, y, offset).
+// The utterance: the last b with col_off[b] <= j, by binary search (B <= 1024: ten probes of a table that stays in cache); columns at or
+// past col_off[B] (a capacity layout's filler) are stored as computed.  One kernel for both, so that the sums are the same instructions:
+// a separate kernel from the same source was compiled into other fused multiply-adds, and the identity row did not give the same bits.
 template <int MM>
 __global__ void __launch_bounds__(256)
 project_cols_kernel(const float* __restrict__ x, int ldx, int K, int N, const float* w, const float* __restrict__ bias, int M,
-                    float* __restrict__ y, int ldy)
+                    float* __restrict__ y, int ldy, const float* __restrict__ pros, int ldr, const int* __restrict__ col_off, int B, int track0)
 {
     // block = 64 columns x 4 k-slices (one wave each: rows k = wave, wave + 4, ...), partial sums meet in LDS; the weights are
     // staged in LDS once, k-major and zero-padded to MM outputs: the MM weights of a k are one or four 16-byte broadcasts and the
@@ -379,10 +384,22 @@ project_cols_kernel(const float* __restrict__ x, int ldx, int K, int N, const fl
         for (int m = 0; m < MM; ++m) part[wave - 1][m][lane] = acc[m];
     }
     __syncthreads();
-    if (wave == 0 && ok) {
+    if (wave != 0 || !ok) return;
+    const float* r = nullptr;                                           // (prosody: this column's gains at r[AS_PROSODY_GAIN + m])
+    if (pros) {
+        int lo = 0, hi = B;
+        while (hi > lo) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (col_off[mid] <= j) lo = mid;
+            else hi = mid - 1;
+        }
+        if (lo < B) r = pros + (size_t)lo * ldr + track0;
+    }
 #pragma unroll
-        for (int m = 0; m < MM; ++m)
-            if (m < M) y[(size_t)m * ldy + j] = ((acc[m] + part[0][m][lane]) + (part[1][m][lane] + part[2][m][lane])) + (bias ? bias[m] : 0.f);
+    for (int m = 0; m < MM; ++m) {
+        if (m >= M) continue;
+        const float v = ((acc[m] + part[0][m][lane]) + (part[1][m][lane] + part[2][m][lane])) + (bias ? bias[m] : 0.f);
+        y[(size_t)m * ldy + j] = r ? __builtin_fmaf(r[AS_PROSODY_GAIN + m], v, r[AS_PROSODY_OFFSET + m]) : v;
     }
 }
 
@@ -396,9 +413,29 @@ extern "C" int as_project_cols_f32(const float* x, int ldx, int K, int N, const 
     AsProfScope prof__(AS_FILE_CLS, 2.0 * M * K * (double)N, 4.0 * (K + M) * (double)N, (hipStream_t)stream);
     const dim3 grid(as_cdiv(N, 64)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (M == 1) hipLaunchKernelGGL(project_cols_kernel<1>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy);
-    else if (M <= 4) hipLaunchKernelGGL(project_cols_kernel<4>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy);
-    else hipLaunchKernelGGL(project_cols_kernel<16>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy);
+    const float* np = nullptr;
+    const int* nc = nullptr;
+    if (M == 1) hipLaunchKernelGGL(project_cols_kernel<1>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy, np, 0, nc, 0, 0);
+    else if (M <= 4) hipLaunchKernelGGL(project_cols_kernel<4>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy, np, 0, nc, 0, 0);
+    else hipLaunchKernelGGL(project_cols_kernel<16>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy, np, 0, nc, 0, 0);
+    AS_CHECK_LAUNCH();
+    return AS_OK;
+}
+
+int as_project_cols_prosody_launch(const float* x, int ldx, int K, int N, const float* w, const float* bias, int M, float* y, int ldy,
+                                   const float* pros, int ld_pros, const int32_t* col_off, int B, int track0, hipStream_t s)
+{
+    const int MM = M == 1 ? 1 : M <= 4 ? 4 : 16;
+    if (!x || !w || !y || !pros || !col_off || K <= 0 || N < 0 || M <= 0 || M > 16 || (size_t)MM * K * 4 > 48 * 1024 || ldx < N || ldy < N ||
+        ld_pros < AS_PROSODY_DIM || B < 1 || track0 < 0 || track0 + M > AS_PROSODY_TRACKS)
+        return AS_EINVAL;
+    if (N == 0) return AS_OK;
+    const size_t wsz = (size_t)MM * K * sizeof(float);
+    AsProfScope prof__(AS_FILE_CLS, 2.0 * M * K * (double)N, 4.0 * (K + M) * (double)N, s);
+    const dim3 grid(as_cdiv(N, 64)), block(256);
+    if (M == 1) hipLaunchKernelGGL(project_cols_kernel<1>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy, pros, ld_pros, col_off, B, track0);
+    else if (M <= 4) hipLaunchKernelGGL(project_cols_kernel<4>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy, pros, ld_pros, col_off, B, track0);
+    else hipLaunchKernelGGL(project_cols_kernel<16>, grid, block, wsz, s, x, ldx, K, N, w, bias, M, y, ldy, pros, ld_pros, col_off, B, track0);
     AS_CHECK_LAUNCH();
     return AS_OK;
 }
@@ -462,12 +499,24 @@ extern "C" int as_pointwise_small_f32(const float* x, int ldx, int K, int N, con
 __global__ void __launch_bounds__(1024)
 durations_kernel(const float* __restrict__ dur_f, const int* __restrict__ forced, const int* __restrict__ tok_off,
                  int B, int* __restrict__ dur_i, int* __restrict__ frame_off, int* __restrict__ tok_of_frame,
-                 int max_frames, unsigned* __restrict__ status)
+                 int max_frames, unsigned* __restrict__ status, const float* __restrict__ pros, int ldr)
 {
     __shared__ int sums[1024];
     const int ntok = tok_off[B];
     const int t = threadIdx.x;
     const int per = (ntok + 1023) / 1024, lo = min(t * per, ntok), hi = min(lo + per, ntok);
+    // prosody control (pros != NULL: rows [B][ldr], AS_PROSODY_DUR scales the predictor's durations): the utterance of token lo --
+    // the last ub < B with tok_off[ub] <= lo -- found once, then advanced along the chunk (its tokens are contiguous)
+    int ub = 0;
+    if (pros && lo < hi) {
+        int l = 0, h = B - 1;
+        while (h > l) {
+            const int mid = (l + h + 1) >> 1;
+            if (tok_off[mid] <= lo) l = mid;
+            else h = mid - 1;
+        }
+        ub = l;
+    }
     int local = 0;
     for (int i = lo; i < hi; ++i) {
         int d;
@@ -476,7 +525,11 @@ durations_kernel(const float* __restrict__ dur_f, const int* __restrict__ forced
             // (the reference's `int(pred_dur[i])` raises on NaN / inf, models.py:363-366: here the device status does -- the count
             //  becomes 1 -- and an absurd finite value is held at 16 384 frames per token so that the sums stay inside an int: the caller's
             //  AS_ENOSPC path meets it)
-            const float v = dur_f[i];
+            float v = dur_f[i];
+            if (pros) {
+                while (ub + 1 < B && tok_off[ub + 1] <= i) ++ub;
+                v = v * pros[(size_t)ub * ldr + AS_PROSODY_DUR];
+            }
             const bool fin = fabsf(v) <= 3.0e38f;
             if (!fin) as_status_raise(status, AS_STATUS_F16_RANGE);
             const float r = fin ? rintf(v) : 1.f;          // ties to even, like torch.round
@@ -519,16 +572,24 @@ durations_kernel(const float* __restrict__ dur_f, const int* __restrict__ forced
     }
 }
 
+int as_durations_prosody_launch(const float* dur_f32, const int32_t* forced_dur, const int32_t* tok_off, int B, const float* pros, int ld_pros,
+                                int32_t* dur_i32, int32_t* frame_off, int32_t* tok_of_frame, int max_frames, hipStream_t stream)
+{
+    if ((!dur_f32 && !forced_dur) || !tok_off || !dur_i32 || !frame_off || B < 0 || B > 1024) return AS_EINVAL;
+    if (pros && (forced_dur || B < 1 || ld_pros < AS_PROSODY_DIM)) return AS_EINVAL;   // (forced durations would not be scaled)
+    AsProfScope prof__(AS_FILE_CLS, 0, 0, stream);
+    hipLaunchKernelGGL(durations_kernel, dim3(1), dim3(1024), 0, stream, dur_f32, forced_dur, tok_off, B,
+                       dur_i32, frame_off, tok_of_frame, max_frames, as_status_words_device(), pros, ld_pros);
+    AS_CHECK_LAUNCH();
+    return AS_OK;
+}
+
 extern "C" int as_durations_f32(const float* dur_f32, const int32_t* forced_dur, const int32_t* tok_off, int B,
                                 int32_t* dur_i32, int32_t* frame_off, int32_t* tok_of_frame, int max_frames,
                                 as_stream_t stream)
 {
-    if ((!dur_f32 && !forced_dur) || !tok_off || !dur_i32 || !frame_off || B < 0 || B > 1024) return AS_EINVAL;
-    AsProfScope prof__(AS_FILE_CLS, 0, 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(durations_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, dur_f32, forced_dur, tok_off, B,
-                       dur_i32, frame_off, tok_of_frame, max_frames, as_status_words_device());
-    AS_CHECK_LAUNCH();
-    return AS_OK;
+    return as_durations_prosody_launch(dur_f32, forced_dur, tok_off, B, nullptr, 0, dur_i32, frame_off, tok_of_frame, max_frames,
+                                       (hipStream_t)stream);
 }
 
 // y[c][f*rep + r] = x[c][tok_of_frame[f]]     (T_en @ aln, and the decoder's nearest x2: models.py:367-368, :500)

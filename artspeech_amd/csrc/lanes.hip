@@ -63,6 +63,7 @@ struct Lane {
         int used_vid = 0;                                         // voice indices taken (one per utterance: a group's indices lie back to back)
         int32_t *tokens = nullptr, *forced = nullptr, *foff = nullptr;   // (foff: frame offsets of submissions under a frame capacity, [utterances + 1] each)
         int32_t* vidx = nullptr;                                  // voice indices of voice-mode submissions [utterances]
+        float* pros = nullptr;                                    // prosody rows [utterances][AS_PROSODY_DIM] (at used_vid, like the indices)
         float *f0 = nullptr, *ema = nullptr, *mel = nullptr, *out = nullptr;
     } blk[2];                                                     // two, alternating from group to group: the next group's copies run under this group's kernels
     int cur = 0;                                                  // the block the group that is being filled lives in
@@ -103,6 +104,7 @@ std::string key_of(const as_batch* b, const as_forward_io* io)
     put(k, io->F0); put(k, io->N); put(k, io->EMA); put(k, io->ld_pred);
     put(k, io->frame_cap);
     put(k, io->voices); put(k, io->ld_voice); put(k, io->n_voices); put(k, io->voice_idx);   // (the indices' CONTENTS are read at replay)
+    put(k, io->prosody); put(k, io->ld_prosody);                                                  // (... and so are the prosody rows)
     if (io->segs) {
         const as_segments& g = *io->segs;
         put(k, g.n);
@@ -429,6 +431,13 @@ static bool voices_adjacent(const as_forward_io& a, long prev_B, const as_forwar
         return io->voices == a.voices && io->ld_voice == a.ld_voice && io->n_voices == a.n_voices && io->voice_idx == a.voice_idx + prev_B;
     return !io->voice_idx && !a.voice_idx && io->ld_voice == a.ld_voice && a.n_voices >= prev_B && io->voices == a.voices + prev_B * a.ld_voice;
 }
+// Prosody control (as_forward_io.prosody): utterance b of the merged call reads row b of the first submission's rows -- so every
+// submission's rows continue where the previous one's end, with the same stride; or no submission of the group carries any.
+static bool prosody_adjacent(const as_forward_io& a, long prev_B, const as_forward_io* io)
+{
+    if ((io->prosody != nullptr) != (a.prosody != nullptr)) return false;
+    return !io->prosody || (io->ld_prosody == a.ld_prosody && io->prosody == a.prosody + prev_B * a.ld_prosody);
+}
 static bool adjacent(const Lane::Pending& p, const as_forward_io* io, bool cap_mode)
 {
     long nt = 0, nr = 0, nf = 0;
@@ -437,7 +446,7 @@ static bool adjacent(const Lane::Pending& p, const as_forward_io* io, bool cap_m
     for (int32_t v : p.frames) nf += v;
     const as_forward_io& a = p.io;
     if (cap_mode != (p.frames.empty() && a.frame_cap > 0)) return false;   // (a group is of one kind)
-    if (!voices_adjacent(a, (long)p.tok_lens.size(), io)) return false;
+    if (!voices_adjacent(a, (long)p.tok_lens.size(), io) || !prosody_adjacent(a, (long)p.tok_lens.size(), io)) return false;
     const bool in = io->tokens == a.tokens + nt &&
                     (io->voices || (io->mel == a.mel + nr && io->ld_mel == a.ld_mel && io->f0_raw == a.f0_raw + nr && io->ema_raw == a.ema_raw + nr &&
                                     io->ld_ema == a.ld_ema));
@@ -455,7 +464,7 @@ static bool plain_cap_io(const as_forward_io* io)
 // ---- debug mode (as_lanes_set_debug, AS_DEBUG=1) -------------------------------------------------------------------------------------
 // Under coalescing a submission's device buffers are read when its GROUP is launched, not when it is submitted: a caller that refills them
 // in between corrupts a batch without any sign.  Debug mode makes that loud: the inputs of a held-back submission (tokens, forced
-// durations, f0, the EMA and mel rows; in voice mode the voice indices) are checksummed on the lane's stream when it is submitted -- the call then WAITS for that stream,
+// durations, f0, the EMA and mel rows; in voice mode the voice indices; the prosody rows) are checksummed on the lane's stream when it is submitted -- the call then WAITS for that stream,
 // so the sum is of the data the caller handed over -- and again when the group goes out; a difference raises AS_STATUS_BAD_LAYOUT (the
 // group's launch returns AS_EDEVICE, as every entry point does while a bit is set).  Costs a stream synchronisation per submission.
 __global__ void __launch_bounds__(256)
@@ -497,6 +506,7 @@ static int inputs_sum(as_lanes* q, Lane& L, const std::vector<int32_t>& tok_lens
         add(io.ema_raw, nr, 10, io.ld_ema, 0x400000000ull);
         add(io.mel, nr, q->cfg.n_mels, io.ld_mel, 0x500000000ull);
     }
+    add(io.prosody, AS_PROSODY_DIM, (long)tok_lens.size(), io.ld_prosody, 0x700000000ull);
     AS_CHECK_LAUNCH();
     AS_CHECK(hipMemcpyAsync(sum, L.dbg, sizeof(unsigned long long), hipMemcpyDeviceToHost, L.stream));
     AS_CHECK(hipStreamSynchronize(L.stream));
@@ -609,6 +619,7 @@ static int lanes_submit(as_lanes* q, const as_batch* batch, const as_forward_io*
                         float* out_host = nullptr, int32_t ld_out_host = 0, int32_t* foff_host = nullptr)
 {
     if (!q || !batch || !io || batch->B <= 0 || !batch->tok_lens || (!batch->ref_lens && !io->voices)) return AS_EINVAL;
+    if (io->prosody && (io->ld_prosody < AS_PROSODY_DIM || io->forced_dur)) return AS_EINVAL;   // (refused now, not when its group goes out)
     Lane& L = q->lanes[q->next];
     // (a host submission always joins the group of its lane's block -- a group of one when coalescing is off)
     const bool cap_mode = !batch->frames && io->frame_cap > 0;
@@ -685,8 +696,8 @@ static int block_fit(as_lanes* q, Lane& L, long nt, long nr, long nf2, int n_utt
     const int ct = std::max(b.cap_tok, grow_to(nt, k)), cr = std::max(b.cap_ref, grow_to(nr, k)), co = std::max(b.cap_out, grow_to(nf2, k));
     const int cu = std::max(b.cap_utt, grow_to(n_utt + 1, k));
     const int n_mels = q->cfg.n_mels;
-    const size_t bytes = 2 * up256((size_t)ct * 4) + 2 * up256((size_t)cu * 4) + up256((size_t)cr * 4) + up256((size_t)10 * cr * 4) +
-                         up256((size_t)n_mels * cr * 4) + up256((size_t)n_mels * co * 4);
+    const size_t bytes = 2 * up256((size_t)ct * 4) + 2 * up256((size_t)cu * 4) + up256((size_t)AS_PROSODY_DIM * cu * 4) + up256((size_t)cr * 4) +
+                         up256((size_t)10 * cr * 4) + up256((size_t)n_mels * cr * 4) + up256((size_t)n_mels * co * 4);
     AS_CHECK(hipStreamSynchronize(L.stream));                     // the groups that used the old block have left it: kernels ...
     AS_CHECK(hipStreamSynchronize(q->d2h));                       // ... and the copies of their results
     drop_graphs(L);                                               // (its graphs hold the old block's addresses)
@@ -704,6 +715,7 @@ static int block_fit(as_lanes* q, Lane& L, long nt, long nr, long nf2, int n_utt
     b.forced = reinterpret_cast<int32_t*>(c); c += up256((size_t)ct * 4);
     b.foff = reinterpret_cast<int32_t*>(c); c += up256((size_t)cu * 4);
     b.vidx = reinterpret_cast<int32_t*>(c); c += up256((size_t)cu * 4);
+    b.pros = reinterpret_cast<float*>(c); c += up256((size_t)AS_PROSODY_DIM * cu * 4);
     b.f0 = reinterpret_cast<float*>(c); c += up256((size_t)cr * 4);
     b.ema = reinterpret_cast<float*>(c); c += up256((size_t)10 * cr * 4);
     b.mel = reinterpret_cast<float*>(c); c += up256((size_t)n_mels * cr * 4);
@@ -719,6 +731,8 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
     // frame counts from the caller, or a capacity (durations predicted on the device: the frame offsets come back with the mel)
     const bool cap_mode = !batch->frames;
     if (cap_mode && (h->frame_cap < 1 || !h->frame_off || h->forced_dur)) return AS_EINVAL;
+    if (h->prosody && (h->ld_prosody < AS_PROSODY_DIM || h->forced_dur)) return AS_EINVAL;
+    const bool pros = h->prosody != nullptr;                      // (prosody rows travel with the tokens, back to back in the block)
     long nt = 0, nr = 0, nf = 0;
     for (int b = 0; b < batch->B; ++b) {
         if (batch->tok_lens[b] < 0 || (!voice && batch->ref_lens[b] < 0) || (!cap_mode && batch->frames[b] < 0)) return AS_EINVAL;
@@ -732,7 +746,8 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
         // what waits on this lane came with device buffers of the caller's, or the block is full: that group goes out first
         size_t waiting = 0;
         for (const Lane::Pending& p : L.pend) waiting += p.tok_lens.size();
-        // (voice mode: the group's indices lie back to back in the block, so indexed submissions of one table always continue each other)
+        // (voice mode: the group's indices lie back to back in the block, so indexed submissions of one table always continue each other;
+        //  so do the prosody rows, and a group carries them for all of its submissions or for none)
         bool voice_fits = true;
         if (!L.pend.empty()) {
             const as_forward_io& a = L.pend.back().io;
@@ -741,6 +756,7 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
                          (!voice || (h->voice_idx ? (a.voice_idx && a.voices == h->voices && a.ld_voice == h->ld_voice && a.n_voices == h->n_voices)
                                                   : (!a.voice_idx && a.ld_voice == h->ld_voice && a.n_voices >= prev_B &&
                                                      h->voices == a.voices + prev_B * a.ld_voice)));
+            voice_fits = voice_fits && (a.prosody != nullptr) == pros;
         }
         const bool foreign = !L.pend.empty() && (!L.pend.back().out_host || (L.pend.back().io.forced_dur != nullptr) != (h->forced_dur != nullptr) ||
                                                  waiting + (size_t)batch->B > 1024 || L.pend.back().frames.empty() != cap_mode ||
@@ -760,6 +776,9 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
         AS_CHECK(hipMemcpyAsync(b.tokens + b.used_tok, h->tokens, (size_t)nt * 4, hipMemcpyHostToDevice, s));
         if (h->forced_dur) AS_CHECK(hipMemcpyAsync(b.forced + b.used_tok, h->forced_dur, (size_t)nt * 4, hipMemcpyHostToDevice, s));
         if (voice && h->voice_idx) AS_CHECK(hipMemcpyAsync(b.vidx + b.used_vid, h->voice_idx, (size_t)batch->B * 4, hipMemcpyHostToDevice, s));
+        if (pros)
+            AS_CHECK(hipMemcpy2DAsync(b.pros + (size_t)b.used_vid * AS_PROSODY_DIM, (size_t)AS_PROSODY_DIM * 4, h->prosody, (size_t)h->ld_prosody * 4,
+                                      (size_t)AS_PROSODY_DIM * 4, (size_t)batch->B, hipMemcpyHostToDevice, s));
         if (!voice) AS_CHECK(hipMemcpyAsync(b.f0 + b.used_ref, h->f0_raw, (size_t)nr * 4, hipMemcpyHostToDevice, s));
         if (nr > 0) {
             AS_CHECK(hipMemcpy2DAsync(b.ema + b.used_ref, (size_t)b.cap_ref * 4, h->ema_raw, (size_t)h->ld_ema * 4, (size_t)nr * 4, 10, hipMemcpyHostToDevice, s));
@@ -776,6 +795,10 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
             io.mel = b.mel + b.used_ref; io.ld_mel = b.cap_ref;
             io.f0_raw = b.f0 + b.used_ref;
             io.ema_raw = b.ema + b.used_ref; io.ld_ema = b.cap_ref;
+        }
+        if (pros) {
+            io.prosody = b.pros + (size_t)b.used_vid * AS_PROSODY_DIM;
+            io.ld_prosody = AS_PROSODY_DIM;
         }
         io.forced_dur = h->forced_dur ? b.forced + b.used_tok : nullptr;
         io.mel_out = b.out + b.used_out; io.ld_out = b.cap_out;

@@ -1885,8 +1885,10 @@ std::vector<as_model::NormSpec> style_norms(const as_model& m)
 
 // ArtsPredictor.forward (models.py:596-621): a [C][N1] on `lay` -> fne [12][ldp]: row 0 F0, 1 N, 2..11 EMA, on the x2 layout.
 // The F0 / N / EMA branches (three AdainResBlk1d each, identical shapes) run as ONE grouped launch sequence on a layout that holds
-// the batch three times; the three BiLSTMs share one recurrence launch.
-void arts_predictor(Ctx& c, const float* a_en, int lda, const Lay* lay, const FcOut& fc, float* fne, int ldp)
+// the batch three times; the three BiLSTMs share one recurrence launch.  pros (as_forward_io.prosody, rows [B][ld_pros]): the track
+// projections store every utterance's tracks through its gains and offsets (same launches, an epilogue of their own).
+void arts_predictor(Ctx& c, const float* a_en, int lda, const Lay* lay, const FcOut& fc, float* fne, int ldp, const float* pros = nullptr,
+                    int ld_pros = 0)
 {
     const as_model& m = c.m;
     const std::string p = "artsPredictor";
@@ -2015,7 +2017,11 @@ void arts_predictor(Ctx& c, const float* a_en, int lda, const Lay* lay, const Fc
     const int rows[3] = {0, 1, 2}, M[3] = {1, 1, 10};
     for (int g = 0; g < 3; ++g) {
         const float *pw = m.vec(p + "." + br[g] + "_proj.weight"), *pb = m.vec(p + "." + br[g] + "_proj.bias");
-        RUN(c, as_project_cols_f32(hs + (size_t)g * N2, NG2, 2 * H, N2, pw, pb, M[g], fne + (size_t)rows[g] * ldp, ldp, c.s));
+        if (pros)
+            RUN(c, as_project_cols_prosody_launch(hs + (size_t)g * N2, NG2, 2 * H, N2, pw, pb, M[g], fne + (size_t)rows[g] * ldp, ldp, pros, ld_pros,
+                                                  lay2->d_off, B, rows[g], c.s));
+        else
+            RUN(c, as_project_cols_f32(hs + (size_t)g * N2, NG2, 2 * H, N2, pw, pb, M[g], fne + (size_t)rows[g] * ldp, ldp, c.s));
     }
 }
 
@@ -2235,7 +2241,8 @@ PhaseA forward_a_full(Ctx& c, const as_batch* batch, const as_forward_io* io)
     // round half even -> clamp(min = 1) (or the forced durations), per-utterance frame offsets (models.py:361-366)
     // (with the frame counts given nobody reads this half's copy: the second half computes durations, offsets and the frame -> token map)
     // (... and so does a call under a frame capacity, as_forward_io.frame_cap)
-    if (!batch->frames && io->frame_cap <= 0) RUN(c, as_durations_f32(A.duration, io->forced_dur, A.tok->d_off, B, A.dur_i, A.frame_off, nullptr, 0, c.s));
+    if (!batch->frames && io->frame_cap <= 0)
+        RUN(c, as_durations_prosody_launch(A.duration, io->forced_dur, A.tok->d_off, B, io->prosody, io->ld_prosody, A.dur_i, A.frame_off, nullptr, 0, c.s));
     return A;
 }
 
@@ -2283,7 +2290,8 @@ PhaseA forward_a_voice(Ctx& c, const as_batch* batch, const as_forward_io* io)
     A.ld_en = eo.ld[ENC_ARTS];
     f.join();
     if (c.go()) c.p.mark(2, c.s);
-    if (!batch->frames && io->frame_cap <= 0) RUN(c, as_durations_f32(A.duration, io->forced_dur, A.tok->d_off, B, A.dur_i, A.frame_off, nullptr, 0, c.s));
+    if (!batch->frames && io->frame_cap <= 0)
+        RUN(c, as_durations_prosody_launch(A.duration, io->forced_dur, A.tok->d_off, B, io->prosody, io->ld_prosody, A.dur_i, A.frame_off, nullptr, 0, c.s));
     return A;
 }
 
@@ -2321,7 +2329,7 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
     float* mel_packed = dyn ? c.f32((size_t)n_mels * std::max(N2, 1)) : nullptr;   // (a merged call's mel before it goes to the submissions' slots)
     if (io->dur_i) dur_i = io->dur_i;
     if (io->frame_off && !segs) frame_off = io->frame_off;
-    RUN(c, as_durations_f32(A.duration, io->forced_dur, A.tok->d_off, B, dur_i, frame_off, tof, N1, c.s));
+    RUN(c, as_durations_prosody_launch(A.duration, io->forced_dur, A.tok->d_off, B, io->prosody, io->ld_prosody, dur_i, frame_off, tof, N1, c.s));
     if (dyn) {
         const Lay *lg1 = c.dyn_lay(2, B, io->frame_cap), *lg2 = lg1 ? c.scaled(lg1, 2) : nullptr;
         if (!lg1 || !lg2) return;
@@ -2370,7 +2378,7 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
         }
         c.hint(0, 4.0 * C * ((double)A.tok->N + N1));
         RUN(c, as_expand_f32(A.a_en, A.ld_en, C, tof, N1, 1, a_ex, N1, c.s));
-        arts_predictor(c, a_ex, N1, lay1, fc, fne, N2);
+        arts_predictor(c, a_ex, N1, lay1, fc, fne, N2, io->prosody, io->ld_prosody);
         if (f) f->join();
     }
     if (c.go()) c.p.mark(3, c.s);
@@ -2421,6 +2429,7 @@ bool io_ok(const as_forward_io* io, bool need_out)
 bool forward_ok(const as_model* m, const as_batch* batch, const as_forward_io* io, bool need_out, bool frames)
 {
     if (!io || !batch_ok(batch, true, !io->voices, frames)) return false;
+    if (io->prosody && (io->ld_prosody < AS_PROSODY_DIM || io->forced_dur)) return false;   // (forced durations would ignore dur_scale)
     if (!io->voices) return io_ok(io, need_out);
     return io->tokens && (!need_out || io->mel_out) && io->ld_voice >= voice_dim(*m) && io->n_voices >= 1 && !io->feat12;
 }

@@ -4,4 +4,5 @@
 // frame capacity, the host submissions and the debug checks of as_lanes (round 6)
 // 9: voices -- as_voice_dim / as_voice_forward, as_forward_io and as_host_io voice fields, AS_MOD_VOICE / AS_MOD_FORWARD_A_VOICE,
 // AS_STATUS_BAD_VOICE
+// 10: prosody control -- as_forward_io and as_host_io prosody / ld_prosody, AS_PROSODY_DIM and the row offsets
 extern "C" int as_abi_version(void) { return AS_ABI_VERSION; }

@@ -15,6 +15,9 @@ Voices: everything forward(step="test") takes from the reference reduces to Styl
 ``ArtsSpeech.compute_voice`` computes them once (as_voice_forward: one row of ``voice_dim`` floats per reference, Style first); ``forward`` /
 ``forward_packed`` / ``Lanes.submit`` with ``voice=`` (a [V, voice_dim] table) and ``voice_idx=`` (row per utterance, None = row b) then
 skip the reference features, the style towers and dur_block.
+
+Prosody: ``prosody=`` (a [B, 25] tensor, pipeline.Prosody rows) on the same calls sets each utterance's speaking rate (its durations are
+scaled before they are rounded) and a gain and an offset for each of the twelve tracks the decoder reads (F0, energy, EMA0..9, normalised).
 """
 import ctypes
 import hashlib
@@ -188,6 +191,28 @@ def _voice_args(rt, voice, voice_idx, B, device_idx=True):
 
 def _set_voice(io, fields):
     io.voices, io.ld_voice, io.n_voices, io.voice_idx = fields
+
+
+def _prosody_args(rt, prosody, B, where="device"):
+    """prosody -> (pointer, ld_prosody) of as_forward_io / as_host_io and the tensor to keep alive.  prosody: fp32 [B, >= AS_PROSODY_DIM]
+    (pipeline.Prosody rows: dur_scale, 12 gains, 12 offsets per utterance), dense rows.  where: "device" -- a tensor on the model's GPU
+    (read when the call runs), "host" -- a host tensor (copied at submit), "any" -- anything torch.as_tensor takes, moved to the GPU."""
+    if prosody is None:
+        return (None, 0), None
+    if where == "any":
+        prosody = torch.as_tensor(prosody, dtype=torch.float32).to(rt.device).contiguous()
+    if not torch.is_tensor(prosody) or prosody.dim() != 2 or prosody.shape[0] != B or prosody.shape[1] < _lib.AS_PROSODY_DIM or \
+            prosody.dtype != torch.float32:
+        got = tuple(prosody.shape) if torch.is_tensor(prosody) else type(prosody).__name__
+        raise ValueError(f"prosody: expected a float32 [{B}, {_lib.AS_PROSODY_DIM}] tensor (one row per utterance), got {got}")
+    on_gpu = prosody.is_cuda and prosody.device == rt.device
+    if prosody.stride(-1) != 1 or (where == "host" and prosody.is_cuda) or (where != "host" and not on_gpu):
+        raise _lib.HipLibraryError(f"prosody: expected {'a host' if where == 'host' else 'a device'} tensor with dense rows")
+    return (prosody.data_ptr(), prosody.stride(0)), prosody
+
+
+def _set_prosody(io, fields):
+    io.prosody, io.ld_prosody = fields
 
 
 def _pack_tokens(x, lens, n_token):
@@ -401,9 +426,11 @@ class ArtsSpeech(_Module):
         return v
 
     def forward(self, batch, s2s_attn=None, s2s_attn_mono=None, step="test", mode="train", epoch=0, features=None,
-                forced_durations=None, return_aux=False, voice=None, voice_idx=None):
+                forced_durations=None, return_aux=False, voice=None, voice_idx=None, prosody=None):
         """voice: a [V, voice_dim] table of compute_voice rows -- utterance b then speaks in row voice_idx[b] (None: row b), and the batch's
-        mels / mel_input_length are not read (they may be None)."""
+        mels / mel_input_length are not read (they may be None).
+        prosody: [B, 25] rows of pipeline.Prosody (as_forward_io.prosody: speaking rate, then a gain and an offset per F0 / energy / EMA
+        track); not with forced_durations."""
         if step != "test":
             raise NotImplementedError("training branches (step='first'/'second') are out of scope (SURVEY.md section 2)")
         if self.rt is None:
@@ -429,23 +456,25 @@ class ArtsSpeech(_Module):
                 forced = torch.cat(fd).to(device=dev, dtype=torch.int32)
                 frames = [int(f.sum()) for f in fd]
             out = self.forward_packed(tok, tl, mel_p, f0_p, ema_p, ml, forced=forced, frames_hint=frames, aux=return_aux, voice=voice,
-                                      voice_idx=voice_idx)
+                                      voice_idx=voice_idx, prosody=prosody)
             mel = unpack(out["mel"], layout(out["frames2"], dev))
         if return_aux:
             return mel, out
         return mel
 
     def forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None,
-                       voice=None, voice_idx=None):
+                       voice=None, voice_idx=None, prosody=None):
         """The whole hot path on packed tensors (what bench.py times): one call of as_forward_test when the integer frame
         counts are known (forced durations), else as_forward_test_begin -> one device->host read of B + 1 integers ->
         as_forward_test_finish.  `out`: the dict of a previous call with the same geometry (its tensors are reused).
         frame_cap (predicted durations only): the half-rate frames to make room for, all utterances together -- ONE as_forward_test call
         with no read-back (capturable); the result's `frame_off` (device, [B + 1]) says where each utterance's frames lie in `mel`
         [n_mels][2 frame_cap], `frames` is None; more frames than room raises the AS_STATUS_CAPACITY bit (as_device_status).
-        voice / voice_idx: voice mode (see `forward`); mel_p / f0_p / ema_p / ref_lens are then not read (None)."""
+        voice / voice_idx: voice mode (see `forward`); mel_p / f0_p / ema_p / ref_lens are then not read (None).
+        prosody: [B, 25] per-utterance controls (see `forward`; a device tensor is read as it is, anything else is copied to the GPU).
+        With frames_hint given, the frames must be the sums of the SCALED durations."""
         if frame_cap is not None:
-            return self._forward_packed_cap(tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, int(frame_cap), aux, out, voice, voice_idx)
+            return self._forward_packed_cap(tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, int(frame_cap), aux, out, voice, voice_idx, prosody)
         rt, L = self.rt, _lib.lib()
         dev = rt.device
         tok_lens = [int(v) for v in tok_lens]
@@ -461,6 +490,8 @@ class ArtsSpeech(_Module):
                 io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
                 io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
             io.forced_dur = _p(forced)
+            pfields, keep_pros = _prosody_args(rt, prosody, B, "any")
+            _set_prosody(io, pfields)
             res = out if out is not None else {}
 
             def new(key, shape, dtype=torch.float32):
@@ -504,7 +535,7 @@ class ArtsSpeech(_Module):
         return res
 
 
-def _forward_packed_cap(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, frame_cap, aux, out, voice=None, voice_idx=None):
+def _forward_packed_cap(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, frame_cap, aux, out, voice=None, voice_idx=None, prosody=None):
     rt, L = self.rt, _lib.lib()
     dev = rt.device
     tok_lens = [int(v) for v in tok_lens]
@@ -520,6 +551,8 @@ def _forward_packed_cap(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, frame
             io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
             io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
         io.frame_cap = frame_cap
+        pfields, keep_pros = _prosody_args(rt, prosody, B, "any")
+        _set_prosody(io, pfields)
         res = out if out is not None else {}
 
         def new(key, shape, dtype=torch.float32):
@@ -588,7 +621,7 @@ class Lanes:
         return int(_lib.lib().as_lanes_merged_calls(self.h, int(lane)))
 
     def submit(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames=None, out=None, capacity=None, frame_cap=None, voice=None,
-               voice_idx=None):
+               voice_idx=None, prosody=None):
         """-> (lane, dict with the output tensors).  frames (per-utterance half-rate frame counts) known: graph-replayed from the second
         submit of the same tensors on a lane; None: predicted durations, `capacity` = the mel frames the output buffer is made for (eager,
         one read-back per call) -- or frame_cap = the half-rate frames to make room for (as_forward_io.frame_cap: no read-back, replayed
@@ -596,7 +629,10 @@ class Lanes:
         2-D tensors may be column ranges of a wider block (row stride = the block's width).
         voice / voice_idx: voice mode (ArtsSpeech.forward); voice_idx a DEVICE int32 [B] tensor (read when the group runs: rewriting it
         changes what a replayed graph computes) or None = row b of `voice` (then a row range of a wider table); mel_p / f0_p / ema_p /
-        ref_lens are not read (None).  Adjacent: indices that continue each other in one table, or row ranges that do."""
+        ref_lens are not read (None).  Adjacent: indices that continue each other in one table, or row ranges that do.
+        prosody: a DEVICE fp32 [B, 25] tensor of per-utterance controls (ArtsSpeech.forward), read when the group runs (rewriting it changes
+        what a replayed graph computes).  Adjacent: row ranges of one table that continue each other; a submission with prosody never
+        joins one without."""
         def _p(t):                                                  # (rows of a wider block: only the last axis has to be dense)
             if t is None:
                 return None
@@ -624,6 +660,8 @@ class Lanes:
                 io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
                 io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
             io.forced_dur = _p(forced)
+            pfields, keep_pros = _prosody_args(rt, prosody, B, "device")
+            _set_prosody(io, pfields)
             n2 = 2 * sum(int(f) for f in frames) if frames is not None else (2 * int(frame_cap) if frame_cap is not None else int(capacity))
             if frame_cap is not None:
                 if frames is not None or forced is not None:
@@ -650,7 +688,7 @@ class Lanes:
             res["frames"] = None if frame_cap is not None else ([int(v) for v in fr] if frames is None else [int(f) for f in frames])
             # (a lane's last group of submissions stays referenced: its launch may still be reading them)
             prev = self._keep[lane.value] or []
-            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, res, keep_voice)])[-2 * max(self.coalesce, 1):]
+            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, res, keep_voice, keep_pros)])[-2 * max(self.coalesce, 1):]
         return lane.value, res
 
     def set_debug(self, on=True):
@@ -658,13 +696,14 @@ class Lanes:
         check(_lib.lib().as_lanes_set_debug(self.h, int(bool(on))), "as_lanes_set_debug")
 
     def submit_host(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames, out_mel, frame_cap=None, frame_off=None, voice=None,
-                    voice_idx=None):
+                    voice_idx=None, prosody=None):
         """as_lanes_submit_host: HOST tensors in (pinned: `.pin_memory()`), the mel back into the host tensor `out_mel` [n_mels][>= 2 sum
         frames]; the lane owns the device side (its block, the copies, the group's launch).  -> lane.  Keep the tensors alive and unchanged
         until `wait(lane)`; `out_mel` is valid after it.  Predicted durations: frames=None, forced=None, frame_cap = the half-rate frames
         there is room for (out_mel [n_mels][>= 2 frame_cap]) and frame_off = a host int32 tensor [B + 1] that receives the offsets.
         voice: a DEVICE table that stays resident (keep it unchanged until `wait`); voice_idx: HOST integers [B] (copied into the lane's
-        block with the tokens) or None = row b; mel_p / f0_p / ema_p / ref_lens are then not read."""
+        block with the tokens) or None = row b; mel_p / f0_p / ema_p / ref_lens are then not read.
+        prosody: a HOST fp32 [B, 25] tensor of per-utterance controls, copied into the lane's block with the tokens."""
         def _h(t):
             if t is None:
                 return None
@@ -687,12 +726,14 @@ class Lanes:
                 io.mel, io.ld_mel = _h(mel_p), mel_p.stride(0)
                 io.f0_raw, io.ema_raw, io.ld_ema = _h(f0_p), _h(ema_p), ema_p.stride(0)
             io.forced_dur = _h(forced)
+            pfields, keep_pros = _prosody_args(self.rt, prosody, len(tok_lens), "host")
+            _set_prosody(io, pfields)
             io.mel_out, io.ld_out = _h(out_mel), out_mel.stride(0)
             ba = self.rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=frames)
             lane = ctypes.c_int32(-1)
             check(_lib.lib().as_lanes_submit_host(self.h, ctypes.byref(ba), ctypes.byref(io), ctypes.byref(lane)), "as_lanes_submit_host")
             prev = self._keep[lane.value] or []
-            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, out_mel, frame_off, keep_voice)])[-2 * max(self.coalesce, 1):]
+            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, out_mel, frame_off, keep_voice, keep_pros)])[-2 * max(self.coalesce, 1):]
         return lane.value
 
     def wait(self, lane=-1):

@@ -9,8 +9,13 @@ reference mel gets the mel -- and, with a vocoder attached, the waveform -- the 
 One voice, many sentences: ``voice_from_mel`` / ``voice_from_wave`` compute what the model takes from a reference utterance once (a
 ``Voice``: Style and dur_style, models.ArtsSpeech.compute_voice); ``synthesis_mel(phonemes, voice=v)`` then skips the reference
 features, the style towers and dur_block.  ``Voice.save`` / ``Voice.load`` keep it as a small .npz, bound to the weights it came from.
+
+How a sentence is spoken: ``Prosody(speed=, pitch_semitones= / pitch_factor=, energy_db=, ema_gain=, ema_offset=)`` in human units;
+``synthesis_mel(..., prosody=p)`` (one for every utterance, or one per utterance) turns it into the per-utterance row the library reads
+(as_forward_io.prosody) with the model's own normalisation statistics.
 """
 import json
+import math
 
 import numpy as np
 import torch
@@ -63,6 +68,76 @@ class Voice:
         if str(fingerprint) != self.fingerprint:
             raise ValueError("the voice was computed with other weights or another configuration than this model's "
                              f"(fingerprint {self.fingerprint} vs {fingerprint})")
+
+
+def _stats24(stats):
+    """the 24 normalisation floats (as_model_cfg.stats: energy mean / std, pitch mean / std, EMA_mean[10], EMA_std[10]) of a model
+    (an ArtSpeech, an ArtsSpeech or a models.Runtime), or the 24 floats themselves"""
+    if isinstance(stats, ArtSpeech):
+        stats = stats.model.ArtsSpeech
+    stats = getattr(stats, "rt", stats)
+    cfg = getattr(stats, "cfg", None)
+    vals = [float(v) for v in (cfg.stats if cfg is not None else stats)]
+    if len(vals) != 24:
+        raise ValueError(f"expected the 24 normalisation statistics of as_model_cfg.stats, got {len(vals)}")
+    return vals
+
+
+class Prosody:
+    """How one utterance is spoken, in human units -> one row of as_forward_io.prosody (AS_PROSODY_DIM = 25 floats: dur_scale, then a
+    gain and an offset for each track the decoder reads: F0, energy, EMA0..9).  The tracks are normalised linearly by the model's
+    statistics (models.py:447-449), so every control is an exact affine map of the normalised values:
+
+    - speed: speaking rate; the predicted durations are multiplied by 1 / speed before they are rounded.  In (0, 16].
+    - pitch_semitones or pitch_factor (r = 2 ** (semitones / 12)): every F0 value f Hz becomes r f; unvoiced frames (0 Hz) stay at 0 Hz.
+    - energy_db: the frame energy (log of the mel norm, models.py:655) is raised by that many dB.
+    - ema_gain [10]: each articulator's movement about the corpus mean is scaled; ema_offset [10]: raw units added to each articulator.
+    """
+
+    def __init__(self, speed=1.0, pitch_semitones=None, pitch_factor=None, energy_db=0.0, ema_gain=None, ema_offset=None):
+        if pitch_semitones is not None and pitch_factor is not None:
+            raise ValueError("give pitch_semitones or pitch_factor, not both")
+        self.speed = float(speed)
+        self.pitch_factor = 2.0 ** (float(pitch_semitones) / 12.0) if pitch_semitones is not None else \
+            (1.0 if pitch_factor is None else float(pitch_factor))
+        self.energy_db = float(energy_db)
+        self.ema_gain = [1.0] * 10 if ema_gain is None else [float(v) for v in np.asarray(ema_gain, dtype=np.float64).reshape(-1)]
+        self.ema_offset = [0.0] * 10 if ema_offset is None else [float(v) for v in np.asarray(ema_offset, dtype=np.float64).reshape(-1)]
+        if len(self.ema_gain) != 10 or len(self.ema_offset) != 10:
+            raise ValueError("ema_gain and ema_offset take one value per articulator (10)")
+        vals = [self.speed, self.pitch_factor, self.energy_db] + self.ema_gain + self.ema_offset
+        if not all(math.isfinite(v) for v in vals):
+            raise ValueError("prosody values must be finite")
+        if not 0.0 < self.speed <= 16.0:
+            raise ValueError(f"speed must lie in (0, 16], not {self.speed}")
+        if self.pitch_factor <= 0.0:
+            raise ValueError(f"pitch_factor must be positive, not {self.pitch_factor}")
+
+    @classmethod
+    def identity(cls):
+        """no control: its row is {1, 1 x 12, 0 x 12}, and a forward with it gives exactly the results of a forward without prosody"""
+        return cls()
+
+    def row(self, stats):
+        """-> float32 [25] for a model (ArtSpeech / ArtsSpeech / models.Runtime) or its 24 normalisation statistics"""
+        st = _stats24(stats)
+        e_std, p_mean, p_std, ema_std = st[1], st[2], st[3], st[14:24]
+        r = self.pitch_factor
+        gain = [r, 1.0] + self.ema_gain
+        off = [(r - 1.0) * p_mean / p_std, math.log(10.0 ** (self.energy_db / 20.0)) / e_std] + \
+              [self.ema_offset[c] / ema_std[c] for c in range(10)]
+        v = np.array([1.0 / self.speed] + gain + off, dtype=np.float64)
+        return torch.from_numpy(v.astype(np.float32))
+
+    @staticmethod
+    def rows(prosody, B, stats):
+        """one Prosody (every utterance) or a list of B -> float32 [B, 25]"""
+        ps = [prosody] * B if isinstance(prosody, Prosody) else list(prosody)
+        if len(ps) != B:
+            raise ValueError(f"{len(ps)} prosody settings for {B} utterances")
+        if not all(isinstance(p, Prosody) for p in ps):
+            raise TypeError("prosody: expected a pipeline.Prosody or a list of them")
+        return torch.stack([p.row(stats) for p in ps])
 
 
 class ArtSpeech:
@@ -159,7 +234,7 @@ class ArtSpeech:
         return table, torch.tensor(idx, dtype=torch.int32)
 
     @torch.no_grad()
-    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None):
+    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed, 24 kHz) reference wave on: log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator.  Returns the samples (mel frames if no vocoder is attached).
         Loading / trimming / resampling the file (librosa, test.py:99-106) and espeak stay with the caller."""
@@ -174,7 +249,7 @@ class ArtSpeech:
             mel, lens = self.frontend(list(ref_wave))
             mels = [mel[b, :, :n] for b, n in enumerate(lens)]
         fn = self.synthesis_wav if self.generator is not None else self.synthesis_mel
-        out = fn(phonemes, mels, features=features, forced_durations=forced_durations)
+        out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody)
         return out[0] if single and out.dim() > 1 and self.generator is not None else out
 
     def attach_vocoder(self, h=None, checkpoint=None):
@@ -187,27 +262,28 @@ class ArtSpeech:
         return self.generator
 
     @torch.no_grad()
-    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None):
+    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised."""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         single = isinstance(phonemes, str)
-        mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice)
+        mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody)
         lens = self._last_frames
         wav = self.generator(mel, lengths=lens)[:, 0]
         return wav[0] if single else wav
 
     @torch.no_grad()
-    def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None):
+    def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None):
         """phonemes: the string the phonemizer returns (test.py:94-96) or a list of such strings; ref_mel: normalised
         log-mel [80,T] (test.py:43-47) or a list; features: (f0_raw, ema_raw) per utterance when no extractor modules
         are attached; (None, ema_raw) with a pitch extractor attached (attach_pitch_extractor).  Returns mel [B,80,2*max M] (what test.py:115 hands to the vocoder).
         world / rank: BASELINE config C4 -- the batch is one GLOBAL batch, this process (one per GPU, torch.distributed initialised by
         the caller) synthesises its length-sorted round-robin shard (artspeech_amd.shard: no data-path collective) and rank 0 gets the
         whole batch back in the caller's order (other ranks: None).
-        voice: a Voice (every utterance) or a list of them, in place of ref_mel / features: the reference is not processed again."""
+        voice: a Voice (every utterance) or a list of them, in place of ref_mel / features: the reference is not processed again.
+        prosody: a Prosody (every utterance) or a list of them: speaking rate, pitch, energy and articulators (not with forced_durations)."""
         if (voice is None) == (ref_mel is None):
             raise ValueError("synthesis needs exactly one of ref_mel and voice")
         if world > 1 and not isinstance(phonemes, str):
@@ -220,7 +296,8 @@ class ArtSpeech:
                 sub = self.synthesis_mel([phonemes[i] for i in idx], None if ref_mel is None else [ref_mel[i] for i in idx],
                                          features=None if features is None else [features[i] for i in idx],
                                          forced_durations=None if forced_durations is None else [forced_durations[i] for i in idx],
-                                         voice=voice if voice is None or isinstance(voice, Voice) else [voice[i] for i in idx])
+                                         voice=voice if voice is None or isinstance(voice, Voice) else [voice[i] for i in idx],
+                                         prosody=prosody if prosody is None or isinstance(prosody, Prosody) else [prosody[i] for i in idx])
                 return [sub[k, :, : self._last_frames[k]].cpu() for k in range(len(idx))]
 
             parts = shard.sharded_forward(step, lens, world, rank)
@@ -237,6 +314,7 @@ class ArtSpeech:
                 features = [features]
         ids = [torch.LongTensor(self.textcleaner(p)) for p in phonemes]               # test.py:96-97
         B = len(ids)
+        rows = None if prosody is None else Prosody.rows(prosody, B, self.model.ArtsSpeech)
         if voice is not None:
             table, vidx = self._voice_table(voice, B)
             nmax = max(len(i) for i in ids)
@@ -244,7 +322,7 @@ class ArtSpeech:
             for b in range(B):
                 text[b, : len(ids[b])] = ids[b]
             mel, aux = self.model.ArtsSpeech([text, torch.LongTensor([len(i) for i in ids]), None, None], None, None, step="test",
-                                             forced_durations=forced_durations, return_aux=True, voice=table, voice_idx=vidx)
+                                             forced_durations=forced_durations, return_aux=True, voice=table, voice_idx=vidx, prosody=rows)
             self._last_frames = list(aux["frames2"])
             return mel
         nmax, tmax = max(len(i) for i in ids), max(m.shape[-1] for m in ref_mel)
@@ -265,7 +343,8 @@ class ArtSpeech:
                 ema[b, :, : e.shape[-1]] = torch.as_tensor(e)
             feats = (f0, ema)
         mel, aux = self.model.ArtsSpeech([text, input_lengths, mels, mel_input_length, None, None, None], None, None,
-                                         step="test", features=feats, forced_durations=forced_durations, return_aux=True)   # test.py:113
+                                         step="test", features=feats, forced_durations=forced_durations, return_aux=True,
+                                         prosody=rows)                                                                    # test.py:113
         self._last_frames = list(aux["frames2"])
         return mel
 

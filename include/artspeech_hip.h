@@ -28,7 +28,7 @@ typedef void* as_stream_t; /* hipStream_t */
 /* library/ABI version; bumped on any change of a signature or of a struct's layout (never held back for anything outside this header:
  * bench.py's source id of the kernel sources leaves version.hip out).  as_abi_version() returns the AS_ABI_VERSION the library was built
  * from: a caller compiled against another header must not go on (artspeech_amd/_lib.py refuses to). */
-#define AS_ABI_VERSION 9
+#define AS_ABI_VERSION 10
 int as_abi_version(void);
 
 /* Device-side status.  The reference's operators cannot return silently stale results: nn.Embedding raises on an id >= n_token
@@ -730,7 +730,22 @@ typedef struct as_forward_io {
      * bounds).  Workspace A: AS_MOD_FORWARD_A_VOICE.  Works with known frames, the read-back, frame_cap and as_forward_test_begin / _finish. */
     const float* voices; int32_t ld_voice; int32_t n_voices;
     const int32_t* voice_idx;
+    /* Prosody control (prosody != NULL): how each utterance is spoken.  DEVICE fp32 [B][ld_prosody >= AS_PROSODY_DIM], read when the call
+     * runs (a replayed graph sees new contents).  Row b: [AS_PROSODY_DUR] dur_scale, then for the twelve tracks the articulatory predictors
+     * hand the decoder (F0, N, EMA0..9, normalised by the model's stats, as_model_cfg.stats) a gain [AS_PROSODY_GAIN + c] and an offset
+     * [AS_PROSODY_OFFSET + c].  Utterance b's integer durations are clamp(rint(duration * dur_scale), 1, 16384) (one fp32 multiply; `duration`
+     * stays the unscaled predictor output; dur_i, frame_off and everything behind them follow the scaled counts -- with known frames,
+     * batch->frames must be their sums), and every track value x of its frames becomes fmaf(gain, x, offset) before the decoder or the
+     * F0 / N / EMA outputs read it.  The identity row {1, 1 x 12, 0 x 12} gives the results of prosody == NULL bit for bit (a -0 track
+     * value may come back as +0).  AS_EINVAL for ld_prosody < AS_PROSODY_DIM and together with forced_dur.  Works with known frames, the
+     * read-back, frame_cap, as_forward_test_begin / _finish, voice mode and merged calls; it adds no launch. */
+    const float* prosody; int32_t ld_prosody;
 } as_forward_io;
+#define AS_PROSODY_DIM 25
+#define AS_PROSODY_TRACKS 12
+#define AS_PROSODY_DUR 0
+#define AS_PROSODY_GAIN 1
+#define AS_PROSODY_OFFSET 13
 typedef struct as_segments {
     int32_t n;                      /* 1 .. AS_MAX_SEGMENTS */
     int32_t first[17];
@@ -789,7 +804,10 @@ int as_lanes_wait(as_lanes* q, int lane);
  * with indices, the same voices / ld_voice / n_voices and voice_idx = the previous voice_idx + its B; or both without, the same ld_voice and
  * voices = the previous voices + its B * ld_voice.  A voice submission never joins a group of reference submissions, nor the reverse.  The
  * graph key holds the voice fields; the indices are device data read at replay.  Debug checksums cover voice_idx instead of the reference
- * rows. */
+ * rows.
+ * Prosody control (as_forward_io.prosody): submissions join a group only if all of them carry rows with the same ld_prosody, each
+ * submission's rows beginning where the previous one's end (prosody = the previous prosody + its B * ld_prosody), or none of them does.
+ * The graph key holds prosody / ld_prosody; the rows are device data read at replay.  Debug checksums cover them. */
 int as_lanes_set_coalesce(as_lanes* q, int k);
 int as_lanes_flush(as_lanes* q);
 /* Debug mode (also switched on by AS_DEBUG=1 in the environment at as_lanes_create).  The buffer rule above is the caller's to keep, and a
@@ -826,6 +844,9 @@ typedef struct as_host_io {
      * f0_raw, ema_raw and batch->ref_lens are then not read. */
     const float* voices; int32_t ld_voice, n_voices;
     const int32_t* voice_idx;
+    /* prosody control (as_forward_io.prosody): HOST fp32 [B][ld_prosody >= AS_PROSODY_DIM], or NULL; its rows are copied into the lane's
+     * block beside the tokens */
+    const float* prosody; int32_t ld_prosody;
 } as_host_io;
 int as_lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_io* io, int32_t* lane_out);
 int64_t as_lanes_merged_calls(const as_lanes* q, int lane);   /* as_forward_test calls of this lane that held more than one submission */
