@@ -230,16 +230,21 @@ def adain_split(X, gb, lay, lrelu=True):
     return xs
 
 
-def adain_image(X, lay, gb, gb_sc, N_out, ldgb=1, gb_off=None, src_off=None, pool_w=None, pool_b=None, x_up=None):
+def adain_image(X, lay, gb, gb_sc, N_out, ldgb=1, gb_off=None, src_off=None, pool_w=None, pool_b=None, x_up=None, col_w=None, col_off=None,
+                out=None):
     """as_adain_image_f32: AdaIN1d + LeakyReLU(0.2) (+ the fused x2 up-sampler) of X [C][*] as an operand image over N_out columns;
-    gamma(u, c) = gb[gb_off[u] + c * gb_sc] (gb_off None: u * ldgb), utterance u reads X at src_off[u] (None: its own columns)."""
+    gamma(u, c) = gb[gb_off[u] + c * gb_sc] (gb_off None: u * ldgb), utterance u reads X at src_off[u] (None: its own columns).
+    col_off (int32, device): the utterances' first output columns instead of lay's; col_w: their widths (None: the differences of
+    col_off, which then has one closing entry); out: the image to write (None: a new one)."""
     C = X.shape[0]
-    xs = new_image(C, N_out, X.device)
+    xs = new_image(C, N_out, X.device) if out is None else out
     a = _lib.AdainArgs()
     a.x, a.ldx, a.C = _p(X), _ld(X), C
     a.gb, a.gb_off, a.ldgb, a.gb_sc = _p(gb), _p(gb_off), ldgb, gb_sc
-    a.col_off, a.src_off, a.U, a.N, a.lrelu, a.yh = _p(lay.col_off), _p(src_off), lay.B, N_out, 1, _p(xs)
+    U = lay.B if col_off is None else (col_w.numel() if col_w is not None else col_off.numel() - 1)
+    a.col_off, a.src_off, a.U, a.N, a.lrelu, a.yh = _p(lay.col_off if col_off is None else col_off), _p(src_off), U, N_out, 1, _p(xs)
     a.pool_w, a.pool_b, a.x_up, a.ld_up = _p(pool_w), _p(pool_b), _p(x_up), (_ld(x_up) if x_up is not None else 0)
+    a.col_w = _p(col_w)
     check(_lib.lib().as_adain_image_f32(ctypes.byref(a), stream()), "as_adain_image_f32")
     return xs
 
@@ -504,6 +509,27 @@ def mean3_image(A, B, C3, n, slope):
     return xh
 
 
+def down_args(kind, X, lin, lout, Y=None, yh=None, w=None, bias=None, kh=0, pool_h=0, Kp=0, res=None, lrelu=False):
+    """AsDownArgs of one tower down-sampling step (include/artspeech_hip.h): kind 0 the depthwise conv (kh 1 / 3), 1 the average pool
+    (pool_h 1 / 2, res: the residual merge; lrelu: on the image only), 2 stem + pool (X [N_in], w = GemmWeight.w32, Kp its padded rows).
+    Y fp32 and / or yh, the operand image over lout.  The tensors must outlive the launch."""
+    a = _lib.DownArgs()
+    a.kind, a.x, a.ldx = kind, _p(X), (_ld(X) if X.dim() > 1 else 0)
+    a.in_off, a.in_w, a.Hin = _p(lin.col_off), _p(lin.widths), lin.H
+    a.out_off, a.out_w, a.Hout = _p(lout.col_off), _p(lout.widths), lout.H
+    a.y, a.ldy, a.yh, a.n_out = _p(Y), (_ld(Y) if Y is not None else 0), _p(yh), lout.N
+    a.w, a.bias, a.kh, a.pool_h, a.Kp = _p(w), _p(bias), kh, pool_h, Kp
+    a.res, a.ldr, a.lrelu = _p(res), (_ld(res) if res is not None else 0), int(lrelu)
+    a.B, a.C, a.max_out = lin.B, (X.shape[0] if kind != 2 else bias.shape[0]), lout.max_cols
+    return a
+
+
+def down_multi(args):
+    """as_down_multi_f32: 1 .. 6 down_args(...) steps as one launch"""
+    arr = (_lib.DownArgs * max(len(args), 1))(*args)
+    check(_lib.lib().as_down_multi_f32(arr, len(args), stream()), "as_down_multi_f32")
+
+
 def dwconv_down(X, lin, Y, lout, w, bias, kh, lrelu):
     check(_lib.lib().as_dwconv_down_f32(_p(X), _ld(X), _p(lin.col_off), _p(lin.widths), lin.H, _p(Y), _ld(Y),
                                         _p(lout.col_off), _p(lout.widths), lout.H, _p(w), _p(bias), kh, lin.B,
@@ -572,13 +598,13 @@ def mean_pool(X, lay, lrelu, y=None):
     return y
 
 
-def channel_layernorm_split(X, lay, gamma, beta, relu=False, eps=1e-4, group2=None):
+def channel_layernorm_split(X, lay, gamma, beta, relu=False, eps=1e-4, group2=None, out=None):
     """channel LayerNorm (+ReLU) of X [C][N] stored only as the pre-split operand image of the conv that follows
-    (conv_gemm(Wt, None, ..., xs=, K=C))."""
+    (conv_gemm(Wt, None, ..., xs=, K=C)); out: the image to write (None: a new one)."""
     L = _lib.lib()
     C = X.shape[0]
     g2, b2, n_split = group2 if group2 is not None else (None, None, 0)
-    xs = new_image(C, lay.N, X.device)
+    xs = new_image(C, lay.N, X.device) if out is None else out
     check(L.as_channel_layernorm_split_f32(_p(X), _ld(X), C, lay.N, _p(gamma), _p(beta), _p(g2), _p(b2), n_split, eps, int(relu), _p(xs),
                                            stream()), "as_channel_layernorm_split_f32")
     return xs

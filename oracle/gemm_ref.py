@@ -250,20 +250,18 @@ def excess(got, want, bound):
 def adain_ref(y, widths, gb, yb=None, slope=0.2):
     """AdaIN1d (instance norm over each utterance's columns, eps 1e-5; gamma = gb[c][u], beta = gb[C + c][u]) + LeakyReLU, float64.
     yb: a bound on |y| errors -> (out, bound of out)."""
+    from oracle.norm_ref import adain_value                            # (the formula lives there; norm_ref imports this module's constants)
     C = y.shape[0]
     out, bnd = torch.empty_like(y), torch.zeros_like(y)
     o = 0
     for u, L in enumerate(widths):
         seg = y[:, o:o + L]
-        mu = seg.mean(1, keepdim=True)
-        sd = torch.sqrt(((seg - mu) ** 2).mean(1, keepdim=True) + 1e-5)
         g, be = 1 + gb[:C, u:u + 1].double(), gb[C:, u:u + 1].double()
-        z = g * (seg - mu) / sd + be
-        out[:, o:o + L] = torch.where(z > 0, z, slope * z)
+        out[:, o:o + L], xh, sd = adain_value(seg, g, be, slope)
         if yb is not None:
             eb = yb[:, o:o + L]
             # a conv error e moves the mean by <= max e and sigma by <= max e: |d z| <= |g| (e + 2 max e + |x_hat| max e) / sigma
-            xh = ((seg - mu) / sd).abs()
+            xh = xh.abs()
             mx = eb.max(1, keepdim=True).values
             bnd[:, o:o + L] = g.abs() * (eb + (2 + xh) * mx) / sd + 16 * U * (g.abs() * (xh + 1) + be.abs()) * math.sqrt(L)
         o += L
@@ -272,12 +270,9 @@ def adain_ref(y, widths, gb, yb=None, slope=0.2):
 
 def layernorm_ref(y, gamma, beta, relu, yb=None, eps=1e-4):
     """channel LayerNorm over each column (eps 1e-4), gamma / beta [C][N] (per column: the groups), optional ReLU -> (out, bound)"""
+    from oracle.norm_ref import layernorm_value
     C = y.shape[0]
-    mu = y.mean(0, keepdim=True)
-    sd = torch.sqrt(((y - mu) ** 2).mean(0, keepdim=True) + eps)
-    xh = (y - mu) / sd
-    z = gamma * xh + beta
-    out = z.clamp(min=0) if relu else z
+    out, xh, sd = layernorm_value(y, gamma, beta, relu, eps)
     bnd = None
     if yb is not None:
         mx = yb.max(0, keepdim=True).values
