@@ -222,6 +222,33 @@ _SIGNATURES.update({
 })
 
 
+
+class VocoderCfg(ctypes.Structure):
+    """as_vocoder_cfg (include/artspeech_hip.h): Vocoder/config.json, ResBlock1"""
+    _fields_ = [("num_mels", ctypes.c_int32), ("upsample_initial_channel", ctypes.c_int32), ("n_stages", ctypes.c_int32),
+                ("upsample_rates", ctypes.c_int32 * 8), ("upsample_kernel_sizes", ctypes.c_int32 * 8), ("n_stacks", ctypes.c_int32),
+                ("resblock_kernel_sizes", ctypes.c_int32 * 4), ("resblock_dilations", (ctypes.c_int32 * 4) * 4), ("n_dilations", ctypes.c_int32)]
+
+
+class VocoderIO(ctypes.Structure):
+    """as_vocoder_io: DEVICE pointers"""
+    _fields_ = [("mel", c_p), ("ld_mel", ctypes.c_int32), ("wav", c_p), ("pcm", c_p)]
+
+
+_pI32 = ctypes.POINTER(ctypes.c_int32)
+_SIGNATURES.update({
+    "as_conv_post_pcm_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, ctypes.c_float, c_i, c_p, c_p, c_p, c_p]),
+    "as_vocoder_create": (c_i, [c_p, c_sz, ctypes.POINTER(VocoderCfg), ctypes.POINTER(c_p)]),
+    "as_vocoder_destroy": (c_i, [c_p]),
+    "as_vocoder_get_cfg": (c_i, [c_p, ctypes.POINTER(VocoderCfg)]),
+    "as_vocoder_hop": (c_i, [c_p]),
+    "as_vocoder_plan_create": (c_i, [c_p, ctypes.POINTER(c_p)]),
+    "as_vocoder_workspace_bytes": (c_sz, [c_p, c_p, c_i, _pI32]),
+    "as_vocoder_forward": (c_i, [c_p, c_p, c_i, _pI32, ctypes.POINTER(VocoderIO), c_p, c_sz, c_p]),
+    "as_vocoder_fold_upsample_host": (c_i, [c_p, c_i, c_i, c_i, c_p]),
+})
+
+
 AS_MAX_LSTM_JOBS = 4
 
 

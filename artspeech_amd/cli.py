@@ -38,12 +38,15 @@ def read_wav(path):
 
 
 def write_wav(path, x, sr=24000):
-    pcm = np.clip(np.asarray(x, dtype=np.float32), -1.0, 1.0)
+    """x: fp32 samples in [-1, 1], or int16 samples (--pcm16: converted on the device), which are written as they are"""
+    x = np.asarray(x)
+    if x.dtype != np.int16:
+        x = (np.clip(x.astype(np.float32), -1.0, 1.0) * 32767.0).astype(np.int16)
     with wave.open(path, "wb") as f:
         f.setnchannels(1)
         f.setsampwidth(2)
         f.setframerate(sr)
-        f.writeframes((pcm * 32767.0).astype(np.int16).tobytes())
+        f.writeframes(x.astype("<i2").tobytes())
 
 
 def build_parser():
@@ -62,6 +65,8 @@ def build_parser():
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
     ap.add_argument("--vocoder-config", help="Vocoder/config.json")
     ap.add_argument("--vocoder", help="Vocoder/g_00935000")
+    ap.add_argument("--vocoder-runtime", action="store_true", help="run the generator inside the library: one C call per batch (as_vocoder_forward)")
+    ap.add_argument("--pcm16", action="store_true", help="16-bit samples straight from the generator's last kernel (no host-side conversion)")
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights instead of checkpoints (smoke / demo)")
     ap.add_argument("--tiny", action="store_true", help="with --synthetic: the small test configuration")
     return ap
@@ -100,7 +105,7 @@ def main(argv=None):
         tts.attach_pitch_extractor({"net": J.synth_jdc_state_dict(1, seed=3407)})
         tts.attach_ema_extractor({"model": E.synth_ema_state_dict(seed=3407)})
         h = dict(V.DEFAULT_H, upsample_initial_channel=32 if a.tiny else 512)
-        tts.attach_vocoder(h, V.synth_generator_state_dict(h, seed=3407))
+        tts.attach_vocoder(h, V.synth_generator_state_dict(h, seed=3407), runtime=a.vocoder_runtime)
     else:
         if not (a.config and a.jdc and a.ema and a.vocoder):
             ap.error("--config, --jdc, --ema and --vocoder are required without --synthetic")
@@ -108,16 +113,16 @@ def main(argv=None):
         tts.attach_pitch_extractor(a.jdc)
         tts.attach_ema_extractor(a.ema)
         h = json.load(open(a.vocoder_config)) if a.vocoder_config else None
-        tts.attach_vocoder(h, a.vocoder)
+        tts.attach_vocoder(h, a.vocoder, runtime=a.vocoder_runtime)
     if a.voice:
         from .pipeline import Voice
-        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody)
+        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16)
     else:
         wave_in = read_wav(a.ref_wav)
         if a.save_voice:
             tts.voice_from_wave(wave_in).save(a.save_voice)
             print(f"{a.save_voice}: voice of {a.ref_wav}")
-        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody)
+        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16)
     write_wav(a.out, audio.cpu().numpy())
     print(f"{a.out}: {audio.numel() / 24000.0:.2f} s of audio from {tts._last_frames[0]} mel frames")
     return 0

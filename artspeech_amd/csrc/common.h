@@ -96,6 +96,9 @@ int as_durations_prosody_launch(const float* dur_f32, const int32_t* forced_dur,
 int as_project_cols_prosody_launch(const float* x, int ldx, int K, int N, const float* w, const float* bias, int M, float* y, int ldy,
                                    const float* pros, int ld_pros, const int32_t* col_off, int B, int track0, hipStream_t s);
 
+// fp32 samples w [N] -> 16-bit PCM by the rule of as_conv_post_pcm_f32 (vocoder.hip; a NaN stores 0 and raises AS_STATUS_F16_RANGE)
+int as_pcm16_launch(const float* w, int N, int16_t* pcm, hipStream_t stream);
+
 // kernel classes for the optional event profiler (prof.hip)
 enum { AS_CLS_GEMM = 0, AS_CLS_ADAIN = 1, AS_CLS_LN = 2, AS_CLS_ATTN = 3, AS_CLS_LSTM = 4, AS_CLS_MAS = 5, AS_CLS_OTHER = 6, AS_N_CLS = 7 };
 struct AsProfScope {

@@ -1,6 +1,7 @@
 // Glue kernels of the HiFi-GAN generator (Vocoder/vocoder.py:75-125) -- SURVEY.md section 8(f) row N2; its
 // convolutions are the conv GEMM of the acoustic path (conv_gemm*.hip).
 #include "conv_gemm.h"
+#include <algorithm>
 #define AS_FILE_CLS AS_CLS_OTHER
 
 // ConvTranspose1d(k = 2u, stride u) runs as ONE 3-tap conv whose output rows are (phase r, channel m) (vocoder.py of
@@ -56,6 +57,14 @@ extern "C" int as_mean3_f32(const float* a, const float* b, const float* c, int 
     return AS_OK;
 }
 
+// the waveform as 16-bit PCM (include/artspeech_hip.h, as_conv_post_pcm_f32): one fp32 multiply, round half to even, saturate; a NaN gives 0
+// (*nan says so: the caller raises AS_STATUS_F16_RANGE)
+static __device__ __forceinline__ int as_pcm16(float w, bool* nan)
+{
+    *nan = w != w;
+    return *nan ? 0 : (int)fmaxf(-32768.f, fminf(32767.f, rintf(__fmul_rn(32767.f, w))));
+}
+
 // conv_post (vocoder.py:97, 111-113): wav = tanh(conv1d(LeakyReLU(x, 0.01), w [1][C][k]) + b), zero padding per utterance.  ONE output row:
 // as a conv GEMM launch this was a 32-row matrix-core tile computing one useful row behind a split pass over the whole input (336 us at
 // 32 channels x 1.92 M samples); as plain fp32 FMAs it is a read of x (245 MB).  A wave owns 256 consecutive columns, a lane the columns
@@ -63,7 +72,8 @@ extern "C" int as_mean3_f32(const float* a, const float* b, const float* c, int 
 template <int K>
 __global__ void __launch_bounds__(256) conv_post_kernel(const float* __restrict__ x, int ldx, int C, int N, const float* __restrict__ w,
                                                         const float* __restrict__ bias, float slope, int tanh_out,
-                                                        const unsigned long long* __restrict__ meta, float* __restrict__ y)
+                                                        const unsigned long long* __restrict__ meta, float* __restrict__ y,
+                                                        short* __restrict__ pcm, int pcm_pairs, unsigned* __restrict__ status)
 {
     constexpr int HALF = K / 2;
     const int j0 = (blockIdx.x * 256 + (threadIdx.x & ~63)) * 4 + (threadIdx.x & 63);
@@ -103,26 +113,70 @@ __global__ void __launch_bounds__(256) conv_post_kernel(const float* __restrict_
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const int j = j0 + 64 * p;
-        if (j < N) {
-            const float v = acc[p] + b;
-            y[j] = tanh_out ? tanhf(v) : v;
+        float v = acc[p] + b;
+        v = tanh_out ? tanhf(v) : v;
+        if (y && j < N) y[j] = v;
+        if (pcm) {                                                      // (uniform; every lane of the wave is here: the shuffle below is whole)
+            bool nan;
+            const int s = as_pcm16(v, &nan);
+            if (nan && j < N) as_status_raise(status, AS_STATUS_F16_RANGE);
+            // the 16-bit samples of the same pass: a lane's neighbour holds the next column, so an even lane stores the pair as one dword
+            // (j is even there and pcm 4-byte aligned: pcm_pairs) -- 128 contiguous bytes per wave either way
+            const int s1 = __shfl_down(s, 1);
+            if (pcm_pairs && j + 1 < N) {
+                if (!(threadIdx.x & 1)) *reinterpret_cast<unsigned*>(pcm + j) = (unsigned)(s & 0xffff) | ((unsigned)s1 << 16);
+            } else if (j < N && !(pcm_pairs && (threadIdx.x & 1))) {    // (an odd lane's sample always went out with its even neighbour's)
+                pcm[j] = (short)s;
+            }
         }
     }
+}
+
+// fp32 samples -> PCM as a pass of its own: behind the conv GEMM form of conv_post (other kernel widths; not the shipped configuration)
+__global__ void pcm16_kernel(const float* __restrict__ w, int N, short* __restrict__ pcm, unsigned* __restrict__ status)
+{
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < N; j += gridDim.x * blockDim.x) {
+        bool nan;
+        pcm[j] = (short)as_pcm16(w[j], &nan);
+        if (nan) as_status_raise(status, AS_STATUS_F16_RANGE);
+    }
+}
+
+int as_pcm16_launch(const float* w, int N, int16_t* pcm, hipStream_t stream)
+{
+    if (!w || !pcm || N < 0) return AS_EINVAL;
+    if (N == 0) return AS_OK;
+    AsProfScope prof__(AS_FILE_CLS, 0, 6.0 * N, stream);
+    hipLaunchKernelGGL(pcm16_kernel, dim3(std::min(as_cdiv(N, 256), 4096)), dim3(256), 0, stream, w, N, reinterpret_cast<short*>(pcm),
+                       as_status_words_device());
+    AS_CHECK_LAUNCH();
+    return AS_OK;
+}
+
+extern "C" int as_conv_post_pcm_f32(const float* x, int ldx, int C, int N, const float* w, const float* bias, int k, float in_slope,
+                                    int tanh_out, const uint64_t* meta, float* y, int16_t* pcm, as_stream_t stream)
+{
+    if (!x || !w || !meta || (!y && !pcm) || C <= 0 || N < 0 || ldx < N || (k != 3 && k != 5 && k != 7)) return AS_EINVAL;
+    if (pcm && (reinterpret_cast<uintptr_t>(pcm) & 1) != 0) return AS_EINVAL;
+    if (N == 0) return AS_OK;
+    AsProfScope prof__(AS_CLS_GEMM, 2.0 * C * k * (double)N, 4.0 * (C + 1.0) * N, (hipStream_t)stream, "conv_post");
+    const dim3 grid(as_cdiv(N, 1024)), block(256);
+    const unsigned long long* md = reinterpret_cast<const unsigned long long*>(meta);
+    short* pc = reinterpret_cast<short*>(pcm);
+    const int pairs = pcm && (reinterpret_cast<uintptr_t>(pcm) & 3) == 0;
+    unsigned* st = pcm ? as_status_words_device() : nullptr;
+    if (k == 3) hipLaunchKernelGGL(conv_post_kernel<3>, grid, block, 0, (hipStream_t)stream, x, ldx, C, N, w, bias, in_slope, tanh_out, md, y, pc, pairs, st);
+    else if (k == 5) hipLaunchKernelGGL(conv_post_kernel<5>, grid, block, 0, (hipStream_t)stream, x, ldx, C, N, w, bias, in_slope, tanh_out, md, y, pc, pairs, st);
+    else hipLaunchKernelGGL(conv_post_kernel<7>, grid, block, 0, (hipStream_t)stream, x, ldx, C, N, w, bias, in_slope, tanh_out, md, y, pc, pairs, st);
+    AS_CHECK_LAUNCH();
+    return AS_OK;
 }
 
 extern "C" int as_conv_post_f32(const float* x, int ldx, int C, int N, const float* w, const float* bias, int k, float in_slope,
                                 int tanh_out, const uint64_t* meta, float* y, as_stream_t stream)
 {
-    if (!x || !w || !meta || !y || C <= 0 || N < 0 || ldx < N || (k != 3 && k != 5 && k != 7)) return AS_EINVAL;
-    if (N == 0) return AS_OK;
-    AsProfScope prof__(AS_CLS_GEMM, 2.0 * C * k * (double)N, 4.0 * (C + 1.0) * N, (hipStream_t)stream, "conv_post");
-    const dim3 grid(as_cdiv(N, 1024)), block(256);
-    const unsigned long long* md = reinterpret_cast<const unsigned long long*>(meta);
-    if (k == 3) hipLaunchKernelGGL(conv_post_kernel<3>, grid, block, 0, (hipStream_t)stream, x, ldx, C, N, w, bias, in_slope, tanh_out, md, y);
-    else if (k == 5) hipLaunchKernelGGL(conv_post_kernel<5>, grid, block, 0, (hipStream_t)stream, x, ldx, C, N, w, bias, in_slope, tanh_out, md, y);
-    else hipLaunchKernelGGL(conv_post_kernel<7>, grid, block, 0, (hipStream_t)stream, x, ldx, C, N, w, bias, in_slope, tanh_out, md, y);
-    AS_CHECK_LAUNCH();
-    return AS_OK;
+    if (!y) return AS_EINVAL;
+    return as_conv_post_pcm_f32(x, ldx, C, N, w, bias, k, in_slope, tanh_out, meta, y, nullptr, stream);
 }
 
 // LeakyReLU((a + b + c) / 3) as the operand image of the conv that follows (the next stage's ConvTranspose1d, vocoder.py:101-110): the

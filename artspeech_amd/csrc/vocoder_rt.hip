@@ -1,0 +1,556 @@
+// Module-level C ABI of the HiFi-GAN generator (include/artspeech_hip.h, "The HiFi-GAN generator behind an opaque handle"): mel in,
+// samples out, one call.  Like model.hip this file holds no kernels: it reads the checkpoint blob, lays the weights out (weight_norm
+// fold, ConvTranspose1d -> 3-tap phase conv, per-row biases, the fp32 conv_post row, the GEMM's weight images) and orders the launches
+// of vocoder.hip / respair.hip / conv_gemm*.hip -- the sequence artspeech_amd/vocoder.py::Generator.forward_packed issues operator by
+// operator, decision for decision.  ONE sequence (generator()) serves two passes: count (as_vocoder_workspace_bytes: the arena only adds
+// up, nothing is launched) and run (kernels are enqueued; nothing is allocated, nothing synchronises once the geometry's tables exist).
+#include "common.h"
+#include "conv_gemm.h"
+#include "runtime.h"
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+using namespace asrt;
+
+namespace {
+
+constexpr float LRELU_SLOPE = 0.1f;     // Vocoder/vocoder.py:8
+constexpr float POST_SLOPE = 0.01f;     // vocoder.py:111: F.leaky_relu's default
+constexpr int ACT_LRELU = 2, ACT_TANH = 3;
+
+struct ConvW {                          // a conv weight prepared for as_conv_gemm_f32 / as_respair_f32, with its bias
+    uint16_t* wh = nullptr;
+    float scale = 1.f;
+    int T = 0, Kp = 0, M = 0, K = 0;
+    float* bias = nullptr;
+};
+struct Step {                           // one residual step of ResBlock1: conv1 (dilated), conv2
+    ConvW c1, c2;
+    int k = 0, dil = 1;
+};
+
+}  // namespace
+
+struct as_vocoder {
+    as_vocoder_cfg cfg;
+    int device = 0, hop = 1;
+    DevPool pool{(size_t)64 << 20};
+    ConvW pre, post;                    // post.wh: only when the fp32 conv_post kernel does not apply
+    float* post32 = nullptr;            // conv_post.weight[0] fp32 [C][k] (k = 3, 5, 7: as_conv_post_pcm_f32)
+    int post_k = 0;
+    std::vector<ConvW> ups;             // the phase convs [u Cout][Cin][3]; bias = the channel's, u times (one per row)
+    std::vector<float*> ups_bias;       // the ConvTranspose1d's own bias [Cout] (as_interleave_phases_f32)
+    std::vector<std::vector<Step>> rb;  // [stage * n_stacks + stack][step]
+};
+
+namespace {
+
+using Raw = std::unordered_map<std::string, HostT>;
+
+bool cfg_ok(const as_vocoder_cfg& c)
+{
+    if (c.num_mels <= 0 || c.upsample_initial_channel <= 0 || c.n_stages < 1 || c.n_stages > 8) return false;
+    if (c.n_stacks != 3 || c.n_dilations < 1 || c.n_dilations > 4) return false;     // (the mean of THREE stacks: as_mean3_*_f32)
+    if (c.upsample_initial_channel % (1 << c.n_stages)) return false;
+    double hop = 1;
+    for (int i = 0; i < c.n_stages; ++i) {
+        const int u = c.upsample_rates[i];
+        if (u < 2 || u > 4096 || c.upsample_kernel_sizes[i] != 2 * u) return false;
+        hop *= u;
+    }
+    if (hop > (double)AS_META_MAX_W) return false;
+    for (int j = 0; j < c.n_stacks; ++j) {
+        const int k = c.resblock_kernel_sizes[j];
+        if (k < 1 || !(k & 1) || k > AS_MAX_TAPS) return false;
+        for (int n = 0; n < c.n_dilations; ++n)
+            if (c.resblock_dilations[j][n] < 1 || c.resblock_dilations[j][n] > 4096) return false;
+    }
+    return true;
+}
+
+// the folded tensor `name` with exactly these dims, or NULL
+const HostT* tensor(const Raw& w, const std::string& name, std::initializer_list<int> dims)
+{
+    const auto it = w.find(name);
+    if (it == w.end()) { if (getenv("AS_DEBUG")) fprintf(stderr, "artspeech_hip: vocoder checkpoint has no tensor '%s'\n", name.c_str()); return nullptr; }
+    if (it->second.dims != std::vector<int>(dims)) { if (getenv("AS_DEBUG")) fprintf(stderr, "artspeech_hip: vocoder tensor '%s' has another shape\n", name.c_str()); return nullptr; }
+    return &it->second;
+}
+
+// every tensor the configuration names, with its shape -- host work only: a bad checkpoint is refused before a device is touched
+bool checkpoint_ok(const Raw& w, const as_vocoder_cfg& c)
+{
+    const int c0 = c.upsample_initial_channel;
+    bool ok = tensor(w, "conv_pre.weight", {c0, c.num_mels, 7}) && tensor(w, "conv_pre.bias", {c0});
+    for (int i = 0; ok && i < c.n_stages; ++i) {
+        const int cin = c0 >> i, cout = c0 >> (i + 1);
+        const std::string p = "ups." + std::to_string(i);
+        ok = tensor(w, p + ".weight", {cin, cout, c.upsample_kernel_sizes[i]}) && tensor(w, p + ".bias", {cout});
+        for (int j = 0; ok && j < c.n_stacks; ++j)
+            for (int n = 0; ok && n < c.n_dilations; ++n)
+                for (const char* cv : {".convs1.", ".convs2."}) {
+                    const std::string q = "resblocks." + std::to_string(i * c.n_stacks + j) + cv + std::to_string(n);
+                    ok = ok && tensor(w, q + ".weight", {cout, cout, c.resblock_kernel_sizes[j]}) && tensor(w, q + ".bias", {cout});
+                }
+    }
+    const auto post = w.find("conv_post.weight");
+    ok = ok && post != w.end() && post->second.dims.size() == 3 && post->second.dim(0) == 1 && post->second.dim(1) == c0 >> c.n_stages &&
+         (post->second.dim(2) & 1) && post->second.dim(2) <= AS_MAX_TAPS && tensor(w, "conv_post.bias", {1});
+    return ok;
+}
+
+float* upload(as_vocoder& v, const float* h, size_t n)
+{
+    float* d = static_cast<float*>(v.pool.alloc(n * sizeof(float)));
+    if (!d || hipMemcpy(d, h, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return d;
+}
+
+// w fp32 [Cout][Cin][T] -> the conv GEMM's weight image on the device (as_prep_weight_f16x2_host), bias [n_bias] beside it
+bool conv_w(as_vocoder& v, ConvW& g, const float* w, int Cout, int Cin, int T, const float* bias, size_t n_bias)
+{
+    g.T = T; g.K = Cin; g.Kp = (Cin + 15) / 16 * 16; g.M = Cout;
+    const size_t bytes = as_prep_weight_f16x2_bytes(1, Cout, Cin, T);
+    std::vector<uint16_t> img(bytes / 2);
+    if (!bytes || as_prep_weight_f16x2_host(w, 1, Cout, Cin, T, img.data(), &g.scale) != AS_OK) return false;
+    g.wh = static_cast<uint16_t*>(v.pool.alloc(bytes));
+    if (!g.wh || hipMemcpy(g.wh, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
+    g.bias = bias ? upload(v, bias, n_bias) : nullptr;
+    return !bias || g.bias;
+}
+bool conv_w(as_vocoder& v, ConvW& g, const Raw& w, const std::string& name)
+{
+    const HostT &wt = w.at(name + ".weight"), &b = w.at(name + ".bias");
+    return conv_w(v, g, wt.v.data(), wt.dim(0), wt.dim(1), wt.dim(2), b.v.data(), b.numel());
+}
+
+int vocoder_create(const void* blob_host, size_t blob_bytes, const as_vocoder_cfg* cfg, as_vocoder** out)
+{
+    Raw blob, w;
+    if (!read_blob(blob_host, blob_bytes, &blob) || !fold(blob, &w)) return AS_EINVAL;
+    blob.clear();
+    if (!checkpoint_ok(w, *cfg)) return AS_EINVAL;
+    struct Guard {                                                       // every error return below gives the device memory back
+        std::unique_ptr<as_vocoder> v;
+        ~Guard() { if (v) v->pool.release(); }
+    } g;
+    g.v.reset(new as_vocoder());
+    as_vocoder& v = *g.v;
+    v.cfg = *cfg;
+    for (int i = 0; i < cfg->n_stages; ++i) v.hop *= cfg->upsample_rates[i];
+    AS_CHECK(hipGetDevice(&v.device));
+    bool ok = conv_w(v, v.pre, w, "conv_pre");
+    const HostT &wp = w.at("conv_post.weight"), &bp = w.at("conv_post.bias");
+    v.post_k = wp.dim(2);
+    if (v.post_k == 3 || v.post_k == 5 || v.post_k == 7) {               // one output row: plain fp32 FMAs (vocoder.hip)
+        v.post32 = upload(v, wp.v.data(), wp.numel());
+        v.post.bias = upload(v, bp.v.data(), 1);
+        ok = ok && v.post32 && v.post.bias;
+    } else {
+        ok = ok && conv_w(v, v.post, w, "conv_post");
+    }
+    v.ups.resize(cfg->n_stages);
+    v.ups_bias.resize(cfg->n_stages);
+    v.rb.resize((size_t)cfg->n_stages * cfg->n_stacks);
+    for (int i = 0; ok && i < cfg->n_stages; ++i) {
+        const std::string p = "ups." + std::to_string(i);
+        const HostT &wt = w.at(p + ".weight"), &b = w.at(p + ".bias");
+        const int u = cfg->upsample_rates[i], cin = wt.dim(0), cout = wt.dim(1);
+        std::vector<float> wc((size_t)u * cout * cin * 3), rows;
+        ok = as_vocoder_fold_upsample_host(wt.v.data(), cin, cout, u, wc.data()) == AS_OK;
+        for (int r = 0; r < u; ++r) rows.insert(rows.end(), b.v.begin(), b.v.end());
+        ok = ok && conv_w(v, v.ups[i], wc.data(), u * cout, cin, 3, rows.data(), rows.size());
+        v.ups_bias[i] = upload(v, b.v.data(), b.numel());
+        ok = ok && v.ups_bias[i];
+        for (int j = 0; ok && j < cfg->n_stacks; ++j) {
+            std::vector<Step>& blk = v.rb[(size_t)i * cfg->n_stacks + j];
+            blk.resize(cfg->n_dilations);
+            for (int n = 0; ok && n < cfg->n_dilations; ++n) {
+                const std::string q = "resblocks." + std::to_string(i * cfg->n_stacks + j);
+                blk[n].k = cfg->resblock_kernel_sizes[j];
+                blk[n].dil = cfg->resblock_dilations[j][n];
+                ok = conv_w(v, blk[n].c1, w, q + ".convs1." + std::to_string(n)) && conv_w(v, blk[n].c2, w, q + ".convs2." + std::to_string(n));
+            }
+        }
+    }
+    if (!ok) return (int)hipErrorOutOfMemory;
+    AS_CHECK(hipDeviceSynchronize());
+    *out = g.v.release();
+    return AS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// one pass over the launch sequence
+// ------------------------------------------------------------------------------------------------------------------
+struct Seq {
+    const as_vocoder& v;
+    as_plan& p;
+    hipStream_t s;
+    char* base;                         // workspace (nullptr when counting)
+    size_t cap, off = 0, peak = 0;
+    bool run;
+    int rc = 0;
+    void fail(int r) { if (!rc) rc = r; }
+    bool go() const { return run && rc == 0; }
+    void* raw_alloc(size_t bytes)
+    {
+        const size_t o = off;
+        off += align256(bytes ? bytes : 1);
+        peak = std::max(peak, off);
+        if (!run) return reinterpret_cast<void*>((size_t)1 << 20);      // counting: a placeholder, never dereferenced
+        if (off > cap) { fail(AS_ENOSPC); return nullptr; }
+        return base + o;
+    }
+    float* f32(int C, int N) { return static_cast<float*>(raw_alloc((size_t)C * std::max(N, 1) * sizeof(float))); }
+    uint16_t* image(int K, int N) { return static_cast<uint16_t*>(raw_alloc(std::max(as_split_f16x2_bytes(K, std::max(N, 1)), (size_t)16))); }
+
+    // geometry: cached in the plan; its device tables (widths, offsets, column descriptors) are made on the first RUN that uses it -- a
+    // blocking upload and one stream synchronisation, never again for that geometry
+    const Lay* lay(const std::vector<int>& widths)
+    {
+        std::pair<std::vector<int>, int> key{widths, 1};
+        auto it = p.lays.find(key);
+        if (it == p.lays.end()) {
+            auto u = std::make_unique<Lay>();
+            Lay& L = *u;
+            L.B = (int)widths.size();
+            L.w = widths;
+            L.off.assign(L.B + 1, 0);
+            for (int b = 0; b < L.B; ++b) {
+                if (widths[b] < 0 || widths[b] > AS_META_MAX_W || (double)L.off[b] + widths[b] > 2147483647.0) { fail(AS_EINVAL); return nullptr; }
+                L.off[b + 1] = L.off[b] + widths[b];
+                L.max_w = std::max(L.max_w, widths[b]);
+            }
+            L.N = L.off[L.B];
+            it = p.lays.emplace(std::move(key), std::move(u)).first;
+        }
+        Lay* L = it->second.get();
+        if (!run) return L;
+        if (!L->d_off) {
+            int32_t* d_w = static_cast<int32_t*>(p.pool.alloc((L->B + 1) * sizeof(int32_t)));
+            int32_t* d_off = static_cast<int32_t*>(p.pool.alloc((L->B + 1) * sizeof(int32_t)));
+            if (!d_w || !d_off || hipMemcpy(d_w, L->w.data(), L->B * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_off, L->off.data(), (L->B + 1) * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+                fail((int)hipErrorOutOfMemory);
+                return nullptr;
+            }
+            L->d_w = d_w;
+            L->d_off = d_off;
+        }
+        if (!L->d_meta) {
+            uint64_t* md = static_cast<uint64_t*>(p.pool.alloc((size_t)std::max(L->N, 1) * sizeof(uint64_t)));
+            if (!md) { fail((int)hipErrorOutOfMemory); return nullptr; }
+            const int r = as_make_meta(L->d_w, L->d_off, L->B, 1, L->N, md, s);
+            if (r != AS_OK || hipStreamSynchronize(s) != hipSuccess) { fail(r ? r : (int)hipErrorUnknown); return nullptr; }
+            L->d_meta = md;
+        }
+        return L;
+    }
+    const Lay* scaled(const Lay* L, int k)
+    {
+        std::vector<int> w(L->w);
+        for (int& x : w) {
+            if ((double)x * k > (double)AS_META_MAX_W) { fail(AS_EINVAL); return nullptr; }
+            x *= k;
+        }
+        return lay(w);
+    }
+};
+
+#define RUN(c, call)                                  \
+    do {                                              \
+        if ((c).go()) {                               \
+            const int r__ = (call);                   \
+            if (r__ != AS_OK) (c).fail(r__);          \
+        }                                             \
+    } while (0)
+
+struct ConvOpt {
+    const float* bias = nullptr;
+    const float* res = nullptr;         // [M][N]
+    int act = 0, in_act = 0;
+    float in_slope = 0.2f;              // (what an unused slope is in the operator-level calls of vocoder.py: the GEMM ignores it)
+    uint16_t* yh = nullptr;
+    bool yh_lrelu = false;
+    int ileave = 0, ldy = 0;            // ldy 0: lay->N
+    int dil = 1;
+};
+
+// Y = epi(conv(W, X)): X fp32 [K][ldx] (the library splits it into the workspace) or the operand image xh; k taps with dilation o.dil
+void conv(Seq& c, const ConvW& w, const float* X, int ldx, const uint16_t* xh, int K, const Lay* lay, float* Y, const ConvOpt& o)
+{
+    if (!lay || c.rc) return;
+    if (K > w.Kp || K <= w.Kp - 16) { c.fail(AS_EINVAL); return; }
+    ConvGemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.Wh = w.wh; a.X = X; a.Xh = xh; a.Y = Y; a.Yh = o.yh;
+    a.bias = o.bias; a.res = o.res;
+    a.M = w.M; a.N = lay->N; a.K = K; a.T = w.T; a.Kp = w.Kp;
+    a.ldx = X ? ldx : lay->N; a.ldy = o.ldy ? o.ldy : lay->N; a.ldr = o.res ? lay->N : 0;
+    a.act = o.act; a.in_act = o.in_act; a.yh_lrelu = o.yh_lrelu;
+    a.acc_scale = 1.0f / w.scale;
+    a.in_slope = o.in_slope; a.act_slope = 0.2f;
+    a.n_prod = 3;
+    a.n_groups = 1;
+    a.ileave_u = o.ileave;
+    for (int t = 0; t < w.T; ++t) { a.dh[t] = 0; a.dw[t] = o.dil * (t - w.T / 2); }
+    if (lay->N == 0) return;
+    // the workspace the library wants depends on WHICH operands are given, not on their addresses: the count pass asks with placeholders
+    ConvGemmArgs q = a;
+    q.X = xh ? nullptr : reinterpret_cast<const float*>(16);
+    q.Xh = xh ? reinterpret_cast<const uint16_t*>(16) : nullptr;
+    const size_t wsb = as_conv_gemm_workspace_bytes(&q);
+    const size_t mark = c.off;
+    a.ws = wsb ? c.raw_alloc(wsb) : nullptr;
+    a.ws_bytes = wsb;
+    c.off = mark;                                                       // (scratch of this launch only: the stream orders the next user behind it)
+    if (!c.go()) return;
+    a.meta = lay->d_meta;
+    RUN(c, as_conv_gemm_f32(&a, c.s));
+}
+
+// Generator.forward (Vocoder/vocoder.py:101-113) on packed frames: the launch sequence of artspeech_amd/vocoder.py::forward_packed
+void generator(Seq& c, const std::vector<int>& lens, const as_vocoder_io& io)
+{
+    const as_vocoder& v = c.v;
+    const as_vocoder_cfg& h = v.cfg;
+    const int nst = h.n_stages, nk = h.n_stacks, nd = h.n_dilations, c0 = h.upsample_initial_channel;
+    const Lay* lay = c.lay(lens);
+    if (!lay) return;
+    if (c.run && io.ld_mel < lay->N) { c.fail(AS_EINVAL); return; }
+    // what one stage hands to the next -- fp32 activations, or LeakyReLU of them as the next ConvTranspose1d's operand image -- lives in
+    // one of two slots at the head of the arena (stage i reads slot i % 2 and writes the other); everything behind them is the stage's
+    // own and is given back when the stage ends
+    size_t slot_bytes = align256((size_t)c0 * std::max(lay->N, 1) * sizeof(float));
+    {
+        double n = lay->N;
+        for (int i = 0; i < nst; ++i) {
+            n *= h.upsample_rates[i];
+            if (n > 2147483647.0) { c.fail(AS_EINVAL); return; }
+            const int cout = c0 >> (i + 1), ni = std::max((int)n, 1);
+            slot_bytes = std::max(slot_bytes, align256(std::max((size_t)cout * ni * sizeof(float), as_split_f16x2_bytes(cout, ni))));
+        }
+    }
+    char* slot[2];
+    for (int i = 0; i < 2; ++i) slot[i] = static_cast<char*>(c.raw_alloc(slot_bytes));
+    if (c.rc) return;
+    const size_t stage_base = c.off;
+
+    float* x = reinterpret_cast<float*>(slot[0]);
+    const uint16_t* xi = nullptr;       // LeakyReLU(x) as an operand image, when the producer of x wrote that instead of x
+    {
+        ConvOpt o;
+        o.bias = v.pre.bias;
+        conv(c, v.pre, io.mel, io.ld_mel, nullptr, h.num_mels, lay, x, o);
+    }
+    for (int i = 0; i < nst && !c.rc; ++i) {
+        c.off = stage_base;
+        const int u = h.upsample_rates[i], cin = c0 >> i, cout = c0 >> (i + 1);
+        const Lay* lay_up = c.scaled(lay, u);
+        if (!lay_up) return;
+        const int N = lay_up->N;
+        // ConvTranspose1d as one 3-tap conv with (phase, channel) rows: its epilogue stores the rows in time order when the channels are a
+        // multiple of 32 (ConvGemmArgs.ileave_u); otherwise as_interleave_phases_f32 behind it
+        const bool il = cout % 32 == 0;
+        float* z = il ? c.f32(cout, N) : c.f32(u * cout, lay->N);
+        ConvOpt o;
+        if (il) { o.bias = v.ups[i].bias; o.ileave = u; o.ldy = N; }
+        if (xi) {
+            conv(c, v.ups[i], nullptr, 0, xi, cin, lay, z, o);
+            xi = nullptr;
+        } else {
+            o.in_act = ACT_LRELU; o.in_slope = LRELU_SLOPE;
+            conv(c, v.ups[i], x, lay->N, nullptr, cin, lay, z, o);
+        }
+        // 32 / 64 channels: the residual steps are fused launches; they address a tensor with 32-bit byte offsets
+        const bool fused = (cout == 32 || cout == 64) && nk == 3 && 4.0 * u * cout * ((double)lay->N + 1.0) < 2147483648.0;
+        if (il) {
+            x = z;
+        } else {
+            x = c.f32(cout, N);
+            RUN(c, as_interleave_phases_f32(z, lay->N, v.ups_bias[i], cout, u, lay->N, x, N, c.s));
+        }
+        lay = lay_up;
+        char* const out_slot = slot[(i + 1) & 1];
+        const bool image_out = i + 1 < nst;                             // the stage's mean feeds only the next ConvTranspose1d
+        float* outs[3] = {c.f32(cout, N), c.f32(cout, N), nullptr};
+        if (fused) {
+            // a residual step is ONE launch that keeps its column tile in LDS between the two convs; the stage's mean (and, between
+            // stages, its LeakyReLU'd operand image) rides in the last step of the third stack
+            float* tmp[2] = {c.f32(cout, N), c.f32(cout, N)};
+            for (int j = 0; j < nk; ++j) {
+                const float* y = x;
+                const std::vector<Step>& blk = v.rb[(size_t)i * nk + j];
+                for (int n = 0; n < nd; ++n) {
+                    const bool end = n + 1 == nd, last = end && j + 1 == nk;
+                    AsResPairArgs a;
+                    memset(&a, 0, sizeof(a));
+                    a.x = y; a.ldx = N;
+                    if (last && image_out) { a.yh = reinterpret_cast<uint16_t*>(out_slot); a.yh_slope = LRELU_SLOPE; }
+                    else { a.y = last ? reinterpret_cast<float*>(out_slot) : (end ? outs[j] : tmp[n & 1]); a.ldy = N; }
+                    a.w1 = blk[n].c1.wh; a.w2 = blk[n].c2.wh; a.b1 = blk[n].c1.bias; a.b2 = blk[n].c2.bias;
+                    a.scale1 = 1.0f / blk[n].c1.scale; a.scale2 = 1.0f / blk[n].c2.scale;
+                    a.C = cout; a.N = N; a.k = blk[n].k; a.dil = blk[n].k > 1 ? blk[n].dil : 1; a.slope = LRELU_SLOPE;
+                    a.col_off = lay->d_off; a.B = lay->B; a.max_w = lay->max_cols();
+                    if (last) { a.add1 = outs[0]; a.add2 = outs[1]; a.ld_add = N; a.out_div = 3.0f; }
+                    RUN(c, as_respair_f32(&a, c.s));
+                    y = a.y;
+                }
+            }
+            if (image_out) { x = nullptr; xi = reinterpret_cast<const uint16_t*>(out_slot); }
+            else x = reinterpret_cast<float*>(out_slot);
+            continue;
+        }
+        // LeakyReLU(x) as an operand image, once for the three stacks that start from x; inside a stack every conv hands its LeakyReLU'd
+        // result to the next one as an image (ConvGemmArgs.Yh / yh_lrelu)
+        outs[2] = c.f32(cout, N);
+        uint16_t* xh = c.image(cout, N);
+        RUN(c, as_split_f16x2_f32(x, N, cout, N, ACT_LRELU, LRELU_SLOPE, xh, c.s));
+        uint16_t* img[3] = {c.image(cout, N), c.image(cout, N), c.image(cout, N)};
+        float* tmp[2] = {c.f32(cout, N), c.f32(cout, N)};
+        for (int j = 0; j < nk; ++j) {
+            const float* y = x;
+            const uint16_t* yh = xh;
+            const std::vector<Step>& blk = v.rb[(size_t)i * nk + j];
+            for (int n = 0; n < nd; ++n) {
+                const bool end = n + 1 == nd;
+                uint16_t* xth = img[0];
+                ConvOpt o1;
+                o1.bias = blk[n].c1.bias; o1.yh = xth; o1.yh_lrelu = true; o1.in_slope = LRELU_SLOPE; o1.dil = blk[n].dil;
+                conv(c, blk[n].c1, nullptr, 0, yh, cout, lay, nullptr, o1);
+                uint16_t* next = end ? nullptr : img[1 + (n & 1)];
+                float* yo = end ? outs[j] : tmp[n & 1];
+                ConvOpt o2;
+                o2.bias = blk[n].c2.bias; o2.res = y; o2.yh = next; o2.yh_lrelu = !end; o2.in_slope = LRELU_SLOPE;
+                conv(c, blk[n].c2, nullptr, 0, xth, cout, lay, yo, o2);
+                y = yo;
+                yh = next;
+            }
+        }
+        if (image_out) {
+            RUN(c, as_mean3_image_f32(outs[0], outs[1], outs[2], N, cout, N, LRELU_SLOPE, reinterpret_cast<uint16_t*>(out_slot), c.s));
+            x = nullptr;
+            xi = reinterpret_cast<const uint16_t*>(out_slot);
+        } else {
+            x = reinterpret_cast<float*>(out_slot);
+            RUN(c, as_mean3_f32(outs[0], outs[1], outs[2], N, cout, N, x, N, c.s));
+        }
+    }
+    if (c.rc) return;
+    // conv_post: LeakyReLU(0.01) -> one output row -> tanh, and the 16-bit samples in the same pass
+    const int C = c0 >> nst, N = lay->N;
+    if (v.post32) {
+        RUN(c, as_conv_post_pcm_f32(x, N, C, N, v.post32, v.post.bias, v.post_k, POST_SLOPE, 1, lay->d_meta, io.wav, io.pcm, c.s));
+    } else {
+        float* wav = io.wav ? io.wav : c.f32(1, N);
+        ConvOpt o;
+        o.bias = v.post.bias; o.in_act = ACT_LRELU; o.in_slope = POST_SLOPE; o.act = ACT_TANH;
+        conv(c, v.post, x, N, nullptr, C, lay, wav, o);
+        if (io.pcm) RUN(c, as_pcm16_launch(wav, N, io.pcm, c.s));
+    }
+}
+
+bool lens_ok(const as_vocoder* v, int B, const int32_t* lens, std::vector<int>* out)
+{
+    if (!v || B < 1 || !lens) return false;
+    out->assign(lens, lens + B);
+    for (int x : *out)
+        if (x < 0 || (double)x * v->hop > (double)AS_META_MAX_W) return false;
+    return true;
+}
+
+size_t count(const as_vocoder* v, as_plan* p, const std::vector<int>& lens, const as_vocoder_io& io, int* rc)
+{
+    Seq c{*v, *p, nullptr, nullptr, 0, 0, 0, false};
+    generator(c, lens, io);
+    *rc = c.rc;
+    return c.rc ? 0 : c.peak + 256;
+}
+
+}  // namespace
+
+extern "C" int as_vocoder_fold_upsample_host(const float* wt, int Cin, int Cout, int u, float* wc)
+{
+    if (!wt || !wc || Cin <= 0 || Cout <= 0 || u < 1) return AS_EINVAL;
+    const int p = u / 2 + u % 2, k = 2 * u;
+    memset(wc, 0, (size_t)u * Cout * Cin * 3 * sizeof(float));
+    for (int r = 0; r < u; ++r) {
+        const int rr = (r + p) % u, s = (r + p) / u;
+        for (int j = 0; j < 2; ++j) {
+            const int d = s - j + 1;                                    // taps x[q - 1], x[q], x[q + 1] = d 0, 1, 2
+            if (d < 0 || d > 2) return AS_EINVAL;
+            for (int m = 0; m < Cout; ++m)
+                for (int c = 0; c < Cin; ++c) wc[(((size_t)r * Cout + m) * Cin + c) * 3 + d] = wt[((size_t)c * Cout + m) * k + rr + u * j];
+        }
+    }
+    return AS_OK;
+}
+
+extern "C" int as_vocoder_create(const void* blob_host, size_t blob_bytes, const as_vocoder_cfg* cfg, as_vocoder** out)
+{
+    if (!blob_host || !cfg || !out || !cfg_ok(*cfg)) return AS_EINVAL;
+    return abi([&] { return vocoder_create(blob_host, blob_bytes, cfg, out); });
+}
+
+extern "C" int as_vocoder_destroy(as_vocoder* v)
+{
+    if (!v) return AS_EINVAL;
+    v->pool.release();
+    delete v;
+    return AS_OK;
+}
+
+extern "C" int as_vocoder_get_cfg(const as_vocoder* v, as_vocoder_cfg* out)
+{
+    if (!v || !out) return AS_EINVAL;
+    *out = v->cfg;
+    return AS_OK;
+}
+
+extern "C" int as_vocoder_hop(const as_vocoder* v) { return v ? v->hop : AS_EINVAL; }
+
+extern "C" int as_vocoder_plan_create(const as_vocoder* v, as_plan** out)
+{
+    if (!v || !out) return AS_EINVAL;
+    return abi([&] { *out = new as_plan(); return AS_OK; });
+}
+
+extern "C" size_t as_vocoder_workspace_bytes(const as_vocoder* v, as_plan* p, int B, const int32_t* lens_host)
+{
+    std::vector<int> lens;
+    if (!p || !lens_ok(v, B, lens_host, &lens)) return 0;
+    size_t n = 0;
+    const as_vocoder_io io = {nullptr, 0, nullptr, nullptr};            // (no output given: the conv GEMM form of conv_post counts its fp32 row)
+    (void)abi([&] { int rc; n = count(v, p, lens, io, &rc); return rc; });
+    return n;
+}
+
+extern "C" int as_vocoder_forward(const as_vocoder* v, as_plan* p, int B, const int32_t* lens_host, const as_vocoder_io* io, void* ws,
+                                  size_t ws_bytes, as_stream_t stream)
+{
+    std::vector<int> lens;
+    if (!p || !io || !io->mel || (!io->wav && !io->pcm) || !lens_ok(v, B, lens_host, &lens)) return AS_EINVAL;
+    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255) != 0 || (io->pcm && (reinterpret_cast<uintptr_t>(io->pcm) & 1) != 0)) return AS_EINVAL;
+    return abi([&] {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        int rc = p->trim(s);
+        if (rc != AS_OK) return rc;
+        p->note_stream(s);
+        if (as_status_peek()) return (int)AS_EDEVICE;                    // sticky until as_device_status(1)
+        long total = 0;
+        for (int x : lens) total += x;
+        if (io->ld_mel < total) return (int)AS_EINVAL;
+        if (total == 0) return (int)AS_OK;
+        // a workspace too small is refused before anything is launched
+        as_vocoder_io q = *io;
+        q.wav = nullptr; q.pcm = nullptr;
+        const size_t need = count(v, p, lens, q, &rc);
+        if (rc != AS_OK) return rc;
+        if (need > ws_bytes) return (int)AS_ENOSPC;
+        Seq c{*v, *p, s, static_cast<char*>(ws), ws_bytes, 0, 0, true};
+        generator(c, lens, *io);
+        return c.rc;
+    });
+}

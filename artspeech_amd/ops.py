@@ -463,9 +463,15 @@ def mean3(A, B, C3, n, Y):
     return Y
 
 
-def conv_post(X, lay, w, bias, in_slope, tanh_out=True):
-    """y [1][N] = tanh(conv1d(LeakyReLU(X [C][N], in_slope), w fp32 [C][k]) + bias): the vocoder's last conv (vocoder.py:111-113)."""
+def conv_post(X, lay, w, bias, in_slope, tanh_out=True, pcm=False):
+    """y [1][N] = tanh(conv1d(LeakyReLU(X [C][N], in_slope), w fp32 [C][k]) + bias): the vocoder's last conv (vocoder.py:111-113).
+    pcm=True: (y, the same samples as int16 [N] written by the same kernel) -- as_conv_post_pcm_f32."""
     Y = lay.new(1)
+    if pcm:
+        P = torch.empty(max(lay.N, 1), dtype=torch.int16, device=X.device)
+        check(_lib.lib().as_conv_post_pcm_f32(_p(X), _ld(X), X.shape[0], lay.N, _p(w), _p(bias), w.shape[1], float(in_slope), int(tanh_out),
+                                              _p(lay.meta), _p(Y), _p(P), stream()), "as_conv_post_pcm_f32")
+        return Y, P
     check(_lib.lib().as_conv_post_f32(_p(X), _ld(X), X.shape[0], lay.N, _p(w), _p(bias), w.shape[1], float(in_slope), int(tanh_out),
                                       _p(lay.meta), _p(Y), stream()), "as_conv_post_f32")
     return Y

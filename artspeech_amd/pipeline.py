@@ -234,7 +234,7 @@ class ArtSpeech:
         return table, torch.tensor(idx, dtype=torch.int32)
 
     @torch.no_grad()
-    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None):
+    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed, 24 kHz) reference wave on: log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator.  Returns the samples (mel frames if no vocoder is attached).
         Loading / trimming / resampling the file (librosa, test.py:99-106) and espeak stay with the caller."""
@@ -249,29 +249,31 @@ class ArtSpeech:
             mel, lens = self.frontend(list(ref_wave))
             mels = [mel[b, :, :n] for b, n in enumerate(lens)]
         fn = self.synthesis_wav if self.generator is not None else self.synthesis_mel
-        out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody)
+        kw = {"pcm16": True} if pcm16 and self.generator is not None else {}
+        out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody, **kw)
         return out[0] if single and out.dim() > 1 and self.generator is not None else out
 
-    def attach_vocoder(self, h=None, checkpoint=None):
-        """test.py:119-125: build the generator from Vocoder/config.json-style `h` and load checkpoint['generator']."""
+    def attach_vocoder(self, h=None, checkpoint=None, runtime=False):
+        """test.py:119-125: build the generator from Vocoder/config.json-style `h` and load checkpoint['generator'].
+        runtime=True: the generator runs inside the library (one as_vocoder_forward call per batch; vocoder.Generator)."""
         from .vocoder import Generator
-        self.generator = Generator(h, device=self.device)
+        self.generator = Generator(h, device=self.device, runtime=runtime)
         if checkpoint is not None:
             sd = checkpoint if isinstance(checkpoint, dict) else torch.load(checkpoint, map_location="cpu")
             self.generator.load_state_dict(sd)
         return self.generator
 
     @torch.no_grad()
-    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None):
+    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
-        generator: no padding is ever synthesised."""
+        generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the generator's last kernel."""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         single = isinstance(phonemes, str)
         mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody)
         lens = self._last_frames
-        wav = self.generator(mel, lengths=lens)[:, 0]
+        wav = (self.generator(mel, lengths=lens, pcm16=True) if pcm16 else self.generator(mel, lengths=lens))[:, 0]
         return wav[0] if single else wav
 
     @torch.no_grad()

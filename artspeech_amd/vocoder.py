@@ -9,12 +9,17 @@ Everything dense runs through the conv GEMM of the acoustic path (``ops.conv_gem
                          out[u q + r] = sum_j w[:, :, (r+p)%u + u j] x[q + (r+p)//u - j]  (p = padding), i.e. taps
                          x[q-1], x[q], x[q+1] with a per-phase weight (zero where a phase does not use the tap)
 Activations stay in the packed-frames layout, so a ragged batch costs nothing and every utterance equals its B = 1 result.
+
+``Generator(h, runtime=True)`` runs the same launch sequence inside the library (``as_vocoder_forward``, csrc/vocoder_rt.hip): one C call
+per batch instead of ~110, capturable into a graph, with the samples as 16-bit PCM from the last kernel on request.  The default is the
+operator-by-operator sequence below.
 """
+import ctypes
 
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .ops import ACT_LRELU, ACT_NONE, ACT_TANH, layout, taps_1d
 from .synth import hash_tensor
 from .weights import fold_state_dict
@@ -83,17 +88,96 @@ def _dil_taps(k, d):
 class Generator:
     """``Generator(h)`` of Vocoder/vocoder.py:75-125 (ResBlock1 configuration)."""
 
-    def __init__(self, h=None, device=None):
+    def __init__(self, h=None, device=None, runtime=False):
         self.h = {**DEFAULT_H, **(h if isinstance(h, dict) else (vars(h) if h is not None else {}))}
         if str(self.h["resblock"]) != "1":
             raise NotImplementedError("only the ResBlock1 generator of Vocoder/config.json is built")
         from .models import _need_gpu
         self.device = _need_gpu(device if device is not None else "cuda")
         self.W = None
+        self.runtime = bool(runtime)
+        self._voc = self._plan = self._ws = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _release(self):
+        L = _lib.lib()
+        if self._plan:
+            torch.cuda.synchronize(self.device)
+            L.as_plan_destroy(self._plan)
+        if self._voc:
+            L.as_vocoder_destroy(self._voc)
+        self._voc = self._plan = self._ws = None
+
+    # ------------------------------------------------------------------ the library's generator (runtime=True)
+    def runtime_cfg(self):
+        """the as_vocoder_cfg of self.h"""
+        h, c = self.h, _lib.VocoderCfg()
+        rates, ks, rk, rd = h["upsample_rates"], h["upsample_kernel_sizes"], h["resblock_kernel_sizes"], h["resblock_dilation_sizes"]
+        if len(rates) > 8 or len(rk) > 4 or any(len(d) != len(rd[0]) or len(d) > 4 for d in rd) or len(rk) != len(rd) or len(ks) != len(rates):
+            raise NotImplementedError("as_vocoder_cfg holds up to 8 stages and 4 stacks of up to 4 dilations each")
+        c.num_mels, c.upsample_initial_channel, c.n_stages, c.n_stacks, c.n_dilations = h["num_mels"], h["upsample_initial_channel"], len(rates), len(rk), len(rd[0])
+        for i, (u, k) in enumerate(zip(rates, ks)):
+            c.upsample_rates[i], c.upsample_kernel_sizes[i] = u, k
+        for j, (k, dil) in enumerate(zip(rk, rd)):
+            c.resblock_kernel_sizes[j] = k
+            for n, d in enumerate(dil):
+                c.resblock_dilations[j][n] = d
+        return c
+
+    def _load_runtime(self, sd):
+        """as_vocoder_create on the state dict.  The blob holds the weights as fold_state_dict folds them (plain ``weight`` keys, which the
+        library takes as they are -- a checkpoint saved after remove_weight_norm() looks the same): torch's fp32 norm and the library's
+        own weight_norm fold (a float64 sum, what a C host gets from a weight_g / weight_v blob) differ in the last bit of about a third
+        of the weights, and the two Python paths are meant to agree bit for bit.  Everything else -- the ConvTranspose1d -> phase conv
+        rewrite, per-row biases, the fp32 conv_post row, the weight images -- happens in the library."""
+        from .blob import state_dict_to_blob
+        self._release()
+        blob = state_dict_to_blob(fold_state_dict(sd))
+        cfg, voc, plan = self.runtime_cfg(), ctypes.c_void_p(), ctypes.c_void_p()
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            _lib.check(L.as_vocoder_create(blob, len(blob), ctypes.byref(cfg), ctypes.byref(voc)), "as_vocoder_create")
+            self._voc = voc
+            _lib.check(L.as_vocoder_plan_create(voc, ctypes.byref(plan)), "as_vocoder_plan_create")
+            self._plan = plan
+        self.hop = L.as_vocoder_hop(voc)
+        return self
+
+    def _forward_runtime(self, mel_p, lay, wav=True, pcm=False):
+        """as_vocoder_forward on the current stream.  The workspace is kept and only ever grows: a graph captured from this generator
+        stays valid as long as no larger geometry has been run since."""
+        if self._voc is None:
+            raise RuntimeError("no weights loaded: call load_state_dict first")
+        if not (wav or pcm):
+            raise ValueError("forward_packed: at least one of wav and pcm")
+        L = _lib.lib()
+        B = lay.B
+        lens = (ctypes.c_int32 * B)(*lay.widths_host)
+        need = L.as_vocoder_workspace_bytes(self._voc, self._plan, B, lens)
+        if need == 0:
+            raise _lib.HipLibraryError("as_vocoder_workspace_bytes: invalid geometry (an utterance beyond AS_META_MAX_W samples?)")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        n = lay.N * self.hop
+        io = _lib.VocoderIO()
+        out_w = torch.empty((1, max(n, 1)), dtype=torch.float32, device=self.device) if wav else None
+        out_p = torch.empty(max(n, 1), dtype=torch.int16, device=self.device) if pcm else None
+        io.mel, io.ld_mel, io.wav, io.pcm = ops._p(mel_p), ops._ld(mel_p), ops._p(out_w), ops._p(out_p)
+        _lib.check(L.as_vocoder_forward(self._voc, self._plan, B, lens, ctypes.byref(io), self._ws.data_ptr(), self._ws.numel(), _lib.stream()),
+                   "as_vocoder_forward")
+        lay_w = lay.scaled(self.hop)
+        return (out_w, lay_w, out_p) if pcm else (out_w, lay_w)
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd, strict=False):
         sd = sd.get("generator", sd) if isinstance(sd, dict) else sd       # test.py:124: checkpoint['generator']
+        if self.runtime:
+            return self._load_runtime(sd)
         w = fold_state_dict(sd)
         dev, h, W = self.device, self.h, {}
         W["pre"] = (ops.prep_weight(w["conv_pre.weight"], dev), w["conv_pre.bias"].to(dev))
@@ -138,8 +222,14 @@ class Generator:
         return self
 
     # ------------------------------------------------------------------ forward
-    def forward_packed(self, mel_p, lay):
-        """mel_p [80][sum T] packed -> (wav [1][300 sum T], layout of the samples)."""
+    def forward_packed(self, mel_p, lay, pcm=False, wav=True):
+        """mel_p [80][sum T] packed -> (wav [1][300 sum T], layout of the samples); pcm=True: also the samples as int16 [300 sum T],
+        converted by the last kernel (as_conv_post_pcm_f32's rule); wav=False (runtime=True, with pcm): no fp32 samples are written (None)."""
+        if self.runtime:
+            with torch.cuda.device(self.device):
+                return self._forward_runtime(mel_p, lay, wav=wav, pcm=pcm)
+        if not wav:
+            raise ValueError("forward_packed(wav=False) needs Generator(runtime=True)")
         W, h = self.W, self.h
         if W is None:
             raise RuntimeError("no weights loaded: call load_state_dict first")
@@ -210,6 +300,11 @@ class Generator:
             else:
                 x = ops.mean3(outs[0], outs[1], outs[2], lay.N, lay.new(cout))
         wt, b = W["post"]
+        if pcm:
+            if W["post32"] is None:
+                raise NotImplementedError("16-bit samples from the operator-level path need the fp32 conv_post kernel (k = 3, 5, 7)")
+            wav, p16 = ops.conv_post(x, lay, W["post32"], b, 0.01, pcm=True)
+            return wav, lay, p16
         if W["post32"] is not None:
             wav = ops.conv_post(x, lay, W["post32"], b, 0.01)
         else:
@@ -217,13 +312,18 @@ class Generator:
         return wav, lay
 
     @torch.no_grad()
-    def forward(self, x, lengths=None):
-        """x: mel [B, 80, T] (zero-padded beyond `lengths`) -> wav [B, 1, 300 * T], zero beyond each utterance."""
+    def forward(self, x, lengths=None, pcm16=False):
+        """x: mel [B, 80, T] (zero-padded beyond `lengths`) -> wav [B, 1, 300 * T], zero beyond each utterance; pcm16=True: the same as
+        int16 samples converted on the device (forward_packed(pcm=True))."""
         from .models import pack, unpack
         B, _, T = x.shape
         lens = [int(v) for v in lengths] if lengths is not None else [T] * B
         lay = layout(lens, self.device)
-        wav, lay_w = self.forward_packed(pack(x.to(self.device), lens), lay)
+        with torch.cuda.device(self.device):
+            if pcm16:
+                _, lay_w, p16 = self.forward_packed(pack(x.to(self.device), lens), lay, pcm=True)
+                return unpack(p16[None], lay_w)
+            wav, lay_w = self.forward_packed(pack(x.to(self.device), lens), lay)
         return unpack(wav, lay_w)
 
     __call__ = forward

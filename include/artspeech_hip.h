@@ -536,6 +536,12 @@ int as_mean3_image_f32(const float* a, const float* b, const float* c, int ld, i
  * zero padding per utterance (meta = the layout's column descriptors), act = tanh when tanh_out; k = 3, 5 or 7.  Plain fp32 FMAs: a read of x. */
 int as_conv_post_f32(const float* x, int ldx, int C, int N, const float* w, const float* bias, int k, float in_slope, int tanh_out,
                      const uint64_t* meta, float* y, as_stream_t stream);
+/* as_conv_post_f32 with the samples (also, or with y NULL: only) as 16-bit PCM, written by the same pass -- the waveform is never re-read:
+ *     pcm = (int16) fmaxf(-32768.f, fminf(32767.f, rintf(32767.f * w)))        w = the fp32 sample y would get
+ * (one fp32 multiply, round half to even, saturate).  A NaN sample stores 0 and raises AS_STATUS_F16_RANGE; the fp32 output is as
+ * as_conv_post_f32 writes it.  At least one of y and pcm; pcm 2-byte aligned (4-byte aligned: two samples per store). */
+int as_conv_post_pcm_f32(const float* x, int ldx, int C, int N, const float* w, const float* bias, int k, float in_slope, int tanh_out,
+                         const uint64_t* meta, float* y, int16_t* pcm, as_stream_t stream);
 /* One residual step of ResBlock1 (vocoder.py:35-42) as ONE launch, for the stages with C = 32 or 64 channels:
  *     y = x + conv2(lrelu(conv1(lrelu(x))))        conv1: k taps with dilation dil, conv2: k taps with dilation 1, zero padding per utterance
  * x, y fp32 [C][N] (y != x: a workgroup reads its neighbours' columns of x); w1, w2 = the conv GEMM's weight images of the two
@@ -760,6 +766,52 @@ int as_forward_test_finish(const as_model* m, as_plan* p, const as_batch* batch,
                            void* ws_b, size_t ws_b_bytes, as_stream_t stream);
 int as_forward_test(const as_model* m, as_plan* p, const as_batch* batch, const as_forward_io* io, void* ws_a, size_t ws_a_bytes,
                     void* ws_b, size_t ws_b_bytes, int32_t* frames_host_out, as_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The HiFi-GAN generator behind an opaque handle (csrc/vocoder_rt.hip; Vocoder/vocoder.py:75-125, test.py:115): mel in, samples out,
+ * ONE call -- the launch sequence artspeech_amd/vocoder.py issues operator by operator, in the library.
+ *
+ * as_vocoder = the generator's weights: immutable after as_vocoder_create, shareable between host threads, one per GPU (like as_model:
+ *              as_vocoder_create ALLOCATES device memory on the current HIP device and synchronises; as_vocoder_destroy frees it).
+ * blob_host  = the Generator's state dict in the "ASWBLOB1" format of as_model_create: conv_pre / ups.i / resblocks.n.convs1|2.j /
+ *              conv_post, each as weight_g + weight_v + bias (weight_norm, folded here) or as weight + bias (a checkpoint saved after
+ *              remove_weight_norm()).  The ConvTranspose1d -> 3-tap phase conv rewrite (as_vocoder_fold_upsample_host), the per-row
+ *              biases, the fp32 conv_post row and the weight images are made here.
+ * as_plan    = the per-caller cache of geometry tables, as for the acoustic model (layouts at 1x and at every stage's rate of `lens`).
+ *              as_vocoder_plan_create makes one that needs no as_model: freed by as_plan_destroy, it serves as_vocoder_* only; a plan made
+ *              by as_plan_create serves too.  The first call with a new geometry uploads tables and synchronises the stream (do not
+ *              capture it); later calls with that geometry only enqueue kernels on `stream`, take nothing from the host but the
+ *              arguments and allocate nothing: they can be captured into a hipGraph.  The chain is serial: no side streams.
+ * AS_EINVAL: k != 2 u, u < 2, channels that do not halve n_stages times, n_stacks != 3 (ResBlock1 of Vocoder/config.json), a tensor
+ * missing from the blob or of another shape, B < 1, a negative length, an utterance of more than AS_META_MAX_W samples, both outputs
+ * NULL, ld_mel < sum lens; AS_ENOSPC: workspace too small (nothing is launched); AS_EDEVICE while a device status bit is set.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct as_vocoder as_vocoder;
+typedef struct as_vocoder_cfg {                 /* Vocoder/config.json; ResBlock1 only */
+    int32_t num_mels, upsample_initial_channel;
+    int32_t n_stages;  int32_t upsample_rates[8], upsample_kernel_sizes[8];      /* k == 2 u required */
+    int32_t n_stacks;  int32_t resblock_kernel_sizes[4], resblock_dilations[4][4], n_dilations;   /* 3 stacks x 3 steps in config.json */
+} as_vocoder_cfg;
+int as_vocoder_create(const void* blob_host, size_t blob_bytes, const as_vocoder_cfg* cfg, as_vocoder** out);
+int as_vocoder_destroy(as_vocoder* v);
+int as_vocoder_get_cfg(const as_vocoder* v, as_vocoder_cfg* out);
+int as_vocoder_hop(const as_vocoder* v);        /* samples per mel frame = the product of the rates (300) */
+int as_vocoder_plan_create(const as_vocoder* v, as_plan** out);
+
+typedef struct as_vocoder_io {
+    const float* mel; int32_t ld_mel;           /* DEVICE [num_mels][ld_mel >= sum lens], packed frames */
+    float* wav;                                 /* DEVICE [hop * sum lens] fp32 in [-1, 1], or NULL */
+    int16_t* pcm;                               /* DEVICE [hop * sum lens] 16-bit PCM (as_conv_post_pcm_f32's rule), or NULL (at least one of the two) */
+} as_vocoder_io;
+/* lens_host int32 [B]: mel frames per utterance.  Workspace: caller-owned device memory, 256-byte aligned; 0 = invalid arguments. */
+size_t as_vocoder_workspace_bytes(const as_vocoder* v, as_plan* p, int B, const int32_t* lens_host);
+int as_vocoder_forward(const as_vocoder* v, as_plan* p, int B, const int32_t* lens_host, const as_vocoder_io* io,
+                       void* ws, size_t ws_bytes, as_stream_t stream);
+/* Host helper (no GPU work): ConvTranspose1d weight wt [Cin][Cout][2u] (stride u, padding u/2 + u%2) -> the 3-tap conv
+ * wc [u*Cout][Cin][3] whose output rows are (phase r, channel m), row r Cout + m:
+ *     y[m][u q + r] = sum_c sum_d wc[r Cout + m][c][d] x[c][q + d - 1]
+ * phase r reads tap kk = (r + p) % u + u j of wt at d = (r + p) / u - j + 1, j = 0, 1; the third entry of a row is zero. */
+int as_vocoder_fold_upsample_host(const float* wt, int Cin, int Cout, int u, float* wc);
 
 /* ---- batches in flight (csrc/lanes.hip; DESIGN.md section 5: the throughput arrangement) -----------------------------------------------
  * as_lanes = n lanes on ONE model: per lane a HIP stream of its own, its two workspaces (grown on demand), TWO serial plans
