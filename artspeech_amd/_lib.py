@@ -235,8 +235,21 @@ class VocoderIO(ctypes.Structure):
     _fields_ = [("mel", c_p), ("ld_mel", ctypes.c_int32), ("wav", c_p), ("pcm", c_p)]
 
 
+class VocoderCap(ctypes.Structure):
+    """as_vocoder_cap: the generator under a frame capacity (DEVICE offsets)"""
+    _fields_ = [("off", c_p), ("mult", ctypes.c_int32), ("cap", ctypes.c_int32), ("max_len", ctypes.c_int32), ("sample_off", c_p)]
+
+
 _pI32 = ctypes.POINTER(ctypes.c_int32)
 _SIGNATURES.update({
+    "as_vocoder_cap_workspace_bytes": (c_sz, [c_p, c_p, c_i, c_i, c_i]),
+    "as_vocoder_forward_cap": (c_i, [c_p, c_p, c_i, ctypes.POINTER(VocoderCap), ctypes.POINTER(VocoderIO), c_p, c_sz, c_p]),
+    "as_vocoder_cap_geometry": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, _pI32, c_p, c_p, c_p, c_p]),
+    "as_split_f16x2_cap_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, ctypes.c_float, c_p, c_p]),
+    "as_mean3_cap_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
+    "as_mean3_image_cap_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, ctypes.c_float, c_p, c_p]),
+    "as_interleave_phases_cap_f32": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
+    "as_conv_post_pcm_cap_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, ctypes.c_float, c_i, c_p, c_p, c_p, c_p, c_p]),
     "as_conv_post_pcm_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, ctypes.c_float, c_i, c_p, c_p, c_p, c_p]),
     "as_vocoder_create": (c_i, [c_p, c_sz, ctypes.POINTER(VocoderCfg), ctypes.POINTER(c_p)]),
     "as_vocoder_destroy": (c_i, [c_p]),
@@ -288,7 +301,7 @@ STATUS_NAMES = ("clustered LSTM hand-over timed out", "MAS band hand-over timed 
                 "non-finite accumulator (an operand beyond fp16's range, or a non-finite input)",
                 "a layout the kernels cannot serve: an utterance wider than the column descriptors (AS_META_MAX_W) or than its caller said, "
                 "or (as_lanes debug mode) device buffers that changed while their submission was waiting for its group",
-                "the predicted durations add up to more frames than the capacity the caller named (as_forward_io.frame_cap)",
+                "the predicted durations add up to more frames than the capacity the caller named (as_forward_io.frame_cap, as_vocoder_cap)",
                 "a voice index outside [0, n_voices) (as_forward_io.voice_idx): that utterance got a zero voice")
 
 

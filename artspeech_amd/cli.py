@@ -66,6 +66,8 @@ def build_parser():
     ap.add_argument("--vocoder-config", help="Vocoder/config.json")
     ap.add_argument("--vocoder", help="Vocoder/g_00935000")
     ap.add_argument("--vocoder-runtime", action="store_true", help="run the generator inside the library: one C call per batch (as_vocoder_forward)")
+    ap.add_argument("--frame-cap", type=int, metavar="N", help="room for N half-rate frames (2 N mel frames): the acoustic model and the generator run as "
+                    "one chain with no read-back of the predicted durations in between (as_vocoder_forward_cap); implies --vocoder-runtime")
     ap.add_argument("--pcm16", action="store_true", help="16-bit samples straight from the generator's last kernel (no host-side conversion)")
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights instead of checkpoints (smoke / demo)")
     ap.add_argument("--tiny", action="store_true", help="with --synthetic: the small test configuration")
@@ -77,6 +79,10 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.save_voice and not a.ref_wav:
         ap.error("--save-voice needs --ref-wav (the voice is computed from it)")
+    if a.frame_cap is not None:
+        if a.frame_cap < 1:
+            ap.error("--frame-cap takes a positive number of frames")
+        a.vocoder_runtime = True
     try:
         a.prosody = prosody_of(a)
     except ValueError as e:
@@ -116,13 +122,13 @@ def main(argv=None):
         tts.attach_vocoder(h, a.vocoder, runtime=a.vocoder_runtime)
     if a.voice:
         from .pipeline import Voice
-        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16)
+        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap)
     else:
         wave_in = read_wav(a.ref_wav)
         if a.save_voice:
             tts.voice_from_wave(wave_in).save(a.save_voice)
             print(f"{a.save_voice}: voice of {a.ref_wav}")
-        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16)
+        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap)
     write_wav(a.out, audio.cpu().numpy())
     print(f"{a.out}: {audio.numel() / 24000.0:.2f} s of audio from {tts._last_frames[0]} mel frames")
     return 0

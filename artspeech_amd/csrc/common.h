@@ -96,8 +96,29 @@ int as_durations_prosody_launch(const float* dur_f32, const int32_t* forced_dur,
 int as_project_cols_prosody_launch(const float* x, int ldx, int K, int N, const float* w, const float* bias, int M, float* y, int ldy,
                                    const float* pros, int ld_pros, const int32_t* col_off, int B, int track0, hipStream_t s);
 
-// fp32 samples w [N] -> 16-bit PCM by the rule of as_conv_post_pcm_f32 (vocoder.hip; a NaN stores 0 and raises AS_STATUS_F16_RANGE)
-int as_pcm16_launch(const float* w, int N, int16_t* pcm, hipStream_t stream);
+// fp32 samples w [N] -> 16-bit PCM by the rule of as_conv_post_pcm_f32 (vocoder.hip; a NaN stores 0 and raises AS_STATUS_F16_RANGE).
+// n_valid (a capacity layout, device count): samples [*n_valid, N) are not read; pcm and w_fill (each may then be NULL) get 0 there
+int as_pcm16_launch(const float* w, int N, const int32_t* n_valid, float* w_fill, int16_t* pcm, hipStream_t stream);
+
+// Capacity layouts of the HiFi-GAN generator (as_vocoder_forward_cap; vocoder.hip): the utterances' lengths exist on the device only --
+// off [B + 1] in units of `mult` mel frames, packed from column 0 -- and ONE launch derives the tables of the mel-rate layout and of every
+// up-sampled one (rate[i] columns per mel frame, rate[0] = 1) from them.  The tables are two flat arrays:
+//   tab  int32 [n_rates][2 B + 2]: per rate the widths w [B], the first columns off_r [B + 1], then n_valid (= off_r[B])
+//   meta [cap * sum rate]:         rate i's column descriptors start at cap * (rate[0] + ... + rate[i - 1])
+// Offsets are cut at cap (AS_STATUS_CAPACITY when off[B] * mult > cap, or when an utterance has more than max_len mel frames); an
+// utterance wider than AS_META_MAX_W columns at a rate raises AS_STATUS_BAD_LAYOUT and its columns there get one-column descriptors.
+#define AS_VOC_MAX_RATES 9
+struct AsVocGeo {
+    const int32_t* off;
+    int32_t B, mult, cap, max_len, n_rates;
+    int32_t rate[AS_VOC_MAX_RATES];
+    long long meta_start[AS_VOC_MAX_RATES];   // in descriptors
+    int32_t* tab;
+    unsigned long long* meta;
+    int32_t* sample_off;                      // optional [B + 1]: off_r of the last rate
+    unsigned* status;
+};
+int as_vocoder_cap_geometry_launch(const AsVocGeo& g, hipStream_t stream);
 
 // kernel classes for the optional event profiler (prof.hip)
 enum { AS_CLS_GEMM = 0, AS_CLS_ADAIN = 1, AS_CLS_LN = 2, AS_CLS_ATTN = 3, AS_CLS_LSTM = 4, AS_CLS_MAS = 5, AS_CLS_OTHER = 6, AS_N_CLS = 7 };

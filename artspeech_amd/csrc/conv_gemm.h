@@ -11,7 +11,8 @@
 // tiles of `n` independent problems (1 <= n <= H3_MAXP), problem i in S[i] K slices; returns AS_OK or a hipError_t.  (conv_gemm_h3.hip)
 int as_conv_gemm_h3_launch(const ConvGemmArgs* const* a, const int* S, int n, int choice, hipStream_t stream);
 // host: the kernel that writes the split image of X (no profiling scope of its own)
-int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, float slope, uint16_t* xh, hipStream_t stream);
+int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, float slope, uint16_t* xh, hipStream_t stream,
+                          const int32_t* n_valid = nullptr);
 
 static inline __host__ __device__ int as_kbx(int K) { return (((K + 15) >> 4) + 3) & ~3; }      // k-blocks of a split image: a multiple of 4
 // host: M output channels fill a 128-row tile well enough to use one (it is not half empty) -- the tile rules of conv_gemm.hip, and the

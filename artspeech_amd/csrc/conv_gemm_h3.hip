@@ -466,25 +466,30 @@ int as_conv_gemm_h3_launch(const ConvGemmArgs* const* a, const int* S, int n, in
 // contiguous bytes of a row and every store 1 KB of an image row (with four CONSECUTIVE columns per lane a store put 16 bytes every 64:
 // 32 quarter-filled lines per instruction).  Range-checked buffer loads: offsets of rows >= K fall outside the descriptor (zero).
 __global__ void __launch_bounds__(256)
-split_f16x2_kernel(const float* __restrict__ x, int ldx, int K, int N, int lrelu, float slope, u32x4_t* __restrict__ xh)
+split_f16x2_kernel(const float* __restrict__ x, int ldx, int K, int N, const int* __restrict__ n_valid, int lrelu, float slope,
+                   u32x4_t* __restrict__ xh)
 {
     const int wcol = (blockIdx.x * 256 + (threadIdx.x & ~63)) * 4;      // the wave's first column
     const int col = wcol + (threadIdx.x & 63);
     const int g = blockIdx.y;                                           // 8-row group: kb = g / 2, kh = g % 2
     if (wcol > N) return;
+    // a capacity layout (n_valid, a device count): columns [nv, N) are filler no conv reads -- neither loaded nor converted
+    const int nv = n_valid ? min(max(*n_valid, 0), N) : N;
+    if (wcol >= nv && wcol + 255 < N) return;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)(((unsigned)(K - 1) * ldx + N) * 4u), 0x00020000);
     float v[8][4];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const int k = g * 8 + r;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) v[r][c] = buf_load1(rs, (k < K && col + 64 * c < N) ? (unsigned)(k * ldx + col + 64 * c) * 4u : OOB, 0);
+        for (int c = 0; c < 4; ++c) v[r][c] = buf_load1(rs, (k < K && col + 64 * c < nv) ? (unsigned)(k * ldx + col + 64 * c) * 4u : OOB, 0);
     }
     const size_t NX = (size_t)N + 1;
     const size_t base = ((size_t)(g >> 1) * 4 + (g & 1)) * NX + col;    // plane p*2 + kh of k-block kb
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         if (col + 64 * c > N) break;                                    // (column N itself is written: the zero column)
+        if (col + 64 * c >= nv && col + 64 * c < N) continue;
         float t[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
@@ -505,10 +510,11 @@ extern "C" size_t as_split_f16x2_bytes(int K, int N)
     return (size_t)as_kbx(K) * 4 * ((size_t)N + 1) * 16;
 }
 
-int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, float slope, uint16_t* xh, hipStream_t stream)
+int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, float slope, uint16_t* xh, hipStream_t stream,
+                          const int32_t* n_valid)
 {
     if ((double)K * ldx * 4.0 >= 2147483648.0) return AS_EINVAL;        // 32-bit offsets in the buffer descriptor
-    hipLaunchKernelGGL(split_f16x2_kernel, dim3(as_cdiv(N + 1, 1024), 2 * as_kbx(K)), dim3(256), 0, stream, x, ldx, K, N, lrelu, slope,
+    hipLaunchKernelGGL(split_f16x2_kernel, dim3(as_cdiv(N + 1, 1024), 2 * as_kbx(K)), dim3(256), 0, stream, x, ldx, K, N, n_valid, lrelu, slope,
                        reinterpret_cast<u32x4_t*>(xh));
     AS_CHECK_LAUNCH();
     return AS_OK;
@@ -516,11 +522,17 @@ int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, floa
 
 extern "C" int as_split_f16x2_f32(const float* x, int ldx, int K, int N, int in_act, float in_slope, uint16_t* xh, as_stream_t stream)
 {
+    return as_split_f16x2_cap_f32(x, ldx, K, N, nullptr, in_act, in_slope, xh, stream);
+}
+
+extern "C" int as_split_f16x2_cap_f32(const float* x, int ldx, int K, int N, const int32_t* n_valid, int in_act, float in_slope, uint16_t* xh,
+                                      as_stream_t stream)
+{
     if (!x || !xh || K <= 0 || N < 0 || ldx < N || (in_act != 0 && in_act != 2) || !(fabsf(in_slope) <= 3.0e38f)) return AS_EINVAL;
     if ((reinterpret_cast<uintptr_t>(xh) & 15) != 0) return AS_EINVAL;
     if (N == 0) return AS_OK;
     AsProfScope prof__(AS_CLS_OTHER, 0, 8.0 * K * (double)N, (hipStream_t)stream);
-    return as_split_f16x2_launch(x, ldx, K, N, in_act == 2, in_slope, xh, (hipStream_t)stream);
+    return as_split_f16x2_launch(x, ldx, K, N, in_act == 2, in_slope, xh, (hipStream_t)stream, n_valid);
 }
 
 // host-side weight preparation (see the header)

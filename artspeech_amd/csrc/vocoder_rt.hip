@@ -3,7 +3,9 @@
 // fold, ConvTranspose1d -> 3-tap phase conv, per-row biases, the fp32 conv_post row, the GEMM's weight images) and orders the launches
 // of vocoder.hip / respair.hip / conv_gemm*.hip -- the sequence artspeech_amd/vocoder.py::Generator.forward_packed issues operator by
 // operator, decision for decision.  ONE sequence (generator()) serves two passes: count (as_vocoder_workspace_bytes: the arena only adds
-// up, nothing is launched) and run (kernels are enqueued; nothing is allocated, nothing synchronises once the geometry's tables exist).
+// up, nothing is launched) and run (kernels are enqueued; nothing is allocated, nothing synchronises once the geometry's tables exist) --
+// and two kinds of geometry: lengths the host knows (as_vocoder_forward: layouts cached in the plan) and lengths that exist on the device
+// only (as_vocoder_forward_cap: capacity layouts whose tables lie in the workspace and are rewritten by every call's geometry launch).
 #include "common.h"
 #include "conv_gemm.h"
 #include "runtime.h"
@@ -248,8 +250,52 @@ struct Seq {
         }
         return L;
     }
+    // Capacity layouts (as_vocoder_forward_cap): rate i of {1, u0, u0 u1, ...} has cap * rate columns of ROOM; widths, offsets, column
+    // descriptors and the valid count live in the WORKSPACE (AsVocGeo's two flat tables) and are written by the call's own geometry
+    // launch -- nothing is cached, uploaded or allocated, so every call can be captured.  The Lay objects live as long as this pass.
+    std::vector<std::unique_ptr<Lay>> caps;
+    AsVocGeo geo;
+    const Lay* cap_lays(int B, int cap, int max_len)
+    {
+        const as_vocoder_cfg& h = v.cfg;
+        memset(&geo, 0, sizeof(geo));
+        geo.B = B; geo.cap = cap; geo.max_len = max_len; geo.n_rates = h.n_stages + 1;
+        long long rate = 1, cols = 0;
+        for (int i = 0; i <= h.n_stages; ++i) {
+            if (i) rate *= h.upsample_rates[i - 1];
+            if ((double)rate * cap > 2147483647.0 || (double)rate * max_len > (double)AS_META_MAX_W) { fail(AS_EINVAL); return nullptr; }
+            geo.rate[i] = (int32_t)rate;
+            geo.meta_start[i] = cols;
+            cols += rate * cap;
+        }
+        int32_t* tab = static_cast<int32_t*>(raw_alloc((size_t)geo.n_rates * (2 * B + 2) * sizeof(int32_t)));
+        uint64_t* meta = static_cast<uint64_t*>(raw_alloc((size_t)cols * sizeof(uint64_t)));
+        if (rc) return nullptr;
+        geo.tab = tab;
+        geo.meta = reinterpret_cast<unsigned long long*>(meta);
+        for (int i = 0; i < geo.n_rates; ++i) {
+            auto u = std::make_unique<Lay>();
+            u->dyn = true; u->dyn_kind = i; u->dyn_B = B; u->cap1 = cap;
+            u->B = B;
+            u->N = geo.rate[i] * cap;
+            u->max_w = geo.rate[i] * max_len;
+            if (run) {
+                u->d_w = tab + (size_t)i * (2 * B + 2);
+                u->d_off = u->d_w + B;
+                u->d_nvalid = u->d_w + 2 * B + 1;
+                u->d_meta = meta + geo.meta_start[i];
+            }
+            caps.push_back(std::move(u));
+        }
+        return caps[0].get();
+    }
     const Lay* scaled(const Lay* L, int k)
     {
+        if (L->dyn) {
+            const size_t i = (size_t)L->dyn_kind + 1;
+            if (i >= caps.size() || (long)caps[i]->N != (long)L->N * k) { fail(AS_EINVAL); return nullptr; }
+            return caps[i].get();
+        }
         std::vector<int> w(L->w);
         for (int& x : w) {
             if ((double)x * k > (double)AS_META_MAX_W) { fail(AS_EINVAL); return nullptr; }
@@ -308,16 +354,19 @@ void conv(Seq& c, const ConvW& w, const float* X, int ldx, const uint16_t* xh, i
     c.off = mark;                                                       // (scratch of this launch only: the stream orders the next user behind it)
     if (!c.go()) return;
     a.meta = lay->d_meta;
+    a.n_valid = lay->d_nvalid;                                          // (a capacity layout: the columns behind the utterances are filler)
     RUN(c, as_conv_gemm_f32(&a, c.s));
 }
 
 // Generator.forward (Vocoder/vocoder.py:101-113) on packed frames: the launch sequence of artspeech_amd/vocoder.py::forward_packed
-void generator(Seq& c, const std::vector<int>& lens, const as_vocoder_io& io)
+// `lay`: the mel-rate layout -- Seq::lay (known lengths) or Seq::cap_lays (a capacity; lay->d_nvalid is then the device's valid count and
+// every launch below is sized by the room, works on the valid columns and leaves the filler alone -- but for the last kernel, which
+// writes the output's filler as 0)
+void generator(Seq& c, const Lay* lay, const as_vocoder_io& io)
 {
     const as_vocoder& v = c.v;
     const as_vocoder_cfg& h = v.cfg;
     const int nst = h.n_stages, nk = h.n_stacks, nd = h.n_dilations, c0 = h.upsample_initial_channel;
-    const Lay* lay = c.lay(lens);
     if (!lay) return;
     if (c.run && io.ld_mel < lay->N) { c.fail(AS_EINVAL); return; }
     // what one stage hands to the next -- fp32 activations, or LeakyReLU of them as the next ConvTranspose1d's operand image -- lives in
@@ -370,7 +419,7 @@ void generator(Seq& c, const std::vector<int>& lens, const as_vocoder_io& io)
             x = z;
         } else {
             x = c.f32(cout, N);
-            RUN(c, as_interleave_phases_f32(z, lay->N, v.ups_bias[i], cout, u, lay->N, x, N, c.s));
+            RUN(c, as_interleave_phases_cap_f32(z, lay->N, v.ups_bias[i], cout, u, lay->N, lay->d_nvalid, x, N, c.s));
         }
         lay = lay_up;
         char* const out_slot = slot[(i + 1) & 1];
@@ -407,7 +456,7 @@ void generator(Seq& c, const std::vector<int>& lens, const as_vocoder_io& io)
         // result to the next one as an image (ConvGemmArgs.Yh / yh_lrelu)
         outs[2] = c.f32(cout, N);
         uint16_t* xh = c.image(cout, N);
-        RUN(c, as_split_f16x2_f32(x, N, cout, N, ACT_LRELU, LRELU_SLOPE, xh, c.s));
+        RUN(c, as_split_f16x2_cap_f32(x, N, cout, N, lay->d_nvalid, ACT_LRELU, LRELU_SLOPE, xh, c.s));
         uint16_t* img[3] = {c.image(cout, N), c.image(cout, N), c.image(cout, N)};
         float* tmp[2] = {c.f32(cout, N), c.f32(cout, N)};
         for (int j = 0; j < nk; ++j) {
@@ -430,25 +479,26 @@ void generator(Seq& c, const std::vector<int>& lens, const as_vocoder_io& io)
             }
         }
         if (image_out) {
-            RUN(c, as_mean3_image_f32(outs[0], outs[1], outs[2], N, cout, N, LRELU_SLOPE, reinterpret_cast<uint16_t*>(out_slot), c.s));
+            RUN(c, as_mean3_image_cap_f32(outs[0], outs[1], outs[2], N, cout, N, lay->d_nvalid, LRELU_SLOPE, reinterpret_cast<uint16_t*>(out_slot), c.s));
             x = nullptr;
             xi = reinterpret_cast<const uint16_t*>(out_slot);
         } else {
             x = reinterpret_cast<float*>(out_slot);
-            RUN(c, as_mean3_f32(outs[0], outs[1], outs[2], N, cout, N, x, N, c.s));
+            RUN(c, as_mean3_cap_f32(outs[0], outs[1], outs[2], N, cout, N, lay->d_nvalid, x, N, c.s));
         }
     }
     if (c.rc) return;
     // conv_post: LeakyReLU(0.01) -> one output row -> tanh, and the 16-bit samples in the same pass
     const int C = c0 >> nst, N = lay->N;
     if (v.post32) {
-        RUN(c, as_conv_post_pcm_f32(x, N, C, N, v.post32, v.post.bias, v.post_k, POST_SLOPE, 1, lay->d_meta, io.wav, io.pcm, c.s));
+        RUN(c, as_conv_post_pcm_cap_f32(x, N, C, N, v.post32, v.post.bias, v.post_k, POST_SLOPE, 1, lay->d_meta, lay->d_nvalid, io.wav, io.pcm, c.s));
     } else {
         float* wav = io.wav ? io.wav : c.f32(1, N);
         ConvOpt o;
         o.bias = v.post.bias; o.in_act = ACT_LRELU; o.in_slope = POST_SLOPE; o.act = ACT_TANH;
         conv(c, v.post, x, N, nullptr, C, lay, wav, o);
-        if (io.pcm) RUN(c, as_pcm16_launch(wav, N, io.pcm, c.s));
+        // (under a capacity the GEMM stores nothing for the filler: this pass writes the zeros there, into wav too)
+        if (io.pcm || lay->d_nvalid) RUN(c, as_pcm16_launch(wav, N, lay->d_nvalid, lay->d_nvalid && io.wav ? io.wav : nullptr, io.pcm, c.s));
     }
 }
 
@@ -464,9 +514,36 @@ bool lens_ok(const as_vocoder* v, int B, const int32_t* lens, std::vector<int>* 
 size_t count(const as_vocoder* v, as_plan* p, const std::vector<int>& lens, const as_vocoder_io& io, int* rc)
 {
     Seq c{*v, *p, nullptr, nullptr, 0, 0, 0, false};
-    generator(c, lens, io);
+    generator(c, c.lay(lens), io);
     *rc = c.rc;
     return c.rc ? 0 : c.peak + 256;
+}
+
+// the capacity form: the tables at the head of the arena, the geometry launch, then the same sequence
+void generator_cap(Seq& c, int B, const as_vocoder_cap& g, const as_vocoder_io& io)
+{
+    const Lay* lay = c.cap_lays(B, g.cap, g.max_len > 0 ? g.max_len : g.cap);
+    if (!lay) return;
+    if (c.go()) {
+        c.geo.off = g.off; c.geo.mult = g.mult; c.geo.sample_off = g.sample_off;
+        c.geo.status = as_status_words_device();
+        RUN(c, as_vocoder_cap_geometry_launch(c.geo, c.s));
+    }
+    generator(c, lay, io);
+}
+
+size_t count_cap(const as_vocoder* v, as_plan* p, int B, const as_vocoder_cap& g, const as_vocoder_io& io, int* rc)
+{
+    Seq c{*v, *p, nullptr, nullptr, 0, 0, 0, false};
+    generator_cap(c, B, g, io);
+    *rc = c.rc;
+    return c.rc ? 0 : c.peak + 256;
+}
+
+bool cap_ok(const as_vocoder* v, int B, int cap, int max_len)
+{
+    if (!v || B < 1 || B > 65535 || cap < 1 || max_len < 0 || max_len > cap) return false;
+    return (double)v->hop * (max_len > 0 ? max_len : cap) <= (double)AS_META_MAX_W && (double)v->hop * cap <= 2147483647.0;
 }
 
 }  // namespace
@@ -550,7 +627,40 @@ extern "C" int as_vocoder_forward(const as_vocoder* v, as_plan* p, int B, const 
         if (rc != AS_OK) return rc;
         if (need > ws_bytes) return (int)AS_ENOSPC;
         Seq c{*v, *p, s, static_cast<char*>(ws), ws_bytes, 0, 0, true};
-        generator(c, lens, *io);
+        generator(c, c.lay(lens), *io);
+        return c.rc;
+    });
+}
+
+extern "C" size_t as_vocoder_cap_workspace_bytes(const as_vocoder* v, as_plan* p, int B, int cap, int max_len)
+{
+    if (!p || !cap_ok(v, B, cap, max_len)) return 0;
+    size_t n = 0;
+    const as_vocoder_io io = {nullptr, 0, nullptr, nullptr};
+    const as_vocoder_cap g = {nullptr, 1, cap, max_len, nullptr};
+    (void)abi([&] { int rc; n = count_cap(v, p, B, g, io, &rc); return rc; });
+    return n;
+}
+
+extern "C" int as_vocoder_forward_cap(const as_vocoder* v, as_plan* p, int B, const as_vocoder_cap* cap, const as_vocoder_io* io, void* ws,
+                                      size_t ws_bytes, as_stream_t stream)
+{
+    if (!p || !cap || !io || !io->mel || (!io->wav && !io->pcm) || !cap->off || cap->mult < 1 || !cap_ok(v, B, cap->cap, cap->max_len))
+        return AS_EINVAL;
+    if (io->ld_mel < cap->cap) return AS_EINVAL;
+    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255) != 0 || (io->pcm && (reinterpret_cast<uintptr_t>(io->pcm) & 1) != 0)) return AS_EINVAL;
+    return abi([&] {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (as_status_peek()) return (int)AS_EDEVICE;                    // sticky until as_device_status(1)
+        // a workspace too small is refused before anything is launched
+        int rc = AS_OK;
+        as_vocoder_io q = *io;
+        q.wav = nullptr; q.pcm = nullptr;
+        const size_t need = count_cap(v, p, B, *cap, q, &rc);
+        if (rc != AS_OK) return rc;
+        if (need > ws_bytes) return (int)AS_ENOSPC;
+        Seq c{*v, *p, s, static_cast<char*>(ws), ws_bytes, 0, 0, true};
+        generator_cap(c, B, *cap, *io);
         return c.rc;
     });
 }

@@ -234,7 +234,7 @@ class ArtSpeech:
         return table, torch.tensor(idx, dtype=torch.int32)
 
     @torch.no_grad()
-    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False):
+    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed, 24 kHz) reference wave on: log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator.  Returns the samples (mel frames if no vocoder is attached).
         Loading / trimming / resampling the file (librosa, test.py:99-106) and espeak stay with the caller."""
@@ -250,6 +250,10 @@ class ArtSpeech:
             mels = [mel[b, :, :n] for b, n in enumerate(lens)]
         fn = self.synthesis_wav if self.generator is not None else self.synthesis_mel
         kw = {"pcm16": True} if pcm16 and self.generator is not None else {}
+        if frame_cap is not None:
+            if self.generator is None:
+                raise RuntimeError("frame_cap runs the acoustic model and the generator as one chain: attach_vocoder(h, checkpoint, runtime=True) first")
+            kw["frame_cap"] = frame_cap
         out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody, **kw)
         return out[0] if single and out.dim() > 1 and self.generator is not None else out
 
@@ -264,17 +268,107 @@ class ArtSpeech:
         return self.generator
 
     @torch.no_grad()
-    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False):
+    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
+                      frame_cap=None):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
-        generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the generator's last kernel."""
+        generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the generator's last kernel.
+        frame_cap=N (predicted durations, a runtime vocoder): room for N half-rate frames, all utterances together -- the acoustic model
+        (forward_packed(frame_cap=N)) hands its device frame_off and mel straight to the generator (forward_packed_cap) on the same
+        stream: no host value is read between the tokens and the samples, then ONE copy brings the sample offsets and the samples back.
+        More frames than room: HipLibraryError (AS_STATUS_CAPACITY)."""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         single = isinstance(phonemes, str)
+        if frame_cap is not None:
+            if forced_durations is not None:
+                raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
+            out = self._synthesis_wav_cap(phonemes, ref_mel, features, voice, prosody, pcm16, int(frame_cap))
+            return out[0] if single else out
         mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody)
         lens = self._last_frames
         wav = (self.generator(mel, lengths=lens, pcm16=True) if pcm16 else self.generator(mel, lengths=lens))[:, 0]
         return wav[0] if single else wav
+
+    def packed_inputs(self, phonemes, ref_mel=None, features=None, voice=None, prosody=None):
+        """The keyword arguments of ArtsSpeech.forward_packed for these utterances (what ArtsSpeech.forward builds before the model call):
+        packed device tokens and either the packed reference features or the voice table; prosody rows on the device."""
+        if (voice is None) == (ref_mel is None):
+            raise ValueError("synthesis needs exactly one of ref_mel and voice")
+        net = self.model.ArtsSpeech
+        dev = net.device
+        if isinstance(phonemes, str):
+            phonemes, ref_mel = [phonemes], None if ref_mel is None else [ref_mel]
+            if features is not None:
+                features = [features]
+        ids = [torch.LongTensor(self.textcleaner(p)) for p in phonemes]
+        B, tl = len(ids), [len(i) for i in ids]
+        text = torch.zeros(B, max(tl), dtype=torch.long)
+        for b in range(B):
+            text[b, : tl[b]] = ids[b]
+        kw = dict(tok_lens=tl, mel_p=None, f0_p=None, ema_p=None, ref_lens=None)
+        with torch.cuda.device(dev):
+            kw["tok"] = models._dev(models._pack_tokens(text, tl, net.rt.cfg.n_token), dev, torch.int32)
+            if prosody is not None:
+                kw["prosody"] = Prosody.rows(prosody, B, net).to(dev)
+            if voice is not None:
+                table, vidx = self._voice_table(voice, B)
+                kw["voice"], kw["voice_idx"] = table, vidx.to(dev)        # (on the device already: a captured call copies nothing)
+                return kw
+            ml = [int(m.shape[-1]) for m in ref_mel]
+            tmax = max(ml)
+            mels = torch.zeros(B, ref_mel[0].shape[0], tmax)
+            for b in range(B):
+                mels[b, :, : ml[b]] = torch.as_tensor(ref_mel[b])
+            feats = None
+            if features is not None:
+                f0 = None if any(f is None for f, _ in features) else torch.zeros(B, 1, tmax)
+                ema = torch.zeros(B, 10, tmax)
+                for b, (f, e) in enumerate(features):
+                    if f0 is not None:
+                        f0[b, :, : f.shape[-1]] = torch.as_tensor(f).reshape(1, -1)
+                    ema[b, :, : e.shape[-1]] = torch.as_tensor(e)
+                feats = (f0, ema)
+            f0_raw, ema_raw = net.style_encoder._extract(mels, feats, ml)
+            kw["mel_p"] = models.pack(mels.to(dev), ml)
+            kw["f0_p"] = models.pack(f0_raw.to(dev).reshape(B, 1, -1), ml)
+            kw["ema_p"] = models.pack(ema_raw.to(dev), ml)
+            kw["ref_lens"] = ml
+        return kw
+
+    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None):
+        """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
+        then the capacity vocoder on its frame_off and mel.  `inputs` = packed_inputs(...).  Every call with the same inputs dict reuses
+        the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
+        with other token / voice / prosody contents of the same geometry.  -> (samples [300 * 2 frame_cap], sample_off [B + 1]), both on the
+        device."""
+        if self.generator is None or not self.generator.runtime:
+            raise RuntimeError("frame_cap needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
+        net = self.model.ArtsSpeech
+        kw = {k: v for k, v in inputs.items() if k != "_out"}
+        with torch.cuda.device(self.device):
+            res = net.forward_packed(kw.pop("tok"), kw.pop("tok_lens"), kw.pop("mel_p"), kw.pop("f0_p"), kw.pop("ema_p"), kw.pop("ref_lens"),
+                                     frame_cap=frame_cap, out=inputs.setdefault("_out", {}), **kw)
+            got = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len, pcm=pcm16, wav=not pcm16)
+        return (got[2] if pcm16 else got[0][0]), got[1]
+
+    def _synthesis_wav_cap(self, phonemes, ref_mel, features, voice, prosody, pcm16, frame_cap):
+        from . import _lib
+        inputs = self.packed_inputs(phonemes, ref_mel, features, voice, prosody)
+        samples, sample_off = self.chain_cap(inputs, frame_cap, pcm16=pcm16)
+        with torch.cuda.device(self.device):
+            off = sample_off.cpu().tolist()                                 # the one synchronisation: offsets, then the samples
+            if _lib.lib().as_device_status(0):
+                raise _lib.HipLibraryError(f"synthesis_wav(frame_cap={frame_cap}) failed: a kernel reported {_lib.device_status()} "
+                                           "(as_device_status); results since then are invalid")
+            host = samples[: off[-1]].cpu()
+        hop = self.generator.hop
+        lens = [off[b + 1] - off[b] for b in range(len(off) - 1)]
+        self._last_frames = [n // hop for n in lens]
+        out = torch.zeros(len(lens), max(max(lens), 1), dtype=host.dtype)
+        for b, n in enumerate(lens):
+            out[b, :n] = host[off[b]: off[b + 1]]
+        return out
 
     @torch.no_grad()
     def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None):

@@ -96,7 +96,7 @@ class Generator:
         self.device = _need_gpu(device if device is not None else "cuda")
         self.W = None
         self.runtime = bool(runtime)
-        self._voc = self._plan = self._ws = None
+        self._voc = self._plan = self._ws = self._ws_cap = None
 
     def __del__(self):
         try:
@@ -111,7 +111,7 @@ class Generator:
             L.as_plan_destroy(self._plan)
         if self._voc:
             L.as_vocoder_destroy(self._voc)
-        self._voc = self._plan = self._ws = None
+        self._voc = self._plan = self._ws = self._ws_cap = None
 
     # ------------------------------------------------------------------ the library's generator (runtime=True)
     def runtime_cfg(self):
@@ -172,6 +172,40 @@ class Generator:
                    "as_vocoder_forward")
         lay_w = lay.scaled(self.hop)
         return (out_w, lay_w, out_p) if pcm else (out_w, lay_w)
+
+    def forward_packed_cap(self, mel_p, off, mult, cap, max_len=None, pcm=False, wav=True):
+        """The generator when the frame counts exist on the device only (as_vocoder_forward_cap; runtime=True): mel_p [80][>= cap] packed
+        from column 0, `off` a DEVICE int32 [B + 1] in units of `mult` mel frames (a forward_packed(frame_cap=)'s frame_off: mult = 2),
+        `cap` mel frames of room for all utterances together, max_len the frames one utterance may have (None: cap).  No host value is
+        read, nothing synchronises: the call can be captured with whatever produced `off` and `mel_p`.  Returns (wav [1][300 cap] or None,
+        sample_off device int32 [B + 1]) and, with pcm=True, the int16 samples [300 cap]: utterance b is [sample_off[b], sample_off[b + 1]),
+        the samples behind the last utterance are 0.  More frames than room raises the AS_STATUS_CAPACITY bit (as_device_status)."""
+        if not self.runtime:
+            raise ValueError("forward_packed_cap needs Generator(runtime=True)")
+        if self._voc is None:
+            raise RuntimeError("no weights loaded: call load_state_dict first")
+        if not (wav or pcm):
+            raise ValueError("forward_packed_cap: at least one of wav and pcm")
+        if off.dtype != torch.int32 or not off.is_cuda or not off.is_contiguous():
+            raise ValueError("forward_packed_cap: off must be a contiguous int32 tensor on the GPU")
+        L = _lib.lib()
+        B, cap, max_len = off.numel() - 1, int(cap), int(max_len or 0)
+        with torch.cuda.device(self.device):
+            need = L.as_vocoder_cap_workspace_bytes(self._voc, self._plan, B, cap, max_len)
+            if need == 0:
+                raise _lib.HipLibraryError("as_vocoder_cap_workspace_bytes: invalid capacity (max_len > cap, or an utterance beyond AS_META_MAX_W samples?)")
+            if self._ws_cap is None or self._ws_cap.numel() < need:
+                self._ws_cap = torch.empty(need, dtype=torch.uint8, device=self.device)
+            n = cap * self.hop
+            out_w = torch.empty((1, n), dtype=torch.float32, device=self.device) if wav else None
+            out_p = torch.empty(n, dtype=torch.int16, device=self.device) if pcm else None
+            sample_off = torch.empty(B + 1, dtype=torch.int32, device=self.device)
+            io, g = _lib.VocoderIO(), _lib.VocoderCap()
+            io.mel, io.ld_mel, io.wav, io.pcm = ops._p(mel_p), ops._ld(mel_p), ops._p(out_w), ops._p(out_p)
+            g.off, g.mult, g.cap, g.max_len, g.sample_off = off.data_ptr(), int(mult), cap, max_len, sample_off.data_ptr()
+            _lib.check(L.as_vocoder_forward_cap(self._voc, self._plan, B, ctypes.byref(g), ctypes.byref(io), self._ws_cap.data_ptr(),
+                                                self._ws_cap.numel(), _lib.stream()), "as_vocoder_forward_cap")
+        return (out_w, sample_off, out_p) if pcm else (out_w, sample_off)
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd, strict=False):

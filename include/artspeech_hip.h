@@ -248,6 +248,10 @@ size_t as_conv_gemm_workspace_bytes(const ConvGemmArgs* args_host);
  * feed every conv reading the same activations.  xh: 16-byte aligned, as_split_f16x2_bytes(K, N) bytes. */
 size_t as_split_f16x2_bytes(int K, int N);
 int as_split_f16x2_f32(const float* x, int ldx, int K, int N, int in_act, float in_slope, uint16_t* xh, as_stream_t stream);
+/* The same under a capacity layout: *n_valid (a DEVICE int, NULL = N) leading columns are valid; columns [*n_valid, N) are filler that no
+ * conv reads -- they are neither loaded nor converted (what xh holds there is left alone); the zero column N is written. */
+int as_split_f16x2_cap_f32(const float* x, int ldx, int K, int N, const int32_t* n_valid, int in_act, float in_slope, uint16_t* xh,
+                           as_stream_t stream);
 /* Host-side weight preparation (no GPU work): w fp32 [G][Cout][Cin][T] (a folded nn.Conv / nn.Linear weight; T = product of
  * the kernel dims) -> wh [G][T][KBx][4][Cout][8] fp16 in HOST memory (as_prep_weight_f16x2_bytes(G, Cout, Cin, T) bytes),
  * scaled by *scale_out = the power of two that puts max |w| in [2^13, 2^14).  Pass ConvGemmArgs.acc_scale = 1 / *scale_out. */
@@ -566,6 +570,30 @@ typedef struct AsResPairArgs {
                                          * x[ch][col] = z[(col % x_u) * C + ch][col / x_u] + x_bias[ch]: as_interleave_phases_f32 folded into the read */
 } AsResPairArgs;
 int as_respair_f32(const AsResPairArgs* a, as_stream_t stream);
+/* The glue kernels under a capacity layout (as_vocoder_forward_cap): N is room, *n_valid (a DEVICE int; NULL = N: exactly the functions
+ * above) the leading columns that hold utterances.  Filler columns are neither read nor written -- except by conv_post, the last kernel,
+ * which stores 0 for them (y and pcm in [*n_valid, N)): a NaN in uninitialised filler reaches no result and raises nothing.
+ * as_interleave_phases_cap_f32 counts INPUT columns (of Nin). */
+int as_interleave_phases_cap_f32(const float* z, int ldz, const float* bias, int C, int u, int Nin, const int32_t* n_valid, float* y, int ldy,
+                                 as_stream_t stream);
+int as_mean3_cap_f32(const float* a, const float* b, const float* c, int ld, int C, int N, const int32_t* n_valid, float* y, int ldy,
+                     as_stream_t stream);
+int as_mean3_image_cap_f32(const float* a, const float* b, const float* c, int ld, int C, int N, const int32_t* n_valid, float slope,
+                           uint16_t* xh, as_stream_t stream);
+int as_conv_post_pcm_cap_f32(const float* x, int ldx, int C, int N, const float* w, const float* bias, int k, float in_slope, int tanh_out,
+                             const uint64_t* meta, const int32_t* n_valid, float* y, int16_t* pcm, as_stream_t stream);
+/* The generator's geometry tables from DEVICE offsets, one launch (csrc/vocoder.hip; what as_vocoder_forward_cap runs first).
+ * off int32 [B + 1] (off[0] = 0, ascending) counts units of `mult` mel frames; cap = mel frames of room for all utterances together;
+ * max_len = the mel frames one utterance may have (0 = cap); rates_host [n_rates <= 9] = columns per mel frame of every layout (1, then
+ * the running products of the upsample rates: 1, 10, 50, 150, 300).  With o_b = min(off[b] * mult, cap), rate r writes
+ *     tab  int32 [n_rates][2 B + 2]:  w[b] = r (o_{b+1} - o_b),  off_r[b] = r o_b (B + 1 entries),  n_valid = r o_B
+ *     meta uint64 [cap * sum r]:      rate i's table starts at cap * (r_0 + ... + r_{i-1}); column off_r[b] + j = AS_META_PACK(0, j, 1, w[b]);
+ *                                     the descriptors of the filler [n_valid, r cap) are left alone
+ * and sample_off (optional, [B + 1]) = off_r of the last rate.  off[B] * mult > cap or an utterance of more than max_len frames raises
+ * AS_STATUS_CAPACITY (the layout is cut at cap: nothing is written past it); w[b] > AS_META_MAX_W raises AS_STATUS_BAD_LAYOUT and that
+ * utterance's columns get AS_META_PACK(0, 0, 1, 1).  AS_EINVAL: B < 1, mult < 1, cap < 1, max_len > cap, r cap >= 2^31. */
+int as_vocoder_cap_geometry(const int32_t* off, int B, int mult, int cap, int max_len, int n_rates, const int32_t* rates_host, int32_t* tab,
+                            uint64_t* meta, int32_t* sample_off, as_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Module-level entry points: the acoustic model behind an opaque handle.  A C / C++ host runs
@@ -807,6 +835,27 @@ typedef struct as_vocoder_io {
 size_t as_vocoder_workspace_bytes(const as_vocoder* v, as_plan* p, int B, const int32_t* lens_host);
 int as_vocoder_forward(const as_vocoder* v, as_plan* p, int B, const int32_t* lens_host, const as_vocoder_io* io,
                        void* ws, size_t ws_bytes, as_stream_t stream);
+/* The same generator when the frame counts exist on the DEVICE only (predicted durations: as_forward_io.frame_cap): the launches are
+ * sized by a capacity, one kernel derives every geometry table from `off` on the device (as_vocoder_cap_geometry, into the workspace), the
+ * convolutions run under ConvGemmArgs.n_valid and the glue kernels under their valid counts.  Nothing is read back, nothing is uploaded,
+ * the plan is not touched and NO call synchronises or allocates: every call -- the first included -- can be captured into a hipGraph and
+ * replayed with other contents of off and mel, other lengths included.  Utterance b's samples are [sample_off[b], sample_off[b + 1]) =
+ * hop * mult * off; wav / pcm in [hop * total, hop * cap) are written as 0 by the last kernel (no earlier request's samples remain).
+ * More frames than cap, or an utterance longer than max_len: AS_STATUS_CAPACITY (as_device_status) -- the layout is cut at the
+ * capacity, nothing is stored out of bounds, and that call's samples are not to be used.  Filler (mel columns past the total, the
+ * workspace) may hold anything, NaNs included.
+ * AS_EINVAL: mult < 1, cap < 1, max_len > cap, ld_mel < cap, hop * max_len > AS_META_MAX_W, both outputs NULL; AS_ENOSPC before anything
+ * is launched; AS_EDEVICE while a status bit is set. */
+typedef struct as_vocoder_cap {
+    const int32_t* off;      /* DEVICE [B + 1], off[0] = 0: as_forward_io.frame_off, or prefix sums of mel lengths */
+    int32_t mult;            /* mel frames per unit of off (2 for frame_off, 1 for mel lengths) */
+    int32_t cap;             /* mel frames of room, all utterances: ld_mel >= cap, wav / pcm hold hop * cap samples */
+    int32_t max_len;         /* mel frames the longest utterance may have (0 = cap): sizes the per-utterance grids */
+    int32_t* sample_off;     /* optional DEVICE out [B + 1]: utterance b = samples [sample_off[b], sample_off[b + 1]) */
+} as_vocoder_cap;
+size_t as_vocoder_cap_workspace_bytes(const as_vocoder* v, as_plan* p, int B, int cap, int max_len);
+int as_vocoder_forward_cap(const as_vocoder* v, as_plan* p, int B, const as_vocoder_cap* cap, const as_vocoder_io* io,
+                           void* ws, size_t ws_bytes, as_stream_t stream);
 /* Host helper (no GPU work): ConvTranspose1d weight wt [Cin][Cout][2u] (stride u, padding u/2 + u%2) -> the 3-tap conv
  * wc [u*Cout][Cin][3] whose output rows are (phase r, channel m), row r Cout + m:
  *     y[m][u q + r] = sum_c sum_d wc[r Cout + m][c][d] x[c][q + d - 1]
