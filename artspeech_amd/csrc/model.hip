@@ -6,7 +6,8 @@
 //   as_forward_test   ArtsSpeech.forward(step="test"), models.py:356-371, batched on packed frames
 //
 // This file holds no kernels: it is the host side that orders the launches of the other files of this library, owns the
-// batch geometry tables and hands out workspace memory.  One launch sequence per module serves three passes (Pass):
+// batch geometry tables and hands out workspace memory -- through the pass context of runtime.h (arena, layout cache, device tables,
+// entry prologue), which the vocoder's runtime shares.  One launch sequence per module serves three passes (Pass):
 //   count   (as_module_workspace_bytes, on placeholder arguments: the bump allocator only adds up; on a model that as_model_create
 //           is preparing, every weight the sequence touches is built and uploaded on the way),
 //   replay  (as_forward_test_finish: the first half's allocations in the caller's workspace, to find its results; nothing launched), and
@@ -36,13 +37,6 @@ constexpr int N_HEADS = 4;      // RelTransformerEnc.py:333
 constexpr int WINDOW = 4;       // RelTransformerEnc.py:335
 constexpr int ACT_NONE = 0, ACT_RELU = 1, ACT_LRELU = 2;
 
-struct GemmW {                  // a conv / linear weight prepared for as_conv_gemm_f32
-    uint16_t* wh = nullptr;     // [G][T][KBx][4][M][8] fp16 split image
-    float* w32 = nullptr;       // [T][Kp][M] fp32 (Cin = 1: the direct kernel)
-    float scale = 1.f;
-    int T = 0, Kp = 0, M = 0, K = 0, G = 1;
-    int K2 = 0;                 // channels of the second operand whose 1x1 weights follow the taps (ConvGemmArgs.Xh2: a folded shortcut)
-};
 struct Vec {
     float* p = nullptr;
     size_t n = 0;
@@ -116,12 +110,8 @@ struct as_model {
     // a weight given as host data [G][Cout][Cin][T] (+ [G][Cout][Cin2] behind the taps), laid out and uploaded into g
     bool gemm_image(GemmW& g, const float* w, int G, int Cout, int Cin, int T, const float* w2 = nullptr, int Cin2 = 0) const
     {
-        g.T = T; g.K = Cin; g.Kp = (Cin + 15) / 16 * 16; g.M = Cout; g.G = G; g.K2 = Cin2;
-        const size_t bytes = as_prep_weight_f16x2_sc_bytes(G, Cout, Cin, T, Cin2);
-        std::vector<uint16_t> img(bytes / 2);
-        if (as_prep_weight_f16x2_sc_host(w, w2, G, Cout, Cin, T, Cin2, img.data(), &g.scale) != AS_OK) { fail_once(AS_EINVAL); return false; }
-        g.wh = static_cast<uint16_t*>(pool.alloc(bytes));
-        if (!g.wh || hipMemcpy(g.wh, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { fail_once((int)hipErrorOutOfMemory); return false; }
+        const int rc = asrt::gemm_image(pool, g, w, G, Cout, Cin, T, w2, Cin2);
+        if (rc != AS_OK) { fail_once(rc); return false; }
         if (Cin == 1 && G == 1) {                                          // the direct kernel's fp32 image [T][Kp][M]
             std::vector<float> w32((size_t)T * g.Kp * Cout, 0.f);
             for (int m = 0; m < Cout; ++m)
@@ -366,22 +356,10 @@ struct Sched {
     int new_queue() { q.emplace_back(); return (int)q.size() - 1; }
 };
 
-// The passes over a launch sequence (see the top of this file)
-enum class Pass {
-    Count,                        // nothing behind the arena, geometry tables stay on the host, nothing launched
-    Replay,                       // the caller's workspace, nothing launched (as_forward_test_finish: where the first half left its results)
-    Run,                          // kernels are enqueued
-};
-const char* pass_name(Pass p) { return p == Pass::Count ? "count" : (p == Pass::Run ? "run" : "replay"); }
-
-struct Ctx {
+// The acoustic model's pass over a launch sequence: the shared pass context (runtime.h: arena, layout cache, device tables) plus the
+// model, the recorded form of launches inside a Fork, the plan-resident capacity layouts and the recurrences' exchange buffer
+struct Ctx : PassCtx {
     const as_model& m;
-    as_plan& p;
-    hipStream_t s;                // the stream launches go to (a side stream inside a Fork)
-    char* base;                   // workspace (nullptr when counting)
-    size_t cap, off = 0;
-    Pass pass;
-    int rc = 0;
     std::shared_ptr<Sched> sched; // launches are being recorded (inside a Fork of a serial, merging plan)
     int cur_q = -1;
     double hint_f = 0, hint_b = 0;
@@ -402,60 +380,11 @@ struct Ctx {
         else as_prof_hint(f, b);
     }
 
+    // (s: the stream launches go to -- a side stream inside a Fork)
     Ctx(const as_model& m_, as_plan& p_, hipStream_t s_, void* ws, size_t ws_bytes, Pass pass_)
-        : m(m_), p(p_), s(s_), base(static_cast<char*>(ws)), cap(ws_bytes), pass(pass_) {}
-    void fail(int r, const char* what = nullptr, int line = 0)
-    {
-        if (!rc) {
-            rc = r;
-            if (getenv("AS_DEBUG")) fprintf(stderr, "artspeech_hip: model.hip:%d: rc %d %s\n", line, r, what ? what : "");
-        }
-    }
-    void* raw_alloc(size_t bytes)
-    {
-        const size_t o = off;
-        off += align256(bytes ? bytes : 1);
-        if (pass == Pass::Run && getenv("AS_DEBUG_ALLOC")) fprintf(stderr, "artspeech_hip: arena %p + %zu : %zu bytes\n", (void*)base, o, bytes);
-        // counting: a non-null placeholder (never dereferenced: nothing launches), so that code which branches on "is there an operand
-        // image" takes the branch the run takes (their workspace needs differ)
-        if (pass == Pass::Count) return reinterpret_cast<void*>((size_t)1 << 20);
-        if (off > cap) { fail(AS_ENOSPC); return nullptr; }
-        return base + o;
-    }
-    float* f32(size_t n) { return static_cast<float*>(raw_alloc(n * sizeof(float))); }
-    int32_t* i32(size_t n) { return static_cast<int32_t*>(raw_alloc(n * sizeof(int32_t))); }
-    uint16_t* image(int K, int N) { return static_cast<uint16_t*>(raw_alloc(as_split_f16x2_bytes(K, N > 0 ? N : 1))); }
-    bool go() const { return pass == Pass::Run && rc == 0 && m.err == 0; }
+        : PassCtx(p_, s_, ws, ws_bytes, pass_, "model.hip"), m(m_) {}
+    bool go() const { return PassCtx::go() && m.err == 0; }
 
-    // geometry (cached in the plan; device tables created on first real use: a blocking upload).  init fills a new layout (false: bad
-    // geometry); a layout is never evicted inside a call (as_plan::trim runs between calls)
-    template <class F>
-    const Lay* lay_at(std::pair<std::vector<int>, int> key, F&& init)
-    {
-        auto it = p.lays.find(key);
-        if (it == p.lays.end()) {
-            auto u = std::make_unique<Lay>();
-            if (!init(*u)) { fail(AS_EINVAL); return nullptr; }
-            it = p.lays.emplace(std::move(key), std::move(u)).first;
-        }
-        return tables(it->second.get()) ? it->second.get() : nullptr;
-    }
-    const Lay* lay(const std::vector<int>& widths, int H = 1)
-    {
-        return lay_at({widths, H}, [&](Lay& L) {
-            L.B = (int)widths.size();
-            L.H = H;
-            L.w = widths;
-            L.off.assign(L.B + 1, 0);
-            for (int b = 0; b < L.B; ++b) {
-                if (widths[b] < 0 || widths[b] > AS_META_MAX_W || H > AS_META_MAX_H) return false;
-                L.off[b + 1] = L.off[b] + H * widths[b];
-                L.max_w = std::max(L.max_w, widths[b]);
-            }
-            L.N = L.off[L.B];
-            return true;
-        });
-    }
     // capacity layout `kind` (AsDynGeo: 0 half rate, 1 mel rate, 2 / 3 the batch three times) of B utterances in cap1 half-rate columns
     const Lay* dyn_lay(int kind, int B, int cap1)
     {
@@ -468,56 +397,13 @@ struct Ctx {
             return true;
         });
     }
-    // L's device tables, made on the first run that uses L: d_w and d_off (B + 1 entries), uploaded at once (a blocking copy); a
-    // capacity layout's instead hold what every call's as_dyn_geometry_launch writes, with d_meta, d_nvalid and (kind 2) src3
-    bool tables(Lay* L)
+    const Lay* scaled(const Lay* L, int k)
     {
-        if (pass != Pass::Run || L->d_off) return true;
-        const auto i32 = [&](size_t n) { return static_cast<int32_t*>(p.pool.alloc(n * sizeof(int32_t))); };
-        int32_t *d_w = i32(L->B + 1), *d_off = i32(L->B + 1);
-        bool ok = d_w && d_off;
-        if (ok && L->dyn) {
-            L->d_meta = static_cast<uint64_t*>(p.pool.alloc((size_t)L->N * sizeof(uint64_t)));
-            L->d_nvalid = i32(1);
-            int32_t* src3 = L->dyn_kind == 2 ? i32(L->B) : nullptr;
-            ok = L->d_meta && L->d_nvalid && (L->dyn_kind != 2 || src3);
-            if (ok && src3) L->tabs["src3"] = src3;
-        } else if (ok) {
-            ok = hipMemcpy(d_w, L->w.data(), L->B * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(d_off, L->off.data(), (L->B + 1) * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-        }
-        if (!ok) { fail((int)hipErrorOutOfMemory); return false; }
-        L->d_w = d_w;
-        L->d_off = d_off;
-        return true;
+        if (!L->dyn) return PassCtx::scaled(L, k);
+        if (k != 2 || (L->dyn_kind & 1)) { fail(AS_EINVAL); return nullptr; }
+        return dyn_lay(L->dyn_kind + 1, L->dyn_B, L->cap1);
     }
-    const uint64_t* meta(const Lay* L)
-    {
-        if (!L || pass != Pass::Run) return nullptr;
-        if (L->dyn) return L->d_meta;                              // (written by the call's as_dyn_geometry_launch)
-        Lay* M = const_cast<Lay*>(L);
-        if (!M->d_meta) {
-            M->d_meta = static_cast<uint64_t*>(p.pool.alloc((size_t)std::max(L->N, 1) * sizeof(uint64_t)));
-            if (!M->d_meta) { fail((int)hipErrorOutOfMemory); return nullptr; }
-            const int r = as_make_meta(L->d_w, L->d_off, L->B, L->H, L->N, M->d_meta, s);
-            if (r != AS_OK || hipStreamSynchronize(s) != hipSuccess) { fail(r ? r : (int)hipErrorUnknown); return nullptr; }
-        }
-        return M->d_meta;
-    }
-    // a per-utterance int32 table that belongs to layout L (built and uploaded on first real use, like L's own tables)
-    template <typename F>
-    const int32_t* itable(const Lay* L, const std::string& key, F&& build)
-    {
-        if (!L || pass != Pass::Run) return nullptr;
-        Lay* M = const_cast<Lay*>(L);
-        auto it = M->tabs.find(key);
-        if (it != M->tabs.end()) return it->second;
-        const std::vector<int32_t> h = build();
-        int32_t* d = static_cast<int32_t*>(p.pool.alloc(h.size() * sizeof(int32_t)));
-        if (!d || hipMemcpy(d, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { fail((int)hipErrorOutOfMemory); return nullptr; }
-        return M->tabs[key] = d;
-    }
-    // the plan's exchange buffer for clustered recurrences (allocated and zero-filled on first real use, like the tables above)
+    // the plan's exchange buffer for clustered recurrences (allocated and zero-filled on first real use, like the layouts' tables)
     void* lstm_xchg(int n_jobs, int B, size_t* bytes)
     {
         *bytes = 0;
@@ -532,33 +418,13 @@ struct Ctx {
         *bytes = p.lstm_xchg_bytes;
         return p.lstm_xchg;
     }
-    const Lay* scaled(const Lay* L, int k)
-    {
-        if (L->dyn) {
-            if (k != 2 || (L->dyn_kind & 1)) { fail(AS_EINVAL); return nullptr; }
-            return dyn_lay(L->dyn_kind + 1, L->dyn_B, L->cap1);
-        }
-        std::vector<int> w(L->w);
-        for (int& v : w) v *= k;
-        return lay(w, L->H);
-    }
-    const Lay* halved(const Lay* L, bool h_too)                 // W -> ceil(W/2); H -> H/2 when h_too
-    {
-        std::vector<int> w(L->w);
-        for (int& v : w) v = (v + 1) / 2;
-        return lay(w, h_too ? L->H / 2 : L->H);
-    }
-    const Lay* valid_conv(const Lay* L, int K, int stride)
-    {
-        std::vector<int> w(L->w);
-        for (int& v : w) v = v >= K ? (v - K) / stride + 1 : 0;
-        return lay(w, L->H >= K ? (L->H - K) / stride + 1 : 0);
-    }
 };
 
 // (a recorded launch that play() moves to the plan's side stream: Op.side)
 static thread_local hipStream_t tl_stream_override = nullptr;
-// (recorded form: the closure copies what the call names -- argument structs and job arrays included -- and sees the stream as `c.s`)
+// runtime.h's RUN with the recorded form in front (the closure copies what the call names -- argument structs and job arrays included --
+// and sees the stream as `c.s`)
+#undef RUN
 #define RUN(c, call)                                   \
     do {                                               \
         if ((c).go()) {                                \
@@ -572,8 +438,7 @@ static thread_local hipStream_t tl_stream_override = nullptr;
                     return (call);                     \
                 };                                     \
             } else {                                   \
-                const int r__ = (call);                \
-                if (r__ != AS_OK) (c).fail(r__, #call, __LINE__); \
+                RUN_NOW(c, call);                      \
             }                                          \
         }                                              \
     } while (0)
@@ -2437,24 +2302,16 @@ size_t count_module(const as_model* m, as_plan* p, int module, const as_batch* b
         forward_b(c, A, &b, &io);
     }
     }
-    return rc || c.rc ? 0 : c.off + 256;
+    return rc || c.rc ? 0 : c.peak + 256;
 }
 
-bool misaligned(const void* ws) { return (reinterpret_cast<uintptr_t>(ws) & 255) != 0; }
-
-struct Call {                     // common prologue of the entry points; `trim`: as_plan::trim may drop layouts first
+struct Call {                     // an entry point's context behind the common prologue (runtime.h: enter)
     Ctx c;
     Call(const as_model* m, as_plan* p, void* ws, size_t bytes, as_stream_t stream, Pass pass, bool trim)
         : c(*m, *p, static_cast<hipStream_t>(stream), ws, bytes, pass)
     {
-        if (pass == Pass::Run) {
-            p->next_event = 0;
-            const int t = trim ? p->trim(static_cast<hipStream_t>(stream)) : AS_OK;
-            if (t != AS_OK) c.fail(t);
-            p->note_stream(static_cast<hipStream_t>(stream));
-            if (as_status_peek()) c.fail(AS_EDEVICE);      // a kernel of earlier work reported a failure: sticky until as_device_status(1)
-        }
-        if (misaligned(ws)) c.fail(AS_EINVAL);
+        const int r = enter(*p, c.s, ws, pass, trim);
+        if (r != AS_OK) c.fail(r);
     }
     int done(int r = AS_OK) const { return r ? r : (c.rc ? c.rc : c.m.err); }     // r: what the sequence returned
 };

@@ -2,10 +2,11 @@
 // samples out, one call.  Like model.hip this file holds no kernels: it reads the checkpoint blob, lays the weights out (weight_norm
 // fold, ConvTranspose1d -> 3-tap phase conv, per-row biases, the fp32 conv_post row, the GEMM's weight images) and orders the launches
 // of vocoder.hip / respair.hip / conv_gemm*.hip -- the sequence artspeech_amd/vocoder.py::Generator.forward_packed issues operator by
-// operator, decision for decision.  ONE sequence (generator()) serves two passes: count (as_vocoder_workspace_bytes: the arena only adds
-// up, nothing is launched) and run (kernels are enqueued; nothing is allocated, nothing synchronises once the geometry's tables exist) --
-// and two kinds of geometry: lengths the host knows (as_vocoder_forward: layouts cached in the plan) and lengths that exist on the device
-// only (as_vocoder_forward_cap: capacity layouts whose tables lie in the workspace and are rewritten by every call's geometry launch).
+// operator, decision for decision.  ONE sequence (generator()), written against runtime.h's pass context like the acoustic model's,
+// serves two passes: count (as_vocoder_workspace_bytes: the arena only adds up, nothing is launched) and run (kernels are enqueued;
+// nothing is allocated, nothing synchronises once the geometry's tables exist) -- and two kinds of geometry: lengths the host knows
+// (as_vocoder_forward: layouts cached in the plan) and lengths that exist on the device only (as_vocoder_forward_cap: capacity layouts
+// whose tables lie in the workspace and are rewritten by every call's geometry launch).
 #include "common.h"
 #include "conv_gemm.h"
 #include "runtime.h"
@@ -22,10 +23,7 @@ constexpr float LRELU_SLOPE = 0.1f;     // Vocoder/vocoder.py:8
 constexpr float POST_SLOPE = 0.01f;     // vocoder.py:111: F.leaky_relu's default
 constexpr int ACT_LRELU = 2, ACT_TANH = 3;
 
-struct ConvW {                          // a conv weight prepared for as_conv_gemm_f32 / as_respair_f32, with its bias
-    uint16_t* wh = nullptr;
-    float scale = 1.f;
-    int T = 0, Kp = 0, M = 0, K = 0;
+struct ConvW : GemmW {                  // a conv weight prepared for as_conv_gemm_f32 / as_respair_f32, with its bias
     float* bias = nullptr;
 };
 struct Step {                           // one residual step of ResBlock1: conv1 (dilated), conv2
@@ -110,15 +108,10 @@ float* upload(as_vocoder& v, const float* h, size_t n)
     return d;
 }
 
-// w fp32 [Cout][Cin][T] -> the conv GEMM's weight image on the device (as_prep_weight_f16x2_host), bias [n_bias] beside it
+// w fp32 [Cout][Cin][T] -> the conv GEMM's weight image on the device (runtime.h: gemm_image), bias [n_bias] beside it
 bool conv_w(as_vocoder& v, ConvW& g, const float* w, int Cout, int Cin, int T, const float* bias, size_t n_bias)
 {
-    g.T = T; g.K = Cin; g.Kp = (Cin + 15) / 16 * 16; g.M = Cout;
-    const size_t bytes = as_prep_weight_f16x2_bytes(1, Cout, Cin, T);
-    std::vector<uint16_t> img(bytes / 2);
-    if (!bytes || as_prep_weight_f16x2_host(w, 1, Cout, Cin, T, img.data(), &g.scale) != AS_OK) return false;
-    g.wh = static_cast<uint16_t*>(v.pool.alloc(bytes));
-    if (!g.wh || hipMemcpy(g.wh, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
+    if (gemm_image(v.pool, g, w, 1, Cout, Cin, T) != AS_OK) return false;
     g.bias = bias ? upload(v, bias, n_bias) : nullptr;
     return !bias || g.bias;
 }
@@ -186,70 +179,14 @@ int vocoder_create(const void* blob_host, size_t blob_bytes, const as_vocoder_cf
 // ------------------------------------------------------------------------------------------------------------------
 // one pass over the launch sequence
 // ------------------------------------------------------------------------------------------------------------------
-struct Seq {
+// the shared pass context (runtime.h: arena, layout cache, device tables; Pass::Count and Pass::Run) plus the generator and the capacity
+// form's workspace-resident layouts
+struct Seq : PassCtx {
     const as_vocoder& v;
-    as_plan& p;
-    hipStream_t s;
-    char* base;                         // workspace (nullptr when counting)
-    size_t cap, off = 0, peak = 0;
-    bool run;
-    int rc = 0;
-    void fail(int r) { if (!rc) rc = r; }
-    bool go() const { return run && rc == 0; }
-    void* raw_alloc(size_t bytes)
-    {
-        const size_t o = off;
-        off += align256(bytes ? bytes : 1);
-        peak = std::max(peak, off);
-        if (!run) return reinterpret_cast<void*>((size_t)1 << 20);      // counting: a placeholder, never dereferenced
-        if (off > cap) { fail(AS_ENOSPC); return nullptr; }
-        return base + o;
-    }
-    float* f32(int C, int N) { return static_cast<float*>(raw_alloc((size_t)C * std::max(N, 1) * sizeof(float))); }
-    uint16_t* image(int K, int N) { return static_cast<uint16_t*>(raw_alloc(std::max(as_split_f16x2_bytes(K, std::max(N, 1)), (size_t)16))); }
+    Seq(const as_vocoder& v_, as_plan& p_, hipStream_t s_, void* ws, size_t ws_bytes, Pass pass_)
+        : PassCtx(p_, s_, ws, ws_bytes, pass_, "vocoder_rt.hip"), v(v_) {}
+    float* f32(int C, int N) { return PassCtx::f32((size_t)C * std::max(N, 1)); }
 
-    // geometry: cached in the plan; its device tables (widths, offsets, column descriptors) are made on the first RUN that uses it -- a
-    // blocking upload and one stream synchronisation, never again for that geometry
-    const Lay* lay(const std::vector<int>& widths)
-    {
-        std::pair<std::vector<int>, int> key{widths, 1};
-        auto it = p.lays.find(key);
-        if (it == p.lays.end()) {
-            auto u = std::make_unique<Lay>();
-            Lay& L = *u;
-            L.B = (int)widths.size();
-            L.w = widths;
-            L.off.assign(L.B + 1, 0);
-            for (int b = 0; b < L.B; ++b) {
-                if (widths[b] < 0 || widths[b] > AS_META_MAX_W || (double)L.off[b] + widths[b] > 2147483647.0) { fail(AS_EINVAL); return nullptr; }
-                L.off[b + 1] = L.off[b] + widths[b];
-                L.max_w = std::max(L.max_w, widths[b]);
-            }
-            L.N = L.off[L.B];
-            it = p.lays.emplace(std::move(key), std::move(u)).first;
-        }
-        Lay* L = it->second.get();
-        if (!run) return L;
-        if (!L->d_off) {
-            int32_t* d_w = static_cast<int32_t*>(p.pool.alloc((L->B + 1) * sizeof(int32_t)));
-            int32_t* d_off = static_cast<int32_t*>(p.pool.alloc((L->B + 1) * sizeof(int32_t)));
-            if (!d_w || !d_off || hipMemcpy(d_w, L->w.data(), L->B * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_off, L->off.data(), (L->B + 1) * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-                fail((int)hipErrorOutOfMemory);
-                return nullptr;
-            }
-            L->d_w = d_w;
-            L->d_off = d_off;
-        }
-        if (!L->d_meta) {
-            uint64_t* md = static_cast<uint64_t*>(p.pool.alloc((size_t)std::max(L->N, 1) * sizeof(uint64_t)));
-            if (!md) { fail((int)hipErrorOutOfMemory); return nullptr; }
-            const int r = as_make_meta(L->d_w, L->d_off, L->B, 1, L->N, md, s);
-            if (r != AS_OK || hipStreamSynchronize(s) != hipSuccess) { fail(r ? r : (int)hipErrorUnknown); return nullptr; }
-            L->d_meta = md;
-        }
-        return L;
-    }
     // Capacity layouts (as_vocoder_forward_cap): rate i of {1, u0, u0 u1, ...} has cap * rate columns of ROOM; widths, offsets, column
     // descriptors and the valid count live in the WORKSPACE (AsVocGeo's two flat tables) and are written by the call's own geometry
     // launch -- nothing is cached, uploaded or allocated, so every call can be captured.  The Lay objects live as long as this pass.
@@ -279,7 +216,7 @@ struct Seq {
             u->B = B;
             u->N = geo.rate[i] * cap;
             u->max_w = geo.rate[i] * max_len;
-            if (run) {
+            if (pass == Pass::Run) {
                 u->d_w = tab + (size_t)i * (2 * B + 2);
                 u->d_off = u->d_w + B;
                 u->d_nvalid = u->d_w + 2 * B + 1;
@@ -291,27 +228,12 @@ struct Seq {
     }
     const Lay* scaled(const Lay* L, int k)
     {
-        if (L->dyn) {
-            const size_t i = (size_t)L->dyn_kind + 1;
-            if (i >= caps.size() || (long)caps[i]->N != (long)L->N * k) { fail(AS_EINVAL); return nullptr; }
-            return caps[i].get();
-        }
-        std::vector<int> w(L->w);
-        for (int& x : w) {
-            if ((double)x * k > (double)AS_META_MAX_W) { fail(AS_EINVAL); return nullptr; }
-            x *= k;
-        }
-        return lay(w);
+        if (!L->dyn) return PassCtx::scaled(L, k);
+        const size_t i = (size_t)L->dyn_kind + 1;
+        if (i >= caps.size() || (long)caps[i]->N != (long)L->N * k) { fail(AS_EINVAL); return nullptr; }
+        return caps[i].get();
     }
 };
-
-#define RUN(c, call)                                  \
-    do {                                              \
-        if ((c).go()) {                               \
-            const int r__ = (call);                   \
-            if (r__ != AS_OK) (c).fail(r__);          \
-        }                                             \
-    } while (0)
 
 struct ConvOpt {
     const float* bias = nullptr;
@@ -353,7 +275,7 @@ void conv(Seq& c, const ConvW& w, const float* X, int ldx, const uint16_t* xh, i
     a.ws_bytes = wsb;
     c.off = mark;                                                       // (scratch of this launch only: the stream orders the next user behind it)
     if (!c.go()) return;
-    a.meta = lay->d_meta;
+    a.meta = c.meta(lay);
     a.n_valid = lay->d_nvalid;                                          // (a capacity layout: the columns behind the utterances are filler)
     RUN(c, as_conv_gemm_f32(&a, c.s));
 }
@@ -368,7 +290,7 @@ void generator(Seq& c, const Lay* lay, const as_vocoder_io& io)
     const as_vocoder_cfg& h = v.cfg;
     const int nst = h.n_stages, nk = h.n_stacks, nd = h.n_dilations, c0 = h.upsample_initial_channel;
     if (!lay) return;
-    if (c.run && io.ld_mel < lay->N) { c.fail(AS_EINVAL); return; }
+    if (c.pass == Pass::Run && io.ld_mel < lay->N) { c.fail(AS_EINVAL); return; }
     // what one stage hands to the next -- fp32 activations, or LeakyReLU of them as the next ConvTranspose1d's operand image -- lives in
     // one of two slots at the head of the arena (stage i reads slot i % 2 and writes the other); everything behind them is the stage's
     // own and is given back when the stage ends
@@ -491,7 +413,8 @@ void generator(Seq& c, const Lay* lay, const as_vocoder_io& io)
     // conv_post: LeakyReLU(0.01) -> one output row -> tanh, and the 16-bit samples in the same pass
     const int C = c0 >> nst, N = lay->N;
     if (v.post32) {
-        RUN(c, as_conv_post_pcm_cap_f32(x, N, C, N, v.post32, v.post.bias, v.post_k, POST_SLOPE, 1, lay->d_meta, lay->d_nvalid, io.wav, io.pcm, c.s));
+        const uint64_t* meta = c.meta(lay);
+        RUN(c, as_conv_post_pcm_cap_f32(x, N, C, N, v.post32, v.post.bias, v.post_k, POST_SLOPE, 1, meta, lay->d_nvalid, io.wav, io.pcm, c.s));
     } else {
         float* wav = io.wav ? io.wav : c.f32(1, N);
         ConvOpt o;
@@ -513,7 +436,7 @@ bool lens_ok(const as_vocoder* v, int B, const int32_t* lens, std::vector<int>* 
 
 size_t count(const as_vocoder* v, as_plan* p, const std::vector<int>& lens, const as_vocoder_io& io, int* rc)
 {
-    Seq c{*v, *p, nullptr, nullptr, 0, 0, 0, false};
+    Seq c(*v, *p, nullptr, nullptr, 0, Pass::Count);
     generator(c, c.lay(lens), io);
     *rc = c.rc;
     return c.rc ? 0 : c.peak + 256;
@@ -534,7 +457,7 @@ void generator_cap(Seq& c, int B, const as_vocoder_cap& g, const as_vocoder_io& 
 
 size_t count_cap(const as_vocoder* v, as_plan* p, int B, const as_vocoder_cap& g, const as_vocoder_io& io, int* rc)
 {
-    Seq c{*v, *p, nullptr, nullptr, 0, 0, 0, false};
+    Seq c(*v, *p, nullptr, nullptr, 0, Pass::Count);
     generator_cap(c, B, g, io);
     *rc = c.rc;
     return c.rc ? 0 : c.peak + 256;
@@ -609,13 +532,11 @@ extern "C" int as_vocoder_forward(const as_vocoder* v, as_plan* p, int B, const 
 {
     std::vector<int> lens;
     if (!p || !io || !io->mel || (!io->wav && !io->pcm) || !lens_ok(v, B, lens_host, &lens)) return AS_EINVAL;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255) != 0 || (io->pcm && (reinterpret_cast<uintptr_t>(io->pcm) & 1) != 0)) return AS_EINVAL;
+    if (!ws || misaligned(ws) || (io->pcm && (reinterpret_cast<uintptr_t>(io->pcm) & 1) != 0)) return AS_EINVAL;
     return abi([&] {
         hipStream_t s = static_cast<hipStream_t>(stream);
-        int rc = p->trim(s);
+        int rc = enter(*p, s, ws, Pass::Run, true);
         if (rc != AS_OK) return rc;
-        p->note_stream(s);
-        if (as_status_peek()) return (int)AS_EDEVICE;                    // sticky until as_device_status(1)
         long total = 0;
         for (int x : lens) total += x;
         if (io->ld_mel < total) return (int)AS_EINVAL;
@@ -626,7 +547,7 @@ extern "C" int as_vocoder_forward(const as_vocoder* v, as_plan* p, int B, const 
         const size_t need = count(v, p, lens, q, &rc);
         if (rc != AS_OK) return rc;
         if (need > ws_bytes) return (int)AS_ENOSPC;
-        Seq c{*v, *p, s, static_cast<char*>(ws), ws_bytes, 0, 0, true};
+        Seq c(*v, *p, s, ws, ws_bytes, Pass::Run);
         generator(c, c.lay(lens), *io);
         return c.rc;
     });
@@ -648,18 +569,18 @@ extern "C" int as_vocoder_forward_cap(const as_vocoder* v, as_plan* p, int B, co
     if (!p || !cap || !io || !io->mel || (!io->wav && !io->pcm) || !cap->off || cap->mult < 1 || !cap_ok(v, B, cap->cap, cap->max_len))
         return AS_EINVAL;
     if (io->ld_mel < cap->cap) return AS_EINVAL;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255) != 0 || (io->pcm && (reinterpret_cast<uintptr_t>(io->pcm) & 1) != 0)) return AS_EINVAL;
+    if (!ws || misaligned(ws) || (io->pcm && (reinterpret_cast<uintptr_t>(io->pcm) & 1) != 0)) return AS_EINVAL;
     return abi([&] {
         hipStream_t s = static_cast<hipStream_t>(stream);
-        if (as_status_peek()) return (int)AS_EDEVICE;                    // sticky until as_device_status(1)
+        int rc = enter(*p, s, ws, Pass::Run, false);                     // (no trim: the call touches no plan table)
+        if (rc != AS_OK) return rc;
         // a workspace too small is refused before anything is launched
-        int rc = AS_OK;
         as_vocoder_io q = *io;
         q.wav = nullptr; q.pcm = nullptr;
         const size_t need = count_cap(v, p, B, *cap, q, &rc);
         if (rc != AS_OK) return rc;
         if (need > ws_bytes) return (int)AS_ENOSPC;
-        Seq c{*v, *p, s, static_cast<char*>(ws), ws_bytes, 0, 0, true};
+        Seq c(*v, *p, s, ws, ws_bytes, Pass::Run);
         generator_cap(c, B, *cap, *io);
         return c.rc;
     });

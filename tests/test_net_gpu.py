@@ -481,6 +481,35 @@ def test_module_workspace_bytes_are_exact(cuda, golden_dir):
         L.as_model_destroy(model)
 
 
+def test_workspace_b_refuses_a_geometry_past_int32_columns(cuda, golden_dir):
+    """as_module_workspace_bytes(AS_MOD_FORWARD_B) on frame counts whose mel-rate widths are each within AS_META_MAX_W while their sum
+    passes 2^31 - 1 -- the smallest such batch, from the two limits: column offsets are int32, so the geometry is refused (0), not
+    wrapped.  A count pass: nothing is launched or allocated on the device.  The same model and plan size a normal batch to the same
+    value before and after the refused call."""
+    import ctypes
+    from artspeech_amd import ops
+    L = _lib.lib()
+    gs = [np.load(f) for f in sorted(glob.glob(os.path.join(golden_dir, "net_tiny_*.npz")))]
+    net = get_model(int(gs[0]["hidden_dim"]), int(gs[0]["dim_in"]), int(gs[0]["weight_seed"]), cuda)
+    rt = net.rt.fork()                                                     # (a plan of its own: the refused layouts' relatives stay out of the shared one)
+    I32P = ctypes.POINTER(ctypes.c_int32)
+
+    def size(tok, ref, frames):
+        a = [(ctypes.c_int32 * len(v))(*v) for v in (tok, ref, frames)]
+        b = _lib.Batch(len(tok), ctypes.cast(a[0], I32P), ctypes.cast(a[1], I32P), ctypes.cast(a[2], I32P))
+        return L.as_module_workspace_bytes(rt.model, rt.plan, _lib.AS_MOD_FORWARD_B, ctypes.byref(b))
+
+    normal = ([len(g["tokens"]) for g in gs], [int(g["t_ref"]) for g in gs], [int(g["ref/pred_dur"].sum()) for g in gs])   # the tiny goldens as one batch
+    before = size(*normal)
+    assert before > 0
+    frames = ops.META_MAX_W // 2                                           # per utterance: 2 * frames <= AS_META_MAX_W mel frames
+    B = (2 ** 31 - 1) // (2 * frames) + 1                                  # the first batch whose mel-rate columns pass 2^31 - 1
+    assert 2 * frames <= ops.META_MAX_W and 2 * frames * (B - 1) <= 2 ** 31 - 1 < 2 * frames * B and frames * B <= 2 ** 31 - 1
+    assert size([normal[0][0]] * B, [normal[1][0]] * B, [frames] * B) == 0
+    assert size(*normal) == before
+    assert L.as_device_status(0) == 0
+
+
 @pytest.mark.parametrize("arrangement", ["side_streams", "merged_chain"])
 def test_c3_full_config_ragged_batch_vs_oracle(cuda, arrangement):
     """BASELINE config C3 at full size: 32 utterances of VARIED lengths through one as_forward_test call, every utterance against the

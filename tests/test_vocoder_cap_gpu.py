@@ -203,12 +203,12 @@ def test_pcm_under_a_capacity(cuda, c0):
     assert _lib.lib().as_device_status(0) == 0
 
 
-def _bare_call(rt, B, off, mult, cap, max_len, mel, wav, pcm, ws, ws_bytes, sample_off=None):
+def _bare_call(rt, B, off, mult, cap, max_len, mel, wav, pcm, ws, ws_bytes, sample_off=None, plan=None):
     io, g = _lib.VocoderIO(), _lib.VocoderCap()
     io.mel, io.ld_mel, io.wav, io.pcm = mel.data_ptr(), mel.stride(0), None if wav is None else wav.data_ptr(), None if pcm is None else pcm.data_ptr()
     g.off, g.mult, g.cap, g.max_len = off.data_ptr(), mult, cap, max_len
     g.sample_off = None if sample_off is None else sample_off.data_ptr()
-    return _lib.lib().as_vocoder_forward_cap(rt._voc, rt._plan, B, ctypes.byref(g), ctypes.byref(io), ws.data_ptr(), ws_bytes, _lib.stream())
+    return _lib.lib().as_vocoder_forward_cap(rt._voc, plan or rt._plan, B, ctypes.byref(g), ctypes.byref(io), ws.data_ptr(), ws_bytes, _lib.stream())
 
 
 @pytest.mark.parametrize("c0", [32, 512])
@@ -287,6 +287,86 @@ def test_one_graph_serves_other_lengths(cuda, c0):
             assert d <= TOL and bool((out[0, HOP * total:] == 0).all())
         del graph
     assert _lib.lib().as_device_status(0) == 0
+
+
+def test_the_first_call_of_a_new_plan_is_captured(cuda):
+    """A plan that has served nothing -- no known-length call, no eager call under a capacity: only its workspace was sized -- has
+    as_vocoder_forward_cap captured as its very first call (the call notes its stream in the plan and makes no plan table: nothing
+    synchronises).  The replay equals an eager call through the generator's own plan bit for bit, and again with other lengths written
+    in place."""
+    L = _lib.lib()
+    rt = gen(32, cuda)
+    B, cap = 2, 24
+    plan = ctypes.c_void_p()
+    with torch.cuda.device(cuda):
+        assert L.as_device_status(0) == 0                                  # (the status words exist before anything is captured)
+        assert L.as_vocoder_plan_create(rt._voc, ctypes.byref(plan)) == 0
+        try:
+            need = L.as_vocoder_cap_workspace_bytes(rt._voc, plan, B, cap, 0)
+            assert need > 0 and L.as_plan_layout_count(plan) == 0
+            ws = torch.empty(need, dtype=torch.uint8, device=cuda)
+            mel, off, _ = mel_room(synth_mels([9, 11], "first0"), cap, cuda)
+            wav = torch.full((HOP * cap,), 5.0, device=cuda)
+            pcm = torch.full((HOP * cap,), 555, dtype=torch.int16, device=cuda)
+            so = torch.full((B + 1,), -5, dtype=torch.int32, device=cuda)
+            rt.forward_packed_cap(mel, off, 1, cap, pcm=True)              # (the generator's OWN plan: the kernels have run once in this process)
+            side = torch.cuda.Stream(device=cuda)
+            graph = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(graph, stream=side):
+                rc = _bare_call(rt, B, off, 1, cap, 0, mel, wav, pcm, ws, need, so, plan=plan)
+            torch.cuda.synchronize()
+            assert rc == 0 and L.as_plan_layout_count(plan) == 0
+            assert bool((wav == 5.0).all())                                # captured, not run
+            for k, lens in enumerate(([9, 11], [20, 1])):
+                m2, o2, _ = mel_room(synth_mels(lens, f"first{k}"), cap, cuda, fill=float(k))
+                mel.copy_(m2)
+                off.copy_(o2)
+                torch.cuda.synchronize()
+                graph.replay()
+                torch.cuda.synchronize()
+                eager, eager_so, eager_pcm = rt.forward_packed_cap(m2, o2, 1, cap, pcm=True)
+                torch.cuda.synchronize()
+                total = sum(lens)
+                assert so.cpu().tolist() == [HOP * v for v in o2.cpu().tolist()] and torch.equal(so, eager_so)
+                assert torch.equal(wav, eager[0]) and torch.equal(pcm, eager_pcm), lens
+                assert float(wav[: HOP * total].abs().max()) > 1e-3 and bool((wav[HOP * total:] == 0).all())
+            del graph
+        finally:
+            torch.cuda.synchronize()
+            assert L.as_plan_destroy(plan) == 0
+    assert L.as_device_status(0) == 0
+
+
+def test_exact_workspace_fits_and_one_notch_short_is_refused(cuda):
+    """as_vocoder_forward_cap, c0 = 32, B = 2, cap = 12.  With exactly as_vocoder_cap_workspace_bytes the call succeeds and gives the
+    samples of a call with room to spare, bit for bit; with 256 bytes fewer -- the arena's next notch -- it returns AS_ENOSPC and neither
+    output buffer is touched."""
+    L = _lib.lib()
+    rt = gen(32, cuda)
+    B, cap = 2, 12
+    with torch.cuda.device(cuda):
+        mel, off, _ = mel_room(synth_mels([7, 3], "fit"), cap, cuda)
+        need = L.as_vocoder_cap_workspace_bytes(rt._voc, rt._plan, B, cap, 0)
+        assert need > 256 and need % 256 == 0
+        ws = torch.empty(need + 65536, dtype=torch.uint8, device=cuda)
+        assert ws.data_ptr() % 256 == 0
+
+        def call(ws_bytes):
+            wav = torch.full((HOP * cap,), 5.0, device=cuda)
+            pcm = torch.full((HOP * cap,), 555, dtype=torch.int16, device=cuda)
+            rc = _bare_call(rt, B, off, 1, cap, 0, mel, wav, pcm, ws, ws_bytes)
+            torch.cuda.synchronize()
+            return rc, wav, pcm
+
+        rc, wav_room, pcm_room = call(need + 65536)
+        assert rc == 0 and float(wav_room[: HOP * 10].abs().max()) > 1e-3 and bool((wav_room[HOP * 10:] == 0).all())
+        rc, wav_fit, pcm_fit = call(need)
+        assert rc == 0 and torch.equal(wav_fit, wav_room) and torch.equal(pcm_fit, pcm_room)
+        rc, wav_short, pcm_short = call(need - 256)
+        assert rc == -2                                                    # AS_ENOSPC
+        assert bool((wav_short == 5.0).all()) and bool((pcm_short == 555).all())
+    assert L.as_device_status(0) == 0
 
 
 @pytest.mark.parametrize("c0", [32, 512])

@@ -69,6 +69,57 @@ def test_runtime_equals_operator_path_bit_for_bit(cuda, golden_dir, c0, case):
     assert _lib.lib().as_device_status(0) == 0
 
 
+@pytest.mark.parametrize("c0", [32, 512])
+def test_zero_length_utterance_inside_a_batch(cuda, c0):
+    """[5, 0, 4] frames: the empty utterance has a row in every table and no column.  The runtime on a geometry it has not seen -- its
+    tables are uploaded and its column descriptors made by this very call, each by the first launch that reads them -- equals the
+    operator path bit for bit, and so does the second call, which makes nothing."""
+    ref, rt = gens(c0, cuda)
+    with torch.cuda.device(cuda):
+        mel_p, lay = packed(synth_mels([5, 0, 4], "zero"), cuda)
+        want, lay_w = ref.forward_packed(mel_p, lay)
+        got, lay_g = rt.forward_packed(mel_p, lay)
+        again, _ = rt.forward_packed(mel_p, lay)
+        torch.cuda.synchronize()
+    assert lay_g.widths_host == lay_w.widths_host == [1500, 0, 1200]
+    assert got.shape == want.shape == (1, 2700) and bool(torch.isfinite(want).all()) and float(want.abs().max()) > 1e-3
+    assert torch.equal(got, want) and torch.equal(again, want)
+    assert _lib.lib().as_device_status(0) == 0
+
+
+def test_exact_workspace_fits_and_one_notch_short_is_refused(cuda):
+    """as_vocoder_forward, c0 = 32, [7, 3] frames.  With exactly as_vocoder_workspace_bytes the call succeeds and gives the samples of a
+    call with room to spare, bit for bit (nothing is placed by how much room there is); with 256 bytes fewer -- the arena's next notch --
+    it returns AS_ENOSPC and neither output buffer is touched."""
+    L = _lib.lib()
+    _, rt = gens(32, cuda)
+    lens = (ctypes.c_int32 * 2)(7, 3)
+    with torch.cuda.device(cuda):
+        mel_p, _ = packed(synth_mels([7, 3], "fit"), cuda)
+        need = L.as_vocoder_workspace_bytes(rt._voc, rt._plan, 2, lens)
+        assert need > 256 and need % 256 == 0
+        ws = torch.empty(need + 65536, dtype=torch.uint8, device=cuda)
+        assert ws.data_ptr() % 256 == 0
+
+        def call(ws_bytes, fill_w, fill_p):
+            wav = torch.full((3000,), fill_w, device=cuda)
+            pcm = torch.full((3000,), fill_p, dtype=torch.int16, device=cuda)
+            io = _lib.VocoderIO()
+            io.mel, io.ld_mel, io.wav, io.pcm = mel_p.data_ptr(), 10, wav.data_ptr(), pcm.data_ptr()
+            rc = L.as_vocoder_forward(rt._voc, rt._plan, 2, lens, ctypes.byref(io), ws.data_ptr(), ws_bytes, _lib.stream())
+            torch.cuda.synchronize()
+            return rc, wav, pcm
+
+        rc, wav_room, pcm_room = call(need + 65536, 5.0, 555)
+        assert rc == 0 and float(wav_room.abs().max()) > 1e-3 and bool((wav_room != 5.0).all())
+        rc, wav_fit, pcm_fit = call(need, 5.0, 555)
+        assert rc == 0 and torch.equal(wav_fit, wav_room) and torch.equal(pcm_fit, pcm_room)
+        rc, wav_short, pcm_short = call(need - 256, 5.0, 555)
+        assert rc == -2                                                    # AS_ENOSPC
+        assert bool((wav_short == 5.0).all()) and bool((pcm_short == 555).all())
+    assert L.as_device_status(0) == 0
+
+
 @pytest.mark.parametrize("tag", ["tiny", "full"])
 def test_runtime_matches_reference(cuda, golden_dir, tag):
     """the runtime path against the reference Generator's own outputs, within the bound of tests/test_vocoder_gpu.py"""
