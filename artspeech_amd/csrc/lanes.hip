@@ -18,8 +18,11 @@
 //     reset (as_plan_reset_layouts: the table memory is reused, nothing is freed);
 //   * nothing here frees device memory while other lanes may be busy (a hipFree synchronises the device): an outgrown workspace is
 //     parked until as_lanes_wait(q, -1) / as_lanes_destroy.
+// Coalescing (as_lanes_set_coalesce) and host submissions (as_lanes_submit_host) hold submissions back in groups: what a group is, who joins
+// it and the call it becomes are lanes_group.h (host-only, tested without a GPU); this file owns the streams, events, copies and graphs.
 #include "common.h"
 #include "artspeech_hip.h"
+#include "lanes_group.h"
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -33,6 +36,8 @@
 
 namespace {
 
+using namespace lanes_group;
+
 struct Lane {
     as_plan* plan = nullptr;                                      // eager calls, workspace queries: flushed whenever its cap says so
     as_plan* gplan = nullptr;                                     // geometries that are (about to be) replayed from graphs; reset with them
@@ -43,16 +48,7 @@ struct Lane {
     std::unordered_set<std::string> once;                         // pairs that ran once, on the eager plan (a bounded memory of candidates)
     std::unordered_set<std::string> met;                          // pairs the graph plan has met eagerly: captured at their next submit
     int64_t n_drops = 0, n_launch = 0, n_eager = 0, n_capture = 0, n_merged = 0;
-    // submissions waiting for their group (as_lanes_set_coalesce): host arrays copied, device pointers as given
-    struct Pending {
-        std::vector<int32_t> tok_lens, ref_lens, frames;
-        as_forward_io io;
-        float* out_host = nullptr;                                // as_lanes_submit_host: where the submission's mel goes once its group is out
-        int32_t ld_out_host = 0;
-        int32_t* foff_host = nullptr;                             // ... and, under a frame capacity, its frame offsets
-        unsigned long long sum = 0;                               // debug mode: checksum of the device inputs as they were at submit
-    };
-    std::vector<Pending> pend;
+    std::vector<Pending> pend;                                    // submissions waiting for their group (as_lanes_set_coalesce; lanes_group.h)
     // as_lanes_submit_host: the lane's own device block -- the inputs of a group's submissions side by side (adjacent column ranges: one
     // batch as they lie) and the group's output
     struct Block {
@@ -155,16 +151,13 @@ bool grow(as_lanes* q, void** p, size_t* have, size_t need)
 
 }  // namespace
 
-static int flush_lane(as_lanes* q, int lane);
+static int flush_lanes(as_lanes* q, int lane, bool keep_going = false);
 extern "C" int as_lanes_destroy(as_lanes* q)
 {
     if (!q) return AS_OK;
-    // submissions still waiting for neighbours were accepted: they go out before the lanes do (their status has nobody left to go to)
-    try {
-        for (int i = 0; i < (int)q->lanes.size(); ++i)
-            if (q->lanes[i].plan && q->lanes[i].gplan && q->lanes[i].stream) (void)flush_lane(q, i);
-    } catch (...) {
-    }
+    // submissions still waiting for neighbours were accepted: they go out before the lanes do (their status has nobody left to go to;
+    // a lane that as_lanes_create did not finish holds none)
+    (void)flush_lanes(q, -1, true);
     for (Lane& L : q->lanes) {
         if (L.stream) (void)hipStreamSynchronize(L.stream);
     }
@@ -278,19 +271,11 @@ extern "C" int as_lanes_stats(const as_lanes* q, int lane, int64_t* out6)
     return AS_OK;
 }
 
-static int flush_lane(as_lanes* q, int lane);
 extern "C" int as_lanes_wait(as_lanes* q, int lane)
 {
     if (!q || lane >= (int)q->lanes.size()) return AS_EINVAL;
-    try {                                                          // submissions still waiting for neighbours go out first
-        for (int i = 0; i < (int)q->lanes.size(); ++i)
-            if (lane < 0 || lane == i) {
-                const int rc = flush_lane(q, i);
-                if (rc != AS_OK) return rc;
-            }
-    } catch (...) {
-        return (int)hipErrorOutOfMemory;
-    }
+    const int rc = flush_lanes(q, lane);                           // submissions still waiting for neighbours go out first
+    if (rc != AS_OK) return rc;
     for (int i = 0; i < (int)q->lanes.size(); ++i)
         if (lane < 0 || lane == i) {
             if (hipStreamSynchronize(q->lanes[i].stream) != hipSuccess) return (int)hipErrorUnknown;
@@ -416,50 +401,7 @@ static int lane_run(as_lanes* q, const as_batch* batch, const as_forward_io* io,
 // flushed / waited for) and launches them as ONE as_forward_test call, with no copy.  What it buys: wider conv GEMM launches (fuller
 // rounds of the chip, the weights fetched once for k batches).  The reference processes one utterance at a time (models.py:361-362):
 // any grouping is legal, and every utterance still gets its batch-1 result (packed frames: no padding, no cross-utterance term).
-static bool plain_io(const as_forward_io* io)                     // only the mel is wanted: the optional outputs have no per-submission home in a merged call
-{
-    return !io->duration && !io->dur_i && !io->frame_off && !io->style && !io->feat12 && !io->t_en && !io->a_en && !io->F0 && !io->N && !io->EMA;
-}
-// Voice mode (as_forward_io.voices): the voice of utterance b of the merged call must still be utterance b's -- indices that continue where
-// the previous submission's end, into the same table; or no indices (row b) and the rows continuing where the previous submission's end (a
-// table of at least its own rows: with fewer it raises AS_STATUS_BAD_VOICE alone and is not merged).  Never with a reference submission.
-static bool voices_adjacent(const as_forward_io& a, long prev_B, const as_forward_io* io)
-{
-    if ((io->voices != nullptr) != (a.voices != nullptr)) return false;
-    if (!io->voices) return true;
-    if (io->voice_idx && a.voice_idx)
-        return io->voices == a.voices && io->ld_voice == a.ld_voice && io->n_voices == a.n_voices && io->voice_idx == a.voice_idx + prev_B;
-    return !io->voice_idx && !a.voice_idx && io->ld_voice == a.ld_voice && a.n_voices >= prev_B && io->voices == a.voices + prev_B * a.ld_voice;
-}
-// Prosody control (as_forward_io.prosody): utterance b of the merged call reads row b of the first submission's rows -- so every
-// submission's rows continue where the previous one's end, with the same stride; or no submission of the group carries any.
-static bool prosody_adjacent(const as_forward_io& a, long prev_B, const as_forward_io* io)
-{
-    if ((io->prosody != nullptr) != (a.prosody != nullptr)) return false;
-    return !io->prosody || (io->ld_prosody == a.ld_prosody && io->prosody == a.prosody + prev_B * a.ld_prosody);
-}
-static bool adjacent(const Lane::Pending& p, const as_forward_io* io, bool cap_mode)
-{
-    long nt = 0, nr = 0, nf = 0;
-    for (int32_t v : p.tok_lens) nt += v;
-    for (int32_t v : p.ref_lens) nr += v;
-    for (int32_t v : p.frames) nf += v;
-    const as_forward_io& a = p.io;
-    if (cap_mode != (p.frames.empty() && a.frame_cap > 0)) return false;   // (a group is of one kind)
-    if (!voices_adjacent(a, (long)p.tok_lens.size(), io) || !prosody_adjacent(a, (long)p.tok_lens.size(), io)) return false;
-    const bool in = io->tokens == a.tokens + nt &&
-                    (io->voices || (io->mel == a.mel + nr && io->ld_mel == a.ld_mel && io->f0_raw == a.f0_raw + nr && io->ema_raw == a.ema_raw + nr &&
-                                    io->ld_ema == a.ld_ema));
-    // under a frame capacity every submission keeps its own output buffer (as_segments: the merged call's mel is dealt out to them)
-    if (cap_mode) return in && !io->forced_dur && !a.forced_dur;
-    return in && ((!io->forced_dur && !a.forced_dur) || (io->forced_dur && a.forced_dur && io->forced_dur == a.forced_dur + nt)) &&
-           io->mel_out == a.mel_out + 2 * nf && io->ld_out == a.ld_out;
-}
-// (frame capacity: frame_off is the one optional output a submission of a merged call can have -- it is how the caller finds its utterances)
-static bool plain_cap_io(const as_forward_io* io)
-{
-    return !io->duration && !io->dur_i && !io->style && !io->feat12 && !io->t_en && !io->a_en && !io->F0 && !io->N && !io->EMA && !io->segs;
-}
+// The rule -- which submissions can be held back, which one joins the group that waits, the call a group becomes -- is lanes_group.h.
 
 // ---- debug mode (as_lanes_set_debug, AS_DEBUG=1) -------------------------------------------------------------------------------------
 // Under coalescing a submission's device buffers are read when its GROUP is launched, not when it is submitted: a caller that refills them
@@ -467,6 +409,7 @@ static bool plain_cap_io(const as_forward_io* io)
 // durations, f0, the EMA and mel rows; in voice mode the voice indices; the prosody rows) are checksummed on the lane's stream when it is submitted -- the call then WAITS for that stream,
 // so the sum is of the data the caller handed over -- and again when the group goes out; a difference raises AS_STATUS_BAD_LAYOUT (the
 // group's launch returns AS_EDEVICE, as every entry point does while a bit is set).  Costs a stream synchronisation per submission.
+// Host submissions (as_lanes_submit_host) get no sum, at either end: their device buffers are the lane's block, which no caller can reach.
 __global__ void __launch_bounds__(256)
 lanes_sum_kernel(const uint32_t* __restrict__ p, long n, long ld, unsigned long long salt, unsigned long long* __restrict__ out)
 {
@@ -482,31 +425,28 @@ lanes_sum_kernel(const uint32_t* __restrict__ p, long n, long ld, unsigned long 
 void as_status_raise_host(int kind);                               // status.hip
 
 // checksum of a submission's device inputs as they are when the lane's stream gets here; blocks until it is known
-static int inputs_sum(as_lanes* q, Lane& L, const std::vector<int32_t>& tok_lens, const std::vector<int32_t>& ref_lens, const as_forward_io& io,
-                      unsigned long long* sum)
+static int inputs_sum(as_lanes* q, Lane& L, const Pending& p, unsigned long long* sum)
 {
     if (!L.dbg && hipMalloc(reinterpret_cast<void**>(&L.dbg), sizeof(unsigned long long)) != hipSuccess) {
         (void)hipGetLastError();
         return (int)hipErrorOutOfMemory;
     }
-    long nt = 0, nr = 0;
-    for (int32_t v : tok_lens) nt += v;
-    for (int32_t v : ref_lens) nr += v;
+    const as_forward_io& io = p.io;
     AS_CHECK(hipMemsetAsync(L.dbg, 0, sizeof(unsigned long long), L.stream));
     auto add = [&](const void* ptr, long n, long rows, long ld, unsigned long long salt) {
         if (!ptr || n <= 0) return;
         hipLaunchKernelGGL(lanes_sum_kernel, dim3(as_cdiv(n, 256), (unsigned)rows), dim3(256), 0, L.stream, static_cast<const uint32_t*>(ptr), n, ld, salt, L.dbg);
     };
-    add(io.tokens, nt, 1, nt, 0x100000000ull);
-    add(io.forced_dur, nt, 1, nt, 0x200000000ull);
+    add(io.tokens, p.n_tok, 1, p.n_tok, 0x100000000ull);
+    add(io.forced_dur, p.n_tok, 1, p.n_tok, 0x200000000ull);
     if (io.voices) {
-        add(io.voice_idx, (long)tok_lens.size(), 1, (long)tok_lens.size(), 0x600000000ull);
+        add(io.voice_idx, p.B, 1, p.B, 0x600000000ull);
     } else {
-        add(io.f0_raw, nr, 1, nr, 0x300000000ull);
-        add(io.ema_raw, nr, 10, io.ld_ema, 0x400000000ull);
-        add(io.mel, nr, q->cfg.n_mels, io.ld_mel, 0x500000000ull);
+        add(io.f0_raw, p.n_ref, 1, p.n_ref, 0x300000000ull);
+        add(io.ema_raw, p.n_ref, 10, io.ld_ema, 0x400000000ull);
+        add(io.mel, p.n_ref, q->cfg.n_mels, io.ld_mel, 0x500000000ull);
     }
-    add(io.prosody, AS_PROSODY_DIM, (long)tok_lens.size(), io.ld_prosody, 0x700000000ull);
+    add(io.prosody, AS_PROSODY_DIM, p.B, io.ld_prosody, 0x700000000ull);
     AS_CHECK_LAUNCH();
     AS_CHECK(hipMemcpyAsync(sum, L.dbg, sizeof(unsigned long long), hipMemcpyDeviceToHost, L.stream));
     AS_CHECK(hipStreamSynchronize(L.stream));
@@ -518,74 +458,26 @@ static int flush_lane(as_lanes* q, int lane)
 {
     Lane& L = q->lanes[lane];
     if (L.pend.empty()) return AS_OK;
-    if (q->debug) {
-        for (const Lane::Pending& p : L.pend) {
-            unsigned long long now = 0;
-            const int rc = inputs_sum(q, L, p.tok_lens, p.ref_lens, p.io, &now);
-            if (rc != AS_OK) return rc;
-            if (now != p.sum) {
-                fprintf(stderr, "artspeech_hip: as_lanes (debug): the device buffers of a submission that was waiting for its group on lane %d "
-                                "changed between as_lanes_submit and the group's launch\n", lane);
-                as_status_raise_host(AS_STATUS_BAD_LAYOUT);
-            }
+    for (const Pending& p : L.pend) {
+        if (!p.has_sum) continue;                                 // (debug mode only; a host submission has none: the lane's block is the library's own)
+        unsigned long long now = 0;
+        const int rc = inputs_sum(q, L, p, &now);
+        if (rc != AS_OK) return rc;
+        if (now != p.sum) {
+            fprintf(stderr, "artspeech_hip: as_lanes (debug): the device buffers of a submission that was waiting for its group on lane %d "
+                            "changed between as_lanes_submit and the group's launch\n", lane);
+            as_status_raise_host(AS_STATUS_BAD_LAYOUT);
         }
-    }
-    std::vector<int32_t> tl, rl, fr;
-    for (const Lane::Pending& p : L.pend) {
-        tl.insert(tl.end(), p.tok_lens.begin(), p.tok_lens.end());
-        rl.insert(rl.end(), p.ref_lens.begin(), p.ref_lens.end());
-        fr.insert(fr.end(), p.frames.begin(), p.frames.end());
     }
     as_batch b;
-    b.B = (int32_t)tl.size();
-    b.tok_lens = tl.data(); b.ref_lens = rl.data(); b.frames = fr.data();
-    as_forward_io io = L.pend.front().io;
-    if (io.voices) {
-        b.ref_lens = nullptr;                                     // (voice mode reads no reference lengths)
-        if (!io.voice_idx && L.pend.size() > 1) {                 // rows b of the merged call: the last submission's table bounds the group's
-            long rows = 0;
-            for (size_t i = 0; i + 1 < L.pend.size(); ++i) rows += (long)L.pend[i].tok_lens.size();
-            io.n_voices = (int32_t)std::min<long>(INT_MAX, rows + L.pend.back().io.n_voices);
-        }
-    }
+    as_forward_io io;
     as_segments segs;
-    if (fr.empty()) {                                             // submissions under a frame capacity: the merged call deals its mel out to them
-        b.frames = nullptr;
-        if (L.pend.size() > 1) {
-            memset(&segs, 0, sizeof(segs));
-            segs.n = (int32_t)L.pend.size();
-            long cap = 0;
-            int32_t first = 0;
-            for (size_t i = 0; i < L.pend.size(); ++i) {
-                const Lane::Pending& p = L.pend[i];
-                segs.first[i] = first;
-                segs.cap[i] = p.io.frame_cap;
-                segs.mel_out[i] = p.io.mel_out;
-                segs.ld_out[i] = p.io.ld_out;
-                segs.frame_off[i] = p.io.frame_off;
-                first += (int32_t)p.tok_lens.size();
-                cap += p.io.frame_cap;
-            }
-            segs.first[segs.n] = first;
-            io.frame_cap = (int32_t)cap;
-            io.frame_off = nullptr;
-            io.segs = &segs;
-        }
-    }
+    Lens lens;
+    merge(L.pend, &b, &io, &segs, &lens);
     if (L.pend.size() > 1) ++L.n_merged;
-    // (host submissions: where each one's mel goes once the group's kernels are enqueued)
-    struct Out { float* host; int32_t ld; const float* dev; long cols; int32_t ld_dev; int32_t* foff_host; const int32_t* foff_dev; int n_foff; };
-    std::vector<Out> outs;
-    for (const Lane::Pending& p : L.pend)
-        if (p.out_host) {
-            long nf = 0;
-            for (int32_t v : p.frames) nf += v;
-            // (under a frame capacity the whole slot goes back: how much of it holds frames is known on the device only)
-            outs.push_back({p.out_host, p.ld_out_host, p.io.mel_out, p.frames.empty() ? 2L * p.io.frame_cap : 2 * nf, p.io.ld_out, p.foff_host,
-                            p.io.frame_off, (int)p.tok_lens.size() + 1});
-        }
-    L.pend.clear();
-    const bool host_group = !outs.empty();
+    std::vector<Pending> group;                                   // the lane holds nothing from here on, whatever happens below; the group
+    group.swap(L.pend);                                           // itself lives until its results' copies are enqueued
+    const bool host_group = group.front().host();
     const int bi = L.cur;
     if (host_group) {                                             // the group's kernels start behind its host -> device copies
         AS_CHECK(hipEventRecord(L.ev_h2d[bi], q->h2d));
@@ -602,12 +494,14 @@ static int flush_lane(as_lanes* q, int lane)
         // ev_d2h[bi] is what the block's NEXT group's copies wait for (recorded whatever happened: a block is never left without it)
         hipError_t e = hipEventRecord(L.ev_comp[bi], L.stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(q->d2h, L.ev_comp[bi], 0);
-        for (const Out& o : outs) {
-            if (rc == AS_OK && e == hipSuccess && o.cols > 0)
-                e = hipMemcpy2DAsync(o.host, (size_t)o.ld * 4, o.dev, (size_t)o.ld_dev * 4, (size_t)o.cols * 4, (size_t)q->cfg.n_mels,
-                                     hipMemcpyDeviceToHost, q->d2h);
-            if (rc == AS_OK && e == hipSuccess && o.foff_host)
-                e = hipMemcpyAsync(o.foff_host, o.foff_dev, (size_t)o.n_foff * 4, hipMemcpyDeviceToHost, q->d2h);
+        for (const Pending& p : group) {
+            // (under a frame capacity the whole slot goes back: how much of it holds frames is known on the device only)
+            const long cols = p.cap_mode() ? 2L * p.io.frame_cap : 2 * p.n_frames;
+            if (rc == AS_OK && e == hipSuccess && cols > 0)
+                e = hipMemcpy2DAsync(p.out_host, (size_t)p.ld_out_host * 4, p.io.mel_out, (size_t)p.io.ld_out * 4, (size_t)cols * 4,
+                                     (size_t)q->cfg.n_mels, hipMemcpyDeviceToHost, q->d2h);
+            if (rc == AS_OK && e == hipSuccess && p.foff_host)
+                e = hipMemcpyAsync(p.foff_host, p.io.frame_off, (size_t)(p.B + 1) * 4, hipMemcpyDeviceToHost, q->d2h);
         }
         const hipError_t e2 = hipEventRecord(L.ev_d2h[bi], q->d2h);
         if (rc == AS_OK && (e != hipSuccess || e2 != hipSuccess)) return (int)(e != hipSuccess ? e : e2);
@@ -615,41 +509,43 @@ static int flush_lane(as_lanes* q, int lane)
     return rc;
 }
 
+// launch what waits on lane `lane` (< 0: on every lane); the first failure ends it, unless the lanes are being torn down
+static int flush_lanes(as_lanes* q, int lane, bool keep_going)
+{
+    try {
+        for (int i = 0; i < (int)q->lanes.size(); ++i)
+            if (lane < 0 || lane == i) {
+                const int rc = flush_lane(q, i);
+                if (rc != AS_OK && !keep_going) return rc;
+            }
+        return AS_OK;
+    } catch (...) {
+        return (int)hipErrorOutOfMemory;
+    }
+}
+
 static int lanes_submit(as_lanes* q, const as_batch* batch, const as_forward_io* io, int32_t* frames_host_out, int32_t* lane_out,
                         float* out_host = nullptr, int32_t ld_out_host = 0, int32_t* foff_host = nullptr)
 {
     if (!q || !batch || !io || batch->B <= 0 || !batch->tok_lens || (!batch->ref_lens && !io->voices)) return AS_EINVAL;
     if (io->prosody && (io->ld_prosody < AS_PROSODY_DIM || io->forced_dur)) return AS_EINVAL;   // (refused now, not when its group goes out)
-    Lane& L = q->lanes[q->next];
-    // (a host submission always joins the group of its lane's block -- a group of one when coalescing is off)
-    const bool cap_mode = !batch->frames && io->frame_cap > 0;
-    const bool can_wait = (q->coalesce > 1 || out_host) && ((batch->frames && plain_io(io)) || (cap_mode && plain_cap_io(io)));
-    size_t waiting = 0;                                           // utterances of the group that waits here
-    for (const Lane::Pending& p : L.pend) waiting += p.tok_lens.size();
-    // (a call takes at most 1024 utterances: as_durations_f32's one-workgroup scan; at most AS_MAX_SEGMENTS submissions under a capacity)
-    if (!L.pend.empty() && !(can_wait && adjacent(L.pend.back(), io, cap_mode) && waiting + (size_t)batch->B <= 1024 &&
-                             (!cap_mode || L.pend.size() < (size_t)AS_MAX_SEGMENTS))) {
+    const bool waits = can_wait(q->coalesce, out_host != nullptr, batch, io);
+    if (!(waits && joins(q->lanes[q->next].pend, batch, io, out_host != nullptr))) {
         const int rc = flush_lane(q, q->next);                    // not a neighbour of what waits here: that group goes out first (and the turn passes on)
         if (rc != AS_OK) return rc;
     }
     if (lane_out) *lane_out = q->next;
-    if (!can_wait) return lane_run(q, batch, io, frames_host_out);
-    Lane& L2 = q->lanes[q->next];
-    Lane::Pending p;
-    p.tok_lens.assign(batch->tok_lens, batch->tok_lens + batch->B);
-    if (!io->voices) p.ref_lens.assign(batch->ref_lens, batch->ref_lens + batch->B);
-    if (batch->frames) p.frames.assign(batch->frames, batch->frames + batch->B);
-    p.io = *io;
-    p.out_host = out_host;
-    p.ld_out_host = ld_out_host;
-    p.foff_host = foff_host;
+    if (!waits) return lane_run(q, batch, io, frames_host_out);
+    Lane& L = q->lanes[q->next];
+    Pending p(batch, io, out_host, ld_out_host, foff_host);
     if (q->debug && !out_host) {                                  // (a host submission's device buffers are the library's own)
-        const int rc = inputs_sum(q, L2, p.tok_lens, p.ref_lens, p.io, &p.sum);
+        const int rc = inputs_sum(q, L, p, &p.sum);
         if (rc != AS_OK) return rc;
+        p.has_sum = true;
     }
-    L2.pend.push_back(std::move(p));
+    L.pend.push_back(std::move(p));
     if (frames_host_out && batch->frames) memcpy(frames_host_out, batch->frames, sizeof(int32_t) * batch->B);
-    if ((int)L2.pend.size() >= q->coalesce) return flush_lane(q, q->next);
+    if ((int)L.pend.size() >= q->coalesce) return flush_lane(q, q->next);
     return AS_OK;
 }
 
@@ -723,6 +619,35 @@ static int block_fit(as_lanes* q, Lane& L, long nt, long nr, long nf2, int n_utt
     return AS_OK;
 }
 
+// the as_forward_io of a host submission whose inputs lie (or are about to lie) in the block's next free positions.  A group's tokens,
+// forced durations, reference rows, voice indices and prosody rows lie back to back there, each kind with one stride: what is left for
+// `joins` to decide is what the caller brought (known frames or a capacity, forced durations, the voice table, prosody) and a call's limits
+static as_forward_io block_io(const Lane::Block& b, const as_host_io* h, bool cap_mode)
+{
+    as_forward_io io;
+    memset(&io, 0, sizeof(io));
+    io.tokens = b.tokens + b.used_tok;
+    if (h->voices) {
+        io.voices = h->voices; io.ld_voice = h->ld_voice; io.n_voices = h->n_voices;
+        io.voice_idx = h->voice_idx ? b.vidx + b.used_vid : nullptr;
+    } else {
+        io.mel = b.mel + b.used_ref; io.ld_mel = b.cap_ref;
+        io.f0_raw = b.f0 + b.used_ref;
+        io.ema_raw = b.ema + b.used_ref; io.ld_ema = b.cap_ref;
+    }
+    if (h->prosody) {
+        io.prosody = b.pros + (size_t)b.used_vid * AS_PROSODY_DIM;
+        io.ld_prosody = AS_PROSODY_DIM;
+    }
+    io.forced_dur = h->forced_dur ? b.forced + b.used_tok : nullptr;
+    io.mel_out = b.out + b.used_out; io.ld_out = b.cap_out;
+    if (cap_mode) {
+        io.frame_cap = h->frame_cap;
+        io.frame_off = b.foff + b.used_utt;
+    }
+    return io;
+}
+
 static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_io* h, int32_t* lane_out)
 {
     if (!q || !batch || !h || batch->B <= 0 || !batch->tok_lens || (!batch->ref_lens && !h->voices)) return AS_EINVAL;
@@ -743,32 +668,21 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
     const int n_mels = q->cfg.n_mels;
     for (int attempt = 0;; ++attempt) {
         Lane& L = q->lanes[q->next];
-        // what waits on this lane came with device buffers of the caller's, or the block is full: that group goes out first
-        size_t waiting = 0;
-        for (const Lane::Pending& p : L.pend) waiting += p.tok_lens.size();
-        // (voice mode: the group's indices lie back to back in the block, so indexed submissions of one table always continue each other;
-        //  so do the prosody rows, and a group carries them for all of its submissions or for none)
-        bool voice_fits = true;
-        if (!L.pend.empty()) {
-            const as_forward_io& a = L.pend.back().io;
-            const long prev_B = (long)L.pend.back().tok_lens.size();
-            voice_fits = (a.voices != nullptr) == voice &&
-                         (!voice || (h->voice_idx ? (a.voice_idx && a.voices == h->voices && a.ld_voice == h->ld_voice && a.n_voices == h->n_voices)
-                                                  : (!a.voice_idx && a.ld_voice == h->ld_voice && a.n_voices >= prev_B &&
-                                                     h->voices == a.voices + prev_B * a.ld_voice)));
-            voice_fits = voice_fits && (a.prosody != nullptr) == pros;
+        // the block has room behind what waits on this lane (AS_ENOSPC: it has not), and the submission, lying in its next free columns,
+        // joins that group by the rule of every submission -- before anything is copied
+        int rc = block_fit(q, L, nt, nr, 2 * nf, batch->B, std::max(q->coalesce, 1));
+        Lane::Block& b = L.blk[L.cur];
+        as_forward_io io;
+        if (rc == AS_OK) {
+            io = block_io(b, h, cap_mode);
+            if (!joins(L.pend, batch, &io, true)) rc = AS_ENOSPC;
         }
-        const bool foreign = !L.pend.empty() && (!L.pend.back().out_host || (L.pend.back().io.forced_dur != nullptr) != (h->forced_dur != nullptr) ||
-                                                 waiting + (size_t)batch->B > 1024 || L.pend.back().frames.empty() != cap_mode ||
-                                                 (cap_mode && L.pend.size() >= (size_t)AS_MAX_SEGMENTS) || !voice_fits);
-        int rc = foreign ? AS_ENOSPC : block_fit(q, L, nt, nr, 2 * nf, batch->B, std::max(q->coalesce, 1));
         if (rc == AS_ENOSPC && attempt <= (int)q->lanes.size()) {
-            rc = flush_lane(q, q->next);                          // (the turn passes on: the submission opens the next lane's group)
+            rc = flush_lane(q, q->next);                          // that group goes out first (the turn passes on: the submission opens the next lane's group)
             if (rc != AS_OK) return rc;
             continue;
         }
         if (rc != AS_OK) return rc;
-        Lane::Block& b = L.blk[L.cur];
         hipStream_t s = q->h2d;
         // the block's previous group (two groups back on this lane) has left it -- its kernels and the copies of its results -- before
         // the first copy of this one lands
@@ -785,28 +699,6 @@ static int lanes_submit_host(as_lanes* q, const as_batch* batch, const as_host_i
             AS_CHECK(hipMemcpy2DAsync(b.mel + b.used_ref, (size_t)b.cap_ref * 4, h->mel, (size_t)h->ld_mel * 4, (size_t)nr * 4, (size_t)n_mels,
                                       hipMemcpyHostToDevice, s));
         }
-        as_forward_io io;
-        memset(&io, 0, sizeof(io));
-        io.tokens = b.tokens + b.used_tok;
-        if (voice) {
-            io.voices = h->voices; io.ld_voice = h->ld_voice; io.n_voices = h->n_voices;
-            io.voice_idx = h->voice_idx ? b.vidx + b.used_vid : nullptr;
-        } else {
-            io.mel = b.mel + b.used_ref; io.ld_mel = b.cap_ref;
-            io.f0_raw = b.f0 + b.used_ref;
-            io.ema_raw = b.ema + b.used_ref; io.ld_ema = b.cap_ref;
-        }
-        if (pros) {
-            io.prosody = b.pros + (size_t)b.used_vid * AS_PROSODY_DIM;
-            io.ld_prosody = AS_PROSODY_DIM;
-        }
-        io.forced_dur = h->forced_dur ? b.forced + b.used_tok : nullptr;
-        io.mel_out = b.out + b.used_out; io.ld_out = b.cap_out;
-        if (cap_mode) {
-            io.frame_cap = h->frame_cap;
-            io.frame_off = b.foff + b.used_utt;
-        }
-        // (a group mixes forced and predicted-from-known-frames submissions only if all or none bring forced durations: `adjacent` says no otherwise)
         b.used_tok += (int)nt; b.used_ref += (int)nr; b.used_out += (int)(2 * nf); b.used_utt += batch->B + 1; b.used_vid += batch->B;
         return lanes_submit(q, batch, &io, nullptr, lane_out, h->mel_out, h->ld_out, cap_mode ? h->frame_off : nullptr);
     }
@@ -827,19 +719,7 @@ extern "C" int64_t as_lanes_merged_calls(const as_lanes* q, int lane)
     return q->lanes[lane].n_merged;
 }
 
-extern "C" int as_lanes_flush(as_lanes* q)
-{
-    if (!q) return AS_EINVAL;
-    try {
-        for (int i = 0; i < (int)q->lanes.size(); ++i) {
-            const int rc = flush_lane(q, i);
-            if (rc != AS_OK) return rc;
-        }
-        return AS_OK;
-    } catch (...) {
-        return (int)hipErrorOutOfMemory;
-    }
-}
+extern "C" int as_lanes_flush(as_lanes* q) { return q ? flush_lanes(q, -1) : AS_EINVAL; }
 
 extern "C" int as_lanes_set_coalesce(as_lanes* q, int k)
 {
@@ -853,7 +733,7 @@ extern "C" int as_lanes_set_coalesce(as_lanes* q, int k)
 extern "C" int as_lanes_set_debug(as_lanes* q, int on)
 {
     if (!q) return AS_EINVAL;
-    const int rc = as_lanes_flush(q);                             // (what waits was submitted without a checksum)
+    const int rc = as_lanes_flush(q);                             // (no group is part summed, part not: what waits goes out as it was submitted)
     if (rc != AS_OK) return rc;
     q->debug = on != 0;
     return AS_OK;

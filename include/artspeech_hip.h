@@ -922,12 +922,17 @@ int as_lanes_set_debug(as_lanes* q, int on);
  * side.  as_lanes_submit_host copies the submission's inputs into the next free column range of the lane's own device block (one block per
  * lane: a group's submissions lie side by side in it, i.e. they are adjacent as as_lanes_set_coalesce wants them, with no gather), launches
  * the group when it is full (coalesce = 1: at once) and copies every submission's mel to ITS host array behind the launch.  A lane keeps
- * TWO such blocks and alternates between them from group to group, with a copy stream of its own for either direction: the copies of a
- * lane's next group run under the kernels of its current one, and a block is refilled only behind the kernels AND the result copies of
- * the group that used it last (events between the lane's three streams; nothing for the caller to keep).  batch->frames must be given (forced durations, or known
- * from an earlier pass).  Pointers are HOST pointers: pinned memory (hipHostMalloc) for copies that do not block the calling thread; the
- * input arrays must stay unchanged and the output array is valid after as_lanes_wait(q, lane) (lane = *lane_out) has returned.  A
- * submission that does not fit behind what waits on its lane's block (or follows a device submission there) sends that group out first. */
+ * TWO such blocks and alternates between them from group to group; the copies run on ONE pair of copy streams, one per direction, that all
+ * lanes share: the copies of a lane's next group run under the kernels of its current one, and a block is refilled only behind the
+ * kernels AND the result copies of the group that used it last (events between the lane's stream and the shared pair; nothing for the
+ * caller to keep).  batch->frames is optional: given (forced durations, or known from an earlier pass), or NULL with frame_cap and
+ * frame_off below (durations predicted on the device).  Pointers are HOST pointers: pinned memory (hipHostMalloc) for copies that do not
+ * block the calling thread; the input arrays must stay unchanged and the output array is valid after as_lanes_wait(q, lane) (lane =
+ * *lane_out) has returned.  Whether a submission joins what waits on its lane is decided by the rule of as_lanes_set_coalesce, applied to
+ * its place in the block: one that does not fit behind the group there, is of the other kind (known frames / a capacity; forced durations
+ * or none; another voice table; prosody or none) or follows a device submission sends that group out first.  Debug mode
+ * (as_lanes_set_debug) does not cover host submissions: their device buffers are the lane's block, which only the library writes, so
+ * there is nothing a caller could overwrite between submit and launch -- no checksum is taken and none is compared. */
 typedef struct as_host_io {
     const int32_t* tokens;                 /* [sum tok_lens] */
     const float* mel; int32_t ld_mel;      /* [n_mels][ld_mel >= sum ref_lens] */

@@ -692,3 +692,70 @@ def test_lanes_frame_capacity_three_unequal_submissions_and_one_too_small():
     lanes.wait()
     check(subs)
     lanes.close()
+
+
+def test_lanes_submit_host_under_debug_mode():
+    """as_lanes_set_debug and as_lanes_submit_host together: a host submission's device buffers are the lane's own block, which no caller
+    can reach -- it gets no checksum at submit and none is looked for when its group goes out.  (The group's launch used to compare a
+    fresh sum against the 0 nobody had written: AS_STATUS_BAD_LAYOUT for every host group under AS_DEBUG=1.)  One lane, k = 2, two host
+    submissions of 2 utterances -- the smallest group that is still a merged call with as_segments -- twice with known frames and twice
+    under a frame capacity: every utterance within 3e-5 of the same batch run alone, the frame offsets equal, no status bit at any point."""
+    import bench
+    from artspeech_amd import _lib, models
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(0)
+    net = _net(dev)
+    solo = _alone(net)
+    per = 2
+    pin = lambda a: torch.from_numpy(a).pin_memory()
+    batches = []
+    for i in range(2):
+        host, _ = bench.make_inputs(None, per, 24, 60, 100, seed0=bench.DATA_SEED + 3300 + i, vary=True)
+        gi = bench.pack_inputs(host, list(range(per)), dev)
+        args = (gi["tok"], gi["tok_lens"], gi["mel"], gi["f0"], gi["ema"], gi["ref_lens"])
+        known = solo.forward_packed(*args, forced=gi["forced"], frames_hint=gi["frames"])["mel"].cpu()
+        ref = solo.forward_packed(*args)                            # predicted durations, read-back path
+        off = ref["frame_off"].cpu()
+        cap = int(1.2 * int(off[-1])) + 3
+        cat = lambda key, ax: np.ascontiguousarray(np.concatenate([host[key][b] for b in range(per)], ax))
+        batches.append(dict(tok=pin(cat("tokens", 0).astype(np.int32)), mel=pin(cat("mel", 1)), f0=pin(cat("f0", 1).reshape(-1)),
+                            ema=pin(cat("ema", 1)), forced=pin(cat("forced", 0).astype(np.int32)), tok_lens=host["tok_lens"],
+                            ref_lens=host["ref_lens"], frames=host["frames"], want=known, want_off=off, want_pred=ref["mel"].cpu(), cap=cap,
+                            out=torch.zeros((80, 2 * sum(host["frames"])), dtype=torch.float32).pin_memory(),
+                            out_cap=torch.zeros((80, 2 * cap), dtype=torch.float32).pin_memory(),
+                            off=torch.zeros(per + 1, dtype=torch.int32).pin_memory()))
+    torch.cuda.synchronize()
+    lanes = models.Lanes(net, 1)
+    try:
+        lanes.set_coalesce(2)
+        lanes.set_debug(True)
+        for r in range(2):
+            for b in batches:
+                b["out"].zero_()
+                lanes.submit_host(b["tok"], b["tok_lens"], b["mel"], b["f0"], b["ema"], b["ref_lens"], b["forced"], b["frames"], b["out"])
+                assert _lib.lib().as_device_status(0) == 0, _lib.device_status()
+            lanes.wait()
+            assert _lib.lib().as_device_status(0) == 0, _lib.device_status()
+            for i, b in enumerate(batches):
+                d = float((b["out"] - b["want"]).abs().max())
+                print(f"known frames, round {r}, batch {i}: max abs {d:.3g}")
+                assert b["out"].shape == b["want"].shape and d <= 3e-5, (r, i, d)
+        for r in range(2):
+            for b in batches:
+                b["out_cap"].zero_()
+                b["off"].zero_()
+                lanes.submit_host(b["tok"], b["tok_lens"], b["mel"], b["f0"], b["ema"], b["ref_lens"], None, None, b["out_cap"],
+                                  frame_cap=b["cap"], frame_off=b["off"])
+                assert _lib.lib().as_device_status(0) == 0, _lib.device_status()
+            lanes.wait()
+            assert _lib.lib().as_device_status(0) == 0, _lib.device_status()
+            for i, b in enumerate(batches):
+                assert torch.equal(b["off"], b["want_off"]), (r, i)
+                n2 = 2 * int(b["want_off"][-1])
+                d = float((b["out_cap"][:, :n2] - b["want_pred"]).abs().max())
+                print(f"frame capacity, round {r}, batch {i}: max abs {d:.3g}")
+                assert d <= 3e-5, (r, i, d)
+        assert lanes.merged_calls(0) == 4                          # every group went out as ONE call of two submissions
+    finally:
+        _lib.lib().as_device_status(1)                             # (a failure here must not stop the tests behind it: the bits are sticky)
+        lanes.close()
