@@ -3,6 +3,10 @@ forwards) as a thin caller of the library's module-level 
 as_forward_test, as_encoder_forward ...).  The launch sequences live in csrc/model.hip; this file packs the reference's padded
 [B, C, L] tensors into packed frames, owns the output tensors and workspaces (PyTorch = device memory and streams), and unpacks.
 
+Every path that hands inputs to the library (``ArtsSpeech.forward_packed``, ``Lanes.submit``, ``Lanes.submit_host``) fills the input half of
+its as_forward_io / as_host_io through ``_fill_inputs``, under one of two pointer rules: ``_dev_ptr`` (on the model's GPU, last axis dense)
+or ``_host_ptr`` (on no GPU, last axis dense).  The module forwards call the library through ``Runtime.call``.
+
 Batched calls give, per utterance, exactly what the reference computes one utterance at a time (its own step="test" is batch-1
 only, models.py:361-362): instance-norm statistics, conv zero padding and the reverse LSTM pass all see the utterance's own
 frames only.
@@ -154,6 +158,12 @@ class Runtime:
             ws = self._ws[slot] = torch.empty(need, dtype=torch.uint8, device=self.device)
         return ws, ws.numel()
 
+    def call(self, name, module, batch, *args, lead=(), slot="m"):
+        """One module-level entry point of the library, `name`(model, plan, *lead, batch, *args, workspace, bytes, stream), on the current
+        stream: the kept workspace of `slot` is sized for `module` on this batch, the status is checked."""
+        ws, nb = self.workspace(slot, module, batch)
+        check(getattr(_lib.lib(), name)(self.model, self.plan, *lead, ctypes.byref(batch), *args, ws.data_ptr(), nb, self.stream()), name)
+
     def drop_retired(self):
         """free the workspaces that were outgrown (only when no captured hipGraph replays into them any more)"""
         self._retired.clear()
@@ -167,7 +177,28 @@ def _dev(t, device, dtype=torch.float32):
 
 
 def _p(t):
+    """the pointer of a tensor this file made itself (outputs, packed copies); a caller's tensor goes through _dev_ptr / _host_ptr"""
     return t.data_ptr() if t is not None else None
+
+
+def _dev_ptr(t, dev):
+    """Pointer rule "device": a tensor on the model's GPU whose last axis is dense (rows of a wider block: ld = stride(0))."""
+    if t is None:
+        return None
+    if not t.is_cuda or t.device != dev:
+        raise _lib.HipLibraryError("expected a tensor on the model's GPU")
+    if t.stride(-1) != 1:
+        raise _lib.HipLibraryError("expected rows that are dense along the column axis")
+    return t.data_ptr()
+
+
+def _host_ptr(t, dev=None):
+    """Pointer rule "host": a tensor that is on no GPU, last axis dense."""
+    if t is None:
+        return None
+    if t.is_cuda or t.stride(-1) != 1:
+        raise _lib.HipLibraryError("expected a host tensor whose rows are dense")
+    return t.data_ptr()
 
 
 def _voice_args(rt, voice, voice_idx, B, device_idx=True):
@@ -189,10 +220,6 @@ def _voice_args(rt, voice, voice_idx, B, device_idx=True):
     return (voice.data_ptr(), voice.stride(0), voice.shape[0], idx.data_ptr() if idx is not None else None), (voice, idx)
 
 
-def _set_voice(io, fields):
-    io.voices, io.ld_voice, io.n_voices, io.voice_idx = fields
-
-
 def _prosody_args(rt, prosody, B, where="device"):
     """prosody -> (pointer, ld_prosody) of as_forward_io / as_host_io and the tensor to keep alive.  prosody: fp32 [B, >= AS_PROSODY_DIM]
     (pipeline.Prosody rows: dur_scale, 12 gains, 12 offsets per utterance), dense rows.  where: "device" -- a tensor on the model's GPU
@@ -211,8 +238,37 @@ def _prosody_args(rt, prosody, B, where="device"):
     return (prosody.data_ptr(), prosody.stride(0)), prosody
 
 
-def _set_prosody(io, fields):
-    io.prosody, io.ld_prosody = fields
+def _fill_inputs(io, rt, B, ptr, where, tok, mel_p, f0_p, ema_p, forced, voice, voice_idx, prosody):
+    """How a call's arguments become the input half of an (empty) as_forward_io / as_host_io, for every call path: tokens, then the voice
+    table (voices / ld_voice / n_voices / voice_idx) or the packed reference (mel / ld_mel / f0_raw / ema_raw / ld_ema), forced_dur and
+    prosody / ld_prosody.  ptr: the rule the caller's tensors are held to (_dev_ptr or _host_ptr; a voice table is always on the device);
+    where: _prosody_args' mode.  -> what has to stay alive while the library may read the struct's pointers."""
+    dev = rt.device
+    io.tokens = ptr(tok, dev)
+    keep_voice = None
+    if voice is not None:
+        (io.voices, io.ld_voice, io.n_voices, io.voice_idx), keep_voice = _voice_args(rt, voice, voice_idx, B, device_idx=where != "host")
+    else:
+        io.mel, io.ld_mel = ptr(mel_p, dev), mel_p.stride(0)
+        io.f0_raw, io.ema_raw, io.ld_ema = ptr(f0_p, dev), ptr(ema_p, dev), ema_p.stride(0)
+    io.forced_dur = ptr(forced, dev)
+    (io.prosody, io.ld_prosody), keep_pros = _prosody_args(rt, prosody, B, where)
+    return tok, mel_p, f0_p, ema_p, forced, keep_voice, keep_pros
+
+
+def _frame_cap_arg(frame_cap, forced, frames):
+    """as_forward_io.frame_cap of a call (None: no capacity); a capacity is for frame counts that only the device knows"""
+    if frame_cap is None:
+        return None
+    if frames is not None or forced is not None:
+        raise _lib.HipLibraryError("frame_cap goes with predicted durations (no frames, no forced durations)")
+    return int(frame_cap)
+
+
+def pack_reference(mels, f0_raw, ema_raw, lens, dev):
+    """the padded reference batch (mels [B, n_mels, T], f0_raw [B, T] or [B, 1, T], ema_raw [B, 10, T]) -> packed device
+    (mel [n_mels][N], f0 [1][N], ema [10][N]) for these lengths"""
+    return pack(mels.to(dev), lens), pack(f0_raw.to(dev).reshape(len(lens), 1, -1), lens), pack(ema_raw.to(dev), lens)
 
 
 def _pack_tokens(x, lens, n_token):
@@ -236,14 +292,10 @@ class RelTransformerEncoder(_Sub):
         self.which = which                    # 0 text_encoder, 1 arts_encoder, 2 durationPredictor.text_encoder
 
     def forward_packed(self, tokens_i32, lens):
-        rt, L = self.rt, _lib.lib()
+        rt = self.rt
         with torch.cuda.device(rt.device):
-            b = rt.batch(tok_lens=lens)
-            N = sum(lens)
-            out = torch.empty((rt.cfg.hidden_dim, max(N, 1)), dtype=torch.float32, device=rt.device)
-            ws, nb = rt.workspace("m", _lib.AS_MOD_ENCODER, b)
-            check(L.as_encoder_forward(rt.model, rt.plan, self.which, ctypes.byref(b), _p(tokens_i32), _p(out), out.stride(0), _p(ws), nb,
-                                       rt.stream()), "as_encoder_forward")
+            out = torch.empty((rt.cfg.hidden_dim, max(sum(lens), 1)), dtype=torch.float32, device=rt.device)
+            rt.call("as_encoder_forward", _lib.AS_MOD_ENCODER, rt.batch(tok_lens=lens), _p(tokens_i32), _p(out), out.stride(0), lead=(self.which,))
         return out
 
     def forward(self, x, x_lengths):
@@ -284,19 +336,17 @@ class StyleEncoder(_Sub):
         return f0, ema
 
     def forward(self, mel, mel_input_length, step="second", distribution=None, epoch=20, features=None):
-        rt, L = self.rt, _lib.lib()
+        rt = self.rt
         dev = rt.device
         lens = [int(v) for v in mel_input_length]
         f0_raw, ema_raw = self._extract(mel, features, lens)
         with torch.cuda.device(dev):
             lay = layout(lens, dev)
-            mel_p, f0_p, ema_p = pack(mel.to(dev), lens), pack(f0_raw.to(dev).reshape(len(lens), 1, -1), lens), pack(ema_raw.to(dev), lens)
-            b = rt.batch(ref_lens=lens)
+            mel_p, f0_p, ema_p = pack_reference(mel, f0_raw, ema_raw, lens, dev)
             feat12 = torch.empty((12, max(lay.N, 1)), dtype=torch.float32, device=dev)
             style = torch.empty((len(lens), 2 * rt.cfg.style_dim), dtype=torch.float32, device=dev)
-            ws, nb = rt.workspace("m", _lib.AS_MOD_STYLE, b)
-            check(L.as_style_forward(rt.model, rt.plan, ctypes.byref(b), _p(mel_p), mel_p.stride(0), _p(f0_p), _p(ema_p), ema_p.stride(0),
-                                     _p(feat12), feat12.stride(0), _p(style), _p(ws), nb, rt.stream()), "as_style_forward")
+            rt.call("as_style_forward", _lib.AS_MOD_STYLE, rt.batch(ref_lens=lens), _p(mel_p), mel_p.stride(0), _p(f0_p), _p(ema_p),
+                    ema_p.stride(0), _p(feat12), feat12.stride(0), _p(style))
         return unpack(feat12[1:2], lay), unpack(feat12[0:1], lay), unpack(feat12[2:12], lay), style
 
 
@@ -304,17 +354,14 @@ class DurationPredictor(_Sub):
     """models.py:519-571.  forward(texts [B,N], style=ema_ext [B,10,T], text_lengths, mel_input_length) -> [B,N]."""
 
     def forward(self, texts, style, text_lengths, mel_input_length):
-        rt, L = self.rt, _lib.lib()
+        rt = self.rt
         dev = rt.device
         tl, ml = [int(v) for v in text_lengths], [int(v) for v in mel_input_length]
         with torch.cuda.device(dev):
             tok = _dev(_pack_tokens(texts, tl, rt.cfg.n_token), dev, torch.int32)
             ema_p = pack(style.to(dev), ml)
-            b = rt.batch(tok_lens=tl, ref_lens=ml)
             dur = torch.empty((1, max(sum(tl), 1)), dtype=torch.float32, device=dev)
-            ws, nb = rt.workspace("m", _lib.AS_MOD_DURATION, b)
-            check(L.as_duration_forward(rt.model, rt.plan, ctypes.byref(b), _p(tok), _p(ema_p), ema_p.stride(0), _p(dur), _p(ws), nb,
-                                        rt.stream()), "as_duration_forward")
+            rt.call("as_duration_forward", _lib.AS_MOD_DURATION, rt.batch(tok_lens=tl, ref_lens=ml), _p(tok), _p(ema_p), ema_p.stride(0), _p(dur))
         return unpack(dur, layout(tl, dev))[:, 0, :]
 
 
@@ -322,7 +369,7 @@ class ArtsPredictor(_Sub):
     """models.py:573-621.  forward(A_ens [B,512,M], style [B,512]) -> F0 [B,1,2M], N [B,1,2M], EMA [B,10,2M]."""
 
     def forward(self, A_ens, style, lengths=None):
-        rt, L = self.rt, _lib.lib()
+        rt = self.rt
         dev = rt.device
         lens = [A_ens.shape[-1]] * A_ens.shape[0] if lengths is None else [int(v) for v in lengths]
         with torch.cuda.device(dev):
@@ -330,10 +377,7 @@ class ArtsPredictor(_Sub):
             st = _dev(style, dev)
             n2 = 2 * sum(lens)
             f0, n, ema = (torch.empty((c, max(n2, 1)), dtype=torch.float32, device=dev) for c in (1, 1, 10))
-            b = rt.batch(frames=lens)
-            ws, nb = rt.workspace("m", _lib.AS_MOD_ARTS, b)
-            check(L.as_arts_forward(rt.model, rt.plan, ctypes.byref(b), _p(a), a.stride(0), _p(st), _p(f0), _p(n), _p(ema), f0.stride(0), _p(ws),
-                                    nb, rt.stream()), "as_arts_forward")
+            rt.call("as_arts_forward", _lib.AS_MOD_ARTS, rt.batch(frames=lens), _p(a), a.stride(0), _p(st), _p(f0), _p(n), _p(ema), f0.stride(0))
         lay2 = layout([2 * l for l in lens], dev)
         return unpack(f0, lay2), unpack(n, lay2), unpack(ema, lay2)
 
@@ -342,7 +386,7 @@ class Decoder(_Sub):
     """models.py:474-517.  forward(asr [B,512,M], Style [B,512], F0 [B,1,2M], N [B,1,2M], EMA [B,10,2M]) -> [B,80,2M]."""
 
     def forward(self, asr, Style, F0, N, EMA, lengths=None):
-        rt, L = self.rt, _lib.lib()
+        rt = self.rt
         dev = rt.device
         lens = [asr.shape[-1]] * asr.shape[0] if lengths is None else [int(v) for v in lengths]
         l2 = [2 * l for l in lens]
@@ -351,10 +395,8 @@ class Decoder(_Sub):
             st = _dev(Style, dev)
             f0, n, ema = pack(F0.to(dev), l2), pack(N.to(dev), l2), pack(EMA.to(dev), l2)
             mel = torch.empty((rt.cfg.n_mels, max(sum(l2), 1)), dtype=torch.float32, device=dev)
-            b = rt.batch(frames=lens)
-            ws, nb = rt.workspace("m", _lib.AS_MOD_DECODER, b)
-            check(L.as_decoder_forward(rt.model, rt.plan, ctypes.byref(b), _p(a), a.stride(0), _p(st), _p(f0), _p(n), _p(ema), f0.stride(0),
-                                       _p(mel), mel.stride(0), _p(ws), nb, rt.stream()), "as_decoder_forward")
+            rt.call("as_decoder_forward", _lib.AS_MOD_DECODER, rt.batch(frames=lens), _p(a), a.stride(0), _p(st), _p(f0), _p(n), _p(ema),
+                    f0.stride(0), _p(mel), mel.stride(0))
         return unpack(mel, layout(l2, dev))
 
 
@@ -405,24 +447,18 @@ class ArtsSpeech(_Module):
         if self.rt is None:
             raise RuntimeError("no weights loaded: call load_checkpoint / load_state_dict first")
         ml = [int(v) for v in mel_input_length]
-        B = len(ml)
         f0_raw, ema_raw = self.style_encoder._extract(mels, features, ml)
         with torch.cuda.device(self.device):
-            mel_p = pack(mels.to(self.device), ml)
-            f0_p = pack(f0_raw.to(self.device).reshape(B, 1, -1), ml)
-            ema_p = pack(ema_raw.to(self.device), ml)
-            return self.compute_voice_packed(mel_p, f0_p, ema_p, ml)
+            return self.compute_voice_packed(*pack_reference(mels, f0_raw, ema_raw, ml, self.device), ml)
 
     def compute_voice_packed(self, mel_p, f0_p, ema_p, ref_lens):
         """compute_voice on packed reference features (mel [n_mels][>= N], f0 [1][N], ema [10][>= N]) -> [B, voice_dim]"""
-        rt, L = self.rt, _lib.lib()
+        rt = self.rt
         ref_lens = [int(v) for v in ref_lens]
         with torch.cuda.device(rt.device):
-            b = rt.batch(ref_lens=ref_lens)
             v = torch.empty((len(ref_lens), rt.voice_dim), dtype=torch.float32, device=rt.device)
-            ws, nb = rt.workspace("v", _lib.AS_MOD_VOICE, b)
-            check(L.as_voice_forward(rt.model, rt.plan, ctypes.byref(b), _p(mel_p), mel_p.stride(0), _p(f0_p), _p(ema_p), ema_p.stride(0), _p(v),
-                                     v.stride(0), _p(ws), nb, rt.stream()), "as_voice_forward")
+            rt.call("as_voice_forward", _lib.AS_MOD_VOICE, rt.batch(ref_lens=ref_lens), _p(mel_p), mel_p.stride(0), _p(f0_p), _p(ema_p),
+                    ema_p.stride(0), _p(v), v.stride(0), slot="v")
         return v
 
     def forward(self, batch, s2s_attn=None, s2s_attn_mono=None, step="test", mode="train", epoch=0, features=None,
@@ -439,17 +475,14 @@ class ArtsSpeech(_Module):
         dev = self.device
         tl = [int(v) for v in input_lengths]
         B = len(tl)
-        if voice is not None:
-            ml, mel_p, f0_p, ema_p = None, None, None, None
-        else:
+        ml, mel_p, f0_p, ema_p = None, None, None, None
+        if voice is None:
             ml = [int(v) for v in mel_input_length]
             f0_raw, ema_raw = self.style_encoder._extract(mels, features, ml)
         with torch.cuda.device(dev):
             tok = _dev(_pack_tokens(texts, tl, self.rt.cfg.n_token), dev, torch.int32)
             if voice is None:
-                mel_p = pack(mels.to(dev), ml)
-                f0_p = pack(f0_raw.to(dev).reshape(B, 1, -1), ml)
-                ema_p = pack(ema_raw.to(dev), ml)
+                mel_p, f0_p, ema_p = pack_reference(mels, f0_raw, ema_raw, ml, dev)
             forced, frames = None, None
             if forced_durations is not None:
                 fd = [torch.as_tensor(forced_durations[b])[: tl[b]].reshape(-1) for b in range(B)]
@@ -470,11 +503,11 @@ class ArtsSpeech(_Module):
         frame_cap (predicted durations only): the half-rate frames to make room for, all utterances together -- ONE as_forward_test call
         with no read-back (capturable); the result's `frame_off` (device, [B + 1]) says where each utterance's frames lie in `mel`
         [n_mels][2 frame_cap], `frames` is None; more frames than room raises the AS_STATUS_CAPACITY bit (as_device_status).
+        Every tensor handed in is on the model's GPU with a dense last axis (2-D ones may be column ranges of a wider block), else
+        HipLibraryError.  forced or frames_hint together with frame_cap raises HipLibraryError.
         voice / voice_idx: voice mode (see `forward`); mel_p / f0_p / ema_p / ref_lens are then not read (None).
         prosody: [B, 25] per-utterance controls (see `forward`; a device tensor is read as it is, anything else is copied to the GPU).
         With frames_hint given, the frames must be the sums of the SCALED durations."""
-        if frame_cap is not None:
-            return self._forward_packed_cap(tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, int(frame_cap), aux, out, voice, voice_idx, prosody)
         rt, L = self.rt, _lib.lib()
         dev = rt.device
         tok_lens = [int(v) for v in tok_lens]
@@ -482,16 +515,9 @@ class ArtsSpeech(_Module):
         B, Nt, Nr, C = len(tok_lens), sum(tok_lens), sum(ref_lens or []), rt.cfg.hidden_dim
         with torch.cuda.device(dev):
             io = _lib.ForwardIO()
-            io.tokens = _p(tok)
-            if voice is not None:
-                fields, keep_voice = _voice_args(rt, voice, voice_idx, B)
-                _set_voice(io, fields)
-            else:
-                io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
-                io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
-            io.forced_dur = _p(forced)
-            pfields, keep_pros = _prosody_args(rt, prosody, B, "any")
-            _set_prosody(io, pfields)
+            # (_keep: converted copies of voice_idx / prosody, referenced until the call is enqueued)
+            _keep = _fill_inputs(io, rt, B, _dev_ptr, "any", tok, mel_p, f0_p, ema_p, forced, voice, voice_idx, prosody)
+            cap = _frame_cap_arg(frame_cap, forced, frames_hint)
             res = out if out is not None else {}
 
             def new(key, shape, dtype=torch.float32):
@@ -513,75 +539,33 @@ class ArtsSpeech(_Module):
             ws_a, na = rt.workspace("a", _lib.AS_MOD_FORWARD_A_VOICE if voice is not None else _lib.AS_MOD_FORWARD_A, ba)
             s = rt.stream()
             frames = frames_hint
-            if frames is None:
-                check(L.as_forward_test_begin(rt.model, rt.plan, ctypes.byref(ba), ctypes.byref(io), _p(ws_a), na, s), "as_forward_test_begin")
-                off = res["frame_off"].cpu().tolist()                            # the one device->host sync
-                frames = [off[b + 1] - off[b] for b in range(B)]
-                ba = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=frames)
-            frames = [int(f) for f in frames]
-            n2 = 2 * sum(frames)
-            io.mel_out, io.ld_out = _p(new("mel", (rt.cfg.n_mels, max(n2, 1)))), max(n2, 1)
+            if cap is not None:
+                io.frame_cap, n2, mod_b = cap, 2 * cap, _lib.AS_MOD_FORWARD_B_CAP
+                bb = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=[cap] + [0] * (B - 1))     # (only the sum counts)
+            else:
+                if frames is None:
+                    check(L.as_forward_test_begin(rt.model, rt.plan, ctypes.byref(ba), ctypes.byref(io), _p(ws_a), na, s), "as_forward_test_begin")
+                    off = res["frame_off"].cpu().tolist()                        # the one device->host sync
+                    frames = [off[b + 1] - off[b] for b in range(B)]
+                    ba = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=frames)
+                frames = [int(f) for f in frames]
+                n2 = max(2 * sum(frames), 1)
+                bb, mod_b = ba, _lib.AS_MOD_FORWARD_B
+            io.mel_out, io.ld_out = _p(new("mel", (rt.cfg.n_mels, n2))), n2
             if aux:
-                io.F0, io.N, io.EMA = _p(new("F0", (1, max(n2, 1)))), _p(new("N", (1, max(n2, 1)))), _p(new("EMA", (10, max(n2, 1))))
-                io.ld_pred = max(n2, 1)
-            ws_b, nb = rt.workspace("b", _lib.AS_MOD_FORWARD_B, ba)
-            if frames_hint is None:
+                io.F0, io.N, io.EMA, io.ld_pred = _p(new("F0", (1, n2))), _p(new("N", (1, n2))), _p(new("EMA", (10, n2))), n2
+            ws_b, nb = rt.workspace("b", mod_b, bb)
+            if cap is None and frames_hint is None:
                 check(L.as_forward_test_finish(rt.model, rt.plan, ctypes.byref(ba), ctypes.byref(io), _p(ws_a), na, _p(ws_b), nb, s),
                       "as_forward_test_finish")
             else:
                 check(L.as_forward_test(rt.model, rt.plan, ctypes.byref(ba), ctypes.byref(io), _p(ws_a), na, _p(ws_b), nb, None, s),
                       "as_forward_test")
-            res["frames"], res["frames2"] = frames, [2 * f for f in frames]
+            if cap is not None:
+                res["frames"], res["frames2"], res["frame_cap"] = None, None, cap
+            else:
+                res["frames"], res["frames2"] = frames, [2 * f for f in frames]
         return res
-
-
-def _forward_packed_cap(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, frame_cap, aux, out, voice=None, voice_idx=None, prosody=None):
-    rt, L = self.rt, _lib.lib()
-    dev = rt.device
-    tok_lens = [int(v) for v in tok_lens]
-    ref_lens = None if voice is not None else [int(v) for v in ref_lens]
-    B, Nt, Nr, C = len(tok_lens), sum(tok_lens), sum(ref_lens or []), rt.cfg.hidden_dim
-    with torch.cuda.device(dev):
-        io = _lib.ForwardIO()
-        io.tokens = _p(tok)
-        if voice is not None:
-            fields, keep_voice = _voice_args(rt, voice, voice_idx, B)
-            _set_voice(io, fields)
-        else:
-            io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
-            io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
-        io.frame_cap = frame_cap
-        pfields, keep_pros = _prosody_args(rt, prosody, B, "any")
-        _set_prosody(io, pfields)
-        res = out if out is not None else {}
-
-        def new(key, shape, dtype=torch.float32):
-            t = res.get(key)
-            if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev:
-                t = res[key] = torch.empty(shape, dtype=dtype, device=dev)
-            return t
-        n2 = 2 * frame_cap
-        io.dur_i, io.frame_off = _p(new("dur_i", (max(Nt, 1),), torch.int32)), _p(new("frame_off", (B + 1,), torch.int32))
-        io.mel_out, io.ld_out = _p(new("mel", (rt.cfg.n_mels, n2))), n2
-        if aux:
-            io.duration = _p(new("duration", (1, max(Nt, 1))))
-            io.style = _p(new("style", (B, 2 * rt.cfg.style_dim)))
-            if voice is None:
-                io.feat12, io.ld_feat = _p(new("feat12", (12, max(Nr, 1)))), max(Nr, 1)
-            io.t_en, io.a_en, io.ld_en = _p(new("t_en", (C, max(Nt, 1)))), _p(new("a_en", (C, max(Nt, 1)))), max(Nt, 1)
-            io.F0, io.N, io.EMA = _p(new("F0", (1, n2))), _p(new("N", (1, n2))), _p(new("EMA", (10, n2)))
-            io.ld_pred = n2
-        ba = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens)
-        ws_a, na = rt.workspace("a", _lib.AS_MOD_FORWARD_A_VOICE if voice is not None else _lib.AS_MOD_FORWARD_A, ba)
-        bc = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=[frame_cap] + [0] * (B - 1))     # (only the sum counts)
-        ws_b, nb = rt.workspace("b", _lib.AS_MOD_FORWARD_B_CAP, bc)
-        check(L.as_forward_test(rt.model, rt.plan, ctypes.byref(ba), ctypes.byref(io), _p(ws_a), na, _p(ws_b), nb, None, rt.stream()),
-              "as_forward_test")
-        res["frames"], res["frames2"], res["frame_cap"] = None, None, frame_cap
-    return res
-
-
-ArtsSpeech._forward_packed_cap = _forward_packed_cap
 
 
 class Lanes:
@@ -633,14 +617,6 @@ class Lanes:
         prosody: a DEVICE fp32 [B, 25] tensor of per-utterance controls (ArtsSpeech.forward), read when the group runs (rewriting it changes
         what a replayed graph computes).  Adjacent: row ranges of one table that continue each other; a submission with prosody never
         joins one without."""
-        def _p(t):                                                  # (rows of a wider block: only the last axis has to be dense)
-            if t is None:
-                return None
-            if not t.is_cuda or t.device != dev:
-                raise _lib.HipLibraryError("expected a tensor on the model's GPU")
-            if t.stride(-1) != 1:
-                raise _lib.HipLibraryError("expected rows that are dense along the column axis")
-            return t.data_ptr()
         rt, L = self.rt, _lib.lib()
         dev = rt.device
         tok_lens = [int(v) for v in tok_lens]
@@ -649,46 +625,35 @@ class Lanes:
         res = out if out is not None else {}
         with torch.cuda.device(dev):
             io = _lib.ForwardIO()
-            io.tokens = _p(tok)
-            keep_voice = None
-            if voice is not None:
-                if voice_idx is not None and (not torch.is_tensor(voice_idx) or voice_idx.dtype != torch.int32 or voice_idx.device != dev):
-                    raise _lib.HipLibraryError("voice_idx: expected an int32 tensor on the model's GPU (it is read when the group runs)")
-                fields, keep_voice = _voice_args(rt, voice, voice_idx, B)
-                _set_voice(io, fields)
-            else:
-                io.mel, io.ld_mel = _p(mel_p), mel_p.stride(0)
-                io.f0_raw, io.ema_raw, io.ld_ema = _p(f0_p), _p(ema_p), ema_p.stride(0)
-            io.forced_dur = _p(forced)
-            pfields, keep_pros = _prosody_args(rt, prosody, B, "device")
-            _set_prosody(io, pfields)
-            n2 = 2 * sum(int(f) for f in frames) if frames is not None else (2 * int(frame_cap) if frame_cap is not None else int(capacity))
-            if frame_cap is not None:
-                if frames is not None or forced is not None:
-                    raise _lib.HipLibraryError("frame_cap goes with predicted durations (no frames, no forced durations)")
-                io.frame_cap = int(frame_cap)
+            # (the struct's pointer is what a replayed graph reads: a converted copy of the indices would be the wrong tensor)
+            if voice is not None and voice_idx is not None and \
+                    (not torch.is_tensor(voice_idx) or voice_idx.dtype != torch.int32 or voice_idx.device != dev):
+                raise _lib.HipLibraryError("voice_idx: expected an int32 tensor on the model's GPU (it is read when the group runs)")
+            keep = _fill_inputs(io, rt, B, _dev_ptr, "device", tok, mel_p, f0_p, ema_p, forced, voice, voice_idx, prosody)
+            cap = _frame_cap_arg(frame_cap, forced, frames)
+            n2 = 2 * sum(int(f) for f in frames) if frames is not None else (2 * cap if cap is not None else int(capacity))
+            if cap is not None:
+                io.frame_cap = cap
             if "mel" not in res:
                 res["mel"] = torch.empty((rt.cfg.n_mels, max(n2, 1)), dtype=torch.float32, device=dev)
             # a submission that a lane may hold back for its group (frames known, coalescing on) has no per-submission home for the
             # optional outputs; every other one -- predicted durations above all, where frame_off is the only record of the split -- has
-            can_merge = self.coalesce > 1 and (frames is not None or frame_cap is not None)
+            can_merge = self.coalesce > 1 and (frames is not None or cap is not None)
             if not can_merge and "dur_i" not in res:
                 res["dur_i"] = torch.empty((max(Nt, 1),), dtype=torch.int32, device=dev)
-            if (not can_merge or frame_cap is not None) and "frame_off" not in res:
+            if (not can_merge or cap is not None) and "frame_off" not in res:
                 res["frame_off"] = torch.empty((B + 1,), dtype=torch.int32, device=dev)
-            io.mel_out, io.ld_out = _p(res["mel"]), res["mel"].stride(0)
+            io.mel_out, io.ld_out = _dev_ptr(res["mel"], dev), res["mel"].stride(0)             # (a caller's own view, perhaps)
             if not can_merge:
-                io.dur_i = _p(res["dur_i"])
-            if not can_merge or frame_cap is not None:            # (under a capacity every submission of a merged call gets its own frame_off)
-                io.frame_off = _p(res["frame_off"])
+                io.dur_i = _dev_ptr(res["dur_i"], dev)
+            if not can_merge or cap is not None:                  # (under a capacity every submission of a merged call gets its own frame_off)
+                io.frame_off = _dev_ptr(res["frame_off"], dev)
             ba = rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=frames)
             fr = (ctypes.c_int32 * B)()
             lane = ctypes.c_int32(-1)
             check(L.as_lanes_submit(self.h, ctypes.byref(ba), ctypes.byref(io), fr, ctypes.byref(lane)), "as_lanes_submit")
-            res["frames"] = None if frame_cap is not None else ([int(v) for v in fr] if frames is None else [int(f) for f in frames])
-            # (a lane's last group of submissions stays referenced: its launch may still be reading them)
-            prev = self._keep[lane.value] or []
-            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, res, keep_voice, keep_pros)])[-2 * max(self.coalesce, 1):]
+            res["frames"] = None if cap is not None else ([int(v) for v in fr] if frames is None else [int(f) for f in frames])
+            self._retain(lane.value, ba, io, res, keep)
         return lane.value, res
 
     def set_debug(self, on=True):
@@ -704,37 +669,24 @@ class Lanes:
         voice: a DEVICE table that stays resident (keep it unchanged until `wait`); voice_idx: HOST integers [B] (copied into the lane's
         block with the tokens) or None = row b; mel_p / f0_p / ema_p / ref_lens are then not read.
         prosody: a HOST fp32 [B, 25] tensor of per-utterance controls, copied into the lane's block with the tokens."""
-        def _h(t):
-            if t is None:
-                return None
-            if t.is_cuda or t.stride(-1) != 1:
-                raise _lib.HipLibraryError("expected a host tensor whose rows are dense")
-            return t.data_ptr()
         tok_lens = [int(v) for v in tok_lens]
         ref_lens = None if voice is not None else [int(v) for v in ref_lens]
         frames = [int(v) for v in frames] if frames is not None else None
         with torch.cuda.device(self.rt.device):
             io = _lib.HostIO()
             if frames is None:
-                io.frame_cap, io.frame_off = int(frame_cap), _h(frame_off)
-            io.tokens = _h(tok)
-            keep_voice = None
-            if voice is not None:
-                fields, keep_voice = _voice_args(self.rt, voice, voice_idx, len(tok_lens), device_idx=False)
-                _set_voice(io, fields)
-            else:
-                io.mel, io.ld_mel = _h(mel_p), mel_p.stride(0)
-                io.f0_raw, io.ema_raw, io.ld_ema = _h(f0_p), _h(ema_p), ema_p.stride(0)
-            io.forced_dur = _h(forced)
-            pfields, keep_pros = _prosody_args(self.rt, prosody, len(tok_lens), "host")
-            _set_prosody(io, pfields)
-            io.mel_out, io.ld_out = _h(out_mel), out_mel.stride(0)
+                io.frame_cap, io.frame_off = int(frame_cap), _host_ptr(frame_off)
+            keep = _fill_inputs(io, self.rt, len(tok_lens), _host_ptr, "host", tok, mel_p, f0_p, ema_p, forced, voice, voice_idx, prosody)
+            io.mel_out, io.ld_out = _host_ptr(out_mel), out_mel.stride(0)
             ba = self.rt.batch(tok_lens=tok_lens, ref_lens=ref_lens, frames=frames)
             lane = ctypes.c_int32(-1)
             check(_lib.lib().as_lanes_submit_host(self.h, ctypes.byref(ba), ctypes.byref(io), ctypes.byref(lane)), "as_lanes_submit_host")
-            prev = self._keep[lane.value] or []
-            self._keep[lane.value] = (prev + [(ba, io, tok, mel_p, f0_p, ema_p, forced, out_mel, frame_off, keep_voice, keep_pros)])[-2 * max(self.coalesce, 1):]
+            self._retain(lane.value, ba, io, out_mel, frame_off, keep)
         return lane.value
+
+    def _retain(self, lane, *objs):
+        """what a submission's launch may still be reading stays referenced: a lane's last two groups of submissions"""
+        self._keep[lane] = ((self._keep[lane] or []) + [objs])[-2 * max(self.coalesce, 1):]
 
     def wait(self, lane=-1):
         check(_lib.lib().as_lanes_wait(self.h, lane), "as_lanes_wait")

@@ -290,6 +290,35 @@ class ArtSpeech:
         wav = (self.generator(mel, lengths=lens, pcm16=True) if pcm16 else self.generator(mel, lengths=lens))[:, 0]
         return wav[0] if single else wav
 
+    def _padded_batch(self, phonemes, ref_mel, features):
+        """One utterance or lists of B -> (text [B, max N] token ids (test.py:96-97), tok_lens, mels [B, n_mels, max T], ref_lens,
+        (f0 [B, 1, max T], ema [B, 10, max T])), zero padded; without ref_mel the last three are None, without features the last one.
+        f0 is None (the attached pitch extractor computes it) when any utterance's is."""
+        if isinstance(phonemes, str):
+            phonemes, ref_mel, features = [phonemes], None if ref_mel is None else [ref_mel], None if features is None else [features]
+        ids = [torch.LongTensor(self.textcleaner(p)) for p in phonemes]
+        B, tl = len(ids), [len(i) for i in ids]
+        text = torch.zeros(B, max(tl), dtype=torch.long)
+        for b in range(B):
+            text[b, : tl[b]] = ids[b]
+        if ref_mel is None:
+            return text, tl, None, None, None
+        ml = [int(m.shape[-1]) for m in ref_mel]
+        tmax = max(ml)
+        mels = torch.zeros(B, ref_mel[0].shape[0], tmax)
+        for b in range(B):
+            mels[b, :, : ml[b]] = torch.as_tensor(ref_mel[b])
+        feats = None
+        if features is not None:
+            f0 = None if any(f is None for f, _ in features) else torch.zeros(B, 1, tmax)
+            ema = torch.zeros(B, 10, tmax)
+            for b, (f, e) in enumerate(features):
+                if f0 is not None:
+                    f0[b, :, : f.shape[-1]] = torch.as_tensor(f).reshape(1, -1)
+                ema[b, :, : e.shape[-1]] = torch.as_tensor(e)
+            feats = (f0, ema)
+        return text, tl, mels, ml, feats
+
     def packed_inputs(self, phonemes, ref_mel=None, features=None, voice=None, prosody=None):
         """The keyword arguments of ArtsSpeech.forward_packed for these utterances (what ArtsSpeech.forward builds before the model call):
         packed device tokens and either the packed reference features or the voice table; prosody rows on the device."""
@@ -297,16 +326,9 @@ class ArtSpeech:
             raise ValueError("synthesis needs exactly one of ref_mel and voice")
         net = self.model.ArtsSpeech
         dev = net.device
-        if isinstance(phonemes, str):
-            phonemes, ref_mel = [phonemes], None if ref_mel is None else [ref_mel]
-            if features is not None:
-                features = [features]
-        ids = [torch.LongTensor(self.textcleaner(p)) for p in phonemes]
-        B, tl = len(ids), [len(i) for i in ids]
-        text = torch.zeros(B, max(tl), dtype=torch.long)
-        for b in range(B):
-            text[b, : tl[b]] = ids[b]
-        kw = dict(tok_lens=tl, mel_p=None, f0_p=None, ema_p=None, ref_lens=None)
+        text, tl, mels, ml, feats = self._padded_batch(phonemes, ref_mel, features)
+        B = len(tl)
+        kw = dict(tok_lens=tl, mel_p=None, f0_p=None, ema_p=None, ref_lens=ml)
         with torch.cuda.device(dev):
             kw["tok"] = models._dev(models._pack_tokens(text, tl, net.rt.cfg.n_token), dev, torch.int32)
             if prosody is not None:
@@ -315,25 +337,8 @@ class ArtSpeech:
                 table, vidx = self._voice_table(voice, B)
                 kw["voice"], kw["voice_idx"] = table, vidx.to(dev)        # (on the device already: a captured call copies nothing)
                 return kw
-            ml = [int(m.shape[-1]) for m in ref_mel]
-            tmax = max(ml)
-            mels = torch.zeros(B, ref_mel[0].shape[0], tmax)
-            for b in range(B):
-                mels[b, :, : ml[b]] = torch.as_tensor(ref_mel[b])
-            feats = None
-            if features is not None:
-                f0 = None if any(f is None for f, _ in features) else torch.zeros(B, 1, tmax)
-                ema = torch.zeros(B, 10, tmax)
-                for b, (f, e) in enumerate(features):
-                    if f0 is not None:
-                        f0[b, :, : f.shape[-1]] = torch.as_tensor(f).reshape(1, -1)
-                    ema[b, :, : e.shape[-1]] = torch.as_tensor(e)
-                feats = (f0, ema)
             f0_raw, ema_raw = net.style_encoder._extract(mels, feats, ml)
-            kw["mel_p"] = models.pack(mels.to(dev), ml)
-            kw["f0_p"] = models.pack(f0_raw.to(dev).reshape(B, 1, -1), ml)
-            kw["ema_p"] = models.pack(ema_raw.to(dev), ml)
-            kw["ref_lens"] = ml
+            kw["mel_p"], kw["f0_p"], kw["ema_p"] = models.pack_reference(mels, f0_raw, ema_raw, ml, dev)
         return kw
 
     def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None):
@@ -404,43 +409,13 @@ class ArtSpeech:
             for b, p in enumerate(parts):
                 out[b, :, : p.shape[1]] = p
             return out
-        if isinstance(phonemes, str):
-            phonemes, ref_mel = [phonemes], None if ref_mel is None else [ref_mel]
-            if features is not None:
-                features = [features]
-        ids = [torch.LongTensor(self.textcleaner(p)) for p in phonemes]               # test.py:96-97
-        B = len(ids)
+        text, tl, mels, ml, feats = self._padded_batch(phonemes, ref_mel, features)
+        B = len(tl)
         rows = None if prosody is None else Prosody.rows(prosody, B, self.model.ArtsSpeech)
-        if voice is not None:
-            table, vidx = self._voice_table(voice, B)
-            nmax = max(len(i) for i in ids)
-            text = torch.zeros(B, nmax, dtype=torch.long)
-            for b in range(B):
-                text[b, : len(ids[b])] = ids[b]
-            mel, aux = self.model.ArtsSpeech([text, torch.LongTensor([len(i) for i in ids]), None, None], None, None, step="test",
-                                             forced_durations=forced_durations, return_aux=True, voice=table, voice_idx=vidx, prosody=rows)
-            self._last_frames = list(aux["frames2"])
-            return mel
-        nmax, tmax = max(len(i) for i in ids), max(m.shape[-1] for m in ref_mel)
-        text = torch.zeros(B, nmax, dtype=torch.long)
-        mels = torch.zeros(B, ref_mel[0].shape[0], tmax)
-        for b in range(B):
-            text[b, : len(ids[b])] = ids[b]
-            mels[b, :, : ref_mel[b].shape[-1]] = torch.as_tensor(ref_mel[b])
-        input_lengths = torch.LongTensor([len(i) for i in ids])                       # test.py:110
-        mel_input_length = torch.LongTensor([m.shape[-1] for m in ref_mel])           # test.py:111
-        feats = None
-        if features is not None:
-            f0 = None if any(f is None for f, _ in features) else torch.zeros(B, 1, tmax)     # None: the attached JDCNet
-            ema = torch.zeros(B, 10, tmax)
-            for b, (f, e) in enumerate(features):
-                if f0 is not None:
-                    f0[b, :, : f.shape[-1]] = torch.as_tensor(f).reshape(1, -1)
-                ema[b, :, : e.shape[-1]] = torch.as_tensor(e)
-            feats = (f0, ema)
-        mel, aux = self.model.ArtsSpeech([text, input_lengths, mels, mel_input_length, None, None, None], None, None,
-                                         step="test", features=feats, forced_durations=forced_durations, return_aux=True,
-                                         prosody=rows)                                                                    # test.py:113
+        table, vidx = (None, None) if voice is None else self._voice_table(voice, B)
+        batch = [text, torch.LongTensor(tl), mels, None if ml is None else torch.LongTensor(ml), None, None, None]     # test.py:110-111
+        mel, aux = self.model.ArtsSpeech(batch, None, None, step="test", features=feats, forced_durations=forced_durations,
+                                         return_aux=True, voice=table, voice_idx=vidx, prosody=rows)                  # test.py:113
         self._last_frames = list(aux["frames2"])
         return mel
 

@@ -301,7 +301,8 @@ def test_lanes_with_prosody(cuda):
 
 
 def test_prosody_argument_errors(cuda, monkeypatch):
-    """AS_EINVAL for ld_prosody < 25 and for prosody together with forced durations, from the C entry points and from the lanes"""
+    """AS_EINVAL for ld_prosody < 25 and for prosody together with forced durations, from the C entry points and from the lanes;
+    forward_packed refuses a host tensor and strided columns, and a frame capacity together with known frame counts or forced durations"""
     net = get_net(64, 8, cuda)
     host, g = inputs(cuda, 2, 7500)
     rows = identity_rows(2, cuda)
@@ -320,6 +321,15 @@ def test_prosody_argument_errors(cuda, monkeypatch):
         lanes.submit_host(g["tok"].cpu(), host["tok_lens"], g["mel"].cpu(), g["f0"].cpu(), g["ema"].cpu(), host["ref_lens"], g["forced"].cpu(),
                           host["frames"], torch.zeros(80, 2 * sum(host["frames"])), prosody=rows.cpu())
     lanes.close()
+    # forward_packed holds its tensors to the lanes' device rule, and a frame capacity goes with predicted durations only
+    with pytest.raises(_lib.HipLibraryError, match="on the model's GPU"):
+        net.forward_packed(g["tok"], host["tok_lens"], g["mel"].cpu(), g["f0"], g["ema"], host["ref_lens"])
+    wide = torch.zeros(g["mel"].shape[0], 2 * g["mel"].shape[1], device=cuda)
+    with pytest.raises(_lib.HipLibraryError, match="dense along the column axis"):
+        net.forward_packed(g["tok"], host["tok_lens"], wide[:, ::2], g["f0"], g["ema"], host["ref_lens"])
+    for kw in ({"forced": g["forced"], "frames_hint": host["frames"]}, {"frames_hint": host["frames"]}, {"forced": g["forced"]}):
+        with pytest.raises(_lib.HipLibraryError, match="frame_cap goes with predicted durations"):
+            run(net, g, host, frame_cap=sum(host["frames"]) * 4, **kw)
     # nothing was launched by the refused calls; the next good one runs
     run(net, g, host, rows)
     assert _lib.lib().as_device_status(0) == 0
