@@ -14,6 +14,7 @@
 //   run     (kernels are enqueued; nothing is allocated, nothing synchronises once the geometry's tables exist).
 #include "common.h"
 #include "conv_gemm.h"
+#include "play_order.h"
 #include "runtime.h"
 #include <algorithm>
 #include <climits>
@@ -332,22 +333,23 @@ namespace {
 // Deferred launches (serial plans with `merge`): inside a Fork every launch of a branch is RECORDED into the branch's queue instead of being
 // enqueued; the root Fork's join() then plays the queues out on the calling stream in an order that keeps every queue's own order and the
 // fork / join edges, and hands conv GEMMs that are ready at the same time to ONE launch (as_conv_gemm_multi_f32): on one stream a step costs
-// the sum of its kernels' durations, and a 40-tile conv beside a 2 000-tile one costs next to nothing.
+// the sum of its kernels' durations, and a 40-tile conv beside a 2 000-tile one costs next to nothing.  The order
+// is play_order.h's rule; play() below carries it out.
+using play_order::Kind;
 struct Op {
-    int kind = 0;                                  // 0: a recorded launch, 1: a conv GEMM (as_conv_gemm_f32 arguments), 2: wait for other queues,
-                                                   // 3: a tower down-sampling step (as_down_multi_f32 arguments)
-    std::function<int()> fn;
-    ConvGemmArgs g;
-    AsAdainArgs post;                              // kind 1: the AdaIN that reads the conv's result (post.yh NULL: none), as_conv_gemm_multi_post_f32
+    Kind kind = Kind::Launch;
+    std::function<int(hipStream_t)> fn;            // Launch: the recorded call, on the stream it is handed
+    ConvGemmArgs g;                                // Conv: as_conv_gemm_f32 arguments
+    AsAdainArgs post;                              // Conv: the AdaIN that reads the conv's result (post.yh NULL: none), as_conv_gemm_multi_post_f32
     int post_max_w = 0;
-    AsLnArgs post_ln;                              // kind 1: ... or the channel LayerNorm that does (post_ln.yh NULL: none)
-    AsDownArgs d;
+    AsLnArgs post_ln;                              // Conv: ... or the channel LayerNorm that does (post_ln.yh NULL: none)
+    AsDownArgs d;                                  // Down: as_down_multi_f32 arguments
     hipStream_t s = nullptr;
     double hint_f = 0, hint_b = 0;                 // as_prof_hint that goes with the launch
-    std::vector<std::pair<int, size_t>> deps;      // kind 2: queue q has played >= n ops
+    std::vector<std::pair<int, size_t>> deps;      // Wait: queue q has played >= n ops
     const char* what = nullptr;
     int line = 0;
-    bool side = false;                             // kind 0: a long launch on a handful of workgroups (the duration predictor's recurrence over
+    bool side = false;                             // Launch: a long launch on a handful of workgroups (the duration predictor's recurrence over
                                                    // hundreds of tokens): play() puts it on the plan's side stream and parks its queue, so that
                                                    // the other queues' launches run beside it
 };
@@ -364,7 +366,7 @@ struct Ctx : PassCtx {
     int cur_q = -1;
     double hint_f = 0, hint_b = 0;
     bool deferring() const { return sched != nullptr && cur_q >= 0; }
-    Op& push(int kind)
+    Op& push(Kind kind)
     {
         sched->q[cur_q].emplace_back();
         Op& o = sched->q[cur_q].back();
@@ -373,6 +375,18 @@ struct Ctx : PassCtx {
         o.hint_f = hint_f; o.hint_b = hint_b;
         hint_f = hint_b = 0;
         return o;
+    }
+    void wait_for(int q, const std::vector<int>& others)                // queue q goes on after everything the other queues hold so far
+    {
+        const int keep = cur_q;
+        cur_q = q;
+        Op& o = push(Kind::Wait);
+        for (int j : others) o.deps.push_back({j, sched->q[j].size()});
+        cur_q = keep;
+    }
+    void long_launch()                             // the launch just recorded is a long one: Op.side
+    {
+        if (deferring() && !sched->q[cur_q].empty()) sched->q[cur_q].back().side = true;
     }
     void hint(double f, double b)                  // as_prof_hint for the NEXT launch: it has to travel with a recorded one
     {
@@ -420,20 +434,17 @@ struct Ctx : PassCtx {
     }
 };
 
-// (a recorded launch that play() moves to the plan's side stream: Op.side)
-static thread_local hipStream_t tl_stream_override = nullptr;
 // runtime.h's RUN with the recorded form in front (the closure copies what the call names -- argument structs and job arrays included --
-// and sees the stream as `c.s`)
+// and sees the stream play() hands it as `c.s`)
 #undef RUN
 #define RUN(c, call)                                   \
     do {                                               \
         if ((c).go()) {                                \
             if ((c).deferring()) {                     \
-                const hipStream_t s__ = (c).s;         \
-                Op& o__ = (c).push(0);                 \
+                Op& o__ = (c).push(Kind::Launch);      \
                 o__.what = #call; o__.line = __LINE__; \
-                o__.fn = [=]() -> int {                \
-                    struct { hipStream_t s; } c = {tl_stream_override ? tl_stream_override : s__}; \
+                o__.fn = [=](hipStream_t s__) -> int { \
+                    struct { hipStream_t s; } c = {s__}; \
                     (void)c;                           \
                     return (call);                     \
                 };                                     \
@@ -443,195 +454,123 @@ static thread_local hipStream_t tl_stream_override = nullptr;
         }                                              \
     } while (0)
 
-// Play the recorded queues out on stream `s` (see Op).  Greedy: every queue runs ahead through its plain launches; when every live head
-// is a conv GEMM (or waits for another queue), the heads that can share a launch -- operand images in, the tiled kernel, one row class --
-// go out together.
-static bool gemm_mergeable(const ConvGemmArgs& g)
-{
-    if (!g.Xh || g.N <= 0) return false;
-    int32_t kind = 0, tile = 0, slices = 0;
-    return as_conv_gemm_plan(&g, &kind, &tile, &slices) == AS_OK && kind == 1;
-}
-static bool gemm_direct(const ConvGemmArgs& g)           // the Cin = 1 direct kernel's fast form
-{
-    int32_t kind = 1, tile = 0, slices = 0;
-    return g.N > 0 && g.T <= 9 && as_conv_gemm_plan(&g, &kind, &tile, &slices) == AS_OK && kind == 0;
-}
-
+// Play the recorded queues out on stream `s`: summarise them for play_order.h (one as_conv_gemm_plan per recorded conv), ask it for the
+// steps, and carry those out until one fails.
 static void play(Ctx& c, Sched& S)
 {
     const int nq = (int)S.q.size();
-    std::vector<size_t> head(nq, 0);
-    // a queue whose last launch went to the side stream (Op.side) is PARKED: its later ops wait until nothing else can go out, then the
-    // calling stream waits for the side stream's event and the queue moves on.  Dependencies see a parked queue one op back.
-    std::vector<hipEvent_t> parked(nq, nullptr);
     const bool no_side = getenv("AS_NO_SIDE_LSTM") != nullptr;          // experiments / tests: everything on the one stream
-    auto unpark_all = [&]() -> bool {
-        bool any = false;
-        for (int qi = 0; qi < nq; ++qi)
-            if (parked[qi]) {
-                if (hipStreamWaitEvent(c.s, parked[qi], 0) != hipSuccess) c.fail((int)hipErrorUnknown, "unpark", __LINE__);
-                parked[qi] = nullptr;
-                any = true;
-            }
-        return any;
-    };
-    auto fail = [&](int r, const Op& o) { c.fail(r, o.what, o.line); };
     static const bool trace = getenv("AS_DEBUG_SCHED") != nullptr;     // print what goes out, in order
+    play_order::Queues Q(nq);
+    for (int qi = 0; qi < nq; ++qi) {
+        Q[qi].reserve(S.q[qi].size());
+        for (const Op& o : S.q[qi]) {
+            play_order::Op u;
+            u.kind = o.kind;
+            u.side = o.side;
+            u.deps = o.deps;
+            if (o.kind == Kind::Conv) {
+                const ConvGemmArgs& g = o.g;
+                int32_t kind = -1, tile = 0, slices = 0;
+                const bool planned = g.N > 0 && as_conv_gemm_plan(&g, &kind, &tile, &slices) == AS_OK;
+                u.mergeable = planned && g.Xh && kind == 1;             // operand image in, the tiled kernel
+                u.direct = planned && g.T <= 9 && kind == 0;            // the Cin = 1 direct kernel's fast form
+                u.tall = as_fills_tall_tile(g.M);
+                u.n_prod = g.n_prod;
+                u.work = (double)g.M * g.N * ((double)g.K * g.T + g.K2);
+            }
+            Q[qi].push_back(std::move(u));
+        }
+    }
     if (trace) {
         fprintf(stderr, "artspeech_hip: playing %d recorded queues:", nq);
         for (int qi = 0; qi < nq; ++qi) fprintf(stderr, " %zu", S.q[qi].size());
         fprintf(stderr, " ops\n");
     }
-    for (;;) {
-        bool progress = false;
-        for (int qi = 0; qi < nq && !c.rc; ++qi) {
-            while (head[qi] < S.q[qi].size() && !parked[qi]) {
-                Op& o = S.q[qi][head[qi]];
-                if (o.kind == 2) {
-                    bool ok = true;
-                    for (auto& d : o.deps) ok = ok && head[d.first] - (parked[d.first] ? 1 : 0) >= d.second;
-                    if (!ok) break;
-                } else if (o.kind == 0) {
-                    if (o.hint_f > 0 || o.hint_b > 0) as_prof_hint(o.hint_f, o.hint_b);
-                    if (trace) fprintf(stderr, "  q%d  %.60s%s\n", qi, o.what ? o.what : "?", o.side && !no_side ? "  [side stream]" : "");
-                    if (o.side && !no_side) {
-                        // fork: the side stream continues from what the calling stream holds so far; join: when the queue is unparked
-                        hipStream_t ss = c.p.stream(0);
-                        hipEvent_t e1 = c.p.event(), e2 = c.p.event();
-                        if (!ss || !e1 || !e2 || hipEventRecord(e1, c.s) != hipSuccess || hipStreamWaitEvent(ss, e1, 0) != hipSuccess) {
-                            fail((int)hipErrorUnknown, o);
-                            break;
-                        }
-                        tl_stream_override = ss;
-                        const int r = o.fn();
-                        tl_stream_override = nullptr;
-                        if (r != AS_OK) { fail(r, o); break; }
-                        if (hipEventRecord(e2, ss) != hipSuccess) { fail((int)hipErrorUnknown, o); break; }
-                        parked[qi] = e2;
-                        ++head[qi];
-                        progress = true;
-                        break;
-                    }
-                    const int r = o.fn();
-                    if (r != AS_OK) { fail(r, o); break; }
-                } else {
-                    break;                                               // a conv GEMM / a down-sampling step: decided below, with the other queues' heads
-                }
-                ++head[qi];
-                progress = true;
+    // a queue whose last launch went to the side stream is PARKED until the next Unpark: the calling stream then waits for its event
+    std::vector<hipEvent_t> parked(nq, nullptr);
+    auto fail = [&](int r, const Op& o) { c.fail(r, o.what, o.line); };
+    auto first = [&](const play_order::Step& st) -> Op& { return S.q[st.q[0]][st.at[0]]; };   // its stream, and the op a failure names
+    for (const play_order::Step& st : play_order::plan(Q, no_side)) {
+        switch (st.what) {
+        case play_order::Step::Launch: {
+            Op& o = first(st);
+            if (o.hint_f > 0 || o.hint_b > 0) as_prof_hint(o.hint_f, o.hint_b);
+            if (trace) fprintf(stderr, "  q%d  %.60s%s\n", st.q[0], o.what ? o.what : "?", st.side ? "  [side stream]" : "");
+            if (!st.side) {
+                const int r = o.fn(o.s);
+                if (r != AS_OK) fail(r, o);
+                break;
             }
+            // fork: the side stream continues from what the calling stream holds so far; join: when the queue is unparked
+            hipStream_t ss = c.p.stream(0);
+            hipEvent_t e1 = c.p.event(), e2 = c.p.event();
+            if (!ss || !e1 || !e2 || hipEventRecord(e1, c.s) != hipSuccess || hipStreamWaitEvent(ss, e1, 0) != hipSuccess) {
+                fail((int)hipErrorUnknown, o);
+                break;
+            }
+            const int r = o.fn(ss);
+            if (r != AS_OK) { fail(r, o); break; }
+            if (hipEventRecord(e2, ss) != hipSuccess) { fail((int)hipErrorUnknown, o); break; }
+            parked[st.q[0]] = e2;
+            break;
         }
-        if (c.rc) return;
-        if (progress) continue;
-        // every live head is a GEMM, a down-sampling step or a wait.  The towers' down-sampling steps that are ready together go out as one
-        // launch first (they are what the towers' next convs wait for)
-        {
+        case play_order::Step::Unpark:
+            for (hipEvent_t& e : parked)
+                if (e) {
+                    if (hipStreamWaitEvent(c.s, e, 0) != hipSuccess) c.fail((int)hipErrorUnknown, "unpark", __LINE__);
+                    e = nullptr;
+                }
+            break;
+        case play_order::Step::Down: {
             AsDownArgs dl[AS_MAX_MULTI];
-            int dq[AS_MAX_MULTI], nd = 0;
             double hf = 0, hb = 0;
-            for (int qi = 0; qi < nq && nd < AS_MAX_MULTI; ++qi)
-                if (!parked[qi] && head[qi] < S.q[qi].size() && S.q[qi][head[qi]].kind == 3) {
-                    const Op& o = S.q[qi][head[qi]];
-                    dl[nd] = o.d;
-                    dq[nd++] = qi;
-                    hf += o.hint_f;
-                    hb += o.hint_b;
-                }
-            if (nd > 0) {
-                if (hf > 0 || hb > 0) as_prof_hint(hf, hb);
-                if (trace) {
-                    fprintf(stderr, "  DOWN x%d:", nd);
-                    for (int i = 0; i < nd; ++i) fprintf(stderr, " q%d kind%d C%d |", dq[i], dl[i].kind, dl[i].C);
-                    fprintf(stderr, "\n");
-                }
-                const Op& o0 = S.q[dq[0]][head[dq[0]]];
-                const int r = as_down_multi_f32(dl, nd, o0.s);
-                if (r != AS_OK) { fail(r, o0); return; }
-                if (c.rc) return;
-                for (int i = 0; i < nd; ++i) ++head[dq[i]];
-                continue;
+            for (int i = 0; i < st.n; ++i) {
+                const Op& oi = S.q[st.q[i]][st.at[i]];
+                dl[i] = oi.d;
+                hf += oi.hint_f;
+                hb += oi.hint_b;
             }
+            if (hf > 0 || hb > 0) as_prof_hint(hf, hb);
+            if (trace) {
+                fprintf(stderr, "  DOWN x%d:", st.n);
+                for (int i = 0; i < st.n; ++i) fprintf(stderr, " q%d kind%d C%d |", st.q[i], dl[i].kind, dl[i].C);
+                fprintf(stderr, "\n");
+            }
+            const Op& o = first(st);
+            const int r = as_down_multi_f32(dl, st.n, o.s);
+            if (r != AS_OK) fail(r, o);
+            break;
         }
-        int heads[64], nh = 0;
-        bool live = false;
-        for (int qi = 0; qi < nq; ++qi)
-            if (head[qi] < S.q[qi].size()) {
-                live = true;
-                if (!parked[qi] && S.q[qi][head[qi]].kind == 1 && nh < 64) heads[nh++] = qi;
-            }
-        if (nh == 0 && unpark_all()) continue;                               // nothing else can go out: the parked queues move on
-        if (!live) return;
-        if (nh == 0) { c.fail(AS_EINVAL, "recorded queues wait for each other", __LINE__); return; }
-        // a queue with a side-stream launch still ahead of it goes FIRST and alone: its convs are what that launch waits for, and every
-        // conv of another queue that goes out before it is one that could have run beside it (the duration predictor's blocks before its
-        // recurrence; the encoders' last two layers then run while the recurrence does)
-        if (!no_side) {
-            int nu = 0, uh[64];
-            for (int i = 0; i < nh; ++i) {
-                const std::vector<Op>& Q = S.q[heads[i]];
-                bool urgent = false;
-                for (size_t k = head[heads[i]]; k < Q.size() && !urgent; ++k) urgent = Q[k].side;
-                if (urgent) uh[nu++] = heads[i];
-            }
-            if (nu > 0 && nu < nh) {
-                for (int i = 0; i < nu; ++i) heads[i] = uh[i];
-                nh = nu;
-            }
-        }
-        // a head that cannot share a launch (fp32 input still to be split, the direct Cin = 1 kernel) goes out first and alone: its queue
-        // moves on to heads that can.  Otherwise the set = the mergeable heads of the row class that holds the most work.
-        int pick[AS_MAX_MULTI], np = 0, lone = -1;
-        for (int i = 0; i < nh && lone < 0; ++i)
-            if (!gemm_mergeable(S.q[heads[i]][head[heads[i]]].g)) lone = heads[i];
-        if (lone >= 0 && gemm_direct(S.q[lone][head[lone]].g)) {        // the towers' Cin = 1 stems that are ready together: one direct launch
-            for (int i = 0; i < nh && np < AS_MAX_MULTI; ++i)
-                if (gemm_direct(S.q[heads[i]][head[heads[i]]].g)) pick[np++] = heads[i];
-            if (np < 2) np = 0;
-        }
-        if (lone < 0) {
-            double work[2] = {0, 0};
-            for (int i = 0; i < nh; ++i) {
-                const ConvGemmArgs& g = S.q[heads[i]][head[heads[i]]].g;
-                work[as_fills_tall_tile(g.M) ? 1 : 0] += (double)g.M * g.N * ((double)g.K * g.T + g.K2);
-            }
-            const int cls = work[1] >= work[0] ? 1 : 0;
-            // (a 64-channel conv may ride with a set of 128-row problems when it is a small part of the work: as_conv_gemm_multi_tile)
-            const bool ride = cls == 1 && work[0] <= 0.1 * work[1];
-            for (int i = 0; i < nh && np < AS_MAX_MULTI; ++i) {
-                const ConvGemmArgs& g = S.q[heads[i]][head[heads[i]]].g;
-                if (((as_fills_tall_tile(g.M) ? 1 : 0) == cls || ride) && (np == 0 || g.n_prod == S.q[pick[0]][head[pick[0]]].g.n_prod)) pick[np++] = heads[i];
-            }
-            if (np < 2) lone = pick[0];
-        }
-        if (np >= 2) {
+        case play_order::Step::Conv: {
             ConvGemmArgs list[AS_MAX_MULTI];
             AsAdainArgs posts[AS_MAX_MULTI];
             AsLnArgs lns[AS_MAX_MULTI];
             int32_t pmw[AS_MAX_MULTI];
-            for (int i = 0; i < np; ++i) {
-                const Op& oi = S.q[pick[i]][head[pick[i]]];
+            const Op& o = first(st);
+            for (int i = 0; i < st.n; ++i) {
+                const Op& oi = S.q[st.q[i]][st.at[i]];
                 list[i] = oi.g;
                 posts[i] = oi.post;
                 lns[i] = oi.post_ln;
                 pmw[i] = oi.post_max_w;
             }
-            if (trace) {
-                fprintf(stderr, "  GEMM x%d:", np);
-                for (int i = 0; i < np; ++i) fprintf(stderr, " q%d M%d N%d K%d T%d |", pick[i], list[i].M, list[i].N, list[i].K, list[i].T);
+            if (trace && st.n >= 2) {
+                fprintf(stderr, "  GEMM x%d:", st.n);
+                for (int i = 0; i < st.n; ++i) fprintf(stderr, " q%d M%d N%d K%d T%d |", st.q[i], list[i].M, list[i].N, list[i].K, list[i].T);
                 fprintf(stderr, "\n");
+            } else if (trace) {
+                fprintf(stderr, "  GEMM alone: q%d M%d N%d K%d T%d (%d heads)\n", st.q[0], o.g.M, o.g.N, o.g.K, o.g.T, st.candidates);
             }
-            const int r = as_conv_gemm_multi_post_f32(list, posts, pmw, lns, np, S.q[pick[0]][head[pick[0]]].s);
-            if (r != AS_OK) { fail(r, S.q[pick[0]][head[pick[0]]]); return; }
-            for (int i = 0; i < np; ++i) ++head[pick[i]];
-        } else {
-            Op& o = S.q[lone][head[lone]];
-            if (trace) fprintf(stderr, "  GEMM alone: q%d M%d N%d K%d T%d (%d heads)\n", lone, o.g.M, o.g.N, o.g.K, o.g.T, nh);
-            const int32_t mw1 = o.post_max_w;
-            const int r = as_conv_gemm_multi_post_f32(&o.g, &o.post, &mw1, &o.post_ln, 1, o.s);
-            if (r != AS_OK) { fail(r, o); return; }
-            ++head[lone];
+            const int r = as_conv_gemm_multi_post_f32(list, posts, pmw, lns, st.n, o.s);
+            if (r != AS_OK) fail(r, o);
+            break;
         }
+        case play_order::Step::Deadlock:
+            c.fail(AS_EINVAL, "recorded queues wait for each other", __LINE__);
+            break;
+        }
+        if (c.rc) return;
     }
 }
 
@@ -658,10 +597,8 @@ struct Fork {
             for (int i = 0; i < n; ++i) {
                 const int qi = c.sched->new_queue();
                 qs.push_back(qi);
-                c.cur_q = qi;
-                c.push(2).deps.push_back({q0, c.sched->q[q0].size()}); // a branch starts after what the calling stream has recorded so far
+                c.wait_for(qi, {q0});                                  // a branch starts after what the calling stream has recorded so far
             }
-            c.cur_q = q0;
             return;
         }
         if (!on_side) return;
@@ -684,13 +621,7 @@ struct Fork {
     }
     void wait_main(int i)                  // branch i continues only after what the calling stream has enqueued so far
     {
-        if (defer) {
-            const int keep = c.cur_q;
-            c.cur_q = qs[i];
-            c.push(2).deps.push_back({q0, c.sched->q[q0].size()});
-            c.cur_q = keep;
-            return;
-        }
+        if (defer) { c.wait_for(qs[i], {q0}); return; }
         if (!on_side) return;
         hipEvent_t e = c.p.event();
         if (!e || hipEventRecord(e, main) != hipSuccess || hipStreamWaitEvent(c.p.stream(first + i), e, 0) != hipSuccess) c.fail((int)hipErrorUnknown);
@@ -698,18 +629,15 @@ struct Fork {
     void after(int i, std::initializer_list<int> js)   // (recorded form only) branch i goes on after everything branches js hold so far
     {
         if (!defer) return;
-        const int keep = c.cur_q;
-        c.cur_q = qs[i];
-        Op& o = c.push(2);
-        for (int j : js) o.deps.push_back({qs[j], c.sched->q[qs[j]].size()});
-        c.cur_q = keep;
+        std::vector<int> others;
+        for (int j : js) others.push_back(qs[j]);
+        c.wait_for(qs[i], others);
     }
     void join()
     {
         if (defer) {
             c.cur_q = q0;
-            Op& o = c.push(2);
-            for (int qi : qs) o.deps.push_back({qi, c.sched->q[qi].size()});
+            c.wait_for(q0, qs);
             if (root) {
                 std::shared_ptr<Sched> S = c.sched;
                 c.sched.reset();
@@ -854,7 +782,7 @@ void conv_impl(Ctx& c, const GemmW* w, const float* X, int ldx, const uint16_t* 
     }
     if (o.ln.yh && (o.post_yh || !Y)) { c.fail(AS_EINVAL); return; }
     if (c.deferring()) {                  // recorded: it may share its launch with other branches' convs
-        Op& op = c.push(1);
+        Op& op = c.push(Kind::Conv);
         op.g = a;
         op.post = post;
         op.post_ln = o.ln;
@@ -1266,7 +1194,7 @@ void down(Ctx& c, const AsDownArgs& a, int line)
 {
     if (!c.go()) return;
     if (c.deferring()) {
-        Op& o = c.push(3);
+        Op& o = c.push(Kind::Down);
         o.d = a;
         o.what = "as_down_multi_f32";
         o.line = line;
@@ -1555,7 +1483,7 @@ float* duration_tail(Ctx& c, float* d, const float* ds, const Lay* tok, float* d
         // hundreds of tokens: milliseconds on a few dozen workgroups (C5: 1.8 ms on 16) while the text / articulatory encoders' last two
         // layers -- which do not depend on it (models.py:356-360) -- have the chip's worth of GEMMs to run: a recording plan puts the
         // launch on its side stream (one fork / join pair of event edges: worth it only for a long launch, >= 200 tokens)
-        if (c.deferring() && c.go() && tok->max_w >= 200 && !c.sched->q[c.cur_q].empty()) c.sched->q[c.cur_q].back().side = true;
+        if (c.go() && tok->max_w >= 200) c.long_launch();
     }
     float* y = c.f32(Nn);
     if (dst) y = dst;
