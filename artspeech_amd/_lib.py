@@ -170,6 +170,7 @@ _SIGNATURES.update({
     "as_conv_gemm_multi_post_f32": (c_i, [ctypes.POINTER(ConvGemmArgs), ctypes.POINTER(AdainArgs), ctypes.POINTER(ctypes.c_int32),
                                           ctypes.POINTER(LnArgs), c_i, c_p]),
     "as_down_multi_f32": (c_i, [ctypes.POINTER(DownArgs), c_i, c_p]),
+    "as_down_strip_rule": (c_i, [c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "as_respair_f32": (c_i, [ctypes.POINTER(ResPairArgs), c_p]),
     "as_xl_attention_image_f32": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_i, c_i, c_p, c_i, c_p, c_p]),
     "as_mean3_image_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p]),

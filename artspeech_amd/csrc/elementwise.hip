@@ -6,6 +6,9 @@
 #include <cstring>
 #include "artspeech_hip.h"
 #include "conv_gemm.h"
+#include "down_strips.h"
+#include <cstdint>
+#include <type_traits>
 #define AS_FILE_CLS AS_CLS_OTHER
 
 static __device__ __forceinline__ float wave_sum(float v)
@@ -772,113 +775,220 @@ extern "C" int as_bn_lrelu_maxpool_rows_f32(const float* x, int ldx, const int32
 // LearnedDownSample (models.py:27-31): depthwise conv, 'half' = 3x3 s2 p1, 'channelpreserve' = 1x3 s(1,2) p(0,1);
 // ResBlk1d.pool (models.py:116) is the H = 1 case of 'channelpreserve'.  Optional LeakyReLU on the result
 // (the activation that follows it at models.py:94 / :148).
-// A workgroup takes 8 consecutive channels of one utterance, a thread one output position of all eight: the values leave as
-// fp32 rows (y) and / or as one 16-byte row per part of the consumer conv's operand image (yh: the output of
-// models.py:27-31,116 feeds nothing but the block's second conv).
-// Branch-free: every tap is loaded from a clamped position and multiplied by its weight or by zero (a tap outside the image), so the
-// 8 x 3 KH loads of a thread are all in flight together -- with `continue` in the tap loops each load sat in its own divergent
-// region and paid its own memory round trip (the 64-channel 509 440-column launch: 82 us for 200 MB).  Same summation order as before.
+// A workgroup takes a STRIP (down_strips.h): 8 consecutive channels of one utterance -- one 16-byte row group of the consumer conv's operand
+// image -- and a run of output rows, a thread one output position of all eight channels per trip, 256 positions a trip.  The values leave
+// as fp32 rows (y) and / or as one 16-byte row per part of the image (yh: the output of models.py:27-31,116 feeds nothing but the block's
+// second conv).  What a workgroup pays once -- layout loads, taps to LDS, the barrier, a division -- it pays per strip; the trips then
+// run as a pipeline over half-sets of four channels: the loads of the next half-set are issued before the arithmetic of this one (two
+// register sets of 4 x KH pairs instead of one of 8 x KH: the body fits 128 registers, four waves per SIMD).
 typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));      // a pair of floats at any 4-byte address (odd row starts)
-template <int KH>
-static __device__ __forceinline__ void dwconv_down_body(const AsDownArgs& a, int b, int g, int bx, int gxn)
+
+// A thread's walk over its strip: output i = r0 Wo + threadIdx.x + 256 t of the utterance's Hout x Wo image, its row and column advanced
+// per trip without a division.  Beyond the strip's end the position is clamped to the strip's last output (loads stay inside the image,
+// whole waves stay in the loop: the shuffles) and nothing is stored.
+struct DownWalk {
+    int i, ho, wo, Wo, dq, dr, end, last_row;
+    __device__ __forceinline__ DownWalk(int r0, int r1, int Wo_) : Wo(Wo_)
+    {
+        const int q = (int)threadIdx.x / Wo;                                // the walk's one division per thread
+        ho = r0 + q; wo = (int)threadIdx.x - q * Wo; i = r0 * Wo + (int)threadIdx.x;
+        end = r1 * Wo; last_row = r1 - 1;
+        dq = 256 / Wo; dr = 256 - dq * Wo;                                 // (uniform)
+    }
+    __device__ __forceinline__ void step()
+    {
+        i += 256; ho += dq; wo += dr;
+        if (wo >= Wo) { wo -= Wo; ++ho; }
+    }
+    __device__ __forceinline__ bool live() const { return i < end; }
+    __device__ __forceinline__ int row() const { return live() ? ho : last_row; }
+    __device__ __forceinline__ int col() const { return live() ? wo : Wo - 1; }
+    // trips of this WAVE (uniform): a wave whose 64 outputs of a trip all lie beyond the strip's end has left; in every trip but a
+    // wave's last all of its lanes are live
+    __device__ __forceinline__ int trips(int r0) const
+    {
+        const int first = r0 * Wo + (__builtin_amdgcn_readfirstlane((int)threadIdx.x) & ~63);
+        return max(0, (end - first + 255) >> 8);
+    }
+};
+
+// the zero column of the image's two row groups of channel group g (column Nout), once per problem
+static __device__ __forceinline__ void down_zero_column(u32x4_t* __restrict__ yh, size_t plane, size_t NX, int Nout, int b, int strip)
 {
-    __shared__ float ws[8][KH * 3 + 1];                                 // the eight channels' taps and bias
+    if (yh && b == 0 && strip == 0 && threadIdx.x < 2) yh[plane + (size_t)threadIdx.x * 2 * NX + Nout] = u32x4_t{0u, 0u, 0u, 0u};
+}
+
+// The walk of a wave over its strip as a pipeline of half-sets of four channels, shared by the depthwise conv and the average pool:
+// where(pos) = the thread's position of the trip the walk stands at, load(half, pos, h) = issue every load of channels 4 h .. 4 h + 3,
+// sums(half, pos, h, live) = their results (and fp32 stores), put(pos, live) = the image's two 16-byte rows of all eight.
+// A trip: the second half-set's loads, the first one's sums, the NEXT trip's first half-set, the second one's sums, the image.  The
+// wave's last trip is the only one with lanes beyond the strip's end and the only one that loads nothing ahead: a copy of its own
+// behind the loop, so that the loop holds no branch around a load and no test of a lane's index (`live` is the constant true there).
+template <class Pos, class Half, class Where, class Load, class Sums, class Put>
+static __device__ __forceinline__ void down_walk_halves(DownWalk& wk, int r0, const Where& where, const Load& load, const Sums& sums, const Put& put)
+{
+    int n = wk.trips(r0);
+    if (n <= 0) return;
+    Pos p, pn;
+    Half d0, d1;
+    where(p);
+    pn = p;
+    load(d0, p, 0);
+    const auto trip = [&](auto last) __attribute__((always_inline)) {
+        const bool live = decltype(last)::value ? p.live : true;
+        load(d1, p, 1);
+        sums(d0, p, 0, live);
+        if constexpr (!decltype(last)::value) {
+            wk.step();
+            where(pn);
+            load(d0, pn, 0);
+        }
+        sums(d1, p, 1, live);
+        put(p, live);
+        p = pn;
+    };
+    for (; n > 1; --n) trip(std::false_type{});
+    trip(std::true_type{});
+}
+
+// the value of the lane before (lane 0: unspecified), as a DPP move of the whole wave: no LDS round trip (measured: as fast as
+// __shfl_up, the ds_bpermute it replaces, and without its three registers per channel for the shuffled values)
+static __device__ __forceinline__ float lane_before(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
+}
+// the taps stay in LDS: read per channel inside the trip (a compiler barrier keeps them from being hoisted into 80 registers of the loop)
+#define DOWN_TAPS_STAY_IN_LDS() asm volatile("" ::: "memory")
+
+// Branch-free: every tap is loaded from a clamped position and multiplied by its weight or skipped (a tap outside the image), so the
+// 4 x KH loads of a half-set are all in flight together -- with `continue` in the tap loops each load sat in its own divergent
+// region and paid its own memory round trip (the 64-channel 509 440-column launch: 82 us for 200 MB).  Same summation order as before.
+template <int KH>
+struct DwPos {                                  // one output position of a thread: where its window lies
+    int i, wo;
+    unsigned off[KH];                           // first float of the pair of window row a, from the channel row's start
+    unsigned left[KH];                          // (uniform) column 2 wo - 1 of the wave's first lane in row a; its pair's start if wo = 0
+    bool live, has_r, own_left, okh[KH];
+};
+template <int KH>
+struct DwHalf {                                 // the window of four channels
+    f32x2u p2[4][KH];
+    float lo[4][KH];
+};
+
+template <int KH>
+static __device__ __forceinline__ void dwconv_down_body(const AsDownArgs& a, int b, int g, int strip, int rows)
+{
+    constexpr int WSN = KH == 3 ? 12 : 4;                               // a channel's row: whole 16-byte reads
+    __shared__ __attribute__((aligned(16))) float ws[8][WSN];          // the eight channels' taps and bias
     const float* __restrict__ x = a.x;
     const int ldx = a.ldx, Hin = a.Hin, ldy = a.ldy, Hout = a.Hout, C = a.C, Nout = a.n_out, act = a.lrelu;
-    const int* __restrict__ in_off = a.in_off;
-    const int* __restrict__ in_w = a.in_w;
-    const int* __restrict__ out_off = a.out_off;
-    const int* __restrict__ out_w = a.out_w;
     const float* __restrict__ w = a.w;
     const float* __restrict__ bias = a.bias;
     float* __restrict__ y = a.y;
     u32x4_t* __restrict__ yh = reinterpret_cast<u32x4_t*>(a.yh);
     const int sh = KH == 3 ? 2 : 1, ph = KH == 3 ? 1 : 0;
     const int c0 = g * 8;
-    const int Wi = in_w[b], Wo = out_w[b];
+    const int Wi = a.in_w[b], Wo = a.out_w[b];
     const size_t NX = (size_t)Nout + 1, plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX;
-    if (yh && b == 0 && bx == 0 && threadIdx.x < 2) yh[plane + (size_t)threadIdx.x * 2 * NX + Nout] = u32x4_t{0u, 0u, 0u, 0u};
+    down_zero_column(yh, plane, NX, Nout, b, strip);
+    if (Wo <= 0) return;                                                // (uniform: before the barrier)
     if (threadIdx.x < 8 * (KH * 3 + 1)) {
         const int r = threadIdx.x / (KH * 3 + 1), k = threadIdx.x % (KH * 3 + 1), c = c0 + r;
         ws[r][k] = c < C ? (k < KH * 3 ? w[(size_t)c * KH * 3 + k] : bias[c]) : 0.f;
     }
     __syncthreads();
-    const int ib = in_off[b], ob = out_off[b], lane = threadIdx.x & 63;
+    const int ib = a.in_off[b], ob = a.out_off[b], lane = threadIdx.x & 63;
+    const int r0 = strip * rows, r1 = min(Hout, r0 + rows);
+    const float* xc[8];                                                 // the channels' rows of x (uniform)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) xc[r] = x + (size_t)min(c0 + r, C - 1) * ldx;
     // The window's columns 2 wo, 2 wo + 1 come as ONE 8-byte load per row and channel (a wave's loads are then whole cache lines; as three
     // 4-byte loads at a stride of two floats every instruction touched its lines half-used and the address path, not the memory, set
     // the pace: 2.5 TB/s); column 2 wo - 1 is the previous lane's second value -- the first lane of a wave fetches its own.  Rows of
     // one column (Wi = 1) and the last column of an odd row (no right neighbour) take the pair from one float earlier.
-    for (int i0 = bx * 256; i0 < Hout * Wo; i0 += gxn * 256) {      // (whole waves stay in the loop: shuffles)
-        const int i = i0 + threadIdx.x, ic = min(i, Hout * Wo - 1);
-        const int ho = ic / Wo, wo = ic - ho * Wo;
-        const bool has_r = 2 * wo + 1 < Wi;                              // the right neighbour exists
-        const int pc = Wi >= 2 ? (has_r ? 2 * wo : 2 * wo - 1) : 0;      // first column of the pair that is loaded
-        const bool own_left = lane == 0 && wo > 0;
-        float t[8];
+    DownWalk wk(r0, r1, Wo);
+    const auto where = [&](DwPos<KH>& p) __attribute__((always_inline)) {
+        const int ho = wk.row(), wo = wk.col();
+        p.i = wk.i; p.live = wk.live(); p.wo = wo;
+        p.has_r = 2 * wo + 1 < Wi;                                       // the right neighbour exists
+        const int pc = Wi >= 2 ? (p.has_r ? 2 * wo : 2 * wo - 1) : 0;    // first column of the pair that is loaded
+        p.own_left = lane == 0 && wo > 0;
 #pragma unroll
-        for (int r = 0; r < 8; ++r) t[r] = 0.f;
-        // every load of the window is issued before anything waits for one (the pairs; then, in ONE divergent region, the first lane's
-        // own left neighbours): a shuffle or a branch between the loads would serialise 24 memory round trips
-        f32x2u p2[8][KH];
-        float lo[8][KH];
-        bool okh[KH];
-        int base[KH];
-#pragma unroll
-        for (int a = 0; a < KH; ++a) {
-            const int hi = ho * sh - ph + a, hc = min(max(hi, 0), Hin - 1);
-            okh[a] = hi >= 0 && hi < Hin;
-            base[a] = ib + hc * Wi;
+        for (int k = 0; k < KH; ++k) {
+            const int hi = ho * sh - ph + k, hc = min(max(hi, 0), Hin - 1);
+            p.okh[k] = hi >= 0 && hi < Hin;
+            p.off[k] = (unsigned)(ib + hc * Wi + pc);
+            p.left[k] = (unsigned)__builtin_amdgcn_readfirstlane(ib + hc * Wi + (wo > 0 ? 2 * wo - 1 : pc));
         }
-        if (Wi >= 2) {
+    };
+    // every load of a half-set is issued before anything waits for one: the pairs, then the first lane's own left neighbours -- by ALL
+    // lanes from the first lane's address (one cache line an instruction).  No load sits behind a branch: the compiler counts the
+    // loads in flight to wait for the older half-set only, and a load that may or may not have been issued makes it wait for all.
+    // (one_col: images of one column, Wi = 1 -- a walk of its own below, so that no wait of that path sits in the pairs' pipeline)
+    const auto load = [&](auto one_col, DwHalf<KH>& d, const DwPos<KH>& p, int h) __attribute__((always_inline)) {
+        if constexpr (!decltype(one_col)::value) {
 #pragma unroll
-            for (int a = 0; a < KH; ++a)
+            for (int k = 0; k < KH; ++k)
 #pragma unroll
-                for (int r = 0; r < 8; ++r) p2[r][a] = *reinterpret_cast<const f32x2u*>(x + (size_t)min(c0 + r, C - 1) * ldx + base[a] + pc);
+                for (int r = 0; r < 4; ++r) d.p2[r][k] = *reinterpret_cast<const f32x2u*>(xc[4 * h + r] + p.off[k]);
         } else {
 #pragma unroll
-            for (int a = 0; a < KH; ++a)
+            for (int k = 0; k < KH; ++k)
 #pragma unroll
-                for (int r = 0; r < 8; ++r) { const float e = x[(size_t)min(c0 + r, C - 1) * ldx + base[a]]; p2[r][a] = f32x2u{e, e}; }
+                for (int r = 0; r < 4; ++r) { const float e = xc[4 * h + r][p.off[k]]; d.p2[r][k] = f32x2u{e, e}; }
         }
-        if (own_left) {
 #pragma unroll
-            for (int a = 0; a < KH; ++a)
+        for (int k = 0; k < KH; ++k)
 #pragma unroll
-                for (int r = 0; r < 8; ++r) lo[r][a] = x[(size_t)min(c0 + r, C - 1) * ldx + base[a] + 2 * wo - 1];
-        }
-        float v[8][KH][3];
-#pragma unroll
-        for (int a = 0; a < KH; ++a)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const float x0 = (has_r || Wi < 2) ? p2[r][a].x : p2[r][a].y, x1 = p2[r][a].y;   // (no right neighbour: x1 unused, its weight is skipped)
-                const float xl = __shfl_up(x1, 1);                       // previous lane: (ho, wo - 1)'s right value = column 2 wo - 1
-                v[r][a][0] = own_left ? lo[r][a] : xl; v[r][a][1] = x0; v[r][a][2] = x1;
-            }
+            for (int r = 0; r < 4; ++r) d.lo[r][k] = xc[4 * h + r][p.left[k]];
+    };
+    float t[8];
+    // taps in ascending (row, column) order, then the bias, then LeakyReLU
+    const auto sums = [&](const DwHalf<KH>& d, const DwPos<KH>& p, int h, bool live) __attribute__((always_inline)) {
         // a previous lane whose pair was shifted (its has_r false) cannot be this lane's neighbour: that lane ends a row, this one starts the next (wo = 0)
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
+        for (int r = 0; r < 4; ++r) {
+            const int rr = 4 * h + r;
+            DOWN_TAPS_STAY_IN_LDS();
+            float wt[WSN];
+#pragma unroll
+            for (int q = 0; q < WSN / 4; ++q) {
+                const float4 w4 = reinterpret_cast<const float4*>(ws[rr])[q];
+                wt[4 * q] = w4.x; wt[4 * q + 1] = w4.y; wt[4 * q + 2] = w4.z; wt[4 * q + 3] = w4.w;
+            }
             float s = 0.f;
 #pragma unroll
-            for (int a = 0; a < KH; ++a) {
-                if (okh[a] && wo > 0) s += v[r][a][0] * ws[r][a * 3 + 0];
-                if (okh[a]) s += v[r][a][1] * ws[r][a * 3 + 1];
-                if (okh[a] && has_r) s += v[r][a][2] * ws[r][a * 3 + 2];
+            for (int k = 0; k < KH; ++k) {
+                const float x0 = (p.has_r || Wi < 2) ? d.p2[r][k].x : d.p2[r][k].y, x1 = d.p2[r][k].y;   // (no right neighbour: x1 unused, its weight is skipped)
+                const float xl = lane_before(x1);                        // previous lane: (ho, wo - 1)'s right value = column 2 wo - 1
+                const float vl = p.own_left ? d.lo[r][k] : xl;
+                if (p.okh[k] && p.wo > 0) s += vl * wt[k * 3 + 0];
+                if (p.okh[k]) s += x0 * wt[k * 3 + 1];
+                if (p.okh[k] && p.has_r) s += x1 * wt[k * 3 + 2];
             }
-            s += ws[r][KH * 3];
+            s += wt[KH * 3];
             if (act) s = lrelu02(s);
-            if (c0 + r >= C) s = 0.f;
-            else if (y && i < Hout * Wo) y[(size_t)(c0 + r) * ldy + ob + i] = s;
-            t[r] = s;
+            if (c0 + rr >= C) s = 0.f;
+            else if (y && live) y[(size_t)(c0 + rr) * ldy + ob + p.i] = s;
+            t[rr] = s;
         }
-        if (yh && i < Hout * Wo) {
+    };
+    const auto put = [&](const DwPos<KH>& p, bool live) __attribute__((always_inline)) {
+        if (yh && live) {
             u32x4_t h, l;
             split2(t, h, l);
-            const size_t at = plane + ob + i;
+            const size_t at = plane + ob + p.i;
             yh[at] = h;
             yh[at + 2 * NX] = l;
         }
-    }
+    };
+    const auto walk = [&](auto one_col) __attribute__((always_inline)) {
+        down_walk_halves<DwPos<KH>, DwHalf<KH>>(
+            wk, r0, where, [&](DwHalf<KH>& d, const DwPos<KH>& p, int h) __attribute__((always_inline)) { load(one_col, d, p, h); }, sums, put);
+    };
+    if (Wi >= 2) walk(std::false_type{});
+    else walk(std::true_type{});
 }
 
 static int down_one(const AsDownArgs& a, hipStream_t stream);
@@ -913,68 +1023,100 @@ extern "C" int as_dwconv_down_image_f32(const float* x, int ldx, const int32_t* 
 // DownSample (models.py:43-57) / ResBlk1d.downsample (:127-130): replicate the last column when W is odd,
 // then average pool (ph x 2); optionally  y = (pool(x) + res) / sqrt(2)  (the block's output, models.py:99-100).
 template <int PH>
-static __device__ __forceinline__ void avgpool_down_body(const AsDownArgs& a, int b, int g, int bx, int gxn)
+struct AvgHalf {                                // the pairs and the residual of four channels
+    f32x2u p2[4][PH];
+    float rv[4];
+};
+struct AvgPos {
+    int i;
+    unsigned off;                               // first float of the pair of row ho PH, from the channel row's start
+    bool live, has_r;
+};
+
+template <int PH>
+static __device__ __forceinline__ void avgpool_down_body(const AsDownArgs& a, int b, int g, int strip, int rows)
 {
-    // 8 consecutive channels per workgroup, one output position of all eight per thread (as dwconv_down_body)
+    // a strip per workgroup, one output position of all eight channels per thread and trip, half-sets of four channels (as dwconv_down_body)
     const float* __restrict__ x = a.x;
     const int ldx = a.ldx, ldy = a.ldy, Hout = a.Hout, C = a.C, Nout = a.n_out, yh_lrelu = a.lrelu, ldr = a.ldr;
-    const int* __restrict__ in_off = a.in_off;
-    const int* __restrict__ in_w = a.in_w;
-    const int* __restrict__ out_off = a.out_off;
-    const int* __restrict__ out_w = a.out_w;
     const float* __restrict__ res = a.res;
     float* __restrict__ y = a.y;
     u32x4_t* __restrict__ yh = reinterpret_cast<u32x4_t*>(a.yh);
     const int c0 = g * 8;
-    const int Wi = in_w[b], Wo = out_w[b], ib = in_off[b], ob = out_off[b];
+    const int Wi = a.in_w[b], Wo = a.out_w[b], ib = a.in_off[b], ob = a.out_off[b];
     const size_t NX = (size_t)Nout + 1, plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX;
-    if (yh && b == 0 && bx == 0 && threadIdx.x < 2) yh[plane + (size_t)threadIdx.x * 2 * NX + Nout] = u32x4_t{0u, 0u, 0u, 0u};
-    for (int i = bx * 256 + threadIdx.x; i < Hout * Wo; i += gxn * 256) {
-        const int ho = i / Wo, wo = i - ho * Wo;
+    down_zero_column(yh, plane, NX, Nout, b, strip);
+    if (Wo <= 0) return;
+    const int r0 = strip * rows, r1 = min(Hout, r0 + rows);
+    const float* xc[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) xc[r] = x + (size_t)min(c0 + r, C - 1) * ldx;
+    DownWalk wk(r0, r1, Wo);
+    const auto where = [&](AvgPos& p) __attribute__((always_inline)) {
         // the pair (2 wo, 2 wo + 1) as one 8-byte load (whole cache lines per wave); the last column of an odd row stands for its
-        // missing neighbour: there the pair is loaded one float earlier and its second value is used twice.  Every load of the
-        // thread (8 channels x PH rows, the residual's 8) is issued before the first sum.
-        const bool has_r = 2 * wo + 1 < Wi;
-        const int pc = Wi >= 2 ? (has_r ? 2 * wo : 2 * wo - 1) : 0;
-        f32x2u p2[8][PH];
-        float rv[8];
+        // missing neighbour: there the pair is loaded one float earlier and its second value is used twice
+        const int ho = wk.row(), wo = wk.col();
+        p.i = wk.live() ? wk.i : wk.end - 1; p.live = wk.live();
+        p.has_r = 2 * wo + 1 < Wi;
+        const int pc = Wi >= 2 ? (p.has_r ? 2 * wo : 2 * wo - 1) : 0;
+        p.off = (unsigned)(ib + ho * PH * Wi + pc);
+    };
+    // every load of a half-set (4 channels x PH rows, the residual's 4) is issued before the first sum
+    const auto load = [&](auto one_col, auto has_res, AvgHalf<PH>& d, const AvgPos& p, int h) __attribute__((always_inline)) {
+        if constexpr (!decltype(one_col)::value) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const float* xr = x + (size_t)min(c0 + r, C - 1) * ldx + ib;
+            for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int a = 0; a < PH; ++a) {
-                if (Wi >= 2) p2[r][a] = *reinterpret_cast<const f32x2u*>(xr + (size_t)(ho * PH + a) * Wi + pc);
-                else { const float e = xr[(size_t)(ho * PH + a) * Wi]; p2[r][a] = f32x2u{e, e}; }
-            }
-            rv[r] = res ? res[(size_t)min(c0 + r, C - 1) * ldr + ob + i] : 0.f;
+                for (int k = 0; k < PH; ++k) d.p2[r][k] = *reinterpret_cast<const f32x2u*>(xc[4 * h + r] + p.off + (unsigned)(k * Wi));
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int k = 0; k < PH; ++k) { const float e = xc[4 * h + r][p.off + (unsigned)(k * Wi)]; d.p2[r][k] = f32x2u{e, e}; }
         }
-        float t[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
+        for (int r = 0; r < 4; ++r) d.rv[r] = decltype(has_res)::value ? res[(size_t)min(c0 + 4 * h + r, C - 1) * ldr + ob + p.i] : 0.f;
+    };
+    float t[8];
+    const auto sums = [&](const AvgHalf<PH>& d, const AvgPos& p, int h, bool live) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rr = 4 * h + r;
             float s = 0.f;
 #pragma unroll
-            for (int a = 0; a < PH; ++a) {
-                s += (has_r || Wi < 2) ? p2[r][a].x : p2[r][a].y;
-                s += p2[r][a].y;
+            for (int k = 0; k < PH; ++k) {
+                s += (p.has_r || Wi < 2) ? d.p2[r][k].x : d.p2[r][k].y;
+                s += d.p2[r][k].y;
             }
             s = s / (float)(2 * PH);
-            if (res) s = (s + rv[r]) / 1.41421356237309504880f;
-            if (c0 + r < C) {
-                if (y) y[(size_t)(c0 + r) * ldy + ob + i] = s;
+            if (res) s = (s + d.rv[r]) / 1.41421356237309504880f;
+            if (c0 + rr < C) {
+                if (y && live) y[(size_t)(c0 + rr) * ldy + ob + p.i] = s;
                 if (yh_lrelu) s = lrelu02(s);
             } else {
                 s = 0.f;
             }
-            t[r] = s;
+            t[rr] = s;
         }
-        if (yh) {
+    };
+    const auto put = [&](const AvgPos& p, bool live) __attribute__((always_inline)) {
+        if (yh && live) {
             u32x4_t h, l;
             split2(t, h, l);
-            const size_t at = plane + ob + i;
+            const size_t at = plane + ob + p.i;
             yh[at] = h;
             yh[at + 2 * NX] = l;
         }
-    }
+    };
+    // (walks of their own for images of one column, as dwconv_down_body, and for the residual: no branch around its loads)
+    const auto walk = [&](auto one_col, auto has_res) __attribute__((always_inline)) {
+        down_walk_halves<AvgPos, AvgHalf<PH>>(
+            wk, r0, where, [&](AvgHalf<PH>& d, const AvgPos& p, int h) __attribute__((always_inline)) { load(one_col, has_res, d, p, h); }, sums, put);
+    };
+    if (Wi >= 2) { if (res) walk(std::false_type{}, std::true_type{}); else walk(std::false_type{}, std::false_type{}); }
+    else if (res) walk(std::true_type{}, std::true_type{});
+    else walk(std::true_type{}, std::false_type{});
+
 }
 
 static int avgpool_launch(const float* x, int ldx, const int32_t* in_off, const int32_t* in_w, int Hin, float* y, int ldy, const int32_t* out_off,
@@ -1010,57 +1152,72 @@ extern "C" int as_avgpool_down_image_f32(const float* x, int ldx, const int32_t*
 // back -- its only other consumer, the block's conv1, reads the LeakyReLU image the stem writes.  w = the stem's fp32 image [T][Kp][M]
 // (k = 0 rows), taps in taps_2d(3, 3) / taps_1d(3) order, zero padding; then DownSample's (pool_h x 2) average with the last column
 // replicated when W is odd, summed in avgpool_down_kernel's order.  Workgroup = 8 channels of one utterance, thread = one output position.
-static __device__ __forceinline__ void stem_pool_image_body(const AsDownArgs& a, int b, int g, int bx, int gxn)
+// s + round(w x): two roundings, whatever -ffp-contract says
+static __device__ __forceinline__ float add_rounded_product(float s, float w, float x)
+{
+#pragma clang fp contract(off)
+    const float p = w * x;
+    return s + p;
+}
+
+struct StemPos {
+    int i, ho, wo;
+    bool live;
+};
+
+static __device__ __forceinline__ void stem_pool_image_body(const AsDownArgs& a, int b, int g, int strip, int rows)
 {
     __shared__ float ws[8][10];                                         // the eight channels' taps and bias
     const float* __restrict__ x = a.x;
     const int Hin = a.Hin, Hout = a.Hout, ph = a.pool_h, Kp = a.Kp, KH = a.kh, C = a.C, Nout = a.n_out;
-    const int* __restrict__ in_off = a.in_off;
-    const int* __restrict__ in_w = a.in_w;
-    const int* __restrict__ out_off = a.out_off;
-    const int* __restrict__ out_w = a.out_w;
     const float* __restrict__ w = a.w;
     const float* __restrict__ bias = a.bias;
     u32x4_t* __restrict__ yh = reinterpret_cast<u32x4_t*>(a.yh);
     const int c0 = g * 8;
-    const int Wi = in_w[b], Wo = out_w[b];
+    const int Wi = a.in_w[b], Wo = a.out_w[b];
     const size_t NX = (size_t)Nout + 1, plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX;
-    if (b == 0 && bx == 0 && threadIdx.x < 2) yh[plane + (size_t)threadIdx.x * 2 * NX + Nout] = u32x4_t{0u, 0u, 0u, 0u};
+    down_zero_column(yh, plane, NX, Nout, b, strip);
+    if (Wo <= 0) return;                                                // (uniform: before the barrier)
     if (threadIdx.x < 80) {
         const int r = threadIdx.x / 10, k = threadIdx.x % 10, c = c0 + r;
         ws[r][k] = c < C ? (k < 9 ? (k < KH * 3 ? w[(size_t)k * Kp * C + c] : 0.f) : (bias ? bias[c] : 0.f)) : 0.f;
     }
     __syncthreads();
-    const int ib = in_off[b], ob = out_off[b], pad = KH / 2;
-    for (int i = bx * 256 + threadIdx.x; i < Hout * Wo; i += gxn * 256) {
-        const int ho = i / Wo, wo = i - ho * Wo;
-        float win[4][4];                                                // rows ho ph - pad .. + ph + KH - 2, columns 2 wo - 1 .. 2 wo + 2 (zero outside)
-        // branch-free: the sixteen loads go to clamped positions, unconditionally, and the zero padding is a select
-        // behind them -- with each load behind its own bounds test every one sat in its own divergent region and paid its own round trip
-        // (round 5: this launch took 71 us for 50 MB of output)
+    const int ib = a.in_off[b], ob = a.out_off[b], pad = KH / 2;
+    const int r0 = strip * rows, r1 = min(Hout, r0 + rows);
+    DownWalk wk(r0, r1, Wo);
+    const auto where = [&](StemPos& p) __attribute__((always_inline)) { p.i = wk.i; p.ho = wk.row(); p.wo = wk.col(); p.live = wk.live(); };
+    // rows ho ph - pad .. + ph + KH - 2, columns 2 wo - 1 .. 2 wo + 2 of the one-channel input.  Branch-free: the
+    // sixteen loads go to clamped positions, unconditionally, and the zero padding is a select behind them -- with each load behind its
+    // own bounds test every one sat in its own divergent region and paid its own round trip (round 5: this launch took 71 us for 50 MB
+    // of output).  The next trip's sixteen are issued before this trip's products.
+    const auto load = [&](float (&win)[4][4], const StemPos& p) __attribute__((always_inline)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int hi = ho * ph - pad + r, hc = min(max(hi, 0), Hin - 1);
+            const int hi = p.ho * ph - pad + r, hc = min(max(hi, 0), Hin - 1);
 #pragma unroll
             for (int cc = 0; cc < 4; ++cc) {
-                const int wi = 2 * wo - 1 + cc, wc = min(max(wi, 0), Wi - 1);
+                const int wi = 2 * p.wo - 1 + cc, wc = min(max(wi, 0), Wi - 1);
                 win[r][cc] = x[ib + hc * Wi + wc];
             }
         }
+    };
+    const auto trip = [&](float (&win)[4][4], const StemPos& p, bool live) __attribute__((always_inline)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int hi = ho * ph - pad + r;
+            const int hi = p.ho * ph - pad + r;
 #pragma unroll
             for (int cc = 0; cc < 4; ++cc) {
-                const int wi = 2 * wo - 1 + cc;
+                const int wi = 2 * p.wo - 1 + cc;
                 const bool ok = r < ph + KH - 1 && hi >= 0 && hi < Hin && wi >= 0 && wi < Wi;
-                win[r][cc] = ok ? win[r][cc] : 0.f;
+                win[r][cc] = ok ? win[r][cc] : 0.f;                     // (zero outside)
             }
         }
-        const bool dup = 2 * wo + 1 >= Wi;                              // odd width: the last column stands for its missing neighbour
+        const bool dup = 2 * p.wo + 1 >= Wi;                            // odd width: the last column stands for its missing neighbour
         float t[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
+            DOWN_TAPS_STAY_IN_LDS();
             float wr[10];                                               // (registers: the products below would otherwise re-read LDS 36 times)
 #pragma unroll
             for (int k = 0; k < 10; ++k) wr[k] = ws[r][k];
@@ -1076,7 +1233,14 @@ static __device__ __forceinline__ void stem_pool_image_body(const AsDownArgs& a,
                     for (int ta = 0; ta < 3; ++ta) {
                         if (ta >= KH) break;
 #pragma unroll
-                        for (int td = 0; td < 3; ++td) sum += wr[ta * 3 + td] * win[a + ta][cc + td];
+                        for (int td = 0; td < 3; ++td) {
+                            // one rounding per tap, stated -- but for the second tap of the first sum, whose product is rounded on its
+                            // own: that is what this loop has compiled to since the stem body exists (the first two products of the
+                            // first sum as one packed multiply, the sums behind it), and the images stay what they were bit for bit
+                            const float wv = wr[ta * 3 + td], xv = win[a + ta][cc + td];
+                            if (a == 0 && cc == 0 && ta == 0 && td == 1) sum = add_rounded_product(sum, wv, xv);
+                            else sum = __builtin_fmaf(wv, xv, sum);
+                        }
                     }
                     v[cc] = sum + wr[9];
                 }
@@ -1085,11 +1249,32 @@ static __device__ __forceinline__ void stem_pool_image_body(const AsDownArgs& a,
             }
             t[r] = c0 + r < C ? s / (float)(2 * ph) : 0.f;
         }
-        u32x4_t h, l;
-        split2(t, h, l);
-        const size_t at = plane + ob + i;
-        yh[at] = h;
-        yh[at + 2 * NX] = l;
+        if (live) {
+            u32x4_t h, l;
+            split2(t, h, l);
+            const size_t at = plane + ob + p.i;
+            yh[at] = h;
+            yh[at + 2 * NX] = l;
+        }
+    };
+    int n = wk.trips(r0);
+    if (n <= 0) return;
+    StemPos p, q;
+    float w0[4][4], w1[4][4];
+    where(p);
+    load(w0, p);
+    for (; n > 2; n -= 2) {                                             // two trips per pass: the two register sets swap roles; the wave's
+        wk.step(); where(q); load(w1, q);                               // last trip (lanes beyond the end, nothing to load ahead) behind the loop
+        trip(w0, p, true);
+        wk.step(); where(p); load(w0, p);
+        trip(w1, q, true);
+    }
+    if (n == 2) {
+        wk.step(); where(q); load(w1, q);
+        trip(w0, p, true);
+        trip(w1, q, q.live);
+    } else {
+        trip(w0, p, p.live);
     }
 }
 
@@ -1104,37 +1289,36 @@ extern "C" int as_stem_pool_image_f32(const float* x, const int32_t* in_off, con
     return down_one(a, (hipStream_t)stream);
 }
 
-// ONE launch for several of the tower down-sampling steps above (AsDownArgs: include/artspeech_hip.h): blockIdx.y walks the problems'
+// ONE launch for several of the tower down-sampling steps above (AsDownArgs: include/artspeech_hip.h): blockIdx.x walks the problems'
 // workgroups back to back (exactly the workgroups every problem needs: a common 3-D grid sized for the widest problem was three quarters empty workgroups and slower than the launches it replaced).
 // The four towers of the style path and dur_block (models.py:385-411, 530-535) are independent and march through their blocks in step,
-// so their LearnedDownSample / DownSample launches -- 7-20 us each at C3 sizes, all latency -- come in sets of four.
+// so their LearnedDownSample / DownSample launches come in sets of four.  A problem's workgroups are its strips (down_strips.h: the
+// grid rule, a function of host-known shapes alone).
 #define DOWN_MAXP 6
 struct DownMulti {
     int32_t n, pad_;
-    int32_t blk0[DOWN_MAXP + 2];         // first workgroup of problem i; its workgroups: (x of gx, utterance of B, 8-channel group of gz), x fastest
-    int32_t gx[DOWN_MAXP], gz[DOWN_MAXP];
+    int32_t blk0[DOWN_MAXP + 2];         // first workgroup of problem i; its workgroups: (strip of ns, utterance of B, 8-channel group), strip fastest
+    int32_t ns[DOWN_MAXP], rows[DOWN_MAXP];
     AsDownArgs a[DOWN_MAXP];
 };
-// HEAVY: the instantiation that also holds the 3-row depthwise conv and the stem bodies (200+ registers per lane); a set without them
-// runs the light one (the 1-D / channel-preserving steps and the average pools: a quarter of the registers, four times the waves)
-template <bool HEAVY>
-__global__ void __launch_bounds__(256)
+// one instantiation: every body fits 128 registers per lane (four waves per SIMD), so a set needs no scan for a heavy member
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
 down_multi_kernel(const DownMulti dm)
 {
     int pi = 0;
 #pragma unroll
     for (int i = 1; i < DOWN_MAXP; ++i) pi += (i < dm.n && (int)blockIdx.x >= dm.blk0[i]) ? 1 : 0;
     const AsDownArgs& a = dm.a[pi];
-    const int gxn = dm.gx[pi], local = (int)blockIdx.x - dm.blk0[pi];
-    const int bx = local % gxn, rest = local / gxn, b = rest % a.B, g = rest / a.B;
+    const int ns = dm.ns[pi], rows = dm.rows[pi], local = (int)blockIdx.x - dm.blk0[pi];
+    const int strip = local % ns, rest = local / ns, b = rest % a.B, g = rest / a.B;
     if (a.kind == 0) {
-        if (a.kh == 3) { if constexpr (HEAVY) dwconv_down_body<3>(a, b, g, bx, gxn); }
-        else dwconv_down_body<1>(a, b, g, bx, gxn);
+        if (a.kh == 3) dwconv_down_body<3>(a, b, g, strip, rows);
+        else dwconv_down_body<1>(a, b, g, strip, rows);
     } else if (a.kind == 1) {
-        if (a.pool_h == 2) avgpool_down_body<2>(a, b, g, bx, gxn);
-        else avgpool_down_body<1>(a, b, g, bx, gxn);
+        if (a.pool_h == 2) avgpool_down_body<2>(a, b, g, strip, rows);
+        else avgpool_down_body<1>(a, b, g, strip, rows);
     } else {
-        if constexpr (HEAVY) stem_pool_image_body(a, b, g, bx, gxn);
+        stem_pool_image_body(a, b, g, strip, rows);
     }
 }
 
@@ -1148,29 +1332,39 @@ static int down_check(const AsDownArgs& a)
     return AS_EINVAL;
 }
 
+extern "C" int as_down_strip_rule(int kind, int Hout, int max_wo, int B, int groups, int32_t* strips, int32_t* rows)
+{
+    if (!strips || !rows || kind < 0 || kind > 2 || Hout < 0 || max_wo < 0 || B < 0 || groups < 0) return AS_EINVAL;
+    const down_strips::Rule r = down_strips::rule(kind, Hout, max_wo, B, groups);
+    *strips = r.strips;
+    *rows = r.rows;
+    return AS_OK;
+}
+
 extern "C" int as_down_multi_f32(const AsDownArgs* list_host, int n, as_stream_t stream_)
 {
     static_assert(DOWN_MAXP == AS_MAX_MULTI, "header and kernel disagree");
     if (!list_host || n < 1 || n > DOWN_MAXP) return AS_EINVAL;
     DownMulti dm;
     memset(&dm, 0, sizeof(dm));
-    bool heavy = false;
     for (int i = 0; i < n; ++i) {
         const AsDownArgs& a = list_host[i];
         const int r = down_check(a);
         if (r != AS_OK) return r;
-        if (a.B == 0 || a.max_out <= 0) continue;
-        heavy = heavy || a.kind == 2 || (a.kind == 0 && a.kh == 3);
+        if (a.B == 0 || a.max_out <= 0 || a.Hout <= 0) continue;
+        const int gz = a.yh ? 2 * as_kbx(a.C) : as_cdiv(a.C, 8);
+        const down_strips::Rule rule = down_strips::rule(a.kind, a.Hout, as_cdiv(a.max_out, a.Hout), a.B, gz);
+        const long last = (long)dm.blk0[dm.n] + (long)rule.strips * a.B * gz;
+        if (last > INT32_MAX) return AS_EINVAL;                          // (a 1-D grid: far beyond any tower)
         dm.a[dm.n] = a;
-        dm.gx[dm.n] = std::min(32, as_cdiv(a.max_out, 256));
-        dm.gz[dm.n] = a.yh ? 2 * as_kbx(a.C) : as_cdiv(a.C, 8);
-        dm.blk0[dm.n + 1] = dm.blk0[dm.n] + dm.gx[dm.n] * a.B * dm.gz[dm.n];
+        dm.ns[dm.n] = rule.strips;
+        dm.rows[dm.n] = rule.rows;
+        dm.blk0[dm.n + 1] = (int32_t)last;
         ++dm.n;
     }
     if (dm.n == 0) return AS_OK;
     AsProfScope prof__(AS_FILE_CLS, 0, 0, (hipStream_t)stream_);
-    if (heavy) hipLaunchKernelGGL(down_multi_kernel<true>, dim3(dm.blk0[dm.n]), dim3(256), 0, (hipStream_t)stream_, dm);
-    else hipLaunchKernelGGL(down_multi_kernel<false>, dim3(dm.blk0[dm.n]), dim3(256), 0, (hipStream_t)stream_, dm);
+    hipLaunchKernelGGL(down_multi_kernel, dim3(dm.blk0[dm.n]), dim3(256), 0, (hipStream_t)stream_, dm);
     AS_CHECK_LAUNCH();
     return AS_OK;
 }

@@ -430,7 +430,8 @@ int as_stem_pool_image_f32(const float* x, const int32_t* in_off, const int32_t*
 /* One launch for up to AS_MAX_MULTI of the down-sampling steps above (independent problems: the style towers and dur_block march through
  * their ResBlks in step, models.py:385-411,530-535).  kind 0 = as_dwconv_down[_image]_f32 (w [C][kh*3], bias [C], lrelu = LeakyReLU on the
  * result), 1 = as_avgpool_down[_image]_f32 (res / ldr optional, lrelu = the image holds LeakyReLU(y)), 2 = as_stem_pool_image_f32 (w = the
- * stem's fp32 image [T][Kp][C], bias or NULL).  y (kinds 0, 1) and yh as there; the single entry points are this with n = 1. */
+ * stem's fp32 image [T][Kp][C], bias or NULL).  y (kinds 0, 1) and yh as there; the single entry points are this with n = 1.  A problem
+ * without outputs (B, max_out or Hout 0) launches nothing and writes nothing, the image's zero column included. */
 typedef struct AsDownArgs {
     int32_t kind;
     const float* x; int32_t ldx;
@@ -444,6 +445,11 @@ typedef struct AsDownArgs {
     uint16_t* yh; int32_t n_out;
 } AsDownArgs;
 int as_down_multi_f32(const AsDownArgs* list_host, int n, as_stream_t stream);
+/* The grid of as_down_multi_f32 for one problem, a function of host-known shapes alone (csrc/down_strips.h states the rule): the output
+ * image of every (utterance, 8-channel group) is cut into *strips runs of *rows output rows (the last run: what is left), one workgroup
+ * each, which walks its rows 256 outputs per trip.  kind as in AsDownArgs, max_wo = the widest utterance's output columns, groups = the
+ * 8-channel groups (an image: 2 * ceil(C / 16) rounded up to a multiple of 8).  Hout = 0: no strips. */
+int as_down_strip_rule(int kind, int Hout, int max_wo, int B, int groups, int32_t* strips, int32_t* rows);
 int as_im2col_valid_image_f32(const float* x, int ldx, const int32_t* in_off, const int32_t* in_w, const int32_t* out_off,
                               const int32_t* out_w, int K, int stride, int lrelu, int B, int C, uint16_t* yh, as_stream_t stream);
 int as_mean_pool_f32(const float* x, int ldx, const int32_t* col_off, int B, int C, int lrelu, float* y, int ldy,
