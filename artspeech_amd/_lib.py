@@ -162,6 +162,11 @@ class HostIO(ctypes.Structure):                 # as_host_io: HOST pointers (as_
                 ("prosody", c_p), ("ld_prosody", ctypes.c_int32)]                                                    # prosody: HOST
 
 
+class TokenProsody(ctypes.Structure):
+    """as_token_prosody (as_plan_set_token_prosody): DEVICE rows [sum tok_lens][ld >= AS_PROSODY_DIM], one per packed token"""
+    _fields_ = [("rows", c_p), ("ld", ctypes.c_int32), ("smooth", ctypes.c_int32)]
+
+
 (AS_MOD_FORWARD_A, AS_MOD_FORWARD_B, AS_MOD_ENCODER, AS_MOD_STYLE, AS_MOD_DURATION, AS_MOD_ARTS, AS_MOD_DECODER, AS_MOD_FORWARD_B_CAP,
  AS_MOD_VOICE, AS_MOD_FORWARD_A_VOICE) = range(10)
 _pB, _pIO = ctypes.POINTER(Batch), ctypes.POINTER(ForwardIO)
@@ -186,6 +191,7 @@ _SIGNATURES.update({
     "as_plan_set_merge": (c_i, [c_p, c_i]),
     "as_plan_set_timing": (c_i, [c_p, c_i]),
     "as_plan_set_operand_mode": (c_i, [c_p, c_i]),
+    "as_plan_set_token_prosody": (c_i, [c_p, ctypes.POINTER(TokenProsody)]),
     "as_plan_phase_ms": (c_i, [c_p, ctypes.POINTER(ctypes.c_float), c_i]),
     "as_plan_set_layout_cap": (c_i, [c_p, c_i]),
     "as_plan_layout_flushes": (c_i, [c_p]),

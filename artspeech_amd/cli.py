@@ -12,7 +12,10 @@ One voice, many sentences: ``--save-voice voice.npz`` (with ``--ref-wav``) also 
 ``--voice voice.npz`` replaces ``--ref-wav`` in later runs -- the reference is not processed again.  Exactly one of ``--ref-wav`` and
 ``--voice`` is given.
 
-How it is spoken: ``--speed`` (speaking rate, 1 = as predicted), ``--pitch-semitones`` and ``--energy-db`` (pipeline.Prosody).
+How it is spoken: ``--speed`` (speaking rate, 1 = as predicted), ``--pitch-semitones`` and ``--energy-db`` (pipeline.Prosody).  Inside the
+utterance: ``--emphasis FIRST:LAST:SEMITONES[:SPEED[:DB]]`` (repeatable) raises the pitch of tokens FIRST..LAST (indices into the cleaned
+phoneme string, inclusive) by SEMITONES, speaks them at SPEED (0.5 = twice as long: a stressed word, a longer pause on a comma) and DB louder;
+``--smooth-prosody`` glides between the tokens' settings instead of stepping.
 """
 import argparse
 import json
@@ -60,6 +63,10 @@ def build_parser():
     ap.add_argument("--speed", type=float, default=1.0, help="speaking rate: 2 = twice as fast (durations halved), in (0, 16]")
     ap.add_argument("--pitch-semitones", type=float, default=0.0, help="raise (or, negative, lower) the pitch by this many semitones")
     ap.add_argument("--energy-db", type=float, default=0.0, help="raise (or lower) the frame energy by this many dB")
+    ap.add_argument("--emphasis", action="append", default=[], metavar="FIRST:LAST:SEMITONES[:SPEED[:DB]]",
+                    help="tokens FIRST..LAST (inclusive) of the phoneme string: pitch raised by SEMITONES, spoken at SPEED (default 1), DB louder "
+                         "(default 0); repeatable, a later span replaces an earlier one where they overlap")
+    ap.add_argument("--smooth-prosody", action="store_true", help="with --emphasis: glide linearly between the tokens' settings (centre to centre)")
     ap.add_argument("--out", default="output.wav")
     ap.add_argument("--jdc", help="Utils/JDC/bst.t7")
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
@@ -85,6 +92,7 @@ def parse_args(argv=None):
         a.vocoder_runtime = True
     try:
         a.prosody = prosody_of(a)
+        a.spans = emphasis_spans(a.emphasis)
     except ValueError as e:
         ap.error(str(e))
     return ap, a
@@ -96,6 +104,33 @@ def prosody_of(a):
     if a.speed == 1.0 and a.pitch_semitones == 0.0 and a.energy_db == 0.0:
         return None
     return Prosody(speed=a.speed, pitch_semitones=a.pitch_semitones, energy_db=a.energy_db)
+
+
+def emphasis_spans(specs):
+    """--emphasis FIRST:LAST:SEMITONES[:SPEED[:DB]] strings -> [(0, first, last, pipeline.Prosody)] (the one utterance of a command line)"""
+    from .pipeline import Prosody
+    spans = []
+    for spec in specs:
+        parts = spec.split(":")
+        if not 3 <= len(parts) <= 5:
+            raise ValueError(f"--emphasis {spec}: expected FIRST:LAST:SEMITONES[:SPEED[:DB]]")
+        try:
+            first, last = int(parts[0]), int(parts[1])
+            semi, speed, db = float(parts[2]), float(parts[3]) if len(parts) > 3 else 1.0, float(parts[4]) if len(parts) > 4 else 0.0
+        except ValueError:
+            raise ValueError(f"--emphasis {spec}: FIRST and LAST are token indices, SEMITONES, SPEED and DB numbers") from None
+        if first < 0 or last < first:
+            raise ValueError(f"--emphasis {spec}: 0 <= FIRST <= LAST")
+        spans.append((0, first, last, Prosody(speed=speed, pitch_semitones=semi, energy_db=db)))
+    return spans
+
+
+def token_prosody_of(a, tts):
+    """the per-token settings of the parsed --emphasis spans for this phoneme string (pipeline.Prosody.from_spans), or None without spans"""
+    from .pipeline import Prosody
+    if not a.spans:
+        return None
+    return Prosody.from_spans(a.spans, [len(tts.textcleaner(a.phonemes))])[0]
 
 
 def main(argv=None):
@@ -120,15 +155,19 @@ def main(argv=None):
         tts.attach_ema_extractor(a.ema)
         h = json.load(open(a.vocoder_config)) if a.vocoder_config else None
         tts.attach_vocoder(h, a.vocoder, runtime=a.vocoder_runtime)
+    try:
+        tok = dict(token_prosody=token_prosody_of(a, tts), token_smooth=a.smooth_prosody)
+    except ValueError as e:
+        ap.error(f"--emphasis: {e}")
     if a.voice:
         from .pipeline import Voice
-        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap)
+        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, **tok)
     else:
         wave_in = read_wav(a.ref_wav)
         if a.save_voice:
             tts.voice_from_wave(wave_in).save(a.save_voice)
             print(f"{a.save_voice}: voice of {a.ref_wav}")
-        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap)
+        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, **tok)
     write_wav(a.out, audio.cpu().numpy())
     print(f"{a.out}: {audio.numel() / 24000.0:.2f} s of audio from {tts._last_frames[0]} mel frames")
     return 0

@@ -95,6 +95,17 @@ int as_durations_prosody_launch(const float* dur_f32, const int32_t* forced_dur,
 // fmaf(gain[b][track], y, offset[b][track]); columns at or past col_off[B] (a capacity layout's filler) as computed
 int as_project_cols_prosody_launch(const float* x, int ldx, int K, int N, const float* w, const float* bias, int M, float* y, int ldy,
                                    const float* pros, int ld_pros, const int32_t* col_off, int B, int track0, hipStream_t s);
+// per-token prosody (as_plan_set_token_prosody, rows [ntok][ld >= AS_PROSODY_DIM]; token_prosody.hip, the rule: token_prosody.h).
+// out[i] = dur_f32[i] * rows[i][AS_PROSODY_DUR] (* pros[utterance of i][AS_PROSODY_DUR] when pros is given): what the durations launch
+// then reads in place of the predictor's output
+int as_token_dur_scale_launch(const float* dur_f32, const float* rows, int ld, const int32_t* tok_off, int B, int ntok, const float* pros,
+                              int ld_pros, float* out, hipStream_t stream);
+// start [ntok + 1] = the exclusive prefix sum of the integer durations over the packed tokens (half-rate frames)
+int as_token_starts_launch(const int32_t* dur_i32, int ntok, int32_t* start, hipStream_t stream);
+// every value of the valid full-rate columns of fne [12][ld] (n_cols = 2 n_frames_max of them; valid: below 2 frame_off[B]) becomes
+// fmaf(gain, x, offset) with its column's gains and offsets by token_prosody.h's rule; tof [n_frames_max] = the frame -> token map
+int as_token_tracks_launch(float* fne, int ld, int n_cols, const int32_t* tof, int n_frames_max, const int32_t* frame_off, const int32_t* tok_off,
+                           int B, int ntok, const int32_t* start, const float* rows, int ld_rows, int smooth, hipStream_t stream);
 
 // fp32 samples w [N] -> 16-bit PCM by the rule of as_conv_post_pcm_f32 (vocoder.hip; a NaN stores 0 and raises AS_STATUS_F16_RANGE).
 // n_valid (a capacity layout, device count): samples [*n_valid, N) are not read; pcm and w_fill (each may then be NULL) get 0 there

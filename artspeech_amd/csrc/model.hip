@@ -1774,6 +1774,10 @@ struct PhaseA {                   // what the first half leaves in workspace A f
     float *feat12 = nullptr, *style = nullptr, *a_en = nullptr, *t_en = nullptr, *duration = nullptr;
     int ld_en = 0;
     int32_t *dur_i = nullptr, *frame_off = nullptr;
+    // per-token prosody (as_plan_set_token_prosody; NULL without): the scaled durations and the tokens' first frames.  Both halves' extra
+    // buffers live in workspace A, so that workspace B is laid out exactly as without controls
+    float* dur_s = nullptr;
+    int32_t* tok_start = nullptr;
     const Lay *tok = nullptr, *ref = nullptr;
     bool voice = false;           // voice mode (as_forward_io.voices): no reference layout, no feat12
     bool ok() const { return tok && (ref || voice); }
@@ -1785,6 +1789,28 @@ bool batch_ok(const as_batch* b, bool tok, bool ref, bool frames)
 }
 std::vector<int> vec_of(const int32_t* p, int n) { return std::vector<int>(p, p + n); }
 int voice_dim(const as_model& m) { return 2 * m.cfg.style_dim + m.cfg.style_dim / 4; }
+
+// round half even -> clamp to [1, 16384] (or the forced durations), frame offsets, the frame -> token map: one launch.  Per-token prosody
+// (tp.rows: as_plan_set_token_prosody) puts one launch in front of it that writes the predictor's durations times the token's scale -- and the
+// utterance's, io->prosody -- into dur_s, which the same durations launch then reads in place of them.
+void durations_launch(Ctx& c, const as_token_prosody& tp, float* dur_s, const float* duration, const as_forward_io* io, const Lay* tok,
+                      int32_t* dur_i, int32_t* frame_off, int32_t* tof, int max_frames)
+{
+    const int B = tok->B, ntok = tok->N;
+    const int32_t *tok_off = tok->d_off, *forced = io->forced_dur;
+    const float* pros = io->prosody;
+    const int ld_pros = io->ld_prosody;
+    if (!tp.rows) {
+        RUN(c, as_durations_prosody_launch(duration, forced, tok_off, B, pros, ld_pros, dur_i, frame_off, tof, max_frames, c.s));
+        return;
+    }
+    if (forced) { c.fail(AS_EINVAL); return; }                           // (forced durations would ignore the scales)
+    // (locals, not tp.rows / tp.ld: a recorded RUN copies what the call names into its closure, and tp is a reference)
+    const float* rows = tp.rows;
+    const int ld = tp.ld;
+    RUN(c, as_token_dur_scale_launch(duration, rows, ld, tok_off, B, ntok, pros, ld_pros, dur_s, c.s));
+    RUN(c, as_durations_prosody_launch(dur_s, nullptr, tok_off, B, nullptr, 0, dur_i, frame_off, tof, max_frames, c.s));
+}
 
 PhaseA forward_a_full(Ctx& c, const as_batch* batch, const as_forward_io* io)
 {
@@ -1807,6 +1833,11 @@ PhaseA forward_a_full(Ctx& c, const as_batch* batch, const as_forward_io* io)
         if (io->frame_off) A.frame_off = io->frame_off;
     }
     float* ds = c.f32((size_t)B * (m.cfg.style_dim / 4));
+    const as_token_prosody tp = c.p.tok_pros;
+    if (tp.rows) {
+        A.dur_s = c.f32(Nt);
+        A.tok_start = c.i32((size_t)Nt + 1);
+    }
     const float* stats = m.vec("__stats24");
     if (c.go()) c.p.mark(0, c.s);
     c.hint(0, 4.0 * (n_mels + 11.0 + 12.0) * A.ref->N);
@@ -1871,7 +1902,7 @@ PhaseA forward_a_full(Ctx& c, const as_batch* batch, const as_forward_io* io)
     // (with the frame counts given nobody reads this half's copy: the second half computes durations, offsets and the frame -> token map)
     // (... and so does a call under a frame capacity, as_forward_io.frame_cap)
     if (!batch->frames && io->frame_cap <= 0)
-        RUN(c, as_durations_prosody_launch(A.duration, io->forced_dur, A.tok->d_off, B, io->prosody, io->ld_prosody, A.dur_i, A.frame_off, nullptr, 0, c.s));
+        durations_launch(c, tp, A.dur_s, A.duration, io, A.tok, A.dur_i, A.frame_off, nullptr, 0);
     return A;
 }
 
@@ -1898,6 +1929,11 @@ PhaseA forward_a_voice(Ctx& c, const as_batch* batch, const as_forward_io* io)
         if (io->frame_off) A.frame_off = io->frame_off;
     }
     float* ds = c.f32((size_t)B * S);
+    const as_token_prosody tp = c.p.tok_pros;
+    if (tp.rows) {
+        A.dur_s = c.f32(Nt);
+        A.tok_start = c.i32((size_t)Nt + 1);
+    }
     if (c.go()) c.p.mark(0, c.s);
     RUN(c, as_voice_gather_launch(io->voices, io->ld_voice, io->n_voices, io->voice_idx, B, sd2, S, A.style, sd2, ds, S, c.s));
     if (c.go()) c.p.mark(1, c.s);
@@ -1920,7 +1956,7 @@ PhaseA forward_a_voice(Ctx& c, const as_batch* batch, const as_forward_io* io)
     f.join();
     if (c.go()) c.p.mark(2, c.s);
     if (!batch->frames && io->frame_cap <= 0)
-        RUN(c, as_durations_prosody_launch(A.duration, io->forced_dur, A.tok->d_off, B, io->prosody, io->ld_prosody, A.dur_i, A.frame_off, nullptr, 0, c.s));
+        durations_launch(c, tp, A.dur_s, A.duration, io, A.tok, A.dur_i, A.frame_off, nullptr, 0);
     return A;
 }
 
@@ -1956,9 +1992,16 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
     int32_t* dur_i = c.i32((size_t)std::max(A.tok->N, 1));
     int32_t* frame_off = c.i32(B + 1);
     float* mel_packed = dyn ? c.f32((size_t)n_mels * std::max(N2, 1)) : nullptr;   // (a merged call's mel before it goes to the submissions' slots)
+    // per-token prosody (as_plan_set_token_prosody): the scaled durations, and the tokens' first frames for the track kernel (workspace A)
+    const as_token_prosody tp = c.p.tok_pros;
+    const int ntok = A.tok->N;
+    float* dur_s = A.dur_s;
+    int32_t* tok_start = A.tok_start;
+    if (tp.rows && (segs || !dur_s || !tok_start)) { c.fail(AS_EINVAL); return; }   // (merged calls never carry token controls)
     if (io->dur_i) dur_i = io->dur_i;
     if (io->frame_off && !segs) frame_off = io->frame_off;
-    RUN(c, as_durations_prosody_launch(A.duration, io->forced_dur, A.tok->d_off, B, io->prosody, io->ld_prosody, dur_i, frame_off, tof, N1, c.s));
+    durations_launch(c, tp, dur_s, A.duration, io, A.tok, dur_i, frame_off, tof, N1);
+    if (tp.rows) RUN(c, as_token_starts_launch(dur_i, ntok, tok_start, c.s));
     if (dyn) {
         const Lay *lg1 = c.dyn_lay(2, B, io->frame_cap), *lg2 = lg1 ? c.scaled(lg1, 2) : nullptr;
         if (!lg1 || !lg2) return;
@@ -2008,6 +2051,15 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
         c.hint(0, 4.0 * C * ((double)A.tok->N + N1));
         RUN(c, as_expand_f32(A.a_en, A.ld_en, C, tof, N1, 1, a_ex, N1, c.s));
         arts_predictor(c, a_ex, N1, lay1, fc, fne, N2, io->prosody, io->ld_prosody);
+        if (tp.rows) {
+            // the tokens' gains and offsets on the twelve tracks, in place: behind the predictors' projections on the calling stream's
+            // queue and in front of the join, so the decoder and the F0 / N / EMA outputs read the controlled values in every kind of plan
+            // (locals: this RUN is a recorded one in merging serial plans, and its closure copies what the call names -- never A or tp whole)
+            const int32_t* tok_off = A.tok->d_off;
+            const float* rows = tp.rows;
+            const int ld_rows = tp.ld, smooth = tp.smooth;
+            RUN(c, as_token_tracks_launch(fne, N2, N2, tof, N1, frame_off, tok_off, B, ntok, tok_start, rows, ld_rows, smooth, c.s));
+        }
         if (f) f->join();
     }
     if (c.go()) c.p.mark(3, c.s);
@@ -2055,10 +2107,11 @@ bool io_ok(const as_forward_io* io, bool need_out)
 }
 // the batch and io of a forward entry point, full or voice mode (voice mode: no reference lengths, a table of at least one voice row,
 // no feat12 -- it has no meaning without a reference)
-bool forward_ok(const as_model* m, const as_batch* batch, const as_forward_io* io, bool need_out, bool frames)
+bool forward_ok(const as_model* m, const as_plan* p, const as_batch* batch, const as_forward_io* io, bool need_out, bool frames)
 {
     if (!io || !batch_ok(batch, true, !io->voices, frames)) return false;
     if (io->prosody && (io->ld_prosody < AS_PROSODY_DIM || io->forced_dur)) return false;   // (forced durations would ignore dur_scale)
+    if (p->tok_pros.rows && (io->forced_dur || io->segs)) return false;                      // (per-token prosody: the same reason; no merged calls)
     if (!io->voices) return io_ok(io, need_out);
     return io->tokens && (!need_out || io->mel_out) && io->ld_voice >= voice_dim(*m) && io->n_voices >= 1 && !io->feat12;
 }
@@ -2537,6 +2590,18 @@ extern "C" int as_plan_set_operand_mode(as_plan* p, int n_prod)
     return AS_OK;
 }
 
+extern "C" int as_plan_set_token_prosody(as_plan* p, const as_token_prosody* tp)
+{
+    if (!p) return AS_EINVAL;
+    if (!tp) {
+        p->tok_pros = as_token_prosody{nullptr, 0, 0};
+        return AS_OK;
+    }
+    if (!tp->rows || tp->ld < AS_PROSODY_DIM || (tp->smooth != 0 && tp->smooth != 1)) return AS_EINVAL;
+    p->tok_pros = *tp;
+    return AS_OK;
+}
+
 extern "C" int as_plan_set_timing(as_plan* p, int on)
 {
     if (!p) return AS_EINVAL;
@@ -2646,7 +2711,7 @@ extern "C" int as_forward_test_begin(const as_model* m, as_plan* p, const as_bat
                                      as_stream_t stream)
 {
     return abi([&] {
-        if (!m || !p || !forward_ok(m, batch, io, false, false)) return AS_EINVAL;
+        if (!m || !p || !forward_ok(m, p, batch, io, false, false)) return AS_EINVAL;
         Call k(m, p, ws_a, ws_a_bytes, stream, Pass::Run, true);
         const PhaseA A = forward_a(k.c, batch, io);
         if (A.ok()) outputs_a(k.c, A, io);
@@ -2658,7 +2723,7 @@ extern "C" int as_forward_test_finish(const as_model* m, as_plan* p, const as_ba
                                       void* ws_b, size_t ws_b_bytes, as_stream_t stream)
 {
     return abi([&] {
-        if (!m || !p || !forward_ok(m, batch, io, true, true)) return AS_EINVAL;
+        if (!m || !p || !forward_ok(m, p, batch, io, true, true)) return AS_EINVAL;
         // recover where the first half left its results: the same allocation sequence, nothing launched (_begin's layouts: no trim)
         Call ka(m, p, ws_a, ws_a_bytes, stream, Pass::Replay, false);
         const PhaseA A = forward_a(ka.c, batch, io);
@@ -2673,7 +2738,7 @@ extern "C" int as_forward_test(const as_model* m, as_plan* p, const as_batch* ba
                                void* ws_b, size_t ws_b_bytes, int32_t* frames_host_out, as_stream_t stream)
 {
     return abi([&] {
-        if (!m || !p || !forward_ok(m, batch, io, true, false)) return AS_EINVAL;
+        if (!m || !p || !forward_ok(m, p, batch, io, true, false)) return AS_EINVAL;
         Call ka(m, p, ws_a, ws_a_bytes, stream, Pass::Run, true);
         const PhaseA A = forward_a(ka.c, batch, io);
         if (ka.done() || !A.ok()) return ka.done() ? ka.done() : AS_EINVAL;

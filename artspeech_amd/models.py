@@ -22,6 +22,9 @@ skip the reference features, the style towers and dur_block.
 
 Prosody: ``prosody=`` (a [B, 25] tensor, pipeline.Prosody rows) on the same calls sets each utterance's speaking rate (its durations are
 scaled before they are rounded) and a gain and an offset for each of the twelve tracks the decoder reads (F0, energy, EMA0..9, normalised).
+``token_prosody=`` (a [sum tok_lens, 25] tensor, pipeline.Prosody.token_rows) on ``forward`` / ``forward_packed`` does the same per TOKEN
+(as_plan_set_token_prosody: stress a word, lengthen a pause); ``token_smooth=True`` joins the tokens' gains and offsets linearly between
+the tokens' centres.  The lanes do not carry it.
 """
 import ctypes
 import hashlib
@@ -231,11 +234,27 @@ def _prosody_args(rt, prosody, B, where="device"):
     if not torch.is_tensor(prosody) or prosody.dim() != 2 or prosody.shape[0] != B or prosody.shape[1] < _lib.AS_PROSODY_DIM or \
             prosody.dtype != torch.float32:
         got = tuple(prosody.shape) if torch.is_tensor(prosody) else type(prosody).__name__
-        raise ValueError(f"prosody: expected a float32 [{B}, {_lib.AS_PROSODY_DIM}] tensor (one row per utterance), got {got}")
+        raise ValueError(f"prosody: expected a float32 [{B}, {_lib.AS_PROSODY_DIM}] tensor (one row per utterance, or per token), got {got}")
     on_gpu = prosody.is_cuda and prosody.device == rt.device
     if prosody.stride(-1) != 1 or (where == "host" and prosody.is_cuda) or (where != "host" and not on_gpu):
         raise _lib.HipLibraryError(f"prosody: expected {'a host' if where == 'host' else 'a device'} tensor with dense rows")
     return (prosody.data_ptr(), prosody.stride(0)), prosody
+
+
+def _token_prosody_args(rt, token_prosody, n_tok, smooth):
+    """token_prosody -> the as_token_prosody of as_plan_set_token_prosody and the tensor to keep alive.  token_prosody: fp32
+    [n_tok, >= AS_PROSODY_DIM] (pipeline.Prosody.token_rows: one row per packed token), moved to the GPU like the utterance rows of
+    forward_packed (_prosody_args' "any": a device tensor is read as it is, anything else is copied)."""
+    (p, ld), keep = _prosody_args(rt, token_prosody, n_tok, "any")
+    tp = _lib.TokenProsody()
+    tp.rows, tp.ld, tp.smooth = p, ld, int(bool(smooth))
+    return tp, keep
+
+
+def _no_token_prosody(token_prosody):
+    if token_prosody is not None:
+        raise ValueError("token_prosody: the lanes do not carry per-token controls (their plans never have them set); "
+                         "use ArtsSpeech.forward / forward_packed")
 
 
 def _fill_inputs(io, rt, B, ptr, where, tok, mel_p, f0_p, ema_p, forced, voice, voice_idx, prosody):
@@ -462,11 +481,12 @@ class ArtsSpeech(_Module):
         return v
 
     def forward(self, batch, s2s_attn=None, s2s_attn_mono=None, step="test", mode="train", epoch=0, features=None,
-                forced_durations=None, return_aux=False, voice=None, voice_idx=None, prosody=None):
+                forced_durations=None, return_aux=False, voice=None, voice_idx=None, prosody=None, token_prosody=None, token_smooth=False):
         """voice: a [V, voice_dim] table of compute_voice rows -- utterance b then speaks in row voice_idx[b] (None: row b), and the batch's
         mels / mel_input_length are not read (they may be None).
         prosody: [B, 25] rows of pipeline.Prosody (as_forward_io.prosody: speaking rate, then a gain and an offset per F0 / energy / EMA
-        track); not with forced_durations."""
+        track); not with forced_durations.
+        token_prosody / token_smooth: the same per token, [sum input_lengths, 25] in packed order (see `forward_packed`)."""
         if step != "test":
             raise NotImplementedError("training branches (step='first'/'second') are out of scope (SURVEY.md section 2)")
         if self.rt is None:
@@ -489,14 +509,38 @@ class ArtsSpeech(_Module):
                 forced = torch.cat(fd).to(device=dev, dtype=torch.int32)
                 frames = [int(f.sum()) for f in fd]
             out = self.forward_packed(tok, tl, mel_p, f0_p, ema_p, ml, forced=forced, frames_hint=frames, aux=return_aux, voice=voice,
-                                      voice_idx=voice_idx, prosody=prosody)
+                                      voice_idx=voice_idx, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth)
             mel = unpack(out["mel"], layout(out["frames2"], dev))
         if return_aux:
             return mel, out
         return mel
 
     def forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None,
-                       voice=None, voice_idx=None, prosody=None):
+                       voice=None, voice_idx=None, prosody=None, token_prosody=None, token_smooth=False):
+        """`_forward_packed` (the arguments are described there), with per-token prosody around it.
+        token_prosody: [sum tok_lens, 25] controls, row i for packed token i (pipeline.Prosody.token_rows; the columns of a prosody row: a
+        duration scale, then a gain and an offset per track; a device tensor is read as it is, anything else is copied to the GPU); not
+        with forced.  token_smooth: the gains and offsets are control points at the tokens' centres, joined linearly inside an utterance,
+        instead of holding over each token's frames.  They are state of the plan (as_plan_set_token_prosody): set before the workspaces
+        are sized, cleared when the call has been enqueued, whatever happens.  With frames_hint given, the frames must be the sums of the
+        controlled durations.  A tensor that is not on the GPU is copied there for this call only: the copy is released when the call
+        returns, which is safe because torch's allocator reuses memory in the order of the current stream, the stream the kernels are on
+        (the same holds for `prosody`).  A call that is captured into a graph must therefore pass a DEVICE tensor and keep it alive:
+        replays read it."""
+        args = (tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames_hint, aux, out, frame_cap, voice, voice_idx, prosody)
+        if token_prosody is None:
+            return self._forward_packed(*args)
+        rt, L = self.rt, _lib.lib()
+        with torch.cuda.device(rt.device):
+            tp, _keep = _token_prosody_args(rt, token_prosody, sum(int(v) for v in tok_lens), token_smooth)
+            check(L.as_plan_set_token_prosody(rt.plan, ctypes.byref(tp)), "as_plan_set_token_prosody")
+            try:
+                return self._forward_packed(*args)
+            finally:
+                L.as_plan_set_token_prosody(rt.plan, None)
+
+    def _forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None,
+                        voice=None, voice_idx=None, prosody=None):
         """The whole hot path on packed tensors (what bench.py times): one call of as_forward_test when the integer frame
         counts are known (forced durations), else as_forward_test_begin -> one device->host read of B + 1 integers ->
         as_forward_test_finish.  `out`: the dict of a previous call with the same geometry (its tensors are reused).
@@ -605,7 +649,7 @@ class Lanes:
         return int(_lib.lib().as_lanes_merged_calls(self.h, int(lane)))
 
     def submit(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames=None, out=None, capacity=None, frame_cap=None, voice=None,
-               voice_idx=None, prosody=None):
+               voice_idx=None, prosody=None, token_prosody=None):
         """-> (lane, dict with the output tensors).  frames (per-utterance half-rate frame counts) known: graph-replayed from the second
         submit of the same tensors on a lane; None: predicted durations, `capacity` = the mel frames the output buffer is made for (eager,
         one read-back per call) -- or frame_cap = the half-rate frames to make room for (as_forward_io.frame_cap: no read-back, replayed
@@ -616,7 +660,8 @@ class Lanes:
         ref_lens are not read (None).  Adjacent: indices that continue each other in one table, or row ranges that do.
         prosody: a DEVICE fp32 [B, 25] tensor of per-utterance controls (ArtsSpeech.forward), read when the group runs (rewriting it changes
         what a replayed graph computes).  Adjacent: row ranges of one table that continue each other; a submission with prosody never
-        joins one without."""
+        joins one without.  token_prosody: ValueError (the lanes do not carry per-token controls)."""
+        _no_token_prosody(token_prosody)
         rt, L = self.rt, _lib.lib()
         dev = rt.device
         tok_lens = [int(v) for v in tok_lens]
@@ -661,14 +706,16 @@ class Lanes:
         check(_lib.lib().as_lanes_set_debug(self.h, int(bool(on))), "as_lanes_set_debug")
 
     def submit_host(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames, out_mel, frame_cap=None, frame_off=None, voice=None,
-                    voice_idx=None, prosody=None):
+                    voice_idx=None, prosody=None, token_prosody=None):
         """as_lanes_submit_host: HOST tensors in (pinned: `.pin_memory()`), the mel back into the host tensor `out_mel` [n_mels][>= 2 sum
         frames]; the lane owns the device side (its block, the copies, the group's launch).  -> lane.  Keep the tensors alive and unchanged
         until `wait(lane)`; `out_mel` is valid after it.  Predicted durations: frames=None, forced=None, frame_cap = the half-rate frames
         there is room for (out_mel [n_mels][>= 2 frame_cap]) and frame_off = a host int32 tensor [B + 1] that receives the offsets.
         voice: a DEVICE table that stays resident (keep it unchanged until `wait`); voice_idx: HOST integers [B] (copied into the lane's
         block with the tokens) or None = row b; mel_p / f0_p / ema_p / ref_lens are then not read.
-        prosody: a HOST fp32 [B, 25] tensor of per-utterance controls, copied into the lane's block with the tokens."""
+        prosody: a HOST fp32 [B, 25] tensor of per-utterance controls, copied into the lane's block with the tokens.
+        token_prosody: ValueError (the lanes do not carry per-token controls)."""
+        _no_token_prosody(token_prosody)
         tok_lens = [int(v) for v in tok_lens]
         ref_lens = None if voice is not None else [int(v) for v in ref_lens]
         frames = [int(v) for v in frames] if frames is not None else None

@@ -12,7 +12,9 @@ features, the style towers and dur_block.  ``Voice.save`` / ``Voice.load`` keep 
 
 How a sentence is spoken: ``Prosody(speed=, pitch_semitones= / pitch_factor=, energy_db=, ema_gain=, ema_offset=)`` in human units;
 ``synthesis_mel(..., prosody=p)`` (one for every utterance, or one per utterance) turns it into the per-utterance row the library reads
-(as_forward_io.prosody) with the model's own normalisation statistics.
+(as_forward_io.prosody) with the model's own normalisation statistics.  Inside an utterance: ``token_prosody=`` takes one entry per
+utterance, each a list with a Prosody (or None) per token -- ``Prosody.from_spans`` builds it from (utterance, first token, last token,
+Prosody) spans -- and ``token_smooth=True`` glides between the tokens' settings instead of stepping (as_plan_set_token_prosody).
 """
 import json
 import math
@@ -139,6 +141,46 @@ class Prosody:
             raise TypeError("prosody: expected a pipeline.Prosody or a list of them")
         return torch.stack([p.row(stats) for p in ps])
 
+    @staticmethod
+    def token_rows(per_token, tok_lens, stats):
+        """Per-token controls -> float32 [sum tok_lens, 25], row i for packed token i (as_plan_set_token_prosody; forward_packed's
+        token_prosody).  per_token: one entry per utterance -- None (no control in that utterance) or a list with one Prosody, or None for
+        identity, per token.  A token's `speed` scales ITS duration (a pause: a slow space or comma), its pitch / energy / articulator
+        settings act on its frames (or, smoothed, glide to its neighbours')."""
+        tok_lens = [int(n) for n in tok_lens]
+        per_token = list(per_token)
+        if len(per_token) != len(tok_lens):
+            raise ValueError(f"{len(per_token)} per-token lists for {len(tok_lens)} utterances")
+        ident, out, made = Prosody.identity().row(stats), [], {}        # (made: a span repeats ONE Prosody object -- its row is built once)
+        for b, (ps, n) in enumerate(zip(per_token, tok_lens)):
+            ps = [None] * n if ps is None else list(ps)
+            if len(ps) != n:
+                raise ValueError(f"utterance {b}: {len(ps)} prosody settings for {n} tokens")
+            for q in ps:
+                if q is not None and not isinstance(q, Prosody):
+                    raise TypeError("token prosody: expected a pipeline.Prosody or None per token")
+                if q is not None and id(q) not in made:
+                    made[id(q)] = q.row(stats)
+                out.append(ident if q is None else made[id(q)])
+        return torch.stack(out) if out else torch.zeros(0, 25)
+
+    @staticmethod
+    def from_spans(spans, tok_lens):
+        """(utterance, first token, last token, Prosody) spans, token indices inclusive -> the per_token list of `token_rows`: a later span
+        replaces an earlier one where they overlap, tokens in no span stay None (identity)."""
+        tok_lens = [int(n) for n in tok_lens]
+        per = [[None] * n for n in tok_lens]
+        for b, first, last, q in spans:
+            b, first, last = int(b), int(first), int(last)
+            if not 0 <= b < len(tok_lens):
+                raise ValueError(f"span for utterance {b}: there are {len(tok_lens)}")
+            if not 0 <= first <= last < tok_lens[b]:
+                raise ValueError(f"span {first}..{last} does not lie inside utterance {b}'s {tok_lens[b]} tokens")
+            if not isinstance(q, Prosody):
+                raise TypeError("span: expected a pipeline.Prosody")
+            per[b][first: last + 1] = [q] * (last - first + 1)
+        return per
+
 
 class ArtSpeech:
     def __init__(self, config=None, checkpoint=None, device=None, stats_path=None):
@@ -234,7 +276,8 @@ class ArtSpeech:
         return table, torch.tensor(idx, dtype=torch.int32)
 
     @torch.no_grad()
-    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None):
+    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
+                            token_prosody=None, token_smooth=False):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed, 24 kHz) reference wave on: log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator.  Returns the samples (mel frames if no vocoder is attached).
         Loading / trimming / resampling the file (librosa, test.py:99-106) and espeak stay with the caller."""
@@ -245,6 +288,7 @@ class ArtSpeech:
             mels = [self.frontend(ref_wave)[0]]
             phonemes = [phonemes]
             features = None if features is None else [features]
+            token_prosody = None if token_prosody is None else [token_prosody]   # (one utterance: its own per-token list)
         else:
             mel, lens = self.frontend(list(ref_wave))
             mels = [mel[b, :, :n] for b, n in enumerate(lens)]
@@ -254,7 +298,8 @@ class ArtSpeech:
             if self.generator is None:
                 raise RuntimeError("frame_cap runs the acoustic model and the generator as one chain: attach_vocoder(h, checkpoint, runtime=True) first")
             kw["frame_cap"] = frame_cap
-        out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody, **kw)
+        out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody, token_prosody=token_prosody,
+                 token_smooth=token_smooth, **kw)
         return out[0] if single and out.dim() > 1 and self.generator is not None else out
 
     def attach_vocoder(self, h=None, checkpoint=None, runtime=False):
@@ -269,7 +314,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
-                      frame_cap=None):
+                      frame_cap=None, token_prosody=None, token_smooth=False):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the generator's last kernel.
@@ -283,9 +328,10 @@ class ArtSpeech:
         if frame_cap is not None:
             if forced_durations is not None:
                 raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
-            out = self._synthesis_wav_cap(phonemes, ref_mel, features, voice, prosody, pcm16, int(frame_cap))
+            out = self._synthesis_wav_cap(phonemes, ref_mel, features, voice, prosody, pcm16, int(frame_cap), token_prosody, token_smooth)
             return out[0] if single else out
-        mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody)
+        mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody,
+                                 token_prosody=token_prosody, token_smooth=token_smooth)
         lens = self._last_frames
         wav = (self.generator(mel, lengths=lens, pcm16=True) if pcm16 else self.generator(mel, lengths=lens))[:, 0]
         return wav[0] if single else wav
@@ -319,9 +365,14 @@ class ArtSpeech:
             feats = (f0, ema)
         return text, tl, mels, ml, feats
 
-    def packed_inputs(self, phonemes, ref_mel=None, features=None, voice=None, prosody=None):
+    def _token_rows(self, token_prosody, tok_lens, single):
+        """synthesis_*'s token_prosody -> the [sum tok_lens, 25] rows.  single (the phonemes came as ONE string): token_prosody is that
+        utterance's own list of per-token settings; else one list, or None, per utterance -- as every other per-utterance argument"""
+        return Prosody.token_rows([token_prosody] if single else token_prosody, tok_lens, self.model.ArtsSpeech)
+
+    def packed_inputs(self, phonemes, ref_mel=None, features=None, voice=None, prosody=None, token_prosody=None, token_smooth=False):
         """The keyword arguments of ArtsSpeech.forward_packed for these utterances (what ArtsSpeech.forward builds before the model call):
-        packed device tokens and either the packed reference features or the voice table; prosody rows on the device."""
+        packed device tokens and either the packed reference features or the voice table; prosody rows (per utterance, per token) on the device."""
         if (voice is None) == (ref_mel is None):
             raise ValueError("synthesis needs exactly one of ref_mel and voice")
         net = self.model.ArtsSpeech
@@ -333,6 +384,8 @@ class ArtSpeech:
             kw["tok"] = models._dev(models._pack_tokens(text, tl, net.rt.cfg.n_token), dev, torch.int32)
             if prosody is not None:
                 kw["prosody"] = Prosody.rows(prosody, B, net).to(dev)
+            if token_prosody is not None:
+                kw["token_prosody"], kw["token_smooth"] = self._token_rows(token_prosody, tl, isinstance(phonemes, str)).to(dev), bool(token_smooth)
             if voice is not None:
                 table, vidx = self._voice_table(voice, B)
                 kw["voice"], kw["voice_idx"] = table, vidx.to(dev)        # (on the device already: a captured call copies nothing)
@@ -357,9 +410,9 @@ class ArtSpeech:
             got = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len, pcm=pcm16, wav=not pcm16)
         return (got[2] if pcm16 else got[0][0]), got[1]
 
-    def _synthesis_wav_cap(self, phonemes, ref_mel, features, voice, prosody, pcm16, frame_cap):
+    def _synthesis_wav_cap(self, phonemes, ref_mel, features, voice, prosody, pcm16, frame_cap, token_prosody=None, token_smooth=False):
         from . import _lib
-        inputs = self.packed_inputs(phonemes, ref_mel, features, voice, prosody)
+        inputs = self.packed_inputs(phonemes, ref_mel, features, voice, prosody, token_prosody, token_smooth)
         samples, sample_off = self.chain_cap(inputs, frame_cap, pcm16=pcm16)
         with torch.cuda.device(self.device):
             off = sample_off.cpu().tolist()                                 # the one synchronisation: offsets, then the samples
@@ -376,7 +429,8 @@ class ArtSpeech:
         return out
 
     @torch.no_grad()
-    def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None):
+    def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None,
+                      token_prosody=None, token_smooth=False):
         """phonemes: the string the phonemizer returns (test.py:94-96) or a list of such strings; ref_mel: normalised
         log-mel [80,T] (test.py:43-47) or a list; features: (f0_raw, ema_raw) per utterance when no extractor modules
         are attached; (None, ema_raw) with a pitch extractor attached (attach_pitch_extractor).  Returns mel [B,80,2*max M] (what test.py:115 hands to the vocoder).
@@ -384,7 +438,9 @@ class ArtSpeech:
         the caller) synthesises its length-sorted round-robin shard (artspeech_amd.shard: no data-path collective) and rank 0 gets the
         whole batch back in the caller's order (other ranks: None).
         voice: a Voice (every utterance) or a list of them, in place of ref_mel / features: the reference is not processed again.
-        prosody: a Prosody (every utterance) or a list of them: speaking rate, pitch, energy and articulators (not with forced_durations)."""
+        prosody: a Prosody (every utterance) or a list of them: speaking rate, pitch, energy and articulators (not with forced_durations).
+        token_prosody: control inside an utterance -- per utterance a list with a Prosody (or None) per token (Prosody.from_spans builds it;
+        one utterance: the list itself), see Prosody.token_rows; token_smooth: glide between the tokens' settings.  Not with forced_durations."""
         if (voice is None) == (ref_mel is None):
             raise ValueError("synthesis needs exactly one of ref_mel and voice")
         if world > 1 and not isinstance(phonemes, str):
@@ -398,7 +454,9 @@ class ArtSpeech:
                                          features=None if features is None else [features[i] for i in idx],
                                          forced_durations=None if forced_durations is None else [forced_durations[i] for i in idx],
                                          voice=voice if voice is None or isinstance(voice, Voice) else [voice[i] for i in idx],
-                                         prosody=prosody if prosody is None or isinstance(prosody, Prosody) else [prosody[i] for i in idx])
+                                         prosody=prosody if prosody is None or isinstance(prosody, Prosody) else [prosody[i] for i in idx],
+                                         token_prosody=None if token_prosody is None else [token_prosody[i] for i in idx],
+                                         token_smooth=token_smooth)
                 return [sub[k, :, : self._last_frames[k]].cpu() for k in range(len(idx))]
 
             parts = shard.sharded_forward(step, lens, world, rank)
@@ -412,10 +470,12 @@ class ArtSpeech:
         text, tl, mels, ml, feats = self._padded_batch(phonemes, ref_mel, features)
         B = len(tl)
         rows = None if prosody is None else Prosody.rows(prosody, B, self.model.ArtsSpeech)
+        trows = None if token_prosody is None else self._token_rows(token_prosody, tl, isinstance(phonemes, str))
         table, vidx = (None, None) if voice is None else self._voice_table(voice, B)
         batch = [text, torch.LongTensor(tl), mels, None if ml is None else torch.LongTensor(ml), None, None, None]     # test.py:110-111
         mel, aux = self.model.ArtsSpeech(batch, None, None, step="test", features=feats, forced_durations=forced_durations,
-                                         return_aux=True, voice=table, voice_idx=vidx, prosody=rows)                  # test.py:113
+                                         return_aux=True, voice=table, voice_idx=vidx, prosody=rows, token_prosody=trows,
+                                         token_smooth=token_smooth)                                                   # test.py:113
         self._last_frames = list(aux["frames2"])
         return mel
 

@@ -660,6 +660,32 @@ int as_plan_set_timing(as_plan* p, int on);
 /* matrix-core products per fp32 product in this plan's forwards: 3 = f16x3 (fp32-accurate, default); 1 = plain fp16 operands
  * (the 16-bit-operand mode BASELINE.md names for config C2; its error is reported by bench.py and tests/test_net_gpu.py) */
 int as_plan_set_operand_mode(as_plan* p, int n_prod);
+/* Per-token prosody: control INSIDE an utterance (stress a word, lengthen a pause, raise the pitch towards the end of a question, open the
+ * jaw on one vowel), as state of the plan.  Row i belongs to packed token i (the order of as_forward_io.tokens) and has the columns of a
+ * prosody row (AS_PROSODY_DUR, AS_PROSODY_GAIN + c, AS_PROSODY_OFFSET + c; below, next to as_forward_io.prosody).  DEVICE memory, fp32
+ * [sum tok_lens][ld >= AS_PROSODY_DIM], read when a forward RUNS (a replayed graph sees new contents).
+ *   Durations: token i of utterance b gets clamp(rint(v), 1, 16384) frames, v = fp32(duration[i] * rows[i][AS_PROSODY_DUR]) and then, with
+ *   as_forward_io.prosody set too, v = fp32(v * prosody[b][AS_PROSODY_DUR]); `duration` stays the unscaled predictor output, dur_i,
+ *   frame_off and everything behind them follow the controlled counts (known frames: batch->frames must be their sums).  A pause is a
+ *   scale on a space or punctuation token.
+ *   Tracks: token k of an utterance covers the full-rate columns [S_k, S_k + 2 d_k) (S_k = twice the frames before it) and has its centre at
+ *   S_k + d_k; column j has the midpoint j + 0.5.  smooth 0: a token's gains / offsets hold over its columns.  smooth 1: they are control
+ *   points at the tokens' centres, joined linearly inside an utterance (never across utterances), constant before the first and after the
+ *   last centre: between the centres c_k < j + 0.5 < c_{k+1}, w = fp32((j + 0.5 - c_k) / (c_{k+1} - c_k)) and q(j) = fmaf(w, q_{k+1} - q_k,
+ *   q_k) for each of the 24 parameters q.  Every track value x of the column (after the utterance's own gain and offset, if any) becomes
+ *   fmaf(gain(j), x, offset(j)) before the decoder or the F0 / N / EMA outputs read it.  Filler columns of a capacity layout are not touched.
+ *   Identity rows {1, 1 x 12, 0 x 12} give the results of a plan without controls bit for bit, in either mode (a -0 track value may come
+ *   back as +0).
+ * The struct is copied; tp NULL = off (the default): a forward then issues exactly the launches it issued before this entry point existed.
+ * With controls set a forward adds three small launches (csrc/token_prosody.hip) and two small buffers, which both halves keep in
+ * workspace A (workspace B is laid out as without controls): set them BEFORE asking as_module_workspace_bytes (AS_MOD_FORWARD_A /
+ * _A_VOICE / _B / _B_CAP then count a call with controls), like as_plan_set_serial, and do not change them between
+ * as_forward_test_begin and _finish.  Works with known frames, the read-back, frame_cap (no synchronisation, no host read, no
+ * allocation: capturable), voice mode and together with as_forward_io.prosody.  AS_EINVAL: p NULL, rows NULL, ld < AS_PROSODY_DIM, smooth
+ * not 0 or 1; and from as_forward_test / _begin / _finish on a plan with controls set when io->forced_dur (forced durations would ignore the
+ * scales) or io->segs is given -- before anything is launched.  as_lanes never sets them on its plans. */
+typedef struct as_token_prosody { const float* rows; int32_t ld; int32_t smooth; } as_token_prosody;
+int as_plan_set_token_prosody(as_plan* p, const as_token_prosody* tp);   /* copied; NULL = off (the default) */
 int as_plan_phase_ms(as_plan* p, float* ms, int n);
 /* The plan caches the device tables of every batch geometry it has seen (key: the whole length vector).  Above max_layouts entries
  * (default 4096, minimum 64) the next entry point first waits for the streams THIS plan has launched on (not for the device: other plans'
@@ -778,7 +804,8 @@ typedef struct as_forward_io {
      * batch->frames must be their sums), and every track value x of its frames becomes fmaf(gain, x, offset) before the decoder or the
      * F0 / N / EMA outputs read it.  The identity row {1, 1 x 12, 0 x 12} gives the results of prosody == NULL bit for bit (a -0 track
      * value may come back as +0).  AS_EINVAL for ld_prosody < AS_PROSODY_DIM and together with forced_dur.  Works with known frames, the
-     * read-back, frame_cap, as_forward_test_begin / _finish, voice mode and merged calls; it adds no launch. */
+     * read-back, frame_cap, as_forward_test_begin / _finish, voice mode and merged calls; it adds no launch.
+     * Control INSIDE an utterance -- one such row per token -- is state of the plan: as_plan_set_token_prosody (above); the two compose. */
     const float* prosody; int32_t ld_prosody;
 } as_forward_io;
 #define AS_PROSODY_DIM 25
