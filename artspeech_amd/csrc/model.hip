@@ -365,6 +365,7 @@ struct Ctx : PassCtx {
     std::shared_ptr<Sched> sched; // launches are being recorded (inside a Fork of a serial, merging plan)
     int cur_q = -1;
     double hint_f = 0, hint_b = 0;
+    bool records() const { return p.serial && p.merge; }    // this plan records the branches of its Forks (decided by its flags alone)
     bool deferring() const { return sched != nullptr && cur_q >= 0; }
     Op& push(Kind kind)
     {
@@ -586,7 +587,7 @@ struct Fork {
     std::vector<int> qs;
     Fork(Ctx& c_, int n_, int first_) : c(c_), main(c_.s), n(n_), first(first_), on_side(c_.go() && !c_.p.serial)
     {
-        defer = c.go() && c.p.serial && c.p.merge;
+        defer = c.go() && c.records();
         if (defer) {
             if (!c.sched) {
                 c.sched = std::make_shared<Sched>();
@@ -743,7 +744,7 @@ void conv_impl(Ctx& c, const GemmW* w, const float* X, int ldx, const uint16_t* 
     // A plan that records its branches (serial + merge): every conv should be able to share a launch, so fp32 activations are split into
     // their operand image by a launch of their own first (what as_conv_gemm_f32 would do inside the call), and the workspace holds the K
     // slices a merged launch may cut the problem into.  Decided by the PLAN's flags, the same in every pass.
-    const bool rec = c.p.serial && c.p.merge;
+    const bool rec = c.records();
     bool in_image = o.in_image;
     if (rec && !in_image && !(K == 1 && w->w32)) {
         uint16_t* img = c.image(K, lay->N);
@@ -1417,6 +1418,16 @@ StyleIn style_inputs(Ctx& c, const float* feat12, int ldf, const float* mel, int
     return s;
 }
 
+// how every sequence on a reference opens: the twelve feature rows feat12 [12][ldf] (energy, F0, ten TV rows) and the towers' inputs cut from them
+StyleIn ref_style_inputs(Ctx& c, const float* mel, int ldm, const float* f0_raw, const float* ema_raw, int lde, float* feat12, int ldf,
+                         const Lay* ref)
+{
+    const float* stats = c.m.vec("__stats24");
+    const int n_mels = c.m.cfg.n_mels;
+    RUN(c, as_ref_features_f32(mel, ldm, n_mels, f0_raw, ema_raw, lde, ref->N, stats, feat12, ldf, c.s));
+    return style_inputs(c, feat12, ldf, mel, ldm, ref);
+}
+
 // one of the four towers of StyleEncoder.style_extractor (models.py:417-424) -> its slice of Style [B][lds] (lds 0: 2 * style_dim)
 void style_tower(Ctx& c, int which, const StyleIn& s, float* style, int lds = 0)
 {
@@ -1661,6 +1672,20 @@ void copy_rows(Ctx& c, float* dst, int ldd, const float* src, int lds, int rows,
         c.fail((int)hipErrorUnknown);
 }
 
+// the twelve track rows fne [12][N2] (F0, N, ten EMA rows) to the caller's three arrays [..][ldp] or from them; a NULL array is left out
+enum class Tracks { ToCaller, FromCaller };
+void track_rows(Ctx& c, Tracks dir, float* fne, int N2, const float* F0, const float* N, const float* EMA, int ldp)
+{
+    const float* theirs[3] = {F0, N, EMA};
+    const int row0[3] = {0, 1, 2}, rows[3] = {1, 1, 10};
+    for (int i = 0; i < 3; ++i) {
+        float* ours = fne + (size_t)row0[i] * N2;
+        if (!theirs[i]) continue;
+        if (dir == Tracks::FromCaller) copy_rows(c, ours, N2, theirs[i], ldp, rows[i], N2);
+        else copy_rows(c, const_cast<float*>(theirs[i]), ldp, ours, N2, rows[i], N2);      // (ToCaller: the arrays are the caller's outputs)
+    }
+}
+
 // Decoder.forward (models.py:497-517).  x0 [C + 128][N2]: rows 0..C-1 already hold the up-sampled text encoding (models.py:500);
 // fne [12][ldp] = F0, N, EMA; mel [n_mels][ldo].
 // One concat buffer: the decode blocks write their fp32 result over the rows they were computed from, so cat([x, asr_res, F0, N, EMA])
@@ -1812,82 +1837,101 @@ void durations_launch(Ctx& c, const as_token_prosody& tp, float* dur_s, const fl
     RUN(c, as_durations_prosody_launch(dur_s, nullptr, tok_off, B, nullptr, 0, dur_i, frame_off, tof, max_frames, c.s));
 }
 
-PhaseA forward_a_full(Ctx& c, const as_batch* batch, const as_forward_io* io)
+// Which branch of the first half's Fork carries what.  The articulatory + text + duration encoders (one triple-width encoder) run on the
+// calling stream; the towers, the duration predictor and the AdaIN fc GEMM are independent of them and of each other (models.py:358-360)
+// and individually too small to fill 256 CUs, so they run beside them.  A side-stream plan puts branch i on side stream i (every edge is
+// calling stream <-> side stream: side-to-side edges break hipGraph instantiation); a recording plan (Ctx::records) records branch i as the
+// i-th queue the Fork opens and plays the queues out on the one stream with their ready conv GEMMs sharing launches; in a serial plan that
+// does not merge the branches simply follow each other.  The order of the calls (hence of the workspace allocations) depends on the PLAN's
+// flags only, never on the pass (count / replay / run).
+struct BranchPlan {
+    int n;                        // branches of the Fork
+    int tower[3];                 // the style towers, by style_tower's `which` (-1: they do not run)
+    int fc;                       // the AdaIN fc GEMM of the predictors and the decoder (-1: the second half opens with it)
+    int dur;                      // dur_block and, once the duration encoder (2 layers) is done, the duration predictor's tail -- beside the
+                                  // last two layers of the text / articulatory pair
+    bool dur_late;                // `dur` is the side stream of a Fork of its own, opened when the duration encoder is done: dur_block runs there
+                                  // in front of the tail (dur_block from the start on a stream of its own was slower in a graph)
+};
+// reference mode: the mel tower; the small towers (measured in round 1: 3 branches 9.35 ms, these 4 8.89 ms, 5 branches 9.76 ms per step)
+constexpr BranchPlan BRANCHES_REF = {2, {0, 1, 1}, -1, 2, true};
+// ... recorded: queues cost nothing, so every tower is its own branch and dur_block starts with the others.  Every AdaIN fc layer (75 MB of
+// weights streamed for 32 columns: bandwidth-bound) needs the Style vector only -- behind the towers it rides along with the encoders'
+// compute-bound convs instead of opening the second half alone
+constexpr BranchPlan BRANCHES_REF_REC = {5, {0, 1, 2}, 4, 3, false};
+// voice mode, every kind of plan: Style is there from the start, so the fc GEMM starts at once
+constexpr BranchPlan BRANCHES_VOICE = {2, {-1, -1, -1}, 0, 1, false};
+
+// The first half.  Reference mode computes Style and dur_style from the reference (features, towers, dur_block); voice mode
+// (as_forward_io.voices) gathers both from the caller's voice table (as_voice_forward's rows), and none of those run.  Everything else --
+// buffers, encoders, the duration predictor's tail, durations -- is the same, and so is forward_b.
+PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
 {
     const as_model& m = c.m;
     PhaseA A;
-    const int B = batch->B, n_mels = m.cfg.n_mels, sd2 = 2 * m.cfg.style_dim;
+    A.voice = io->voices != nullptr;
+    const int B = batch->B, n_mels = m.cfg.n_mels, sd2 = 2 * m.cfg.style_dim, S = m.cfg.style_dim / 4;
     A.tok = c.lay(vec_of(batch->tok_lens, B));
-    A.ref = c.lay(vec_of(batch->ref_lens, B));
-    if (!A.tok || !A.ref) return A;
-    const int Nt = std::max(A.tok->N, 1), Nr = std::max(A.ref->N, 1);
-    A.feat12 = c.f32((size_t)12 * Nr);
+    if (!A.voice) A.ref = c.lay(vec_of(batch->ref_lens, B));
+    if (!A.ok()) return A;
+    const int Nt = std::max(A.tok->N, 1);
+    if (A.ref) A.feat12 = c.f32((size_t)12 * std::max(A.ref->N, 1));
     // results the caller asked for are written where the caller wants them (no copy nodes in the graph)
     A.style = c.f32((size_t)B * sd2);
     if (io->style) A.style = io->style;
-    A.duration = nullptr;
     A.dur_i = c.i32(Nt);
     A.frame_off = c.i32(B + 1);
     if (!batch->frames) {
         if (io->dur_i) A.dur_i = io->dur_i;
         if (io->frame_off) A.frame_off = io->frame_off;
     }
-    float* ds = c.f32((size_t)B * (m.cfg.style_dim / 4));
+    float* ds = c.f32((size_t)B * S);
     const as_token_prosody tp = c.p.tok_pros;
     if (tp.rows) {
         A.dur_s = c.f32(Nt);
         A.tok_start = c.i32((size_t)Nt + 1);
     }
-    const float* stats = m.vec("__stats24");
     if (c.go()) c.p.mark(0, c.s);
-    c.hint(0, 4.0 * (n_mels + 11.0 + 12.0) * A.ref->N);
-    RUN(c, as_ref_features_f32(io->mel, io->ld_mel, n_mels, io->f0_raw, io->ema_raw, io->ld_ema, A.ref->N, stats, A.feat12, A.ref->N, c.s));
-    const StyleIn si = style_inputs(c, A.feat12, A.ref->N, io->mel, io->ld_mel, A.ref);
-    if (!si.l1) return A;
+    StyleIn si;
+    if (A.voice) {
+        RUN(c, as_voice_gather_launch(io->voices, io->ld_voice, io->n_voices, io->voice_idx, B, sd2, S, A.style, sd2, ds, S, c.s));
+    } else {
+        c.hint(0, 4.0 * (n_mels + 11.0 + 12.0) * A.ref->N);
+        si = ref_style_inputs(c, io->mel, io->ld_mel, io->f0_raw, io->ema_raw, io->ld_ema, A.feat12, A.ref->N, A.ref);
+        if (!si.l1) return A;
+    }
     if (c.go()) c.p.mark(1, c.s);
-    // The articulatory + text encoders (twins: one double-width encoder), the mel tower, the duration predictor and the three
-    // small towers are mutually independent (models.py:358-360) and individually too small to fill 256 CUs: four concurrent
-    // branches (measured in round 1: 3 branches 9.35 ms, these 4 8.89 ms, 5 branches 9.76 ms per step).
-    // Side streams: the mel tower; the small towers; the duration predictor's dur_block.  The calling stream runs the three encoders as one
-    // triple-width encoder; when the duration predictor's (2 layers) is finished the third side stream waits for it and runs the
-    // predictor's tail while the text / articulatory pair runs its last two layers.  (Every edge is calling stream <-> side stream:
-    // side-to-side edges break hipGraph instantiation.)  (dur_block from the start on a stream of its own was slower in a graph.)
-    // Serial plans that merge (as_plan_set_serial + as_plan_set_merge, the default of a serial plan): the branches are RECORDED (Fork, Op)
-    // and played out on the one stream with their ready conv GEMMs sharing launches -- queues cost nothing, so every tower is its own
-    // branch and dur_block starts with the others; the predictor's tail joins its queue once the duration encoder is done.  The order of
-    // the calls (hence of the workspace allocations) depends on the PLAN's flags only, never on the pass (count / prepare / run).
-    const bool rec = c.p.serial && c.p.merge;
-    Fork f(c, rec ? 5 : 2, 0);
-    f.branch(0);
-    style_tower(c, 0, si, A.style);
-    f.branch(1);
-    if (rec) {
-        style_tower(c, 1, si, A.style);
-        f.branch(2);
-        style_tower(c, 2, si, A.style);
-        f.branch(3);
-        duration_style(c, A.feat12 ? A.feat12 + (size_t)2 * A.ref->N : nullptr, A.ref->N, A.ref, ds);
-        // every AdaIN fc layer of the predictors and the decoder (75 MB of weights streamed for 32 columns: bandwidth-bound) needs the
-        // Style vector only -- here it rides along with the encoders' compute-bound convs instead of opening the second half alone
-        f.after(4, {0, 1, 2});
-        f.branch(4);
+    const BranchPlan& bp = A.voice ? BRANCHES_VOICE : (c.records() ? BRANCHES_REF_REC : BRANCHES_REF);
+    auto dur_block = [&] { duration_style(c, A.feat12 ? A.feat12 + (size_t)2 * A.ref->N : nullptr, A.ref->N, A.ref, ds); };
+    Fork f(c, bp.n, 0);
+    if (A.ref) {
+        for (int t = 0; t < 3; ++t) {
+            f.branch(bp.tower[t]);
+            style_tower(c, t, si, A.style);
+        }
+        if (!bp.dur_late) {
+            f.branch(bp.dur);
+            dur_block();
+        }
+    }
+    if (bp.fc >= 0) {
+        if (A.ref) f.after(bp.fc, {bp.tower[0], bp.tower[1], bp.tower[2]});   // (Style is what the towers write)
+        f.branch(bp.fc);
         A.fc = adain_fc_all(c, "style", style_norms(m), A.style, sd2, sd2, B);
         A.has_fc = true;
-    } else {
-        for (int t = 1; t <= 3; ++t) style_tower(c, t, si, A.style);
     }
     f.back();
     EncOut eo;
     std::unique_ptr<Fork> f2;
     rel_encoder_multi(c, path_encoders(), io->tokens, A.tok, &eo, [&](int g) {
         if (g != ENC_DUR) return;
-        if (rec) {
-            f.wait_main(3);                                              // the duration encoder's result
-            f.branch(3);
-        } else {
-            f2.reset(new Fork(c, 1, 2));
+        if (bp.dur_late) {
+            f2.reset(new Fork(c, 1, bp.dur));
             f2->branch(0);
-            duration_style(c, A.feat12 ? A.feat12 + (size_t)2 * A.ref->N : nullptr, A.ref->N, A.ref, ds);
+            dur_block();
+        } else {
+            f.wait_main(bp.dur);                                         // the duration encoder's result
+            f.branch(bp.dur);
         }
         A.duration = duration_tail(c, eo.y[ENC_DUR], ds, A.tok, io->duration);
         f.back();
@@ -1906,63 +1950,74 @@ PhaseA forward_a_full(Ctx& c, const as_batch* batch, const as_forward_io* io)
     return A;
 }
 
-// The first half in voice mode (as_forward_io.voices): Style and dur_style are gathered from the caller's voice table (as_voice_forward's
-// rows) -- the reference features, the style towers and dur_block do not run.  What is left beside the encoders: the AdaIN fc GEMM of the
-// predictors and the decoder, which needs the Style rows only and so starts at once (branch 0), and the duration predictor's tail (branch 1),
-// which joins after the duration encoder as in the full sequence.  Side-stream plans put the two branches on side streams 0 and 1 (every
-// edge calling stream <-> side stream); recording plans record them as queues.  forward_b is the same for both modes.
-PhaseA forward_a_voice(Ctx& c, const as_batch* batch, const as_forward_io* io)
+// ---- the second half's steps, in the order forward_b takes them ----
+// a merged call's segments against the batch and the half-rate capacity N1: a status, nothing launched
+int segments_status(const as_segments* segs, int B, int N1, bool wants_pred)
 {
-    const as_model& m = c.m;
-    PhaseA A;
-    A.voice = true;
-    const int B = batch->B, sd2 = 2 * m.cfg.style_dim, S = m.cfg.style_dim / 4;
-    A.tok = c.lay(vec_of(batch->tok_lens, B));
-    if (!A.tok) return A;
-    const int Nt = std::max(A.tok->N, 1);
-    A.style = c.f32((size_t)B * sd2);
-    if (io->style) A.style = io->style;
-    A.dur_i = c.i32(Nt);
-    A.frame_off = c.i32(B + 1);
-    if (!batch->frames) {
-        if (io->dur_i) A.dur_i = io->dur_i;
-        if (io->frame_off) A.frame_off = io->frame_off;
+    long sum = 0;
+    if (segs->n < 1 || segs->n > AS_MAX_SEGMENTS || segs->first[0] != 0 || segs->first[segs->n] != B) return AS_EINVAL;
+    for (int i = 0; i < segs->n; ++i) {
+        if (segs->first[i + 1] <= segs->first[i] || segs->cap[i] < 1 || !segs->mel_out[i]) return AS_EINVAL;
+        if (segs->ld_out[i] < 2 * segs->cap[i]) return AS_ENOSPC;
+        sum += segs->cap[i];
     }
-    float* ds = c.f32((size_t)B * S);
-    const as_token_prosody tp = c.p.tok_pros;
-    if (tp.rows) {
-        A.dur_s = c.f32(Nt);
-        A.tok_start = c.i32((size_t)Nt + 1);
-    }
-    if (c.go()) c.p.mark(0, c.s);
-    RUN(c, as_voice_gather_launch(io->voices, io->ld_voice, io->n_voices, io->voice_idx, B, sd2, S, A.style, sd2, ds, S, c.s));
-    if (c.go()) c.p.mark(1, c.s);
-    Fork f(c, 2, 0);
-    f.branch(0);
-    A.fc = adain_fc_all(c, "style", style_norms(m), A.style, sd2, sd2, B);
-    A.has_fc = true;
-    f.back();
-    EncOut eo;
-    rel_encoder_multi(c, path_encoders(), io->tokens, A.tok, &eo, [&](int g) {
-        if (g != ENC_DUR) return;
-        f.wait_main(1);                                                  // the duration encoder's result
-        f.branch(1);
-        A.duration = duration_tail(c, eo.y[ENC_DUR], ds, A.tok, io->duration);
-        f.back();
-    });
-    A.a_en = eo.y[ENC_ARTS];
-    A.t_en = eo.y[ENC_TEXT];
-    A.ld_en = eo.ld[ENC_ARTS];
-    f.join();
-    if (c.go()) c.p.mark(2, c.s);
-    if (!batch->frames && io->frame_cap <= 0)
-        durations_launch(c, tp, A.dur_s, A.duration, io, A.tok, A.dur_i, A.frame_off, nullptr, 0);
-    return A;
+    return sum != N1 || wants_pred ? AS_EINVAL : AS_OK;                  // (the predictions have no per-submission home)
 }
 
-PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
+// under a frame capacity: what lies where in the capacity layouts (lay1, its x2, and the batch three times at both rates), derived on the
+// device from frame_off; false: a layout could not be made
+bool dyn_geometry(Ctx& c, const as_segments* segs, const Lay* lay1, const Lay* lay2, int B, int frame_cap, int32_t* frame_off, int32_t* tof)
 {
-    return io->voices ? forward_a_voice(c, batch, io) : forward_a_full(c, batch, io);
+    const Lay *lg1 = c.dyn_lay(2, B, frame_cap), *lg2 = lg1 ? c.scaled(lg1, 2) : nullptr;
+    if (!lg1 || !lg2) return false;
+    if (!c.go()) return true;
+    const int N1 = lay1->N;
+    AsDynGeo g;
+    memset(&g, 0, sizeof(g));
+    g.frame_off = frame_off; g.B = B; g.cap1 = N1;
+    g.n_seg = segs ? segs->n : 1;
+    for (int i = 0; i < g.n_seg; ++i) {
+        g.seg_first[i] = segs ? segs->first[i] : 0;
+        g.seg_cap[i] = segs ? segs->cap[i] : N1;
+        g.seg_frame_off[i] = segs ? segs->frame_off[i] : nullptr;
+    }
+    g.seg_first[g.n_seg] = B;
+    const Lay* ls[4] = {lay1, lay2, lg1, lg2};
+    for (int i = 0; i < 4; ++i) {
+        g.w[i] = ls[i]->d_w; g.off[i] = ls[i]->d_off; g.nvalid[i] = ls[i]->d_nvalid;
+        g.meta[i] = reinterpret_cast<unsigned long long*>(ls[i]->d_meta);
+    }
+    auto t3 = lg1->tabs.find("src3");
+    g.src3 = t3 != lg1->tabs.end() ? t3->second : nullptr;
+    g.tof = tof;
+    g.status = as_status_words_device();
+    RUN(c, as_dyn_geometry_launch(g, c.s));
+    return true;
+}
+
+// the text half: T_en @ pred_aln_trg is a column gather (models.py:367-368), the text encoding at the mel rate is nearest x2 of it
+// (models.py:500) -- x0's text part -- and what the decoder can make of it before the predictors are done (decoder_pre)
+DecPre text_half(Ctx& c, const PhaseA& A, const int32_t* tof, int N1, float* x0, const Lay* lay2)
+{
+    const int C = c.m.cfg.hidden_dim, N2 = lay2->N;
+    c.hint(0, 4.0 * C * ((double)A.tok->N + N2));
+    RUN(c, as_expand_f32(A.t_en, A.ld_en, C, tof, N1, 2, x0, N2, c.s));
+    return decoder_pre(c, x0, lay2);
+}
+
+// a merged call's mel [rows][ld_src] from its packed home to the submissions' slots
+void seg_scatter(Ctx& c, const as_segments* segs, const float* src, int ld_src, int rows, const int32_t* frame_off, int B)
+{
+    if (!c.go()) return;
+    AsSegScatter sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.src = src; sc.ld_src = ld_src; sc.rows = rows; sc.n_seg = segs->n; sc.frame_off = frame_off;
+    for (int i = 0; i < segs->n; ++i) {
+        sc.seg_first[i] = segs->first[i]; sc.seg_cap[i] = segs->cap[i];
+        sc.dst[i] = segs->mel_out[i]; sc.ld_dst[i] = segs->ld_out[i];
+    }
+    sc.seg_first[segs->n] = B;
+    RUN(c, as_seg_scatter_launch(sc, c.s));
 }
 
 void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_io* io)
@@ -1978,16 +2033,10 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
     const Lay* lay2 = c.scaled(lay1, 2);
     if (!lay2) return;
     const int N1 = lay1->N, N2 = lay2->N;
-    if (segs) {
-        long sum = 0;
-        if (segs->n < 1 || segs->n > AS_MAX_SEGMENTS || segs->first[0] != 0 || segs->first[segs->n] != B) { c.fail(AS_EINVAL); return; }
-        for (int i = 0; i < segs->n; ++i) {
-            if (segs->first[i + 1] <= segs->first[i] || segs->cap[i] < 1 || !segs->mel_out[i]) { c.fail(AS_EINVAL); return; }
-            if (segs->ld_out[i] < 2 * segs->cap[i]) { c.fail(AS_ENOSPC); return; }
-            sum += segs->cap[i];
-        }
-        if (sum != N1 || io->F0) { c.fail(AS_EINVAL); return; }         // (the predictions have no per-submission home)
-    } else if (io->ld_out < N2 || (io->F0 && io->ld_pred < N2)) { c.fail(AS_ENOSPC); return; }
+    int fits = AS_OK;
+    if (segs) fits = segments_status(segs, B, N1, io->F0 != nullptr);
+    else if (io->ld_out < N2 || (io->F0 && io->ld_pred < N2)) fits = AS_ENOSPC;
+    if (fits != AS_OK) { c.fail(fits); return; }
     int32_t* tof = c.i32((size_t)std::max(N1, 1));
     int32_t* dur_i = c.i32((size_t)std::max(A.tok->N, 1));
     int32_t* frame_off = c.i32(B + 1);
@@ -2002,50 +2051,22 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
     if (io->frame_off && !segs) frame_off = io->frame_off;
     durations_launch(c, tp, dur_s, A.duration, io, A.tok, dur_i, frame_off, tof, N1);
     if (tp.rows) RUN(c, as_token_starts_launch(dur_i, ntok, tok_start, c.s));
-    if (dyn) {
-        const Lay *lg1 = c.dyn_lay(2, B, io->frame_cap), *lg2 = lg1 ? c.scaled(lg1, 2) : nullptr;
-        if (!lg1 || !lg2) return;
-        if (c.go()) {
-            AsDynGeo g;
-            memset(&g, 0, sizeof(g));
-            g.frame_off = frame_off; g.B = B; g.cap1 = N1;
-            g.n_seg = segs ? segs->n : 1;
-            for (int i = 0; i < g.n_seg; ++i) {
-                g.seg_first[i] = segs ? segs->first[i] : 0;
-                g.seg_cap[i] = segs ? segs->cap[i] : N1;
-                g.seg_frame_off[i] = segs ? segs->frame_off[i] : nullptr;
-            }
-            g.seg_first[g.n_seg] = B;
-            const Lay* ls[4] = {lay1, lay2, lg1, lg2};
-            for (int i = 0; i < 4; ++i) {
-                g.w[i] = ls[i]->d_w; g.off[i] = ls[i]->d_off; g.nvalid[i] = ls[i]->d_nvalid;
-                g.meta[i] = reinterpret_cast<unsigned long long*>(ls[i]->d_meta);
-            }
-            auto t3 = lg1->tabs.find("src3");
-            g.src3 = t3 != lg1->tabs.end() ? t3->second : nullptr;
-            g.tof = tof;
-            g.status = as_status_words_device();
-            RUN(c, as_dyn_geometry_launch(g, c.s));
-        }
-    }
+    if (dyn && !dyn_geometry(c, segs, lay1, lay2, B, io->frame_cap, frame_off, tof)) return;
     float* a_ex = c.f32((size_t)C * std::max(N1, 1));
     float* fne = c.f32((size_t)12 * std::max(N2, 1));                    // rows: F0, N, EMA[10] (what the three branches predict)
     float* x0 = c.f32((size_t)(C + 128) * std::max(N2, 1));
     // every AdaIN fc layer of the predictors and the decoder (~75 MB of weights): one GEMM on the style vectors
     const FcOut fc = A.has_fc ? A.fc : adain_fc_all(c, "style", style_norms(m), A.style, 2 * m.cfg.style_dim, 2 * m.cfg.style_dim, B);
-    // T_en @ pred_aln_trg is a column gather (models.py:367-368); the text encoding at the mel rate is nearest x2 of it (models.py:500).
-    // What the decoder can do before the predictors are done -- x0's text part, its image, asr_res -- a recording plan runs BESIDE them
-    // (one more queue: the 64-channel asr_res conv then rides in a predictor launch).
-    const bool rec = c.p.serial && c.p.merge;
+    // The text half needs nothing from the predictors: a recording plan runs it BESIDE them (one more queue: the 64-channel asr_res conv
+    // then rides in a predictor launch), every other plan behind them.
+    const bool rec = c.records();
     DecPre dp;
     {
         std::unique_ptr<Fork> f;
         if (rec) {
             f.reset(new Fork(c, 1, 0));
             f->branch(0);
-            c.hint(0, 4.0 * C * ((double)A.tok->N + N2));
-            RUN(c, as_expand_f32(A.t_en, A.ld_en, C, tof, N1, 2, x0, N2, c.s));
-            dp = decoder_pre(c, x0, lay2);
+            dp = text_half(c, A, tof, N1, x0, lay2);
             f->back();
         }
         c.hint(0, 4.0 * C * ((double)A.tok->N + N1));
@@ -2063,33 +2084,11 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
         if (f) f->join();
     }
     if (c.go()) c.p.mark(3, c.s);
-    if (!rec) {
-        c.hint(0, 4.0 * C * ((double)A.tok->N + N2));
-        RUN(c, as_expand_f32(A.t_en, A.ld_en, C, tof, N1, 2, x0, N2, c.s));
-        dp = decoder_pre(c, x0, lay2);
-    }
-    if (segs) {
-        decoder(c, dp, x0, lay2, fne, N2, fc, mel_packed, N2);
-        if (c.go()) {
-            AsSegScatter sc;
-            memset(&sc, 0, sizeof(sc));
-            sc.src = mel_packed; sc.ld_src = N2; sc.rows = n_mels; sc.n_seg = segs->n; sc.frame_off = frame_off;
-            for (int i = 0; i < segs->n; ++i) {
-                sc.seg_first[i] = segs->first[i]; sc.seg_cap[i] = segs->cap[i];
-                sc.dst[i] = segs->mel_out[i]; sc.ld_dst[i] = segs->ld_out[i];
-            }
-            sc.seg_first[segs->n] = B;
-            RUN(c, as_seg_scatter_launch(sc, c.s));
-        }
-    } else {
-        decoder(c, dp, x0, lay2, fne, N2, fc, io->mel_out, io->ld_out);
-    }
+    if (!rec) dp = text_half(c, A, tof, N1, x0, lay2);
+    decoder(c, dp, x0, lay2, fne, N2, fc, segs ? mel_packed : io->mel_out, segs ? N2 : io->ld_out);
+    if (segs) seg_scatter(c, segs, mel_packed, N2, n_mels, frame_off, B);
     if (c.go()) c.p.mark(4, c.s);
-    if (c.go()) {
-        if (io->F0) copy_rows(c, io->F0, io->ld_pred, fne, N2, 1, N2);
-        if (io->N) copy_rows(c, io->N, io->ld_pred, fne + (size_t)N2, N2, 1, N2);
-        if (io->EMA) copy_rows(c, io->EMA, io->ld_pred, fne + (size_t)2 * N2, N2, 10, N2);
-    }
+    track_rows(c, Tracks::ToCaller, fne, N2, io->F0, io->N, io->EMA, io->ld_pred);
 }
 
 void outputs_a(Ctx& c, const PhaseA& A, const as_forward_io* io)
@@ -2145,11 +2144,8 @@ int style_module(Ctx& c, const as_batch* batch, const float* mel, int ldm, const
 {
     const Lay* ref = c.lay(vec_of(batch->ref_lens, batch->B));
     if (!ref || ldm < ref->N || lde < ref->N || ldf < ref->N) return AS_EINVAL;
-    const float* stats = c.m.vec("__stats24");
-    const int n_mels = c.m.cfg.n_mels;
-    RUN(c, as_ref_features_f32(mel, ldm, n_mels, f0_raw, ema_raw, lde, ref->N, stats, feat12, ldf, c.s));
-    const StyleIn si = style_inputs(c, feat12, ldf, mel, ldm, ref);
-    if (si.l1) for (int t = 0; t < 4; ++t) style_tower(c, t, si, style);
+    const StyleIn si = ref_style_inputs(c, mel, ldm, f0_raw, ema_raw, lde, feat12, ldf, ref);
+    if (si.l1) for (int t = 0; t < 3; ++t) style_tower(c, t, si, style);
     return AS_OK;
 }
 
@@ -2159,11 +2155,9 @@ int voice_module(Ctx& c, const as_batch* batch, const float* mel, int ldm, const
 {
     const Lay* ref = c.lay(vec_of(batch->ref_lens, batch->B));
     if (!ref || ldm < ref->N || lde < ref->N || ldv < voice_dim(c.m)) return AS_EINVAL;
-    const int n_mels = c.m.cfg.n_mels, sd2 = 2 * c.m.cfg.style_dim;
+    const int sd2 = 2 * c.m.cfg.style_dim;
     float* feat12 = c.f32((size_t)12 * std::max(ref->N, 1));
-    const float* stats = c.m.vec("__stats24");
-    RUN(c, as_ref_features_f32(mel, ldm, n_mels, f0_raw, ema_raw, lde, ref->N, stats, feat12, ref->N, c.s));
-    const StyleIn si = style_inputs(c, feat12, ref->N, mel, ldm, ref);
+    const StyleIn si = ref_style_inputs(c, mel, ldm, f0_raw, ema_raw, lde, feat12, ref->N, ref);
     if (!si.l1) return AS_OK;
     for (int t = 0; t < 3; ++t) style_tower(c, t, si, voice, ldv);
     duration_style(c, feat12 ? feat12 + (size_t)2 * ref->N : nullptr, ref->N, ref, voice ? voice + sd2 : nullptr, ldv);
@@ -2190,9 +2184,7 @@ int arts_module(Ctx& c, const as_batch* batch, const float* a_ens, int lda, cons
     const FcOut fc = adain_fc_all(c, "style", style_norms(c.m), style, sd2, sd2, batch->B);
     float* fne = c.f32((size_t)12 * std::max(N2, 1));
     arts_predictor(c, a_ens, lda, lay, fc, fne, N2);
-    copy_rows(c, F0, ldp, fne, N2, 1, N2);
-    copy_rows(c, N, ldp, fne + (size_t)N2, N2, 1, N2);
-    copy_rows(c, EMA, ldp, fne + (size_t)2 * N2, N2, 10, N2);
+    track_rows(c, Tracks::ToCaller, fne, N2, F0, N, EMA, ldp);
     return AS_OK;
 }
 
@@ -2215,9 +2207,7 @@ int decoder_module(Ctx& c, const as_batch* batch, const float* asr, int lda, con
     float* x0 = c.f32((size_t)(C + 128) * std::max(N2, 1));
     RUN(c, as_expand_f32(asr, lda, C, ident, lay->N, 2, x0, N2, c.s));
     float* fne = c.f32((size_t)12 * std::max(N2, 1));
-    copy_rows(c, fne, N2, F0, ldp, 1, N2);
-    copy_rows(c, fne + (size_t)N2, N2, N, ldp, 1, N2);
-    copy_rows(c, fne + (size_t)2 * N2, N2, EMA, ldp, 10, N2);
+    track_rows(c, Tracks::FromCaller, fne, N2, F0, N, EMA, ldp);
     const FcOut fc = adain_fc_all(c, "style", style_norms(c.m), style, sd2, sd2, batch->B);
     decoder(c, decoder_pre(c, x0, lay2), x0, lay2, fne, N2, fc, mel, ldo);
     return AS_OK;
@@ -2254,8 +2244,13 @@ size_t count_module(const as_model* m, as_plan* p, int module, const as_batch* b
 {
     // the batch fields every module reads: tok_lens, ref_lens, frames (AS_MOD_FORWARD_B_CAP: capacities).  Workspace B is counted behind a
     // voice-mode first half when ref_lens is NULL (a voice-mode caller has no reference lengths)
-    static const bool need[10][3] = {{1, 1, 0}, {1, 0, 1}, {1, 0, 0}, {0, 1, 0}, {1, 1, 0}, {0, 0, 1}, {0, 0, 1}, {1, 0, 1}, {0, 1, 0}, {1, 0, 0}};
-    if (module < 0 || module > AS_MOD_FORWARD_A_VOICE || !batch_ok(batch, need[module][0], need[module][1], need[module][2])) return 0;
+    static const struct { int module; bool tok, ref, frames; } need[] = {
+        {AS_MOD_FORWARD_A, 1, 1, 0}, {AS_MOD_FORWARD_B, 1, 0, 1}, {AS_MOD_ENCODER, 1, 0, 0},       {AS_MOD_STYLE, 0, 1, 0},
+        {AS_MOD_DURATION, 1, 1, 0},  {AS_MOD_ARTS, 0, 0, 1},      {AS_MOD_DECODER, 0, 0, 1},       {AS_MOD_FORWARD_B_CAP, 1, 0, 1},
+        {AS_MOD_VOICE, 0, 1, 0},     {AS_MOD_FORWARD_A_VOICE, 1, 0, 0}};
+    static_assert(sizeof(need) / sizeof(need[0]) == AS_MOD_FORWARD_A_VOICE + 1, "one row per AS_MOD_* value");
+    const auto* nd = std::find_if(std::begin(need), std::end(need), [&](const auto& r) { return r.module == module; });
+    if (nd == std::end(need) || !batch_ok(batch, nd->tok, nd->ref, nd->frames)) return 0;
     Ctx c(*m, *p, nullptr, nullptr, 0, Pass::Count);
     int rc = AS_OK;
     switch (module) {

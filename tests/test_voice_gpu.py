@@ -196,6 +196,56 @@ def test_frame_cap_with_voices(cuda, golden_dir):
     assert _lib.lib().as_device_status(0) == 0
 
 
+def test_voice_forward_on_every_kind_of_plan(cuda, golden_dir):
+    """voice mode on the three kinds of plan -- branches on side streams (eager, and the call captured into a graph and replayed), the
+    serial chain, the serial chain that records and merges -- on three tiny goldens as one ragged batch under a frame capacity:
+    durations = ref/pred_dur, every utterance's mel within 1e-4 of its golden"""
+    files = sorted(glob.glob(os.path.join(golden_dir, "net_tiny_*.npz")))
+    gs = [np.load(f) for f in files[:2] + files[-1:]]                   # 12, 30 and 5 tokens
+    net = get_net(64, 8, int(gs[0]["weight_seed"]), cuda)
+    table = torch.cat([voice_of(net, *raw_features(int(g["t_ref"]), int(g["seed"]))) for g in gs])
+    tok = torch.from_numpy(np.concatenate([g["tokens"] for g in gs]).astype(np.int32)).to(cuda)
+    tl = [len(g["tokens"]) for g in gs]
+    want_dur = np.concatenate([g["ref/pred_dur"] for g in gs]).astype(np.int32)
+    M = [int(g["ref/pred_dur"].sum()) for g in gs]
+    cap = sum(M) + 13
+
+    def run(n, out=None):
+        return n.forward_packed(tok, tl, None, None, None, None, frame_cap=cap, voice=table, out=out)
+
+    def check(res, what):
+        torch.cuda.synchronize()
+        off = res["frame_off"].cpu().tolist()
+        assert off == [0] + list(np.cumsum(M)), (what, off)
+        assert np.array_equal(res["dur_i"][: len(want_dur)].cpu().numpy(), want_dur), what
+        for b, g in enumerate(gs):
+            d = float(np.abs(res["mel"][:, 2 * off[b]: 2 * off[b + 1]].cpu().numpy() - g["ref/mel"]).max())
+            print(what, "utterance", b, "mel max-abs", d)
+            assert d <= MEL_TOL, (what, b, d)
+
+    plans = {"side streams": net.replica(), "serial": net.replica(), "serial, merging": net.replica()}
+    plans["serial"].rt.set_serial(True)
+    plans["serial"].rt.set_merge(False)
+    plans["serial, merging"].rt.set_serial(True)
+    for what, n in plans.items():
+        check(run(n), what)
+    n = plans["side streams"]
+    out = run(n)
+    graph, st = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    st.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(st):
+        run(n, out)
+        torch.cuda.synchronize()
+        with torch.cuda.graph(graph, stream=st):
+            run(n, out)
+    for k in ("mel", "frame_off", "dur_i"):
+        out[k].zero_()
+    torch.cuda.synchronize()
+    graph.replay()
+    check(out, "side streams, graph replay")
+    assert _lib.lib().as_device_status(0) == 0
+
+
 def test_lanes_voice_submissions(cuda):
     """coalescing lanes with voice submissions: merged, eager = graph-plan = replayed bit for bit, new device indices take effect at
     replay, a voice submission behind a reference one is not merged, and host submissions equal device ones"""
