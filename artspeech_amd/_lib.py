@@ -266,6 +266,11 @@ _SIGNATURES.update({
     "as_vocoder_workspace_bytes": (c_sz, [c_p, c_p, c_i, _pI32]),
     "as_vocoder_forward": (c_i, [c_p, c_p, c_i, _pI32, ctypes.POINTER(VocoderIO), c_p, c_sz, c_p]),
     "as_vocoder_fold_upsample_host": (c_i, [c_p, c_i, c_i, c_i, c_p]),
+    "as_resample_design_host": (c_i, [c_i, c_i, _pI32, _pI32, _pI32, c_p, c_i]),
+    "as_resampler_create": (c_i, [c_i, c_i, ctypes.POINTER(c_p)]),
+    "as_resampler_destroy": (c_i, [c_p]),
+    "as_resampler_info": (c_i, [c_p, _pI32, _pI32, _pI32]),
+    "as_resample_f32": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
 })
 
 

@@ -5,7 +5,9 @@ stage on the HIP path (log-mel front end, JDCNet, EMA_Predictor, acoustic model,
         --jdc Utils/JDC/bst.t7 --ema Utils/EMA/200000.pth.tar --vocoder-config Vocoder/config.json --vocoder Vocoder/g_00935000
 
 What test.py does and this does not: espeak phonemisation (pass the phoneme string the phonemizer prints, test.py:95), and
-librosa's load / trim / resample (the wave must already be 24 kHz mono PCM; it is read with the standard library).
+librosa's load / trim (the wave is mono PCM, read with the standard library).  The reference wave may have any rate the library's
+resampler takes (include/artspeech_hip.h, as_resample_f32: 8 to 48 kHz and more): it is brought to the model's 24 kHz on the device, and
+``--out-rate HZ`` writes the synthesised wave at another rate than 24 kHz, resampled on the device as well.
 ``--synthetic`` replaces every checkpoint by the seeded synthetic weights the tests use (the reference ships no weights).
 
 One voice, many sentences: ``--save-voice voice.npz`` (with ``--ref-wav``) also writes the voice computed from the reference, and
@@ -27,6 +29,15 @@ import torch
 
 
 def read_wav(path):
+    """a 24 kHz wave's samples (any other rate: ValueError; read_wav_any returns the rate instead)"""
+    x, sr = read_wav_any(path)
+    if sr != 24000:
+        raise ValueError(f"{path}: {sr} Hz; resample to 24000 Hz first (test.py:105-106 uses librosa for that)")
+    return x
+
+
+def read_wav_any(path):
+    """-> (samples fp32 in [-1, 1), rate): 16- or 32-bit PCM of any rate, first channel (main resamples what is not 24 kHz on the device)"""
     with wave.open(path, "rb") as f:
         n, ch, sw, sr = f.getnframes(), f.getnchannels(), f.getsampwidth(), f.getframerate()
         raw = f.readframes(n)
@@ -35,9 +46,7 @@ def read_wav(path):
     x = np.frombuffer(raw, dtype=np.int16 if sw == 2 else np.int32).astype(np.float32) / float(2 ** (8 * sw - 1))
     if ch > 1:
         x = x.reshape(-1, ch)[:, 0]                                   # test.py:101-102 keeps the first channel
-    if sr != 24000:
-        raise ValueError(f"{path}: {sr} Hz; resample to 24000 Hz first (test.py:105-106 uses librosa for that)")
-    return x
+    return x, int(sr)
 
 
 def write_wav(path, x, sr=24000):
@@ -57,7 +66,7 @@ def build_parser():
     ap.add_argument("--config", help="Configs/config.yaml of the reference (model_params, stats_path, pretrained_model)")
     ap.add_argument("--phonemes", required=True, help="the phoneme string espeak produces for the text (test.py:94-95)")
     ref = ap.add_mutually_exclusive_group(required=True)
-    ref.add_argument("--ref-wav", help="reference utterance, 24 kHz mono PCM wav")
+    ref.add_argument("--ref-wav", help="reference utterance, mono PCM wav (another rate than 24 kHz is resampled on the device)")
     ref.add_argument("--voice", help="a voice saved with --save-voice (in place of --ref-wav)")
     ap.add_argument("--save-voice", metavar="PATH", help="with --ref-wav: also write the voice computed from it (.npz)")
     ap.add_argument("--speed", type=float, default=1.0, help="speaking rate: 2 = twice as fast (durations halved), in (0, 16]")
@@ -68,6 +77,8 @@ def build_parser():
                          "(default 0); repeatable, a later span replaces an earlier one where they overlap")
     ap.add_argument("--smooth-prosody", action="store_true", help="with --emphasis: glide linearly between the tokens' settings (centre to centre)")
     ap.add_argument("--out", default="output.wav")
+    ap.add_argument("--out-rate", type=int, default=24000, metavar="HZ", help="sample rate of --out (default 24000: the generator's own); "
+                    "another rate is resampled on the device (as_resample_f32), with --pcm16 straight to 16-bit samples")
     ap.add_argument("--jdc", help="Utils/JDC/bst.t7")
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
     ap.add_argument("--vocoder-config", help="Vocoder/config.json")
@@ -86,6 +97,8 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.save_voice and not a.ref_wav:
         ap.error("--save-voice needs --ref-wav (the voice is computed from it)")
+    if a.out_rate < 1:
+        ap.error("--out-rate takes a positive sample rate")
     if a.frame_cap is not None:
         if a.frame_cap < 1:
             ap.error("--frame-cap takes a positive number of frames")
@@ -161,15 +174,17 @@ def main(argv=None):
         ap.error(f"--emphasis: {e}")
     if a.voice:
         from .pipeline import Voice
-        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, **tok)
+        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
+                                  sample_rate=a.out_rate, **tok)
     else:
-        wave_in = read_wav(a.ref_wav)
+        wave_in, ref_rate = read_wav_any(a.ref_wav)
         if a.save_voice:
-            tts.voice_from_wave(wave_in).save(a.save_voice)
+            tts.voice_from_wave(wave_in, rate=ref_rate).save(a.save_voice)
             print(f"{a.save_voice}: voice of {a.ref_wav}")
-        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, **tok)
-    write_wav(a.out, audio.cpu().numpy())
-    print(f"{a.out}: {audio.numel() / 24000.0:.2f} s of audio from {tts._last_frames[0]} mel frames")
+        audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, ref_rate=ref_rate,
+                                        sample_rate=a.out_rate, **tok)
+    write_wav(a.out, audio.cpu().numpy(), sr=a.out_rate)
+    print(f"{a.out}: {audio.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {tts._last_frames[0]} mel frames")
     return 0
 
 

@@ -146,6 +146,13 @@ static __device__ __forceinline__ void as_status_raise(unsigned* words, int kind
 {
     if (words) __hip_atomic_store(words + kind, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+// the waveform as 16-bit PCM (include/artspeech_hip.h, as_conv_post_pcm_f32; vocoder.hip, resample.hip): one fp32 multiply, round half to even, saturate; a NaN gives 0
+// (*nan says so: the caller raises AS_STATUS_F16_RANGE)
+static __device__ __forceinline__ int as_pcm16(float w, bool* nan)
+{
+    *nan = w != w;
+    return *nan ? 0 : (int)fmaxf(-32768.f, fminf(32767.f, rintf(__fmul_rn(32767.f, w))));
+}
 // AdaIN1d value and the fused depthwise ConvTranspose1d(k3, s2, p1, op1) pair, written with explicit roundings so that every
 // kernel that evaluates them (adain_kernel: fp32 output; adain_image_kernel: operand image) produces the same bits whatever
 // the compiler would contract.

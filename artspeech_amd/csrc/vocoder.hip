@@ -72,14 +72,6 @@ extern "C" int as_mean3_f32(const float* a, const float* b, const float* c, int 
     return as_mean3_cap_f32(a, b, c, ld, C, N, nullptr, y, ldy, stream);
 }
 
-// the waveform as 16-bit PCM (include/artspeech_hip.h, as_conv_post_pcm_f32): one fp32 multiply, round half to even, saturate; a NaN gives 0
-// (*nan says so: the caller raises AS_STATUS_F16_RANGE)
-static __device__ __forceinline__ int as_pcm16(float w, bool* nan)
-{
-    *nan = w != w;
-    return *nan ? 0 : (int)fmaxf(-32768.f, fminf(32767.f, rintf(__fmul_rn(32767.f, w))));
-}
-
 // conv_post (vocoder.py:97, 111-113): wav = tanh(conv1d(LeakyReLU(x, 0.01), w [1][C][k]) + b), zero padding per utterance.  ONE output row:
 // as a conv GEMM launch this was a 32-row matrix-core tile computing one useful row behind a split pass over the whole input (336 us at
 // 32 channels x 1.92 M samples); as plain fp32 FMAs it is a read of x (245 MB).  A wave owns 256 consecutive columns, a lane the columns

@@ -26,6 +26,8 @@ from . import models
 from .text import TextCleaner
 from .weights import DEFAULT_STATS, load_distribution
 
+SAMPLE_RATE = 24000             # of the log-mel front end and of the generator (test.py:105-106, Vocoder/config.json)
+
 
 class Voice:
     """A speaker's voice for one model: vector fp32 [2 * style_dim + style_dim / 4] (Style, then dur_style), the model's style_dim and
@@ -250,11 +252,23 @@ class ArtSpeech:
         return Voice(v[0].cpu(), net.rt.cfg.style_dim, net.rt.fingerprint)
 
     @torch.no_grad()
-    def voice_from_wave(self, ref_wave):
-        """The Voice of a reference wave (24 kHz, already loaded / trimmed): the log-mel front end, the attached extractors, the voice"""
+    def voice_from_wave(self, ref_wave, rate=24000):
+        """The Voice of a reference wave (already loaded / trimmed; `rate` Hz: another rate than 24000 is resampled on the device,
+        resample.Resampler): the log-mel front end, the attached extractors, the voice"""
         if getattr(self, "frontend", None) is None:
             self.attach_frontend()
-        return self.voice_from_mel(self.frontend(ref_wave)[0])
+        return self.voice_from_mel(self.frontend(self._ref_at_24k(ref_wave, rate))[0])
+
+    def _ref_at_24k(self, ref_wave, rate):
+        """a reference wave, or a list of them, of `rate` Hz -> at the front end's 24 kHz (as it came when that is its rate)"""
+        from .resample import resampler
+        rs = resampler(rate, SAMPLE_RATE, self.device)
+        return ref_wave if rs is None else rs(ref_wave)
+
+    def _out_resampler(self, sample_rate):
+        """the Resampler behind the generator for synthesis_*'s sample_rate, or None (None / 24000: the generator's own samples)"""
+        from .resample import resampler
+        return resampler(SAMPLE_RATE, sample_rate, self.device)
 
     def _voice_table(self, voice, B):
         """one Voice (every utterance) or a list of B -> (device table [V, voice_dim], indices [B]); each voice checked against the model"""
@@ -277,12 +291,15 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
-                            token_prosody=None, token_smooth=False):
-        """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed, 24 kHz) reference wave on: log-mel front
-        end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator.  Returns the samples (mel frames if no vocoder is attached).
-        Loading / trimming / resampling the file (librosa, test.py:99-106) and espeak stay with the caller."""
+                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None):
+        """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
+        end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
+        attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
+        device, with the library's own filter); sample_rate: the rate of the returned samples (synthesis_wav).  Loading / trimming the
+        file and espeak stay with the caller."""
         if getattr(self, "frontend", None) is None:
             self.attach_frontend()
+        ref_wave = self._ref_at_24k(ref_wave, ref_rate)
         single = isinstance(phonemes, str)
         if single:
             mels = [self.frontend(ref_wave)[0]]
@@ -298,6 +315,8 @@ class ArtSpeech:
             if self.generator is None:
                 raise RuntimeError("frame_cap runs the acoustic model and the generator as one chain: attach_vocoder(h, checkpoint, runtime=True) first")
             kw["frame_cap"] = frame_cap
+        if sample_rate is not None and self.generator is not None:
+            kw["sample_rate"] = sample_rate
         out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody, token_prosody=token_prosody,
                  token_smooth=token_smooth, **kw)
         return out[0] if single and out.dim() > 1 and self.generator is not None else out
@@ -314,27 +333,52 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
-                      frame_cap=None, token_prosody=None, token_smooth=False):
+                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the generator's last kernel.
         frame_cap=N (predicted durations, a runtime vocoder): room for N half-rate frames, all utterances together -- the acoustic model
         (forward_packed(frame_cap=N)) hands its device frame_off and mel straight to the generator (forward_packed_cap) on the same
         stream: no host value is read between the tokens and the samples, then ONE copy brings the sample offsets and the samples back.
-        More frames than room: HipLibraryError (AS_STATUS_CAPACITY)."""
+        More frames than room: HipLibraryError (AS_STATUS_CAPACITY).
+        sample_rate (None or 24000: the generator's own samples, exactly the calls above): the samples at that rate -- the packed fp32
+        samples go through resample.Resampler(24000, sample_rate) on the device before they are padded out or read back
+        ([B, max ceil(300 frames L / M)]); with pcm16 the generator writes fp32 only and the resampler writes the 16-bit samples."""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         single = isinstance(phonemes, str)
+        rs = self._out_resampler(sample_rate)
         if frame_cap is not None:
             if forced_durations is not None:
                 raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
-            out = self._synthesis_wav_cap(phonemes, ref_mel, features, voice, prosody, pcm16, int(frame_cap), token_prosody, token_smooth)
+            out = self._synthesis_wav_cap(phonemes, ref_mel, features, voice, prosody, pcm16, int(frame_cap), token_prosody, token_smooth,
+                                          sample_rate)
             return out[0] if single else out
         mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody,
                                  token_prosody=token_prosody, token_smooth=token_smooth)
         lens = self._last_frames
+        if rs is not None:
+            wav = self._generate_resampled(mel, lens, rs, pcm16)
+            return wav[0] if single else wav
         wav = (self.generator(mel, lengths=lens, pcm16=True) if pcm16 else self.generator(mel, lengths=lens))[:, 0]
         return wav[0] if single else wav
+
+    def _generate_resampled(self, mel, lens, rs, pcm16):
+        """Generator.forward with the resampler between the generator's packed fp32 samples and the padding: mel [B, 80, T] with `lens` mel
+        frames each -> [B, max ceil(hop lens L / M)] at rs.out_rate (fp32, or int16 written by the resampler), zero beyond each utterance"""
+        from .models import pack
+        from .vocoder import layout
+        gen = self.generator
+        lens = [int(v) for v in lens]
+        with torch.cuda.device(gen.device):
+            wav, lay_w = gen.forward_packed(pack(mel.to(gen.device), lens), layout(lens, gen.device))[:2]
+            outs = [rs.out_len(n) for n in lay_w.widths_host]
+            y, p16, _ = rs.forward_packed(wav.reshape(-1)[: max(lay_w.N, 1)], lay_w.col_off, max(sum(outs), 1), pcm=pcm16, wav=not pcm16)
+            packed = p16 if pcm16 else y
+            out = torch.zeros((len(outs), max(max(outs), 1)), dtype=packed.dtype, device=packed.device)
+            for b, part in enumerate(torch.split(packed[: sum(outs)], outs)):
+                out[b, : part.numel()] = part
+            return out
 
     def _padded_batch(self, phonemes, ref_mel, features):
         """One utterance or lists of B -> (text [B, max N] token ids (test.py:96-97), tok_lens, mels [B, n_mels, max T], ref_lens,
@@ -394,12 +438,13 @@ class ArtSpeech:
             kw["mel_p"], kw["f0_p"], kw["ema_p"] = models.pack_reference(mels, f0_raw, ema_raw, ml, dev)
         return kw
 
-    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None):
+    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None):
         """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
         then the capacity vocoder on its frame_off and mel.  `inputs` = packed_inputs(...).  Every call with the same inputs dict reuses
         the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
         with other token / voice / prosody contents of the same geometry.  -> (samples [300 * 2 frame_cap], sample_off [B + 1]), both on the
-        device."""
+        device.  sample_rate (other than None / 24000): the generator writes fp32 and resample.Resampler(24000, sample_rate) runs on its
+        device sample_off on the same stream -> (samples [ceil(600 frame_cap L / M) + B], out_off [B + 1]); still no host value, still capturable."""
         if self.generator is None or not self.generator.runtime:
             raise RuntimeError("frame_cap needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
         net = self.model.ArtsSpeech
@@ -407,13 +452,20 @@ class ArtSpeech:
         with torch.cuda.device(self.device):
             res = net.forward_packed(kw.pop("tok"), kw.pop("tok_lens"), kw.pop("mel_p"), kw.pop("f0_p"), kw.pop("ema_p"), kw.pop("ref_lens"),
                                      frame_cap=frame_cap, out=inputs.setdefault("_out", {}), **kw)
+            rs = self._out_resampler(sample_rate)
+            if rs is not None:
+                wav, sample_off = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len)
+                B = sample_off.numel() - 1
+                y, p16, out_off = rs.forward_packed(wav[0], sample_off, rs.out_len(wav.shape[1]) + B, pcm=pcm16, wav=not pcm16)
+                return (p16 if pcm16 else y), out_off
             got = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len, pcm=pcm16, wav=not pcm16)
         return (got[2] if pcm16 else got[0][0]), got[1]
 
-    def _synthesis_wav_cap(self, phonemes, ref_mel, features, voice, prosody, pcm16, frame_cap, token_prosody=None, token_smooth=False):
+    def _synthesis_wav_cap(self, phonemes, ref_mel, features, voice, prosody, pcm16, frame_cap, token_prosody=None, token_smooth=False,
+                           sample_rate=None):
         from . import _lib
         inputs = self.packed_inputs(phonemes, ref_mel, features, voice, prosody, token_prosody, token_smooth)
-        samples, sample_off = self.chain_cap(inputs, frame_cap, pcm16=pcm16)
+        samples, sample_off = self.chain_cap(inputs, frame_cap, pcm16=pcm16, sample_rate=sample_rate)
         with torch.cuda.device(self.device):
             off = sample_off.cpu().tolist()                                 # the one synchronisation: offsets, then the samples
             if _lib.lib().as_device_status(0):
@@ -422,7 +474,9 @@ class ArtSpeech:
             host = samples[: off[-1]].cpu()
         hop = self.generator.hop
         lens = [off[b + 1] - off[b] for b in range(len(off) - 1)]
-        self._last_frames = [n // hop for n in lens]
+        rs = self._out_resampler(sample_rate)
+        # (mel frames, whatever the sample rate: n = ceil(hop f L / M) samples came from f = ceil(n M / L) // hop frames)
+        self._last_frames = [n // hop for n in lens] if rs is None else [-((-n * rs.M) // rs.L) // hop for n in lens]
         out = torch.zeros(len(lens), max(max(lens), 1), dtype=host.dtype)
         for b, n in enumerate(lens):
             out[b, :n] = host[off[b]: off[b + 1]]

@@ -895,6 +895,42 @@ int as_vocoder_forward_cap(const as_vocoder* v, as_plan* p, int B, const as_voco
  * phase r reads tap kk = (r + p) % u + u j of wt at d = (r + p) / u - j + 1, j = 0, 1; the third entry of a row is zero. */
 int as_vocoder_fold_upsample_host(const float* wt, int Cin, int Cout, int u, float* wc);
 
+/* ---- sample-rate conversion (csrc/resample.hip; the rule: csrc/resample_rule.h) ---------------------------------
+ * A polyphase windowed-sinc resampler over packed utterances: the reference wave at any rate in front of the mel front end, the
+ * generator's 24 kHz samples at any rate behind it, without a host step.
+ * The rule.  g = gcd(in_rate, out_rate), L = out_rate / g, M = in_rate / g, q = max(L, M).  Prototype filter at the rate in_rate * L, half
+ * length H = 32 q: h[i] = fc sinc(fc i) kaiser(i) for i in [-H, H], fc = 0.915 / q, sinc(x) = sin(pi x) / (pi x), kaiser(i) =
+ * I0(8.6 sqrt(1 - (i / H)^2)) / I0(8.6), scaled so that sum h = L; computed in double, rounded once to fp32.  An utterance of n_in samples
+ * gives n_out = ceil(n_in L / M) samples,
+ *     y[n] = sum_k h[n M - k L] x[k]     over 0 <= k < n_in with |n M - k L| <= H,
+ * accumulated in fp32: an utterance sees zeros beyond its own ends, never a neighbour's samples, and an utterance in a batch equals the
+ * same utterance alone bit for bit.
+ * Limits (AS_EINVAL): a rate < 1, in_rate == out_rate, q > 640, M / L > 8 or L / M > 8.  Every pair among 8000, 11025, 12000, 16000,
+ * 22050, 24000, 32000, 44100 and 48000 Hz is inside them but 11025 <-> 32000 (1280 / 441).
+ * as_resample_design_host   no GPU work: L, M, H (each pointer may be NULL) and, taps != NULL, the prototype h[-H .. H] as fp32
+ *                           taps[0 .. 2 H] (AS_EINVAL if n_taps < 2 H + 1); taps == NULL: sizes only.
+ * as_resampler_create       designs the filter and uploads its phase table to the current HIP device (allocates, synchronises).  The
+ *                           handle is immutable: any number of calls, streams and threads may share it.
+ * as_resample_f32           in_off DEVICE int32 [B + 1], in_off[0] = 0: utterance b is x[in_off[b] .. in_off[b + 1]) (an
+ *                           as_vocoder_cap.sample_off, or prefix sums of known lengths); x DEVICE [in_cap].  Outputs, each out_cap
+ *                           samples, packed from 0: y fp32 and / or pcm 16-bit (as_conv_post_pcm_f32's rule applied to the fp32 value in
+ *                           the same pass: a NaN stores 0 and raises AS_STATUS_F16_RANGE), at least one of the two; out_off (optional,
+ *                           DEVICE [B + 1]) = the prefix sums of ceil(len_b L / M).  The lengths exist on the device only: ONE launch, sized
+ *                           by out_cap, derives the layout and resamples.  Nothing is read back, uploaded or allocated and no call
+ *                           synchronises: every call, the first included, can be captured into a hipGraph and replayed with other
+ *                           offsets and samples.  y / pcm in [out_off[B], out_cap) are written as 0.  More output than out_cap, or
+ *                           in_off[B] > in_cap: AS_STATUS_CAPACITY -- the layout is cut at the capacities, nothing is read or stored out
+ *                           of bounds, and that call's samples are not to be used.
+ *                           AS_EINVAL before anything is launched: r, in_off or x NULL, both outputs NULL, B < 1, in_cap < 1, out_cap < 1,
+ *                           in_cap * L >= 2^31 or out_cap * M >= 2^31; AS_EDEVICE while a status bit is set. */
+typedef struct as_resampler as_resampler;
+int as_resample_design_host(int in_rate, int out_rate, int32_t* L, int32_t* M, int32_t* H, float* taps, int n_taps);
+int as_resampler_create(int in_rate, int out_rate, as_resampler** out);
+int as_resampler_destroy(as_resampler* r);
+int as_resampler_info(const as_resampler* r, int32_t* L, int32_t* M, int32_t* H);
+int as_resample_f32(const as_resampler* r, int B, const int32_t* in_off, int in_cap, const float* x, int out_cap, float* y, int16_t* pcm,
+                    int32_t* out_off, as_stream_t stream);
+
 /* ---- batches in flight (csrc/lanes.hip; DESIGN.md section 5: the throughput arrangement) -----------------------------------------------
  * as_lanes = n lanes on ONE model: per lane a HIP stream of its own, its two workspaces (grown on demand), TWO serial plans
  * (as_plan_set_serial) -- one for eager calls, whose layout cache may be flushed at any entry point, and one that only ever sees the
