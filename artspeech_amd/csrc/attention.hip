@@ -193,8 +193,21 @@ relpos_attention_kernel(const float* __restrict__ qkv, int ld, int C, int heads,
 //                   staged in LDS in exactly that order and nothing is shuffled between the two products.
 //   The two 9-row relative-position tables are matrix-core operands too (built once per workgroup in LDS): q . Ek[r] is one more
 //   "key" block, sum_r p_r Ev[r] one more 16-deep contraction block in the <= 3 key blocks that intersect a wave's band.
+// Two forms of the one kernel.  The general one (ONE = false) is the above.  The short-sequence one (ONE = true: max_len <= 64, two
+// waves, ONE key tile) is the same arithmetic -- the same MFMAs in the same order, bit for bit -- in a footprint that lets three
+// workgroups share a CU (LDS <= 160 KB / 3, <= 256 registers), because a launch of a few hundred 40-token utterances is as long as the
+// rounds of resident workgroups it takes, each round one dependent chain: no K tile in LDS (with a single tile nothing is double
+// buffered; a lane's K fragment is a 16-byte row of the image, loaded straight into registers like Q, one 32-key block at a time),
+// only the 9 live rows of the Ek operand stored (lanes of the rows above take zeros by a select), V staged before the tables' barrier
+// (one barrier in all).
 // ---------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void attn_lds_void;
+// dynamic LDS of a workgroup: [K tiles] V tile, Ek operand, Ev^T operand (16-byte entries), Rk, Pb (floats)
+static constexpr size_t attn_image_lds_bytes(int nw, bool one)
+{
+    return (size_t)((one ? 0 : 2 * (2 * 8 * 2 * FK)) + 2 * 4 * 2 * 128 + 2 * 8 * 2 * (one ? MAXREL : 32) + 2 * 2 * 128) * 16 +
+           sizeof(float) * (nw * 32 * MAXREL + nw * 32 * 16);
+}
 struct AttnImageArgs {
     const float* qkv;            // fp32 [3C][ld]  (rows 2C.. = V)
     const uint16_t* qkv_h;       // image of the same [3C][n_total] matrix
@@ -205,19 +218,20 @@ struct AttnImageArgs {
     int ld, C, window, b_split, n_total, ldo;
 };
 
-template <int NW>
-__global__ void __launch_bounds__(NW * 64)
+template <int NW, bool ONE>
+__global__ void __launch_bounds__(NW * 64, ONE ? 2 : 1)                  // ONE: two waves a SIMD (three 2-wave workgroups a CU) = 256 registers
 relpos_attention_image_kernel(const AttnImageArgs a)
 {
     constexpr int DK = 128, KB = DK / 16, NT = NW * 64, NQ = NW * 32;
+    constexpr int ER = ONE ? MAXREL : 32;                               // rows of the Ek operand kept in LDS
     const int grp = a.ek2 ? (int)blockIdx.z / a.b_split : 0;
     const float* emb_k = a.ek1 + (ptrdiff_t)grp * (a.ek2 - a.ek1);
     const float* emb_v = a.ev1 + (ptrdiff_t)grp * (a.ev2 - a.ev1);
     extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
-    u32x4_t* Kt = reinterpret_cast<u32x4_t*>(smraw);                    // [2 buffers][p][kb][g][key 64]   (2 x 32 KB)
-    u32x4_t* Vt = Kt + 2 * (2 * KB * 2 * FK);                           // [p][c][g][d 128]                (32 KB)
-    u32x4_t* EkI = Vt + 2 * 4 * 2 * DK;                                 // [p][kb][g][32 rows r][8 d]: Ek as an A operand (rows >= nrel zero)  16 KB
-    u32x4_t* EvT = EkI + 2 * KB * 2 * 32;                               // [p][g][d 128][8 r]: Ev^T as an A operand                             8 KB
+    u32x4_t* Kt = reinterpret_cast<u32x4_t*>(smraw);                    // [2 buffers][p][kb][g][key 64]   (2 x 32 KB; ONE: none)
+    u32x4_t* Vt = Kt + (ONE ? 0 : 2 * (2 * KB * 2 * FK));               // [p][c][g][d 128]                (32 KB)
+    u32x4_t* EkI = Vt + 2 * 4 * 2 * DK;                                 // [p][kb][g][ER rows r][8 d]: Ek as an A operand (rows >= nrel zero; ONE: not stored)  16 / 4.5 KB
+    u32x4_t* EvT = EkI + 2 * KB * 2 * ER;                               // [p][g][d 128][8 r]: Ev^T as an A operand                             8 KB
     float* Rk = reinterpret_cast<float*>(EvT + 2 * 2 * DK);             // [NQ][9]    q . Ek[r] * log2(e)/sqrt(dk)
     float* Pb = Rk + NQ * MAXREL;                                       // [NQ][16]   the band's probabilities of the current block
 
@@ -240,11 +254,20 @@ relpos_attention_image_kernel(const AttnImageArgs a)
     const int ql = wave * 32 + lq, qi = q0 + ql, qw0 = q0 + wave * 32;
     const size_t qcol = (size_t)min(o0 + qi, a.n_total);
     u32x4_t Qh[KB], Ql[KB];
+    if constexpr (!ONE) {
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-        Qh[kb] = img[((size_t)(qkb0 + kb) * 4 + g) * NX + qcol];
-        Ql[kb] = img[((size_t)(qkb0 + kb) * 4 + 2 + g) * NX + qcol];
+        for (int kb = 0; kb < KB; ++kb) {
+            Qh[kb] = img[((size_t)(qkb0 + kb) * 4 + g) * NX + qcol];
+            Ql[kb] = img[((size_t)(qkb0 + kb) * 4 + 2 + g) * NX + qcol];
+        }
     }
+    // ONE: the K fragments of 32-key block sb, like Q (keys past the image's end read its zero column; keys >= N are masked below)
+    u32x4_t Kh[2][KB], Kl[2][KB];
+    auto load_k = [&](int sb, int kb) {
+        const size_t kcol = (size_t)min(o0 + sb * 32 + lq, a.n_total);
+        Kh[sb][kb] = img[((size_t)(kkb0 + kb) * 4 + g) * NX + kcol];
+        Kl[sb][kb] = img[((size_t)(kkb0 + kb) * 4 + 2 + g) * NX + kcol];
+    };
     // K tile k0 -> buffer `buf`: chunk (p, kb, g') = 64 keys x 16 bytes, contiguous in the image and in LDS
     const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.qkv_h), 0,
                                                                          (int)((unsigned)(3 * a.C / 16) * 4u * (unsigned)NX * 16u), 0x00020000);
@@ -265,19 +288,31 @@ relpos_attention_image_kernel(const AttnImageArgs a)
     constexpr int VI = DK * (FK / 4) / NT;
     float vr[VI][4];
     auto load_v = [&](int k0) {
-#pragma unroll
-        for (int it = 0; it < VI; ++it) {
+        const bool quads = o0 + k0 + FK + 3 < a.ld;                     // (workgroup-uniform) every quad of the tile stays inside its row
+        auto item = [&](int it, bool q4) {
             const int idx = tid + it * NT, kq = idx % (FK / 4), d = idx / (FK / 4), kk = k0 + kq * 4;
             const float* row = Vg + (size_t)d * a.ld;
             // loads only -- nothing here may consume a loaded value, or every item becomes its own memory round trip (measured: 16 x 460 cycles);
             // keys past the utterance are zeroed when the tile is stored
-            if (o0 + k0 + FK + 3 < a.ld) {                              // (workgroup-uniform) every quad of the tile stays inside its row
+            if (q4) {
                 const f32x4 v4 = *reinterpret_cast<const f32x4 __attribute__((aligned(4)))*>(row + kk);
                 vr[it][0] = v4[0]; vr[it][1] = v4[1]; vr[it][2] = v4[2]; vr[it][3] = v4[3];
             } else {                                                    // the batch's last columns: element loads, clamped to the utterance
 #pragma unroll
                 for (int e = 0; e < 4; ++e) vr[it][e] = row[min(kk + e, N - 1)];
             }
+        };
+        if constexpr (ONE) {                                            // one uniform branch around all the items: with one per item, every
+            if (quads) {                                                // item is three basic blocks, and within 256 registers values were
+#pragma unroll                                                          // spilled across them
+                for (int it = 0; it < VI; ++it) item(it, true);
+            } else {
+#pragma unroll
+                for (int it = 0; it < VI; ++it) item(it, false);
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < VI; ++it) item(it, quads);
         }
     };
     auto store_v = [&](int k0) {
@@ -297,18 +332,25 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             V2[(((1 * 4 + c) * 2 + gg) * DK + d) * 2 + (ig & 1)] = ll;
         }
     };
-    issue_k(0, 0);                                                      // (in flight while the tables are built)
+    if constexpr (!ONE) issue_k(0, 0);                                  // (in flight while the tables are built)
     load_v(0);
+    if constexpr (ONE) {                                                // (the same loads behind the V tile's branch: in front of it, the branch's
+#pragma unroll                                                          //  blocks waited for them -- a memory round trip of their own)
+        for (int kb = 0; kb < KB; ++kb) {
+            Qh[kb] = img[((size_t)(qkb0 + kb) * 4 + g) * NX + qcol];
+            Ql[kb] = img[((size_t)(qkb0 + kb) * 4 + 2 + g) * NX + qcol];
+        }
+    }
     // the two 9-row tables as matrix-core operands: q . Ek[r] is one more "key" block, sum_r p_r Ev[r] one more contraction block.
     // (all loads first, then the conversions: one memory round trip, shared with the K / V tile above)
     {
-        constexpr int EI = 32 * (DK / 8) / NT, VI2 = 2 * DK / NT;
+        constexpr int EI = (ER * (DK / 8) + NT - 1) / NT, VI2 = 2 * DK / NT;
         typedef f32x4 __attribute__((aligned(4))) f32x4u;
         f32x4 xe[EI][2];
         float xv[VI2][8];
 #pragma unroll
         for (int it = 0; it < EI; ++it) {
-            const int idx = tid + it * NT, r = idx & 31, dg = idx >> 5;
+            const int idx = tid + it * NT, r = ONE ? idx / (DK / 8) : idx & 31, dg = ONE ? idx % (DK / 8) : idx >> 5;
             const int rc = r < nrel ? r : 0;
             xe[it][0] = *reinterpret_cast<const f32x4u*>(emb_k + rc * DK + dg * 8);
             xe[it][1] = *reinterpret_cast<const f32x4u*>(emb_k + rc * DK + dg * 8 + 4);
@@ -321,14 +363,16 @@ relpos_attention_image_kernel(const AttnImageArgs a)
         }
 #pragma unroll
         for (int it = 0; it < EI; ++it) {
-            const int idx = tid + it * NT, r = idx & 31, dg = idx >> 5;
+            const int idx = tid + it * NT, r = ONE ? idx / (DK / 8) : idx & 31, dg = ONE ? idx % (DK / 8) : idx >> 5;
             float x[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[j] = r < nrel ? xe[it][j >> 2][j & 3] : 0.f;
             u32x4_t hh, ll;
             split2(x, hh, ll);
-            EkI[((0 * KB + (dg >> 1)) * 2 + (dg & 1)) * 32 + r] = hh;
-            EkI[((1 * KB + (dg >> 1)) * 2 + (dg & 1)) * 32 + r] = ll;
+            if (!ONE || r < nrel) {                                     // (ONE: the live rows only)
+                EkI[((0 * KB + (dg >> 1)) * 2 + (dg & 1)) * ER + r] = hh;
+                EkI[((1 * KB + (dg >> 1)) * 2 + (dg & 1)) * ER + r] = ll;
+            }
         }
 #pragma unroll
         for (int it = 0; it < VI2; ++it) {
@@ -342,7 +386,12 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             EvT[(1 * 2 + gg) * DK + d] = ll;
         }
     }
-    __syncthreads();                                                    // the tables are visible
+    if constexpr (ONE) {
+        store_v(0);
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) load_k(0, kb);                  // (in flight across the barrier and the table's products; the V tile's
+    }                                                                   //  registers are free now)
+    __syncthreads();                                                    // the tables are visible (ONE: and the V tile)
     // q . Ek[r] for the wave's 32 queries: S_rel^T = Ek . Q^T, rows r = 8 (e >> 2) + 4 g + (e & 3)
     {
         f32x16 SR;
@@ -350,8 +399,10 @@ relpos_attention_image_kernel(const AttnImageArgs a)
         for (int e = 0; e < 16; ++e) SR[e] = 0.f;
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
-            const f16x8 ah = __builtin_bit_cast(f16x8, EkI[((0 * KB + kb) * 2 + g) * 32 + lq]);
-            const f16x8 al = __builtin_bit_cast(f16x8, EkI[((1 * KB + kb) * 2 + g) * 32 + lq]);
+            const int er = ONE && lq >= nrel ? 0 : lq;                  // ONE: rows >= nrel are not in LDS, their lanes take the zeros here
+            u32x4_t eh = EkI[((0 * KB + kb) * 2 + g) * ER + er], el = EkI[((1 * KB + kb) * 2 + g) * ER + er];
+            if (ONE && lq >= nrel) eh = el = u32x4_t{0u, 0u, 0u, 0u};
+            const f16x8 ah = __builtin_bit_cast(f16x8, eh), al = __builtin_bit_cast(f16x8, el);
             SR = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, Ql[kb]), SR, 0, 0, 0);
             SR = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, __builtin_bit_cast(f16x8, Qh[kb]), SR, 0, 0, 0);
             SR = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, Qh[kb]), SR, 0, 0, 0);
@@ -361,6 +412,7 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             const int r = 8 * (e >> 2) + 4 * g + (e & 3);
             if (r < nrel) Rk[ql * MAXREL + r] = SR[e] * cs;
         }
+        if constexpr (ONE) __builtin_amdgcn_wave_barrier();             // Rk: written and read by this wave only (no workgroup barrier follows)
     }
     float m = -INFINITY, lsum = 0.f;
     f32x16 acc[4];
@@ -371,12 +423,14 @@ relpos_attention_image_kernel(const AttnImageArgs a)
 
     int buf = 0;
     for (int k0 = 0; k0 < N; k0 += FK, buf ^= 1) {
-        store_v(k0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // this wave's share of the K tile has landed
-        __syncthreads();                                                // K tile k0 (DMA) and V tile k0 are in LDS (first time: Rk too)
-        if (k0 + FK < N) {
-            issue_k(k0 + FK, buf ^ 1);
-            load_v(k0 + FK);
+        if constexpr (!ONE) {
+            store_v(k0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's share of the K tile has landed
+            __syncthreads();                                            // K tile k0 (DMA) and V tile k0 are in LDS (first time: Rk too)
+            if (k0 + FK < N) {
+                issue_k(k0 + FK, buf ^ 1);
+                load_v(k0 + FK);
+            }
         }
         const u32x4_t* Kc = Kt + (size_t)buf * (2 * KB * 2 * FK);
         f32x16 S[2];
@@ -386,11 +440,17 @@ relpos_attention_image_kernel(const AttnImageArgs a)
             for (int e = 0; e < 16; ++e) S[sb][e] = 0.f;
 #pragma unroll
             for (int kb = 0; kb < KB; ++kb) {
-                const f16x8 ah = __builtin_bit_cast(f16x8, Kc[(0 * KB * 2 + kb * 2 + g) * FK + sb * 32 + lq]);
-                const f16x8 al = __builtin_bit_cast(f16x8, Kc[(1 * KB * 2 + kb * 2 + g) * FK + sb * 32 + lq]);
+                const f16x8 ah = __builtin_bit_cast(f16x8, ONE ? Kh[sb][kb] : Kc[(0 * KB * 2 + kb * 2 + g) * FK + sb * 32 + lq]);
+                const f16x8 al = __builtin_bit_cast(f16x8, ONE ? Kl[sb][kb] : Kc[(1 * KB * 2 + kb * 2 + g) * FK + sb * 32 + lq]);
                 S[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, Ql[kb]), S[sb], 0, 0, 0);
                 S[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, __builtin_bit_cast(f16x8, Qh[kb]), S[sb], 0, 0, 0);
                 S[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, Qh[kb]), S[sb], 0, 0, 0);
+                if constexpr (ONE) {                                    // the second block's fragments take the registers the first block's
+                    if (sb == 0) {                                      // leave, eight k-blocks ahead of their use (left to the scheduler, each
+                        load_k(1, kb);                                  // pair was loaded just before its products and waited for in turn)
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
             }
         }
         bool band[2];
@@ -480,6 +540,7 @@ relpos_attention_image_kernel(const AttnImageArgs a)
                 acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, __builtin_bit_cast(f16x8, ph), acc[mb], 0, 0, 0);
             }
         }
+        if constexpr (ONE) break;                                       // the one key tile (max_len <= 64)
         __syncthreads();                                                // everybody is done with Vt and this K buffer
     }
     const float ltot = lsum + __shfl_xor(lsum, 32);
@@ -510,14 +571,15 @@ relpos_attention_image_kernel(const AttnImageArgs a)
     }
 }
 
-template <int NW>
+template <int NW, bool ONE>
 static int launch_attention_image(const AttnImageArgs& a, int heads, int B, int max_len, hipStream_t stream)
 {
     constexpr int NQ = NW * 32;
-    const size_t smem = (size_t)(2 * (2 * 8 * 2 * FK) + 2 * 4 * 2 * 128 + 2 * 8 * 2 * 32 + 2 * 2 * 128) * 16 + sizeof(float) * (NQ * MAXREL + NQ * 16);
-    AS_LDS_OPT_IN(relpos_attention_image_kernel<NW>, 160 * 1024);
+    constexpr size_t smem = attn_image_lds_bytes(NW, ONE);
+    static_assert(!ONE || 3 * smem <= 160 * 1024, "three short-sequence workgroups share a CU's LDS");
+    if constexpr (smem > 64 * 1024) AS_LDS_OPT_IN((relpos_attention_image_kernel<NW, ONE>), 160 * 1024);   // > 64 KiB of dynamic LDS needs an explicit opt-in
     AsProfScope prof__(AS_FILE_CLS, 0, 0, stream);
-    hipLaunchKernelGGL(relpos_attention_image_kernel<NW>, dim3(as_cdiv(max_len, NQ), heads, B), dim3(NW * 64), smem, stream, a);
+    hipLaunchKernelGGL((relpos_attention_image_kernel<NW, ONE>), dim3(as_cdiv(max_len, NQ), heads, B), dim3(NW * 64), smem, stream, a);
     AS_CHECK_LAUNCH();
     return AS_OK;
 }
@@ -538,8 +600,14 @@ extern "C" int as_relpos_attention_image_f32(const float* qkv, int ld, const uin
     AttnImageArgs a;
     a.qkv = qkv; a.qkv_h = qkv_h; a.ek1 = emb_rel_k; a.ev1 = emb_rel_v; a.ek2 = emb_rel_k2; a.ev2 = emb_rel_v2; a.col_off = col_off;
     a.out = out; a.out_h = out_h; a.ld = ld; a.C = C; a.window = window; a.b_split = b_split; a.n_total = n_total; a.ldo = ldo;
-    if (max_len <= 64) return launch_attention_image<2>(a, heads, B, max_len, (hipStream_t)stream);
-    return launch_attention_image<4>(a, heads, B, max_len, (hipStream_t)stream);
+    if (max_len <= FK) return launch_attention_image<2, true>(a, heads, B, max_len, (hipStream_t)stream);
+    return launch_attention_image<4, false>(a, heads, B, max_len, (hipStream_t)stream);
+}
+
+extern "C" int as_relpos_attention_image_lds_bytes(int max_len)
+{
+    if (max_len <= 0) return 0;
+    return (int)(max_len <= FK ? attn_image_lds_bytes(2, true) : attn_image_lds_bytes(4, false));
 }
 
 extern "C" int as_relpos_attention_groups_f32(const float* qkv, int ld, int C, int heads, int window, const float* emb_rel_k,

@@ -292,6 +292,9 @@ int as_relpos_attention_image_f32(const float* qkv, int ld, const uint16_t* qkv_
                                   const float* emb_rel_k, const float* emb_rel_v, const float* emb_rel_k2, const float* emb_rel_v2,
                                   int b_split, const int32_t* col_off, int B, int max_len, float* out, int ldo, uint16_t* out_h,
                                   as_stream_t stream);
+/* no GPU work: the dynamic LDS bytes of a workgroup of the launch as_relpos_attention_image_f32 makes for this max_len (0 for
+ * max_len <= 0).  max_len <= 64 takes the short-sequence form, of which three workgroups share a CU's 160 KB. */
+int as_relpos_attention_image_lds_bytes(int max_len);
 /* channel LayerNorm (eps 1e-4) (+ReLU)       RelTransformerEnc.py:272-290, :322-323 */
 int as_channel_layernorm_f32(const float* x, int ldx, int C, int N, const float* gamma, const float* beta, float eps,
                              int relu, float* y, int ldy, as_stream_t stream);
