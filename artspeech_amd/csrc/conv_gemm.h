@@ -3,6 +3,7 @@
 #pragma once
 #include "artspeech_hip.h"
 #include "common.h"
+#include "conv_gemm_rule.h"
 
 #define OOB 0xFFFFFFFFu
 #define OOBH 0x80000000u   /* epilogue: out of range for every descriptor (< 2 GiB, host-checked) even after adding an in-range offset */
@@ -14,10 +15,27 @@ int as_conv_gemm_h3_launch(const ConvGemmArgs* const* a, const int* S, int n, in
 int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, float slope, uint16_t* xh, hipStream_t stream,
                           const int32_t* n_valid = nullptr);
 
-static inline __host__ __device__ int as_kbx(int K) { return (((K + 15) >> 4) + 3) & ~3; }      // k-blocks of a split image: a multiple of 4
-// host: M output channels fill a 128-row tile well enough to use one (it is not half empty) -- the tile rules of conv_gemm.hip, and the
-// row classes by which the recorded schedule (model.hip: play) picks the convs that share a launch
-static inline bool as_fills_tall_tile(int M) { return M > 64 && (M % 128 == 0 || M % 128 > 64 || M >= 512); }
+static inline __host__ __device__ int as_kbx(int K) { return conv_gemm_rule::kbx(K); }
+// host: M output channels fill a 128-row tile well enough to use one -- the tile rules of conv_gemm_rule.h, and the row classes by which
+// the recorded schedule (model.hip: play) picks the convs that share a launch
+static inline bool as_fills_tall_tile(int M) { return conv_gemm_rule::fills_tall_tile(M); }
+
+// host: what the rule sees of `a` (n_prod / n_groups defaulted as conv_gemm_normalise does): the operands by which pointers are given
+static inline conv_gemm_rule::Shape as_conv_gemm_shape(const ConvGemmArgs& a)
+{
+    conv_gemm_rule::Shape s;
+    s.M = a.M; s.N = a.N; s.K = a.K; s.Kp = a.Kp; s.T = a.T; s.K2 = a.K2;
+    s.n_prod = a.n_prod ? a.n_prod : 3;
+    s.n_groups = a.n_groups < 1 ? 1 : a.n_groups;
+    s.group_cols = a.group_cols; s.ileave_u = a.ileave_u; s.act = a.act;
+    s.x32 = a.X != nullptr; s.xh = a.Xh != nullptr; s.y32 = a.Y != nullptr; s.yh = a.Yh != nullptr; s.w32 = a.W != nullptr;
+    s.res = a.res != nullptr; s.div_sqrt2 = a.div_sqrt2 != 0; s.transpose_out = a.transpose_out != 0;
+    s.has_ws = a.ws != nullptr; s.ws_bytes = a.ws_bytes;
+    return s;
+}
+// host: the workspace a call of this shape wants, as as_conv_gemm_workspace_bytes (set: _multi_workspace_bytes) answers -- for callers
+// that know the shape before they hold the pointers (the count pass of a plan).  (conv_gemm.hip)
+size_t as_conv_gemm_shape_workspace(const conv_gemm_rule::Shape& s, bool set);
 
 // tap offsets packed one byte per tap, (dh+8) << 4 | (dw+8) (|dh|, |dw| <= 7, checked by the host), eight taps per
 // word: the k loop then selects a tap with scalar ALU only (a scalar or scratch load inside it would stall the wave)

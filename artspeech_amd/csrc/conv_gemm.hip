@@ -1,4 +1,4 @@
-// Host side of the conv GEMM (include/artspeech_hip.h: as_conv_gemm_f32): argument checks, tile and split-K choice, the
+// Host side of the conv GEMM (include/artspeech_hip.h: as_conv_gemm_f32): argument checks, the launch plan (conv_gemm_rule.h), the
 // split of fp32 activations into the matrix-core kernel's operand image when the caller has none, the deterministic split-K
 // reduction, and the direct kernel for Cin = 1.  The matrix-core kernel itself is conv_gemm_h3.hip.
 //
@@ -557,155 +557,47 @@ extern "C" int as_set_range_probe(int on)
     return AS_OK;
 }
 
-static void tile_dims(int choice, int* bm, int* bn)
+namespace rule = conv_gemm_rule;                    // what a call runs is decided there; this file normalises, asks and launches
+static_assert(rule::DIRECT_M == DIRECT_MAX_M, "rule and direct kernel disagree");
+
+// the switches of tests and bench scripts, read per call (tests change them between calls in one process)
+static rule::Force gemm_force()
 {
-    // 22 / 21 / 12 / 11 / 14 / 2: 128x128, 128x64, 64x128, 64x64, 64x256, 32x128 (4 waves each)
-    *bm = (choice == 22 || choice == 21) ? 128 : choice == 2 ? 32 : 64;
-    *bn = choice == 14 ? 256 : (choice == 22 || choice == 12 || choice == 2) ? 128 : 64;
+    rule::Force f;
+    const char *tile = getenv("AS_GEMM_TILE"), *ksplit = getenv("AS_GEMM_KSPLIT");   // 22, 21, 12, 11, 14 / the slices wanted
+    f.tile = tile ? atoi(tile) : 0;
+    f.ksplit = ksplit ? atoi(ksplit) : 0;
+    f.no_reduce_adain = getenv("AS_NO_REDUCE_ADAIN") != nullptr;
+    f.no_reduce_ln = getenv("AS_NO_REDUCE_LN") != nullptr;
+    return f;
 }
 
-// Tile choice, fitted to sweeps on MI355X (scripts/gemm_bench.py, round 2).  The time of a launch is the time of its busiest CU:
-// a tile alone on a CU costs t1 (relative to 128x128: 128x64 / 64x128 0.78 -- they split K over wave pairs and stage more per flop --
-// 64x64 0.59), n > 1 tiles sharing a CU cost 0.71 n t1 (two co-resident workgroups cover each other's waits).  Examples the fit
-// reproduces: M512 N6400 K512 T3: 128x128 (200 tiles) 33.5 us, 128x64 (400) 37.1; M512 N3840 K512 T5: 44.8 (120 tiles) against 35.0
-// (240); M512 N1280 K512 T3: 25.6 / 17.8 / 15.2 us for 40 / 80 / 160 tiles.
-static int gemm_tile_choice(int M, int N, int n_prod, int Kp)
+size_t as_conv_gemm_shape_workspace(const rule::Shape& s, bool set)
 {
-    const char* env = getenv("AS_GEMM_TILE");           // tests/tuning only: 22, 21, 12, 11, 14
-    if (env && atoi(env) > 0) return atoi(env);
-    if (M <= 32 && n_prod == 3) return 2;                              // a 64-row tile would be half empty (HiFi-GAN's last stage: 32 channels, 1.9 M columns)
-    // <= 64 output channels over many columns (the towers' first convs, 64 x 509 440): the 64 x 128 tile splits K over wave pairs and
-    // reads six fragments per six products; 64 x 256 gives every wave a 64 x 64 block over the whole k (eight per twelve, like 128 x 128):
-    // M64 N509440 K64 T9 167 -> 139 us, N128000 41 -> 34, N63680 20.8 -> 19.7; below one round of the chip (N6400: 8.6 -> 10.8) it loses.
-    if (M <= 64 && n_prod == 3 && as_cdiv(N, 256) >= 240) return 14;
-    const bool tall = as_fills_tall_tile(M);
-    // (a 256 x 128 tile was measured and removed: faster alone, no gain inside the step -- DESIGN.md section 3.1)
-    static const int choices[4] = {22, 21, 12, 11};
-    static const double t1[4] = {1.0, 0.78, 0.78, 0.59};
-    int best = 11;
-    double best_cost = 1e30;
-    for (int c = 0; c < 4; ++c) {
-        int bm, bn;
-        tile_dims(choices[c], &bm, &bn);
-        if (bm >= 128 && !tall) continue;
-        const double tiles = (double)as_cdiv(M, bm) * as_cdiv(N, bn);
-        const double n = ceil(tiles / 256.0);
-        const double cost = t1[c] * (n > 1.0 ? 0.71 * n : 1.0);
-        if (cost < best_cost * 0.97) { best_cost = cost; best = choices[c]; }   // (ties go to the larger tile)
-    }
-    // An image of <= 32 channels may come from the 32-row tile, which leaves the upper half of the image's 64-row block unwritten (clearing
-    // it would be 245 MB per launch at the vocoder's last stage): such a K is never given to the tile whose four waves read all four
-    // k-blocks of the block (64 x 64); every other tile reads two at most, i.e. rows 0..31, which every producer writes.
-    if (Kp <= 32 && best == 11) best = 12;
-    return best;
+    return set ? rule::workspace_set(s, gemm_force()) : rule::workspace_one(s, gemm_force());
 }
+extern "C" size_t as_conv_gemm_workspace_bytes(const ConvGemmArgs* a) { return a ? as_conv_gemm_shape_workspace(as_conv_gemm_shape(*a), false) : 0; }
+// room for the K slices a problem may be cut into inside a multi-problem launch: never less than the single launch wants
+extern "C" size_t as_conv_gemm_multi_workspace_bytes(const ConvGemmArgs* a) { return a ? as_conv_gemm_shape_workspace(as_conv_gemm_shape(*a), true) : 0; }
 
-// K slices: only where even the smallest tiles leave most CUs idle (the towers' last convs: a few hundred columns, K = 12800).
-// Everywhere else one launch without the reduce pass is as fast or faster (M1024 N2560 K512 T9: 94 us unsplit, 100 + 17 in four
-// slices; M512 N1280 K512 T3: 16 against 31).
-static int gemm_ksplit(int M, int N, int Kp, int T, int choice, int K2 = 0)
-{
-    const char* env = getenv("AS_GEMM_KSPLIT");          // tuning/experiments only
-    int bm, bn;
-    tile_dims(choice, &bm, &bn);
-    const long tiles = (long)as_cdiv(M, bm) * as_cdiv(N, bn);
-    const int wk = choice == 2 ? 2 : bm * bn >= 4 * 64 * 64 ? 1 : 4 * 64 * 64 / (bm * bn);   // waves that split K inside the workgroup
-    const int nkt = T * as_cdiv(Kp / 16, wk) + as_cdiv(as_cdiv(K2, 16), wk);   // iterations (k-tile = 16 * WK)
-    int s = 1;
-    if (env && atoi(env) > 0) s = atoi(env);
-    else if (tiles < 64) {
-        s = as_cdiv(192, tiles);
-        if (s > 16) s = 16;
-    } else if (tiles <= 128 && nkt * wk >= 64) {
-        // 64 .. 128 workgroups, each alone on its CU: the k loop runs at the latency of its own staging (3 stages in flight per workgroup:
-        // M1024 N286 K512 T9 at batch 1, 80 tiles: 49 us = 0.4 TB/s of weights), so K slices that fill the 512 workgroup slots pay even
-        // with the reduction pass behind them
-        s = 512 / (int)tiles;
-    }
-    const int min_kt = 24 / wk;                           // a slice keeps >= 384 k
-    if (s > nkt / min_kt) s = nkt / min_kt;
-    return s < 1 ? 1 : s;
-}
-
-// What one call runs: tile, K slices, and whether the activations still have to be split into the operand image.
-struct GemmPlan {
-    int choice, S;
-    size_t slab_bytes, xh_bytes;      // workspace: split-K slabs first, then (256-byte aligned) the split activations
-};
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-static GemmPlan gemm_plan(const ConvGemmArgs& a)
-{
-    GemmPlan p = {};
-    p.choice = gemm_tile_choice(a.M, a.N, a.n_prod ? a.n_prod : 3, a.Kp);
-    p.S = a.ileave_u > 1 ? 1 : gemm_ksplit(a.M, a.N, a.Kp, a.T, p.choice, a.K2);   // (the slab reduction writes plain rows)
-    p.slab_bytes = p.S > 1 ? (size_t)p.S * a.M * a.N * sizeof(float) : 0;
-    p.xh_bytes = a.Xh ? 0 : as_split_f16x2_bytes(a.K, a.N);
-    return p;
-}
-
-static bool direct_cin1(const ConvGemmArgs& a)
-{
-    return a.K == 1 && !a.K2 && a.W && a.X && (!a.Yh || a.T <= 9) && !a.res && !a.div_sqrt2 && !a.transpose_out && a.ileave_u <= 1 && a.M <= DIRECT_MAX_M && a.n_groups <= 1;
-}
-
-// A conv with an AdaIN / LayerNorm behind it (as_conv_gemm_multi_post_f32) whose output is tiny (batch-1 sizes: <= 1 MB) is cut into TWO K
-// slices even where the slicing rules would leave it whole: its reduction kernel then replaces the normalisation's launch (the slices
-// themselves cost nothing there: the launch is a few microseconds of latency either way).  The workspace always has room for it.
-static const size_t kPostSlabMax = (size_t)1 << 20;
-static bool post_slice_ok(const ConvGemmArgs& a)
-{
-    return a.Xh && a.ileave_u <= 1 && !a.transpose_out && (size_t)a.M * a.N * sizeof(float) <= kPostSlabMax &&
-           a.T * (a.Kp / 16) + as_cdiv(a.K2, 16) >= 8;
-}
-// the K slices of a problem planned at S: two where S = 1, post_slice_ok holds, the workspace has room for two slabs and a reduction can
-// write the LayerNorm (ln) / AdaIN (adain, max_w: its widest utterance) behind it.  Whatever AS_NO_REDUCE_* says -- the switch changes who
-// normalises, never the conv's own arithmetic.  (Two slices always have a k iteration each: the >= 8 k-blocks of post_slice_ok are >= 2
-// iterations of any tile, which splits K over at most 4 waves.)
-static int post_slices(const ConvGemmArgs& a, int S, bool ln, bool adain, int max_w)
-{
-    const bool two = S == 1 && post_slice_ok(a) && a.ws && a.ws_bytes >= 2 * (size_t)a.M * a.N * sizeof(float) &&
-                     ((ln && a.M % 8 == 0 && a.M <= 512 && !a.Yh && a.act <= 2) || (adain && max_w > 0 && max_w <= 256 && a.act <= 2));
-    return two ? 2 : S;
-}
-
-extern "C" size_t as_conv_gemm_workspace_bytes(const ConvGemmArgs* a)
-{
-    if (!a || a->M <= 0 || a->N <= 0 || a->Kp <= 0 || a->T <= 0) return 0;
-    if (direct_cin1(*a)) return 0;
-    const GemmPlan p = gemm_plan(*a);
-    const size_t slabs = std::max(p.slab_bytes, post_slice_ok(*a) ? 2 * (size_t)a->M * a->N * sizeof(float) : (size_t)0);
-    return p.xh_bytes ? align256(slabs) + p.xh_bytes : slabs;
-}
-
-// Room for the K slices a problem may be cut into inside a multi-problem launch (as_conv_gemm_multi_f32 takes no more slices than
-// a.ws_bytes holds slabs for): up to 16 slabs of a small output (<= 4 MB: anything larger has tiles enough to never need them), each
-// slice keeping >= 384 k; never less than the single launch wants.
-extern "C" size_t as_conv_gemm_multi_workspace_bytes(const ConvGemmArgs* a)
-{
-    const size_t single = as_conv_gemm_workspace_bytes(a);
-    if (!a || a->M <= 0 || a->N <= 0 || a->Kp <= 0 || a->T <= 0 || !a->Xh) return single;
-    const size_t slab = (size_t)a->M * a->N * sizeof(float);
-    if (slab > ((size_t)4 << 20)) return single;
-    const int nkt = a->T * (a->Kp / 16) + as_cdiv(a->K2, 16);
-    const int s = std::min(16, nkt / 24);
-    return std::max(single, s > 1 ? (size_t)s * slab : (size_t)0);
-}
-
-// which kernel a call with these arguments runs (tests, tuning): kind 0 = direct Cin = 1, 1 = tiled (tile = 22 / 21 / 12 / 11 / 14 / 2)
+// which kernel a call with these arguments wants to run (tests, tuning): kind 0 = direct Cin = 1, 1 = tiled (tile = 22 / 21 / 12 / 11 / 14 / 2)
 extern "C" int as_conv_gemm_plan(const ConvGemmArgs* a, int32_t* kind, int32_t* tile, int32_t* slices)
 {
-    if (!a || !kind || !tile || !slices || a->M <= 0 || a->N <= 0 || a->Kp <= 0 || a->T <= 0) return AS_EINVAL;
-    ConvGemmArgs n = *a;
-    if (n.n_prod == 0) n.n_prod = 3;
-    if (n.n_groups < 1) n.n_groups = 1;
-    *tile = 0;
-    *slices = 1;
-    if (direct_cin1(n)) { *kind = 0; return AS_OK; }
-    const GemmPlan p = gemm_plan(n);
-    *kind = 1;
-    *tile = p.choice;
-    *slices = p.S;
+    if (!a || !kind || !tile || !slices || !rule::sized(as_conv_gemm_shape(*a))) return AS_EINVAL;
+    const rule::Plan p = rule::want_one(as_conv_gemm_shape(*a), gemm_force());
+    *kind = p.direct ? 0 : 1;
+    *tile = p.tile;
+    *slices = p.S[0];
     return AS_OK;
+}
+
+// the one tile a set's launch runs
+extern "C" int as_conv_gemm_multi_tile(const ConvGemmArgs* list_host, int n)
+{
+    if (!list_host || n < 1 || n > H3_MAXP) return AS_EINVAL;
+    rule::Shape s[H3_MAXP];
+    for (int i = 0; i < n; ++i) s[i] = as_conv_gemm_shape(list_host[i]);
+    return rule::tile_set(s, n, gemm_force());
 }
 
 // argument checks and defaults shared by the single and the multi-problem entry point: `norm` becomes what the kernels are given
@@ -765,6 +657,24 @@ static double gemm_bytes(const ConvGemmArgs& a)
 {
     return 4.0 * (((double)a.T * a.K + a.K2) * a.M * a.n_groups + ((double)a.K + a.K2) * a.N + (double)a.M * a.N);
 }
+// the profiler's tag of a tiled launch: the problems in launch order with tile and slices
+static void gemm_launch_tag(const ConvGemmArgs* const* ptr, const int* So, int m, int tile, char* tag, size_t n)
+{
+    char shape[64];
+    if (m == 1) {
+        const ConvGemmArgs& a = *ptr[0];
+        gemm_tag(a, shape, sizeof(shape));
+        snprintf(tag, n, "%s tile%d S%d%s%s%s", shape, tile, So[0], a.n_prod == 1 ? " h1" : "", a.Xh ? "" : " +split", a.Yh ? (a.Y ? " y+yh" : " yh") : "");
+        return;
+    }
+    int at = snprintf(tag, n, "multi%d tile%d:", m, tile);
+    for (int k = 0; k < m; ++k) {
+        char sl[8] = "";
+        gemm_tag(*ptr[k], shape, sizeof(shape));
+        if (So[k] > 1) snprintf(sl, sizeof(sl), " S%d", So[k]);
+        if (at < (int)n - 1) at += snprintf(tag + at, n - at, " %s%s%s", shape, sl, k + 1 < m ? " |" : "");
+    }
+}
 // the fast direct form (T <= 9) for n problems
 static int launch_direct_x4(const ConvGemmArgs* a, int n, hipStream_t stream)
 {
@@ -806,16 +716,13 @@ static int ln_check(const ConvGemmArgs& a, const AsLnArgs& n)
         return AS_EINVAL;
     return AS_OK;
 }
-// can the reduction kernel of this K-sliced problem write the LayerNorm image itself?  (a wave per column, a lane per 8 channels; 16-byte loads)
-static bool ln_fusable(const ConvGemmArgs& a, const AsLnArgs& n)
+// the pointer half of "can the reduction kernel write the LayerNorm image itself" (conv_gemm_rule.h: post_fused): its 16-byte loads
+static bool ln_aligned(const ConvGemmArgs& a, const AsLnArgs& n)
 {
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const ptrdiff_t gs = n.gamma2 ? n.gamma2 - n.gamma : 0, bs = n.beta2 ? n.beta2 - n.beta : 0;
-    return a.M % 8 == 0 && a.M <= 512 && a.act <= 2 && !a.Yh && al16(n.gamma) && al16(n.beta) && gs % 4 == 0 && bs % 4 == 0 &&
-           (!a.bias || al16(a.bias)) && (double)a.M * a.N * 4.0 * 16.0 < 2147483648.0 && !getenv("AS_NO_REDUCE_LN");
+    return al16(n.gamma) && al16(n.beta) && gs % 4 == 0 && bs % 4 == 0 && (!a.bias || al16(a.bias));
 }
-// can the reduction kernel of this K-sliced problem write the AdaIN image itself?
-static bool post_fusable(const ConvGemmArgs& a, int max_w) { return max_w > 0 && max_w <= 256 && a.act <= 2 && (double)a.M * a.N * 4.0 * 16.0 < 2147483648.0 && !getenv("AS_NO_REDUCE_ADAIN"); }
 
 // one launch for the reductions of the K-sliced problems ptr[k] (So[k] > 1) of a launch; np[k] non-NULL: with the AdaIN behind it
 static int launch_reduce_post(const ConvGemmArgs* const* ptr, const int* So, const AsAdainArgs* const* np, const int* max_w,
@@ -826,7 +733,7 @@ static int launch_reduce_post(const ConvGemmArgs* const* ptr, const int* So, con
     int mw = 1;
     for (int k = 0; k < m; ++k)
         if (So[k] > 1 && np[k]) mw = std::max(mw, max_w[k]);
-    const int nj = (mw + 63) / 64;                                       // register columns per lane (post_fusable: <= 4)
+    const int nj = (mw + 63) / 64;                                       // register columns per lane (conv_gemm_rule.h: post_fits, <= 4)
     for (int k = 0; k < m; ++k)
         if (So[k] > 1) {
             const ConvGemmArgs& a = *ptr[k];
@@ -906,61 +813,9 @@ static int launch_reductions(const ConvGemmArgs* const* ptr, const int* So, cons
 // ----------------------------------------------------------------------------------------------------------------
 // One convolution, or several independent ones as ONE launch (include/artspeech_hip.h: as_conv_gemm_f32, as_conv_gemm_multi[_post]_f32).
 // ----------------------------------------------------------------------------------------------------------------
-// one tile for the whole set: the cost model of gemm_tile_choice on the SUM of the problems' tiles
-static int multi_tile_choice(const ConvGemmArgs* a, int n)
-{
-    const char* env = getenv("AS_GEMM_TILE");           // tuning/experiments only
-    if (env && atoi(env) > 0) return atoi(env);
-    // 128-row tiles when the problems that can fill them carry (nearly) all of the set's work: a 64-channel conv that rides along -- the
-    // decoder's asr_res beside a predictor block -- leaves the lower half of its few tiles empty, which costs less than a launch of its own
-    bool all_short = true, small_k = false, all_32 = true;
-    double work = 0, tall_work = 0;
-    for (int i = 0; i < n; ++i) {
-        const double wi = (double)a[i].M * a[i].N * ((double)a[i].K * a[i].T + a[i].K2);
-        work += wi;
-        if (as_fills_tall_tile(a[i].M)) tall_work += wi;
-        all_short = all_short && a[i].M <= 64;
-        all_32 = all_32 && a[i].M <= 32;
-        small_k = small_k || a[i].Kp <= 32;
-    }
-    const bool all_tall = tall_work >= 0.9 * work;
-    if (all_32 && a[0].n_prod == 3) return 2;             // (as the single launch: a 64-row tile would be half empty)
-    static const int choices[5] = {22, 21, 12, 11, 14};
-    static const double t1[5] = {1.0, 0.78, 0.78, 0.59, 1.3};   // (64 x 256 from M64 N509440 K64 T9: 139 us against 167 with 64 x 128)
-    int best = 11;
-    double best_cost = 1e30;
-    for (int c = 0; c < 5; ++c) {
-        int bm, bn;
-        tile_dims(choices[c], &bm, &bn);
-        if (bm >= 128 && !all_tall) continue;
-        if (choices[c] == 14 && (!all_short || a[0].n_prod != 3)) continue;
-        double tiles = 0;
-        for (int i = 0; i < n; ++i)
-            tiles += (double)as_cdiv(a[i].M, bm) * (a[i].n_groups > 1 ? a[i].n_groups * as_cdiv(a[i].group_cols, bn) : as_cdiv(a[i].N, bn));
-        if (choices[c] == 14 && tiles < 240) continue;
-        const double r = ceil(tiles / 256.0);
-        const double cost = t1[c] * (r > 1.0 ? 0.71 * r : 1.0);
-        if (cost < best_cost * 0.97) { best_cost = cost; best = choices[c]; }
-    }
-    if (small_k && best == 11) best = 12;               // (see gemm_tile_choice: images written by the 32-row tile)
-    return best;
-}
-
-extern "C" int as_conv_gemm_multi_tile(const ConvGemmArgs* list_host, int n)
-{
-    if (!list_host || n < 1 || n > H3_MAXP) return AS_EINVAL;
-    ConvGemmArgs norm[H3_MAXP];
-    for (int i = 0; i < n; ++i) {
-        norm[i] = list_host[i];
-        if (norm[i].n_prod == 0) norm[i].n_prod = 3;
-        if (norm[i].n_groups < 1) norm[i].n_groups = 1;
-    }
-    return multi_tile_choice(norm, n);
-}
-
-// 1 .. AS_MAX_MULTI problems: checks, plan, launch, then the AdaINs / LayerNorms no reduction took along.  ONE problem (after those
-// with N = 0 are dropped) runs by the single launch's rules: gemm_plan, fp32 activations split into the workspace first, the direct
-// Cin = 1 kernel for any T.  Several run as ONE launch by the set's rules -- multi_tile_choice, K slices by share -- from operand images only.
+// 1 .. AS_MAX_MULTI problems: normalise and check, ask the rule (conv_gemm_rule.h: plan_one for ONE problem -- after those with N = 0
+// are dropped -- plan_set for several, which run as ONE launch from operand images only), launch, then the AdaINs / LayerNorms no
+// reduction took along.
 static int conv_gemm(const ConvGemmArgs* list_host, const AsAdainArgs* post_host, const int32_t* post_max_w, const AsLnArgs* ln_host, int n,
                      hipStream_t stream)
 {
@@ -972,6 +827,8 @@ static int conv_gemm(const ConvGemmArgs* list_host, const AsAdainArgs* post_host
     bool has_ln[H3_MAXP];
     bool has_post[H3_MAXP], post_done[H3_MAXP];
     int pmw[H3_MAXP];
+    rule::Shape shape[H3_MAXP];
+    rule::Post rp[H3_MAXP];
     int m = 0;
     for (int i = 0; i < n; ++i) {
         const int r = conv_gemm_normalise(&list_host[i], norm[m]);
@@ -988,9 +845,13 @@ static int conv_gemm(const ConvGemmArgs* list_host, const AsAdainArgs* post_host
         post_done[m] = false;
         pmw[m] = has_post[m] ? post_max_w[i] : 0;
         if (has_post[m]) {
-            const int rp = post_normalise(norm[m], post_host[i], post[m]);
-            if (rp != AS_OK) return rp;
+            const int rn = post_normalise(norm[m], post_host[i], post[m]);
+            if (rn != AS_OK) return rn;
         }
+        shape[m] = as_conv_gemm_shape(norm[m]);
+        rp[m].kind = has_ln[m] ? rule::Post::Ln : has_post[m] ? rule::Post::Adain : rule::Post::None;
+        rp[m].max_w = pmw[m];
+        rp[m].ln_aligned = has_ln[m] && ln_aligned(norm[m], lnp[m]);
         ++m;
     }
     if (m == 0) return AS_OK;
@@ -1009,9 +870,9 @@ static int conv_gemm(const ConvGemmArgs* list_host, const AsAdainArgs* post_host
         }
         return AS_OK;
     };
-    bool direct = true;                                                  // one Cin = 1 conv, or a set of Cin = 1 stems (T <= 9): the direct kernel
-    for (int i = 0; i < m; ++i) direct = direct && direct_cin1(norm[i]) && (m == 1 || norm[i].T <= 9);
-    if (direct) {
+    const rule::Plan plan = m == 1 ? rule::plan_one(shape[0], rp[0], gemm_force()) : rule::plan_set(shape, rp, m, gemm_force());
+    if (!plan.ok) return AS_EINVAL;
+    if (plan.direct) {                                                   // one Cin = 1 conv, or a set of Cin = 1 stems (T <= 9)
         static_assert(DIRECT_MAXP == H3_MAXP, "one list length");
         double fl = 0, by = 0;
         for (int i = 0; i < m; ++i) {
@@ -1033,108 +894,45 @@ static int conv_gemm(const ConvGemmArgs* list_host, const AsAdainArgs* post_host
         }
         return finish_posts();
     }
-    // the tiled kernel needs a weight image; a set, in one launch, only what it runs from operand images with the same arithmetic
-    for (int i = 0; i < m; ++i)
-        if (direct_cin1(norm[i]) || !norm[i].Wh || (m > 1 && (!norm[i].Xh || norm[i].n_prod != norm[0].n_prod || norm[i].ileave_u > 1)))
-            return AS_EINVAL;
-    int choice, S[H3_MAXP], order[H3_MAXP];
-    size_t xh_off = 0;                                                   // one problem without an operand image: where its split goes
-    for (int i = 0; i < m; ++i) order[i] = i;
-    if (m == 1) {
-        const ConvGemmArgs& a = norm[0];
-        GemmPlan plan = gemm_plan(a);
-        if (plan.xh_bytes) {                                   // no operand image from the caller: it needs room in the workspace
-            if (!a.ws || a.ws_bytes < plan.xh_bytes) return AS_EINVAL;
-            if (a.ws_bytes < align256(plan.slab_bytes) + plan.xh_bytes) { plan.S = 1; plan.slab_bytes = 0; }
-        } else if (plan.S > 1 && (!a.ws || a.ws_bytes < plan.slab_bytes)) {
-            plan.S = 1;                                        // no workspace: no K slices
-            plan.slab_bytes = 0;
-        }
-        choice = plan.choice;
-        S[0] = post_slices(a, plan.S, has_ln[0], has_post[0], pmw[0]);
-        xh_off = align256(plan.slab_bytes);
-    } else {
-        choice = multi_tile_choice(norm, m);
-        int bm, bn;
-        tile_dims(choice, &bm, &bn);
-        // K slices: a launch costs what its longest chain of k iterations on one CU costs.  With W = all problems' tiles x iterations spread
-        // over the chip's 512 workgroup slots, a problem whose tile alone runs longer than that share (the towers' closing 5 x 5 convs: 800
-        // k-blocks on a dozen tiles, beside convs of 30-300) is cut into slices of about that length -- as many as its workspace holds slabs
-        // for, each keeping >= 384 k.  (That is also the rule of the single launch for grids that leave most of the chip idle.)
-        const int wk = choice == 2 ? 2 : bm * bn >= 4 * 64 * 64 ? 1 : 4 * 64 * 64 / (bm * bn);
-        int nkt[H3_MAXP];
-        double len[H3_MAXP], W = 0;
-        for (int i = 0; i < m; ++i) {
-            const ConvGemmArgs& a = norm[i];
-            nkt[i] = a.T * as_cdiv(a.Kp / 16, wk) + as_cdiv(as_cdiv(a.K2, 16), wk);
-            W += (double)nkt[i] * as_cdiv(a.M, bm) * (a.n_groups > 1 ? a.n_groups * as_cdiv(a.group_cols, bn) : as_cdiv(a.N, bn));
-        }
-        const double share = std::max(W / 512.0, 1.0);
-        for (int i = 0; i < m; ++i) {
-            const ConvGemmArgs& a = norm[i];
-            const int min_kt = std::max(1, 24 / wk);
-            int s = nkt[i] > 1.5 * share ? (int)ceil(nkt[i] / share) : 1;
-            s = std::min(std::min(s, 16), nkt[i] / min_kt);
-            const size_t slab = (size_t)a.M * a.N * sizeof(float);
-            if (s > 1 && (!a.ws || a.ws_bytes / slab < (size_t)s)) s = a.ws ? (int)std::min<size_t>(a.ws_bytes / slab, (size_t)s) : 1;
-            S[i] = post_slices(a, s < 1 ? 1 : s, has_ln[i], has_post[i], pmw[i]);
-            len[i] = (double)nkt[i] / S[i];
-        }
-        std::sort(order, order + m, [&](int x, int y) { return len[x] > len[y]; });
-    }
+    // the tiled kernel, the problems in the plan's order.  A K-sliced problem whose result is read through a LayerNorm / an AdaIN (few
+    // columns: the reduction holds a channel's whole time axis) may have the reduction write that image too (plan.fused); with a LayerNorm
+    // the slices then store their slabs time-major (it normalises whole columns).
     const ConvGemmArgs* ptr[H3_MAXP];
-    int So[H3_MAXP];
-    double flops = 0, bytes = 0;
-    for (int k = 0; k < m; ++k) {
-        ptr[k] = &norm[order[k]];
-        So[k] = S[order[k]];
-        flops += gemm_flops(*ptr[k]);
-        bytes += gemm_bytes(*ptr[k]);
-    }
-    char tag[160], shape[64];
-    if (m == 1) {
-        const ConvGemmArgs& a = norm[0];
-        gemm_tag(a, shape, sizeof(shape));
-        snprintf(tag, sizeof(tag), "%s tile%d S%d%s%s%s", shape, choice, So[0], a.n_prod == 1 ? " h1" : "", a.Xh ? "" : " +split",
-                 a.Yh ? (a.Y ? " y+yh" : " yh") : "");
-    } else {
-        int at = snprintf(tag, sizeof(tag), "multi%d tile%d:", m, choice);
-        for (int k = 0; k < m; ++k) {
-            char sl[8] = "";
-            gemm_tag(*ptr[k], shape, sizeof(shape));
-            if (So[k] > 1) snprintf(sl, sizeof(sl), " S%d", So[k]);
-            if (at < (int)sizeof(tag) - 1) at += snprintf(tag + at, sizeof(tag) - at, " %s%s%s", shape, sl, k + 1 < m ? " |" : "");
-        }
-    }
-    // K-sliced problems whose result is read through a LayerNorm / an AdaIN (few columns: the reduction holds a channel's whole time
-    // axis): the reduction launch writes that image too.  With a LayerNorm the slices store their slabs time-major (it normalises whole columns).
     const AsLnArgs* nl[H3_MAXP];
     const AsAdainArgs* np[H3_MAXP];
-    int mwo[H3_MAXP];
+    int So[H3_MAXP], mwo[H3_MAXP];
+    double flops = 0, bytes = 0;
     for (int k = 0; k < m; ++k) {
-        const int i = order[k];
-        nl[k] = (has_ln[i] && So[k] > 1 && ln_fusable(norm[i], lnp[i])) ? &lnp[i] : nullptr;
-        np[k] = (has_post[i] && So[k] > 1 && post_fusable(norm[i], pmw[i])) ? &post[i] : nullptr;
+        const int i = plan.order[k];
+        if (!norm[i].Wh) return AS_EINVAL;                               // (it needs a weight image)
+        ptr[k] = &norm[i];
+        So[k] = plan.S[i];
+        flops += gemm_flops(norm[i]);
+        bytes += gemm_bytes(norm[i]);
+        nl[k] = has_ln[i] && plan.fused[i] ? &lnp[i] : nullptr;
+        np[k] = has_post[i] && plan.fused[i] ? &post[i] : nullptr;
         norm[i].slab_tr = nl[k] ? 1 : 0;
         mwo[k] = pmw[i];
     }
+    char tag[160];
+    gemm_launch_tag(ptr, So, m, plan.tile, tag, sizeof(tag));
     {
         // algorithmic work of this launch: 2*M*N*(K*T + K2) flop; bytes = weights + inputs + output once (4 bytes per element)
         AsProfScope prof__(AS_CLS_GEMM, flops, bytes, stream, tag);
         if (!norm[0].Xh) {                                               // (one problem) split once, behind the K slabs in the workspace
             ConvGemmArgs& a = norm[0];
-            uint16_t* xh = reinterpret_cast<uint16_t*>(reinterpret_cast<unsigned char*>(a.ws) + xh_off);
+            uint16_t* xh = reinterpret_cast<uint16_t*>(reinterpret_cast<unsigned char*>(a.ws) + plan.xh_off);
             const int rc = as_split_f16x2_launch(a.X, a.ldx, a.K, a.N, a.in_act == 2, a.in_slope, xh, stream);
             if (rc != AS_OK) return rc;
             a.Xh = xh;
         }
-        const int rc = as_conv_gemm_h3_launch(ptr, So, m, choice, stream);
+        const int rc = as_conv_gemm_h3_launch(ptr, So, m, plan.tile, stream);
         if (rc != AS_OK) return rc;
         const int rr = launch_reductions(ptr, So, np, mwo, nl, m, stream);
         if (rr != AS_OK) return rr;
     }
     for (int k = 0; k < m; ++k)
-        if (np[k] || nl[k]) post_done[order[k]] = true;
+        if (np[k] || nl[k]) post_done[plan.order[k]] = true;
     return finish_posts();
 }
 

@@ -506,8 +506,7 @@ split_f16x2_kernel(const float* __restrict__ x, int ldx, int K, int N, const int
 
 extern "C" size_t as_split_f16x2_bytes(int K, int N)
 {
-    if (K <= 0 || N <= 0) return 0;
-    return (size_t)as_kbx(K) * 4 * ((size_t)N + 1) * 16;
+    return conv_gemm_rule::split_f16x2_bytes(K, N);
 }
 
 int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, float slope, uint16_t* xh, hipStream_t stream,

@@ -340,6 +340,7 @@ struct Op {
     Kind kind = Kind::Launch;
     std::function<int(hipStream_t)> fn;            // Launch: the recorded call, on the stream it is handed
     ConvGemmArgs g;                                // Conv: as_conv_gemm_f32 arguments
+    bool direct = false, image_in = false;         // Conv: the rule's answer for its shape (the Cin = 1 kernel), and whether it reads an operand image
     AsAdainArgs post;                              // Conv: the AdaIN that reads the conv's result (post.yh NULL: none), as_conv_gemm_multi_post_f32
     int post_max_w = 0;
     AsLnArgs post_ln;                              // Conv: ... or the channel LayerNorm that does (post_ln.yh NULL: none)
@@ -455,8 +456,8 @@ struct Ctx : PassCtx {
         }                                              \
     } while (0)
 
-// Play the recorded queues out on stream `s`: summarise them for play_order.h (one as_conv_gemm_plan per recorded conv), ask it for the
-// steps, and carry those out until one fails.
+// Play the recorded queues out on stream `s`: summarise them for play_order.h (a conv by what conv_gemm_rule.h said of its shape when it
+// was recorded), ask it for the steps, and carry those out until one fails.
 static void play(Ctx& c, Sched& S)
 {
     const int nq = (int)S.q.size();
@@ -472,10 +473,8 @@ static void play(Ctx& c, Sched& S)
             u.deps = o.deps;
             if (o.kind == Kind::Conv) {
                 const ConvGemmArgs& g = o.g;
-                int32_t kind = -1, tile = 0, slices = 0;
-                const bool planned = g.N > 0 && as_conv_gemm_plan(&g, &kind, &tile, &slices) == AS_OK;
-                u.mergeable = planned && g.Xh && kind == 1;             // operand image in, the tiled kernel
-                u.direct = planned && g.T <= 9 && kind == 0;            // the Cin = 1 direct kernel's fast form
+                u.mergeable = g.N > 0 && o.image_in && !o.direct;       // operand image in, the tiled kernel
+                u.direct = g.N > 0 && g.T <= 9 && o.direct;             // the Cin = 1 direct kernel's fast form
                 u.tall = as_fills_tall_tile(g.M);
                 u.n_prod = g.n_prod;
                 u.work = (double)g.M * g.N * ((double)g.K * g.T + g.K2);
@@ -754,13 +753,10 @@ void conv_impl(Ctx& c, const GemmW* w, const float* X, int ldx, const uint16_t* 
         a.in_act = 0;
         in_image = true;
     }
-    // pointers that are null only because this pass does not run kernels must not change the plan the library makes
-    ConvGemmArgs q = a;
-    q.X = in_image ? nullptr : reinterpret_cast<const float*>(16);
-    q.Xh = in_image ? reinterpret_cast<const uint16_t*>(16) : nullptr;
-    q.Yh = o.want_yh ? reinterpret_cast<uint16_t*>(16) : nullptr;
-    q.Xh2 = o.K2 ? reinterpret_cast<const uint16_t*>(16) : nullptr;
-    const size_t wsb = rec ? as_conv_gemm_multi_workspace_bytes(&q) : as_conv_gemm_workspace_bytes(&q);
+    // what the library's plan depends on, by what THIS plan knows in every pass (a pass that runs no kernels holds null pointers)
+    conv_gemm_rule::Shape sh = as_conv_gemm_shape(a);
+    sh.x32 = !in_image; sh.xh = in_image; sh.yh = o.want_yh; sh.w32 = w->w32 != nullptr;
+    const size_t wsb = as_conv_gemm_shape_workspace(sh, rec);
     if (getenv("AS_DEBUG_ALLOC"))
         fprintf(stderr, "artspeech_hip: conv %s M%d N%d K%d T%d G%d img%d -> ws %zu (arena at %zu)\n", pass_name(c.pass), a.M, a.N, a.K, a.T,
                 a.n_groups, (int)in_image, wsb, c.off);
@@ -785,6 +781,8 @@ void conv_impl(Ctx& c, const GemmW* w, const float* X, int ldx, const uint16_t* 
     if (c.deferring()) {                  // recorded: it may share its launch with other branches' convs
         Op& op = c.push(Kind::Conv);
         op.g = a;
+        op.direct = conv_gemm_rule::direct_cin1(sh);
+        op.image_in = in_image;
         op.post = post;
         op.post_ln = o.ln;
         op.post_max_w = post_mw;

@@ -265,11 +265,10 @@ void conv(Seq& c, const ConvW& w, const float* X, int ldx, const uint16_t* xh, i
     a.ileave_u = o.ileave;
     for (int t = 0; t < w.T; ++t) { a.dh[t] = 0; a.dw[t] = o.dil * (t - w.T / 2); }
     if (lay->N == 0) return;
-    // the workspace the library wants depends on WHICH operands are given, not on their addresses: the count pass asks with placeholders
-    ConvGemmArgs q = a;
-    q.X = xh ? nullptr : reinterpret_cast<const float*>(16);
-    q.Xh = xh ? reinterpret_cast<const uint16_t*>(16) : nullptr;
-    const size_t wsb = as_conv_gemm_workspace_bytes(&q);
+    // the workspace the library wants depends on WHICH operands are given, not on their addresses (null in the count pass)
+    conv_gemm_rule::Shape sh = as_conv_gemm_shape(a);
+    sh.x32 = !xh; sh.xh = xh != nullptr;
+    const size_t wsb = as_conv_gemm_shape_workspace(sh, false);
     const size_t mark = c.off;
     a.ws = wsb ? c.raw_alloc(wsb) : nullptr;
     a.ws_bytes = wsb;

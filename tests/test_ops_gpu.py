@@ -819,6 +819,53 @@ def test_conv_gemm_multi(cuda, monkeypatch, impl, name, tile):
             assert float((y - y1).abs().max()) <= 2e-5
 
 
+def test_conv_gemm_launches_what_the_rule_table_says(cuda, monkeypatch, tmp_path):
+    """What is launched is what tests/test_gemm_rule_cpu.py pins on the CPU: one K-sliced conv and the recorded three-problem set with one
+    problem cut (at the smallest N it is still cut at) run with the profiler on, and the GEMM tags -- tile, S, problem order -- are those
+    of the same two cases of tests/golden/gemm_rule_parent.json."""
+    import ctypes
+    import json
+    import os
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_rule_parent.json")))
+    cases = {c["name"]: c for c in golden["cases"]}
+    one, three = cases["gpu: M256 N300 K256 T25"], cases["gpu: the one-cut set at small N"]
+    for env in ("AS_GEMM_TILE", "AS_GEMM_KSPLIT"):
+        monkeypatch.delenv(env, raising=False)
+    csv = tmp_path / "launches.csv"
+    monkeypatch.setenv("AS_PROF_CSV", str(csv))
+    g = torch.Generator().manual_seed(77)
+    spec = lambda c: [(p["K"], p["M"], p["T"], [p["N"]], "plain") for p in c["problems"]]
+    d1, outs1, wants1, _ = _multi_problems(cuda, g, spec(one))
+    d3, outs3, wants3, _ = _multi_problems(cuda, g, spec(three))
+    for c, deferred in ((one, d1), (three, d3)):                       # the launches are the table's cases
+        for p, (a, _keep) in zip(c["problems"], deferred):
+            assert [a.M, a.N, a.K, a.Kp, a.T, a.K2, a.n_prod, a.n_groups, a.act, bool(a.Xh), bool(a.Yh), bool(a.res)] == \
+                   [p["M"], p["N"], p["K"], p["Kp"], p["T"], p["K2"], p["n_prod"], p["n_groups"], p["act"], bool(p["xh"]), bool(p["yh"]), bool(p["res"])]
+    a = d1[0][0]
+    a.ws_bytes = one["problems"][0]["ws_bytes"]                         # (deferred: the set's room was allocated, never less than the single's)
+    assert three["want"]["ws_set"] == [x.ws_bytes for x, _ in d3] and a.ws_bytes == one["want"]["ws_one"][0]
+    L = ops._lib.lib()
+    L.as_prof_enable(1)
+    try:
+        ops.check(L.as_conv_gemm_f32(ctypes.byref(a), ops.stream()), "as_conv_gemm_f32")
+        ops.conv_gemm_multi(d3)
+        n = 7
+        ms, fl, by, cnt = (ctypes.c_double * n)(), (ctypes.c_double * n)(), (ctypes.c_double * n)(), (ctypes.c_int32 * n)()
+        ops.check(L.as_prof_collect(ms, fl, by, cnt, n), "as_prof_collect")
+    finally:
+        L.as_prof_enable(0)
+    torch.cuda.synchronize()
+    for y, want in zip(outs1 + outs3, wants1 + wants3):
+        assert float((y.double().cpu() - want).abs().max()) <= 3e-5
+    tags = [ln.split(",")[1] for ln in csv.read_text().splitlines() if ln.startswith("0,")]
+    shape = lambda p: f"M{p['M']} N{p['N']} K{p['K']} T{p['T']}"
+    w1, w3 = one["want"], three["want"]
+    assert w1["S"][0] > 1 and sum(s > 1 for s in w3["S"]) == 1 and w3["order"] != sorted(w3["order"])   # (what the cases are about)
+    want_tags = [f"{shape(one['problems'][0])} tile{w1['tile']} S{w1['S'][0]}",
+                 f"multi3 tile{w3['tile']}: " + " | ".join(shape(three["problems"][i]) + (f" S{w3['S'][i]}" if w3["S"][i] > 1 else "") for i in w3["order"])]
+    assert tags == want_tags, (tags, want_tags)
+
+
 @pytest.mark.parametrize("case", ["single", "multi", "grouped", "wide", "unsliced"])
 def test_conv_gemm_post_adain(cuda, monkeypatch, case):
     """as_conv_gemm_multi_post_f32 (models.py:189-202: conv -> AdaIN -> LeakyReLU -> conv): the AdaIN image of a conv's result from the
