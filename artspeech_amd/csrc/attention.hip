@@ -33,19 +33,6 @@
 #define MAXDK 128
 #define MAXREL 9
 
-static __device__ __forceinline__ float wmax(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-static __device__ __forceinline__ float wsum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ void __launch_bounds__(256)
 relpos_attention_kernel(const float* __restrict__ qkv, int ld, int C, int heads, int window,
                         const float* __restrict__ emb_k1, const float* __restrict__ emb_v1, const float* __restrict__ emb_k2,
@@ -122,10 +109,10 @@ relpos_attention_kernel(const float* __restrict__ qkv, int ld, int C, int heads,
             const int r = kj - qi + window;
             if (r >= 0 && r < nrel) sc += Rk[(wave * 4 + qq) * MAXREL + r];
             if (kj >= N) sc = -INFINITY;
-            const float mn = fmaxf(m[qq], wmax(sc));
+            const float mn = fmaxf(m[qq], as_wave_max(sc));
             const float p = (kj < N) ? expf(sc - mn) : 0.f;
             const float corr = expf(m[qq] - mn);           // exp(-inf) = 0 on the first tile
-            l[qq] = l[qq] * corr + wsum(p);
+            l[qq] = l[qq] * corr + as_wave_sum(p);
             acc[qq][0] *= corr;
             acc[qq][1] *= corr;
             m[qq] = mn;
@@ -240,9 +227,9 @@ relpos_attention_image_kernel(const AttnImageArgs a)
     const int q0 = blockIdx.x * NQ;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 5, lq = lane & 31;
     const int nrel = 2 * a.window + 1, window = a.window;
-    const size_t NX = (size_t)a.n_total + 1;
+    const size_t NX = operand_image::rows(a.n_total);
     if (a.out_h && blockIdx.x == 0 && b == 0 && tid < KB * 4) {         // the image's zero column, this head's k-blocks
-        reinterpret_cast<u32x4_t*>(a.out_h)[((size_t)(h * KB) * 4 + tid) * NX + a.n_total] = u32x4_t{0u, 0u, 0u, 0u};
+        reinterpret_cast<u32x4_t*>(a.out_h)[operand_image::plane_row((size_t)(h * KB) * 4 + tid, a.n_total, NX)] = u32x4_t{0u, 0u, 0u, 0u};
     }
     if (q0 >= N) return;
     const float cs = 1.44269504088896340736f / sqrtf((float)DK);
@@ -257,20 +244,20 @@ relpos_attention_image_kernel(const AttnImageArgs a)
     if constexpr (!ONE) {
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
-            Qh[kb] = img[((size_t)(qkb0 + kb) * 4 + g) * NX + qcol];
-            Ql[kb] = img[((size_t)(qkb0 + kb) * 4 + 2 + g) * NX + qcol];
+            Qh[kb] = img[operand_image::row_of(qkb0 + kb, 0, g, qcol, NX)];
+            Ql[kb] = img[operand_image::row_of(qkb0 + kb, 1, g, qcol, NX)];
         }
     }
     // ONE: the K fragments of 32-key block sb, like Q (keys past the image's end read its zero column; keys >= N are masked below)
     u32x4_t Kh[2][KB], Kl[2][KB];
     auto load_k = [&](int sb, int kb) {
         const size_t kcol = (size_t)min(o0 + sb * 32 + lq, a.n_total);
-        Kh[sb][kb] = img[((size_t)(kkb0 + kb) * 4 + g) * NX + kcol];
-        Kl[sb][kb] = img[((size_t)(kkb0 + kb) * 4 + 2 + g) * NX + kcol];
+        Kh[sb][kb] = img[operand_image::row_of(kkb0 + kb, 0, g, kcol, NX)];
+        Kl[sb][kb] = img[operand_image::row_of(kkb0 + kb, 1, g, kcol, NX)];
     };
     // K tile k0 -> buffer `buf`: chunk (p, kb, g') = 64 keys x 16 bytes, contiguous in the image and in LDS
     const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.qkv_h), 0,
-                                                                         (int)((unsigned)(3 * a.C / 16) * 4u * (unsigned)NX * 16u), 0x00020000);
+                                                                         (int)operand_image::desc_bytes_kb(3 * a.C / 16, (unsigned)NX), 0x00020000);
     (void)rsK;
     (void)kkb0;
     auto issue_k = [&](int k0, int buf) {
@@ -278,7 +265,7 @@ relpos_attention_image_kernel(const AttnImageArgs a)
 #pragma unroll
         for (int i = 0; i < 2 * KB * 2 / NW; ++i) {
             const int ch = wave + NW * i, pp = ch / (KB * 2), kb = (ch / 2) % KB, gg = ch & 1;
-            const unsigned voff = (unsigned)((((kkb0 + kb) * 4 + pp * 2 + gg) * NX + (size_t)(o0 + k0 + lane)) * 16u);
+            const unsigned voff = (unsigned)(operand_image::row_of(kkb0 + kb, pp, gg, o0 + k0 + lane, NX) * 16u);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, (attn_lds_void*)(smraw + (size_t)buf * (2 * KB * 2 * FK * 16) + ch * (FK * 16)), 16, voff, 0,
                                                      0, 0);
         }
@@ -337,8 +324,8 @@ relpos_attention_image_kernel(const AttnImageArgs a)
     if constexpr (ONE) {                                                // (the same loads behind the V tile's branch: in front of it, the branch's
 #pragma unroll                                                          //  blocks waited for them -- a memory round trip of their own)
         for (int kb = 0; kb < KB; ++kb) {
-            Qh[kb] = img[((size_t)(qkb0 + kb) * 4 + g) * NX + qcol];
-            Ql[kb] = img[((size_t)(qkb0 + kb) * 4 + 2 + g) * NX + qcol];
+            Qh[kb] = img[operand_image::row_of(qkb0 + kb, 0, g, qcol, NX)];
+            Ql[kb] = img[operand_image::row_of(qkb0 + kb, 1, g, qcol, NX)];
         }
     }
     // the two 9-row tables as matrix-core operands: q . Ek[r] is one more "key" block, sum_r p_r Ev[r] one more contraction block.
@@ -562,10 +549,10 @@ relpos_attention_image_kernel(const AttnImageArgs a)
                     unsigned h0, l0, h1, l1;
                     split2_pair(v[0], v[1], h0, l0);
                     split2_pair(v[2], v[3], h1, l1);
-                    const size_t kbo = (size_t)(h * KB + mb * 2 + (e4 >> 1));
-                    u32x2_t* oh = reinterpret_cast<u32x2_t*>(a.out_h);
-                    oh[((kbo * 4 + (e4 & 1)) * NX + o0 + qi) * 2 + g] = u32x2_t{h0, h1};
-                    oh[((kbo * 4 + 2 + (e4 & 1)) * NX + o0 + qi) * 2 + g] = u32x2_t{l0, l1};
+                    const int kbo = h * KB + mb * 2 + (e4 >> 1);
+                    u32x2_t* oh = reinterpret_cast<u32x2_t*>(a.out_h);             // (this lane's half of the row)
+                    oh[(operand_image::row_of(kbo, 0, e4 & 1, 0, NX) + o0 + qi) * 2 + g] = u32x2_t{h0, h1};
+                    oh[(operand_image::row_of(kbo, 1, e4 & 1, 0, NX) + o0 + qi) * 2 + g] = u32x2_t{l0, l1};
                 }
             }
     }

@@ -153,6 +153,24 @@ static __device__ __forceinline__ int as_pcm16(float w, bool* nan)
     *nan = w != w;
     return *nan ? 0 : (int)fmaxf(-32768.f, fminf(32767.f, rintf(__fmul_rn(32767.f, w))));
 }
+// 64-lane butterfly sum / maximum, o = 32 .. 1: every lane gets the result, and every kernel that must agree bitwise uses this one order
+template <typename T>
+static __device__ __forceinline__ T as_wave_sum(T v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+static __device__ __forceinline__ float as_wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+// THE ORDER OF ADDITIONS of the AdaIN statistics over an utterance of L columns (adain_kernel, adain_image_kernel, the K-sliced
+// reduction with the AdaIN behind it: the same bits in all of them): one wave per channel, a lane adds its elements i = lane, lane + 64,
+// ... in ascending order, then as_wave_sum; mean = sum / L; the variance is a second pass over d = __fsub_rn(x, mean) with
+// __fmaf_rn(d, d, acc) per element, the same two steps; rstd = 1 / sqrtf(var / L + 1e-5f).
 // AdaIN1d value and the fused depthwise ConvTranspose1d(k3, s2, p1, op1) pair, written with explicit roundings so that every
 // kernel that evaluates them (adain_kernel: fp32 output; adain_image_kernel: operand image) produces the same bits whatever
 // the compiler would contract.

@@ -26,19 +26,6 @@
 #define XPW (XKT + XQT)            // window of p rows a (query tile, key tile) pair touches: 79 <= 80
 #define XPP (XPW + 1)
 
-static __device__ __forceinline__ float xwmax(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-static __device__ __forceinline__ float xwsum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ void __launch_bounds__(256)
 xl_attention_kernel(const float* __restrict__ qkv, int ld, int C, const float* __restrict__ pos, int ldp,
                     const float* __restrict__ u_bias, const float* __restrict__ v_bias, float inv_scale,
@@ -130,10 +117,10 @@ xl_attention_kernel(const float* __restrict__ qkv, int ld, int C, const float* _
         for (int qq = 0; qq < 4; ++qq) {
             float s = (sc[qq] + sp[qq]) * inv_scale;
             if (kj >= T) s = -INFINITY;
-            const float mn = fmaxf(m[qq], xwmax(s));
+            const float mn = fmaxf(m[qq], as_wave_max(s));
             const float p = (kj < T) ? expf(s - mn) : 0.f;
             const float corr = expf(m[qq] - mn);           // exp(-inf) = 0 on the first tile
-            l[qq] = l[qq] * corr + xwsum(p);
+            l[qq] = l[qq] * corr + as_wave_sum(p);
             acc[qq] *= corr;
             m[qq] = mn;
             Pw[lane * 4 + qq] = p;

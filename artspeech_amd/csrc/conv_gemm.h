@@ -4,6 +4,7 @@
 #include "artspeech_hip.h"
 #include "common.h"
 #include "conv_gemm_rule.h"
+#include "operand_image.h"
 
 #define OOB 0xFFFFFFFFu
 #define OOBH 0x80000000u   /* epilogue: out of range for every descriptor (< 2 GiB, host-checked) even after adding an in-range offset */
@@ -15,7 +16,7 @@ int as_conv_gemm_h3_launch(const ConvGemmArgs* const* a, const int* S, int n, in
 int as_split_f16x2_launch(const float* x, int ldx, int K, int N, int lrelu, float slope, uint16_t* xh, hipStream_t stream,
                           const int32_t* n_valid = nullptr);
 
-static inline __host__ __device__ int as_kbx(int K) { return conv_gemm_rule::kbx(K); }
+static inline __host__ __device__ int as_kbx(int K) { return operand_image::kbx(K); }
 // host: M output channels fill a 128-row tile well enough to use one -- the tile rules of conv_gemm_rule.h, and the row classes by which
 // the recorded schedule (model.hip: play) picks the convs that share a launch
 static inline bool as_fills_tall_tile(int M) { return conv_gemm_rule::fills_tall_tile(M); }
@@ -75,10 +76,7 @@ static __device__ __forceinline__ unsigned long long h3_tap_word(const H3Taps& t
 #ifdef __HIPCC__
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 static __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
@@ -116,27 +114,6 @@ static __device__ __forceinline__ int logical_of(int local, int wgs)
     return (local & 7) * (wgs >> 3) + (local >> 3);
 }
 
-// two fp32 -> (h, l) fp16 pairs with x = h + l to 22 bits: v_cvt_pk_f16_f32 (RNE), the residual is exact in fp32
-static __device__ __forceinline__ void split2_pair(float x0, float x1, unsigned& h, unsigned& l)
-{
-    const f32x2 v = {x0, x1};
-    const f16x2 hh = __builtin_convertvector(v, f16x2);
-    const f32x2 r = v - __builtin_convertvector(hh, f32x2);
-    h = __builtin_bit_cast(unsigned, hh);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-}
-// 8 fp32 (consecutive k of one column) -> two 16-byte rows of 8 fp16
-static __device__ __forceinline__ void split2(const float (&x)[8], u32x4_t& h, u32x4_t& l)
-{
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        unsigned hu, lu;
-        split2_pair(x[2 * e], x[2 * e + 1], hu, lu);
-        h[e] = hu;
-        l[e] = lu;
-    }
-}
-
 static __device__ __forceinline__ float div_sqrt2f(float x)
 {
     // x / sqrt(2), correctly rounded without the division sequence: q = x*(1/c), one Newton correction in fma
@@ -162,7 +139,7 @@ static __device__ __forceinline__ float epi_act(float x, float slope)
 static __device__ __forceinline__ void yh_store_tile(const ConvGemmArgs& a, __amdgpu_buffer_rsrc_t rsH, const float (&v)[16], int row0,
                                                      int col, int lk, int n_end)
 {
-    const unsigned NXy = (unsigned)a.N + 1u;
+    const unsigned NXy = operand_image::rows32(a.N);
     const int groups = 2 * as_kbx(a.M);
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
@@ -185,12 +162,14 @@ static __device__ __forceinline__ void yh_store_tile(const ConvGemmArgs& a, __am
         split2(t, h, l);
         const int g = (row0 >> 3) + 2 * pr + lk;                        // 8-row group: k-block g / 2, k-half g % 2
         const bool ok = col < n_end && g < groups;
-        const unsigned off = ok ? ((unsigned)((g >> 1) * 4 + (g & 1)) * NXy + (unsigned)col) * 16u : OOBH;
+        // (the two stores by hand, = oi_store_buf(rsH, off, NXy, h, l): through that helper hipcc allocates the conv GEMM kernels'
+        // registers differently, and their speed is the project's headline)
+        const unsigned off = ok ? operand_image::byte_off(operand_image::plane(g), col, NXy) : OOBH;
         __builtin_amdgcn_raw_buffer_store_b128(h, rsH, off, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b128(l, rsH, off + 2u * NXy * 16u, 0, 0);
         if (col == 0 && g < groups) {                                   // the zero column N, once per (group, part)
             const u32x4_t z = {0u, 0u, 0u, 0u};
-            const unsigned offz = ((unsigned)((g >> 1) * 4 + (g & 1)) * NXy + (unsigned)a.N) * 16u;
+            const unsigned offz = operand_image::byte_off(operand_image::plane(g), a.N, NXy);
             __builtin_amdgcn_raw_buffer_store_b128(z, rsH, offz, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b128(z, rsH, offz + 2u * NXy * 16u, 0, 0);
         }
@@ -214,7 +193,7 @@ static __device__ __forceinline__ void epilogue_tiles(const ConvGemmArgs& a, con
     const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(
         a.Y, 0, a.Y ? (int)((unsigned)(TR ? a.N : (a.ileave_u > 1 ? a.M / a.ileave_u : a.M)) * a.ldy * 4u) : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(
-        a.Yh, 0, a.Yh ? (int)((unsigned)as_kbx(a.M) * 4u * ((unsigned)a.N + 1u) * 16u) : 0, 0x00020000);
+        a.Yh, 0, a.Yh ? (int)operand_image::desc_bytes(a.M, operand_image::rows32(a.N)) : 0, 0x00020000);
     const float sc = a.acc_scale;
     if (a.range_probe) {                                   // range probe (as_set_range_probe): a wave-uniform branch, off by default
         bool bad = false;
@@ -439,10 +418,8 @@ static __device__ __forceinline__ void as_reduce_epilogue(const ConvGemmArgs& a,
         }
         u32x4_t h, l;
         split2(v, h, l);
-        const size_t NX = (size_t)a.N + 1;
-        u32x4_t* yh = reinterpret_cast<u32x4_t*>(a.Yh) + ((size_t)(g >> 1) * 4 + (g & 1)) * NX + j;
-        yh[0] = h;
-        yh[2 * NX] = l;
+        const size_t NX = operand_image::rows(a.N);
+        oi_store(reinterpret_cast<u32x4_t*>(a.Yh) + operand_image::row(g, 0, j, NX), 0, NX, h, l);
     }
 }
 

@@ -81,14 +81,14 @@ conv_direct_cin1_x4_kernel(const DirectMulti dm)
     }
     // channels in groups of 8: a group of a column is one 16-byte row per part of the consumer's operand image (a.Yh)
     u32x4_t* yh = reinterpret_cast<u32x4_t*>(a.Yh);
-    const size_t NX = (size_t)a.N + 1;
+    const size_t NX = operand_image::rows(a.N);
     const int groups = yh ? 2 * as_kbx(a.M) : (a.M + 7) / 8;
     // `by` (of the problem's ny) takes a share of the channel groups: few columns (the 1-D towers: 7 column blocks) would otherwise leave the chip to
     // 7 workgroups walking 64 channels each (47 us for 1.6 MB of output)
     const int gpb = (groups + nyp - 1) / nyp, g_lo = by * gpb, g_hi = min(groups, g_lo + gpb);
     if (yh && bx == 0 && threadIdx.x == 0)
         for (int g = g_lo; g < g_hi; ++g)
-            for (int p = 0; p < 2; ++p) yh[((size_t)(g >> 1) * 4 + (g & 1) + 2 * p) * NX + a.N] = u32x4_t{0u, 0u, 0u, 0u};
+            for (int p = 0; p < 2; ++p) yh[operand_image::row(g, p, a.N, NX)] = u32x4_t{0u, 0u, 0u, 0u};
     for (int g = g_lo; g < g_hi; ++g) {
         float t8[4][8];
 #pragma unroll
@@ -126,15 +126,10 @@ conv_direct_cin1_x4_kernel(const DirectMulti dm)
             for (int c = 0; c < 4; ++c) t8[c][r] = (a.yh_lrelu && y[c] < 0.f) ? a.in_slope * y[c] : y[c];
         }
         if (yh) {
-            const size_t plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX + j0;
+            const size_t at = operand_image::row(g, 0, j0, NX);
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                if (j0 + 64 * c < a.N) {
-                    u32x4_t h, l;
-                    split2(t8[c], h, l);
-                    yh[plane + 64 * c] = h;
-                    yh[plane + 64 * c + 2 * NX] = l;
-                }
+                if (j0 + 64 * c < a.N) oi_store(yh, at + 64 * c, NX, t8[c]);
         }
     }
 }
@@ -216,25 +211,18 @@ splitk_reduce_multi_kernel(const ReduceMulti rm)
 // The mapping is adain_image_kernel's (conv_gemm_h3.hip): a WAVE owns one 16-byte row group of the image -- 8 channels (k-block kb,
 // k-half kh) of one utterance --, lane = column (i = lane + 64 j, j < 4), values in registers from the slab loads to the last store; the
 // slabs are summed in the plain reduction's order (s ascending), the value epilogue is the plain one (as_reduce_value) and the statistics
-// are adain_image_kernel's, so the image is bit-identical to reduce -> AdaIN as two launches.
+// follow common.h's order of additions, so the image is bit-identical to reduce -> AdaIN as two launches.
 // ----------------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ float rp_wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // NJ = register columns in use (utterance of <= 64 NJ columns): no condition inside the load loops
 template <int NJ>
 static __device__ __forceinline__ void reduce_adain_body(const ConvGemmArgs& a, int S, const AsAdainArgs& n, int kb, int kh, int u, int o0, int L)
 {
     const int lane = threadIdx.x & 63;
     const int M = a.M;
-    const size_t NX = (size_t)a.N + 1;
+    const size_t NX = operand_image::rows(a.N);
     u32x4_t* xs = reinterpret_cast<u32x4_t*>(n.yh);
     u32x4_t* yh = reinterpret_cast<u32x4_t*>(a.Yh);
-    const size_t plane = ((size_t)kb * 4 + kh) * NX;                    // h part; the l part two planes on
+    const size_t plane = operand_image::row_of(kb, 0, kh, 0, NX);       // h part; the l part two planes on
     const int c0 = kb * 16 + kh * 8;
     const int grp = a.n_groups > 1 ? o0 / a.group_cols : 0;             // (an utterance lies inside one weight group)
     const size_t gbase = n.gb_off ? (size_t)n.gb_off[u] : (size_t)u * n.ldgb;
@@ -317,13 +305,10 @@ static __device__ __forceinline__ void reduce_adain_body(const ConvGemmArgs& a, 
             for (int r = 0; r < 8; ++r) t[r] = (a.yh_lrelu && v[r][j] < 0.f) ? a.in_slope * v[r][j] : v[r][j];
             u32x4_t h, l;
             split2(t, h, l);
-            if (i < L) {
-                yh[plane + o0 + i] = h;
-                yh[plane + o0 + i + 2 * NX] = l;
-            }
+            if (i < L) oi_store(yh, plane + o0 + i, NX, h, l);
         }
     }
-    // AdaIN over the utterance (adain_image_kernel's arithmetic: a lane adds its elements in ascending order, then the wave's butterfly)
+    // AdaIN over the utterance (common.h: the order of additions)
     float mean[8], rstd[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -331,7 +316,7 @@ static __device__ __forceinline__ void reduce_adain_body(const ConvGemmArgs& a, 
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
             if (lane + 64 * j < L) sacc += v[r][j];
-        mean[r] = rp_wave_sum(sacc) / (float)L;
+        mean[r] = as_wave_sum(sacc) / (float)L;
     }
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -339,7 +324,7 @@ static __device__ __forceinline__ void reduce_adain_body(const ConvGemmArgs& a, 
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
             if (lane + 64 * j < L) { const float d = __fsub_rn(v[r][j], mean[r]); vacc = __fmaf_rn(d, d, vacc); }
-        rstd[r] = 1.0f / sqrtf(rp_wave_sum(vacc) / (float)L + 1e-5f);
+        rstd[r] = 1.0f / sqrtf(as_wave_sum(vacc) / (float)L + 1e-5f);
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -349,10 +334,7 @@ static __device__ __forceinline__ void reduce_adain_body(const ConvGemmArgs& a, 
         for (int r = 0; r < 8; ++r) t[r] = (c0 + r < M && i < L) ? as_adain_val(v[r][j], mean[r], rstd[r], g1[r], bt[r], n.lrelu) : 0.f;
         u32x4_t h, l;
         split2(t, h, l);
-        if (i < L) {
-            xs[plane + o0 + i] = h;
-            xs[plane + o0 + i + 2 * NX] = l;
-        }
+        if (i < L) oi_store(xs, plane + o0 + i, NX, h, l);
     }
 }
 
@@ -362,11 +344,12 @@ static __device__ __forceinline__ void reduce_adain(const ConvGemmArgs& a, int S
 {
     const int lane = threadIdx.x & 63;
     const int kb = rg >> 1, kh = rg & 1;
-    const size_t NX = (size_t)a.N + 1;
-    const size_t plane = ((size_t)kb * 4 + kh) * NX;
+    const size_t NX = operand_image::rows(a.N);
+    const size_t plane = operand_image::row_of(kb, 0, kh, 0, NX);
     if (u == 0 && lane == 0) {                                          // the zero columns
         u32x4_t* xs = reinterpret_cast<u32x4_t*>(n.yh);
         u32x4_t* yh = reinterpret_cast<u32x4_t*>(a.Yh);
+        // (by hand, = oi_zero_column(xs / yh, plane, a.N, NX): through it hipcc gives the fused reduction kernels other scalar registers)
         xs[plane + a.N] = u32x4_t{0u, 0u, 0u, 0u};
         xs[plane + 2 * NX + a.N] = u32x4_t{0u, 0u, 0u, 0u};
         if (yh) {
@@ -413,6 +396,7 @@ static __device__ __forceinline__ void reduce_ln(const ConvGemmArgs& a, int S, c
     const int g = threadIdx.x & 63;
     const int M = a.M, N = a.N;
     const int groups = 2 * as_kbx(M);                                    // row groups of the image (zero beyond M)
+    // (by hand: NX = operand_image::rows(N), plane = row(g, 0, 0, NX), oi_zero_column, oi_store at plane + j -- through any of them hipcc gives this kernel 88 VGPRs for 80)
     const size_t NX = (size_t)N + 1;
     u32x4_t* xs = reinterpret_cast<u32x4_t*>(n.yh);
     const size_t plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX;

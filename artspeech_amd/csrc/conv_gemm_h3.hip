@@ -141,9 +141,9 @@ static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.Wh) + (size_t)grp * w_bytes), 0, (int)w_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint16_t*>(a.Xh), 0, (int)((unsigned)KBx * 4u * NX * 16u), 0x00020000);
+        const_cast<uint16_t*>(a.Xh), 0, (int)operand_image::desc_bytes_kb(KBx, NX), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsX2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint16_t*>(KB2 ? a.Xh2 : a.Xh), 0, (int)((unsigned)KBx2 * 4u * NX * 16u), 0x00020000);
+        const_cast<uint16_t*>(KB2 ? a.Xh2 : a.Xh), 0, (int)operand_image::desc_bytes_kb(KBx2, NX), 0x00020000);
 
     (void)rsW;
     (void)rsX;      // (the host pass does not see the LDS-DMA builtins that use them)
@@ -156,7 +156,7 @@ static __device__ __forceinline__ void h3_tile(const H3Prob& prob, unsigned char
         const int c = tid + NT * i, kblk = c / (QP * BM), rem = c % (QP * BM), pk = rem / BM, row = rem % BM;
         a_voff[i] = (m0 + row) < a.M ? (unsigned)(((kblk * 4 + pk) * a.M + m0 + row) * 16) : OOB;
     }
-    unsigned b_plane[BCH];                                               // (kblk*4 + pk) * NX * 16: plane of chunk i
+    unsigned b_plane[BCH];                                               // (kblk*4 + pk) * NX * 16: plane of chunk i (operand_image.h: plane_of)
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
         const int c = tid + NT * i, kblk = c / (QP * BN), pk = (c % (QP * BN)) / BN;
@@ -442,7 +442,7 @@ int as_conv_gemm_h3_launch(const ConvGemmArgs* const* a, const int* S, int n, in
     if (n < 1 || n > H3_MAXP) return AS_EINVAL;
     for (int i = 0; i < n; ++i) {
         if (a[i]->n_prod != a[0]->n_prod || S[i] < 1) return AS_EINVAL;
-        if ((double)as_kbx(a[i]->K) * 4.0 * ((a[i]->src_col ? a[i]->N_in : a[i]->N) + 1.0) * 16.0 >= 2147483648.0) return AS_EINVAL;   // 32-bit offsets in the descriptor
+        if (operand_image::bytes(a[i]->K, a[i]->src_col ? a[i]->N_in : a[i]->N) >= ((size_t)1 << 31)) return AS_EINVAL;   // 32-bit offsets in the descriptor
     }
     switch (choice) {
     case 2:                                                             // 32 x 128 (a wave owns 32 x 64): the vocoder's 32-channel stage, M <= 32
@@ -460,8 +460,7 @@ int as_conv_gemm_h3_launch(const ConvGemmArgs* const* a, const int* S, int n, in
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// X fp32 [K][ldx] -> Xh[(K/16 up to a multiple of 4)][p*2 + kh][N + 1][8] fp16, x = h + l; optional LeakyReLU first;
-// column N and rows >= K are zero.
+// X fp32 [K][ldx] -> its split operand image (operand_image.h); optional LeakyReLU first.
 // A thread owns 8 consecutive k of 4 columns -- lane, lane + 64, lane + 128, lane + 192 of its wave's 256: every load is 256
 // contiguous bytes of a row and every store 1 KB of an image row (with four CONSECUTIVE columns per lane a store put 16 bytes every 64:
 // 32 quarter-filled lines per instruction).  Range-checked buffer loads: offsets of rows >= K fall outside the descriptor (zero).
@@ -484,8 +483,8 @@ split_f16x2_kernel(const float* __restrict__ x, int ldx, int K, int N, const int
 #pragma unroll
         for (int c = 0; c < 4; ++c) v[r][c] = buf_load1(rs, (k < K && col + 64 * c < nv) ? (unsigned)(k * ldx + col + 64 * c) * 4u : OOB, 0);
     }
-    const size_t NX = (size_t)N + 1;
-    const size_t base = ((size_t)(g >> 1) * 4 + (g & 1)) * NX + col;    // plane p*2 + kh of k-block kb
+    const size_t NX = operand_image::rows(N);
+    const size_t base = operand_image::row(g, 0, col, NX);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         if (col + 64 * c > N) break;                                    // (column N itself is written: the zero column)
@@ -497,10 +496,7 @@ split_f16x2_kernel(const float* __restrict__ x, int ldx, int K, int N, const int
             if (lrelu) e = e > 0.f ? e : slope * e;
             t[r] = e;
         }
-        u32x4_t h, l;
-        split2(t, h, l);
-        xh[base + 64 * c] = h;
-        xh[base + 64 * c + 2 * NX] = l;
+        oi_store(xh, base + 64 * c, NX, t);
     }
 }
 
@@ -591,27 +587,18 @@ extern "C" int as_prep_weight_f16x2_host(const float* w, int G, int Cout, int Ci
 
 // ----------------------------------------------------------------------------------------------------------------
 // AdaIN + LeakyReLU written DIRECTLY as the split image (the output of models.py:189-197's norm -> actv feeds nothing but
-// the following conv, so the fp32 activations never exist): per-(channel, utterance) statistics exactly as
-// adain_kernel (elementwise.hip) computes them -- one wave per channel, the same summation order -- then a thread takes
-// 8 channels of one column, normalises, applies LeakyReLU(0.2), splits and stores three 16-byte rows.
+// the following conv, so the fp32 activations never exist): per-(channel, utterance) statistics in adain_kernel's order of additions
+// (common.h), then a thread takes 8 channels of one column, normalises, applies LeakyReLU(0.2), splits and stores its rows.
 // Workgroup = (8-channel group = one (k-block, k-half) of the image, utterance).
 // ----------------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ float h3_wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // AsAdainArgs addressing (include/artspeech_hip.h): gamma(u, c) = gb[gb_off[u] + c * gb_sc] (gb_off NULL: u * ldgb), beta at channel
 // C + c; utterance u reads its input at columns src_off[u].. (NULL: col_off[u]) and writes at col_off[u].. -- at 2 col_off[u]
 // with the fused depthwise ConvTranspose1d(k3, s2, p1, op1) x2 up-sampler (models.py:172,195): out[2i] = a[i] w1 + b,
 // out[2i+1] = a[i] w2 + a[i+1] w0 + b, and x_up (fp32) gets the nearest x2 copy of x (the block's shortcut, models.py:184).
 //
 // A WAVE owns one 16-byte row group of the image -- 8 consecutive channels (k-block kb, k-half kh) of one utterance -- from the first
-// load to the last store: lane = column (i = lane + 64 j), the 8 x RV values stay in registers through the two statistics passes
-// (summation order of adain_kernel: a lane adds its elements in ascending order, then the wave's butterfly), the normalisation and
-// the split, so the input is read ONCE, nothing goes through LDS and there is no barrier (the round-1 / early round-2 kernel computed
+// load to the last store: lane = column (i = lane + 64 j), the 8 x RV values stay in registers through the two statistics passes, the
+// normalisation and the split, so the input is read ONCE, nothing goes through LDS and there is no barrier (the round-1 / early round-2 kernel computed
 // the statistics per wave of four channels, parked them in LDS and re-read x from L2 for the second pass: 15-25 us per launch).  The
 // up-sampler's a[i+1] is the next lane's value (lane 63: lane 0 of the next register).  Utterances longer than 64 RV frames take
 // the same mapping with loops over global memory (three passes).  Workgroup = 4 waves = two k-blocks of one utterance.
@@ -623,13 +610,10 @@ adain_image_kernel(const AsAdainArgs a)
     const int kb = blockIdx.x * 2 + (wave >> 1), kh = wave & 1, u = blockIdx.y;
     const int C = a.C;
     if (kb >= as_kbx(C)) return;
-    const size_t NX = (size_t)a.N + 1;
+    const size_t NX = operand_image::rows(a.N);
     u32x4_t* xs = reinterpret_cast<u32x4_t*>(a.yh);
-    const size_t plane = ((size_t)kb * 4 + kh) * NX;                    // h part; the l part two planes on
-    if (u == 0 && lane == 0) {                                          // the zero column
-        xs[plane + a.N] = u32x4_t{0u, 0u, 0u, 0u};
-        xs[plane + 2 * NX + a.N] = u32x4_t{0u, 0u, 0u, 0u};
-    }
+    const size_t plane = operand_image::row_of(kb, 0, kh, 0, NX);       // h part; the l part two planes on
+    if (u == 0 && lane == 0) oi_zero_column(xs, plane, a.N, NX);
     const int o0 = a.col_off[u], L = a.col_w ? a.col_w[u] : a.col_off[u + 1] - o0;
     if (L <= 0) return;
     const int s0 = a.src_off ? a.src_off[u] : o0;
@@ -664,15 +648,15 @@ adain_image_kernel(const AsAdainArgs a)
 #pragma unroll
             for (int j = 0; j < RV; ++j)
                 if (lane + 64 * j < L) sacc += v[r][j];
-            mean[r] = h3_wave_sum(sacc) / (float)L;
+            mean[r] = as_wave_sum(sacc) / (float)L;
         }
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             float vacc = 0.f;
 #pragma unroll
             for (int j = 0; j < RV; ++j)
-                if (lane + 64 * j < L) { const float d = __fsub_rn(v[r][j], mean[r]); vacc = __fmaf_rn(d, d, vacc); }   // (explicit: the same bits in every kernel that computes these statistics)
-            rstd[r] = 1.0f / sqrtf(h3_wave_sum(vacc) / (float)L + 1e-5f);
+                if (lane + 64 * j < L) { const float d = __fsub_rn(v[r][j], mean[r]); vacc = __fmaf_rn(d, d, vacc); }
+            rstd[r] = 1.0f / sqrtf(as_wave_sum(vacc) / (float)L + 1e-5f);
         }
         if (UP && a.x_up) {
 #pragma unroll
@@ -702,10 +686,7 @@ adain_image_kernel(const AsAdainArgs a)
                 for (int r = 0; r < 8; ++r) t[r] = v[r][j];
                 u32x4_t h, l;
                 split2(t, h, l);
-                if (i < L) {
-                    xs[at0 + i] = h;
-                    xs[at0 + i + 2 * NX] = l;
-                }
+                if (i < L) oi_store(xs, at0 + i, NX, h, l);
             } else {
                 float e0[8], e1[8];
 #pragma unroll
@@ -722,10 +703,8 @@ adain_image_kernel(const AsAdainArgs a)
                 split2(e0, h, l);
                 split2(e1, h2, l2);
                 if (i < L) {
-                    xs[at0 + 2 * i] = h;
-                    xs[at0 + 2 * i + 2 * NX] = l;
-                    xs[at0 + 2 * i + 1] = h2;
-                    xs[at0 + 2 * i + 1 + 2 * NX] = l2;
+                    oi_store(xs, at0 + 2 * i, NX, h, l);
+                    oi_store(xs, at0 + 2 * i + 1, NX, h2, l2);
                 }
             }
         }
@@ -740,7 +719,7 @@ adain_image_kernel(const AsAdainArgs a)
         float acc[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) acc[r] = 0.f;
-        // the eight channels side by side, four columns per trip: 32 loads in flight (a channel's elements still add up in ascending order)
+        // the eight channels side by side, four columns per trip: 32 loads in flight (the order of additions: common.h)
         int i = lane;
         for (; i + 192 < L; i += 256) {
             float t[4][8];
@@ -757,7 +736,7 @@ adain_image_kernel(const AsAdainArgs a)
 #pragma unroll
             for (int r = 0; r < 8; ++r) acc[r] += xr0[rowoff[r] + i];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) { mean[r] = h3_wave_sum(acc[r]) / (float)L; acc[r] = 0.f; }
+        for (int r = 0; r < 8; ++r) { mean[r] = as_wave_sum(acc[r]) / (float)L; acc[r] = 0.f; }
         i = lane;
         for (; i + 192 < L; i += 256) {
             float t[4][8];
@@ -774,7 +753,7 @@ adain_image_kernel(const AsAdainArgs a)
 #pragma unroll
             for (int r = 0; r < 8; ++r) { const float d = __fsub_rn(xr0[rowoff[r] + i], mean[r]); acc[r] = __fmaf_rn(d, d, acc[r]); }
 #pragma unroll
-        for (int r = 0; r < 8; ++r) rstd[r] = 1.0f / sqrtf(h3_wave_sum(acc[r]) / (float)L + 1e-5f);
+        for (int r = 0; r < 8; ++r) rstd[r] = 1.0f / sqrtf(as_wave_sum(acc[r]) / (float)L + 1e-5f);
     }
     // third pass: two columns per trip (i and i + 64), every load before the first use
     for (int i0 = lane; i0 < L; i0 += 128) {
@@ -808,8 +787,7 @@ adain_image_kernel(const AsAdainArgs a)
             u32x4_t h, l;
             if (!UP) {
                 split2(a0, h, l);
-                xs[at0 + i] = h;
-                xs[at0 + i + 2 * NX] = l;
+                oi_store(xs, at0 + i, NX, h, l);
             } else {
                 float e0[8], e1[8];
 #pragma unroll
@@ -818,11 +796,9 @@ adain_image_kernel(const AsAdainArgs a)
                     if (c0 + r >= C) { e0[r] = 0.f; e1[r] = 0.f; }
                 }
                 split2(e0, h, l);
-                xs[at0 + 2 * i] = h;
-                xs[at0 + 2 * i + 2 * NX] = l;
+                oi_store(xs, at0 + 2 * i, NX, h, l);
                 split2(e1, h, l);
-                xs[at0 + 2 * i + 1] = h;
-                xs[at0 + 2 * i + 1 + 2 * NX] = l;
+                oi_store(xs, at0 + 2 * i + 1, NX, h, l);
             }
         }
     }
@@ -866,9 +842,8 @@ rows_image_kernel(const float* __restrict__ x, int ldx, int K, int B, u32x4_t* _
     for (int r = 0; r < 8; ++r) t[r] = (b < B && g * 8 + r < K) ? x[(size_t)b * ldx + g * 8 + r] : 0.f;
     u32x4_t h, l;
     split2(t, h, l);
-    const size_t at = ((size_t)(g >> 1) * 4 + (g & 1)) * (B + 1) + b;
-    xh[at] = h;
-    xh[at + 2 * (size_t)(B + 1)] = l;
+    const size_t NX = operand_image::rows(B);
+    oi_store(xh, operand_image::row(g, 0, b, NX), NX, h, l);
 }
 
 extern "C" int as_rows_image_f32(const float* x, int ldx, int K, int B, uint16_t* xh, as_stream_t stream)
@@ -936,13 +911,13 @@ channel_ln_split_kernel(const float* __restrict__ x, int ldx, int C, int N, cons
 #pragma unroll
     for (int q = 0; q < LNS_PARTS; ++q) tot += red[q][col];
     const float rs = 1.0f / sqrtf(tot / (float)C + eps);
-    const size_t NX = (size_t)N + 1;
+    const size_t NX = operand_image::rows(N);
     if (blockIdx.x == 0 && col == 0) {                                   // the zero column N of every plane this thread's groups own
 #pragma unroll
         for (int i = 0; i < LNS_MAXG; ++i) {
             const int g = part + i * LNS_PARTS;
             if (g < ngroups)
-                for (int p = 0; p < 2; ++p) xs[((size_t)(g >> 1) * 4 + (g & 1) + 2 * p) * NX + N] = u32x4_t{0u, 0u, 0u, 0u};
+                for (int p = 0; p < 2; ++p) xs[operand_image::row(g, p, N, NX)] = u32x4_t{0u, 0u, 0u, 0u};
         }
     }
     if (!ok) return;
@@ -963,9 +938,7 @@ channel_ln_split_kernel(const float* __restrict__ x, int ldx, int C, int N, cons
         }
         u32x4_t h, l;
         split2(t, h, l);
-        const size_t at = ((size_t)(g >> 1) * 4 + (g & 1)) * NX + j;
-        xs[at] = h;
-        xs[at + 2 * NX] = l;
+        oi_store(xs, operand_image::row(g, 0, j, NX), NX, h, l);
     }
 }
 

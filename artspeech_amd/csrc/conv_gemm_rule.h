@@ -46,6 +46,7 @@
 //     split image.  workspace_set: never less, and for an output of <= 4 MB read from an image up to 16 slabs, each slice >= 384 k.
 #pragma once
 #include "artspeech_hip.h"
+#include "operand_image.h"
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -91,8 +92,8 @@ struct Plan {
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-constexpr int kbx(int K) { return (((K + 15) >> 4) + 3) & ~3; }        // k-blocks of a split image: a multiple of 4 (constexpr: kernels call it too)
-inline size_t split_f16x2_bytes(int K, int N) { return K <= 0 || N <= 0 ? 0 : (size_t)kbx(K) * 4 * ((size_t)N + 1) * 16; }
+constexpr int kbx(int K) { return operand_image::kbx(K); }             // the split image's k-blocks and size: operand_image.h
+inline size_t split_f16x2_bytes(int K, int N) { return operand_image::bytes(K, N); }
 inline size_t slab_bytes(const Shape& s) { return (size_t)s.M * s.N * sizeof(float); }
 inline bool sized(const Shape& s) { return s.M > 0 && s.N > 0 && s.Kp > 0 && s.T > 0; }
 // M output channels fill a 128-row tile well enough to use one (it is not half empty)

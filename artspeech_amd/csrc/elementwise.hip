@@ -11,13 +11,6 @@
 #include <type_traits>
 #define AS_FILE_CLS AS_CLS_OTHER
 
-static __device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 static __device__ __forceinline__ float lrelu02(float v) { return v > 0.f ? v : 0.2f * v; }
 
 // ---------------------------------------------------------------------------------------------------
@@ -201,10 +194,10 @@ adain_kernel(const float* __restrict__ x, int ldx, int C, const float* __restric
     const float* xr = x + (size_t)c * ldx + o0;
     float s = 0.f;
     for (int i = lane; i < L; i += 64) s += xr[i];
-    const float mean = wave_sum(s) / (float)L;
+    const float mean = as_wave_sum(s) / (float)L;
     float v = 0.f;
-    for (int i = lane; i < L; i += 64) { const float d = __fsub_rn(xr[i], mean); v = __fmaf_rn(d, d, v); }   // (explicit: as adain_image_kernel)
-    const float var = wave_sum(v) / (float)L;
+    for (int i = lane; i < L; i += 64) { const float d = __fsub_rn(xr[i], mean); v = __fmaf_rn(d, d, v); }   // (the order of additions: common.h)
+    const float var = as_wave_sum(v) / (float)L;
     const float rs = 1.0f / sqrtf(var + 1e-5f);
     const float g = 1.0f + gb[(size_t)b * ldgb + c];
     const float be = gb[(size_t)b * ldgb + C + c];
@@ -291,7 +284,7 @@ linear_rows_kernel(const float* __restrict__ x, int ldx, const float* __restrict
                 float s = 0.f;
 #pragma unroll
                 for (int c = 0; c < KR; ++c) s += wq[c].x * v[r][c].x + wq[c].y * v[r][c].y + wq[c].z * v[r][c].z + wq[c].w * v[r][c].w;
-                s = wave_sum(s);
+                s = as_wave_sum(s);
                 if (lane == 0 && b0 + r < B) y[(size_t)(b0 + r) * ldy + m] = s + bm;
             }
         }
@@ -301,7 +294,7 @@ linear_rows_kernel(const float* __restrict__ x, int ldx, const float* __restrict
         const float* xr = x + (size_t)b * ldx;
         float s = 0.f;
         for (int k = lane; k < K; k += 64) s += wr[k] * xr[k];
-        s = wave_sum(s);
+        s = as_wave_sum(s);
         if (lane == 0) y[(size_t)b * ldy + m] = s + bm;
     }
 }
@@ -471,10 +464,10 @@ pointwise_small_kernel(const float* __restrict__ x, int ldx, int K, int N, const
         if (ok && y2) y2[(size_t)m * ld2 + j] = acc;
     }
     u32x4_t h, l;
-    split2(v, h, l);
-    const size_t NX = (size_t)N + 1, at = ((size_t)(g >> 1) * 4 + (g & 1)) * NX + j;
-    if (h1) { h1[at] = h; h1[at + 2 * NX] = l; }
-    if (h2) { h2[at] = h; h2[at + 2 * NX] = l; }
+    split2(v, h, l);                                                    // (once, for both images)
+    const size_t NX = operand_image::rows(N), at = operand_image::row(g, 0, j, NX);
+    if (h1) oi_store(h1, at, NX, h, l);
+    if (h2) oi_store(h2, at, NX, h, l);
 }
 
 extern "C" int as_pointwise_small_f32(const float* x, int ldx, int K, int N, const float* w, const float* bias, int M, float* y1, int ld1,
@@ -815,7 +808,7 @@ struct DownWalk {
 // the zero column of the image's two row groups of channel group g (column Nout), once per problem
 static __device__ __forceinline__ void down_zero_column(u32x4_t* __restrict__ yh, size_t plane, size_t NX, int Nout, int b, int strip)
 {
-    if (yh && b == 0 && strip == 0 && threadIdx.x < 2) yh[plane + (size_t)threadIdx.x * 2 * NX + Nout] = u32x4_t{0u, 0u, 0u, 0u};
+    if (yh && b == 0 && strip == 0 && threadIdx.x < 2) oi_zero_column(yh, plane, (size_t)threadIdx.x, Nout, NX);   // (a thread per part)
 }
 
 // The walk of a wave over its strip as a pipeline of half-sets of four channels, shared by the depthwise conv and the average pool:
@@ -890,7 +883,7 @@ static __device__ __forceinline__ void dwconv_down_body(const AsDownArgs& a, int
     const int sh = KH == 3 ? 2 : 1, ph = KH == 3 ? 1 : 0;
     const int c0 = g * 8;
     const int Wi = a.in_w[b], Wo = a.out_w[b];
-    const size_t NX = (size_t)Nout + 1, plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX;
+    const size_t NX = operand_image::rows(Nout), plane = operand_image::row(g, 0, 0, NX);
     down_zero_column(yh, plane, NX, Nout, b, strip);
     if (Wo <= 0) return;                                                // (uniform: before the barrier)
     if (threadIdx.x < 8 * (KH * 3 + 1)) {
@@ -978,9 +971,7 @@ static __device__ __forceinline__ void dwconv_down_body(const AsDownArgs& a, int
         if (yh && live) {
             u32x4_t h, l;
             split2(t, h, l);
-            const size_t at = plane + ob + p.i;
-            yh[at] = h;
-            yh[at + 2 * NX] = l;
+            oi_store(yh, plane + ob + p.i, NX, h, l);
         }
     };
     const auto walk = [&](auto one_col) __attribute__((always_inline)) {
@@ -1044,7 +1035,7 @@ static __device__ __forceinline__ void avgpool_down_body(const AsDownArgs& a, in
     u32x4_t* __restrict__ yh = reinterpret_cast<u32x4_t*>(a.yh);
     const int c0 = g * 8;
     const int Wi = a.in_w[b], Wo = a.out_w[b], ib = a.in_off[b], ob = a.out_off[b];
-    const size_t NX = (size_t)Nout + 1, plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX;
+    const size_t NX = operand_image::rows(Nout), plane = operand_image::row(g, 0, 0, NX);
     down_zero_column(yh, plane, NX, Nout, b, strip);
     if (Wo <= 0) return;
     const int r0 = strip * rows, r1 = min(Hout, r0 + rows);
@@ -1103,9 +1094,7 @@ static __device__ __forceinline__ void avgpool_down_body(const AsDownArgs& a, in
         if (yh && live) {
             u32x4_t h, l;
             split2(t, h, l);
-            const size_t at = plane + ob + p.i;
-            yh[at] = h;
-            yh[at + 2 * NX] = l;
+            oi_store(yh, plane + ob + p.i, NX, h, l);
         }
     };
     // (walks of their own for images of one column, as dwconv_down_body, and for the residual: no branch around its loads)
@@ -1175,7 +1164,7 @@ static __device__ __forceinline__ void stem_pool_image_body(const AsDownArgs& a,
     u32x4_t* __restrict__ yh = reinterpret_cast<u32x4_t*>(a.yh);
     const int c0 = g * 8;
     const int Wi = a.in_w[b], Wo = a.out_w[b];
-    const size_t NX = (size_t)Nout + 1, plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX;
+    const size_t NX = operand_image::rows(Nout), plane = operand_image::row(g, 0, 0, NX);
     down_zero_column(yh, plane, NX, Nout, b, strip);
     if (Wo <= 0) return;                                                // (uniform: before the barrier)
     if (threadIdx.x < 80) {
@@ -1252,9 +1241,7 @@ static __device__ __forceinline__ void stem_pool_image_body(const AsDownArgs& a,
         if (live) {
             u32x4_t h, l;
             split2(t, h, l);
-            const size_t at = plane + ob + p.i;
-            yh[at] = h;
-            yh[at + 2 * NX] = l;
+            oi_store(yh, plane + ob + p.i, NX, h, l);
         }
     };
     int n = wk.trips(r0);
@@ -1416,8 +1403,8 @@ im2col_valid_image_kernel(const float* __restrict__ x, int ldx, const int* __res
 {
     const int g = blockIdx.x;
     const int total = out_off[B];
-    const size_t NX = (size_t)total + 1, plane = ((size_t)(g >> 1) * 4 + (g & 1)) * NX;
-    if (threadIdx.x < 2) yh[plane + (size_t)threadIdx.x * 2 * NX + total] = u32x4_t{0u, 0u, 0u, 0u};
+    const size_t NX = operand_image::rows(total), plane = operand_image::row(g, 0, 0, NX);
+    if (threadIdx.x < 2) oi_zero_column(yh, plane, (size_t)threadIdx.x, total, NX);   // (a thread per part)
     for (int j = threadIdx.x; j < total; j += blockDim.x) {
         int b = 0;
         while (b + 1 < B && out_off[b + 1] <= j) ++b;
@@ -1435,10 +1422,7 @@ im2col_valid_image_kernel(const float* __restrict__ x, int ldx, const int* __res
             }
             t[r] = v;
         }
-        u32x4_t h, l;
-        split2(t, h, l);
-        yh[plane + j] = h;
-        yh[plane + j + 2 * NX] = l;
+        oi_store(yh, plane + j, NX, t);
     }
 }
 
@@ -1471,7 +1455,7 @@ mean_pool_kernel(const float* __restrict__ x, int ldx, const int* __restrict__ c
         if (act) v = lrelu02(v);
         s += v;
     }
-    s = wave_sum(s);
+    s = as_wave_sum(s);
     if (lane == 0) y[(size_t)b * ldy + c] = s / (float)L;
 }
 

@@ -417,8 +417,7 @@ lanes_sum_kernel(const uint32_t* __restrict__ p, long n, long ld, unsigned long 
     const long r = blockIdx.y;
     unsigned long long v = 0;
     if (j < n) v = (unsigned long long)p[r * ld + j] * (2ull * (unsigned long long)(r * n + j) + 1ull + salt);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = as_wave_sum(v);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);          // (a sum: the order of the additions does not matter)
 }
 

@@ -888,16 +888,14 @@ softmax_last_kernel(const float* __restrict__ x, int Ty, float* __restrict__ y)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float m = -INFINITY;
     for (int i = threadIdx.x; i < Ty; i += 256) m = fmaxf(m, xr[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = as_wave_max(m);
     if (lane == 0) red[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     __syncthreads();
     float s = 0.f;
     for (int i = threadIdx.x; i < Ty; i += 256) s += expf(xr[i] - m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    s = as_wave_sum(s);
     if (lane == 0) red[wave] = s;
     __syncthreads();
     s = (red[0] + red[1]) + (red[2] + red[3]);

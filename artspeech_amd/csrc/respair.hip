@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
     if constexpr (WLDS) dma(0);
     // offset of fragment q inside a granule.  C = 32: q = (k-block, part); C = 64: q = (32-row block, part)
     auto frag_off = [&](int q) {
-        return C == 32 ? (unsigned)((((q >> 1) * 4 + (q & 1) * 2 + lk) * 32 + l31) * 16)
+        return C == 32 ? (unsigned)((operand_image::plane_of(q >> 1, q & 1, lk) * 32 + l31) * 16)
                        : (unsigned)((((q & 1) * 2 + lk) * C + (q >> 1) * 32 + l31) * 16);
     };
     auto lda = [&](f16x8 (&w)[4], const __amdgpu_buffer_rsrc_t& rs, int g) {
@@ -145,9 +145,9 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
                     for (int e = 0; e < 8; ++e) v[i][e] = v[i][e] > 0.f ? v[i][e] : a.slope * v[i][e];
                     u32x4_t h, l;
                     split2(v[i], h, l);
-                    const int pl = (g >> 1) * 4 + (g & 1);
-                    *reinterpret_cast<u32x4_t*>(tile + ((size_t)pl * XW + c) * 16) = h;
-                    *reinterpret_cast<u32x4_t*>(tile + ((size_t)(pl + 2) * XW + c) * 16) = l;
+                    // (the image's plane order, XW columns to a plane)
+                    *reinterpret_cast<u32x4_t*>(tile + ((size_t)operand_image::plane(g, 0) * XW + c) * 16) = h;
+                    *reinterpret_cast<u32x4_t*>(tile + ((size_t)operand_image::plane(g, 1) * XW + c) * 16) = l;
                 }
             }
         }
@@ -268,9 +268,8 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
                     u32x4_t h, l;
                     split2(t, h, l);
                     const int g = m * 4 + 2 * pr + lk;                   // 8-row group: k-block g / 2, k-half g % 2
-                    const int pl = (g >> 1) * 4 + (g & 1);
-                    *reinterpret_cast<u32x4_t*>(tile + (pl * RP_MWP + mc) * 16) = h;
-                    *reinterpret_cast<u32x4_t*>(tile + ((pl + 2) * RP_MWP + mc) * 16) = l;
+                    *reinterpret_cast<u32x4_t*>(tile + (operand_image::plane(g, 0) * RP_MWP + mc) * 16) = h;
+                    *reinterpret_cast<u32x4_t*>(tile + (operand_image::plane(g, 1) * RP_MWP + mc) * 16) = l;
                 }
             }
         }
@@ -289,7 +288,7 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
         const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.b2), 0, a.b2 ? C * 4 : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y ? (int)((unsigned)C * a.ldy * 4u) : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(
-            a.yh, 0, a.yh ? (int)(4u * 4u * ((unsigned)a.N + 1u) * 16u) : 0, 0x00020000);
+            a.yh, 0, a.yh ? (int)operand_image::desc_bytes(C, operand_image::rows32(a.N)) : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float*>(a.add1), 0, a.add1 ? (int)((unsigned)C * a.ld_add * 4u) : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc(
@@ -336,7 +335,7 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
                                                               yo + (unsigned)(((e & 3) + 8 * (e >> 2)) * a.ldy) * 4u, 0, 0);
                 }
                 if (a.yh) {                                              // LeakyReLU(y) as the next conv's operand image (conv_gemm.h yh_store_tile)
-                    const unsigned NXy = (unsigned)a.N + 1u;
+                    const unsigned NXy = operand_image::rows32(a.N);
                     const u32x4_t z = {0u, 0u, 0u, 0u};
 #pragma unroll
                     for (int pr = 0; pr < 2; ++pr) {
@@ -353,21 +352,19 @@ __global__ void __launch_bounds__(64 * NW, C == 32 && NW == 4 ? 4 : (C == 32 ? 2
                         u32x4_t h, l;
                         split2(t, h, l);
                         const int g = m * 4 + 2 * pr + lk;
-                        const unsigned pl = (unsigned)((g >> 1) * 4 + (g & 1));
-                        const unsigned off = ok ? (pl * NXy + (unsigned)col) * 16u : OOBH;
-                        __builtin_amdgcn_raw_buffer_store_b128(h, rsH, off, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b128(l, rsH, off + 2u * NXy * 16u, 0, 0);
+                        const int pl = operand_image::plane(g);
+                        const unsigned off = ok ? operand_image::byte_off(pl, col, NXy) : OOBH;
+                        oi_store_buf(rsH, off, NXy, h, l);
                         if (C == 32) {                                   // k-blocks 2, 3 of the image (as_kbx(32) = 4) are zero rows
-                            __builtin_amdgcn_raw_buffer_store_b128(z, rsH, off + 8u * NXy * 16u, 0, 0);
-                            __builtin_amdgcn_raw_buffer_store_b128(z, rsH, off + 10u * NXy * 16u, 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b128(z, rsH, off + operand_image::byte_off(operand_image::plane(4, 0), 0, NXy), 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b128(z, rsH, off + operand_image::byte_off(operand_image::plane(4, 1), 0, NXy), 0, 0);
                         }
                         if (ok && col == 0) {                            // the zero column N, once per (group, part)
-                            const unsigned offz = (pl * NXy + (unsigned)a.N) * 16u;
-                            __builtin_amdgcn_raw_buffer_store_b128(z, rsH, offz, 0, 0);
-                            __builtin_amdgcn_raw_buffer_store_b128(z, rsH, offz + 2u * NXy * 16u, 0, 0);
+                            const unsigned offz = operand_image::byte_off(pl, a.N, NXy);
+                            oi_store_buf(rsH, offz, NXy, z, z);
                             if (C == 32) {
-                                __builtin_amdgcn_raw_buffer_store_b128(z, rsH, offz + 8u * NXy * 16u, 0, 0);
-                                __builtin_amdgcn_raw_buffer_store_b128(z, rsH, offz + 10u * NXy * 16u, 0, 0);
+                                __builtin_amdgcn_raw_buffer_store_b128(z, rsH, offz + operand_image::byte_off(operand_image::plane(4, 0), 0, NXy), 0, 0);
+                                __builtin_amdgcn_raw_buffer_store_b128(z, rsH, offz + operand_image::byte_off(operand_image::plane(4, 1), 0, NXy), 0, 0);
                             }
                         }
                     }

@@ -222,8 +222,8 @@ mean3_image_kernel(const float* __restrict__ a, const float* __restrict__ b, con
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a), 0, bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b), 0, bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(c), 0, bytes, 0x00020000);
-    const size_t NX = (size_t)N + 1;
-    const size_t base = ((size_t)(g >> 1) * 4 + (g & 1)) * NX + col;    // plane p*2 + kh of k-block kb
+    const size_t NX = operand_image::rows(N);
+    const size_t base = operand_image::row(g, 0, col, NX);
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc) {
         if (col + 64 * cc > N) break;                                   // (column N itself is written: the zero column)
@@ -236,10 +236,7 @@ mean3_image_kernel(const float* __restrict__ a, const float* __restrict__ b, con
             const float e = ((buf_load1(ra, off, 0) + buf_load1(rb, off, 0)) + buf_load1(rc, off, 0)) / 3.0f;
             t[r] = e > 0.f ? e : slope * e;
         }
-        u32x4_t h, l;
-        split2(t, h, l);
-        xh[base + 64 * cc] = h;
-        xh[base + 64 * cc + 2 * NX] = l;
+        oi_store(xh, base + 64 * cc, NX, t);
     }
 }
 

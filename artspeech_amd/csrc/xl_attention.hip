@@ -55,19 +55,19 @@ __global__ void __launch_bounds__(256) xl_attention_mfma_kernel(const XlArgs a)
     const int i0 = 31 * ((int)blockIdx.x * 4 + wave);
     if (a.oh && b == 0 && blockIdx.x == 0 && wave == 0 && lane < 16) {  // the image's zero column: this head's 4 k-blocks x 4 planes,
         const size_t pz = (size_t)(h * 16 + lane);                        // written before any wave leaves (utterance 0 may be empty)
-        reinterpret_cast<u32x4_t*>(a.oh)[pz * ((size_t)a.N + 1) + a.N] = u32x4_t{0u, 0u, 0u, 0u};
+        reinterpret_cast<u32x4_t*>(a.oh)[operand_image::plane_row(pz, a.N, operand_image::rows(a.N))] = u32x4_t{0u, 0u, 0u, 0u};
     }
     if (i0 >= T) return;                                                 // (no barrier below: a wave leaves alone)
     float* sc = xsm + wave * (64 * 32);                                  // this wave's shift scratch [64][32]
-    const unsigned NX = (unsigned)a.N + 1u;                              // columns of an image plane (the last one is zero)
+    const unsigned NX = operand_image::rows32(a.N);                      // rows of an image plane (the last one is the zero column)
     const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint16_t*>(a.qh), 0, (int)((unsigned)as_kbx(4 * a.C) * 4u * NX * 16u), 0x00020000);
+        const_cast<uint16_t*>(a.qh), 0, (int)operand_image::desc_bytes(4 * a.C, NX), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint16_t*>(a.ph), 0, (int)((unsigned)as_kbx(a.C) * 4u * NX * 16u), 0x00020000);
+        const_cast<uint16_t*>(a.ph), 0, (int)operand_image::desc_bytes(a.C, NX), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(a.qkv), 0, (int)((unsigned)(4 * a.C) * a.ld * 4u), 0x00020000);
     // image offset of (k-block kb of a 64-channel group starting at channel c0, part p, this lane's k-half, column col)
-    auto img = [&](int c0, int kb, int p, unsigned col) { return ((unsigned)(((c0 >> 4) + kb) * 4 + p * 2 + lk) * NX + col) * 16u; };
+    auto img = [&](int c0, int kb, int p, unsigned col) { return operand_image::byte_off(operand_image::plane_of((c0 >> 4) + kb, p, lk), col, NX); };
     const unsigned zc = (unsigned)a.N;                                   // the zero column
 
     // the wave's queries as B operands: columns i0 + l31 of the rows q + u (content) and q + v (positions)
@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(256) xl_attention_mfma_kernel(const XlArgs a)
     }
     if (a.oh) {                                                          // 16-byte rows of 8 consecutive channels (conv_gemm.h yh_store_tile)
         const __amdgpu_buffer_rsrc_t rsO =
-            __builtin_amdgcn_make_buffer_rsrc(a.oh, 0, (int)((unsigned)as_kbx(a.C) * 4u * NX * 16u), 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(a.oh, 0, (int)operand_image::desc_bytes(a.C, NX), 0x00020000);
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -237,13 +237,8 @@ __global__ void __launch_bounds__(256) xl_attention_mfma_kernel(const XlArgs a)
                     t[r] = x0;
                     t[4 + r] = x1;
                 }
-                u32x4_t hh, ll;
-                split2(t, hh, ll);
                 const int ch = h * 64 + rb * 32 + 16 * pr + 8 * lk;      // first of this lane's 8 channels
-                const unsigned pl = (unsigned)((ch >> 4) * 4 + ((ch >> 3) & 1));
-                const unsigned off = mine ? (pl * NX + (unsigned)(o0 + i)) * 16u : OOBH;
-                __builtin_amdgcn_raw_buffer_store_b128(hh, rsO, off, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(ll, rsO, off + 2u * NX * 16u, 0, 0);
+                oi_store_buf(rsO, mine ? operand_image::byte_off(operand_image::plane_of(ch >> 4, 0, (ch >> 3) & 1), o0 + i, NX) : OOBH, NX, t);
             }
     }
 }

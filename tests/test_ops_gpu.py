@@ -7,6 +7,7 @@ import torch.nn.functional as F
 
 from artspeech_amd import ops
 from artspeech_amd.ops import Layout, taps_1d, taps_2d
+from oracle.gemm_ref import image_parts
 
 pytestmark = pytest.mark.gpu
 
@@ -20,13 +21,6 @@ def impl(request):
     """the f16x3 conv GEMM's one pipeline shape (one k-block per wave and iteration, three LDS stages): a parameter of its own so
     that the ids of the GEMM tests name it"""
     return request.param
-
-
-def image_parts(xs, K, N):
-    """split image int16 [KBx][4][N+1][8] -> fp32 [2 parts][KBx*16][N+1]"""
-    kbx, nx = ops.kbx(K), N + 1
-    img = xs[: kbx * 4 * nx * 8].view(torch.float16).reshape(kbx, 2, 2, nx, 8).float()       # [kb][p][kh][n][8]
-    return img.permute(1, 0, 2, 4, 3).reshape(2, kbx * 16, nx)
 
 
 def split_ref(x):
