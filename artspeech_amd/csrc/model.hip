@@ -1,7 +1,9 @@
 // Module-level C ABI (include/artspeech_hip.h, "Module-level entry points"): the acoustic model behind an opaque handle.
 //
 //   as_model_create   reads the checkpoint blob, folds weight_norm / spectral_norm (what the reference's modules do implicitly
-//                     on every forward, models.py:685-701), lays every weight out for the kernels and uploads it
+//                     on every forward, models.py:685-701), lays every weight out for the kernels and uploads it.  The reader, the
+//                     folds, the twin merge and every host assembly of a weight are checkpoint.h (plain C++, tested on the CPU);
+//                     as_model's getters here add the cache key, the weight image, the upload and the cache
 //   as_*_forward      the launch sequences of RelTransformerEncoder / StyleEncoder / DurationPredictor / ArtsPredictor / Decoder
 //   as_forward_test   ArtsSpeech.forward(step="test"), models.py:356-371, batched on packed frames
 //
@@ -54,7 +56,7 @@ struct LstmW {
 struct as_model {
     as_model_cfg cfg;
     int device = 0;
-    std::unordered_map<std::string, HostT> raw;             // folded fp32 host tensors, reference names with plain ".weight"
+    checkpoint::Map raw;                                    // folded fp32 host tensors, reference names with plain ".weight"
     struct Proj {                                           // a projection with its bias (and its fp32 matrix)
         const GemmW* w = nullptr;
         const float* bias = nullptr;
@@ -108,22 +110,39 @@ struct as_model {
         if (!d || hipMemcpy(d, h, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fail_once((int)hipErrorOutOfMemory); return nullptr; }
         return d;
     }
+    // Every getter below: the cache key -> checkpoint.h's assembly of the host arrays -> gemm_image / upload -> the cache.
+    // What an assembly reports when it fails: the name of a tensor it did not find (host()'s words), or nothing (a shape does not fit)
+    bool refuse(const std::string& missing) const
+    {
+        fail_once(AS_EINVAL, missing.empty() ? missing : "checkpoint has no tensor '" + missing + "'");
+        return false;
+    }
     // a weight given as host data [G][Cout][Cin][T] (+ [G][Cout][Cin2] behind the taps), laid out and uploaded into g
     bool gemm_image(GemmW& g, const float* w, int G, int Cout, int Cin, int T, const float* w2 = nullptr, int Cin2 = 0) const
     {
         const int rc = asrt::gemm_image(pool, g, w, G, Cout, Cin, T, w2, Cin2);
         if (rc != AS_OK) { fail_once(rc); return false; }
         if (Cin == 1 && G == 1) {                                          // the direct kernel's fp32 image [T][Kp][M]
-            std::vector<float> w32((size_t)T * g.Kp * Cout, 0.f);
-            for (int m = 0; m < Cout; ++m)
-                for (int t = 0; t < T; ++t) w32[((size_t)t * g.Kp) * Cout + m] = w[(size_t)m * T + t];
+            const std::vector<float> w32 = checkpoint::direct_image(w, Cout, T, g.Kp);
             g.w32 = upload(w32.data(), w32.size());
         }
         return true;
     }
-    const GemmW* gemm_at(const std::string& key, const std::vector<float>& w, int G, int Cout, int Cin) const     // (1x1)
+    bool gemm_image(GemmW& g, const checkpoint::Mat& a) const
     {
-        return cached(gemm, key, [&](GemmW& g) { return gemm_image(g, w.data(), G, Cout, Cin, 1); });
+        return gemm_image(g, a.w.data(), a.G, a.M, a.K, a.T, a.K2 ? a.w2.data() : nullptr, a.K2);
+    }
+    const GemmW* gemm_at(const std::string& key, const checkpoint::Mat& a) const
+    {
+        return cached(gemm, key, [&](GemmW& g) { return gemm_image(g, a); });
+    }
+    // a projection under `key` (its weight image under the same key): the matrix, its bias and, keep32, the matrix in fp32 as well
+    bool proj(Proj& r, const std::string& key, const checkpoint::Mat& a, bool keep32 = false) const
+    {
+        r.w = gemm_at(key, a);
+        r.bias = upload(a.b.data(), a.b.size());
+        if (keep32) r.w32 = upload(a.w.data(), a.w.size());
+        return r.w && r.bias && (!keep32 || r.w32);
     }
     // conv weights `names` ([Cout][Cin][k...] each, same shape) stacked as the weight sets of one grouped launch
     const GemmW* conv_stack(const std::vector<std::string>& names) const
@@ -131,16 +150,9 @@ struct as_model {
         std::string key = names[0];
         for (size_t i = 1; i < names.size(); ++i) key += "|" + names[i];
         return cached(gemm, key, [&](GemmW& g) {
-            const HostT* a = host(names[0] + ".weight");
-            if (!a) return false;
-            std::vector<float> w;
-            for (const std::string& n : names) {
-                const HostT* b = host(n + ".weight");
-                if (!b || b->dims != a->dims) { fail_once(AS_EINVAL); return false; }
-                w.insert(w.end(), b->v.begin(), b->v.end());
-            }
-            const int Cout = a->dim(0), Cin = a->dim(1), T = (int)(a->numel() / ((size_t)Cout * Cin));
-            return gemm_image(g, w.data(), (int)names.size(), Cout, Cin, T);
+            checkpoint::Mat a;
+            std::string missing;
+            return checkpoint::conv_stack(raw, names, &a, &missing) ? gemm_image(g, a) : refuse(missing);
         });
     }
     // the same with the blocks' learned shortcuts `sc_names` ([Cout][Cin2][1], no bias: models.py:77,123,178) behind the taps of every
@@ -150,20 +162,9 @@ struct as_model {
         std::string key = "FOLD:";
         for (size_t i = 0; i < names.size(); ++i) key += names[i] + "+" + sc_names[i] + "|";
         return cached(gemm, key, [&](GemmW& g) {
-            const HostT *a = host(names[0] + ".weight"), *s0 = host(sc_names[0] + ".weight");
-            if (!a || !s0 || names.size() != sc_names.size()) { fail_once(AS_EINVAL); return false; }
-            const int Cout = a->dim(0), Cin = a->dim(1), T = (int)(a->numel() / ((size_t)Cout * Cin)), Cin2 = s0->dim(1);
-            std::vector<float> w, w2;
-            for (size_t i = 0; i < names.size(); ++i) {
-                const HostT *b = host(names[i] + ".weight"), *sc = host(sc_names[i] + ".weight");
-                if (!b || !sc || b->dims != a->dims || sc->dims != s0->dims || sc->dim(0) != Cout || sc->numel() != (size_t)Cout * Cin2) {
-                    fail_once(AS_EINVAL);
-                    return false;
-                }
-                w.insert(w.end(), b->v.begin(), b->v.end());
-                w2.insert(w2.end(), sc->v.begin(), sc->v.end());
-            }
-            return gemm_image(g, w.data(), (int)names.size(), Cout, Cin, T, w2.data(), Cin2);
+            checkpoint::Mat a;
+            std::string missing;
+            return checkpoint::conv_fold(raw, names, sc_names, &a, &missing) ? gemm_image(g, a) : refuse(missing);
         });
     }
     const GemmW* conv(const std::string& name, const std::string& name2 = std::string()) const
@@ -177,13 +178,9 @@ struct as_model {
         for (size_t i = 1; i < names.size(); ++i) key += "|" + names[i];
         const Vec* r = cached(vecs, key, [&](Vec& d) {
             std::vector<float> v;
-            size_t n0 = 0;
-            for (size_t i = 0; i < names.size(); ++i) {
-                const HostT* a = host(names[i]);
-                if (!a || (i && a->numel() != n0)) { fail_once(AS_EINVAL); return false; }
-                n0 = a->numel();
-                v.insert(v.end(), a->v.begin(), a->v.end());
-            }
+            const HostT* first;
+            std::string missing;
+            if (!checkpoint::concat(raw, names, false, &v, &first, &missing)) return refuse(missing);
             d.n = v.size();
             d.p = upload(v.data(), v.size());
             return d.p != nullptr;
@@ -219,20 +216,9 @@ struct as_model {
         std::string key = "QKV:";
         for (const std::string& q : ps) key += q + "|";
         return proj_out(cached(projs, key, [&](Proj& r) {
-            std::vector<float> w, b;
-            int C = 0;
-            for (const std::string& q : ps)
-                for (const char* n : {"q", "k", "v"}) {
-                    const HostT* wt = host(q + ".conv_" + n + ".weight");
-                    const HostT* bt = host(q + ".conv_" + n + ".bias");
-                    if (!wt || !bt) return false;
-                    C = wt->dim(1);
-                    w.insert(w.end(), wt->v.begin(), wt->v.end());
-                    b.insert(b.end(), bt->v.begin(), bt->v.end());
-                }
-            r.w = gemm_at(key, w, (int)ps.size(), 3 * C, C);
-            r.bias = upload(b.data(), b.size());
-            return r.w && r.bias;
+            checkpoint::Mat a;
+            std::string missing;
+            return checkpoint::qkv(raw, ps, &a, &missing) ? proj(r, key, a) : refuse(missing);
         }), bias_out);
     }
     // input projections of several LSTMs of the same shape as the weight sets of one grouped launch
@@ -241,89 +227,49 @@ struct as_model {
         std::string key = "LSTMS:";
         for (const auto& n : names) key += n + "|";
         return proj_out(cached(projs, key, [&](Proj& r) {
-            std::vector<float> w, b;
-            int H = 0, I = 0;
-            for (const auto& p : names) {
-                const HostT *wi = host(p + ".weight_ih_l0"), *wir = host(p + ".weight_ih_l0_reverse"), *bi = host(p + ".bias_ih_l0"),
-                            *bh = host(p + ".bias_hh_l0"), *bir = host(p + ".bias_ih_l0_reverse"), *bhr = host(p + ".bias_hh_l0_reverse");
-                if (!wi || !wir || !bi || !bh || !bir || !bhr) return false;
-                H = wi->dim(0) / 4;
-                I = wi->dim(1);
-                w.insert(w.end(), wi->v.begin(), wi->v.end());
-                w.insert(w.end(), wir->v.begin(), wir->v.end());
-                for (int i = 0; i < 4 * H; ++i) b.push_back(bi->v[i] + bh->v[i]);
-                for (int i = 0; i < 4 * H; ++i) b.push_back(bir->v[i] + bhr->v[i]);
-            }
-            r.w = gemm_at(key, w, (int)names.size(), 8 * H, I);
-            r.bias = upload(b.data(), b.size());
-            return r.w && r.bias;
+            checkpoint::Mat a;
+            std::string missing;
+            return checkpoint::lstm_wih(raw, names, &a, &missing) ? proj(r, key, a) : refuse(missing);
         }), bias_out);
     }
     // nn.LSTM(bidirectional): input projection of both directions as one GEMM, biases summed, W_hh transposed
     const LstmW* lstm(const std::string& p) const
     {
         return cached(lstms, p, [&](LstmW& L) {
-            const HostT *wh = host(p + ".weight_hh_l0"), *whr = host(p + ".weight_hh_l0_reverse");
+            std::vector<float> t;
+            std::string missing;
+            const bool ok = checkpoint::lstm_whh_t(raw, p, &t, &L.H, &missing) || refuse(missing);
             L.wih = lstm_wih_stack({p}, &L.bias);
-            if (!wh || !whr || !L.wih) return false;
-            const int H = L.H = wh->dim(1);
-            std::vector<float> t((size_t)2 * H * 4 * H);
-            for (int d = 0; d < 2; ++d) {
-                const std::vector<float>& src = d ? whr->v : wh->v;               // [4H][H] -> [H][4H]
-                for (int r = 0; r < 4 * H; ++r)
-                    for (int k = 0; k < H; ++k) t[((size_t)d * H + k) * 4 * H + r] = src[(size_t)r * H + k];
-            }
+            if (!ok || !L.wih) return false;
             L.whh_t = upload(t.data(), t.size());
             return true;
         });
     }
     // `norms` = (layer name, first style entry it reads, entries it reads): a layer that reads a slice of the style
     // (models.py:499,597-599) gets zero columns elsewhere
-    struct NormSpec { std::string name; int off, S; };
+    using NormSpec = checkpoint::NormSpec;
     const FcAll* fc_all(const std::string& key, const std::vector<NormSpec>& norms, int K) const
     {
         return cached(fcalls, key, [&](FcAll& f) {
+            checkpoint::Mat a;
+            std::string missing;
+            if (!checkpoint::fc_all(raw, norms, K, &a, &f.row0, &missing)) return refuse(missing);
             f.K = K;
-            std::vector<float> w, b;
-            for (const auto& n : norms) {
-                const HostT *wt = host(n.name + ".fc.weight"), *bt = host(n.name + ".fc.bias");
-                if (!wt || !bt || wt->dim(1) != n.S || n.off + n.S > K) { fail_once(AS_EINVAL); return false; }
-                const int M = wt->dim(0);
-                f.row0[n.name] = f.Mtot;
-                f.Mtot += M;
-                const size_t base = w.size();
-                w.resize(base + (size_t)M * K, 0.f);
-                for (int m = 0; m < M; ++m)
-                    for (int k = 0; k < n.S; ++k) w[base + (size_t)m * K + n.off + k] = wt->v[(size_t)m * n.S + k];
-                b.insert(b.end(), bt->v.begin(), bt->v.end());
-            }
-            f.w = gemm_at("FCALL:" + key, w, 1, f.Mtot, K);
-            f.bias = upload(b.data(), b.size());
+            f.Mtot = a.M;
+            f.w = gemm_at("FCALL:" + key, a);
+            f.bias = upload(a.b.data(), a.b.size());
             return f.w && f.bias;
         });
     }
-    // decoder.F0_conv (1 -> 32), N_conv (1 -> 32), EMA_conv (10 -> 64) (models.py:480-482, 1x1, weight-norm) as ONE block-diagonal
-    // 1x1 conv from the stacked [F0; N; EMA] rows (12) to the 128 channels the decoder concatenates (models.py:503-505)
+    // decoder.F0_conv, N_conv, EMA_conv as ONE block-diagonal 1x1 conv (checkpoint.h: fne), and the same matrix in fp32 [M][K]
+    // (as_pointwise_small_f32)
     const GemmW* fne(const float** bias_out, const float** w32_out = nullptr) const
     {
         const std::string key = "FNE:decoder";
         return proj_out(cached(projs, key, [&](Proj& r) {
-            const HostT *f = host("decoder.F0_conv.weight"), *n = host("decoder.N_conv.weight"), *e = host("decoder.EMA_conv.weight");
-            const HostT *fb = host("decoder.F0_conv.bias"), *nb = host("decoder.N_conv.bias"), *eb = host("decoder.EMA_conv.bias");
-            if (!f || !n || !e || !fb || !nb || !eb) return false;
-            const int mf = f->dim(0), mn = n->dim(0), me = e->dim(0), ke = e->dim(1), K = 2 + ke, M = mf + mn + me;
-            std::vector<float> w((size_t)M * K, 0.f), b;
-            for (int m = 0; m < mf; ++m) w[(size_t)m * K + 0] = f->v[m];
-            for (int m = 0; m < mn; ++m) w[(size_t)(mf + m) * K + 1] = n->v[m];
-            for (int m = 0; m < me; ++m)
-                for (int k = 0; k < ke; ++k) w[(size_t)(mf + mn + m) * K + 2 + k] = e->v[(size_t)m * ke + k];
-            b.insert(b.end(), fb->v.begin(), fb->v.end());
-            b.insert(b.end(), nb->v.begin(), nb->v.end());
-            b.insert(b.end(), eb->v.begin(), eb->v.end());
-            r.w = gemm_at(key, w, 1, M, K);
-            r.bias = upload(b.data(), b.size());
-            r.w32 = upload(w.data(), w.size());                          // the same matrix in fp32 [M][K] (as_pointwise_small_f32)
-            return r.w && r.bias && r.w32;
+            checkpoint::Mat a;
+            std::string missing;
+            return checkpoint::fne(raw, &a, &missing) ? proj(r, key, a, true) : refuse(missing);
         }), bias_out, w32_out);
     }
 };
@@ -2295,193 +2241,9 @@ struct Call {                     // an entry point's context behind the common 
 // ------------------------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------------------------
-namespace asrt {
-
-bool read_blob(const void* blob, size_t bytes, std::unordered_map<std::string, HostT>* raw_out)
-{
-    // Every bound is checked in subtraction form against what is left (o <= bytes always holds): nothing here can wrap for any
-    // header content, and nothing is allocated from a count the file merely claims.
-    const unsigned char* b = static_cast<const unsigned char*>(blob);
-    size_t o = 0;
-    auto need = [&](size_t n) { return n <= bytes - o; };
-    if (!need(12) || memcmp(b, "ASWBLOB1", 8) != 0) return false;
-    o = 8;
-    uint32_t n;
-    memcpy(&n, b + o, 4);
-    o += 4;
-    if ((size_t)n > (bytes - o) / 11) return false;         // an entry is at least 2 + 0 + 1 + 0 + 8 bytes
-    struct Ent { std::string name; std::vector<int> dims; uint64_t off; size_t numel; };
-    std::vector<Ent> ents(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        uint16_t nl;
-        if (!need(2)) return false;
-        memcpy(&nl, b + o, 2);
-        o += 2;
-        if (!need((size_t)nl + 1)) return false;
-        ents[i].name.assign(reinterpret_cast<const char*>(b + o), nl);
-        o += nl;
-        const int nd = b[o++];
-        if (nd > 8 || !need((size_t)nd * 4 + 8)) return false;
-        size_t numel = 1;
-        for (int d = 0; d < nd; ++d) {
-            uint32_t v;
-            memcpy(&v, b + o, 4);
-            o += 4;
-            if (v > (uint32_t)INT32_MAX) return false;
-            if (v != 0 && numel > (SIZE_MAX / 4) / v) return false;   // numel * 4 must not wrap either
-            numel *= v;
-            ents[i].dims.push_back((int)v);
-        }
-        ents[i].numel = numel;
-        memcpy(&ents[i].off, b + o, 8);
-        o += 8;
-    }
-    uint64_t data_bytes;
-    if (!need(8)) return false;
-    memcpy(&data_bytes, b + o, 8);
-    o += 8;
-    if (data_bytes > bytes - o) return false;
-    for (auto& e : ents) {
-        if (e.off > data_bytes || e.numel * 4 > data_bytes - e.off) return false;
-        HostT t;
-        t.dims = e.dims;
-        t.v.resize(e.numel);
-        if (e.numel) memcpy(t.v.data(), b + o + e.off, e.numel * 4);
-        (*raw_out)[e.name] = std::move(t);
-    }
-    return true;
-}
-
-static bool ends_with(const std::string& s, const char* suf)
-{
-    const size_t n = strlen(suf);
-    return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
-}
-
-// weight_norm (torch old-style, dim 0): w = v * g / ||v|| over all dims but 0; spectral_norm in eval: w = W / (u . (W2d v))
-// (artspeech_amd/weights.py is the Python statement of the same)
-bool fold(const std::unordered_map<std::string, HostT>& in, std::unordered_map<std::string, HostT>* out)
-{
-    for (const auto& kv : in) {
-        std::string k = kv.first;
-        if (k.compare(0, 7, "module.") == 0) k = k.substr(7);
-        if (k.compare(0, 30, "style_encoder.pitch_extractor.") == 0 || k.compare(0, 28, "style_encoder.ema_extractor.") == 0) continue;
-        auto get = [&](const std::string& name) -> const HostT* {
-            auto it = in.find(name);
-            if (it == in.end()) it = in.find("module." + name);
-            return it == in.end() ? nullptr : &it->second;
-        };
-        if (ends_with(k, ".weight_g")) {
-            const std::string p = k.substr(0, k.size() - 9);
-            const HostT* v = get(p + ".weight_v");
-            if (!v || v->dims.empty() || kv.second.numel() != (size_t)v->dims[0]) return false;
-            HostT w;
-            w.dims = v->dims;
-            w.v.resize(v->numel());
-            const size_t rows = v->dims[0], per = v->numel() / rows;
-            for (size_t r = 0; r < rows; ++r) {
-                double s = 0;
-                for (size_t i = 0; i < per; ++i) s += (double)v->v[r * per + i] * v->v[r * per + i];
-                const float scale = kv.second.v[r] / (float)sqrt(s);
-                for (size_t i = 0; i < per; ++i) w.v[r * per + i] = v->v[r * per + i] * scale;
-            }
-            (*out)[p + ".weight"] = std::move(w);
-        } else if (ends_with(k, ".weight_orig")) {
-            const std::string p = k.substr(0, k.size() - 12);
-            const HostT *u = get(p + ".weight_u"), *vv = get(p + ".weight_v");
-            const HostT& W = kv.second;
-            if (!u || !vv || W.dims.empty() || u->numel() != (size_t)W.dims[0] || vv->numel() * W.dims[0] != W.numel()) return false;
-            const size_t rows = W.dims[0], per = W.numel() / rows;
-            double sigma = 0;
-            for (size_t r = 0; r < rows; ++r) {
-                double s = 0;
-                for (size_t i = 0; i < per; ++i) s += (double)W.v[r * per + i] * vv->v[i];
-                sigma += (double)u->v[r] * (double)(float)s;
-            }
-            HostT w;
-            w.dims = W.dims;
-            w.v.resize(W.numel());
-            const float sg = (float)sigma;
-            for (size_t i = 0; i < W.numel(); ++i) w.v[i] = W.v[i] / sg;
-            (*out)[p + ".weight"] = std::move(w);
-        } else if (ends_with(k, ".weight_v") || ends_with(k, ".weight_u")) {
-            continue;
-        } else {
-            (*out)[k] = kv.second;
-        }
-    }
-    return true;
-}
-
-}  // namespace asrt
-
-namespace {
-// Two towers of the same architecture on different input channels (style_encoder.energy_block / F0_block + their Linear layers,
-// models.py:402-411,414-415) as ONE tower of twice the width: every conv weight becomes block diagonal (the off-diagonal zeros multiply
-// exactly to zero), depthwise weights and biases are concatenated.  Half the launches -- these 1-D towers are ~20 kernels of 8-10 us
-// each, all at the fixed cost of a launch -- for twice the (negligible) flop.  Channel order: tower a first.
-bool merge_twin_towers(std::unordered_map<std::string, HostT>* raw, const std::string& a, const std::string& b, const std::string& merged)
-{
-    std::vector<std::pair<std::string, HostT>> add;
-    for (const auto& kv : *raw) {
-        if (kv.first.compare(0, a.size() + 1, a + ".") != 0) continue;
-        const std::string sfx = kv.first.substr(a.size());
-        const auto itb = raw->find(b + sfx);
-        if (itb == raw->end() || itb->second.dims != kv.second.dims) return false;
-        const HostT &ta = kv.second, &tb = itb->second;
-        HostT t;
-        const bool is_w = sfx.size() >= 7 && sfx.compare(sfx.size() - 7, 7, ".weight") == 0;
-        if (!is_w || sfx.find(".pool.") != std::string::npos) {           // bias / depthwise [C][1][k]: concatenate
-            t.dims = ta.dims;
-            t.dims[0] *= 2;
-            t.v = ta.v;
-            t.v.insert(t.v.end(), tb.v.begin(), tb.v.end());
-        } else {                                                          // [Cout][Cin][k]: block diagonal
-            const int co = ta.dim(0), ci = ta.dim(1), k = (int)(ta.numel() / ((size_t)co * ci));
-            t.dims = ta.dims;
-            t.dims[0] = 2 * co;
-            t.dims[1] = 2 * ci;
-            t.v.assign((size_t)4 * co * ci * k, 0.f);
-            for (int m = 0; m < co; ++m)
-                for (int c = 0; c < ci; ++c)
-                    for (int j = 0; j < k; ++j) {
-                        t.v[((size_t)m * 2 * ci + c) * k + j] = ta.v[((size_t)m * ci + c) * k + j];
-                        t.v[((size_t)(co + m) * 2 * ci + ci + c) * k + j] = tb.v[((size_t)m * ci + c) * k + j];
-                    }
-        }
-        add.emplace_back(merged + sfx, std::move(t));
-    }
-    if (add.empty()) return false;
-    for (auto& kv : add) (*raw)[kv.first] = std::move(kv.second);
-    return true;
-}
-// Linear layers of the twins -> one block Linear on [pooled a | pooled b] whose output rows are [rows of lb | rows of la] (the Style
-// vector holds the F0 slice before the energy slice, models.py:423)
-bool merge_twin_linears(std::unordered_map<std::string, HostT>* raw, const std::string& la, const std::string& lb, const std::string& merged)
-{
-    const auto wa = raw->find(la + ".weight"), wb = raw->find(lb + ".weight"), ba = raw->find(la + ".bias"), bb = raw->find(lb + ".bias");
-    if (wa == raw->end() || wb == raw->end() || ba == raw->end() || bb == raw->end() || wa->second.dims != wb->second.dims) return false;
-    const int o = wa->second.dim(0), i = wa->second.dim(1);
-    HostT w, bias;
-    w.dims = {2 * o, 2 * i};
-    w.v.assign((size_t)4 * o * i, 0.f);
-    for (int m = 0; m < o; ++m)
-        for (int c = 0; c < i; ++c) {
-            w.v[(size_t)m * 2 * i + i + c] = wb->second.v[(size_t)m * i + c];          // rows 0 .. o-1: lb on the second half of the input
-            w.v[(size_t)(o + m) * 2 * i + c] = wa->second.v[(size_t)m * i + c];        // rows o .. : la on the first half
-        }
-    bias.dims = {2 * o};
-    bias.v = bb->second.v;
-    bias.v.insert(bias.v.end(), ba->second.v.begin(), ba->second.v.end());
-    (*raw)[merged + ".weight"] = std::move(w);
-    (*raw)[merged + ".bias"] = std::move(bias);
-    return true;
-}
-}  // namespace
-
 static int model_create(const void* blob_host, size_t blob_bytes, const as_model_cfg* cfg, as_model** out)
 {
-    std::unordered_map<std::string, HostT> blob;
+    checkpoint::Map blob;
     if (!read_blob(blob_host, blob_bytes, &blob)) return AS_EINVAL;
     struct Guard {                                                       // every error return below gives the device memory back
         std::unique_ptr<as_model> m;
@@ -2493,8 +2255,8 @@ static int model_create(const void* blob_host, size_t blob_bytes, const as_model
     if (!fold(blob, &m->raw)) return AS_EINVAL;
     blob.clear();
     // energy tower (input: crop row 0) + F0 tower (row 1) as one double-width tower
-    if (!merge_twin_towers(&m->raw, "style_encoder.energy_block", "style_encoder.F0_block", "style_encoder.ENF0_block") ||
-        !merge_twin_linears(&m->raw, "style_encoder.Energylinear", "style_encoder.F0linear", "style_encoder.ENF0linear"))
+    if (!checkpoint::merge_twin_towers(&m->raw, "style_encoder.energy_block", "style_encoder.F0_block", "style_encoder.ENF0_block") ||
+        !checkpoint::merge_twin_linears(&m->raw, "style_encoder.Energylinear", "style_encoder.F0linear", "style_encoder.ENF0linear"))
         return AS_EINVAL;
     AS_CHECK(hipGetDevice(&m->device));
     {

@@ -1,10 +1,12 @@
 // Host-side state shared by the module-level translation units (model.hip: the acoustic model; vocoder_rt.hip: the HiFi-GAN generator):
-// device memory that lives as long as its owner, checkpoint tensors, the packed-frames geometry and the plan that caches its device tables;
+// device memory that lives as long as its owner, the packed-frames geometry and the plan that caches its device tables;
 // and the object both write their launch sequences against: PassCtx (the workspace arena, the plan's layout cache and its device tables,
 // RUN), with the entry points' prologue (enter) and the weight-image upload (gemm_image).  Nothing here knows as_model or as_vocoder.
+// The checkpoint side -- the tensor type, the blob reader, the folds and every host assembly of weights -- is checkpoint.h (no HIP).
 #pragma once
 #include "common.h"
 #include "artspeech_hip.h"
+#include "checkpoint.h"
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -73,17 +75,9 @@ struct DevPool {
     }
 };
 
-struct HostT {
-    std::vector<int> dims;
-    std::vector<float> v;
-    size_t numel() const { return v.size(); }
-    int dim(int i) const { return i < (int)dims.size() ? dims[i] : 1; }
-};
-
-// the "ASWBLOB1" checkpoint format (include/artspeech_hip.h, as_model_create) -> name -> tensor; false: not a well-formed blob
-bool read_blob(const void* blob, size_t bytes, std::unordered_map<std::string, HostT>* raw_out);
-// weight_norm / spectral_norm folded into plain "<prefix>.weight" tensors (plain tensors pass through); false: a part is missing
-bool fold(const std::unordered_map<std::string, HostT>& in, std::unordered_map<std::string, HostT>* out);
+using checkpoint::HostT;
+using checkpoint::read_blob;
+using checkpoint::fold;
 
 // nothing may unwind through the C boundary
 template <class F>

@@ -1,7 +1,7 @@
 // Module-level C ABI of the HiFi-GAN generator (include/artspeech_hip.h, "The HiFi-GAN generator behind an opaque handle"): mel in,
 // samples out, one call.  Like model.hip this file holds no kernels: it reads the checkpoint blob, lays the weights out (weight_norm
-// fold, ConvTranspose1d -> 3-tap phase conv, per-row biases, the fp32 conv_post row, the GEMM's weight images) and orders the launches
-// of vocoder.hip / respair.hip / conv_gemm*.hip -- the sequence artspeech_amd/vocoder.py::Generator.forward_packed issues operator by
+// fold, ConvTranspose1d -> 3-tap phase conv, per-row biases: checkpoint.h's host arithmetic; the fp32 conv_post row, the GEMM's weight
+// images: uploads made here) and orders the launches of vocoder.hip / respair.hip / conv_gemm*.hip -- the sequence artspeech_amd/vocoder.py::Generator.forward_packed issues operator by
 // operator, decision for decision.  ONE sequence (generator()), written against runtime.h's pass context like the acoustic model's,
 // serves two passes: count (as_vocoder_workspace_bytes: the arena only adds up, nothing is launched) and run (kernels are enqueued;
 // nothing is allocated, nothing synchronises once the geometry's tables exist) -- and two kinds of geometry: lengths the host knows
@@ -47,7 +47,7 @@ struct as_vocoder {
 
 namespace {
 
-using Raw = std::unordered_map<std::string, HostT>;
+using Raw = checkpoint::Map;
 
 bool cfg_ok(const as_vocoder_cfg& c)
 {
@@ -70,35 +70,16 @@ bool cfg_ok(const as_vocoder_cfg& c)
     return true;
 }
 
-// the folded tensor `name` with exactly these dims, or NULL
-const HostT* tensor(const Raw& w, const std::string& name, std::initializer_list<int> dims)
-{
-    const auto it = w.find(name);
-    if (it == w.end()) { if (getenv("AS_DEBUG")) fprintf(stderr, "artspeech_hip: vocoder checkpoint has no tensor '%s'\n", name.c_str()); return nullptr; }
-    if (it->second.dims != std::vector<int>(dims)) { if (getenv("AS_DEBUG")) fprintf(stderr, "artspeech_hip: vocoder tensor '%s' has another shape\n", name.c_str()); return nullptr; }
-    return &it->second;
-}
-
-// every tensor the configuration names, with its shape -- host work only: a bad checkpoint is refused before a device is touched
+// every tensor the configuration names, with its shape (checkpoint.h) -- host work only: a bad checkpoint is refused before a device is
+// touched
 bool checkpoint_ok(const Raw& w, const as_vocoder_cfg& c)
 {
-    const int c0 = c.upsample_initial_channel;
-    bool ok = tensor(w, "conv_pre.weight", {c0, c.num_mels, 7}) && tensor(w, "conv_pre.bias", {c0});
-    for (int i = 0; ok && i < c.n_stages; ++i) {
-        const int cin = c0 >> i, cout = c0 >> (i + 1);
-        const std::string p = "ups." + std::to_string(i);
-        ok = tensor(w, p + ".weight", {cin, cout, c.upsample_kernel_sizes[i]}) && tensor(w, p + ".bias", {cout});
-        for (int j = 0; ok && j < c.n_stacks; ++j)
-            for (int n = 0; ok && n < c.n_dilations; ++n)
-                for (const char* cv : {".convs1.", ".convs2."}) {
-                    const std::string q = "resblocks." + std::to_string(i * c.n_stacks + j) + cv + std::to_string(n);
-                    ok = ok && tensor(w, q + ".weight", {cout, cout, c.resblock_kernel_sizes[j]}) && tensor(w, q + ".bias", {cout});
-                }
-    }
-    const auto post = w.find("conv_post.weight");
-    ok = ok && post != w.end() && post->second.dims.size() == 3 && post->second.dim(0) == 1 && post->second.dim(1) == c0 >> c.n_stages &&
-         (post->second.dim(2) & 1) && post->second.dim(2) <= AS_MAX_TAPS && tensor(w, "conv_post.bias", {1});
-    return ok;
+    const checkpoint::GeneratorShape g = {c.num_mels, c.upsample_initial_channel, c.n_stages, c.n_stacks, c.n_dilations,
+                                          c.upsample_kernel_sizes, c.resblock_kernel_sizes, AS_MAX_TAPS};
+    std::string why;
+    if (checkpoint::checkpoint_ok(w, g, &why)) return true;
+    if (getenv("AS_DEBUG")) fprintf(stderr, "artspeech_hip: %s\n", why.c_str());
+    return false;
 }
 
 float* upload(as_vocoder& v, const float* h, size_t n)
@@ -153,9 +134,9 @@ int vocoder_create(const void* blob_host, size_t blob_bytes, const as_vocoder_cf
         const std::string p = "ups." + std::to_string(i);
         const HostT &wt = w.at(p + ".weight"), &b = w.at(p + ".bias");
         const int u = cfg->upsample_rates[i], cin = wt.dim(0), cout = wt.dim(1);
-        std::vector<float> wc((size_t)u * cout * cin * 3), rows;
-        ok = as_vocoder_fold_upsample_host(wt.v.data(), cin, cout, u, wc.data()) == AS_OK;
-        for (int r = 0; r < u; ++r) rows.insert(rows.end(), b.v.begin(), b.v.end());
+        std::vector<float> wc((size_t)u * cout * cin * 3);
+        const std::vector<float> rows = checkpoint::row_bias(b, u);
+        ok = checkpoint::fold_upsample(wt.v.data(), cin, cout, u, wc.data());
         ok = ok && conv_w(v, v.ups[i], wc.data(), u * cout, cin, 3, rows.data(), rows.size());
         v.ups_bias[i] = upload(v, b.v.data(), b.numel());
         ok = ok && v.ups_bias[i];
@@ -473,18 +454,7 @@ bool cap_ok(const as_vocoder* v, int B, int cap, int max_len)
 extern "C" int as_vocoder_fold_upsample_host(const float* wt, int Cin, int Cout, int u, float* wc)
 {
     if (!wt || !wc || Cin <= 0 || Cout <= 0 || u < 1) return AS_EINVAL;
-    const int p = u / 2 + u % 2, k = 2 * u;
-    memset(wc, 0, (size_t)u * Cout * Cin * 3 * sizeof(float));
-    for (int r = 0; r < u; ++r) {
-        const int rr = (r + p) % u, s = (r + p) / u;
-        for (int j = 0; j < 2; ++j) {
-            const int d = s - j + 1;                                    // taps x[q - 1], x[q], x[q + 1] = d 0, 1, 2
-            if (d < 0 || d > 2) return AS_EINVAL;
-            for (int m = 0; m < Cout; ++m)
-                for (int c = 0; c < Cin; ++c) wc[(((size_t)r * Cout + m) * Cin + c) * 3 + d] = wt[((size_t)c * Cout + m) * k + rr + u * j];
-        }
-    }
-    return AS_OK;
+    return checkpoint::fold_upsample(wt, Cin, Cout, u, wc) ? AS_OK : AS_EINVAL;
 }
 
 extern "C" int as_vocoder_create(const void* blob_host, size_t blob_bytes, const as_vocoder_cfg* cfg, as_vocoder** out)
