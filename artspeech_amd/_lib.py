@@ -275,6 +275,28 @@ _SIGNATURES.update({
 })
 
 
+class JoinCfg(ctypes.Structure):
+    """as_join_cfg (include/artspeech_hip.h): the paragraph joiner's rule in samples and ratios"""
+    _fields_ = [("frame", ctypes.c_int32), ("trim_ratio", ctypes.c_float), ("keep", ctypes.c_int32), ("fade", ctypes.c_int32),
+                ("gap", ctypes.c_int32), ("lead", ctypes.c_int32), ("tail", ctypes.c_int32), ("target_rms", ctypes.c_float),
+                ("peak_ceiling", ctypes.c_float), ("max_gain", ctypes.c_float)]
+
+
+class JoinIO(ctypes.Structure):
+    """as_join_io: DEVICE pointers (as_join_host: host pointers)"""
+    _fields_ = [("in_off", c_p), ("in_cap", ctypes.c_int32), ("x", c_p), ("G", ctypes.c_int32), ("group_off", c_p), ("gap", c_p),
+                ("out_cap", ctypes.c_int32), ("y", c_p), ("pcm", c_p), ("out_off", c_p), ("piece", c_p), ("gain", c_p)]
+
+
+_pJC, _pJIO = ctypes.POINTER(JoinCfg), ctypes.POINTER(JoinIO)
+_SIGNATURES.update({
+    "as_join_workspace_bytes": (c_sz, [c_i, c_i, _pJC]),
+    "as_join_f32": (c_i, [_pJC, c_i, _pJIO, c_p, c_sz, c_p]),
+    "as_join_measure_f32": (c_i, [_pJC, c_i, _pJIO, c_p, c_sz, c_p]),
+    "as_join_host": (c_i, [_pJC, c_i, _pJIO]),
+})
+
+
 AS_MAX_LSTM_JOBS = 4
 
 

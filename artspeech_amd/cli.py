@@ -14,6 +14,11 @@ One voice, many sentences: ``--save-voice voice.npz`` (with ``--ref-wav``) also 
 ``--voice voice.npz`` replaces ``--ref-wav`` in later runs -- the reference is not processed again.  Exactly one of ``--ref-wav`` and
 ``--voice`` is given.
 
+A page of text: ``--paragraph`` cuts ``--phonemes`` into sentences (text.split_sentences), synthesises them as one batch and joins them
+into one stream on the device (join.Joiner, as_join_f32): every sentence trimmed of its silent ends (``--trim-db``), levelled
+(``--level-db``), faded at the cuts, with ``--pause-ms`` between sentences.  ``--trim-ref-db DB`` cuts the silent ends of the reference
+wave on the device by the same block rule (test.py:101 does this with librosa; the rule here is the library's own).
+
 How it is spoken: ``--speed`` (speaking rate, 1 = as predicted), ``--pitch-semitones`` and ``--energy-db`` (pipeline.Prosody).  Inside the
 utterance: ``--emphasis FIRST:LAST:SEMITONES[:SPEED[:DB]]`` (repeatable) raises the pitch of tokens FIRST..LAST (indices into the cleaned
 phoneme string, inclusive) by SEMITONES, speaks them at SPEED (0.5 = twice as long: a stressed word, a longer pause on a comma) and DB louder;
@@ -79,6 +84,15 @@ def build_parser():
     ap.add_argument("--out", default="output.wav")
     ap.add_argument("--out-rate", type=int, default=24000, metavar="HZ", help="sample rate of --out (default 24000: the generator's own); "
                     "another rate is resampled on the device (as_resample_f32), with --pcm16 straight to 16-bit samples")
+    ap.add_argument("--paragraph", action="store_true", help="--phonemes is a paragraph: it is cut into sentences (text.split_sentences), synthesised "
+                    "as ONE batch and joined into one stream on the device (as_join_f32): trimmed, faded, with pauses; needs a vocoder")
+    ap.add_argument("--pause-ms", type=float, metavar="MS", help="pause between sentences (default 250; clause cuts get half); implies --paragraph")
+    ap.add_argument("--trim-db", type=float, metavar="DB", help="a sentence's ends are cut where its 5 ms blocks fall DB below its loudest block "
+                    "(default 40); implies --paragraph")
+    ap.add_argument("--level-db", type=float, metavar="DB", help="bring every sentence to this RMS, in dB re full scale (default: no levelling); "
+                    "implies --paragraph")
+    ap.add_argument("--trim-ref-db", type=float, metavar="DB", help="with --ref-wav: trim the reference wave on the device by the same block rule "
+                    "before the mel front end (test.py:101 trims with librosa at 30 dB; this is the library's own rule, not librosa's)")
     ap.add_argument("--jdc", help="Utils/JDC/bst.t7")
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
     ap.add_argument("--vocoder-config", help="Vocoder/config.json")
@@ -103,12 +117,31 @@ def parse_args(argv=None):
         if a.frame_cap < 1:
             ap.error("--frame-cap takes a positive number of frames")
         a.vocoder_runtime = True
+    if a.pause_ms is not None and a.pause_ms < 0:
+        ap.error("--pause-ms takes a pause of 0 ms or more")
+    for name in ("trim_db", "trim_ref_db"):
+        if getattr(a, name) is not None and getattr(a, name) <= 0:
+            ap.error(f"--{name.replace('_', '-')} takes a positive number of decibels below the loudest block")
+    if a.trim_ref_db is not None and not a.ref_wav:
+        ap.error("--trim-ref-db needs --ref-wav")
+    a.paragraph = a.paragraph or a.pause_ms is not None or a.trim_db is not None or a.level_db is not None
+    if a.paragraph and a.emphasis:
+        ap.error("--emphasis counts the tokens of one utterance: not with --paragraph")
     try:
         a.prosody = prosody_of(a)
         a.spans = emphasis_spans(a.emphasis)
     except ValueError as e:
         ap.error(str(e))
     return ap, a
+
+
+def joiner_of(a, rate):
+    """the join.Joiner of the parsed arguments at the output's rate, or None when they ask for no paragraph"""
+    from .join import Joiner
+    if not a.paragraph:
+        return None
+    kw = {k: v for k, v in (("pause_ms", a.pause_ms), ("trim_db", a.trim_db), ("level_db", a.level_db)) if v is not None}
+    return Joiner(rate, **kw)
 
 
 def prosody_of(a):
@@ -172,6 +205,23 @@ def main(argv=None):
         tok = dict(token_prosody=token_prosody_of(a, tts), token_smooth=a.smooth_prosody)
     except ValueError as e:
         ap.error(f"--emphasis: {e}")
+    if a.paragraph:
+        from .pipeline import Voice
+        if a.voice:
+            voice = Voice.load(a.voice, tts)
+        else:
+            wave_in, ref_rate = read_wav_any(a.ref_wav)
+            voice = tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db)
+            if a.save_voice:
+                voice.save(a.save_voice)
+                print(f"{a.save_voice}: voice of {a.ref_wav}")
+        audio, piece = tts.synthesis_paragraph(a.phonemes, voice=voice, prosody=a.prosody, joiner=joiner_of(a, a.out_rate), pcm16=a.pcm16,
+                                               frame_cap=a.frame_cap, sample_rate=a.out_rate)
+        write_wav(a.out, audio.numpy(), sr=a.out_rate)
+        print(f"{a.out}: {audio.numel()} samples, {audio.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {piece.shape[0]} sentences")
+        for b, (o0, o1, s0, s1) in enumerate(piece.tolist()):
+            print(f"  sentence {b}: {o0 / float(a.out_rate):.3f} s .. {o1 / float(a.out_rate):.3f} s (its samples {s0} .. {s1})")
+        return 0
     if a.voice:
         from .pipeline import Voice
         audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
@@ -179,10 +229,10 @@ def main(argv=None):
     else:
         wave_in, ref_rate = read_wav_any(a.ref_wav)
         if a.save_voice:
-            tts.voice_from_wave(wave_in, rate=ref_rate).save(a.save_voice)
+            tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db).save(a.save_voice)
             print(f"{a.save_voice}: voice of {a.ref_wav}")
         audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, ref_rate=ref_rate,
-                                        sample_rate=a.out_rate, **tok)
+                                        sample_rate=a.out_rate, trim_db=a.trim_ref_db, **tok)
     write_wav(a.out, audio.cpu().numpy(), sr=a.out_rate)
     print(f"{a.out}: {audio.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {tts._last_frames[0]} mel frames")
     return 0

@@ -252,12 +252,43 @@ class ArtSpeech:
         return Voice(v[0].cpu(), net.rt.cfg.style_dim, net.rt.fingerprint)
 
     @torch.no_grad()
-    def voice_from_wave(self, ref_wave, rate=24000):
+    def voice_from_wave(self, ref_wave, rate=24000, trim_db=None):
         """The Voice of a reference wave (already loaded / trimmed; `rate` Hz: another rate than 24000 is resampled on the device,
-        resample.Resampler): the log-mel front end, the attached extractors, the voice"""
+        resample.Resampler): the log-mel front end, the attached extractors, the voice.  trim_db (None: the wave as it came): the wave's
+        silent ends are cut on the device first (_trim_ref: the library's own block rule, not librosa's)."""
         if getattr(self, "frontend", None) is None:
             self.attach_frontend()
+        if trim_db is not None:
+            ref_wave = self._trim_ref(ref_wave, rate, trim_db)
         return self.voice_from_mel(self.frontend(self._ref_at_24k(ref_wave, rate))[0])
+
+    REF_KEEP_MS = 20                # what _trim_ref keeps in front of the first and behind the last active block
+
+    def _trim_ref(self, ref_wave, rate, trim_db):
+        """A reference wave, or a list of them, of `rate` Hz with the silence at its ends cut, on the device (join.Joiner.measure,
+        as_join_measure_f32): the wave is measured in blocks of 5 ms, a block is active when its mean square is positive and at most
+        trim_db below the loudest block's, and what is kept runs from REF_KEEP_MS in front of the first active block to REF_KEEP_MS behind
+        the last.  This is the library's own block rule in the spirit of test.py:101 (librosa.effects.trim(top_db=30): frames of 2048
+        samples every 512, RMS against the peak frame); it is NOT librosa parity -- the frames, the hop and the margin differ, and
+        nothing here pins librosa's result.  Returns device tensors."""
+        from . import _lib
+        from .join import Joiner
+        single = not isinstance(ref_wave, (list, tuple))
+        waves = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in ([ref_wave] if single else ref_wave)]
+        lens = [int(w.numel()) for w in waves]
+        if min(lens) < 1:
+            raise ValueError("trim_db: an empty reference wave")
+        with torch.cuda.device(self.device):
+            x = torch.cat([w.to(self.device) for w in waves]).contiguous()
+            off = np.concatenate([[0], np.cumsum(lens)])
+            kept, _ = Joiner(rate, trim_db=trim_db, keep_ms=self.REF_KEEP_MS, device=self.device).measure(x, torch.tensor(off, dtype=torch.int32).to(self.device))
+            kept = kept.cpu().tolist()
+            if _lib.lib().as_device_status(0):
+                raise _lib.HipLibraryError(f"trim_db: a kernel reported {_lib.device_status()} (as_device_status): a sample of the reference is not finite")
+        if any(e <= s for s, e in kept):
+            raise ValueError("trim_db: a reference wave is silent throughout")
+        out = [x[int(off[b]) + s: int(off[b]) + e] for b, (s, e) in enumerate(kept)]
+        return out[0] if single else out
 
     def _ref_at_24k(self, ref_wave, rate):
         """a reference wave, or a list of them, of `rate` Hz -> at the front end's 24 kHz (as it came when that is its rate)"""
@@ -291,14 +322,17 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
-                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None):
+                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
         attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
         device, with the library's own filter); sample_rate: the rate of the returned samples (synthesis_wav).  Loading / trimming the
-        file and espeak stay with the caller."""
+        file and espeak stay with the caller.  trim_db (None: the wave as it came): the silent ends of ref_wave are cut on the device
+        before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity)."""
         if getattr(self, "frontend", None) is None:
             self.attach_frontend()
+        if trim_db is not None:
+            ref_wave = self._trim_ref(ref_wave, ref_rate, trim_db)
         ref_wave = self._ref_at_24k(ref_wave, ref_rate)
         single = isinstance(phonemes, str)
         if single:
@@ -438,21 +472,50 @@ class ArtSpeech:
             kw["mel_p"], kw["f0_p"], kw["ema_p"] = models.pack_reference(mels, f0_raw, ema_raw, ml, dev)
         return kw
 
-    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None):
+    def _join_packed(self, join, x, off, groups, gaps, pcm16, join_cap=None):
+        """join.Joiner.forward_packed on packed fp32 device samples and their device offsets -> (stream [join_cap], out_off [G + 1], piece
+        [B][4]); join_cap None: what always suffices (every sample kept, every gap in place), which needs the gaps as a list or None"""
+        B = off.numel() - 1
+        G = 1 if groups is None else len(groups) - 1
+        if join_cap is None:
+            if torch.is_tensor(gaps):
+                raise ValueError("gaps on the device: name join_cap, the samples of room for the joined streams")
+            join_cap = join.out_cap(x.numel(), B, G, None if gaps is None else max(max(int(v) for v in gaps), 0))
+        y, p16, out_off, piece, _ = join.forward_packed(x, off, join_cap, groups=groups, gaps=gaps, pcm=pcm16, wav=not pcm16)
+        return (p16 if pcm16 else y), out_off, piece
+
+    def _check_joiner(self, join, sample_rate):
+        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        if join.rate != rate:
+            raise ValueError(f"the joiner counts its milliseconds at {join.rate} Hz, the samples it is given are at {rate} Hz")
+
+    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None):
         """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
         then the capacity vocoder on its frame_off and mel.  `inputs` = packed_inputs(...).  Every call with the same inputs dict reuses
         the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
         with other token / voice / prosody contents of the same geometry.  -> (samples [300 * 2 frame_cap], sample_off [B + 1]), both on the
         device.  sample_rate (other than None / 24000): the generator writes fp32 and resample.Resampler(24000, sample_rate) runs on its
-        device sample_off on the same stream -> (samples [ceil(600 frame_cap L / M) + B], out_off [B + 1]); still no host value, still capturable."""
+        device sample_off on the same stream -> (samples [ceil(600 frame_cap L / M) + B], out_off [B + 1]); still no host value, still capturable.
+        join (a join.Joiner at the rate of the samples; groups / gaps / join_cap as Joiner.forward_packed and _join_packed take them): the
+        joiner runs on the device offsets the chain already has -- sample_off, or the resampler's out_off -- on the same stream, and the
+        call returns (stream [join_cap] fp32 or int16, out_off [G + 1], piece [B][4]) instead; with groups and gaps as device tensors (or
+        None) the chain stays capturable."""
         if self.generator is None or not self.generator.runtime:
             raise RuntimeError("frame_cap needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
+        if join is not None:
+            self._check_joiner(join, sample_rate)
         net = self.model.ArtsSpeech
         kw = {k: v for k, v in inputs.items() if k != "_out"}
         with torch.cuda.device(self.device):
             res = net.forward_packed(kw.pop("tok"), kw.pop("tok_lens"), kw.pop("mel_p"), kw.pop("f0_p"), kw.pop("ema_p"), kw.pop("ref_lens"),
                                      frame_cap=frame_cap, out=inputs.setdefault("_out", {}), **kw)
             rs = self._out_resampler(sample_rate)
+            if join is not None:
+                wav, off = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len)
+                x = wav[0]
+                if rs is not None:
+                    x, _, off = rs.forward_packed(x, off, rs.out_len(wav.shape[1]) + off.numel() - 1)
+                return self._join_packed(join, x, off, groups, gaps, pcm16, join_cap)
             if rs is not None:
                 wav, sample_off = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len)
                 B = sample_off.numel() - 1
@@ -481,6 +544,61 @@ class ArtSpeech:
         for b, n in enumerate(lens):
             out[b, :n] = host[off[b]: off[b + 1]]
         return out
+
+    @torch.no_grad()
+    def synthesis_paragraph(self, sentences, ref_mel=None, voice=None, prosody=None, pause_ms=None, joiner=None, sample_rate=None, pcm16=False,
+                            frame_cap=None, features=None, max_tokens=None):
+        """A paragraph as ONE stream: `sentences` is a list of phoneme strings, or one string that text.split_sentences cuts (max_tokens:
+        its limit per piece).  The sentences run as one batch through the calls above (synthesis_mel and the generator, or with frame_cap
+        the chain with no read-back; the resampler when sample_rate is given), then through join.Joiner on the device -- every sentence
+        trimmed of the silence at its ends, faded at the cuts, levelled if the joiner says so, with pauses between -- and ONE copy brings
+        the stream back.  One reference (ref_mel [80, T], with features as synthesis_mel takes them for one utterance) or one voice serves
+        every sentence; lists of them go sentence by sentence.  joiner: a join.Joiner at the output's rate (None: Joiner(rate) with
+        pause_ms, default 250); pause_ms: the pause behind a full stop -- a cut of another class gets text.PAUSE_SCALE's share of it.
+        Returns (stream 1-D fp32 or int16, piece int32 [B][4] = out_start, out_end, src_start, src_end per sentence: where it landed in the
+        stream and which of its own samples were kept)."""
+        from . import _lib
+        from .join import Joiner
+        from .text import PAUSE_SCALE, split_sentences
+        if self.generator is None:
+            raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
+        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        if joiner is None:
+            joiner = Joiner(rate, device=self.device, **({} if pause_ms is None else {"pause_ms": pause_ms}))
+        self._check_joiner(joiner, sample_rate)
+        pause = joiner.cfg.gap if pause_ms is None else joiner.samples(pause_ms)
+        if isinstance(sentences, str):
+            sentences, classes = split_sentences(sentences, max_tokens)
+            gaps = [0] + [int(round(PAUSE_SCALE[c] * pause)) for c in classes]
+        else:
+            sentences = list(sentences)
+            gaps = None if pause_ms is None else [0] + [pause] * (len(sentences) - 1)
+        B = len(sentences)
+        if B < 1:
+            raise ValueError("synthesis_paragraph: nothing to say")
+        if ref_mel is not None and not isinstance(ref_mel, (list, tuple)):
+            ref_mel, features = [ref_mel] * B, None if features is None else [features] * B
+        rs = self._out_resampler(sample_rate)
+        if frame_cap is not None:
+            inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody)
+            stream, out_off, piece = self.chain_cap(inputs, int(frame_cap), pcm16=pcm16, sample_rate=sample_rate, join=joiner, gaps=gaps)
+        else:
+            from .models import pack
+            from .vocoder import layout
+            mel = self.synthesis_mel(sentences, ref_mel, features=features, voice=voice, prosody=prosody)
+            gen, lens = self.generator, [int(v) for v in self._last_frames]
+            with torch.cuda.device(gen.device):
+                wav, lay_w = gen.forward_packed(pack(mel.to(gen.device), lens), layout(lens, gen.device))[:2]
+                x, off = wav.reshape(-1)[: max(lay_w.N, 1)], lay_w.col_off
+                if rs is not None:
+                    x, _, off = rs.forward_packed(x, off, max(sum(rs.out_len(n) for n in lay_w.widths_host), 1))
+                stream, out_off, piece = self._join_packed(joiner, x.contiguous(), off, None, gaps, pcm16)
+        with torch.cuda.device(self.device):
+            n = int(out_off.cpu()[-1])                                      # the one synchronisation: the length, then the stream
+            if _lib.lib().as_device_status(0):
+                raise _lib.HipLibraryError(f"synthesis_paragraph failed: a kernel reported {_lib.device_status()} (as_device_status); "
+                                           "results since then are invalid")
+            return stream[:n].cpu(), piece.cpu()
 
     @torch.no_grad()
     def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None,

@@ -934,6 +934,63 @@ int as_resampler_info(const as_resampler* r, int32_t* L, int32_t* M, int32_t* H)
 int as_resample_f32(const as_resampler* r, int B, const int32_t* in_off, int in_cap, const float* x, int out_cap, float* y, int16_t* pcm,
                     int32_t* out_off, as_stream_t stream);
 
+/* ---- paragraphs: a batch's utterances as streams (csrc/join.hip; the rule: csrc/join_rule.h) ---------------------
+ * A page of text is synthesised as a batch of its sentences; the joiner turns the packed samples of that batch into G streams on the
+ * device: every utterance trimmed of the silence at its ends, levelled against the others, faded at the cuts, with pauses between.
+ * The rule, per utterance x[0 .. n), F = cfg->frame.  Blocks: K = ceil(n / F), block k has cnt_k = min(F, n - k F) samples, ss_k = its fp32
+ * sum of squares (in the one order join_rule.h fixes), pk_k = max |x|, ms_k = ss_k / cnt_k, top = max ms_k.  Trim (trim_ratio > 0, a power
+ * ratio 10^(-dB / 10)): block k is active when ms_k > 0 and ms_k >= fp32(trim_ratio * top); k0, k1 = first and last active block; kept
+ * [s0, s1) = [max(0, k0 F - keep), min(n, (k1 + 1) F + keep)), empty when no block is active; trim off: all blocks active, [0, n).  Level
+ * (target_rms > 0): A = sum ss_k and C = sum cnt_k over the active blocks, rms = sqrtf(A / C), peak = max pk_k over all blocks,
+ * g = min(target_rms / rms, peak_ceiling / peak, max_gain); g = 1 when A == 0 or the level is off.  Edges: m = s1 - s0, f = min(fade, m / 2),
+ * w(i) = (i + 0.5) / f for i < f, (m - 1 - i + 0.5) / f for i >= m - f, else 1; y_i = (x[s0 + i] g) w(i).  Layout: group_off [G + 1] cuts the
+ * B utterances into G streams (a group may be empty); a stream is `lead` zeros, its non-empty pieces in order, `tail` zeros, with
+ * max(gap[b], 0) zeros (cfg->gap without an array) in front of every piece that is not the first non-empty one of its stream; an empty
+ * piece adds nothing and its gap is dropped.  An utterance in a batch gives the bits of the same utterance joined alone; with the trim
+ * and the level off and fade = gap = lead = tail = 0 and one group the output is the packed input bit for bit.
+ * as_join_io: in_off DEVICE int32 [B + 1] (in_off[0] = 0; an as_vocoder_cap.sample_off, an as_resample_f32 out_off, or prefix sums of
+ * known lengths), x DEVICE [in_cap]; group_off DEVICE [G + 1] or NULL (one stream; inner cuts are read clamped to [0, B]), gap DEVICE [B] or
+ * NULL; outputs, each out_cap samples: y fp32 and / or pcm (as_conv_post_pcm_f32's rule on the fp32 value), samples in [out_off[G], out_cap)
+ * are 0; optional out_off [G + 1], piece [B] (where utterance b landed and which of its own samples were kept: subtitles, lip-sync; an empty
+ * piece has out_start == out_end) and gain [B].
+ * as_join_f32           three launches (measure, reduce, write), sized by in_cap and out_cap: nothing is read back, uploaded or allocated
+ *                       and no call synchronises -- every call, the first included, can be captured into a hipGraph and replayed with other
+ *                       offsets, samples and gaps.  The streams need more than out_cap, or in_off[B] > in_cap: AS_STATUS_CAPACITY (the layout
+ *                       is cut at the capacities, nothing is read or stored out of bounds); a sample that is not finite:
+ *                       AS_STATUS_F16_RANGE; either way that call's output is void.
+ * as_join_measure_f32   the first two launches only: piece[b].src_start / src_end = the kept range (out_start = out_end = 0), gain if
+ *                       given; y, pcm, out_cap, group_off and gap are not read.  The device trim of a reference wave.
+ * as_join_host          the same rule on HOST arrays (every pointer of io is a host pointer; no GPU, no workspace): io->y or io->pcm given:
+ *                       the join; neither: the measurement, into io->piece.  AS_ENOSPC: the streams need more than out_cap (the output is
+ *                       cut there); AS_EDEVICE: a sample is not finite; AS_EINVAL also for offsets that do not ascend from 0 to <= in_cap.
+ * AS_EINVAL before anything is launched: cfg, io, ws, in_off or x NULL, B < 1, G < 1, both outputs NULL (measure: piece NULL), frame outside
+ * [16, 4096], negative keep / fade / lead / tail, a negative or non-finite float, in_cap or out_cap below 1 or above 2^30.  AS_ENOSPC: ws_bytes below
+ * as_join_workspace_bytes(B, in_cap, cfg) (0 for arguments it refuses).  AS_EDEVICE while a status bit is set. */
+typedef struct as_join_cfg {
+    int32_t frame;                 /* samples per measuring block */
+    float trim_ratio;              /* 0: no trim */
+    int32_t keep, fade, gap, lead, tail;   /* samples */
+    float target_rms, peak_ceiling, max_gain;   /* target_rms 0: no levelling */
+} as_join_cfg;
+typedef struct as_join_piece {
+    int32_t out_start, out_end, src_start, src_end;
+} as_join_piece;
+typedef struct as_join_io {
+    const int32_t* in_off; int32_t in_cap;
+    const float* x;
+    int32_t G; const int32_t* group_off;
+    const int32_t* gap;
+    int32_t out_cap;
+    float* y; int16_t* pcm;
+    int32_t* out_off;
+    as_join_piece* piece;
+    float* gain;
+} as_join_io;
+size_t as_join_workspace_bytes(int B, int in_cap, const as_join_cfg* cfg);
+int as_join_f32(const as_join_cfg* cfg, int B, const as_join_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_join_measure_f32(const as_join_cfg* cfg, int B, const as_join_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_join_host(const as_join_cfg* cfg, int B, const as_join_io* io);
+
 /* ---- batches in flight (csrc/lanes.hip; DESIGN.md section 5: the throughput arrangement) -----------------------------------------------
  * as_lanes = n lanes on ONE model: per lane a HIP stream of its own, its two workspaces (grown on demand), TWO serial plans
  * (as_plan_set_serial) -- one for eager calls, whose layout cache may be flushed at any entry point, and one that only ever sees the
