@@ -297,6 +297,38 @@ _SIGNATURES.update({
 })
 
 
+AS_DTW_MAX_T, AS_DTW_MAX_C = 4096, 128
+
+
+class DtwIO(ctypes.Structure):
+    """as_dtw_io: DEVICE pointers (as_dtw_features_host: host pointers)"""
+    _fields_ = [("a", c_p), ("lda", ctypes.c_int32), ("a_off", c_p), ("a_mult", ctypes.c_int32),
+                ("b", c_p), ("ldb", ctypes.c_int32), ("b_off", c_p), ("b_mult", ctypes.c_int32),
+                ("C", ctypes.c_int32), ("B", ctypes.c_int32), ("Tx", ctypes.c_int32), ("Ty", ctypes.c_int32), ("center", ctypes.c_int32),
+                ("rows", c_p), ("cols", c_p), ("total", c_p), ("steps", c_p), ("cost_out", c_p)]
+
+
+class TransferIO(ctypes.Structure):
+    """as_transfer_io: DEVICE pointers (as_transfer_rows_host: host pointers)"""
+    _fields_ = [("B", ctypes.c_int32), ("rows", c_p), ("ld_rows", ctypes.c_int32), ("tok_off", c_p), ("tok_cap", ctypes.c_int32),
+                ("dur_i", c_p), ("duration", c_p), ("F0", c_p), ("N", c_p), ("EMA", c_p), ("ld_pred", ctypes.c_int32),
+                ("syn_off", c_p), ("syn_mult", ctypes.c_int32), ("feat12", c_p), ("ld_feat", ctypes.c_int32),
+                ("rec_off", c_p), ("rec_mult", ctypes.c_int32), ("strength", ctypes.c_float * 13),
+                ("out_rows", c_p), ("ld_out", ctypes.c_int32), ("target_dur", c_p), ("misses", c_p)]
+
+
+_pDIO, _pTIO = ctypes.POINTER(DtwIO), ctypes.POINTER(TransferIO)
+_SIGNATURES.update({
+    "as_dtw_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "as_dtw_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "as_dtw_features_f32": (c_i, [_pDIO, c_p, c_sz, c_p]),
+    "as_transfer_rows_f32": (c_i, [_pTIO, c_p]),
+    "as_dtw_host": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "as_dtw_features_host": (c_i, [_pDIO]),
+    "as_transfer_rows_host": (c_i, [_pTIO]),
+})
+
+
 AS_MAX_LSTM_JOBS = 4
 
 

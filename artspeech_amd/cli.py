@@ -23,6 +23,11 @@ How it is spoken: ``--speed`` (speaking rate, 1 = as predicted), ``--pitch-semit
 utterance: ``--emphasis FIRST:LAST:SEMITONES[:SPEED[:DB]]`` (repeatable) raises the pitch of tokens FIRST..LAST (indices into the cleaned
 phoneme string, inclusive) by SEMITONES, speaks them at SPEED (0.5 = twice as long: a stressed word, a longer pause on a comma) and DB louder;
 ``--smooth-prosody`` glides between the tokens' settings instead of stepping.
+
+Like a recording: ``--like-wav said.wav`` is a recording of the SAME phonemes (any speaker, any rate the resampler takes); the sentence is
+synthesised once, warped onto the recording on the device (as_dtw_features_f32) and synthesised again with the recording's rhythm and
+melody (pipeline.ArtSpeech.synthesis_like).  ``--like-tracks timing,pitch,energy,ema`` says what is taken over (default
+timing,pitch,energy).  Not with ``--emphasis`` (both set the per-token controls) nor with ``--paragraph``.
 """
 import argparse
 import json
@@ -81,6 +86,10 @@ def build_parser():
                     help="tokens FIRST..LAST (inclusive) of the phoneme string: pitch raised by SEMITONES, spoken at SPEED (default 1), DB louder "
                          "(default 0); repeatable, a later span replaces an earlier one where they overlap")
     ap.add_argument("--smooth-prosody", action="store_true", help="with --emphasis: glide linearly between the tokens' settings (centre to centre)")
+    ap.add_argument("--like-wav", metavar="PATH", help="a recording of the same phonemes, mono PCM wav: speak with its timing and melody "
+                    "(the synthesis is warped onto it on the device: as_dtw_features_f32, as_transfer_rows_f32)")
+    ap.add_argument("--like-tracks", metavar="LIST", help="with --like-wav: what is taken from the recording, a comma list among timing, pitch, "
+                    "energy, ema (default timing,pitch,energy)")
     ap.add_argument("--out", default="output.wav")
     ap.add_argument("--out-rate", type=int, default=24000, metavar="HZ", help="sample rate of --out (default 24000: the generator's own); "
                     "another rate is resampled on the device (as_resample_f32), with --pcm16 straight to 16-bit samples")
@@ -127,12 +136,30 @@ def parse_args(argv=None):
     a.paragraph = a.paragraph or a.pause_ms is not None or a.trim_db is not None or a.level_db is not None
     if a.paragraph and a.emphasis:
         ap.error("--emphasis counts the tokens of one utterance: not with --paragraph")
+    if a.like_tracks is not None and not a.like_wav:
+        ap.error("--like-tracks needs --like-wav")
+    if a.like_wav and a.emphasis:
+        ap.error("--like-wav and --emphasis both set the per-token controls: one of them")
+    if a.like_wav and a.paragraph:
+        ap.error("--like-wav is a recording of one utterance: not with --paragraph")
+    if a.like_wav and a.frame_cap is not None:
+        ap.error("--like-wav reads the first pass's frame counts back: not with --frame-cap")
+    a.like_tracks = a.like_tracks if a.like_tracks is not None else "timing,pitch,energy"
     try:
         a.prosody = prosody_of(a)
         a.spans = emphasis_spans(a.emphasis)
+        transfer_of(a)
     except ValueError as e:
         ap.error(str(e))
     return ap, a
+
+
+def transfer_of(a):
+    """the mimic.Transfer of the parsed --like-tracks, or None without --like-wav"""
+    from .mimic import Transfer
+    if not a.like_wav:
+        return None
+    return Transfer.of_tracks(a.like_tracks.split(","))
 
 
 def joiner_of(a, rate):
@@ -222,7 +249,22 @@ def main(argv=None):
         for b, (o0, o1, s0, s1) in enumerate(piece.tolist()):
             print(f"  sentence {b}: {o0 / float(a.out_rate):.3f} s .. {o1 / float(a.out_rate):.3f} s (its samples {s0} .. {s1})")
         return 0
-    if a.voice:
+    if a.like_wav:
+        from .pipeline import Voice
+        like, like_rate = read_wav_any(a.like_wav)
+        if a.voice:
+            voice = Voice.load(a.voice, tts)
+        else:
+            wave_in, ref_rate = read_wav_any(a.ref_wav)
+            voice = tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db)
+            if a.save_voice:
+                voice.save(a.save_voice)
+                print(f"{a.save_voice}: voice of {a.ref_wav}")
+        audio, info = tts.synthesis_like(a.phonemes, like_wave=like, like_rate=like_rate, voice=voice, transfer=transfer_of(a), smooth=True,
+                                         prosody=a.prosody, pcm16=a.pcm16, sample_rate=a.out_rate)
+        print(f"{a.like_wav}: {int(info['rec_frames'][0])} frames aligned to {int(info['syn_frames'][0])} synthesised ones, "
+              f"{int(info['misses'].sum())} token(s) kept their own duration")
+    elif a.voice:
         from .pipeline import Voice
         audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
                                   sample_rate=a.out_rate, **tok)

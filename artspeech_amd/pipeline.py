@@ -651,6 +651,104 @@ class ArtSpeech:
         self._last_frames = list(aux["frames2"])
         return mel
 
+    @torch.no_grad()
+    def synthesis_like(self, phonemes, like_wave=None, like_mel=None, like_rate=24000, ref_mel=None, voice=None, features=None,
+                       like_features=None, like_feat12=None, transfer=None, smooth=True, center=True, prosody=None, vocode=None,
+                       pcm16=False, sample_rate=None):
+        """Speak `phonemes` in the voice of ref_mel / voice WITH THE DELIVERY OF A RECORDING of the same phonemes (any speaker): its rhythm
+        and, per track, how its pitch, energy and articulators differ from what the model predicts (mimic.Transfer says which).
+        like_wave (samples at like_rate Hz: resampled and turned into a log-mel on the device) or like_mel (normalised log-mel [80, T]);
+        one utterance or lists.  The recording's twelve normalised tracks come from the attached extractors (like_features = (f0_raw,
+        ema_raw) bypasses them as `features` does for the reference) and ops.ref_features -- or are handed in as like_feat12 [12, T]
+        (energy, F0, EMA0..9).
+        The chain: pass A synthesises normally; its mel is warped onto the recording's (mimic.dtw_features, per-bin means taken off when
+        `center`: another speaker, another microphone); mimic.transfer_rows turns the warp into one prosody row per token -- a duration
+        scale target / predicted and the offsets strength * (recording - pass A) -- and pass B synthesises with them (token_prosody,
+        glided between the tokens' centres when `smooth`).  The offsets are first order: they are measured against pass A's tracks while
+        pass B's predictors see the new durations.  Between pass A's frame counts (its one read-back) and the result nothing is read
+        from the device.
+        Returns (what synthesis_wav returns when a vocoder is attached and `vocode` is not False, else what synthesis_mel returns,
+        info): info = dict(rows [B, Ty], target_dur, misses [B], total [B], token_rows, dur_a, dur_b, duration, tok_off, syn_frames,
+        rec_frames), device tensors but for the two host lists of frame counts.  An utterance-level `prosody` composes on top: its speed
+        scales the recording's timing."""
+        from . import mimic, ops
+        from .models import layout, pack, pack_reference, unpack
+        if (like_wave is None) == (like_mel is None):
+            raise ValueError("synthesis_like needs exactly one of like_wave and like_mel")
+        net = self.model.ArtsSpeech
+        dev = net.device
+        single = isinstance(phonemes, str)
+        if like_wave is not None:
+            if getattr(self, "frontend", None) is None:
+                self.attach_frontend()
+            w = self._ref_at_24k(like_wave, like_rate)
+            if single:
+                rec = [self.frontend(w)[0]]
+            else:
+                m, n = self.frontend(list(w))
+                rec = [m[b, :, :k] for b, k in enumerate(n)]
+        else:
+            rec = [like_mel] if single else list(like_mel)
+        rec = [torch.as_tensor(m, dtype=torch.float32) for m in rec]
+        ml = [int(m.shape[-1]) for m in rec]
+        B = len(ml)
+        use_vocoder = self.generator is not None if vocode is None else bool(vocode)
+        if use_vocoder and self.generator is None:
+            raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
+        kw = self.packed_inputs(phonemes, ref_mel, features, voice, prosody)
+        if len(kw["tok_lens"]) != B:
+            raise ValueError(f"{B} recordings for {len(kw['tok_lens'])} utterances")
+        with torch.cuda.device(dev):
+            # the recording: packed log-mel [80][Nr] and its twelve normalised tracks [12][Nr]
+            rec_p = torch.cat([m.to(dev) for m in rec], dim=1).contiguous()
+            Nr = rec_p.shape[1]
+            if like_feat12 is not None:
+                f12 = [like_feat12] if single else list(like_feat12)
+                feat12 = torch.cat([torch.as_tensor(f, dtype=torch.float32).to(dev) for f in f12], dim=1).contiguous()
+                if tuple(feat12.shape) != (12, Nr):
+                    raise ValueError("like_feat12: [12, T] per utterance, T the recording's frames")
+            else:
+                mels = torch.zeros(B, rec_p.shape[0], max(ml))
+                for b, m in enumerate(rec):
+                    mels[b, :, : ml[b]] = m.cpu()
+                feats = None
+                if like_features is not None:
+                    lf = [like_features] if single else list(like_features)
+                    f0 = None if any(f is None for f, _ in lf) else torch.zeros(B, 1, max(ml))
+                    ema = torch.zeros(B, 10, max(ml))
+                    for b, (f, e) in enumerate(lf):
+                        if f0 is not None:
+                            f0[b, :, : ml[b]] = torch.as_tensor(f, dtype=torch.float32).reshape(1, -1)
+                        ema[b, :, : ml[b]] = torch.as_tensor(e, dtype=torch.float32)
+                    feats = (f0, ema)
+                f0_raw, ema_raw = net.style_encoder._extract(mels, feats, ml)
+                _, f0_p, ema_p = pack_reference(mels, f0_raw, ema_raw, ml, dev)
+                feat12 = ops.ref_features(rec_p, f0_p, ema_p, Nr, torch.tensor(_stats24(net), dtype=torch.float32, device=dev),
+                                          torch.empty((12, Nr), dtype=torch.float32, device=dev))
+            rec_off = torch.tensor(np.concatenate([[0], np.cumsum(ml)]), dtype=torch.int32).to(dev)
+            tok_off = torch.tensor(np.concatenate([[0], np.cumsum(kw["tok_lens"])]), dtype=torch.int32).to(dev)
+            a = net.forward_packed(**kw, aux=True)                                   # pass A (reads its frame counts back)
+            Tx, Ty = max(max(a["frames2"]), 1), max(ml)
+            if Tx > mimic.MAX_T or Ty > mimic.MAX_T:
+                raise ValueError(f"synthesis_like: an utterance of more than {mimic.MAX_T} mel frames ({Tx} synthesised, {Ty} recorded)")
+            rows, _, total, _ = mimic.dtw_features(a["mel"], a["frame_off"], rec_p, rec_off, Tx, Ty, a_mult=2, b_mult=1, center=center)
+            trows, target, misses = mimic.transfer_rows(rows, tok_off, a["dur_i"], a["duration"].reshape(-1), a["F0"].reshape(-1),
+                                                        a["N"].reshape(-1), a["EMA"], a["frame_off"], feat12, rec_off, transfer=transfer)
+            syn_frames = list(a["frames2"])
+            b_out = net.forward_packed(**kw, aux=True, token_prosody=trows, token_smooth=smooth)       # pass B
+            self._last_frames = list(b_out["frames2"])
+            mel = unpack(b_out["mel"], layout(b_out["frames2"], dev))
+            info = dict(rows=rows, target_dur=target, misses=misses, total=total, dur_a=a["dur_i"], dur_b=b_out["dur_i"],
+                        duration=a["duration"], tok_off=tok_off, token_rows=trows, syn_frames=syn_frames, rec_frames=ml)
+        if not use_vocoder:
+            return mel, info
+        rs = self._out_resampler(sample_rate)
+        if rs is not None:
+            wav = self._generate_resampled(mel, self._last_frames, rs, pcm16)
+        else:
+            wav = (self.generator(mel, lengths=self._last_frames, pcm16=True) if pcm16 else self.generator(mel, lengths=self._last_frames))[:, 0]
+        return (wav[0] if single else wav), info
+
     def synthesis(self, text, ref_wav, save_path):
         raise NotImplementedError("text -> phonemes (espeak) and reading / trimming the wav file (librosa) are outside this path "
                                   "(SURVEY.md section 2); use synthesis_from_wave(phonemes, wave) / synthesis_wav(phonemes, ref_mel)")

@@ -991,6 +991,77 @@ int as_join_f32(const as_join_cfg* cfg, int B, const as_join_io* io, void* ws, s
 int as_join_measure_f32(const as_join_cfg* cfg, int B, const as_join_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
 int as_join_host(const as_join_cfg* cfg, int B, const as_join_io* io);
 
+/* ---- prosody transfer (csrc/dtw.hip, csrc/dtw_rule.h) -------------------------------------------------------------
+ * Speak a sentence the way a recording of it was spoken: synthesise it once (pass A), warp pass A's mel onto the recording's log-mel
+ * (dynamic time warping, frame by frame), turn the warp into one prosody row per token (as_plan_set_token_prosody's rows: a duration scale
+ * and twelve track offsets) and synthesise again with those rows (pass B).  Nothing here synchronises, allocates or reads back; every
+ * length is DEVICE data, so the whole chain can be captured into a hipGraph and replayed with other contents.
+ * The rule (csrc/dtw_rule.h states it in full).  Cost of synthesised frame i and recording frame j over C <= AS_DTW_MAX_C bins: acc = 0,
+ * for k in order d = a_k(i) - b_k(j), acc = fmaf(d, d, acc); center = 1 takes each side's per-bin mean over its own frames (fp32 sum in
+ * ascending frame order / fp32(count)) off first: d = (a_k(i) - ma_k) - (b_k(j) - mb_k) -- what makes another speaker's recording
+ * alignable.  Lattice [t_x][t_y], path from (0, 0) to (t_x - 1, t_y - 1): D(0, 0) = c(0, 0), D(i, j) = c(i, j) + min(D(i-1, j-1), D(i-1, j),
+ * D(i, j-1)) with +inf outside the lattice: a min and exactly one fp32 add per cell.  The predecessor is the argmin; ties go to the diagonal,
+ * then to (i-1, j), then to (i, j-1).  NaN inputs are excepted.  Outputs per utterance, each optional: rows [B][Ty] (rows[j] = the largest i
+ * on the path in column j; -1 for j >= t_y), cols [B][Tx] (cols[i] = the largest j on the path in row i; -1 for i >= t_x),
+ * total [B] = D(t_x - 1, t_y - 1), steps [B] = the number of path cells.  A length > its capacity raises AS_STATUS_CAPACITY and is
+ * clamped; a length <= 0 writes only the -1 fill (total and steps of that utterance are left alone).
+ * as_dtw_f32            a caller's dense cost [B][Tx][Ty] (the counterpart of as_mas_f32), t_x / t_y DEVICE int32 [B].  Two launches (the lattice
+ *                       re-laid in the order of the wavefront's steps, then the warp and the walk back).
+ * as_dtw_features_f32   packed features [C][ld] on both sides; utterance u lies at the columns [mult off[u], mult off[u + 1]) of its side
+ *                       (off DEVICE int32 [B + 1]; as_forward_io.mel_out lies at 2 * frame_off), cut at ld and at the capacity
+ *                       (AS_STATUS_CAPACITY).  Four launches: the means and the spans, the cost lattice (into the workspace, or into cost_out
+ *                       [B][Tx][Ty] if given; cells outside an utterance's lattice are not written), then as_dtw_f32's two.
+ * as_transfer_rows_f32  one launch, a workgroup per utterance.  Packed token k of utterance u (tok_off DEVICE [B + 1]) owns the synthesised
+ *                       columns [2 s_k, 2 s_{k+1}), s_k = pass A's dur_i summed over u's tokens before k.  E_k = the first j < t_y with
+ *                       rows[j] >= 2 s_{k+1}, else t_y (t_y = the recording's span, cut at ld_rows); E_{-1} = 0; H_k = (E_k + 1) >> 1; the
+ *                       target t_k = clamp(H_k - H_{k-1}, 1, 16384) goes to target_dur[k] (optional).  out_rows[k] (row stride ld_out >=
+ *                       AS_PROSODY_DIM, columns behind AS_PROSODY_DIM are left alone): [AS_PROSODY_DUR] = q = fp32(t_k) / duration_k; if q is
+ *                       not finite or rintf(fp32(duration_k q)) != t_k, q = 1 and misses[u] (optional, [B]) goes up; with strength[0] == 0 the
+ *                       scale is 1 and nothing is a miss.  Gains 1.  [AS_PROSODY_OFFSET + c] = strength[1 + c] (mean_rec - mean_syn): mean_rec
+ *                       over the columns [E_{k-1}, E_k) of row (c == 0 ? 1 : c == 1 ? 0 : c) of feat12 (as_ref_features_f32: energy, F0,
+ *                       EMA), mean_syn over the token's own columns of pass A's F0 / N / EMA (as_forward_io.F0 ...; cut at the utterance's
+ *                       span), both fp32 sums in ascending order / fp32(count); 0 if either range is empty.  Tokens from tok_cap on are not
+ *                       written (AS_STATUS_CAPACITY).  The offsets are FIRST ORDER: measured against pass A's tracks, while pass B's
+ *                       predictors see the new durations.  Durations go in as a scale because a plan with token rows refuses forced_dur.
+ * as_dtw_host, as_dtw_features_host, as_transfer_rows_host: the same rule on HOST arrays (every pointer is a host pointer; no GPU, no
+ *                       workspace, over-long lengths are clamped without a word).
+ * AS_EINVAL before anything is launched: a NULL io, input, offset array or workspace, B < 1, a capacity outside [1, AS_DTW_MAX_T],
+ * C outside [1, AS_DTW_MAX_C], a multiplier < 1, ld below what one frame needs (ld < 1; ld_out < AS_PROSODY_DIM), center not 0 or 1, a
+ * negative or non-finite strength.  AS_ENOSPC: ws_bytes below as_dtw_workspace_bytes(B, Tx, Ty) (0 for arguments it refuses).  AS_EDEVICE
+ * while a status bit is set. */
+#define AS_DTW_MAX_T 4096
+#define AS_DTW_MAX_C 128
+typedef struct as_dtw_io {
+    const float* a; int32_t lda; const int32_t* a_off; int32_t a_mult;    /* the synthesised side [C][lda] */
+    const float* b; int32_t ldb; const int32_t* b_off; int32_t b_mult;    /* the recording [C][ldb] */
+    int32_t C, B, Tx, Ty, center;
+    int32_t* rows; int32_t* cols; float* total; int32_t* steps;           /* optional outputs */
+    float* cost_out;                                                      /* optional [B][Tx][Ty] */
+} as_dtw_io;
+typedef struct as_transfer_io {
+    int32_t B;
+    const int32_t* rows; int32_t ld_rows;                                 /* the warp's rows [B][ld_rows] */
+    const int32_t* tok_off; int32_t tok_cap;                              /* [B + 1]; the packed tokens there is room for */
+    const int32_t* dur_i; const float* duration;                          /* pass A's, [sum tok_lens] */
+    const float* F0; const float* N; const float* EMA; int32_t ld_pred;   /* pass A's tracks: [1] / [1] / [10] x [ld_pred] */
+    const int32_t* syn_off; int32_t syn_mult;                             /* [B + 1]: utterance u at the columns syn_mult * syn_off[u] .. */
+    const float* feat12; int32_t ld_feat;                                 /* the recording's tracks [12][ld_feat] */
+    const int32_t* rec_off; int32_t rec_mult;                             /* [B + 1] */
+    float strength[13];                                                   /* timing, then F0, N, EMA0..9 */
+    float* out_rows; int32_t ld_out;                                      /* [tok_cap][ld_out >= AS_PROSODY_DIM] */
+    int32_t* target_dur;                                                  /* optional [tok_cap] */
+    int32_t* misses;                                                      /* optional [B] */
+} as_transfer_io;
+size_t as_dtw_workspace_bytes(int B, int Tx, int Ty);
+int as_dtw_f32(const float* cost, const int32_t* t_x, const int32_t* t_y, int B, int Tx, int Ty, int32_t* rows, int32_t* cols,
+               float* total, int32_t* steps, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_dtw_features_f32(const as_dtw_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_transfer_rows_f32(const as_transfer_io* io, as_stream_t stream);
+int as_dtw_host(const float* cost, const int32_t* t_x, const int32_t* t_y, int B, int Tx, int Ty, int32_t* rows, int32_t* cols,
+                float* total, int32_t* steps);
+int as_dtw_features_host(const as_dtw_io* io);
+int as_transfer_rows_host(const as_transfer_io* io);
+
 /* ---- batches in flight (csrc/lanes.hip; DESIGN.md section 5: the throughput arrangement) -----------------------------------------------
  * as_lanes = n lanes on ONE model: per lane a HIP stream of its own, its two workspaces (grown on demand), TWO serial plans
  * (as_plan_set_serial) -- one for eager calls, whose layout cache may be flushed at any entry point, and one that only ever sees the
