@@ -297,6 +297,27 @@ _SIGNATURES.update({
 })
 
 
+class MarksCfg(ctypes.Structure):
+    """as_marks_cfg (include/artspeech_hip.h): the chain behind the acoustic model and the animation clock, as the speech marks' rule takes them"""
+    _fields_ = [("hop", ctypes.c_int32), ("L", ctypes.c_int32), ("M", ctypes.c_int32), ("rate", ctypes.c_int32), ("fps_num", ctypes.c_int32),
+                ("fps_den", ctypes.c_int32)]
+
+
+class MarksIO(ctypes.Structure):
+    """as_marks_io: DEVICE pointers (as_marks_host: host pointers)"""
+    _fields_ = [("tok_off", c_p), ("dur_i", c_p), ("frame_off", c_p), ("F0", c_p), ("N", c_p), ("EMA", c_p), ("ld_pred", ctypes.c_int32),
+                ("piece", c_p), ("G", ctypes.c_int32), ("group_off", c_p), ("out_off", c_p), ("scale", c_p), ("offset", c_p),
+                ("marks", c_p), ("tracks", c_p), ("ld_tracks", ctypes.c_int32), ("anim_cap", ctypes.c_int32), ("active", c_p), ("anim_off", c_p)]
+
+
+_pMC, _pMIO = ctypes.POINTER(MarksCfg), ctypes.POINTER(MarksIO)
+_SIGNATURES.update({
+    "as_marks_workspace_bytes": (c_sz, [c_i, c_i, _pMC]),
+    "as_marks_f32": (c_i, [_pMC, c_i, c_i, _pMIO, c_p, c_sz, c_p]),
+    "as_marks_host": (c_i, [_pMC, c_i, c_i, _pMIO]),
+})
+
+
 AS_DTW_MAX_T, AS_DTW_MAX_C = 4096, 128
 
 

@@ -28,6 +28,10 @@ Like a recording: ``--like-wav said.wav`` is a recording of the SAME phonemes (a
 synthesised once, warped onto the recording on the device (as_dtw_features_f32) and synthesised again with the recording's rhythm and
 melody (pipeline.ArtSpeech.synthesis_like).  ``--like-tracks timing,pitch,energy,ema`` says what is taken over (default
 timing,pitch,energy).  Not with ``--emphasis`` (both set the per-token controls) nor with ``--paragraph``.
+
+Speech marks: ``--marks PATH`` also writes when every sentence, word and token is spoken in ``--out`` -- ``.jsonl`` (one JSON object per
+mark), ``.srt`` or ``.vtt`` (subtitles) -- and ``--tracks-out PATH.npz`` the pitch, energy and ten articulator tracks retimed onto ``--out`` at
+``--marks-fps N[/D]`` frames per second (default 60), computed on the device behind the last stage (marks.Marker, as_marks_f32).
 """
 import argparse
 import json
@@ -102,6 +106,11 @@ def build_parser():
                     "implies --paragraph")
     ap.add_argument("--trim-ref-db", type=float, metavar="DB", help="with --ref-wav: trim the reference wave on the device by the same block rule "
                     "before the mel front end (test.py:101 trims with librosa at 30 dB; this is the library's own rule, not librosa's)")
+    ap.add_argument("--marks", metavar="PATH", help="also write the speech marks -- when every sentence, word and token is spoken in --out -- as "
+                    "PATH.jsonl (one JSON object per mark), PATH.srt or PATH.vtt (subtitles: sentences with --paragraph, else words)")
+    ap.add_argument("--marks-fps", metavar="N[/D]", help="the animation clock of --tracks-out, frames per second (default 60; 30000/1001 is exact)")
+    ap.add_argument("--tracks-out", metavar="PATH.npz", help="also write F0, energy and the ten articulator tracks, retimed onto --out at "
+                    "--marks-fps frames per second, in physical units (as_marks_f32)")
     ap.add_argument("--jdc", help="Utils/JDC/bst.t7")
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
     ap.add_argument("--vocoder-config", help="Vocoder/config.json")
@@ -145,7 +154,16 @@ def parse_args(argv=None):
     if a.like_wav and a.frame_cap is not None:
         ap.error("--like-wav reads the first pass's frame counts back: not with --frame-cap")
     a.like_tracks = a.like_tracks if a.like_tracks is not None else "timing,pitch,energy"
+    if a.marks is not None and not a.marks.lower().endswith((".jsonl", ".srt", ".vtt")):
+        ap.error("--marks writes .jsonl, .srt or .vtt")
+    if a.tracks_out is not None and not a.tracks_out.lower().endswith(".npz"):
+        ap.error("--tracks-out writes an .npz")
+    a.with_marks = a.marks is not None or a.marks_fps is not None or a.tracks_out is not None
+    if a.with_marks and a.like_wav:
+        ap.error("--marks, --marks-fps and --tracks-out: not with --like-wav")
     try:
+        if a.with_marks:
+            marker_of(a, a.out_rate, None)
         a.prosody = prosody_of(a)
         a.spans = emphasis_spans(a.emphasis)
         transfer_of(a)
@@ -169,6 +187,29 @@ def joiner_of(a, rate):
         return None
     kw = {k: v for k, v in (("pause_ms", a.pause_ms), ("trim_db", a.trim_db), ("level_db", a.level_db)) if v is not None}
     return Joiner(rate, **kw)
+
+
+def marker_of(a, rate, resampler, hop=300):
+    """the marks.Marker of the parsed arguments for an output of `rate` Hz behind `resampler` (or None), or None when no marks are asked for"""
+    from .marks import Marker
+    if not a.with_marks:
+        return None
+    return Marker(rate, fps=a.marks_fps if a.marks_fps is not None else 60, hop=hop, resampler=resampler)
+
+
+def marker_for(a, tts):
+    """marker_of for the attached generator and the output's rate (nothing is looked up when no marks are asked for)"""
+    return marker_of(a, a.out_rate, tts._out_resampler(a.out_rate), tts._hop()) if a.with_marks else None
+
+
+def write_marks(a, sm):
+    """the files --marks and --tracks-out name, from a marks.SpeechMarks"""
+    if a.marks is not None:
+        sm.save(a.marks, level="sentence" if a.paragraph else "word")
+        print(f"{a.marks}: {len(sm.sentences)} sentences, {len(sm.words)} words, {len(sm.tokens)} tokens")
+    if a.tracks_out is not None:
+        sm.save_tracks(a.tracks_out)
+        print(f"{a.tracks_out}: 12 tracks x {sm.tracks.shape[1]} frames at {float(sm.fps):.3f} frames per second")
 
 
 def prosody_of(a):
@@ -242,8 +283,11 @@ def main(argv=None):
             if a.save_voice:
                 voice.save(a.save_voice)
                 print(f"{a.save_voice}: voice of {a.ref_wav}")
-        audio, piece = tts.synthesis_paragraph(a.phonemes, voice=voice, prosody=a.prosody, joiner=joiner_of(a, a.out_rate), pcm16=a.pcm16,
-                                               frame_cap=a.frame_cap, sample_rate=a.out_rate)
+        marker = marker_for(a, tts)
+        audio, piece, *sm = tts.synthesis_paragraph(a.phonemes, voice=voice, prosody=a.prosody, joiner=joiner_of(a, a.out_rate), pcm16=a.pcm16,
+                                                    frame_cap=a.frame_cap, sample_rate=a.out_rate, marks=marker)
+        if sm:
+            write_marks(a, sm[0])
         write_wav(a.out, audio.numpy(), sr=a.out_rate)
         print(f"{a.out}: {audio.numel()} samples, {audio.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {piece.shape[0]} sentences")
         for b, (o0, o1, s0, s1) in enumerate(piece.tolist()):
@@ -267,14 +311,18 @@ def main(argv=None):
     elif a.voice:
         from .pipeline import Voice
         audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
-                                  sample_rate=a.out_rate, **tok)
+                                  sample_rate=a.out_rate, marks=marker_for(a, tts), **tok)
     else:
         wave_in, ref_rate = read_wav_any(a.ref_wav)
         if a.save_voice:
             tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db).save(a.save_voice)
             print(f"{a.save_voice}: voice of {a.ref_wav}")
         audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, ref_rate=ref_rate,
-                                        sample_rate=a.out_rate, trim_db=a.trim_ref_db, **tok)
+                                        sample_rate=a.out_rate, trim_db=a.trim_ref_db,
+                                        marks=marker_for(a, tts), **tok)
+    if a.with_marks:
+        audio, sm = audio
+        write_marks(a, sm)
     write_wav(a.out, audio.cpu().numpy(), sr=a.out_rate)
     print(f"{a.out}: {audio.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {tts._last_frames[0]} mel frames")
     return 0

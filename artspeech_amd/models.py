@@ -516,8 +516,10 @@ class ArtsSpeech(_Module):
         return mel
 
     def forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None,
-                       voice=None, voice_idx=None, prosody=None, token_prosody=None, token_smooth=False):
+                       voice=None, voice_idx=None, prosody=None, token_prosody=None, token_smooth=False, tracks=False):
         """`_forward_packed` (the arguments are described there), with per-token prosody around it.
+        tracks: the result also holds F0 / N / EMA, the twelve tracks the predictors hand the decoder, without the rest of `aux` (what the
+        speech marks retime: marks.Marker).
         token_prosody: [sum tok_lens, 25] controls, row i for packed token i (pipeline.Prosody.token_rows; the columns of a prosody row: a
         duration scale, then a gain and an offset per track; a device tensor is read as it is, anything else is copied to the GPU); not
         with forced.  token_smooth: the gains and offsets are control points at the tokens' centres, joined linearly inside an utterance,
@@ -527,7 +529,7 @@ class ArtsSpeech(_Module):
         returns, which is safe because torch's allocator reuses memory in the order of the current stream, the stream the kernels are on
         (the same holds for `prosody`).  A call that is captured into a graph must therefore pass a DEVICE tensor and keep it alive:
         replays read it."""
-        args = (tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames_hint, aux, out, frame_cap, voice, voice_idx, prosody)
+        args = (tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames_hint, aux, out, frame_cap, voice, voice_idx, prosody, tracks)
         if token_prosody is None:
             return self._forward_packed(*args)
         rt, L = self.rt, _lib.lib()
@@ -540,7 +542,7 @@ class ArtsSpeech(_Module):
                 L.as_plan_set_token_prosody(rt.plan, None)
 
     def _forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None,
-                        voice=None, voice_idx=None, prosody=None):
+                        voice=None, voice_idx=None, prosody=None, tracks=False):
         """The whole hot path on packed tensors (what bench.py times): one call of as_forward_test when the integer frame
         counts are known (forced durations), else as_forward_test_begin -> one device->host read of B + 1 integers ->
         as_forward_test_finish.  `out`: the dict of a previous call with the same geometry (its tensors are reused).
@@ -596,7 +598,7 @@ class ArtsSpeech(_Module):
                 n2 = max(2 * sum(frames), 1)
                 bb, mod_b = ba, _lib.AS_MOD_FORWARD_B
             io.mel_out, io.ld_out = _p(new("mel", (rt.cfg.n_mels, n2))), n2
-            if aux:
+            if aux or tracks:
                 io.F0, io.N, io.EMA, io.ld_pred = _p(new("F0", (1, n2))), _p(new("N", (1, n2))), _p(new("EMA", (10, n2))), n2
             ws_b, nb = rt.workspace("b", mod_b, bb)
             if cap is None and frames_hint is None:

@@ -322,7 +322,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
-                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None):
+                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
         attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
@@ -351,9 +351,16 @@ class ArtSpeech:
             kw["frame_cap"] = frame_cap
         if sample_rate is not None and self.generator is not None:
             kw["sample_rate"] = sample_rate
+        with_marks = marks is not None and marks is not False
+        if with_marks:
+            if self.generator is None:
+                raise RuntimeError("marks time the samples: attach_vocoder(h, checkpoint) first")
+            kw["marks"] = marks                                             # (synthesis_wav: the result is then (samples, SpeechMarks))
         out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody, token_prosody=token_prosody,
                  token_smooth=token_smooth, **kw)
-        return out[0] if single and out.dim() > 1 and self.generator is not None else out
+        out, sm = out if with_marks else (out, None)
+        out = out[0] if single and out.dim() > 1 and self.generator is not None else out
+        return (out, sm) if with_marks else out
 
     def attach_vocoder(self, h=None, checkpoint=None, runtime=False):
         """test.py:119-125: build the generator from Vocoder/config.json-style `h` and load checkpoint['generator'].
@@ -367,7 +374,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
-                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None):
+                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the generator's last kernel.
@@ -377,25 +384,40 @@ class ArtSpeech:
         More frames than room: HipLibraryError (AS_STATUS_CAPACITY).
         sample_rate (None or 24000: the generator's own samples, exactly the calls above): the samples at that rate -- the packed fp32
         samples go through resample.Resampler(24000, sample_rate) on the device before they are padded out or read back
-        ([B, max ceil(300 frames L / M)]); with pcm16 the generator writes fp32 only and the resampler writes the 16-bit samples."""
+        ([B, max ceil(300 frames L / M)]); with pcm16 the generator writes fp32 only and the resampler writes the 16-bit samples.
+        marks (True: 60 frames per second, or a marks.Marker for this chain): the call returns (samples, marks.SpeechMarks) -- when every
+        token and word is spoken, in samples and seconds from the start of its own utterance's row, and F0, energy and the articulators
+        on the animation clock (as_marks_f32 on the device results the call already has, read back with the samples)."""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         single = isinstance(phonemes, str)
         rs = self._out_resampler(sample_rate)
+        marker = self._marker(marks, sample_rate)
         if frame_cap is not None:
             if forced_durations is not None:
                 raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
             out = self._synthesis_wav_cap(phonemes, ref_mel, features, voice, prosody, pcm16, int(frame_cap), token_prosody, token_smooth,
-                                          sample_rate)
+                                          sample_rate, marker)
+            if marker is not None:
+                return (out[0][0] if single else out[0]), out[1]
             return out[0] if single else out
         mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody,
                                  token_prosody=token_prosody, token_smooth=token_smooth)
         lens = self._last_frames
+        sm = None
+        if marker is not None:
+            # every utterance a stream of its own at the prefix sums of its resampled length: the rule's own layout without pieces
+            n = [self._hop() * int(f) if rs is None else rs.out_len(self._hop() * int(f)) for f in lens]
+            off = np.concatenate([[0], np.cumsum(n)])
+            with torch.cuda.device(self.device):
+                m = self._marks_packed(marker, self._tok_off(self._last_tok_lens), self._last_aux, max(int(off[-1]), 1))
+                sm = self._speech_marks(marker, [phonemes] if single else phonemes, m, stream_off=off)
         if rs is not None:
             wav = self._generate_resampled(mel, lens, rs, pcm16)
-            return wav[0] if single else wav
-        wav = (self.generator(mel, lengths=lens, pcm16=True) if pcm16 else self.generator(mel, lengths=lens))[:, 0]
-        return wav[0] if single else wav
+        else:
+            wav = (self.generator(mel, lengths=lens, pcm16=True) if pcm16 else self.generator(mel, lengths=lens))[:, 0]
+        wav = wav[0] if single else wav
+        return wav if marker is None else (wav, sm)
 
     def _generate_resampled(self, mel, lens, rs, pcm16):
         """Generator.forward with the resampler between the generator's packed fp32 samples and the padding: mel [B, 80, T] with `lens` mel
@@ -489,7 +511,70 @@ class ArtSpeech:
         if join.rate != rate:
             raise ValueError(f"the joiner counts its milliseconds at {join.rate} Hz, the samples it is given are at {rate} Hz")
 
-    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None):
+    def _hop(self):
+        """samples per mel frame of the attached generator: the product of its up-sampling rates (300)"""
+        return int(np.prod([int(u) for u in self.generator.h["upsample_rates"]]))
+
+    def marker(self, sample_rate=None, fps=(60, 1), physical=True):
+        """a marks.Marker for what synthesis_*(sample_rate=) returns: the attached generator's hop, the output resampler's ratio and the
+        output's rate, on an animation clock of `fps` frames per second"""
+        from .marks import Marker
+        if self.generator is None:
+            raise RuntimeError("marks time the samples: attach_vocoder(h, checkpoint) first")
+        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        return Marker(rate, fps=fps, hop=self._hop(), resampler=self._out_resampler(sample_rate), physical=physical)
+
+    def _marker(self, marks, sample_rate):
+        """synthesis_*'s `marks` argument -> a marks.Marker for samples at sample_rate, or None: True makes one at 60 frames per second, a
+        Marker is checked against the chain (its rate, the resampler's ratio, the generator's hop)"""
+        from .marks import Marker
+        if marks is None or marks is False:
+            return None
+        if marks is True:
+            return self.marker(sample_rate)
+        if not isinstance(marks, Marker):
+            raise TypeError("marks: True, False or a marks.Marker")
+        if self.generator is None:
+            raise RuntimeError("marks time the samples: attach_vocoder(h, checkpoint) first")
+        rs = self._out_resampler(sample_rate)
+        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        want = (self._hop(), 1, 1, rate) if rs is None else (self._hop(), rs.L, rs.M, rate)
+        have = (marks.cfg.hop, marks.cfg.L, marks.cfg.M, marks.cfg.rate)
+        if have != want:
+            raise ValueError(f"the marker describes a chain of (hop, L, M, rate) = {have}, the samples it is to mark come from {want}")
+        return marks
+
+    def _tok_off(self, tok_lens):
+        return torch.tensor(np.concatenate([[0], np.cumsum([int(v) for v in tok_lens])]), dtype=torch.int32).to(self.device)
+
+    def _marks_packed(self, marker, tok_off, res, room, piece=None, groups=None, out_off=None):
+        """marks.Marker.forward_packed behind the acoustic model's result `res` (dur_i, frame_off, F0 / N / EMA) on the current stream;
+        room: the samples of the buffer the marks point into; piece / groups / out_off: the joiner's device results, or none"""
+        net = self.model.ArtsSpeech
+        B = res["frame_off"].numel() - 1
+        G = B if piece is None else out_off.numel() - 1
+        scale, offset = marker.affine(_stats24(net), torch.device(self.device)) if marker.physical else (None, None)
+        return marker.forward_packed(tok_off, res["dur_i"], res["frame_off"], res["F0"], res["N"], res["EMA"], piece=piece, groups=groups,
+                                     out_off=out_off, anim_cap=marker.anim_cap(room, G), scale=scale, offset=offset)
+
+    def _speech_marks(self, marker, phonemes, m, piece=None, stream_off=None):
+        """the device results of _marks_packed -> marks.SpeechMarks (copies them to the host).  piece (host [B][4]): the utterances lie in
+        joined streams, positions are absolute; stream_off (host [B + 1]): every utterance is a stream of its own, positions count from
+        its own first sample"""
+        from .marks import SpeechMarks, kept_symbols
+        syms = [kept_symbols(self.textcleaner, p) for p in phonemes]
+        anim_off = m["anim_off"].cpu().numpy()
+        n = int(anim_off[-1])
+        marks_h = m["marks"].cpu().numpy()[: sum(len(s) for s in syms)]
+        tracks, active = m["tracks"][:, :n].cpu().numpy(), m["active"][:n].cpu().numpy()
+        if piece is not None:
+            spans, origin = [(int(p[0]), int(p[1])) for p in piece], None
+        else:
+            spans, origin = [(int(stream_off[b]), int(stream_off[b + 1])) for b in range(len(syms))], [int(v) for v in stream_off[:-1]]
+        return SpeechMarks(marker.rate, marker.fps, syms, marks_h, spans, origin, tracks, active, anim_off)
+
+    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None,
+                  marks=None):
         """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
         then the capacity vocoder on its frame_off and mel.  `inputs` = packed_inputs(...).  Every call with the same inputs dict reuses
         the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
@@ -499,14 +584,25 @@ class ArtSpeech:
         join (a join.Joiner at the rate of the samples; groups / gaps / join_cap as Joiner.forward_packed and _join_packed take them): the
         joiner runs on the device offsets the chain already has -- sample_off, or the resampler's out_off -- on the same stream, and the
         call returns (stream [join_cap] fp32 or int16, out_off [G + 1], piece [B][4]) instead; with groups and gaps as device tensors (or
-        None) the chain stays capturable."""
+        None) the chain stays capturable.
+        marks (a marks.Marker for this chain: its rate, the resampler's ratio, the generator's hop): the acoustic model also hands out
+        F0 / N / EMA and as_marks_f32 runs on the same stream behind the joiner -- or behind the resampler or the generator when there is
+        none -- on the device durations, offsets and pieces the chain already has; the call returns what it returns without marks and, as
+        one more entry, the dict of Marker.forward_packed (marks [sum tok_lens][2], tracks [12][anim_cap], active, anim_off), all on the
+        device.  The chain stays capturable (after one eager call, which also uploads the token offsets); marks=None issues exactly the
+        launches of before."""
         if self.generator is None or not self.generator.runtime:
             raise RuntimeError("frame_cap needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
         if join is not None:
             self._check_joiner(join, sample_rate)
+        marker = self._marker(marks, sample_rate)
         net = self.model.ArtsSpeech
-        kw = {k: v for k, v in inputs.items() if k != "_out"}
+        kw = {k: v for k, v in inputs.items() if not k.startswith("_")}
         with torch.cuda.device(self.device):
+            if marker is not None:
+                kw["tracks"] = True
+                if "_tok_off" not in inputs:
+                    inputs["_tok_off"] = self._tok_off(inputs["tok_lens"])
             res = net.forward_packed(kw.pop("tok"), kw.pop("tok_lens"), kw.pop("mel_p"), kw.pop("f0_p"), kw.pop("ema_p"), kw.pop("ref_lens"),
                                      frame_cap=frame_cap, out=inputs.setdefault("_out", {}), **kw)
             rs = self._out_resampler(sample_rate)
@@ -515,26 +611,36 @@ class ArtSpeech:
                 x = wav[0]
                 if rs is not None:
                     x, _, off = rs.forward_packed(x, off, rs.out_len(wav.shape[1]) + off.numel() - 1)
-                return self._join_packed(join, x, off, groups, gaps, pcm16, join_cap)
+                if marker is None:
+                    return self._join_packed(join, x, off, groups, gaps, pcm16, join_cap)
+                if groups is not None:
+                    groups = join._i32(groups, torch.device(self.device), len(groups), "groups")       # (the joiner and the marker read ONE device copy)
+                stream, out_off, piece = self._join_packed(join, x, off, groups, gaps, pcm16, join_cap)
+                return stream, out_off, piece, self._marks_packed(marker, inputs["_tok_off"], res, stream.numel(), piece, groups, out_off)
             if rs is not None:
                 wav, sample_off = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len)
                 B = sample_off.numel() - 1
                 y, p16, out_off = rs.forward_packed(wav[0], sample_off, rs.out_len(wav.shape[1]) + B, pcm=pcm16, wav=not pcm16)
-                return (p16 if pcm16 else y), out_off
-            got = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len, pcm=pcm16, wav=not pcm16)
-        return (got[2] if pcm16 else got[0][0]), got[1]
+                ret = (p16 if pcm16 else y), out_off
+            else:
+                got = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len, pcm=pcm16, wav=not pcm16)
+                ret = (got[2] if pcm16 else got[0][0]), got[1]
+            if marker is not None:
+                ret = ret + (self._marks_packed(marker, inputs["_tok_off"], res, ret[0].numel()),)
+        return ret
 
     def _synthesis_wav_cap(self, phonemes, ref_mel, features, voice, prosody, pcm16, frame_cap, token_prosody=None, token_smooth=False,
-                           sample_rate=None):
+                           sample_rate=None, marker=None):
         from . import _lib
         inputs = self.packed_inputs(phonemes, ref_mel, features, voice, prosody, token_prosody, token_smooth)
-        samples, sample_off = self.chain_cap(inputs, frame_cap, pcm16=pcm16, sample_rate=sample_rate)
+        samples, sample_off, *m = self.chain_cap(inputs, frame_cap, pcm16=pcm16, sample_rate=sample_rate, marks=marker)
         with torch.cuda.device(self.device):
             off = sample_off.cpu().tolist()                                 # the one synchronisation: offsets, then the samples
             if _lib.lib().as_device_status(0):
                 raise _lib.HipLibraryError(f"synthesis_wav(frame_cap={frame_cap}) failed: a kernel reported {_lib.device_status()} "
                                            "(as_device_status); results since then are invalid")
             host = samples[: off[-1]].cpu()
+            sm = self._speech_marks(marker, [phonemes] if isinstance(phonemes, str) else phonemes, m[0], stream_off=off) if m else None
         hop = self.generator.hop
         lens = [off[b + 1] - off[b] for b in range(len(off) - 1)]
         rs = self._out_resampler(sample_rate)
@@ -543,11 +649,11 @@ class ArtSpeech:
         out = torch.zeros(len(lens), max(max(lens), 1), dtype=host.dtype)
         for b, n in enumerate(lens):
             out[b, :n] = host[off[b]: off[b + 1]]
-        return out
+        return out if marker is None else (out, sm)
 
     @torch.no_grad()
     def synthesis_paragraph(self, sentences, ref_mel=None, voice=None, prosody=None, pause_ms=None, joiner=None, sample_rate=None, pcm16=False,
-                            frame_cap=None, features=None, max_tokens=None):
+                            frame_cap=None, features=None, max_tokens=None, marks=False):
         """A paragraph as ONE stream: `sentences` is a list of phoneme strings, or one string that text.split_sentences cuts (max_tokens:
         its limit per piece).  The sentences run as one batch through the calls above (synthesis_mel and the generator, or with frame_cap
         the chain with no read-back; the resampler when sample_rate is given), then through join.Joiner on the device -- every sentence
@@ -556,7 +662,10 @@ class ArtSpeech:
         every sentence; lists of them go sentence by sentence.  joiner: a join.Joiner at the output's rate (None: Joiner(rate) with
         pause_ms, default 250); pause_ms: the pause behind a full stop -- a cut of another class gets text.PAUSE_SCALE's share of it.
         Returns (stream 1-D fp32 or int16, piece int32 [B][4] = out_start, out_end, src_start, src_end per sentence: where it landed in the
-        stream and which of its own samples were kept)."""
+        stream and which of its own samples were kept).
+        marks (True: 60 frames per second, or a marks.Marker for this chain): one more entry, a marks.SpeechMarks -- when every token, word
+        and sentence is spoken in the stream and the twelve tracks on the animation clock, with `active` 0 in the pauses -- from
+        as_marks_f32 behind the joiner, read back with the stream."""
         from . import _lib
         from .join import Joiner
         from .text import PAUSE_SCALE, split_sentences
@@ -579,9 +688,13 @@ class ArtSpeech:
         if ref_mel is not None and not isinstance(ref_mel, (list, tuple)):
             ref_mel, features = [ref_mel] * B, None if features is None else [features] * B
         rs = self._out_resampler(sample_rate)
+        marker = self._marker(marks, sample_rate)
+        m = None
         if frame_cap is not None:
             inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody)
-            stream, out_off, piece = self.chain_cap(inputs, int(frame_cap), pcm16=pcm16, sample_rate=sample_rate, join=joiner, gaps=gaps)
+            stream, out_off, piece, *m = self.chain_cap(inputs, int(frame_cap), pcm16=pcm16, sample_rate=sample_rate, join=joiner, gaps=gaps,
+                                                        marks=marker)
+            m = m[0] if m else None
         else:
             from .models import pack
             from .vocoder import layout
@@ -593,12 +706,17 @@ class ArtSpeech:
                 if rs is not None:
                     x, _, off = rs.forward_packed(x, off, max(sum(rs.out_len(n) for n in lay_w.widths_host), 1))
                 stream, out_off, piece = self._join_packed(joiner, x.contiguous(), off, None, gaps, pcm16)
+                if marker is not None:
+                    m = self._marks_packed(marker, self._tok_off(self._last_tok_lens), self._last_aux, stream.numel(), piece, None, out_off)
         with torch.cuda.device(self.device):
             n = int(out_off.cpu()[-1])                                      # the one synchronisation: the length, then the stream
             if _lib.lib().as_device_status(0):
                 raise _lib.HipLibraryError(f"synthesis_paragraph failed: a kernel reported {_lib.device_status()} (as_device_status); "
                                            "results since then are invalid")
-            return stream[:n].cpu(), piece.cpu()
+            if marker is None:
+                return stream[:n].cpu(), piece.cpu()
+            piece_h = piece.cpu()
+            return stream[:n].cpu(), piece_h, self._speech_marks(marker, sentences, m, piece=piece_h.tolist())
 
     @torch.no_grad()
     def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None,
@@ -649,6 +767,7 @@ class ArtSpeech:
                                          return_aux=True, voice=table, voice_idx=vidx, prosody=rows, token_prosody=trows,
                                          token_smooth=token_smooth)                                                   # test.py:113
         self._last_frames = list(aux["frames2"])
+        self._last_aux, self._last_tok_lens = aux, tl                  # (device results the speech marks read: dur_i, frame_off, F0 / N / EMA)
         return mel
 
     @torch.no_grad()

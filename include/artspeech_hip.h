@@ -991,6 +991,66 @@ int as_join_f32(const as_join_cfg* cfg, int B, const as_join_io* io, void* ws, s
 int as_join_measure_f32(const as_join_cfg* cfg, int B, const as_join_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
 int as_join_host(const as_join_cfg* cfg, int B, const as_join_io* io);
 
+/* ---- speech marks (csrc/marks.hip; the rule: csrc/marks_rule.h) ---------------------------------------------------
+ * When every token is spoken in the samples the caller receives, and the twelve tracks the predictors hand the decoder (F0, N, EMA 0..9)
+ * retimed onto an animation clock of fps_num / fps_den frames per second of those samples -- behind the duration rounding, the hop, the
+ * resampler's ceil(n L / M) and the joiner's trim and placement, all of which exist on the device only.
+ * as_marks_cfg: hop = samples per full-rate column at 24 kHz (as_vocoder_hop), L / M = the resampler's ratio (as_resampler_info; 1 / 1
+ * without one), rate = samples per second of the final stream, fps_num / fps_den = the animation clock (30000 / 1001 is exact).
+ * The rule.  fcap = min(ld_pred / 2, 2^24) with tracks, else 2^24.  Utterance b: f0 = clamp(frame_off[b], 0, fcap), f1 = clamp(frame_off[b + 1],
+ * f0, fcap), its columns are [col0, col0 + W_b) with col0 = 2 f0, W_b = 2 (f1 - f0); r(p) = ceil(p L / M); n_b = min(r(hop W_b), 2^30).
+ * Placement with `piece` (an as_join_f32 result, with the G, group_off and out_off of that call): utterance b lies in stream grp_b = the
+ * number of inner cuts group_off[1 .. G) at or below b (no group_off: G = 1), stream g = [s_g, e_g) = out_off[g], out_off[g + 1] clamped to
+ * [0, 2^30] and e_g >= s_g; os = clamp(out_start, s_g, e_g), oe = clamp(out_end, os, e_g), ss = clamp(src_start, 0, n_b), se = clamp(src_end, ss,
+ * n_b), m = min(oe - os, se - ss): kept samples [ss, ss + m) at [os, os + m); the pieces of a stream ascend.  Without `piece`: G = B, every
+ * utterance is a stream of its own at the prefix sums of n_b (= as_vocoder_cap.sample_off, or as_resample_f32's out_off), ss = 0, m = n_b.
+ * Token marks: the tokens of utterance b are [t0, t1) = tok_off[b], tok_off[b + 1] clamped to [0, n_tokens] and ascending, d_k = max(dur_i[k],
+ * 0), e_k = min(sum of d over [t0, k), W_b / 2); mark(e) = os + clamp(r(2 hop e) - ss, 0, m); marks[k] = {mark(e_k), mark(min(e_k + d_k,
+ * W_b / 2))}, absolute sample positions in the output buffer, monotone inside an utterance; a token the trim removed entirely has start ==
+ * end.  Packed tokens outside every [t0, t1) are not written.
+ * Tracks: stream g has n_g = floor((e_g - s_g - 1) num / (rate den)) + 1 frames (0 when empty), anim_off = their prefix sums; frame m stands at
+ * q = s_g + m den rate / num, exactly: Q = m den rate + s_g num.  b* = the last piece of the stream with os num <= Q; Q < oe(b*) num: inside,
+ * active = 1: A = (Q - (os - ss) num) M, D = num L hop, x = (2 A - D) / (2 D) (column j has its midpoint at j + 1/2), j = floor(x); j < 0:
+ * column 0; j >= W_b - 1: column W_b - 1; else w = fp32(double(2 A - D - 2 D j) / double(2 D)) clamped to [0, 1] and the value of track c is
+ * fmaf(w, v[j + 1] - v[j], v[j]), v[j] = row c at column col0 + j.  Else active = 0; a / c = the nearest non-empty piece of the stream at or
+ * before / behind b*; E_a = a's value at A = se num M, S_c = c's value at A = ss num M; both: fmaf(wg, S_c - E_a, E_a) with
+ * wg = fp32(double(Q - oe_a num) / double((os_c - oe_a) num)) clamped to [0, 1]; only c (the lead): S_c; only a (the tail): E_a; neither
+ * (a stream without a non-empty piece): 0.  scale / offset (both or neither, [12]): every value but those zeros becomes
+ * fmaf(scale[c], value, offset[c]).  tracks and active in [anim_off[G], anim_cap) are 0.
+ * as_marks_io: DEVICE pointers.  Inputs: tok_off [B + 1] and dur_i [n_tokens] (read for marks only), frame_off [B + 1], F0 / N / EMA with
+ * ld_pred (as_forward_io's, read for tracks only); optional piece [B] with G, group_off [G + 1] or NULL, out_off [G + 1] (required with
+ * piece); optional scale, offset.  Outputs, each optional, at least one: marks [n_tokens][2] (8-byte aligned), tracks [12][ld_tracks >=
+ * anim_cap], active [anim_cap], anim_off [G + 1] ([B + 1] without piece).
+ * as_marks_f32          at most three launches (layout, token marks, tracks), sized by B, n_tokens and anim_cap: nothing is read back,
+ *                       uploaded or allocated and no call synchronises -- every call, the first included, can be captured into a hipGraph and
+ *                       replayed with other durations, pieces and tracks.  The frames need more than anim_cap, or an offset, a piece or a
+ *                       stream had to be clamped: AS_STATUS_CAPACITY -- the layout is cut at the capacities, nothing is read or stored out of
+ *                       bounds, and that call's output is void.
+ * as_marks_host         the same rule on HOST arrays (every pointer of io is a host pointer; no GPU, no workspace); AS_ENOSPC where the
+ *                       device raises AS_STATUS_CAPACITY.
+ * AS_EINVAL before anything is launched: cfg, io, ws or frame_off NULL; no output; marks without tok_off / dur_i; piece without out_off, or
+ * without group_off and G != 1; tracks without F0 / N / EMA, with ld_pred < 2 or ld_tracks < anim_cap; tracks or active with anim_cap < 1;
+ * one of scale and offset; outside the rule's limits: hop in [1, 2^16], L, M in [1, 2^12], rate in [1, 2^20], fps_num, fps_den in [1, 2^16],
+ * B in [1, 2^20], n_tokens, anim_cap in [0, 2^30], G in [1, 4096] with piece.  AS_ENOSPC: ws_bytes below as_marks_workspace_bytes(B,
+ * n_tokens, cfg) (0 for arguments it refuses).  AS_EDEVICE while a status bit is set. */
+typedef struct as_marks_cfg {
+    int32_t hop, L, M, rate, fps_num, fps_den;
+} as_marks_cfg;
+typedef struct as_marks_io {
+    const int32_t* tok_off; const int32_t* dur_i;
+    const int32_t* frame_off;
+    const float* F0; const float* N; const float* EMA; int32_t ld_pred;
+    const as_join_piece* piece; int32_t G; const int32_t* group_off; const int32_t* out_off;
+    const float* scale; const float* offset;
+    int32_t* marks;
+    float* tracks; int32_t ld_tracks; int32_t anim_cap;
+    uint8_t* active;
+    int32_t* anim_off;
+} as_marks_io;
+size_t as_marks_workspace_bytes(int B, int n_tokens, const as_marks_cfg* cfg);
+int as_marks_f32(const as_marks_cfg* cfg, int B, int n_tokens, const as_marks_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_marks_host(const as_marks_cfg* cfg, int B, int n_tokens, const as_marks_io* io);
+
 /* ---- prosody transfer (csrc/dtw.hip, csrc/dtw_rule.h) -------------------------------------------------------------
  * Speak a sentence the way a recording of it was spoken: synthesise it once (pass A), warp pass A's mel onto the recording's log-mel
  * (dynamic time warping, frame by frame), turn the warp into one prosody row per token (as_plan_set_token_prosody's rows: a duration scale
