@@ -318,6 +318,21 @@ _SIGNATURES.update({
 })
 
 
+class FitC(ctypes.Structure):
+    """as_fit (as_plan_set_fit, as_fit_durations_f32: DEVICE pointers; as_fit_host: host pointers): spans of tokens and their targets"""
+    _fields_ = [("span_tok", c_p), ("span_frames", c_p), ("lock", c_p), ("n_spans", ctypes.c_int32), ("max_count", ctypes.c_int32)]
+
+
+AS_FIT_MAX_SPANS, AS_FIT_MAX_COUNT = 4096, 4096
+_pFit = ctypes.POINTER(FitC)
+_SIGNATURES.update({
+    "as_plan_set_fit": (c_i, [c_p, _pFit]),
+    "as_fit_workspace_bytes": (c_sz, [c_i, _pFit]),
+    "as_fit_durations_f32": (c_i, [c_p, c_p, c_i, c_i, _pFit, c_p, c_p, c_p, c_sz, c_p]),
+    "as_fit_host": (c_i, [c_p, c_p, c_i, c_i, _pFit, c_p, c_p]),
+})
+
+
 AS_DTW_MAX_T, AS_DTW_MAX_C = 4096, 128
 
 

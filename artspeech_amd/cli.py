@@ -24,6 +24,10 @@ utterance: ``--emphasis FIRST:LAST:SEMITONES[:SPEED[:DB]]`` (repeatable) raises 
 phoneme string, inclusive) by SEMITONES, speaks them at SPEED (0.5 = twice as long: a stressed word, a longer pause on a comma) and DB louder;
 ``--smooth-prosody`` glides between the tokens' settings instead of stepping.
 
+When it is spoken: ``--fit-seconds S`` says the utterance in exactly S seconds, ``--fit FIRST:LAST:SECONDS`` (repeatable) tokens FIRST..LAST
+in exactly SECONDS, both to the 25 ms of a half-rate frame (pipeline.Fit, as_plan_set_fit); ``--hold-pauses`` keeps spaces and punctuation
+at their predicted lengths.  Not with ``--paragraph`` (the indices count one utterance's tokens) nor with ``--like-wav``.
+
 Like a recording: ``--like-wav said.wav`` is a recording of the SAME phonemes (any speaker, any rate the resampler takes); the sentence is
 synthesised once, warped onto the recording on the device (as_dtw_features_f32) and synthesised again with the recording's rhythm and
 melody (pipeline.ArtSpeech.synthesis_like).  ``--like-tracks timing,pitch,energy,ema`` says what is taken over (default
@@ -35,6 +39,7 @@ mark), ``.srt`` or ``.vtt`` (subtitles) -- and ``--tracks-out PATH.npz`` the pit
 """
 import argparse
 import json
+import math
 import sys
 import wave
 
@@ -89,6 +94,13 @@ def build_parser():
     ap.add_argument("--emphasis", action="append", default=[], metavar="FIRST:LAST:SEMITONES[:SPEED[:DB]]",
                     help="tokens FIRST..LAST (inclusive) of the phoneme string: pitch raised by SEMITONES, spoken at SPEED (default 1), DB louder "
                          "(default 0); repeatable, a later span replaces an earlier one where they overlap")
+    ap.add_argument("--fit-seconds", type=float, metavar="S", help="say the utterance in exactly S seconds (to 25 ms: rint(40 S) frames of 600 "
+                    "samples at 24 kHz); the durations stay proportional to what the predictor and --speed / --emphasis ask for")
+    ap.add_argument("--fit", action="append", default=[], metavar="FIRST:LAST:SECONDS",
+                    help="say tokens FIRST..LAST (indices into the cleaned phoneme string, inclusive) in exactly SECONDS; repeatable, the spans "
+                         "must not overlap")
+    ap.add_argument("--hold-pauses", action="store_true", help="with --fit-seconds / --fit: spaces and punctuation keep their predicted lengths, "
+                    "the speech absorbs the difference")
     ap.add_argument("--smooth-prosody", action="store_true", help="with --emphasis: glide linearly between the tokens' settings (centre to centre)")
     ap.add_argument("--like-wav", metavar="PATH", help="a recording of the same phonemes, mono PCM wav: speak with its timing and melody "
                     "(the synthesis is warped onto it on the device: as_dtw_features_f32, as_transfer_rows_f32)")
@@ -153,6 +165,15 @@ def parse_args(argv=None):
         ap.error("--like-wav is a recording of one utterance: not with --paragraph")
     if a.like_wav and a.frame_cap is not None:
         ap.error("--like-wav reads the first pass's frame counts back: not with --frame-cap")
+    a.with_fit = a.fit_seconds is not None or bool(a.fit)
+    if a.fit_seconds is not None and a.fit:
+        ap.error("--fit-seconds fits the whole utterance, --fit spans of it: one of them")
+    if a.hold_pauses and not a.with_fit:
+        ap.error("--hold-pauses needs --fit-seconds or --fit")
+    if a.paragraph and a.with_fit:
+        ap.error("--fit-seconds and --fit count the tokens of one utterance: not with --paragraph")
+    if a.like_wav and a.with_fit:
+        ap.error("--like-wav takes its timing from the recording: not with --fit-seconds / --fit")
     a.like_tracks = a.like_tracks if a.like_tracks is not None else "timing,pitch,energy"
     if a.marks is not None and not a.marks.lower().endswith((".jsonl", ".srt", ".vtt")):
         ap.error("--marks writes .jsonl, .srt or .vtt")
@@ -166,6 +187,11 @@ def parse_args(argv=None):
             marker_of(a, a.out_rate, None)
         a.prosody = prosody_of(a)
         a.spans = emphasis_spans(a.emphasis)
+        a.fit_spans = fit_spans(a.fit)
+        from .fit import seconds_to_frames
+        for s in ([] if a.fit_seconds is None else [a.fit_seconds]) + [sp[3] for sp in a.fit_spans]:
+            if not (math.isfinite(s) and seconds_to_frames(s) >= 1):
+                raise ValueError("--fit-seconds and --fit take a time of at least one frame (25 ms)")
         transfer_of(a)
     except ValueError as e:
         ap.error(str(e))
@@ -239,6 +265,40 @@ def emphasis_spans(specs):
     return spans
 
 
+def fit_spans(specs):
+    """--fit FIRST:LAST:SECONDS strings -> [(0, first, last, seconds)] (the one utterance of a command line)"""
+    spans = []
+    for spec in specs:
+        parts = spec.split(":")
+        if len(parts) != 3:
+            raise ValueError(f"--fit {spec}: expected FIRST:LAST:SECONDS")
+        try:
+            first, last, seconds = int(parts[0]), int(parts[1]), float(parts[2])
+        except ValueError:
+            raise ValueError(f"--fit {spec}: FIRST and LAST are token indices, SECONDS a number") from None
+        if first < 0 or last < first:
+            raise ValueError(f"--fit {spec}: 0 <= FIRST <= LAST")
+        if not seconds > 0:
+            raise ValueError(f"--fit {spec}: SECONDS > 0")
+        spans.append((0, first, last, seconds))
+    return spans
+
+
+def fit_of(a, tts=None):
+    """the pipeline.Fit of the parsed --fit-seconds / --fit / --hold-pauses, or None without them.  tts: the fit is also built once for this
+    phoneme string (fit.Fit.build), so that a span outside the utterance's tokens, overlapping spans or fewer frames than tokens raise
+    ValueError here and not inside the synthesis"""
+    from .fit import Fit
+    if not a.with_fit:
+        return None
+    hold = Fit.hold_pauses if a.hold_pauses else None
+    f = Fit.whole(a.fit_seconds, hold=hold) if a.fit_seconds is not None else Fit(a.fit_spans, hold=hold)
+    if tts is not None:
+        ids = tts.textcleaner(a.phonemes)
+        f.build([len(ids)], [ids])
+    return f
+
+
 def token_prosody_of(a, tts):
     """the per-token settings of the parsed --emphasis spans for this phoneme string (pipeline.Prosody.from_spans), or None without spans"""
     from .pipeline import Prosody
@@ -273,6 +333,11 @@ def main(argv=None):
         tok = dict(token_prosody=token_prosody_of(a, tts), token_smooth=a.smooth_prosody)
     except ValueError as e:
         ap.error(f"--emphasis: {e}")
+    try:
+        if a.with_fit:
+            tok["fit"] = fit_of(a, tts)
+    except ValueError as e:
+        ap.error(f"--fit-seconds / --fit: {e}")
     if a.paragraph:
         from .pipeline import Voice
         if a.voice:

@@ -106,6 +106,12 @@ int as_token_starts_launch(const int32_t* dur_i32, int ntok, int32_t* start, hip
 // fmaf(gain, x, offset) with its column's gains and offsets by token_prosody.h's rule; tof [n_frames_max] = the frame -> token map
 int as_token_tracks_launch(float* fne, int ld, int n_cols, const int32_t* tof, int n_frames_max, const int32_t* frame_off, const int32_t* tok_off,
                            int B, int ntok, const int32_t* start, const float* rows, int ld_rows, int smooth, hipStream_t stream);
+// fit to time (as_plan_set_fit; duration_fit.hip, the rule: duration_fit.h).  as_fit_durations_f32 on v[i] * pros[utterance of i]
+// [AS_PROSODY_DUR] (pros NULL: on v itself): dur_i [ntok] for every token, the spans' tokens fitted; ws: as_fit_workspace_bytes
+struct as_fit;
+bool as_fit_valid(const as_fit* fit);
+int as_fit_launch(const float* v, const float* pros, int ld_pros, const int32_t* tok_off, int B, int ntok, const as_fit& fit, int32_t* dur_i,
+                  int32_t* span_scale_q16, void* ws, hipStream_t stream);
 
 // fp32 samples w [N] -> 16-bit PCM by the rule of as_conv_post_pcm_f32 (vocoder.hip; a NaN stores 0 and raises AS_STATUS_F16_RANGE).
 // n_valid (a capacity layout, device count): samples [*n_valid, N) are not read; pcm and w_fill (each may then be NULL) get 0 there

@@ -1747,6 +1747,9 @@ struct PhaseA {                   // what the first half leaves in workspace A f
     // buffers live in workspace A, so that workspace B is laid out exactly as without controls
     float* dur_s = nullptr;
     int32_t* tok_start = nullptr;
+    // fit to time (as_plan_set_fit; NULL without): the fitted durations and the fit launches' workspace, in workspace A for the same reason
+    int32_t* fit_dur = nullptr;
+    void* fit_ws = nullptr;
     const Lay *tok = nullptr, *ref = nullptr;
     bool voice = false;           // voice mode (as_forward_io.voices): no reference layout, no feat12
     bool ok() const { return tok && (ref || voice); }
@@ -1761,14 +1764,36 @@ int voice_dim(const as_model& m) { return 2 * m.cfg.style_dim + m.cfg.style_dim 
 
 // round half even -> clamp to [1, 16384] (or the forced durations), frame offsets, the frame -> token map: one launch.  Per-token prosody
 // (tp.rows: as_plan_set_token_prosody) puts one launch in front of it that writes the predictor's durations times the token's scale -- and the
-// utterance's, io->prosody -- into dur_s, which the same durations launch then reads in place of them.
-void durations_launch(Ctx& c, const as_token_prosody& tp, float* dur_s, const float* duration, const as_forward_io* io, const Lay* tok,
-                      int32_t* dur_i, int32_t* frame_off, int32_t* tof, int max_frames)
+// utterance's, io->prosody -- into dur_s, which the same durations launch then reads in place of them.  A fit (c.p.fit: as_plan_set_fit) puts
+// its two launches between them: they round the controlled durations -- dur_s, or the predictor's under io->prosody -- into A.fit_dur, the
+// spans' tokens fitted to their targets, and the durations launch takes those as forced durations.
+void durations_launch(Ctx& c, const as_token_prosody& tp, const PhaseA& A, const as_forward_io* io, int32_t* dur_i, int32_t* frame_off, int32_t* tof,
+                      int max_frames)
 {
+    const Lay* tok = A.tok;
+    float* dur_s = A.dur_s;
+    const float* duration = A.duration;
     const int B = tok->B, ntok = tok->N;
     const int32_t *tok_off = tok->d_off, *forced = io->forced_dur;
     const float* pros = io->prosody;
     const int ld_pros = io->ld_prosody;
+    if (c.p.fit.n_spans) {
+        // (locals, not c.p.fit / A: a recorded RUN copies what the call names into its closure)
+        const as_fit fit = c.p.fit;
+        int32_t* fit_dur = A.fit_dur;
+        void* fit_ws = A.fit_ws;
+        if (forced || !fit_dur || !fit_ws) { c.fail(AS_EINVAL); return; }    // (forced durations would ignore the targets)
+        if (tp.rows) {
+            const float* rows = tp.rows;
+            const int ld = tp.ld;
+            RUN(c, as_token_dur_scale_launch(duration, rows, ld, tok_off, B, ntok, pros, ld_pros, dur_s, c.s));
+            RUN(c, as_fit_launch(dur_s, nullptr, 0, tok_off, B, ntok, fit, fit_dur, nullptr, fit_ws, c.s));
+        } else {
+            RUN(c, as_fit_launch(duration, pros, ld_pros, tok_off, B, ntok, fit, fit_dur, nullptr, fit_ws, c.s));
+        }
+        RUN(c, as_durations_prosody_launch(nullptr, fit_dur, tok_off, B, nullptr, 0, dur_i, frame_off, tof, max_frames, c.s));
+        return;
+    }
     if (!tp.rows) {
         RUN(c, as_durations_prosody_launch(duration, forced, tok_off, B, pros, ld_pros, dur_i, frame_off, tof, max_frames, c.s));
         return;
@@ -1835,6 +1860,10 @@ PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
         A.dur_s = c.f32(Nt);
         A.tok_start = c.i32((size_t)Nt + 1);
     }
+    if (c.p.fit.n_spans) {
+        A.fit_dur = c.i32(Nt);
+        A.fit_ws = c.raw_alloc(as_fit_workspace_bytes(Nt, &c.p.fit));
+    }
     if (c.go()) c.p.mark(0, c.s);
     StyleIn si;
     if (A.voice) {
@@ -1890,7 +1919,7 @@ PhaseA forward_a(Ctx& c, const as_batch* batch, const as_forward_io* io)
     // (with the frame counts given nobody reads this half's copy: the second half computes durations, offsets and the frame -> token map)
     // (... and so does a call under a frame capacity, as_forward_io.frame_cap)
     if (!batch->frames && io->frame_cap <= 0)
-        durations_launch(c, tp, A.dur_s, A.duration, io, A.tok, A.dur_i, A.frame_off, nullptr, 0);
+        durations_launch(c, tp, A, io, A.dur_i, A.frame_off, nullptr, 0);
     return A;
 }
 
@@ -1993,7 +2022,8 @@ void forward_b(Ctx& c, const PhaseA& A, const as_batch* batch, const as_forward_
     if (tp.rows && (segs || !dur_s || !tok_start)) { c.fail(AS_EINVAL); return; }   // (merged calls never carry token controls)
     if (io->dur_i) dur_i = io->dur_i;
     if (io->frame_off && !segs) frame_off = io->frame_off;
-    durations_launch(c, tp, dur_s, A.duration, io, A.tok, dur_i, frame_off, tof, N1);
+    if (c.p.fit.n_spans && segs) { c.fail(AS_EINVAL); return; }           // (merged calls never carry a fit)
+    durations_launch(c, tp, A, io, dur_i, frame_off, tof, N1);
     if (tp.rows) RUN(c, as_token_starts_launch(dur_i, ntok, tok_start, c.s));
     if (dyn && !dyn_geometry(c, segs, lay1, lay2, B, io->frame_cap, frame_off, tof)) return;
     float* a_ex = c.f32((size_t)C * std::max(N1, 1));
@@ -2055,6 +2085,7 @@ bool forward_ok(const as_model* m, const as_plan* p, const as_batch* batch, cons
     if (!io || !batch_ok(batch, true, !io->voices, frames)) return false;
     if (io->prosody && (io->ld_prosody < AS_PROSODY_DIM || io->forced_dur)) return false;   // (forced durations would ignore dur_scale)
     if (p->tok_pros.rows && (io->forced_dur || io->segs)) return false;                      // (per-token prosody: the same reason; no merged calls)
+    if (p->fit.n_spans && (io->forced_dur || io->segs)) return false;                        // (a fit: forced durations would ignore the targets)
     if (!io->voices) return io_ok(io, need_out);
     return io->tokens && (!need_out || io->mel_out) && io->ld_voice >= voice_dim(*m) && io->n_voices >= 1 && !io->feat12;
 }
@@ -2354,6 +2385,18 @@ extern "C" int as_plan_set_token_prosody(as_plan* p, const as_token_prosody* tp)
     }
     if (!tp->rows || tp->ld < AS_PROSODY_DIM || (tp->smooth != 0 && tp->smooth != 1)) return AS_EINVAL;
     p->tok_pros = *tp;
+    return AS_OK;
+}
+
+extern "C" int as_plan_set_fit(as_plan* p, const as_fit* fit)
+{
+    if (!p) return AS_EINVAL;
+    if (!fit) {
+        p->fit = as_fit{nullptr, nullptr, nullptr, 0, 0};
+        return AS_OK;
+    }
+    if (!as_fit_valid(fit)) return AS_EINVAL;
+    p->fit = *fit;
     return AS_OK;
 }
 

@@ -126,6 +126,7 @@ struct as_plan {
     bool timing = false;                  // record phase marks on the calling stream (as_plan_phase_ms)
     int n_prod = 3;                       // matrix-core products per fp32 product (as_plan_set_operand_mode)
     as_token_prosody tok_pros = {nullptr, 0, 0};   // per-token prosody of this plan's forwards (as_plan_set_token_prosody); rows NULL: off
+    as_fit fit = {nullptr, nullptr, nullptr, 0, 0};   // fit to time of this plan's forwards (as_plan_set_fit); n_spans 0: off
     hipEvent_t marks[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     void mark(int i, hipStream_t s)
     {

@@ -24,8 +24,10 @@ Prosody: ``prosody=`` (a [B, 25] tensor, pipeline.Prosody rows) on the same call
 scaled before they are rounded) and a gain and an offset for each of the twelve tracks the decoder reads (F0, energy, EMA0..9, normalised).
 ``token_prosody=`` (a [sum tok_lens, 25] tensor, pipeline.Prosody.token_rows) on ``forward`` / ``forward_packed`` does the same per TOKEN
 (as_plan_set_token_prosody: stress a word, lengthen a pause); ``token_smooth=True`` joins the tokens' gains and offsets linearly between
-the tokens' centres.  The lanes do not carry it.
+the tokens' centres.  The lanes do not carry it.  ``fit=`` (a fit.Fit or fit.Built) on ``forward`` / ``forward_packed`` gives spans of
+tokens an exact number of frames (as_plan_set_fit); the lanes do not carry that either.
 """
+import contextlib
 import ctypes
 import hashlib
 
@@ -249,6 +251,33 @@ def _token_prosody_args(rt, token_prosody, n_tok, smooth):
     tp = _lib.TokenProsody()
     tp.rows, tp.ld, tp.smooth = p, ld, int(bool(smooth))
     return tp, keep
+
+
+def _fit_args(rt, f, tok, tok_lens):
+    """fit -> the as_fit of as_plan_set_fit, the tensors to keep alive and the frame counts the host knows (or None).  f: a fit.Fit (built
+    here for this batch; a hold= predicate reads the token ids back from `tok`) or a fit.Built, whose arrays may be device tensors already
+    (a captured call: replays read them, new targets included)."""
+    from . import fit as fit_mod
+    tok_lens = [int(v) for v in tok_lens]
+    if isinstance(f, fit_mod.Fit):
+        ids = None
+        if callable(f.hold):
+            ids = list(torch.split(tok.reshape(-1)[: sum(tok_lens)].cpu(), tok_lens))
+        f = f.build(tok_lens, ids)
+    if not isinstance(f, fit_mod.Built):
+        raise TypeError("fit: expected a fit.Fit or a fit.Built")
+
+    def dev(a):
+        return None if a is None else torch.as_tensor(a).to(device=rt.device, dtype=torch.int32).contiguous()
+
+    keep = [dev(f.span_tok), dev(f.span_frames), dev(f.lock)]
+    n_spans = int(keep[0].shape[0])
+    if keep[0].dim() != 2 or keep[0].shape[1] != 2 or keep[1].numel() != n_spans or (keep[2] is not None and keep[2].numel() != sum(tok_lens)):
+        raise ValueError("fit: span_tok [n_spans, 2], span_frames [n_spans] and lock [sum tok_lens] expected")
+    fc = _lib.FitC()
+    fc.span_tok, fc.span_frames, fc.lock = keep[0].data_ptr(), keep[1].data_ptr(), None if keep[2] is None else keep[2].data_ptr()
+    fc.n_spans, fc.max_count = n_spans, int(f.max_count)
+    return fc, keep, f.frames_hint
 
 
 def _no_token_prosody(token_prosody):
@@ -481,12 +510,13 @@ class ArtsSpeech(_Module):
         return v
 
     def forward(self, batch, s2s_attn=None, s2s_attn_mono=None, step="test", mode="train", epoch=0, features=None,
-                forced_durations=None, return_aux=False, voice=None, voice_idx=None, prosody=None, token_prosody=None, token_smooth=False):
+                forced_durations=None, return_aux=False, voice=None, voice_idx=None, prosody=None, token_prosody=None, token_smooth=False, fit=None):
         """voice: a [V, voice_dim] table of compute_voice rows -- utterance b then speaks in row voice_idx[b] (None: row b), and the batch's
         mels / mel_input_length are not read (they may be None).
         prosody: [B, 25] rows of pipeline.Prosody (as_forward_io.prosody: speaking rate, then a gain and an offset per F0 / energy / EMA
         track); not with forced_durations.
-        token_prosody / token_smooth: the same per token, [sum input_lengths, 25] in packed order (see `forward_packed`)."""
+        token_prosody / token_smooth: the same per token, [sum input_lengths, 25] in packed order (see `forward_packed`).
+        fit: spans of tokens spoken in an exact number of frames (a fit.Fit or fit.Built; see `forward_packed`); not with forced_durations."""
         if step != "test":
             raise NotImplementedError("training branches (step='first'/'second') are out of scope (SURVEY.md section 2)")
         if self.rt is None:
@@ -509,14 +539,14 @@ class ArtsSpeech(_Module):
                 forced = torch.cat(fd).to(device=dev, dtype=torch.int32)
                 frames = [int(f.sum()) for f in fd]
             out = self.forward_packed(tok, tl, mel_p, f0_p, ema_p, ml, forced=forced, frames_hint=frames, aux=return_aux, voice=voice,
-                                      voice_idx=voice_idx, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth)
+                                      voice_idx=voice_idx, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth, fit=fit)
             mel = unpack(out["mel"], layout(out["frames2"], dev))
         if return_aux:
             return mel, out
         return mel
 
     def forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None,
-                       voice=None, voice_idx=None, prosody=None, token_prosody=None, token_smooth=False, tracks=False):
+                       voice=None, voice_idx=None, prosody=None, token_prosody=None, token_smooth=False, tracks=False, fit=None):
         """`_forward_packed` (the arguments are described there), with per-token prosody around it.
         tracks: the result also holds F0 / N / EMA, the twelve tracks the predictors hand the decoder, without the rest of `aux` (what the
         speech marks retime: marks.Marker).
@@ -528,18 +558,35 @@ class ArtsSpeech(_Module):
         controlled durations.  A tensor that is not on the GPU is copied there for this call only: the copy is released when the call
         returns, which is safe because torch's allocator reuses memory in the order of the current stream, the stream the kernels are on
         (the same holds for `prosody`).  A call that is captured into a graph must therefore pass a DEVICE tensor and keep it alive:
-        replays read it."""
-        args = (tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames_hint, aux, out, frame_cap, voice, voice_idx, prosody, tracks)
-        if token_prosody is None:
-            return self._forward_packed(*args)
+        replays read it.
+        fit: a fit.Fit (or what its `build` made for this batch: fit.Built): spans of tokens spoken in an exact number of frames
+        (as_plan_set_fit), state of the plan like the per-token controls and set and cleared around the call in the same way; not with
+        forced.  Where the spans cover every utterance end to end (and nothing is held) the frame counts are the targets' sums: without
+        frames_hint or frame_cap the call then goes out as one as_forward_test with no read-back.  The result's `fit_frames_known` says
+        whether it did."""
         rt, L = self.rt, _lib.lib()
-        with torch.cuda.device(rt.device):
-            tp, _keep = _token_prosody_args(rt, token_prosody, sum(int(v) for v in tok_lens), token_smooth)
-            check(L.as_plan_set_token_prosody(rt.plan, ctypes.byref(tp)), "as_plan_set_token_prosody")
-            try:
-                return self._forward_packed(*args)
-            finally:
-                L.as_plan_set_token_prosody(rt.plan, None)
+        if token_prosody is None and fit is None:
+            return self._forward_packed(tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames_hint, aux, out, frame_cap, voice, voice_idx,
+                                        prosody, tracks)
+        with torch.cuda.device(rt.device), contextlib.ExitStack() as undo:
+            known = False
+            if fit is not None:
+                if forced is not None:
+                    raise ValueError("fit: not with forced durations (they would ignore the targets)")
+                fc, _keep_fit, hint = _fit_args(rt, fit, tok, tok_lens)
+                if frames_hint is None and frame_cap is None and hint is not None:
+                    frames_hint, known = hint, True
+                check(L.as_plan_set_fit(rt.plan, ctypes.byref(fc)), "as_plan_set_fit")
+                undo.callback(L.as_plan_set_fit, rt.plan, None)
+            if token_prosody is not None:
+                tp, _keep = _token_prosody_args(rt, token_prosody, sum(int(v) for v in tok_lens), token_smooth)
+                check(L.as_plan_set_token_prosody(rt.plan, ctypes.byref(tp)), "as_plan_set_token_prosody")
+                undo.callback(L.as_plan_set_token_prosody, rt.plan, None)
+            res = self._forward_packed(tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced, frames_hint, aux, out, frame_cap, voice, voice_idx,
+                                       prosody, tracks)
+            if fit is not None:
+                res["fit_frames_known"] = known
+            return res
 
     def _forward_packed(self, tok, tok_lens, mel_p, f0_p, ema_p, ref_lens, forced=None, frames_hint=None, aux=False, out=None, frame_cap=None,
                         voice=None, voice_idx=None, prosody=None, tracks=False):

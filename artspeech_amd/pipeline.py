@@ -15,6 +15,10 @@ How a sentence is spoken: ``Prosody(speed=, pitch_semitones= / pitch_factor=, en
 (as_forward_io.prosody) with the model's own normalisation statistics.  Inside an utterance: ``token_prosody=`` takes one entry per
 utterance, each a list with a Prosody (or None) per token -- ``Prosody.from_spans`` builds it from (utterance, first token, last token,
 Prosody) spans -- and ``token_smooth=True`` glides between the tokens' settings instead of stepping (as_plan_set_token_prosody).
+
+When it is spoken: ``fit=Fit.whole(2.4)`` says the utterance in exactly 2.40 s, ``fit=Fit([(utterance, first token, last token, seconds)])``
+gives spans of tokens their time, ``hold=Fit.hold_pauses`` keeps the pauses as predicted (fit.py; as_plan_set_fit).  The durations stay
+proportional to what the predictor and the controls above ask for.
 """
 import json
 import math
@@ -23,6 +27,7 @@ import numpy as np
 import torch
 
 from . import models
+from .fit import Fit
 from .text import TextCleaner
 from .weights import DEFAULT_STATS, load_distribution
 
@@ -322,13 +327,14 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
-                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False):
+                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False, fit=None):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
         attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
         device, with the library's own filter); sample_rate: the rate of the returned samples (synthesis_wav).  Loading / trimming the
         file and espeak stay with the caller.  trim_db (None: the wave as it came): the silent ends of ref_wave are cut on the device
-        before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity)."""
+        before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity).  fit: as
+        synthesis_wav / synthesis_mel take it."""
         if getattr(self, "frontend", None) is None:
             self.attach_frontend()
         if trim_db is not None:
@@ -356,6 +362,8 @@ class ArtSpeech:
             if self.generator is None:
                 raise RuntimeError("marks time the samples: attach_vocoder(h, checkpoint) first")
             kw["marks"] = marks                                             # (synthesis_wav: the result is then (samples, SpeechMarks))
+        if fit is not None:
+            kw["fit"] = fit
         out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody, token_prosody=token_prosody,
                  token_smooth=token_smooth, **kw)
         out, sm = out if with_marks else (out, None)
@@ -374,7 +382,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
-                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False):
+                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False, fit=None):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the generator's last kernel.
@@ -387,7 +395,8 @@ class ArtSpeech:
         ([B, max ceil(300 frames L / M)]); with pcm16 the generator writes fp32 only and the resampler writes the 16-bit samples.
         marks (True: 60 frames per second, or a marks.Marker for this chain): the call returns (samples, marks.SpeechMarks) -- when every
         token and word is spoken, in samples and seconds from the start of its own utterance's row, and F0, energy and the articulators
-        on the animation clock (as_marks_f32 on the device results the call already has, read back with the samples)."""
+        on the animation clock (as_marks_f32 on the device results the call already has, read back with the samples).
+        fit: a Fit (fit.py) -- Fit.whole(s) gives every utterance rint(40 s) * 600 samples at 24 kHz, spans give their tokens an exact time."""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         single = isinstance(phonemes, str)
@@ -397,12 +406,12 @@ class ArtSpeech:
             if forced_durations is not None:
                 raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
             out = self._synthesis_wav_cap(phonemes, ref_mel, features, voice, prosody, pcm16, int(frame_cap), token_prosody, token_smooth,
-                                          sample_rate, marker)
+                                          sample_rate, marker, fit)
             if marker is not None:
                 return (out[0][0] if single else out[0]), out[1]
             return out[0] if single else out
         mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody,
-                                 token_prosody=token_prosody, token_smooth=token_smooth)
+                                 token_prosody=token_prosody, token_smooth=token_smooth, fit=fit)
         lens = self._last_frames
         sm = None
         if marker is not None:
@@ -470,9 +479,26 @@ class ArtSpeech:
         utterance's own list of per-token settings; else one list, or None, per utterance -- as every other per-utterance argument"""
         return Prosody.token_rows([token_prosody] if single else token_prosody, tok_lens, self.model.ArtsSpeech)
 
-    def packed_inputs(self, phonemes, ref_mel=None, features=None, voice=None, prosody=None, token_prosody=None, token_smooth=False):
+    @staticmethod
+    def _fit_built(fit, text, tok_lens, device=None):
+        """synthesis_*'s fit (a Fit, or None) -> the fit.Built of this batch (text: the padded token ids); device: its arrays go there now (a
+        chain that is captured reads them at every replay)"""
+        if fit is None:
+            return None
+        if not isinstance(fit, Fit):
+            raise TypeError("fit: expected a pipeline.Fit")
+        built = fit.build(tok_lens, [text[b, :n] for b, n in enumerate(tok_lens)])
+        if device is not None:
+            for k in ("span_tok", "span_frames", "lock"):
+                if getattr(built, k) is not None:
+                    setattr(built, k, torch.as_tensor(getattr(built, k)).to(device))
+        return built
+
+    def packed_inputs(self, phonemes, ref_mel=None, features=None, voice=None, prosody=None, token_prosody=None, token_smooth=False, fit=None):
         """The keyword arguments of ArtsSpeech.forward_packed for these utterances (what ArtsSpeech.forward builds before the model call):
-        packed device tokens and either the packed reference features or the voice table; prosody rows (per utterance, per token) on the device."""
+        packed device tokens and either the packed reference features or the voice table; prosody rows (per utterance, per token) on the device;
+        fit (a Fit): its spans, targets and locks as device tensors (`inputs["fit"]`, a fit.Built), which chain_cap hands to forward_packed --
+        a captured chain reads them at every replay, so targets rewritten in place (`inputs["fit"].span_frames`) reach the next one."""
         if (voice is None) == (ref_mel is None):
             raise ValueError("synthesis needs exactly one of ref_mel and voice")
         net = self.model.ArtsSpeech
@@ -486,6 +512,8 @@ class ArtSpeech:
                 kw["prosody"] = Prosody.rows(prosody, B, net).to(dev)
             if token_prosody is not None:
                 kw["token_prosody"], kw["token_smooth"] = self._token_rows(token_prosody, tl, isinstance(phonemes, str)).to(dev), bool(token_smooth)
+            if fit is not None:
+                kw["fit"] = self._fit_built(fit, text, tl, dev)
             if voice is not None:
                 table, vidx = self._voice_table(voice, B)
                 kw["voice"], kw["voice_idx"] = table, vidx.to(dev)        # (on the device already: a captured call copies nothing)
@@ -630,9 +658,9 @@ class ArtSpeech:
         return ret
 
     def _synthesis_wav_cap(self, phonemes, ref_mel, features, voice, prosody, pcm16, frame_cap, token_prosody=None, token_smooth=False,
-                           sample_rate=None, marker=None):
+                           sample_rate=None, marker=None, fit=None):
         from . import _lib
-        inputs = self.packed_inputs(phonemes, ref_mel, features, voice, prosody, token_prosody, token_smooth)
+        inputs = self.packed_inputs(phonemes, ref_mel, features, voice, prosody, token_prosody, token_smooth, fit)
         samples, sample_off, *m = self.chain_cap(inputs, frame_cap, pcm16=pcm16, sample_rate=sample_rate, marks=marker)
         with torch.cuda.device(self.device):
             off = sample_off.cpu().tolist()                                 # the one synchronisation: offsets, then the samples
@@ -653,7 +681,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_paragraph(self, sentences, ref_mel=None, voice=None, prosody=None, pause_ms=None, joiner=None, sample_rate=None, pcm16=False,
-                            frame_cap=None, features=None, max_tokens=None, marks=False):
+                            frame_cap=None, features=None, max_tokens=None, marks=False, fit=None):
         """A paragraph as ONE stream: `sentences` is a list of phoneme strings, or one string that text.split_sentences cuts (max_tokens:
         its limit per piece).  The sentences run as one batch through the calls above (synthesis_mel and the generator, or with frame_cap
         the chain with no read-back; the resampler when sample_rate is given), then through join.Joiner on the device -- every sentence
@@ -665,7 +693,9 @@ class ArtSpeech:
         stream and which of its own samples were kept).
         marks (True: 60 frames per second, or a marks.Marker for this chain): one more entry, a marks.SpeechMarks -- when every token, word
         and sentence is spoken in the stream and the twelve tracks on the animation clock, with `active` 0 in the pauses -- from
-        as_marks_f32 behind the joiner, read back with the stream."""
+        as_marks_f32 behind the joiner, read back with the stream.
+        fit: a Fit whose utterances are the sentences -- Fit.whole([2.0, 3.5, None]) gives every sentence its slot (subtitles) on the
+        vocoder's clock, before the joiner trims and spaces them."""
         from . import _lib
         from .join import Joiner
         from .text import PAUSE_SCALE, split_sentences
@@ -691,14 +721,14 @@ class ArtSpeech:
         marker = self._marker(marks, sample_rate)
         m = None
         if frame_cap is not None:
-            inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody)
+            inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody, fit=fit)
             stream, out_off, piece, *m = self.chain_cap(inputs, int(frame_cap), pcm16=pcm16, sample_rate=sample_rate, join=joiner, gaps=gaps,
                                                         marks=marker)
             m = m[0] if m else None
         else:
             from .models import pack
             from .vocoder import layout
-            mel = self.synthesis_mel(sentences, ref_mel, features=features, voice=voice, prosody=prosody)
+            mel = self.synthesis_mel(sentences, ref_mel, features=features, voice=voice, prosody=prosody, fit=fit)
             gen, lens = self.generator, [int(v) for v in self._last_frames]
             with torch.cuda.device(gen.device):
                 wav, lay_w = gen.forward_packed(pack(mel.to(gen.device), lens), layout(lens, gen.device))[:2]
@@ -720,7 +750,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None,
-                      token_prosody=None, token_smooth=False):
+                      token_prosody=None, token_smooth=False, fit=None):
         """phonemes: the string the phonemizer returns (test.py:94-96) or a list of such strings; ref_mel: normalised
         log-mel [80,T] (test.py:43-47) or a list; features: (f0_raw, ema_raw) per utterance when no extractor modules
         are attached; (None, ema_raw) with a pitch extractor attached (attach_pitch_extractor).  Returns mel [B,80,2*max M] (what test.py:115 hands to the vocoder).
@@ -730,9 +760,13 @@ class ArtSpeech:
         voice: a Voice (every utterance) or a list of them, in place of ref_mel / features: the reference is not processed again.
         prosody: a Prosody (every utterance) or a list of them: speaking rate, pitch, energy and articulators (not with forced_durations).
         token_prosody: control inside an utterance -- per utterance a list with a Prosody (or None) per token (Prosody.from_spans builds it;
-        one utterance: the list itself), see Prosody.token_rows; token_smooth: glide between the tokens' settings.  Not with forced_durations."""
+        one utterance: the list itself), see Prosody.token_rows; token_smooth: glide between the tokens' settings.  Not with forced_durations.
+        fit: a Fit -- spans of tokens, or whole utterances, spoken in an exact time (fit.py); utterance indices count this call's list.  Not
+        with forced_durations, nor with world > 1."""
         if (voice is None) == (ref_mel is None):
             raise ValueError("synthesis needs exactly one of ref_mel and voice")
+        if fit is not None and world > 1:
+            raise ValueError("fit: its utterance indices count one process's batch (no world / rank)")
         if world > 1 and not isinstance(phonemes, str):
             from . import shard
             lens = [len(p) for p in phonemes]
@@ -765,7 +799,7 @@ class ArtSpeech:
         batch = [text, torch.LongTensor(tl), mels, None if ml is None else torch.LongTensor(ml), None, None, None]     # test.py:110-111
         mel, aux = self.model.ArtsSpeech(batch, None, None, step="test", features=feats, forced_durations=forced_durations,
                                          return_aux=True, voice=table, voice_idx=vidx, prosody=rows, token_prosody=trows,
-                                         token_smooth=token_smooth)                                                   # test.py:113
+                                         token_smooth=token_smooth, fit=self._fit_built(fit, text, tl))                                               # test.py:113
         self._last_frames = list(aux["frames2"])
         self._last_aux, self._last_tok_lens = aux, tl                  # (device results the speech marks read: dur_i, frame_off, F0 / N / EMA)
         return mel

@@ -689,6 +689,48 @@ int as_plan_set_operand_mode(as_plan* p, int n_prod);
  * scales) or io->segs is given -- before anything is launched.  as_lanes never sets them on its plans. */
 typedef struct as_token_prosody { const float* rows; int32_t ld; int32_t smooth; } as_token_prosody;
 int as_plan_set_token_prosody(as_plan* p, const as_token_prosody* tp);   /* copied; NULL = off (the default) */
+/* Fit to time: spans of tokens spoken in an exact number of frames ("say this in 2.40 s", "this word ends at 1.2 s"), as state of the plan.
+ * Span s = the packed tokens [span_tok[s][0], + span_tok[s][1]) of ONE utterance, in ascending order without overlap; span_frames[s] = its
+ * target in half-rate frames (one = 2 mel frames = 25 ms at 24 kHz).  When a forward runs, the tokens of a span get integer durations that
+ * add up to the target exactly, lie in [1, 16384] and stay proportional to the controlled durations v (the predictor's values under
+ * as_forward_io.prosody and the per-token duration scales): the rule, its bounds and why the pinned tokens are a prefix are in
+ * csrc/duration_fit.h.  Tokens outside every span are rounded as without a fit; lock[i] != 0 keeps token i's own rounded duration and lets
+ * the rest of its span absorb the difference (hold the pauses and stretch the speech, or the reverse).
+ *   A structural defect (first < 0, count < 1, first + count past the tokens, spans out of order or overlapping) voids the whole fit; a span
+ *   with count > max_count, across an utterance boundary, with a target its free tokens cannot meet inside [1, 16384] each (or, with no free
+ *   token, other than the locked sum) voids that span.  Void tokens get the plain rounding and AS_STATUS_BAD_LAYOUT is raised.
+ * All three arrays are DEVICE memory read when the call RUNS: a replayed graph sees new targets.  dur_i, frame_off, the frame -> token map,
+ * the marks and everything behind them follow the fitted counts (known frames: batch->frames must be their sums -- with every utterance
+ * covered by spans the host knows them before the call).
+ * as_plan_set_fit       the struct is copied; fit NULL = off (the default): a forward then issues exactly the launches and needs exactly
+ *                       the workspace it did before this entry point existed.  With a fit a forward adds two small launches
+ *                       (csrc/duration_fit.hip) and two small buffers in workspace A (workspace B is laid out as without): set it BEFORE
+ *                       asking as_module_workspace_bytes, and do not change it between as_forward_test_begin and _finish.  Works with known
+ *                       frames, the read-back, frame_cap (capturable), voice mode, as_forward_io.prosody and per-token prosody.
+ *                       AS_EINVAL: p NULL, a NULL span_tok / span_frames, n_spans or max_count outside [1, 4096]; and from
+ *                       as_forward_test / _begin / _finish on a plan with a fit when io->forced_dur or io->segs is given -- before anything
+ *                       is launched.  as_lanes never sets one on its plans.
+ * as_fit_durations_f32  the kernels on their own: v [n_tokens] (DEVICE, already controlled) -> dur_i [n_tokens] for EVERY token, and
+ *                       (optional) span_scale_q16 [n_spans] = floor(R * 65536 / U*), the stretch the span received in units of 2^-16 (0 for
+ *                       a void span or one without a free token), so that a caller can refuse an unnatural fit.  Two launches; nothing is
+ *                       read back, uploaded, allocated or waited for: capturable.  A non-finite v raises AS_STATUS_F16_RANGE (its plain
+ *                       duration is 1, its weight that of 1).  AS_EINVAL: NULL v / tok_off / fit / dur_i / ws, B outside [1, 1024],
+ *                       n_tokens < 0, the fit as above; AS_ENOSPC: ws_bytes below as_fit_workspace_bytes(n_tokens, fit) (0 for arguments it
+ *                       refuses); AS_EDEVICE while a status bit is set.
+ * as_fit_host           the same rule on HOST arrays (every pointer, those of fit included, is a host pointer; no GPU, no workspace);
+ *                       AS_EDEVICE where the device would raise a status. */
+typedef struct as_fit {
+    const int32_t* span_tok;     /* DEVICE [n_spans][2]: first packed token, count */
+    const int32_t* span_frames;  /* DEVICE [n_spans]: target, half-rate frames; read when the call RUNS */
+    const int32_t* lock;         /* DEVICE [sum tok_lens] or NULL */
+    int32_t n_spans;             /* 1 .. 4096 */
+    int32_t max_count;           /* 1 .. 4096: sizes the launch */
+} as_fit;
+int as_plan_set_fit(as_plan* p, const as_fit* fit);   /* copied; NULL = off (the default) */
+size_t as_fit_workspace_bytes(int n_tokens, const as_fit* fit);
+int as_fit_durations_f32(const float* v, const int32_t* tok_off, int B, int n_tokens, const as_fit* fit, int32_t* dur_i,
+                         int32_t* span_scale_q16, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_fit_host(const float* v, const int32_t* tok_off, int B, int n_tokens, const as_fit* fit, int32_t* dur_i, int32_t* span_scale_q16);
 int as_plan_phase_ms(as_plan* p, float* ms, int n);
 /* The plan caches the device tables of every batch geometry it has seen (key: the whole length vector).  Above max_layouts entries
  * (default 4096, minimum 64) the next entry point first waits for the streams THIS plan has launched on (not for the device: other plans'
