@@ -225,7 +225,21 @@ def marker_of(a, rate, resampler, hop=300):
 
 def marker_for(a, tts):
     """marker_of for the attached generator and the output's rate (nothing is looked up when no marks are asked for)"""
-    return marker_of(a, a.out_rate, tts._out_resampler(a.out_rate), tts._hop()) if a.with_marks else None
+    return tts.marker(a.out_rate, fps=a.marks_fps if a.marks_fps is not None else 60) if a.with_marks else None
+
+
+def voice_of(a, tts):
+    """the pipeline.Voice of the parsed arguments: --voice loaded and checked against the model, or computed from --ref-wav (trimmed by
+    --trim-ref-db) and, with --save-voice, written"""
+    from .pipeline import Voice
+    if a.voice:
+        return Voice.load(a.voice, tts)
+    wave_in, ref_rate = read_wav_any(a.ref_wav)
+    voice = tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db)
+    if a.save_voice:
+        voice.save(a.save_voice)
+        print(f"{a.save_voice}: voice of {a.ref_wav}")
+    return voice
 
 
 def write_marks(a, sm):
@@ -339,18 +353,8 @@ def main(argv=None):
     except ValueError as e:
         ap.error(f"--fit-seconds / --fit: {e}")
     if a.paragraph:
-        from .pipeline import Voice
-        if a.voice:
-            voice = Voice.load(a.voice, tts)
-        else:
-            wave_in, ref_rate = read_wav_any(a.ref_wav)
-            voice = tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db)
-            if a.save_voice:
-                voice.save(a.save_voice)
-                print(f"{a.save_voice}: voice of {a.ref_wav}")
-        marker = marker_for(a, tts)
-        audio, piece, *sm = tts.synthesis_paragraph(a.phonemes, voice=voice, prosody=a.prosody, joiner=joiner_of(a, a.out_rate), pcm16=a.pcm16,
-                                                    frame_cap=a.frame_cap, sample_rate=a.out_rate, marks=marker)
+        audio, piece, *sm = tts.synthesis_paragraph(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, joiner=joiner_of(a, a.out_rate),
+                                                    pcm16=a.pcm16, frame_cap=a.frame_cap, sample_rate=a.out_rate, marks=marker_for(a, tts))
         if sm:
             write_marks(a, sm[0])
         write_wav(a.out, audio.numpy(), sr=a.out_rate)
@@ -359,29 +363,18 @@ def main(argv=None):
             print(f"  sentence {b}: {o0 / float(a.out_rate):.3f} s .. {o1 / float(a.out_rate):.3f} s (its samples {s0} .. {s1})")
         return 0
     if a.like_wav:
-        from .pipeline import Voice
         like, like_rate = read_wav_any(a.like_wav)
-        if a.voice:
-            voice = Voice.load(a.voice, tts)
-        else:
-            wave_in, ref_rate = read_wav_any(a.ref_wav)
-            voice = tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db)
-            if a.save_voice:
-                voice.save(a.save_voice)
-                print(f"{a.save_voice}: voice of {a.ref_wav}")
-        audio, info = tts.synthesis_like(a.phonemes, like_wave=like, like_rate=like_rate, voice=voice, transfer=transfer_of(a), smooth=True,
-                                         prosody=a.prosody, pcm16=a.pcm16, sample_rate=a.out_rate)
+        audio, info = tts.synthesis_like(a.phonemes, like_wave=like, like_rate=like_rate, voice=voice_of(a, tts), transfer=transfer_of(a),
+                                         smooth=True, prosody=a.prosody, pcm16=a.pcm16, sample_rate=a.out_rate)
         print(f"{a.like_wav}: {int(info['rec_frames'][0])} frames aligned to {int(info['syn_frames'][0])} synthesised ones, "
               f"{int(info['misses'].sum())} token(s) kept their own duration")
     elif a.voice:
-        from .pipeline import Voice
-        audio = tts.synthesis_wav(a.phonemes, voice=Voice.load(a.voice, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
+        audio = tts.synthesis_wav(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
                                   sample_rate=a.out_rate, marks=marker_for(a, tts), **tok)
     else:
-        wave_in, ref_rate = read_wav_any(a.ref_wav)
         if a.save_voice:
-            tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db).save(a.save_voice)
-            print(f"{a.save_voice}: voice of {a.ref_wav}")
+            voice_of(a, tts)                                           # (written; the synthesis below starts from the wave itself)
+        wave_in, ref_rate = read_wav_any(a.ref_wav)
         audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, ref_rate=ref_rate,
                                         sample_rate=a.out_rate, trim_db=a.trim_ref_db,
                                         marks=marker_for(a, tts), **tok)

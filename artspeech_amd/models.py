@@ -319,6 +319,15 @@ def pack_reference(mels, f0_raw, ema_raw, lens, dev):
     return pack(mels.to(dev), lens), pack(f0_raw.to(dev).reshape(len(lens), 1, -1), lens), pack(ema_raw.to(dev), lens)
 
 
+def forced_args(forced_durations, tok_lens, dev):
+    """forced_durations (per utterance, its tokens' integer durations first) -> forward_packed's (forced: packed int32 on the device,
+    frames_hint: the frames each utterance's sum to); None -> (None, None)"""
+    if forced_durations is None:
+        return None, None
+    fd = [torch.as_tensor(forced_durations[b])[: n].reshape(-1) for b, n in enumerate(tok_lens)]
+    return torch.cat(fd).to(device=dev, dtype=torch.int32), [int(f.sum()) for f in fd]
+
+
 def _pack_tokens(x, lens, n_token):
     tok = torch.cat([torch.as_tensor(x[b])[: int(l)].reshape(-1) for b, l in enumerate(lens)]).to(torch.int64)
     if tok.numel() and (int(tok.min()) < 0 or int(tok.max()) >= n_token):
@@ -524,7 +533,6 @@ class ArtsSpeech(_Module):
         texts, input_lengths, mels, mel_input_length = batch[0], batch[1], batch[2], batch[3]   # 7- or 4-tuple (B1)
         dev = self.device
         tl = [int(v) for v in input_lengths]
-        B = len(tl)
         ml, mel_p, f0_p, ema_p = None, None, None, None
         if voice is None:
             ml = [int(v) for v in mel_input_length]
@@ -533,11 +541,7 @@ class ArtsSpeech(_Module):
             tok = _dev(_pack_tokens(texts, tl, self.rt.cfg.n_token), dev, torch.int32)
             if voice is None:
                 mel_p, f0_p, ema_p = pack_reference(mels, f0_raw, ema_raw, ml, dev)
-            forced, frames = None, None
-            if forced_durations is not None:
-                fd = [torch.as_tensor(forced_durations[b])[: tl[b]].reshape(-1) for b in range(B)]
-                forced = torch.cat(fd).to(device=dev, dtype=torch.int32)
-                frames = [int(f.sum()) for f in fd]
+            forced, frames = forced_args(forced_durations, tl, dev)
             out = self.forward_packed(tok, tl, mel_p, f0_p, ema_p, ml, forced=forced, frames_hint=frames, aux=return_aux, voice=voice,
                                       voice_idx=voice_idx, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth, fit=fit)
             mel = unpack(out["mel"], layout(out["frames2"], dev))

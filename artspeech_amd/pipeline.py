@@ -19,6 +19,13 @@ Prosody) spans -- and ``token_smooth=True`` glides between the tokens' settings 
 When it is spoken: ``fit=Fit.whole(2.4)`` says the utterance in exactly 2.40 s, ``fit=Fit([(utterance, first token, last token, seconds)])``
 gives spans of tokens their time, ``hold=Fit.hold_pauses`` keeps the pauses as predicted (fit.py; as_plan_set_fit).  The durations stay
 proportional to what the predictor and the controls above ask for.
+
+How a call runs.  Every public call turns "one utterance or lists" into lists at its first lines (``_lists``); everything private takes
+lists.  ``packed_inputs`` is the one place where a request becomes the tensors of ArtsSpeech.forward_packed, ``_forward`` the one call of
+the acoustic model (it returns the result dict), and ``_back_end`` the one chain behind it -- generator -> [resampler] -> [joiner] ->
+[marks] on packed samples and a device offset table -- whether the frame counts were read back or only a capacity is known
+(``_chain``: both regimes; ``chain_cap``: the capturable one).  ``_last_frames`` / ``_last_aux`` are records for the caller, written
+once at the end of a public call (``_record``); nothing in the library reads them.
 """
 import json
 import math
@@ -66,7 +73,7 @@ class Voice:
         with np.load(path, allow_pickle=False) as z:
             v = cls(z["vector"], int(z["style_dim"]), str(z["fingerprint"]))
         if model is not None:
-            rt = model.model.ArtsSpeech.rt if isinstance(model, ArtSpeech) else getattr(model, "rt", model)
+            rt = _runtime(model)
             v.check(rt.fingerprint, int(rt.cfg.style_dim))
         return v
 
@@ -79,12 +86,15 @@ class Voice:
                              f"(fingerprint {self.fingerprint} vs {fingerprint})")
 
 
+def _runtime(model):
+    """the models.Runtime of an ArtSpeech or an ArtsSpeech; anything else (a Runtime) as it came"""
+    return getattr(model.model.ArtsSpeech if isinstance(model, ArtSpeech) else model, "rt", model)
+
+
 def _stats24(stats):
     """the 24 normalisation floats (as_model_cfg.stats: energy mean / std, pitch mean / std, EMA_mean[10], EMA_std[10]) of a model
     (an ArtSpeech, an ArtsSpeech or a models.Runtime), or the 24 floats themselves"""
-    if isinstance(stats, ArtSpeech):
-        stats = stats.model.ArtsSpeech
-    stats = getattr(stats, "rt", stats)
+    stats = _runtime(stats)
     cfg = getattr(stats, "cfg", None)
     vals = [float(v) for v in (cfg.stats if cfg is not None else stats)]
     if len(vals) != 24:
@@ -215,6 +225,7 @@ class ArtSpeech:
         self.textcleaner = TextCleaner()
         self.device = dev
         self.generator = None                       # test.py:119-125: the HiFi-GAN generator (attach_vocoder)
+        self._record(None, None)
 
     def attach_pitch_extractor(self, checkpoint=None):
         """models.py:377-379: ``JDCNet(num_class=1, seq_len=192)`` + ``torch.load("Utils/JDC/bst.t7")['net']``, on the HIP
@@ -242,6 +253,267 @@ class ArtSpeech:
         self.frontend = LogMel(device=self.device)
         return self.frontend
 
+    def attach_vocoder(self, h=None, checkpoint=None, runtime=False):
+        """test.py:119-125: build the generator from Vocoder/config.json-style `h` and load checkpoint['generator'].
+        runtime=True: the generator runs inside the library (one as_vocoder_forward call per batch; vocoder.Generator)."""
+        from .vocoder import Generator
+        self.generator = Generator(h, device=self.device, runtime=runtime)
+        if checkpoint is not None:
+            sd = checkpoint if isinstance(checkpoint, dict) else torch.load(checkpoint, map_location="cpu")
+            self.generator.load_state_dict(sd)
+        return self.generator
+
+    # ------------------------------------------------------------------ the request: one utterance or lists -> lists -> packed tensors
+    @staticmethod
+    def _lists(phonemes, *per_utterance):
+        """What every public call does first.  One utterance (phonemes: ONE string; every other argument that utterance's own) or lists of
+        B -> (single, the phonemes as a list, every other argument as a list of B, or None).  Everything private takes lists."""
+        if isinstance(phonemes, str):
+            return (True, [phonemes]) + tuple(None if a is None else [a] for a in per_utterance)
+        return (False, list(phonemes)) + per_utterance
+
+    def _record(self, frames, res):
+        """What a public call leaves for its caller, written once at its end and read by nothing in the library: `_last_frames`, the mel
+        frames of every utterance (None where only the device knows them), and `_last_aux`, the acoustic model's result dict (`_forward`:
+        dur_i, frame_off, F0 / N / EMA, fit_frames_known ...; None where several processes shared the batch)."""
+        self._last_frames, self._last_aux = frames, res
+
+    def _wave_mels(self, waves, rate, trim_db=None):
+        """a list of waves of `rate` Hz -> their normalised log-mels [80, T_b] on the device: [_trim_ref ->] [resampler ->] front end"""
+        if getattr(self, "frontend", None) is None:
+            self.attach_frontend()
+        waves = list(waves)
+        if trim_db is not None:
+            waves = self._trim_ref(waves, rate, trim_db)
+        mel, lens = self.frontend(self._ref_at_24k(waves, rate))
+        return [mel[b, :, :n] for b, n in enumerate(lens)]
+
+    @staticmethod
+    def _padded_reference(ref_mel, features):
+        """B reference log-mels [n_mels, T_b] and, or None, their (f0_raw, ema_raw) -> (mels [B, n_mels, max T], ref_lens, (f0 [B, 1, max T],
+        ema [B, 10, max T]) or None), zero padded, on the host.  f0 is None (the attached pitch extractor computes it) when any utterance's is."""
+        ml = [int(m.shape[-1]) for m in ref_mel]
+        B, tmax = len(ml), max(ml)
+        mels = torch.zeros(B, ref_mel[0].shape[0], tmax)
+        for b, m in enumerate(ref_mel):
+            mels[b, :, : ml[b]] = torch.as_tensor(m)
+        if features is None:
+            return mels, ml, None
+        f0 = None if any(f is None for f, _ in features) else torch.zeros(B, 1, tmax)
+        ema = torch.zeros(B, 10, tmax)
+        for b, (f, e) in enumerate(features):
+            if f0 is not None:
+                f = torch.as_tensor(f).reshape(1, -1)
+                f0[b, :, : f.shape[-1]] = f
+            e = torch.as_tensor(e)
+            ema[b, :, : e.shape[-1]] = e
+        return mels, ml, (f0, ema)
+
+    def _token_rows(self, token_prosody, tok_lens, single):
+        """synthesis_*'s token_prosody -> the [sum tok_lens, 25] rows.  single (the phonemes came as ONE string): token_prosody is that
+        utterance's own list of per-token settings; else one list, or None, per utterance -- as every other per-utterance argument"""
+        return Prosody.token_rows([token_prosody] if single else token_prosody, tok_lens, self.model.ArtsSpeech)
+
+    @staticmethod
+    def _fit_built(fit, ids, tok_lens, device):
+        """synthesis_*'s fit (a Fit) -> the fit.Built of this batch (ids: every utterance's token ids) with its arrays on the device (a
+        chain that is captured reads them at every replay)"""
+        if not isinstance(fit, Fit):
+            raise TypeError("fit: expected a pipeline.Fit")
+        built = fit.build(tok_lens, ids)
+        for k in ("span_tok", "span_frames", "lock"):
+            if getattr(built, k) is not None:
+                setattr(built, k, torch.as_tensor(getattr(built, k)).to(device))
+        return built
+
+    def _voice_table(self, voice, B):
+        """one Voice (every utterance) or a list of B -> (device table [V, voice_dim], indices [B]); each voice checked against the model"""
+        rt = self.model.ArtsSpeech.rt
+        voices = [voice] * B if isinstance(voice, Voice) else list(voice)
+        if len(voices) != B:
+            raise ValueError(f"{len(voices)} voices for {B} utterances")
+        rows, idx = [], []
+        for v in voices:
+            if not isinstance(v, Voice):
+                raise TypeError("voice: expected a pipeline.Voice (voice_from_mel / voice_from_wave / Voice.load) or a list of them")
+            v.check(rt.fingerprint, int(rt.cfg.style_dim))
+            k = next((i for i, u in enumerate(rows) if u is v), None)
+            if k is None:
+                rows.append(v)
+                k = len(rows) - 1
+            idx.append(k)
+        table = torch.stack([v.vector for v in rows]).to(rt.device)
+        return table, torch.tensor(idx, dtype=torch.int32)
+
+    def packed_inputs(self, phonemes, ref_mel=None, features=None, voice=None, prosody=None, token_prosody=None, token_smooth=False, fit=None,
+                      forced_durations=None):
+        """THE place where a request becomes the keyword arguments of ArtsSpeech.forward_packed: packed device tokens and either the packed
+        reference features or the voice table; prosody rows (per utterance, per token) on the device; forced_durations (per utterance) as
+        `forced` and `frames_hint`; fit (a Fit): its spans, targets and locks as device tensors (`inputs["fit"]`, a fit.Built), which
+        chain_cap hands to forward_packed -- a captured chain reads them at every replay, so targets rewritten in place
+        (`inputs["fit"].span_frames`) reach the next one.  Entries that start with "_" are not arguments: the chain keeps what it reuses
+        from call to call there (`_out`, `_tok_off`)."""
+        if (voice is None) == (ref_mel is None):
+            raise ValueError("synthesis needs exactly one of ref_mel and voice")
+        _, phonemes, ref_mel, features, token_prosody = self._lists(phonemes, ref_mel, features, token_prosody)
+        net = self.model.ArtsSpeech
+        dev = net.device
+        ids = [torch.LongTensor(self.textcleaner(p)) for p in phonemes]                 # test.py:96-97
+        tl = [len(i) for i in ids]
+        B = len(tl)
+        kw = dict(tok_lens=tl, mel_p=None, f0_p=None, ema_p=None, ref_lens=None)
+        with torch.cuda.device(dev):
+            kw["tok"] = models._dev(models._pack_tokens(ids, tl, net.rt.cfg.n_token), dev, torch.int32)
+            if forced_durations is not None:
+                kw["forced"], kw["frames_hint"] = models.forced_args(forced_durations, tl, dev)
+            if prosody is not None:
+                kw["prosody"] = Prosody.rows(prosody, B, net).to(dev)
+            if token_prosody is not None:
+                kw["token_prosody"], kw["token_smooth"] = self._token_rows(token_prosody, tl, False).to(dev), bool(token_smooth)
+            if fit is not None:
+                kw["fit"] = self._fit_built(fit, ids, tl, dev)
+            if voice is not None:
+                table, vidx = self._voice_table(voice, B)
+                kw["voice"], kw["voice_idx"] = table, vidx.to(dev)        # (on the device already: a captured call copies nothing)
+                return kw
+            mels, ml, feats = self._padded_reference(ref_mel, features)
+            f0_raw, ema_raw = net.style_encoder._extract(mels, feats, ml)
+            kw["ref_lens"] = ml
+            kw["mel_p"], kw["f0_p"], kw["ema_p"] = models.pack_reference(mels, f0_raw, ema_raw, ml, dev)
+        return kw
+
+    @staticmethod
+    def _take(req, idx):
+        """the request of the utterances `idx` alone (a shard): every per-utterance list sliced; None, a flag, and ONE Voice or Prosody
+        (every utterance's) as they are"""
+        return {k: v if v is None or isinstance(v, (bool, Voice, Prosody)) else [v[i] for i in idx] for k, v in req.items()}
+
+    # ------------------------------------------------------------------ the acoustic model and the chain behind it
+    def _forward(self, inputs, **more):
+        """THE call of the acoustic model: packed_inputs' dict and what the caller adds to it (aux=, frame_cap= and out=, tracks=, other
+        per-token rows) -> ArtsSpeech.forward_packed's result dict (mel, frames2, dur_i, frame_off, the tracks it was asked for ...), which
+        also carries the request's `tok_lens`"""
+        kw = {k: v for k, v in inputs.items() if not k.startswith("_")}
+        kw.update(more)
+        res = self.model.ArtsSpeech.forward_packed(**kw)
+        res["tok_lens"] = inputs["tok_lens"]
+        return res
+
+    def _back_end(self, inputs, res, frame_cap=None, max_len=None, pcm16=False, rs=None, join=None, groups=None, gaps=None, join_cap=None,
+                  marker=None):
+        """generator -> [resampler rs] -> [joiner join] -> [marks] behind `_forward`'s result, on the current stream; between the stages
+        travel packed fp32 samples and a device offset table [B + 1].  Two regimes: frame_cap None -- the host knows the frame counts
+        (res["frames2"]) and every stage gets exactly the room its samples need; frame_cap=N -- only the device knows them (res["frame_off"]),
+        the generator writes 300 * 2 N samples and the resampler gets out_len(that) + B; no host value is read and, with groups and gaps
+        on the device (or None), nothing is uploaded: the call can be captured.  Decided here and nowhere else: the LAST stage writes the
+        int16 samples of pcm16, every stage before it fp32; the marker is told the size of the buffer its marks point into.
+        -> (samples fp32 or int16, off [B + 1] -- behind a joiner out_off [G + 1] --, piece [B][4] or None, Marker.forward_packed's dict or
+        None), all on the device."""
+        from .models import layout
+        gen, dev = self.generator, torch.device(self.device)
+        B = res["frame_off"].numel() - 1
+        last = "join" if join is not None else "rs" if rs is not None else "gen"
+        with torch.cuda.device(self.device):
+            p = pcm16 and last == "gen"
+            if frame_cap is None:
+                # (the packed mel as forward_packed wrote it; the operator-level generator always writes fp32 too)
+                wav, lay_w, *pcm = gen.forward_packed(res["mel"], layout(res["frames2"], gen.device), pcm=p)
+                x, off = wav.reshape(-1)[: max(lay_w.N, 1)], lay_w.col_off
+            else:
+                wav, off, *pcm = gen.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len, pcm=p, wav=not p)
+                x = None if p else wav[0]
+            out = pcm[0] if p else x
+            if rs is not None:
+                p = pcm16 and last == "rs"
+                room = max(sum(rs.out_len(n) for n in lay_w.widths_host), 1) if frame_cap is None else rs.out_len(x.numel()) + B
+                y, p16, off = rs.forward_packed(x, off, room, pcm=p, wav=not p)
+                out = x = p16 if p else y
+            piece = None
+            if join is not None:
+                G = 1 if groups is None else len(groups) - 1
+                if groups is not None:
+                    groups = join._i32(groups, dev, G + 1, "groups")                   # (the joiner and the marker read ONE device copy)
+                if join_cap is None:                                                    # what always suffices: every sample kept, every gap in place
+                    if torch.is_tensor(gaps):
+                        raise ValueError("gaps on the device: name join_cap, the samples of room for the joined streams")
+                    join_cap = join.out_cap(x.numel(), B, G, None if gaps is None else max(max(int(v) for v in gaps), 0))
+                y, p16, off, piece, _ = join.forward_packed(x, off, join_cap, groups=groups, gaps=gaps, pcm=pcm16, wav=not pcm16)
+                out = p16 if pcm16 else y
+            m = None
+            if marker is not None:
+                if "_tok_off" not in inputs:                                            # (uploaded by the first, eager call: a captured one finds it)
+                    inputs["_tok_off"] = torch.tensor(np.concatenate([[0], np.cumsum(inputs["tok_lens"])]), dtype=torch.int32).to(self.device)
+                scale, offset = marker.affine(_stats24(self), dev) if marker.physical else (None, None)
+                G = B if piece is None else off.numel() - 1
+                m = marker.forward_packed(inputs["_tok_off"], res["dur_i"], res["frame_off"], res["F0"], res["N"], res["EMA"], piece=piece,
+                                          groups=groups, out_off=None if piece is None else off, anim_cap=marker.anim_cap(out.numel(), G),
+                                          scale=scale, offset=offset)
+        return out, off, piece, m
+
+    def _chain(self, inputs, frame_cap, pcm16, sample_rate, marker, **stages):
+        """tokens -> samples: `_forward` then `_back_end` (stages: its max_len / join / groups / gaps / join_cap), in either regime.
+        frame_cap None: the frame counts are read back between the two (the one host read; the result has everything `aux` has);
+        frame_cap=N: no host value is read, and every call with the same inputs dict reuses the acoustic model's output tensors
+        (inputs["_out"]).  -> (res, samples, off, piece, marks)"""
+        if frame_cap is not None and (self.generator is None or not self.generator.runtime):
+            raise RuntimeError("frame_cap needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
+        with torch.cuda.device(self.device):
+            if frame_cap is None:
+                res = self._forward(inputs, aux=True)
+            else:
+                res = self._forward(inputs, frame_cap=frame_cap, out=inputs.setdefault("_out", {}), tracks=marker is not None)
+            return (res,) + self._back_end(inputs, res, frame_cap=frame_cap, pcm16=pcm16, rs=self._out_resampler(sample_rate), marker=marker,
+                                           **stages)
+
+    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None,
+                  marks=None):
+        """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
+        then the capacity vocoder on its frame_off and mel (`_chain`).  `inputs` = packed_inputs(...).  Every call with the same inputs dict
+        reuses the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
+        with other token / voice / prosody contents of the same geometry.  -> (samples [300 * 2 frame_cap], sample_off [B + 1]), both on the
+        device.  sample_rate (other than None / 24000): the generator writes fp32 and resample.Resampler(24000, sample_rate) runs on its
+        device sample_off on the same stream -> (samples [ceil(600 frame_cap L / M) + B], out_off [B + 1]); still no host value, still capturable.
+        join (a join.Joiner at the rate of the samples; groups / gaps / join_cap as Joiner.forward_packed takes them; join_cap None: what
+        always suffices, which needs the gaps as a list or None): the joiner runs on the device offsets the chain already has -- sample_off,
+        or the resampler's out_off -- on the same stream, and the call returns (stream [join_cap] fp32 or int16, out_off [G + 1], piece
+        [B][4]) instead; with groups and gaps as device tensors (or None) the chain stays capturable.
+        marks (a marks.Marker for this chain: its rate, the resampler's ratio, the generator's hop): the acoustic model also hands out
+        F0 / N / EMA and as_marks_f32 runs on the same stream behind the joiner -- or behind the resampler or the generator when there is
+        none -- on the device durations, offsets and pieces the chain already has; the call returns what it returns without marks and, as
+        one more entry, the dict of Marker.forward_packed (marks [sum tok_lens][2], tracks [12][anim_cap], active, anim_off), all on the
+        device.  The chain stays capturable (after one eager call, which also uploads the token offsets); marks=None issues exactly the
+        launches of before."""
+        if join is not None:
+            self._check_joiner(join, sample_rate)
+        _, out, off, piece, m = self._chain(inputs, frame_cap, pcm16, sample_rate, self._marker(marks, sample_rate), max_len=max_len, join=join,
+                                            groups=groups, gaps=gaps, join_cap=join_cap)
+        ret = (out, off) if join is None else (out, off, piece)
+        return ret if m is None else ret + (m,)
+
+    def _read_back(self, samples, off, what):
+        """the one synchronisation of a chain whose lengths only the device knows: the offsets first, then the status check, then the
+        samples in front of the last offset -> (off as a host list, those samples on the host)"""
+        from . import _lib
+        off = off.cpu().tolist()
+        if _lib.lib().as_device_status(0):
+            raise _lib.HipLibraryError(f"{what} failed: a kernel reported {_lib.device_status()} (as_device_status); results since then are invalid")
+        return off, samples[: off[-1]].cpu()
+
+    def _sample_off(self, frames2, rs):
+        """host prefix sums [B + 1] of the samples that utterances of `frames2` mel frames have behind the generator and the resampler rs"""
+        n = [self._hop() * int(f) for f in frames2]
+        return [0] + np.cumsum(n if rs is None else [rs.out_len(v) for v in n]).tolist()
+
+    @staticmethod
+    def _rows(packed, off):
+        """packed samples and their host offsets [B + 1] -> [B, max length] zero-padded rows, where the samples are (device or host)"""
+        lens = [off[b + 1] - off[b] for b in range(len(off) - 1)]
+        out = torch.zeros((len(lens), max(max(lens), 1)), dtype=packed.dtype, device=packed.device)
+        for b, n in enumerate(lens):
+            out[b, :n] = packed[off[b]: off[b + 1]]
+        return out
+
+    # ------------------------------------------------------------------ the reference wave
     @torch.no_grad()
     def voice_from_mel(self, ref_mel, features=None):
         """The Voice of one reference utterance: normalised log-mel [80, T] (test.py:43-47); features = (f0_raw, ema_raw) [or
@@ -261,11 +533,7 @@ class ArtSpeech:
         """The Voice of a reference wave (already loaded / trimmed; `rate` Hz: another rate than 24000 is resampled on the device,
         resample.Resampler): the log-mel front end, the attached extractors, the voice.  trim_db (None: the wave as it came): the wave's
         silent ends are cut on the device first (_trim_ref: the library's own block rule, not librosa's)."""
-        if getattr(self, "frontend", None) is None:
-            self.attach_frontend()
-        if trim_db is not None:
-            ref_wave = self._trim_ref(ref_wave, rate, trim_db)
-        return self.voice_from_mel(self.frontend(self._ref_at_24k(ref_wave, rate))[0])
+        return self.voice_from_mel(self._wave_mels([ref_wave], rate, trim_db)[0])
 
     REF_KEEP_MS = 20                # what _trim_ref keeps in front of the first and behind the last active block
 
@@ -306,234 +574,7 @@ class ArtSpeech:
         from .resample import resampler
         return resampler(SAMPLE_RATE, sample_rate, self.device)
 
-    def _voice_table(self, voice, B):
-        """one Voice (every utterance) or a list of B -> (device table [V, voice_dim], indices [B]); each voice checked against the model"""
-        rt = self.model.ArtsSpeech.rt
-        voices = [voice] * B if isinstance(voice, Voice) else list(voice)
-        if len(voices) != B:
-            raise ValueError(f"{len(voices)} voices for {B} utterances")
-        rows, idx = [], []
-        for v in voices:
-            if not isinstance(v, Voice):
-                raise TypeError("voice: expected a pipeline.Voice (voice_from_mel / voice_from_wave / Voice.load) or a list of them")
-            v.check(rt.fingerprint, int(rt.cfg.style_dim))
-            k = next((i for i, u in enumerate(rows) if u is v), None)
-            if k is None:
-                rows.append(v)
-                k = len(rows) - 1
-            idx.append(k)
-        table = torch.stack([v.vector for v in rows]).to(rt.device)
-        return table, torch.tensor(idx, dtype=torch.int32)
-
-    @torch.no_grad()
-    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
-                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False, fit=None):
-        """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
-        end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
-        attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
-        device, with the library's own filter); sample_rate: the rate of the returned samples (synthesis_wav).  Loading / trimming the
-        file and espeak stay with the caller.  trim_db (None: the wave as it came): the silent ends of ref_wave are cut on the device
-        before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity).  fit: as
-        synthesis_wav / synthesis_mel take it."""
-        if getattr(self, "frontend", None) is None:
-            self.attach_frontend()
-        if trim_db is not None:
-            ref_wave = self._trim_ref(ref_wave, ref_rate, trim_db)
-        ref_wave = self._ref_at_24k(ref_wave, ref_rate)
-        single = isinstance(phonemes, str)
-        if single:
-            mels = [self.frontend(ref_wave)[0]]
-            phonemes = [phonemes]
-            features = None if features is None else [features]
-            token_prosody = None if token_prosody is None else [token_prosody]   # (one utterance: its own per-token list)
-        else:
-            mel, lens = self.frontend(list(ref_wave))
-            mels = [mel[b, :, :n] for b, n in enumerate(lens)]
-        fn = self.synthesis_wav if self.generator is not None else self.synthesis_mel
-        kw = {"pcm16": True} if pcm16 and self.generator is not None else {}
-        if frame_cap is not None:
-            if self.generator is None:
-                raise RuntimeError("frame_cap runs the acoustic model and the generator as one chain: attach_vocoder(h, checkpoint, runtime=True) first")
-            kw["frame_cap"] = frame_cap
-        if sample_rate is not None and self.generator is not None:
-            kw["sample_rate"] = sample_rate
-        with_marks = marks is not None and marks is not False
-        if with_marks:
-            if self.generator is None:
-                raise RuntimeError("marks time the samples: attach_vocoder(h, checkpoint) first")
-            kw["marks"] = marks                                             # (synthesis_wav: the result is then (samples, SpeechMarks))
-        if fit is not None:
-            kw["fit"] = fit
-        out = fn(phonemes, mels, features=features, forced_durations=forced_durations, prosody=prosody, token_prosody=token_prosody,
-                 token_smooth=token_smooth, **kw)
-        out, sm = out if with_marks else (out, None)
-        out = out[0] if single and out.dim() > 1 and self.generator is not None else out
-        return (out, sm) if with_marks else out
-
-    def attach_vocoder(self, h=None, checkpoint=None, runtime=False):
-        """test.py:119-125: build the generator from Vocoder/config.json-style `h` and load checkpoint['generator'].
-        runtime=True: the generator runs inside the library (one as_vocoder_forward call per batch; vocoder.Generator)."""
-        from .vocoder import Generator
-        self.generator = Generator(h, device=self.device, runtime=runtime)
-        if checkpoint is not None:
-            sd = checkpoint if isinstance(checkpoint, dict) else torch.load(checkpoint, map_location="cpu")
-            self.generator.load_state_dict(sd)
-        return self.generator
-
-    @torch.no_grad()
-    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
-                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False, fit=None):
-        """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
-        (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
-        generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the generator's last kernel.
-        frame_cap=N (predicted durations, a runtime vocoder): room for N half-rate frames, all utterances together -- the acoustic model
-        (forward_packed(frame_cap=N)) hands its device frame_off and mel straight to the generator (forward_packed_cap) on the same
-        stream: no host value is read between the tokens and the samples, then ONE copy brings the sample offsets and the samples back.
-        More frames than room: HipLibraryError (AS_STATUS_CAPACITY).
-        sample_rate (None or 24000: the generator's own samples, exactly the calls above): the samples at that rate -- the packed fp32
-        samples go through resample.Resampler(24000, sample_rate) on the device before they are padded out or read back
-        ([B, max ceil(300 frames L / M)]); with pcm16 the generator writes fp32 only and the resampler writes the 16-bit samples.
-        marks (True: 60 frames per second, or a marks.Marker for this chain): the call returns (samples, marks.SpeechMarks) -- when every
-        token and word is spoken, in samples and seconds from the start of its own utterance's row, and F0, energy and the articulators
-        on the animation clock (as_marks_f32 on the device results the call already has, read back with the samples).
-        fit: a Fit (fit.py) -- Fit.whole(s) gives every utterance rint(40 s) * 600 samples at 24 kHz, spans give their tokens an exact time."""
-        if self.generator is None:
-            raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
-        single = isinstance(phonemes, str)
-        rs = self._out_resampler(sample_rate)
-        marker = self._marker(marks, sample_rate)
-        if frame_cap is not None:
-            if forced_durations is not None:
-                raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
-            out = self._synthesis_wav_cap(phonemes, ref_mel, features, voice, prosody, pcm16, int(frame_cap), token_prosody, token_smooth,
-                                          sample_rate, marker, fit)
-            if marker is not None:
-                return (out[0][0] if single else out[0]), out[1]
-            return out[0] if single else out
-        mel = self.synthesis_mel(phonemes, ref_mel, features=features, forced_durations=forced_durations, voice=voice, prosody=prosody,
-                                 token_prosody=token_prosody, token_smooth=token_smooth, fit=fit)
-        lens = self._last_frames
-        sm = None
-        if marker is not None:
-            # every utterance a stream of its own at the prefix sums of its resampled length: the rule's own layout without pieces
-            n = [self._hop() * int(f) if rs is None else rs.out_len(self._hop() * int(f)) for f in lens]
-            off = np.concatenate([[0], np.cumsum(n)])
-            with torch.cuda.device(self.device):
-                m = self._marks_packed(marker, self._tok_off(self._last_tok_lens), self._last_aux, max(int(off[-1]), 1))
-                sm = self._speech_marks(marker, [phonemes] if single else phonemes, m, stream_off=off)
-        if rs is not None:
-            wav = self._generate_resampled(mel, lens, rs, pcm16)
-        else:
-            wav = (self.generator(mel, lengths=lens, pcm16=True) if pcm16 else self.generator(mel, lengths=lens))[:, 0]
-        wav = wav[0] if single else wav
-        return wav if marker is None else (wav, sm)
-
-    def _generate_resampled(self, mel, lens, rs, pcm16):
-        """Generator.forward with the resampler between the generator's packed fp32 samples and the padding: mel [B, 80, T] with `lens` mel
-        frames each -> [B, max ceil(hop lens L / M)] at rs.out_rate (fp32, or int16 written by the resampler), zero beyond each utterance"""
-        from .models import pack
-        from .vocoder import layout
-        gen = self.generator
-        lens = [int(v) for v in lens]
-        with torch.cuda.device(gen.device):
-            wav, lay_w = gen.forward_packed(pack(mel.to(gen.device), lens), layout(lens, gen.device))[:2]
-            outs = [rs.out_len(n) for n in lay_w.widths_host]
-            y, p16, _ = rs.forward_packed(wav.reshape(-1)[: max(lay_w.N, 1)], lay_w.col_off, max(sum(outs), 1), pcm=pcm16, wav=not pcm16)
-            packed = p16 if pcm16 else y
-            out = torch.zeros((len(outs), max(max(outs), 1)), dtype=packed.dtype, device=packed.device)
-            for b, part in enumerate(torch.split(packed[: sum(outs)], outs)):
-                out[b, : part.numel()] = part
-            return out
-
-    def _padded_batch(self, phonemes, ref_mel, features):
-        """One utterance or lists of B -> (text [B, max N] token ids (test.py:96-97), tok_lens, mels [B, n_mels, max T], ref_lens,
-        (f0 [B, 1, max T], ema [B, 10, max T])), zero padded; without ref_mel the last three are None, without features the last one.
-        f0 is None (the attached pitch extractor computes it) when any utterance's is."""
-        if isinstance(phonemes, str):
-            phonemes, ref_mel, features = [phonemes], None if ref_mel is None else [ref_mel], None if features is None else [features]
-        ids = [torch.LongTensor(self.textcleaner(p)) for p in phonemes]
-        B, tl = len(ids), [len(i) for i in ids]
-        text = torch.zeros(B, max(tl), dtype=torch.long)
-        for b in range(B):
-            text[b, : tl[b]] = ids[b]
-        if ref_mel is None:
-            return text, tl, None, None, None
-        ml = [int(m.shape[-1]) for m in ref_mel]
-        tmax = max(ml)
-        mels = torch.zeros(B, ref_mel[0].shape[0], tmax)
-        for b in range(B):
-            mels[b, :, : ml[b]] = torch.as_tensor(ref_mel[b])
-        feats = None
-        if features is not None:
-            f0 = None if any(f is None for f, _ in features) else torch.zeros(B, 1, tmax)
-            ema = torch.zeros(B, 10, tmax)
-            for b, (f, e) in enumerate(features):
-                if f0 is not None:
-                    f0[b, :, : f.shape[-1]] = torch.as_tensor(f).reshape(1, -1)
-                ema[b, :, : e.shape[-1]] = torch.as_tensor(e)
-            feats = (f0, ema)
-        return text, tl, mels, ml, feats
-
-    def _token_rows(self, token_prosody, tok_lens, single):
-        """synthesis_*'s token_prosody -> the [sum tok_lens, 25] rows.  single (the phonemes came as ONE string): token_prosody is that
-        utterance's own list of per-token settings; else one list, or None, per utterance -- as every other per-utterance argument"""
-        return Prosody.token_rows([token_prosody] if single else token_prosody, tok_lens, self.model.ArtsSpeech)
-
-    @staticmethod
-    def _fit_built(fit, text, tok_lens, device=None):
-        """synthesis_*'s fit (a Fit, or None) -> the fit.Built of this batch (text: the padded token ids); device: its arrays go there now (a
-        chain that is captured reads them at every replay)"""
-        if fit is None:
-            return None
-        if not isinstance(fit, Fit):
-            raise TypeError("fit: expected a pipeline.Fit")
-        built = fit.build(tok_lens, [text[b, :n] for b, n in enumerate(tok_lens)])
-        if device is not None:
-            for k in ("span_tok", "span_frames", "lock"):
-                if getattr(built, k) is not None:
-                    setattr(built, k, torch.as_tensor(getattr(built, k)).to(device))
-        return built
-
-    def packed_inputs(self, phonemes, ref_mel=None, features=None, voice=None, prosody=None, token_prosody=None, token_smooth=False, fit=None):
-        """The keyword arguments of ArtsSpeech.forward_packed for these utterances (what ArtsSpeech.forward builds before the model call):
-        packed device tokens and either the packed reference features or the voice table; prosody rows (per utterance, per token) on the device;
-        fit (a Fit): its spans, targets and locks as device tensors (`inputs["fit"]`, a fit.Built), which chain_cap hands to forward_packed --
-        a captured chain reads them at every replay, so targets rewritten in place (`inputs["fit"].span_frames`) reach the next one."""
-        if (voice is None) == (ref_mel is None):
-            raise ValueError("synthesis needs exactly one of ref_mel and voice")
-        net = self.model.ArtsSpeech
-        dev = net.device
-        text, tl, mels, ml, feats = self._padded_batch(phonemes, ref_mel, features)
-        B = len(tl)
-        kw = dict(tok_lens=tl, mel_p=None, f0_p=None, ema_p=None, ref_lens=ml)
-        with torch.cuda.device(dev):
-            kw["tok"] = models._dev(models._pack_tokens(text, tl, net.rt.cfg.n_token), dev, torch.int32)
-            if prosody is not None:
-                kw["prosody"] = Prosody.rows(prosody, B, net).to(dev)
-            if token_prosody is not None:
-                kw["token_prosody"], kw["token_smooth"] = self._token_rows(token_prosody, tl, isinstance(phonemes, str)).to(dev), bool(token_smooth)
-            if fit is not None:
-                kw["fit"] = self._fit_built(fit, text, tl, dev)
-            if voice is not None:
-                table, vidx = self._voice_table(voice, B)
-                kw["voice"], kw["voice_idx"] = table, vidx.to(dev)        # (on the device already: a captured call copies nothing)
-                return kw
-            f0_raw, ema_raw = net.style_encoder._extract(mels, feats, ml)
-            kw["mel_p"], kw["f0_p"], kw["ema_p"] = models.pack_reference(mels, f0_raw, ema_raw, ml, dev)
-        return kw
-
-    def _join_packed(self, join, x, off, groups, gaps, pcm16, join_cap=None):
-        """join.Joiner.forward_packed on packed fp32 device samples and their device offsets -> (stream [join_cap], out_off [G + 1], piece
-        [B][4]); join_cap None: what always suffices (every sample kept, every gap in place), which needs the gaps as a list or None"""
-        B = off.numel() - 1
-        G = 1 if groups is None else len(groups) - 1
-        if join_cap is None:
-            if torch.is_tensor(gaps):
-                raise ValueError("gaps on the device: name join_cap, the samples of room for the joined streams")
-            join_cap = join.out_cap(x.numel(), B, G, None if gaps is None else max(max(int(v) for v in gaps), 0))
-        y, p16, out_off, piece, _ = join.forward_packed(x, off, join_cap, groups=groups, gaps=gaps, pcm=pcm16, wav=not pcm16)
-        return (p16 if pcm16 else y), out_off, piece
-
+    # ------------------------------------------------------------------ joiner and marks
     def _check_joiner(self, join, sample_rate):
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if join.rate != rate:
@@ -572,23 +613,10 @@ class ArtSpeech:
             raise ValueError(f"the marker describes a chain of (hop, L, M, rate) = {have}, the samples it is to mark come from {want}")
         return marks
 
-    def _tok_off(self, tok_lens):
-        return torch.tensor(np.concatenate([[0], np.cumsum([int(v) for v in tok_lens])]), dtype=torch.int32).to(self.device)
-
-    def _marks_packed(self, marker, tok_off, res, room, piece=None, groups=None, out_off=None):
-        """marks.Marker.forward_packed behind the acoustic model's result `res` (dur_i, frame_off, F0 / N / EMA) on the current stream;
-        room: the samples of the buffer the marks point into; piece / groups / out_off: the joiner's device results, or none"""
-        net = self.model.ArtsSpeech
-        B = res["frame_off"].numel() - 1
-        G = B if piece is None else out_off.numel() - 1
-        scale, offset = marker.affine(_stats24(net), torch.device(self.device)) if marker.physical else (None, None)
-        return marker.forward_packed(tok_off, res["dur_i"], res["frame_off"], res["F0"], res["N"], res["EMA"], piece=piece, groups=groups,
-                                     out_off=out_off, anim_cap=marker.anim_cap(room, G), scale=scale, offset=offset)
-
     def _speech_marks(self, marker, phonemes, m, piece=None, stream_off=None):
-        """the device results of _marks_packed -> marks.SpeechMarks (copies them to the host).  piece (host [B][4]): the utterances lie in
-        joined streams, positions are absolute; stream_off (host [B + 1]): every utterance is a stream of its own, positions count from
-        its own first sample"""
+        """the device results of the chain's marker (`_back_end`) -> marks.SpeechMarks (copies them to the host).  piece (host [B][4]): the
+        utterances lie in joined streams, positions are absolute; stream_off (host [B + 1]): every utterance is a stream of its own,
+        positions count from its own first sample"""
         from .marks import SpeechMarks, kept_symbols
         syms = [kept_symbols(self.textcleaner, p) for p in phonemes]
         anim_off = m["anim_off"].cpu().numpy()
@@ -601,90 +629,129 @@ class ArtSpeech:
             spans, origin = [(int(stream_off[b]), int(stream_off[b + 1])) for b in range(len(syms))], [int(v) for v in stream_off[:-1]]
         return SpeechMarks(marker.rate, marker.fps, syms, marks_h, spans, origin, tracks, active, anim_off)
 
-    def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marks=None):
-        """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
-        then the capacity vocoder on its frame_off and mel.  `inputs` = packed_inputs(...).  Every call with the same inputs dict reuses
-        the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
-        with other token / voice / prosody contents of the same geometry.  -> (samples [300 * 2 frame_cap], sample_off [B + 1]), both on the
-        device.  sample_rate (other than None / 24000): the generator writes fp32 and resample.Resampler(24000, sample_rate) runs on its
-        device sample_off on the same stream -> (samples [ceil(600 frame_cap L / M) + B], out_off [B + 1]); still no host value, still capturable.
-        join (a join.Joiner at the rate of the samples; groups / gaps / join_cap as Joiner.forward_packed and _join_packed take them): the
-        joiner runs on the device offsets the chain already has -- sample_off, or the resampler's out_off -- on the same stream, and the
-        call returns (stream [join_cap] fp32 or int16, out_off [G + 1], piece [B][4]) instead; with groups and gaps as device tensors (or
-        None) the chain stays capturable.
-        marks (a marks.Marker for this chain: its rate, the resampler's ratio, the generator's hop): the acoustic model also hands out
-        F0 / N / EMA and as_marks_f32 runs on the same stream behind the joiner -- or behind the resampler or the generator when there is
-        none -- on the device durations, offsets and pieces the chain already has; the call returns what it returns without marks and, as
-        one more entry, the dict of Marker.forward_packed (marks [sum tok_lens][2], tracks [12][anim_cap], active, anim_off), all on the
-        device.  The chain stays capturable (after one eager call, which also uploads the token offsets); marks=None issues exactly the
-        launches of before."""
-        if self.generator is None or not self.generator.runtime:
-            raise RuntimeError("frame_cap needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
-        if join is not None:
-            self._check_joiner(join, sample_rate)
-        marker = self._marker(marks, sample_rate)
-        net = self.model.ArtsSpeech
-        kw = {k: v for k, v in inputs.items() if not k.startswith("_")}
-        with torch.cuda.device(self.device):
-            if marker is not None:
-                kw["tracks"] = True
-                if "_tok_off" not in inputs:
-                    inputs["_tok_off"] = self._tok_off(inputs["tok_lens"])
-            res = net.forward_packed(kw.pop("tok"), kw.pop("tok_lens"), kw.pop("mel_p"), kw.pop("f0_p"), kw.pop("ema_p"), kw.pop("ref_lens"),
-                                     frame_cap=frame_cap, out=inputs.setdefault("_out", {}), **kw)
-            rs = self._out_resampler(sample_rate)
-            if join is not None:
-                wav, off = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len)
-                x = wav[0]
-                if rs is not None:
-                    x, _, off = rs.forward_packed(x, off, rs.out_len(wav.shape[1]) + off.numel() - 1)
-                if marker is None:
-                    return self._join_packed(join, x, off, groups, gaps, pcm16, join_cap)
-                if groups is not None:
-                    groups = join._i32(groups, torch.device(self.device), len(groups), "groups")       # (the joiner and the marker read ONE device copy)
-                stream, out_off, piece = self._join_packed(join, x, off, groups, gaps, pcm16, join_cap)
-                return stream, out_off, piece, self._marks_packed(marker, inputs["_tok_off"], res, stream.numel(), piece, groups, out_off)
-            if rs is not None:
-                wav, sample_off = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len)
-                B = sample_off.numel() - 1
-                y, p16, out_off = rs.forward_packed(wav[0], sample_off, rs.out_len(wav.shape[1]) + B, pcm=pcm16, wav=not pcm16)
-                ret = (p16 if pcm16 else y), out_off
-            else:
-                got = self.generator.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len, pcm=pcm16, wav=not pcm16)
-                ret = (got[2] if pcm16 else got[0][0]), got[1]
-            if marker is not None:
-                ret = ret + (self._marks_packed(marker, inputs["_tok_off"], res, ret[0].numel()),)
-        return ret
+    # ------------------------------------------------------------------ the public calls
+    @torch.no_grad()
+    def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None,
+                      token_prosody=None, token_smooth=False, fit=None):
+        """phonemes: the string the phonemizer returns (test.py:94-96) or a list of such strings; ref_mel: normalised
+        log-mel [80,T] (test.py:43-47) or a list; features: (f0_raw, ema_raw) per utterance when no extractor modules
+        are attached; (None, ema_raw) with a pitch extractor attached (attach_pitch_extractor).  Returns mel [B,80,2*max M] (what test.py:115 hands to the vocoder).
+        world / rank: BASELINE config C4 -- the batch is one GLOBAL batch, this process (one per GPU, torch.distributed initialised by
+        the caller) synthesises its length-sorted round-robin shard (artspeech_amd.shard: no data-path collective) and rank 0 gets the
+        whole batch back in the caller's order (other ranks: None).
+        voice: a Voice (every utterance) or a list of them, in place of ref_mel / features: the reference is not processed again.
+        prosody: a Prosody (every utterance) or a list of them: speaking rate, pitch, energy and articulators (not with forced_durations).
+        token_prosody: control inside an utterance -- per utterance a list with a Prosody (or None) per token (Prosody.from_spans builds it;
+        one utterance: the list itself), see Prosody.token_rows; token_smooth: glide between the tokens' settings.  Not with forced_durations.
+        fit: a Fit -- spans of tokens, or whole utterances, spoken in an exact time (fit.py); utterance indices count this call's list.  Not
+        with forced_durations, nor with world > 1."""
+        from .models import layout, unpack
+        if (voice is None) == (ref_mel is None):
+            raise ValueError("synthesis needs exactly one of ref_mel and voice")
+        if fit is not None and world > 1:
+            raise ValueError("fit: its utterance indices count one process's batch (no world / rank)")
+        single, phonemes, ref_mel, features, token_prosody = self._lists(phonemes, ref_mel, features, token_prosody)
+        req = dict(ref_mel=ref_mel, features=features, voice=voice, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth,
+                   fit=fit, forced_durations=forced_durations)
+        if world > 1 and not single:
+            from . import shard
 
-    def _synthesis_wav_cap(self, phonemes, ref_mel, features, voice, prosody, pcm16, frame_cap, token_prosody=None, token_smooth=False,
-                           sample_rate=None, marker=None, fit=None):
-        from . import _lib
-        inputs = self.packed_inputs(phonemes, ref_mel, features, voice, prosody, token_prosody, token_smooth, fit)
-        samples, sample_off, *m = self.chain_cap(inputs, frame_cap, pcm16=pcm16, sample_rate=sample_rate, marks=marker)
+            def step(idx):
+                if not idx:
+                    return []
+                res = self._forward(self.packed_inputs([phonemes[i] for i in idx], **self._take(req, idx)), aux=True)
+                return [m.cpu() for m in shard.split_utterances(res["mel"], res["frames2"])]
+
+            parts = shard.sharded_forward(step, [len(p) for p in phonemes], world, rank)
+            if parts is None:
+                return None
+            frames = [p.shape[1] for p in parts]
+            out = torch.zeros(len(parts), parts[0].shape[0], max(frames))
+            for b, p in enumerate(parts):
+                out[b, :, : p.shape[1]] = p
+            self._record(frames, None)
+            return out
+        res = self._forward(self.packed_inputs(phonemes, **req), aux=True)                             # test.py:110-113
         with torch.cuda.device(self.device):
-            off = sample_off.cpu().tolist()                                 # the one synchronisation: offsets, then the samples
-            if _lib.lib().as_device_status(0):
-                raise _lib.HipLibraryError(f"synthesis_wav(frame_cap={frame_cap}) failed: a kernel reported {_lib.device_status()} "
-                                           "(as_device_status); results since then are invalid")
-            host = samples[: off[-1]].cpu()
-            sm = self._speech_marks(marker, [phonemes] if isinstance(phonemes, str) else phonemes, m[0], stream_off=off) if m else None
-        hop = self.generator.hop
-        lens = [off[b + 1] - off[b] for b in range(len(off) - 1)]
-        rs = self._out_resampler(sample_rate)
-        # (mel frames, whatever the sample rate: n = ceil(hop f L / M) samples came from f = ceil(n M / L) // hop frames)
-        self._last_frames = [n // hop for n in lens] if rs is None else [-((-n * rs.M) // rs.L) // hop for n in lens]
-        out = torch.zeros(len(lens), max(max(lens), 1), dtype=host.dtype)
-        for b, n in enumerate(lens):
-            out[b, :n] = host[off[b]: off[b + 1]]
-        return out if marker is None else (out, sm)
+            mel = unpack(res["mel"], layout(res["frames2"], res["mel"].device))
+        self._record(list(res["frames2"]), res)
+        return mel
+
+    @torch.no_grad()
+    def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
+                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False, fit=None):
+        """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
+        (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
+        generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the chain's last kernel.
+        frame_cap=N (predicted durations, a runtime vocoder): room for N half-rate frames, all utterances together -- the acoustic model
+        hands its device frame_off and mel straight to the generator on the same stream (chain_cap): no host value is read between the
+        tokens and the samples, then ONE copy brings the sample offsets and the samples back.
+        More frames than room: HipLibraryError (AS_STATUS_CAPACITY).
+        sample_rate (None or 24000: the generator's own samples, exactly the calls above): the samples at that rate -- the packed fp32
+        samples go through resample.Resampler(24000, sample_rate) on the device before they are padded out or read back
+        ([B, max ceil(300 frames L / M)]); with pcm16 the generator writes fp32 only and the resampler writes the 16-bit samples.
+        marks (True: 60 frames per second, or a marks.Marker for this chain): the call returns (samples, marks.SpeechMarks) -- when every
+        token and word is spoken, in samples and seconds from the start of its own utterance's row, and F0, energy and the articulators
+        on the animation clock (as_marks_f32 on the device results the call already has, read back with the samples).
+        fit: a Fit (fit.py) -- Fit.whole(s) gives every utterance rint(40 s) * 600 samples at 24 kHz, spans give their tokens an exact time."""
+        single, phonemes, ref_mel, features, token_prosody = self._lists(phonemes, ref_mel, features, token_prosody)
+        req = dict(ref_mel=ref_mel, features=features, voice=voice, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth,
+                   fit=fit, forced_durations=forced_durations)
+        return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks)
+
+    def _wav(self, single, phonemes, req, pcm16, frame_cap, sample_rate, marks):
+        """synthesis_wav on lists: req = packed_inputs' keyword arguments"""
+        if self.generator is None:
+            raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
+        rs, marker = self._out_resampler(sample_rate), self._marker(marks, sample_rate)
+        if frame_cap is not None:
+            frame_cap = int(frame_cap)
+            if req["forced_durations"] is not None:
+                raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
+        res, out, off, _, m = self._chain(self.packed_inputs(phonemes, **req), frame_cap, pcm16, sample_rate, marker)
+        hop = self._hop()
+        with torch.cuda.device(self.device):
+            if frame_cap is None:
+                frames = list(res["frames2"])
+                off = self._sample_off(frames, rs)                          # every utterance a stream of its own at these prefix sums
+            else:
+                off, out = self._read_back(out, off, f"synthesis_wav(frame_cap={frame_cap})")
+                lens = [off[b + 1] - off[b] for b in range(len(off) - 1)]
+                # (mel frames, whatever the sample rate: n = ceil(hop f L / M) samples came from f = ceil(n M / L) // hop frames)
+                frames = [n // hop for n in lens] if rs is None else [-((-n * rs.M) // rs.L) // hop for n in lens]
+            wav = self._rows(out, off)                                      # (under a capacity: on the host)
+            sm = None if marker is None else self._speech_marks(marker, phonemes, m, stream_off=off)
+        self._record(frames, res)
+        wav = wav[0] if single else wav
+        return wav if marker is None else (wav, sm)
+
+    @torch.no_grad()
+    def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
+                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False, fit=None):
+        """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
+        end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
+        attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
+        device, with the library's own filter); sample_rate: the rate of the returned samples (synthesis_wav).  Loading / trimming the
+        file and espeak stay with the caller.  trim_db (None: the wave as it came): the silent ends of ref_wave are cut on the device
+        before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity).  fit: as
+        synthesis_wav / synthesis_mel take it."""
+        single, phonemes, waves, features, token_prosody = self._lists(phonemes, ref_wave, features, token_prosody)
+        req = dict(ref_mel=self._wave_mels(waves, ref_rate, trim_db), features=features, voice=None, prosody=prosody,
+                   token_prosody=token_prosody, token_smooth=token_smooth, fit=fit, forced_durations=forced_durations)
+        if self.generator is not None:
+            return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks)
+        if frame_cap is not None:
+            raise RuntimeError("frame_cap runs the acoustic model and the generator as one chain: attach_vocoder(h, checkpoint, runtime=True) first")
+        if marks is not None and marks is not False:
+            raise RuntimeError("marks time the samples: attach_vocoder(h, checkpoint) first")
+        return self.synthesis_mel(phonemes, **req)
 
     @torch.no_grad()
     def synthesis_paragraph(self, sentences, ref_mel=None, voice=None, prosody=None, pause_ms=None, joiner=None, sample_rate=None, pcm16=False,
                             frame_cap=None, features=None, max_tokens=None, marks=False, fit=None):
         """A paragraph as ONE stream: `sentences` is a list of phoneme strings, or one string that text.split_sentences cuts (max_tokens:
-        its limit per piece).  The sentences run as one batch through the calls above (synthesis_mel and the generator, or with frame_cap
-        the chain with no read-back; the resampler when sample_rate is given), then through join.Joiner on the device -- every sentence
+        its limit per piece).  The sentences run as one batch through the chain above (the acoustic model and the generator, with frame_cap
+        with no read-back in between; the resampler when sample_rate is given), then through join.Joiner on the device -- every sentence
         trimmed of the silence at its ends, faded at the cuts, levelled if the joiner says so, with pauses between -- and ONE copy brings
         the stream back.  One reference (ref_mel [80, T], with features as synthesis_mel takes them for one utterance) or one voice serves
         every sentence; lists of them go sentence by sentence.  joiner: a join.Joiner at the output's rate (None: Joiner(rate) with
@@ -696,7 +763,6 @@ class ArtSpeech:
         as_marks_f32 behind the joiner, read back with the stream.
         fit: a Fit whose utterances are the sentences -- Fit.whole([2.0, 3.5, None]) gives every sentence its slot (subtitles) on the
         vocoder's clock, before the joiner trims and spaces them."""
-        from . import _lib
         from .join import Joiner
         from .text import PAUSE_SCALE, split_sentences
         if self.generator is None:
@@ -717,92 +783,16 @@ class ArtSpeech:
             raise ValueError("synthesis_paragraph: nothing to say")
         if ref_mel is not None and not isinstance(ref_mel, (list, tuple)):
             ref_mel, features = [ref_mel] * B, None if features is None else [features] * B
-        rs = self._out_resampler(sample_rate)
         marker = self._marker(marks, sample_rate)
-        m = None
-        if frame_cap is not None:
-            inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody, fit=fit)
-            stream, out_off, piece, *m = self.chain_cap(inputs, int(frame_cap), pcm16=pcm16, sample_rate=sample_rate, join=joiner, gaps=gaps,
-                                                        marks=marker)
-            m = m[0] if m else None
-        else:
-            from .models import pack
-            from .vocoder import layout
-            mel = self.synthesis_mel(sentences, ref_mel, features=features, voice=voice, prosody=prosody, fit=fit)
-            gen, lens = self.generator, [int(v) for v in self._last_frames]
-            with torch.cuda.device(gen.device):
-                wav, lay_w = gen.forward_packed(pack(mel.to(gen.device), lens), layout(lens, gen.device))[:2]
-                x, off = wav.reshape(-1)[: max(lay_w.N, 1)], lay_w.col_off
-                if rs is not None:
-                    x, _, off = rs.forward_packed(x, off, max(sum(rs.out_len(n) for n in lay_w.widths_host), 1))
-                stream, out_off, piece = self._join_packed(joiner, x.contiguous(), off, None, gaps, pcm16)
-                if marker is not None:
-                    m = self._marks_packed(marker, self._tok_off(self._last_tok_lens), self._last_aux, stream.numel(), piece, None, out_off)
+        inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody, fit=fit)
+        res, stream, out_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, sample_rate, marker,
+                                                     join=joiner, gaps=gaps)
         with torch.cuda.device(self.device):
-            n = int(out_off.cpu()[-1])                                      # the one synchronisation: the length, then the stream
-            if _lib.lib().as_device_status(0):
-                raise _lib.HipLibraryError(f"synthesis_paragraph failed: a kernel reported {_lib.device_status()} (as_device_status); "
-                                           "results since then are invalid")
-            if marker is None:
-                return stream[:n].cpu(), piece.cpu()
-            piece_h = piece.cpu()
-            return stream[:n].cpu(), piece_h, self._speech_marks(marker, sentences, m, piece=piece_h.tolist())
-
-    @torch.no_grad()
-    def synthesis_mel(self, phonemes, ref_mel=None, features=None, forced_durations=None, world=1, rank=0, voice=None, prosody=None,
-                      token_prosody=None, token_smooth=False, fit=None):
-        """phonemes: the string the phonemizer returns (test.py:94-96) or a list of such strings; ref_mel: normalised
-        log-mel [80,T] (test.py:43-47) or a list; features: (f0_raw, ema_raw) per utterance when no extractor modules
-        are attached; (None, ema_raw) with a pitch extractor attached (attach_pitch_extractor).  Returns mel [B,80,2*max M] (what test.py:115 hands to the vocoder).
-        world / rank: BASELINE config C4 -- the batch is one GLOBAL batch, this process (one per GPU, torch.distributed initialised by
-        the caller) synthesises its length-sorted round-robin shard (artspeech_amd.shard: no data-path collective) and rank 0 gets the
-        whole batch back in the caller's order (other ranks: None).
-        voice: a Voice (every utterance) or a list of them, in place of ref_mel / features: the reference is not processed again.
-        prosody: a Prosody (every utterance) or a list of them: speaking rate, pitch, energy and articulators (not with forced_durations).
-        token_prosody: control inside an utterance -- per utterance a list with a Prosody (or None) per token (Prosody.from_spans builds it;
-        one utterance: the list itself), see Prosody.token_rows; token_smooth: glide between the tokens' settings.  Not with forced_durations.
-        fit: a Fit -- spans of tokens, or whole utterances, spoken in an exact time (fit.py); utterance indices count this call's list.  Not
-        with forced_durations, nor with world > 1."""
-        if (voice is None) == (ref_mel is None):
-            raise ValueError("synthesis needs exactly one of ref_mel and voice")
-        if fit is not None and world > 1:
-            raise ValueError("fit: its utterance indices count one process's batch (no world / rank)")
-        if world > 1 and not isinstance(phonemes, str):
-            from . import shard
-            lens = [len(p) for p in phonemes]
-
-            def step(idx):
-                if not idx:
-                    return []
-                sub = self.synthesis_mel([phonemes[i] for i in idx], None if ref_mel is None else [ref_mel[i] for i in idx],
-                                         features=None if features is None else [features[i] for i in idx],
-                                         forced_durations=None if forced_durations is None else [forced_durations[i] for i in idx],
-                                         voice=voice if voice is None or isinstance(voice, Voice) else [voice[i] for i in idx],
-                                         prosody=prosody if prosody is None or isinstance(prosody, Prosody) else [prosody[i] for i in idx],
-                                         token_prosody=None if token_prosody is None else [token_prosody[i] for i in idx],
-                                         token_smooth=token_smooth)
-                return [sub[k, :, : self._last_frames[k]].cpu() for k in range(len(idx))]
-
-            parts = shard.sharded_forward(step, lens, world, rank)
-            if parts is None:
-                return None
-            self._last_frames = [p.shape[1] for p in parts]
-            out = torch.zeros(len(parts), parts[0].shape[0], max(self._last_frames))
-            for b, p in enumerate(parts):
-                out[b, :, : p.shape[1]] = p
-            return out
-        text, tl, mels, ml, feats = self._padded_batch(phonemes, ref_mel, features)
-        B = len(tl)
-        rows = None if prosody is None else Prosody.rows(prosody, B, self.model.ArtsSpeech)
-        trows = None if token_prosody is None else self._token_rows(token_prosody, tl, isinstance(phonemes, str))
-        table, vidx = (None, None) if voice is None else self._voice_table(voice, B)
-        batch = [text, torch.LongTensor(tl), mels, None if ml is None else torch.LongTensor(ml), None, None, None]     # test.py:110-111
-        mel, aux = self.model.ArtsSpeech(batch, None, None, step="test", features=feats, forced_durations=forced_durations,
-                                         return_aux=True, voice=table, voice_idx=vidx, prosody=rows, token_prosody=trows,
-                                         token_smooth=token_smooth, fit=self._fit_built(fit, text, tl))                                               # test.py:113
-        self._last_frames = list(aux["frames2"])
-        self._last_aux, self._last_tok_lens = aux, tl                  # (device results the speech marks read: dur_i, frame_off, F0 / N / EMA)
-        return mel
+            _, stream = self._read_back(stream, out_off, "synthesis_paragraph")     # the one synchronisation: the length, then the stream
+            piece = piece.cpu()
+            sm = None if marker is None else self._speech_marks(marker, sentences, m, piece=piece.tolist())
+        self._record(None if frame_cap is not None else list(res["frames2"]), res)
+        return (stream, piece) if marker is None else (stream, piece, sm)
 
     @torch.no_grad()
     def synthesis_like(self, phonemes, like_wave=None, like_mel=None, like_rate=24000, ref_mel=None, voice=None, features=None,
@@ -825,23 +815,14 @@ class ArtSpeech:
         rec_frames), device tensors but for the two host lists of frame counts.  An utterance-level `prosody` composes on top: its speed
         scales the recording's timing."""
         from . import mimic, ops
-        from .models import layout, pack, pack_reference, unpack
+        from .models import layout, pack_reference, unpack
         if (like_wave is None) == (like_mel is None):
             raise ValueError("synthesis_like needs exactly one of like_wave and like_mel")
+        single, phonemes, like_wave, like_mel, ref_mel, features, like_features, like_feat12 = \
+            self._lists(phonemes, like_wave, like_mel, ref_mel, features, like_features, like_feat12)
         net = self.model.ArtsSpeech
         dev = net.device
-        single = isinstance(phonemes, str)
-        if like_wave is not None:
-            if getattr(self, "frontend", None) is None:
-                self.attach_frontend()
-            w = self._ref_at_24k(like_wave, like_rate)
-            if single:
-                rec = [self.frontend(w)[0]]
-            else:
-                m, n = self.frontend(list(w))
-                rec = [m[b, :, :k] for b, k in enumerate(n)]
-        else:
-            rec = [like_mel] if single else list(like_mel)
+        rec = self._wave_mels(like_wave, like_rate) if like_wave is not None else like_mel
         rec = [torch.as_tensor(m, dtype=torch.float32) for m in rec]
         ml = [int(m.shape[-1]) for m in rec]
         B = len(ml)
@@ -856,31 +837,18 @@ class ArtSpeech:
             rec_p = torch.cat([m.to(dev) for m in rec], dim=1).contiguous()
             Nr = rec_p.shape[1]
             if like_feat12 is not None:
-                f12 = [like_feat12] if single else list(like_feat12)
-                feat12 = torch.cat([torch.as_tensor(f, dtype=torch.float32).to(dev) for f in f12], dim=1).contiguous()
+                feat12 = torch.cat([torch.as_tensor(f, dtype=torch.float32).to(dev) for f in like_feat12], dim=1).contiguous()
                 if tuple(feat12.shape) != (12, Nr):
                     raise ValueError("like_feat12: [12, T] per utterance, T the recording's frames")
             else:
-                mels = torch.zeros(B, rec_p.shape[0], max(ml))
-                for b, m in enumerate(rec):
-                    mels[b, :, : ml[b]] = m.cpu()
-                feats = None
-                if like_features is not None:
-                    lf = [like_features] if single else list(like_features)
-                    f0 = None if any(f is None for f, _ in lf) else torch.zeros(B, 1, max(ml))
-                    ema = torch.zeros(B, 10, max(ml))
-                    for b, (f, e) in enumerate(lf):
-                        if f0 is not None:
-                            f0[b, :, : ml[b]] = torch.as_tensor(f, dtype=torch.float32).reshape(1, -1)
-                        ema[b, :, : ml[b]] = torch.as_tensor(e, dtype=torch.float32)
-                    feats = (f0, ema)
+                mels, _, feats = self._padded_reference(rec, like_features)
                 f0_raw, ema_raw = net.style_encoder._extract(mels, feats, ml)
                 _, f0_p, ema_p = pack_reference(mels, f0_raw, ema_raw, ml, dev)
                 feat12 = ops.ref_features(rec_p, f0_p, ema_p, Nr, torch.tensor(_stats24(net), dtype=torch.float32, device=dev),
                                           torch.empty((12, Nr), dtype=torch.float32, device=dev))
             rec_off = torch.tensor(np.concatenate([[0], np.cumsum(ml)]), dtype=torch.int32).to(dev)
             tok_off = torch.tensor(np.concatenate([[0], np.cumsum(kw["tok_lens"])]), dtype=torch.int32).to(dev)
-            a = net.forward_packed(**kw, aux=True)                                   # pass A (reads its frame counts back)
+            a = self._forward(kw, aux=True)                                          # pass A (reads its frame counts back)
             Tx, Ty = max(max(a["frames2"]), 1), max(ml)
             if Tx > mimic.MAX_T or Ty > mimic.MAX_T:
                 raise ValueError(f"synthesis_like: an utterance of more than {mimic.MAX_T} mel frames ({Tx} synthesised, {Ty} recorded)")
@@ -888,19 +856,17 @@ class ArtSpeech:
             trows, target, misses = mimic.transfer_rows(rows, tok_off, a["dur_i"], a["duration"].reshape(-1), a["F0"].reshape(-1),
                                                         a["N"].reshape(-1), a["EMA"], a["frame_off"], feat12, rec_off, transfer=transfer)
             syn_frames = list(a["frames2"])
-            b_out = net.forward_packed(**kw, aux=True, token_prosody=trows, token_smooth=smooth)       # pass B
-            self._last_frames = list(b_out["frames2"])
-            mel = unpack(b_out["mel"], layout(b_out["frames2"], dev))
+            b_out = self._forward(kw, aux=True, token_prosody=trows, token_smooth=smooth)              # pass B
+            frames = list(b_out["frames2"])
             info = dict(rows=rows, target_dur=target, misses=misses, total=total, dur_a=a["dur_i"], dur_b=b_out["dur_i"],
                         duration=a["duration"], tok_off=tok_off, token_rows=trows, syn_frames=syn_frames, rec_frames=ml)
-        if not use_vocoder:
-            return mel, info
-        rs = self._out_resampler(sample_rate)
-        if rs is not None:
-            wav = self._generate_resampled(mel, self._last_frames, rs, pcm16)
-        else:
-            wav = (self.generator(mel, lengths=self._last_frames, pcm16=True) if pcm16 else self.generator(mel, lengths=self._last_frames))[:, 0]
-        return (wav[0] if single else wav), info
+            if use_vocoder:
+                rs = self._out_resampler(sample_rate)
+                out = self._rows(self._back_end(kw, b_out, pcm16=pcm16, rs=rs)[0], self._sample_off(frames, rs))
+            else:
+                out = unpack(b_out["mel"], layout(frames, dev))
+        self._record(frames, b_out)
+        return (out[0] if single and use_vocoder else out), info
 
     def synthesis(self, text, ref_wav, save_path):
         raise NotImplementedError("text -> phonemes (espeak) and reading / trimming the wav file (librosa) are outside this path "

@@ -236,3 +236,24 @@ def test_like_a_wave(cuda):
     assert int(info["rows"][0, ty - 1]) == tx - 1 and bool((info["rows"][0, ty:] == -1).all())
     assert wav.dim() == 1 and wav.numel() == 300 * tts._last_frames[0] and bool(torch.isfinite(wav).all())
     assert int(info["dur_b"].sum()) * 2 == tts._last_frames[0] and abs(int(info["target_dur"].sum()) - (ty + 1) // 2) <= info["target_dur"].numel()
+
+
+def test_like_a_wave_resampled_to_pcm16(cuda):
+    """synthesis_like(sample_rate=16000, pcm16=True) == Generator.forward_packed then Resampler(24000, 16000).forward_packed(pcm=True) on the
+    mel that synthesis_like(vocode=False) returns for the same arguments, bit for bit"""
+    from artspeech_amd import resample
+    from artspeech_amd.models import layout, pack
+    tts = tts_of(cuda)
+    voice = tts.voice_from_wave(ref_wave(27000, 24000, 3))
+    args = dict(like_wave=ref_wave(30000, 16000, 5), like_rate=16000, voice=voice)
+    mel, _ = tts.synthesis_like(PH[0], vocode=False, **args)
+    frames = mel.shape[-1]
+    got, _ = tts.synthesis_like(PH[0], sample_rate=16000, pcm16=True, **args)
+    with torch.cuda.device(cuda):
+        wav, lay_w = tts.generator.forward_packed(pack(mel, [frames]), layout([frames], tts.generator.device))[:2]
+        _, want, off = resample.Resampler(24000, 16000, device=cuda).forward_packed(wav.reshape(-1), lay_w.col_off, 200 * frames, pcm=True, wav=False)
+    torch.cuda.synchronize()
+    assert _lib.lib().as_device_status(0) == 0
+    assert off.cpu().tolist() == [0, 200 * frames] and frames > 0
+    assert got.dtype == torch.int16 and got.shape == (200 * frames,) and bool(got.any())
+    assert torch.equal(got.cpu(), want.cpu())
