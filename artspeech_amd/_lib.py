@@ -275,6 +275,23 @@ _SIGNATURES.update({
 })
 
 
+class WindowCfg(ctypes.Structure):
+    """as_window_cfg: windowed vocoding in rounds of `core` mel frames per utterance (halo -1: the generator's own)"""
+    _fields_ = [("core", ctypes.c_int32), ("halo", ctypes.c_int32), ("hop", ctypes.c_int32)]
+
+
+_pWC = ctypes.POINTER(WindowCfg)
+_SIGNATURES.update({
+    "as_vocoder_halo_cfg": (c_i, [ctypes.POINTER(VocoderCfg)]),
+    "as_vocoder_halo": (c_i, [c_p]),
+    "as_window_host": (c_i, [_pWC, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, _pI32, _pI32]),
+    "as_window_gather_f32": (c_i, [_pWC, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p]),
+    "as_window_stitch_f32": (c_i, [_pWC, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "as_vocoder_windowed_workspace_bytes": (c_sz, [c_p, c_p, c_i, _pWC]),
+    "as_vocoder_forward_windowed": (c_i, [c_p, c_p, c_i, ctypes.POINTER(VocoderCap), ctypes.POINTER(VocoderIO), _pWC, c_i, c_i, c_p, c_sz, c_p]),
+})
+
+
 class JoinCfg(ctypes.Structure):
     """as_join_cfg (include/artspeech_hip.h): the paragraph joiner's rule in samples and ratios"""
     _fields_ = [("frame", ctypes.c_int32), ("trim_ratio", ctypes.c_float), ("keep", ctypes.c_int32), ("fade", ctypes.c_int32),

@@ -36,6 +36,10 @@ timing,pitch,energy).  Not with ``--emphasis`` (both set the per-token controls)
 Speech marks: ``--marks PATH`` also writes when every sentence, word and token is spoken in ``--out`` -- ``.jsonl`` (one JSON object per
 mark), ``.srt`` or ``.vtt`` (subtitles) -- and ``--tracks-out PATH.npz`` the pitch, energy and ten articulator tracks retimed onto ``--out`` at
 ``--marks-fps N[/D]`` frames per second (default 60), computed on the device behind the last stage (marks.Marker, as_marks_f32).
+
+In rounds: ``--window-ms MS`` (with ``--vocoder-runtime``) runs the generator of any of the chains above in rounds of MS milliseconds of audio
+per utterance (as_vocoder_forward_windowed: the same samples, a workspace that does not grow with the length), and ``--stream`` writes
+``--out`` as the rounds arrive (pipeline.ArtSpeech.synthesis_stream; ``--out -``: raw 16-bit PCM at 24 kHz on stdout).
 """
 import argparse
 import json
@@ -130,6 +134,11 @@ def build_parser():
     ap.add_argument("--vocoder-runtime", action="store_true", help="run the generator inside the library: one C call per batch (as_vocoder_forward)")
     ap.add_argument("--frame-cap", type=int, metavar="N", help="room for N half-rate frames (2 N mel frames): the acoustic model and the generator run as "
                     "one chain with no read-back of the predicted durations in between (as_vocoder_forward_cap); implies --vocoder-runtime")
+    ap.add_argument("--window-ms", type=float, metavar="MS", help="run the generator in rounds of MS milliseconds of audio per utterance (windowed "
+                    "vocoding, as_vocoder_forward_windowed: round(MS / 12.5) mel frames, at least 1): its workspace no longer grows with the "
+                    "length; needs --vocoder-runtime")
+    ap.add_argument("--stream", action="store_true", help="write --out as the rounds arrive (24 kHz, 16-bit; the wav header is patched at the end; "
+                    "--out - writes raw 16-bit PCM to stdout); rounds of --window-ms (default 800); needs --vocoder-runtime")
     ap.add_argument("--pcm16", action="store_true", help="16-bit samples straight from the generator's last kernel (no host-side conversion)")
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights instead of checkpoints (smoke / demo)")
     ap.add_argument("--tiny", action="store_true", help="with --synthetic: the small test configuration")
@@ -147,6 +156,11 @@ def parse_args(argv=None):
         if a.frame_cap < 1:
             ap.error("--frame-cap takes a positive number of frames")
         a.vocoder_runtime = True
+    if a.window_ms is not None and not (math.isfinite(a.window_ms) and a.window_ms > 0):
+        ap.error("--window-ms takes a positive number of milliseconds")
+    if (a.window_ms is not None or a.stream) and not a.vocoder_runtime:
+        ap.error("--window-ms and --stream need --vocoder-runtime")
+    a.window = window_frames(a.window_ms if a.window_ms is not None else STREAM_WINDOW_MS) if (a.window_ms is not None or a.stream) else None
     if a.pause_ms is not None and a.pause_ms < 0:
         ap.error("--pause-ms takes a pause of 0 ms or more")
     for name in ("trim_db", "trim_ref_db"):
@@ -174,6 +188,8 @@ def parse_args(argv=None):
         ap.error("--fit-seconds and --fit count the tokens of one utterance: not with --paragraph")
     if a.like_wav and a.with_fit:
         ap.error("--like-wav takes its timing from the recording: not with --fit-seconds / --fit")
+    if a.stream and (a.paragraph or a.like_wav or a.out_rate != 24000):
+        ap.error("--stream hands out the generator's own 24 kHz samples: not with --paragraph, --like-wav or another --out-rate")
     a.like_tracks = a.like_tracks if a.like_tracks is not None else "timing,pitch,energy"
     if a.marks is not None and not a.marks.lower().endswith((".jsonl", ".srt", ".vtt")):
         ap.error("--marks writes .jsonl, .srt or .vtt")
@@ -182,6 +198,10 @@ def parse_args(argv=None):
     a.with_marks = a.marks is not None or a.marks_fps is not None or a.tracks_out is not None
     if a.with_marks and a.like_wav:
         ap.error("--marks, --marks-fps and --tracks-out: not with --like-wav")
+    if a.with_marks and a.stream:
+        ap.error("--marks, --marks-fps and --tracks-out: not with --stream")
+    if a.out == "-" and not a.stream:
+        ap.error("--out - (raw PCM to stdout) needs --stream")
     try:
         if a.with_marks:
             marker_of(a, a.out_rate, None)
@@ -196,6 +216,33 @@ def parse_args(argv=None):
     except ValueError as e:
         ap.error(str(e))
     return ap, a
+
+
+STREAM_WINDOW_MS = 800.0       # --stream without --window-ms: 64 mel frames (ArtSpeech.synthesis_stream's default)
+
+
+def window_frames(ms):
+    """--window-ms -> mel frames of 12.5 ms (300 samples at 24 kHz), at least 1"""
+    return max(int(round(ms / 12.5)), 1)
+
+
+def stream_out(a, tts, rounds):
+    """--stream: the rounds of ArtSpeech.synthesis_stream (one utterance) to --out as they arrive -> samples written"""
+    n = 0
+    if a.out == "-":
+        for _, chunks in rounds:
+            sys.stdout.buffer.write(chunks[0].astype("<i2").tobytes())
+            sys.stdout.buffer.flush()
+            n += chunks[0].size
+        return n
+    with wave.open(a.out, "wb") as f:                                  # (the header's lengths are patched when the file is closed)
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(24000)
+        for _, chunks in rounds:
+            f.writeframesraw(chunks[0].astype("<i2").tobytes())
+            n += chunks[0].size
+    return n
 
 
 def transfer_of(a):
@@ -238,7 +285,7 @@ def voice_of(a, tts):
     voice = tts.voice_from_wave(wave_in, rate=ref_rate, trim_db=a.trim_ref_db)
     if a.save_voice:
         voice.save(a.save_voice)
-        print(f"{a.save_voice}: voice of {a.ref_wav}")
+        print(f"{a.save_voice}: voice of {a.ref_wav}", file=sys.stderr if a.out == "-" else sys.stdout)   # (--out -: stdout is the samples)
     return voice
 
 
@@ -352,9 +399,15 @@ def main(argv=None):
             tok["fit"] = fit_of(a, tts)
     except ValueError as e:
         ap.error(f"--fit-seconds / --fit: {e}")
+    if a.stream:
+        n = stream_out(a, tts, tts.synthesis_stream(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, frame_cap=a.frame_cap, window=a.window,
+                                                    pcm16=True, **tok))
+        print(f"{a.out}: {n / 24000.0:.2f} s of audio at 24000 Hz in rounds of {a.window} mel frames", file=sys.stderr)
+        return 0
     if a.paragraph:
         audio, piece, *sm = tts.synthesis_paragraph(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, joiner=joiner_of(a, a.out_rate),
-                                                    pcm16=a.pcm16, frame_cap=a.frame_cap, sample_rate=a.out_rate, marks=marker_for(a, tts))
+                                                    pcm16=a.pcm16, frame_cap=a.frame_cap, sample_rate=a.out_rate, marks=marker_for(a, tts),
+                                                    window=a.window)
         if sm:
             write_marks(a, sm[0])
         write_wav(a.out, audio.numpy(), sr=a.out_rate)
@@ -365,19 +418,19 @@ def main(argv=None):
     if a.like_wav:
         like, like_rate = read_wav_any(a.like_wav)
         audio, info = tts.synthesis_like(a.phonemes, like_wave=like, like_rate=like_rate, voice=voice_of(a, tts), transfer=transfer_of(a),
-                                         smooth=True, prosody=a.prosody, pcm16=a.pcm16, sample_rate=a.out_rate)
+                                         smooth=True, prosody=a.prosody, pcm16=a.pcm16, sample_rate=a.out_rate, window=a.window)
         print(f"{a.like_wav}: {int(info['rec_frames'][0])} frames aligned to {int(info['syn_frames'][0])} synthesised ones, "
               f"{int(info['misses'].sum())} token(s) kept their own duration")
     elif a.voice:
         audio = tts.synthesis_wav(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
-                                  sample_rate=a.out_rate, marks=marker_for(a, tts), **tok)
+                                  sample_rate=a.out_rate, marks=marker_for(a, tts), window=a.window, **tok)
     else:
         if a.save_voice:
             voice_of(a, tts)                                           # (written; the synthesis below starts from the wave itself)
         wave_in, ref_rate = read_wav_any(a.ref_wav)
         audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, ref_rate=ref_rate,
                                         sample_rate=a.out_rate, trim_db=a.trim_ref_db,
-                                        marks=marker_for(a, tts), **tok)
+                                        marks=marker_for(a, tts), window=a.window, **tok)
     if a.with_marks:
         audio, sm = audio
         write_marks(a, sm)

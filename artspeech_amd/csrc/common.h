@@ -137,6 +137,14 @@ struct AsVocGeo {
 };
 int as_vocoder_cap_geometry_launch(const AsVocGeo& g, hipStream_t stream);
 
+// Windowed vocoding (window.hip; the rule: window_rule.h): as_window_gather_f32 / as_window_stitch_f32 with the look at the device status
+// as an option (peek false: inside as_vocoder_forward_windowed, which has looked once)
+struct as_window_cfg;
+int as_window_gather_launch(const as_window_cfg* w, int round, const float* mel, int ld_mel, int num_mels, const int32_t* off, int B, int mult,
+                            int cap, int max_len, float* wmel, int ld_w, int32_t* woff, int32_t* skip_count, bool peek, hipStream_t s);
+int as_window_stitch_launch(const as_window_cfg* w, int round, const float* wwav, int ld_w, const int32_t* woff, const int32_t* off, int B,
+                            int mult, int cap, int max_len, float* wav, int16_t* pcm, int32_t* sample_off, bool peek, hipStream_t s);
+
 // kernel classes for the optional event profiler (prof.hip)
 enum { AS_CLS_GEMM = 0, AS_CLS_ADAIN = 1, AS_CLS_LN = 2, AS_CLS_ATTN = 3, AS_CLS_LSTM = 4, AS_CLS_MAS = 5, AS_CLS_OTHER = 6, AS_N_CLS = 7 };
 struct AsProfScope {

@@ -6,10 +6,13 @@
 // serves two passes: count (as_vocoder_workspace_bytes: the arena only adds up, nothing is launched) and run (kernels are enqueued;
 // nothing is allocated, nothing synchronises once the geometry's tables exist) -- and two kinds of geometry: lengths the host knows
 // (as_vocoder_forward: layouts cached in the plan) and lengths that exist on the device only (as_vocoder_forward_cap: capacity layouts
-// whose tables lie in the workspace and are rewritten by every call's geometry launch).
+// whose tables lie in the workspace and are rewritten by every call's geometry launch).  as_vocoder_forward_windowed runs the capacity
+// form round by round on windows of the mel (window.hip's gather in front, its stitch behind): the same sequence, a workspace sized by
+// the window.
 #include "common.h"
 #include "conv_gemm.h"
 #include "runtime.h"
+#include "window_rule.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -449,7 +452,109 @@ bool cap_ok(const as_vocoder* v, int B, int cap, int max_len)
     return (double)v->hop * (max_len > 0 ? max_len : cap) <= (double)AS_META_MAX_W && (double)v->hop * cap <= 2147483647.0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// windowed: rounds of gather -> generator_cap on the round's packed windows -> stitch (window_rule.h)
+// ------------------------------------------------------------------------------------------------------------------
+struct WinGeo {
+    as_window_cfg w;            // halo resolved, hop the generator's
+    int per, room;              // frames a window may have; frames of a round's buffers (B windows)
+};
+
+bool window_ok(const as_vocoder* v, int B, const as_window_cfg* w, WinGeo* out)
+{
+    if (!v || !w || B < 1 || B > 65535 || w->core < 1 || w->halo < -1) return false;
+    const int halo = w->halo >= 0 ? w->halo : as_window_halo(&v->cfg);
+    const double per = (double)w->core + 2.0 * halo;
+    if (halo < 0 || per * v->hop > (double)AS_META_MAX_W || per * B * v->hop > 2147483647.0) return false;
+    out->w = as_window_cfg{w->core, halo, v->hop};
+    out->per = (int)per;
+    out->room = (int)per * B;
+    return cap_ok(v, B, out->room, out->per);
+}
+
+// The outer geometry of the windowed call: no utterance is ever laid out whole -- a round lays out core + 2 halo frames of it --, so the
+// one-piece call's limit on an utterance's width (hop max_len <= AS_META_MAX_W) does not apply; sample positions stay 32-bit.
+bool window_cap_ok(const as_vocoder* v, int B, int cap, int max_len)
+{
+    if (!v || B < 1 || B > 65535 || cap < 1 || max_len < 0 || max_len > cap) return false;
+    return (double)v->hop * cap <= 2147483647.0;
+}
+
+// one round (the count pass: what any round needs).  The arena holds woff, the window mel and the window waveform in front of the
+// capacity form's own tables and tensors: every round lays them out alike, and the stream orders a round behind the one before it.
+void window_round(Seq& c, int B, const WinGeo& q, int round, const as_vocoder_cap* g, const as_vocoder_io* io)
+{
+    const as_vocoder& v = c.v;
+    int32_t* woff = c.i32((size_t)B + 1);
+    float* wmel = c.f32(v.cfg.num_mels, q.room);
+    float* wwav = c.f32(1, (int)((long long)v.hop * q.room));
+    if (c.rc) return;
+    if (c.go())
+        RUN(c, as_window_gather_launch(&q.w, round, io->mel, io->ld_mel, v.cfg.num_mels, g->off, B, g->mult, g->cap, g->max_len, wmel, q.room,
+                                       woff, nullptr, false, c.s));
+    const as_vocoder_cap inner = {woff, 1, q.room, q.per, nullptr};
+    const as_vocoder_io wio = {wmel, q.room, wwav, nullptr};
+    generator_cap(c, B, inner, wio);
+    if (c.go())
+        RUN(c, as_window_stitch_launch(&q.w, round, wwav, q.room, woff, g->off, B, g->mult, g->cap, g->max_len, io->wav, io->pcm,
+                                       g->sample_off, false, c.s));
+}
+
+size_t count_windowed(const as_vocoder* v, as_plan* p, int B, const WinGeo& q, int* rc)
+{
+    Seq c(*v, *p, nullptr, nullptr, 0, Pass::Count);
+    window_round(c, B, q, 0, nullptr, nullptr);
+    *rc = c.rc;
+    return c.rc ? 0 : c.peak + 256;
+}
+
 }  // namespace
+
+extern "C" int as_vocoder_halo_cfg(const as_vocoder_cfg* cfg)
+{
+    if (!cfg || !cfg_ok(*cfg)) return AS_EINVAL;
+    const int h = as_window_halo(cfg);
+    return h < 0 ? AS_EINVAL : h;
+}
+
+extern "C" int as_vocoder_halo(const as_vocoder* v) { return v ? as_vocoder_halo_cfg(&v->cfg) : AS_EINVAL; }
+
+extern "C" size_t as_vocoder_windowed_workspace_bytes(const as_vocoder* v, as_plan* p, int B, const as_window_cfg* w)
+{
+    WinGeo q;
+    if (!p || !window_ok(v, B, w, &q)) return 0;
+    size_t n = 0;
+    (void)abi([&] { int rc; n = count_windowed(v, p, B, q, &rc); return rc; });
+    return n;
+}
+
+extern "C" int as_vocoder_forward_windowed(const as_vocoder* v, as_plan* p, int B, const as_vocoder_cap* cap, const as_vocoder_io* io,
+                                           const as_window_cfg* w, int round0, int n_rounds, void* ws, size_t ws_bytes, as_stream_t stream)
+{
+    if (!p || !cap || !io || !io->mel || (!io->wav && !io->pcm) || !cap->off || cap->mult < 1 || !window_cap_ok(v, B, cap->cap, cap->max_len))
+        return AS_EINVAL;
+    WinGeo q;
+    if (!window_ok(v, B, w, &q) || round0 < 0 || n_rounds < 0 || io->ld_mel < cap->cap) return AS_EINVAL;
+    if (!ws || misaligned(ws) || (io->pcm && (reinterpret_cast<uintptr_t>(io->pcm) & 1) != 0)) return AS_EINVAL;
+    return abi([&] {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        int rc = enter(*p, s, ws, Pass::Run, false);                     // (no trim: the call touches no plan table)
+        if (rc != AS_OK) return rc;
+        // a workspace too small is refused before anything is launched
+        const size_t need = count_windowed(v, p, B, q, &rc);
+        if (rc != AS_OK) return rc;
+        if (need > ws_bytes) return (int)AS_ENOSPC;
+        const int all = window_rule::n_rounds(cap->max_len > 0 ? cap->max_len : cap->cap, q.w.core);
+        const long long end = n_rounds > 0 ? std::min<long long>((long long)round0 + n_rounds, all) : all;
+        for (long long r = round0; r < end; ++r) {
+            p->next_event = 0;                                          // (rounds are ordered by the stream: each may use the plan's events again)
+            Seq c(*v, *p, s, ws, ws_bytes, Pass::Run);
+            window_round(c, B, q, (int)r, cap, io);
+            if (c.rc) return c.rc;
+        }
+        return (int)AS_OK;
+    });
+}
 
 extern "C" int as_vocoder_fold_upsample_host(const float* wt, int Cin, int Cout, int u, float* wc)
 {

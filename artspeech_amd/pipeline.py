@@ -400,13 +400,16 @@ class ArtSpeech:
         return res
 
     def _back_end(self, inputs, res, frame_cap=None, max_len=None, pcm16=False, rs=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marker=None):
+                  marker=None, window=None):
         """generator -> [resampler rs] -> [joiner join] -> [marks] behind `_forward`'s result, on the current stream; between the stages
         travel packed fp32 samples and a device offset table [B + 1].  Two regimes: frame_cap None -- the host knows the frame counts
         (res["frames2"]) and every stage gets exactly the room its samples need; frame_cap=N -- only the device knows them (res["frame_off"]),
         the generator writes 300 * 2 N samples and the resampler gets out_len(that) + B; no host value is read and, with groups and gaps
         on the device (or None), nothing is uploaded: the call can be captured.  Decided here and nowhere else: the LAST stage writes the
-        int16 samples of pcm16, every stage before it fp32; the marker is told the size of the buffer its marks point into.
+        int16 samples of pcm16, every stage before it fp32; the marker is told the size of the buffer its marks point into; and
+        window=frames (a runtime vocoder) makes the generator's windowed call (Generator.forward_packed_windowed: rounds of `window` mel
+        frames per utterance, a workspace that does not grow with the capacity) take the place of the one-piece call -- the stages behind
+        it see the same offsets and, within the generator's bound, the same samples; window=None issues exactly the launches of before.
         -> (samples fp32 or int16, off [B + 1] -- behind a joiner out_off [G + 1] --, piece [B][4] or None, Marker.forward_packed's dict or
         None), all on the device."""
         from .models import layout
@@ -415,12 +418,24 @@ class ArtSpeech:
         last = "join" if join is not None else "rs" if rs is not None else "gen"
         with torch.cuda.device(self.device):
             p = pcm16 and last == "gen"
-            if frame_cap is None:
+            if window is not None and not gen.runtime:
+                raise RuntimeError("window needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
+            if frame_cap is None and window is None:
                 # (the packed mel as forward_packed wrote it; the operator-level generator always writes fp32 too)
                 wav, lay_w, *pcm = gen.forward_packed(res["mel"], layout(res["frames2"], gen.device), pcm=p)
                 x, off = wav.reshape(-1)[: max(lay_w.N, 1)], lay_w.col_off
             else:
-                wav, off, *pcm = gen.forward_packed_cap(res["mel"], res["frame_off"], 2, 2 * frame_cap, max_len=max_len, pcm=p, wav=not p)
+                if frame_cap is None:                                       # (the host knows the lengths: the capacity is their sum)
+                    lay = layout(res["frames2"], gen.device)
+                    lay_w = lay.scaled(gen.hop)
+                    geo = (lay.col_off, 1, max(lay.N, 1))
+                    max_len = max(lay.max_w, 1)
+                else:
+                    geo = (res["frame_off"], 2, 2 * frame_cap)
+                if window is not None:
+                    wav, off, *pcm = gen.forward_packed_windowed(res["mel"], *geo, window, max_len=max_len, pcm=p, wav=not p)
+                else:
+                    wav, off, *pcm = gen.forward_packed_cap(res["mel"], *geo, max_len=max_len, pcm=p, wav=not p)
                 x = None if p else wav[0]
             out = pcm[0] if p else x
             if rs is not None:
@@ -466,7 +481,7 @@ class ArtSpeech:
                                            **stages)
 
     def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marks=None):
+                  marks=None, window=None):
         """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
         then the capacity vocoder on its frame_off and mel (`_chain`).  `inputs` = packed_inputs(...).  Every call with the same inputs dict
         reuses the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
@@ -482,11 +497,15 @@ class ArtSpeech:
         none -- on the device durations, offsets and pieces the chain already has; the call returns what it returns without marks and, as
         one more entry, the dict of Marker.forward_packed (marks [sum tok_lens][2], tracks [12][anim_cap], active, anim_off), all on the
         device.  The chain stays capturable (after one eager call, which also uploads the token offsets); marks=None issues exactly the
-        launches of before."""
+        launches of before.
+        window (mel frames; None: the one-piece generator, exactly the launches of before): the generator runs in rounds of `window` frames
+        per utterance (`_back_end`): same offsets, same samples within its bound, and its workspace no longer grows with frame_cap.  The
+        call issues ceil(max_len / window) rounds -- max_len None: ceil(2 frame_cap / window), most of them past every utterance's end --,
+        so name max_len, the mel frames the longest utterance may have, with it."""
         if join is not None:
             self._check_joiner(join, sample_rate)
         _, out, off, piece, m = self._chain(inputs, frame_cap, pcm16, sample_rate, self._marker(marks, sample_rate), max_len=max_len, join=join,
-                                            groups=groups, gaps=gaps, join_cap=join_cap)
+                                            groups=groups, gaps=gaps, join_cap=join_cap, window=window)
         ret = (out, off) if join is None else (out, off, piece)
         return ret if m is None else ret + (m,)
 
@@ -679,7 +698,8 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
-                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False, fit=None):
+                      frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False, fit=None, window=None,
+                      max_len=None):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the chain's last kernel.
@@ -693,13 +713,16 @@ class ArtSpeech:
         marks (True: 60 frames per second, or a marks.Marker for this chain): the call returns (samples, marks.SpeechMarks) -- when every
         token and word is spoken, in samples and seconds from the start of its own utterance's row, and F0, energy and the articulators
         on the animation clock (as_marks_f32 on the device results the call already has, read back with the samples).
-        fit: a Fit (fit.py) -- Fit.whole(s) gives every utterance rint(40 s) * 600 samples at 24 kHz, spans give their tokens an exact time."""
+        fit: a Fit (fit.py) -- Fit.whole(s) gives every utterance rint(40 s) * 600 samples at 24 kHz, spans give their tokens an exact time.
+        window (mel frames, a runtime vocoder): the generator in rounds of that many frames per utterance (`_back_end`).
+        max_len (with frame_cap): the mel frames the longest utterance may have (None: 2 frame_cap) -- it sizes the generator's grids and,
+        with window, is what the number of rounds is taken from: ceil(max_len / window); a longer utterance raises AS_STATUS_CAPACITY."""
         single, phonemes, ref_mel, features, token_prosody = self._lists(phonemes, ref_mel, features, token_prosody)
         req = dict(ref_mel=ref_mel, features=features, voice=voice, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth,
                    fit=fit, forced_durations=forced_durations)
-        return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks)
+        return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len)
 
-    def _wav(self, single, phonemes, req, pcm16, frame_cap, sample_rate, marks):
+    def _wav(self, single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=None, max_len=None):
         """synthesis_wav on lists: req = packed_inputs' keyword arguments"""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
@@ -708,7 +731,10 @@ class ArtSpeech:
             frame_cap = int(frame_cap)
             if req["forced_durations"] is not None:
                 raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
-        res, out, off, _, m = self._chain(self.packed_inputs(phonemes, **req), frame_cap, pcm16, sample_rate, marker)
+        if max_len is not None and frame_cap is None:
+            raise ValueError("max_len goes with frame_cap (without it the frame counts are read back and every stage is sized by them)")
+        res, out, off, _, m = self._chain(self.packed_inputs(phonemes, **req), frame_cap, pcm16, sample_rate, marker, window=window,
+                                          max_len=max_len)
         hop = self._hop()
         with torch.cuda.device(self.device):
             if frame_cap is None:
@@ -727,19 +753,20 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
-                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False, fit=None):
+                            token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False, fit=None, window=None,
+                            max_len=None):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
         attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
         device, with the library's own filter); sample_rate: the rate of the returned samples (synthesis_wav).  Loading / trimming the
         file and espeak stay with the caller.  trim_db (None: the wave as it came): the silent ends of ref_wave are cut on the device
-        before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity).  fit: as
-        synthesis_wav / synthesis_mel take it."""
+        before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity).  fit, window,
+        max_len: as synthesis_wav takes them."""
         single, phonemes, waves, features, token_prosody = self._lists(phonemes, ref_wave, features, token_prosody)
         req = dict(ref_mel=self._wave_mels(waves, ref_rate, trim_db), features=features, voice=None, prosody=prosody,
                    token_prosody=token_prosody, token_smooth=token_smooth, fit=fit, forced_durations=forced_durations)
         if self.generator is not None:
-            return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks)
+            return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len)
         if frame_cap is not None:
             raise RuntimeError("frame_cap runs the acoustic model and the generator as one chain: attach_vocoder(h, checkpoint, runtime=True) first")
         if marks is not None and marks is not False:
@@ -748,7 +775,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_paragraph(self, sentences, ref_mel=None, voice=None, prosody=None, pause_ms=None, joiner=None, sample_rate=None, pcm16=False,
-                            frame_cap=None, features=None, max_tokens=None, marks=False, fit=None):
+                            frame_cap=None, features=None, max_tokens=None, marks=False, fit=None, window=None, max_len=None):
         """A paragraph as ONE stream: `sentences` is a list of phoneme strings, or one string that text.split_sentences cuts (max_tokens:
         its limit per piece).  The sentences run as one batch through the chain above (the acoustic model and the generator, with frame_cap
         with no read-back in between; the resampler when sample_rate is given), then through join.Joiner on the device -- every sentence
@@ -762,7 +789,9 @@ class ArtSpeech:
         and sentence is spoken in the stream and the twelve tracks on the animation clock, with `active` 0 in the pauses -- from
         as_marks_f32 behind the joiner, read back with the stream.
         fit: a Fit whose utterances are the sentences -- Fit.whole([2.0, 3.5, None]) gives every sentence its slot (subtitles) on the
-        vocoder's clock, before the joiner trims and spaces them."""
+        vocoder's clock, before the joiner trims and spaces them.
+        window (mel frames, a runtime vocoder): the generator in rounds of that many frames per sentence (`_back_end`); max_len (with
+        frame_cap): the mel frames the longest sentence may have, as synthesis_wav takes it."""
         from .join import Joiner
         from .text import PAUSE_SCALE, split_sentences
         if self.generator is None:
@@ -786,7 +815,8 @@ class ArtSpeech:
         marker = self._marker(marks, sample_rate)
         inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody, fit=fit)
         res, stream, out_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, sample_rate, marker,
-                                                     join=joiner, gaps=gaps)
+                                                     join=joiner, gaps=gaps, window=window,
+                                                     **({} if frame_cap is None else {"max_len": max_len}))
         with torch.cuda.device(self.device):
             _, stream = self._read_back(stream, out_off, "synthesis_paragraph")     # the one synchronisation: the length, then the stream
             piece = piece.cpu()
@@ -794,10 +824,93 @@ class ArtSpeech:
         self._record(None if frame_cap is not None else list(res["frames2"]), res)
         return (stream, piece) if marker is None else (stream, piece, sm)
 
+    def synthesis_stream(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, frame_cap=None,
+                         token_prosody=None, token_smooth=False, fit=None, window=64, pcm16=True, sample_rate=None, joiner=None, marks=False):
+        """synthesis_wav whose samples leave while later ones are still being made: a Python generator over the rounds of the windowed
+        vocoder (Generator.forward_packed_windowed).  ONE acoustic call (under frame_cap, or with known frame counts), ONE read-back of the
+        B + 1 frame offsets -- the one synchronisation of the acoustic side, and when the device status is checked --, then the generator's
+        rounds of `window` mel frames per utterance one at a time, one round launched ahead of the one being copied out.  Yields
+        (round, [numpy samples of utterance b in that round, int16 or fp32, possibly empty]) and stops after the last round in which an
+        utterance has frames; the chunks of an utterance, concatenated, are its synthesis_wav(window=) samples bit for bit.
+        `rounds_launched` counts the vocoder rounds issued so far; it lives on this object and every call sets it to 0, so two streams of
+        one ArtSpeech that are consumed in turns share it: it is a figure for one stream at a time.  24 kHz generator output only:
+        sample_rate, a joiner or marks raise ValueError (a streaming resampler and joiner need state of their own)."""
+        if sample_rate not in (None, SAMPLE_RATE) or joiner is not None or (marks is not None and marks is not False):
+            raise ValueError("synthesis_stream hands out the generator's own 24 kHz samples: no sample_rate, joiner or marks")
+        if self.generator is None or not self.generator.runtime:
+            raise RuntimeError("synthesis_stream needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
+        if int(window) < 1:
+            raise ValueError("synthesis_stream: window is a number of mel frames >= 1")
+        if frame_cap is not None and forced_durations is not None:
+            raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
+        _, phonemes, ref_mel, features, token_prosody = self._lists(phonemes, ref_mel, features, token_prosody)
+        req = dict(ref_mel=ref_mel, features=features, voice=voice, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth,
+                   fit=fit, forced_durations=forced_durations)
+        self.rounds_launched = 0
+        return self._stream(self.packed_inputs(phonemes, **req), None if frame_cap is None else int(frame_cap), int(window), bool(pcm16))
+
+    @torch.no_grad()
+    def _stream(self, inputs, frame_cap, core, pcm16):
+        from . import _lib
+        from .models import layout
+        gen, hop = self.generator, self._hop()
+        with torch.cuda.device(self.device):
+            if frame_cap is None:
+                res = self._forward(inputs, aux=True)
+                lay = layout(res["frames2"], gen.device)
+                off_dev, mult, cap, lens = lay.col_off, 1, max(lay.N, 1), [int(f) for f in res["frames2"]]
+            else:
+                res = self._forward(inputs, frame_cap=frame_cap, out=inputs.setdefault("_out", {}))
+                off_dev, mult, cap = res["frame_off"], 2, 2 * frame_cap
+                off = off_dev.cpu().tolist()                                # the one synchronisation: the offsets, then the status
+                if _lib.lib().as_device_status(0):
+                    raise _lib.HipLibraryError(f"synthesis_stream(frame_cap={frame_cap}) failed: a kernel reported {_lib.device_status()} "
+                                               "(as_device_status); results since then are invalid")
+                lens = [mult * (off[b + 1] - off[b]) for b in range(len(off) - 1)]
+            self._record(lens, res)
+            first = np.concatenate([[0], np.cumsum(lens)]).tolist()
+            longest = max(max(lens), 1) if lens else 1
+            n_rounds = -(-max(lens) // core) if lens else 0
+            out, copier, done = None, torch.cuda.Stream(device=self.device), []
+            # ONE pinned buffer for every round's chunks (a round has at most hop * core samples per utterance)
+            host = torch.empty(hop * min(core, longest) * len(lens), dtype=torch.int16 if pcm16 else torch.float32).pin_memory()
+
+            def launch(r):
+                nonlocal out
+                out = gen.forward_packed_windowed(res["mel"], off_dev, mult, cap, core, max_len=longest, pcm=pcm16, wav=not pcm16,
+                                                  rounds=(r, 1), out=out)
+                if len(out) == 2:
+                    out = out + (None,)
+                ev = torch.cuda.Event()
+                ev.record()
+                done.append(ev)
+                self.rounds_launched += 1
+
+            if n_rounds:
+                launch(0)
+            for r in range(n_rounds):
+                if r + 1 < n_rounds:
+                    launch(r + 1)                                           # one round ahead of the one that is copied out
+                samples = out[2] if pcm16 else out[0][0]
+                spans = [(hop * (first[b] + min(r * core, n)), hop * (first[b] + min((r + 1) * core, n))) for b, n in enumerate(lens)]
+                with torch.cuda.stream(copier):
+                    copier.wait_event(done[r])
+                    at = 0
+                    for a, e in spans:
+                        host[at: at + e - a].copy_(samples[a:e], non_blocking=True)
+                        at += e - a
+                    copier.synchronize()
+                view, at, chunks = host.numpy(), 0, []
+                for a, e in spans:
+                    chunks.append(view[at: at + e - a].copy())
+                    at += e - a
+                yield r, chunks
+            torch.cuda.current_stream().wait_stream(copier)
+
     @torch.no_grad()
     def synthesis_like(self, phonemes, like_wave=None, like_mel=None, like_rate=24000, ref_mel=None, voice=None, features=None,
                        like_features=None, like_feat12=None, transfer=None, smooth=True, center=True, prosody=None, vocode=None,
-                       pcm16=False, sample_rate=None):
+                       pcm16=False, sample_rate=None, window=None):
         """Speak `phonemes` in the voice of ref_mel / voice WITH THE DELIVERY OF A RECORDING of the same phonemes (any speaker): its rhythm
         and, per track, how its pitch, energy and articulators differ from what the model predicts (mimic.Transfer says which).
         like_wave (samples at like_rate Hz: resampled and turned into a log-mel on the device) or like_mel (normalised log-mel [80, T]);
@@ -813,7 +926,8 @@ class ArtSpeech:
         Returns (what synthesis_wav returns when a vocoder is attached and `vocode` is not False, else what synthesis_mel returns,
         info): info = dict(rows [B, Ty], target_dur, misses [B], total [B], token_rows, dur_a, dur_b, duration, tok_off, syn_frames,
         rec_frames), device tensors but for the two host lists of frame counts.  An utterance-level `prosody` composes on top: its speed
-        scales the recording's timing."""
+        scales the recording's timing.
+        window (mel frames, a runtime vocoder): the generator in rounds of that many frames, as synthesis_wav takes it."""
         from . import mimic, ops
         from .models import layout, pack_reference, unpack
         if (like_wave is None) == (like_mel is None):
@@ -862,7 +976,7 @@ class ArtSpeech:
                         duration=a["duration"], tok_off=tok_off, token_rows=trows, syn_frames=syn_frames, rec_frames=ml)
             if use_vocoder:
                 rs = self._out_resampler(sample_rate)
-                out = self._rows(self._back_end(kw, b_out, pcm16=pcm16, rs=rs)[0], self._sample_off(frames, rs))
+                out = self._rows(self._back_end(kw, b_out, pcm16=pcm16, rs=rs, window=window)[0], self._sample_off(frames, rs))
             else:
                 out = unpack(b_out["mel"], layout(frames, dev))
         self._record(frames, b_out)

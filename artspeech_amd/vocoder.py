@@ -96,7 +96,8 @@ class Generator:
         self.device = _need_gpu(device if device is not None else "cuda")
         self.W = None
         self.runtime = bool(runtime)
-        self._voc = self._plan = self._ws = self._ws_cap = None
+        self._voc = self._plan = self._ws = self._ws_cap = self._ws_win = None
+        self.halo = None
 
     def __del__(self):
         try:
@@ -111,7 +112,7 @@ class Generator:
             L.as_plan_destroy(self._plan)
         if self._voc:
             L.as_vocoder_destroy(self._voc)
-        self._voc = self._plan = self._ws = self._ws_cap = None
+        self._voc = self._plan = self._ws = self._ws_cap = self._ws_win = None
 
     # ------------------------------------------------------------------ the library's generator (runtime=True)
     def runtime_cfg(self):
@@ -146,6 +147,7 @@ class Generator:
             _lib.check(L.as_vocoder_plan_create(voc, ctypes.byref(plan)), "as_vocoder_plan_create")
             self._plan = plan
         self.hop = L.as_vocoder_hop(voc)
+        self.halo = L.as_vocoder_halo(voc)                 # mel frames a window needs on either side (csrc/window_rule.h)
         return self
 
     def _forward_runtime(self, mel_p, lay, wav=True, pcm=False):
@@ -205,6 +207,48 @@ class Generator:
             g.off, g.mult, g.cap, g.max_len, g.sample_off = off.data_ptr(), int(mult), cap, max_len, sample_off.data_ptr()
             _lib.check(L.as_vocoder_forward_cap(self._voc, self._plan, B, ctypes.byref(g), ctypes.byref(io), self._ws_cap.data_ptr(),
                                                 self._ws_cap.numel(), _lib.stream()), "as_vocoder_forward_cap")
+        return (out_w, sample_off, out_p) if pcm else (out_w, sample_off)
+
+    def forward_packed_windowed(self, mel_p, off, mult, cap, core, max_len=None, halo=None, pcm=False, wav=True, rounds=None, out=None):
+        """forward_packed_cap in rounds of `core` mel frames per utterance (as_vocoder_forward_windowed; csrc/window_rule.h): the same
+        arguments, the same return value and output layout, the same samples within the module's bound -- every round vocodes each
+        utterance's next `core` frames with `halo` frames of context on either side (None: self.halo, the generator's receptive field) and
+        stores the core's samples in place.  The workspace is this method's own, depends on B, core and halo only (not on cap) and only ever
+        grows: a graph captured from this call stays valid as long as no larger (B, core, halo) has been run since.
+        rounds = (round0, n): only those rounds (n = 0: every round from round0 on); round 0 also writes the filler's zeros and sample_off.
+        out = (wav, sample_off, pcm) of an earlier call: the buffers to write into (rounds in pieces)."""
+        if not self.runtime:
+            raise ValueError("forward_packed_windowed needs Generator(runtime=True)")
+        if self._voc is None:
+            raise RuntimeError("no weights loaded: call load_state_dict first")
+        if not (wav or pcm):
+            raise ValueError("forward_packed_windowed: at least one of wav and pcm")
+        if off.dtype != torch.int32 or not off.is_cuda or not off.is_contiguous():
+            raise ValueError("forward_packed_windowed: off must be a contiguous int32 tensor on the GPU")
+        L = _lib.lib()
+        B, cap, max_len = off.numel() - 1, int(cap), int(max_len or 0)
+        wc = _lib.WindowCfg(int(core), -1 if halo is None else int(halo), self.hop)
+        round0, n_rounds = (0, 0) if rounds is None else (int(rounds[0]), int(rounds[1]))
+        if round0 < 0 or n_rounds < 0:
+            raise ValueError("forward_packed_windowed: rounds = (first round >= 0, count >= 0)")
+        with torch.cuda.device(self.device):
+            need = L.as_vocoder_windowed_workspace_bytes(self._voc, self._plan, B, ctypes.byref(wc))
+            if need == 0:
+                raise _lib.HipLibraryError("as_vocoder_windowed_workspace_bytes: invalid window (core < 1, halo < -1, or a window beyond AS_META_MAX_W samples?)")
+            if self._ws_win is None or self._ws_win.numel() < need:
+                self._ws_win = torch.empty(need, dtype=torch.uint8, device=self.device)
+            n = cap * self.hop
+            if out is not None:
+                out_w, sample_off, out_p = out
+            else:
+                out_w = torch.empty((1, n), dtype=torch.float32, device=self.device) if wav else None
+                out_p = torch.empty(n, dtype=torch.int16, device=self.device) if pcm else None
+                sample_off = torch.empty(B + 1, dtype=torch.int32, device=self.device)
+            io, g = _lib.VocoderIO(), _lib.VocoderCap()
+            io.mel, io.ld_mel, io.wav, io.pcm = ops._p(mel_p), ops._ld(mel_p), ops._p(out_w), ops._p(out_p)
+            g.off, g.mult, g.cap, g.max_len, g.sample_off = off.data_ptr(), int(mult), cap, max_len, sample_off.data_ptr()
+            _lib.check(L.as_vocoder_forward_windowed(self._voc, self._plan, B, ctypes.byref(g), ctypes.byref(io), ctypes.byref(wc), round0, n_rounds,
+                                                     self._ws_win.data_ptr(), self._ws_win.numel(), _lib.stream()), "as_vocoder_forward_windowed")
         return (out_w, sample_off, out_p) if pcm else (out_w, sample_off)
 
     # ------------------------------------------------------------------ weights

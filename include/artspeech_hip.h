@@ -934,6 +934,51 @@ typedef struct as_vocoder_cap {
 size_t as_vocoder_cap_workspace_bytes(const as_vocoder* v, as_plan* p, int B, int cap, int max_len);
 int as_vocoder_forward_cap(const as_vocoder* v, as_plan* p, int B, const as_vocoder_cap* cap, const as_vocoder_io* io,
                            void* ws, size_t ws_bytes, as_stream_t stream);
+/* Windowed vocoding (csrc/window.hip, csrc/vocoder_rt.hip; the rule: csrc/window_rule.h): the capacity call in
+ * rounds of `core` mel frames per utterance -- the same inputs, the same output layout, the same samples within the module's bound -- with
+ * a workspace that does not depend on the capacity and rounds that can be handed out one by one (streaming).
+ * The generator is convolutions only, so a sample depends on the mel frames within a fixed radius: conv_pre 3 frames; per stage the 3-tap
+ * phase conv 1 sample at the stage's input rate and the widest stack max_j (k_j / 2) (sum_n d_jn + n_dilations) samples at its output
+ * rate; conv_post 3 samples.  halo = ceil(radius) frames: 12 for Vocoder/config.json (an upper bound).
+ * The rule, per utterance of n mel frames (n as as_vocoder_cap_geometry lays it out: mult (off[b + 1] - off[b]) cut at cap and max_len;
+ * a cut raises AS_STATUS_CAPACITY).  Round w: core frames [c0, c1) = [w core, min(n, (w + 1) core)), empty when w core >= n; source
+ * frames [s0, s1) = [max(0, c0 - halo), min(n, c1 + halo)); skip = c0 - s0, count = c1 - c0.  The source is clamped to the utterance's
+ * own ends: the window's zero padding is then the utterance's, first and last windows included.  woff [B + 1] = the prefix sums of
+ * s1 - s0 over the batch (an ended utterance has an empty window): never more than core + 2 halo frames per utterance.
+ * as_window_cfg: core >= 1; halo >= 0, or -1 = the generator's own (as_vocoder_* only); hop = samples per frame for the stitch called
+ * alone (the as_vocoder_* calls use the generator's own and ignore it).
+ * as_vocoder_halo_cfg    host only, no GPU: the halo in frames of a configuration; AS_EINVAL for one as_vocoder_create refuses.
+ * as_window_host         the rule on HOST arrays: woff [B + 1], skip [B], count [B] of round `round`, *n_rounds = ceil(max_len / core)
+ *                        (max_len 0 = cap), *over = 1 when the layout was cut (each pointer may be NULL).
+ * as_window_gather_f32   one launch: mel [num_mels][ld_mel] -> the round's packed frames wmel [num_mels][ld_w], ld_w >= B (core + 2 halo);
+ *                        woff DEVICE out [B + 1]; skip_count DEVICE out [2 B] = {skip, count} per utterance, or NULL.  Every workgroup
+ *                        recomputes its utterance's offset from `off` (B <= 65535): no second launch.  Raises AS_STATUS_CAPACITY for a cut.
+ * as_window_stitch_f32   one launch: the round's samples wwav [hop ld_w] (utterance b from hop woff[b]) -> each utterance's core samples
+ *                        [hop skip, hop (skip + count)) at hop (o_b + round core) of wav fp32 and / or pcm (as_conv_post_pcm_f32's rule on
+ *                        the fp32 value: a NaN stores 0 and raises AS_STATUS_F16_RANGE), each hop cap samples.  Round 0 also writes the
+ *                        zeros of the filler [hop total, hop cap) and sample_off [B + 1] when given.  skip and count are derived from
+ *                        `off` by the rule; a woff outside its buffer stores nothing and raises AS_STATUS_CAPACITY.
+ * Both launches work on DEVICE offsets, read nothing back, upload and allocate nothing and can be captured.
+ * as_vocoder_forward_windowed   rounds [round0, round0 + n_rounds) (n_rounds 0: all of them) of: gather, the launch sequence of
+ *                        as_vocoder_forward_cap on woff with mult 1, cap B (core + 2 halo), max_len core + 2 halo into a window waveform in
+ *                        the workspace, stitch.  cap / io as for as_vocoder_forward_cap; the outputs are those of that call.  Rounds are
+ *                        independent but for round 0's duties: in pieces on one stream they give the bits of one call.  A round past every
+ *                        utterance's end stores nothing.  Capturable like as_vocoder_forward_cap.
+ * AS_EINVAL: core < 1, halo < -1, round0 < 0, n_rounds < 0, hop (core + 2 halo) > AS_META_MAX_W, both outputs NULL and
+ * as_vocoder_forward_cap's own conditions but one: no utterance is laid out whole, so an utterance may be longer than AS_META_MAX_W
+ * samples (hop cap < 2^31 is the limit); AS_ENOSPC before anything is launched; AS_EDEVICE while a status bit is set. */
+typedef struct as_window_cfg { int32_t core, halo, hop; } as_window_cfg;
+int as_vocoder_halo_cfg(const as_vocoder_cfg* cfg);
+int as_vocoder_halo(const as_vocoder* v);
+int as_window_host(const as_window_cfg* w, const int32_t* off_host, int B, int mult, int cap, int max_len, int round, int32_t* woff,
+                   int32_t* skip, int32_t* count, int32_t* n_rounds, int32_t* over);
+int as_window_gather_f32(const as_window_cfg* w, int round, const float* mel, int ld_mel, int num_mels, const int32_t* off, int B, int mult,
+                         int cap, int max_len, float* wmel, int ld_w, int32_t* woff, int32_t* skip_count, as_stream_t stream);
+int as_window_stitch_f32(const as_window_cfg* w, int round, const float* wwav, int ld_w, const int32_t* woff, const int32_t* off, int B,
+                         int mult, int cap, int max_len, float* wav, int16_t* pcm, int32_t* sample_off, as_stream_t stream);
+size_t as_vocoder_windowed_workspace_bytes(const as_vocoder* v, as_plan* p, int B, const as_window_cfg* w);
+int as_vocoder_forward_windowed(const as_vocoder* v, as_plan* p, int B, const as_vocoder_cap* cap, const as_vocoder_io* io,
+                                const as_window_cfg* w, int round0, int n_rounds, void* ws, size_t ws_bytes, as_stream_t stream);
 /* Host helper (no GPU work): ConvTranspose1d weight wt [Cin][Cout][2u] (stride u, padding u/2 + u%2) -> the 3-tap conv
  * wc [u*Cout][Cin][3] whose output rows are (phase r, channel m), row r Cout + m:
  *     y[m][u q + r] = sum_c sum_d wc[r Cout + m][c][d] x[c][q + d - 1]
