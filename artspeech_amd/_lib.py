@@ -314,6 +314,35 @@ _SIGNATURES.update({
 })
 
 
+class MasterCfg(ctypes.Structure):
+    """as_master_cfg (include/artspeech_hip.h): the mastering stage's rule in linear values and samples"""
+    _fields_ = [("rate", ctypes.c_int32), ("target_power", ctypes.c_float), ("abs_gate", ctypes.c_float), ("max_gain", ctypes.c_float),
+                ("ceiling", ctypes.c_float), ("lookahead", ctypes.c_int32)]
+
+
+class MasterReport(ctypes.Structure):
+    """as_master_report"""
+    _fields_ = [("power", ctypes.c_float), ("gain", ctypes.c_float), ("peak", ctypes.c_float), ("floor", ctypes.c_float),
+                ("blocks", ctypes.c_int32), ("gated", ctypes.c_int32)]
+
+
+class MasterIO(ctypes.Structure):
+    """as_master_io: DEVICE pointers (as_master_host: host pointers)"""
+    _fields_ = [("in_off", c_p), ("in_cap", ctypes.c_int32), ("x", c_p), ("y", c_p), ("pcm", c_p), ("report", c_p)]
+
+
+_pMaC, _pMaIO = ctypes.POINTER(MasterCfg), ctypes.POINTER(MasterIO)
+_SIGNATURES.update({
+    "as_master_design_host": (c_i, [c_i, c_p, c_p, c_p, c_p]),
+    "as_master_create": (c_i, [_pMaC, ctypes.POINTER(c_p)]),
+    "as_master_destroy": (c_i, [c_p]),
+    "as_master_workspace_bytes": (c_sz, [c_i, c_i, _pMaC]),
+    "as_master_f32": (c_i, [c_p, c_i, _pMaIO, c_p, c_sz, c_p]),
+    "as_master_measure_f32": (c_i, [c_p, c_i, _pMaIO, c_p, c_sz, c_p]),
+    "as_master_host": (c_i, [_pMaC, c_i, _pMaIO]),
+})
+
+
 class MarksCfg(ctypes.Structure):
     """as_marks_cfg (include/artspeech_hip.h): the chain behind the acoustic model and the animation clock, as the speech marks' rule takes them"""
     _fields_ = [("hop", ctypes.c_int32), ("L", ctypes.c_int32), ("M", ctypes.c_int32), ("rate", ctypes.c_int32), ("fps_num", ctypes.c_int32),

@@ -120,6 +120,11 @@ def build_parser():
                     "(default 40); implies --paragraph")
     ap.add_argument("--level-db", type=float, metavar="DB", help="bring every sentence to this RMS, in dB re full scale (default: no levelling); "
                     "implies --paragraph")
+    ap.add_argument("--lufs", type=float, metavar="L", help="bring --out to this programme loudness (ITU-R BS.1770 integrated loudness, e.g. -16, "
+                    "-19 or -23) on the device (as_master_f32), then hold it under --true-peak-db (default -1)")
+    ap.add_argument("--true-peak-db", type=float, metavar="D", help="hold the 4x oversampled peak of --out under D dB re full scale with a look-ahead "
+                    "limiter (default with --lufs: -1; alone: the limiter without a loudness gain)")
+    ap.add_argument("--lookahead-ms", type=float, metavar="T", help="how far ahead of a peak the limiter's gain starts to fall (default 2)")
     ap.add_argument("--trim-ref-db", type=float, metavar="DB", help="with --ref-wav: trim the reference wave on the device by the same block rule "
                     "before the mel front end (test.py:101 trims with librosa at 30 dB; this is the library's own rule, not librosa's)")
     ap.add_argument("--marks", metavar="PATH", help="also write the speech marks -- when every sentence, word and token is spoken in --out -- as "
@@ -168,6 +173,17 @@ def parse_args(argv=None):
             ap.error(f"--{name.replace('_', '-')} takes a positive number of decibels below the loudest block")
     if a.trim_ref_db is not None and not a.ref_wav:
         ap.error("--trim-ref-db needs --ref-wav")
+    if a.lufs is not None and not (math.isfinite(a.lufs) and a.lufs <= 0):
+        ap.error("--lufs takes a loudness of 0 LUFS or below")
+    if a.true_peak_db is not None and not (math.isfinite(a.true_peak_db) and a.true_peak_db <= 0):
+        ap.error("--true-peak-db takes a ceiling of 0 dB re full scale or below")
+    if a.lookahead_ms is not None and not (math.isfinite(a.lookahead_ms) and a.lookahead_ms >= 0):
+        ap.error("--lookahead-ms takes 0 ms or more")
+    a.with_master = a.lufs is not None or a.true_peak_db is not None
+    if a.lookahead_ms is not None and not a.with_master:
+        ap.error("--lookahead-ms needs --lufs or --true-peak-db")
+    if a.with_master and (a.stream or a.like_wav):
+        ap.error("--lufs and --true-peak-db measure the whole output: not with --stream or --like-wav")
     a.paragraph = a.paragraph or a.pause_ms is not None or a.trim_db is not None or a.level_db is not None
     if a.paragraph and a.emphasis:
         ap.error("--emphasis counts the tokens of one utterance: not with --paragraph")
@@ -260,6 +276,27 @@ def joiner_of(a, rate):
         return None
     kw = {k: v for k, v in (("pause_ms", a.pause_ms), ("trim_db", a.trim_db), ("level_db", a.level_db)) if v is not None}
     return Joiner(rate, **kw)
+
+
+def master_of(a, rate):
+    """the master.Master of the parsed arguments at the output's rate, or None when neither --lufs nor --true-peak-db is given"""
+    from .master import Master
+    if not a.with_master:
+        return None
+    kw = {} if a.lookahead_ms is None else {"lookahead_ms": a.lookahead_ms}
+    return Master(rate, lufs=a.lufs, true_peak_db=-1.0 if a.true_peak_db is None else a.true_peak_db, **kw)
+
+
+def print_master(a, tts):
+    """one line per stream from the stage's report: the loudness that was measured, the gain, the true peak in front of the limiter and
+    the deepest reduction"""
+    rep = tts.last_master_report
+    if rep is None:
+        return
+    measured = rep.lufs if a.lufs is not None else [None] * len(rep.gain_db)
+    for m, g, p, f in zip(measured, rep.gain_db, rep.true_peak_db, rep.reduction_db):
+        was = "loudness not measured" if m is None else f"measured {m:.2f} LUFS"
+        print(f"{a.out}: {was}, gain {g:+.2f} dB, true peak {p:.2f} dB in front of the limiter, deepest reduction {f:.2f} dB")
 
 
 def marker_of(a, rate, resampler, hop=300):
@@ -407,13 +444,14 @@ def main(argv=None):
     if a.paragraph:
         audio, piece, *sm = tts.synthesis_paragraph(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, joiner=joiner_of(a, a.out_rate),
                                                     pcm16=a.pcm16, frame_cap=a.frame_cap, sample_rate=a.out_rate, marks=marker_for(a, tts),
-                                                    window=a.window)
+                                                    window=a.window, master=master_of(a, a.out_rate))
         if sm:
             write_marks(a, sm[0])
         write_wav(a.out, audio.numpy(), sr=a.out_rate)
         print(f"{a.out}: {audio.numel()} samples, {audio.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {piece.shape[0]} sentences")
         for b, (o0, o1, s0, s1) in enumerate(piece.tolist()):
             print(f"  sentence {b}: {o0 / float(a.out_rate):.3f} s .. {o1 / float(a.out_rate):.3f} s (its samples {s0} .. {s1})")
+        print_master(a, tts)
         return 0
     if a.like_wav:
         like, like_rate = read_wav_any(a.like_wav)
@@ -423,19 +461,20 @@ def main(argv=None):
               f"{int(info['misses'].sum())} token(s) kept their own duration")
     elif a.voice:
         audio = tts.synthesis_wav(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
-                                  sample_rate=a.out_rate, marks=marker_for(a, tts), window=a.window, **tok)
+                                  sample_rate=a.out_rate, marks=marker_for(a, tts), window=a.window, master=master_of(a, a.out_rate), **tok)
     else:
         if a.save_voice:
             voice_of(a, tts)                                           # (written; the synthesis below starts from the wave itself)
         wave_in, ref_rate = read_wav_any(a.ref_wav)
         audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, ref_rate=ref_rate,
                                         sample_rate=a.out_rate, trim_db=a.trim_ref_db,
-                                        marks=marker_for(a, tts), window=a.window, **tok)
+                                        marks=marker_for(a, tts), window=a.window, master=master_of(a, a.out_rate), **tok)
     if a.with_marks:
         audio, sm = audio
         write_marks(a, sm)
     write_wav(a.out, audio.cpu().numpy(), sr=a.out_rate)
     print(f"{a.out}: {audio.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {tts._last_frames[0]} mel frames")
+    print_master(a, tts)
     return 0
 
 

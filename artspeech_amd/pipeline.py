@@ -225,6 +225,7 @@ class ArtSpeech:
         self.textcleaner = TextCleaner()
         self.device = dev
         self.generator = None                       # test.py:119-125: the HiFi-GAN generator (attach_vocoder)
+        self.last_master_report = None              # the master.Report of the last call with master= (`_back_end`), on the device
         self._record(None, None)
 
     def attach_pitch_extractor(self, checkpoint=None):
@@ -400,8 +401,8 @@ class ArtSpeech:
         return res
 
     def _back_end(self, inputs, res, frame_cap=None, max_len=None, pcm16=False, rs=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marker=None, window=None):
-        """generator -> [resampler rs] -> [joiner join] -> [marks] behind `_forward`'s result, on the current stream; between the stages
+                  marker=None, window=None, master=None):
+        """generator -> [resampler rs] -> [joiner join] -> [master] -> [marks] behind `_forward`'s result, on the current stream; between the stages
         travel packed fp32 samples and a device offset table [B + 1].  Two regimes: frame_cap None -- the host knows the frame counts
         (res["frames2"]) and every stage gets exactly the room its samples need; frame_cap=N -- only the device knows them (res["frame_off"]),
         the generator writes 300 * 2 N samples and the resampler gets out_len(that) + B; no host value is read and, with groups and gaps
@@ -410,12 +411,16 @@ class ArtSpeech:
         window=frames (a runtime vocoder) makes the generator's windowed call (Generator.forward_packed_windowed: rounds of `window` mel
         frames per utterance, a workspace that does not grow with the capacity) take the place of the one-piece call -- the stages behind
         it see the same offsets and, within the generator's bound, the same samples; window=None issues exactly the launches of before.
+        master (a master.Master at the rate of the samples it receives): the loudness gain and the true-peak limiter (as_master_f32) behind
+        the joiner -- or behind the resampler or the generator when those are absent -- on the offsets the chain already has, which it
+        leaves as they are: the marker sees the same offsets.  When present it is the last stage of samples and it alone writes the int16
+        of pcm16; its master.Report (on the device) is kept as self.last_master_report.  master=None issues exactly the launches of before.
         -> (samples fp32 or int16, off [B + 1] -- behind a joiner out_off [G + 1] --, piece [B][4] or None, Marker.forward_packed's dict or
         None), all on the device."""
         from .models import layout
         gen, dev = self.generator, torch.device(self.device)
         B = res["frame_off"].numel() - 1
-        last = "join" if join is not None else "rs" if rs is not None else "gen"
+        last = "master" if master is not None else "join" if join is not None else "rs" if rs is not None else "gen"
         with torch.cuda.device(self.device):
             p = pcm16 and last == "gen"
             if window is not None and not gen.runtime:
@@ -452,7 +457,11 @@ class ArtSpeech:
                     if torch.is_tensor(gaps):
                         raise ValueError("gaps on the device: name join_cap, the samples of room for the joined streams")
                     join_cap = join.out_cap(x.numel(), B, G, None if gaps is None else max(max(int(v) for v in gaps), 0))
-                y, p16, off, piece, _ = join.forward_packed(x, off, join_cap, groups=groups, gaps=gaps, pcm=pcm16, wav=not pcm16)
+                p = pcm16 and last == "join"
+                y, p16, off, piece, _ = join.forward_packed(x, off, join_cap, groups=groups, gaps=gaps, pcm=p, wav=not p)
+                out = x = p16 if p else y
+            if master is not None:
+                y, p16, self.last_master_report = master.forward_packed(x, off, pcm=pcm16, wav=not pcm16)
                 out = p16 if pcm16 else y
             m = None
             if marker is not None:
@@ -466,7 +475,7 @@ class ArtSpeech:
         return out, off, piece, m
 
     def _chain(self, inputs, frame_cap, pcm16, sample_rate, marker, **stages):
-        """tokens -> samples: `_forward` then `_back_end` (stages: its max_len / join / groups / gaps / join_cap), in either regime.
+        """tokens -> samples: `_forward` then `_back_end` (stages: its max_len / join / groups / gaps / join_cap / master), in either regime.
         frame_cap None: the frame counts are read back between the two (the one host read; the result has everything `aux` has);
         frame_cap=N: no host value is read, and every call with the same inputs dict reuses the acoustic model's output tensors
         (inputs["_out"]).  -> (res, samples, off, piece, marks)"""
@@ -481,7 +490,7 @@ class ArtSpeech:
                                            **stages)
 
     def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marks=None, window=None):
+                  marks=None, window=None, master=None):
         """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
         then the capacity vocoder on its frame_off and mel (`_chain`).  `inputs` = packed_inputs(...).  Every call with the same inputs dict
         reuses the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
@@ -501,11 +510,16 @@ class ArtSpeech:
         window (mel frames; None: the one-piece generator, exactly the launches of before): the generator runs in rounds of `window` frames
         per utterance (`_back_end`): same offsets, same samples within its bound, and its workspace no longer grows with frame_cap.  The
         call issues ceil(max_len / window) rounds -- max_len None: ceil(2 frame_cap / window), most of them past every utterance's end --,
-        so name max_len, the mel frames the longest utterance may have, with it."""
+        so name max_len, the mel frames the longest utterance may have, with it.
+        master (a master.Master at the rate of the samples): the last stage of samples (`_back_end`) -- every stream of the result brought
+        to its loudness target and held under its true-peak ceiling, at the same offsets; the chain stays capturable, and the stage's
+        Report is self.last_master_report (a device tensor: reading it synchronises).  master=None issues exactly the launches of before."""
         if join is not None:
             self._check_joiner(join, sample_rate)
+        if master is not None:
+            self._check_master(master, sample_rate)
         _, out, off, piece, m = self._chain(inputs, frame_cap, pcm16, sample_rate, self._marker(marks, sample_rate), max_len=max_len, join=join,
-                                            groups=groups, gaps=gaps, join_cap=join_cap, window=window)
+                                            groups=groups, gaps=gaps, join_cap=join_cap, window=window, master=master)
         ret = (out, off) if join is None else (out, off, piece)
         return ret if m is None else ret + (m,)
 
@@ -598,6 +612,11 @@ class ArtSpeech:
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if join.rate != rate:
             raise ValueError(f"the joiner counts its milliseconds at {join.rate} Hz, the samples it is given are at {rate} Hz")
+
+    def _check_master(self, master, sample_rate):
+        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        if master.rate != rate:
+            raise ValueError(f"the master's filters are designed for {master.rate} Hz, the samples it is given are at {rate} Hz")
 
     def _hop(self):
         """samples per mel frame of the attached generator: the product of its up-sampling rates (300)"""
@@ -699,7 +718,7 @@ class ArtSpeech:
     @torch.no_grad()
     def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
                       frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False, fit=None, window=None,
-                      max_len=None):
+                      max_len=None, master=None):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the chain's last kernel.
@@ -716,17 +735,21 @@ class ArtSpeech:
         fit: a Fit (fit.py) -- Fit.whole(s) gives every utterance rint(40 s) * 600 samples at 24 kHz, spans give their tokens an exact time.
         window (mel frames, a runtime vocoder): the generator in rounds of that many frames per utterance (`_back_end`).
         max_len (with frame_cap): the mel frames the longest utterance may have (None: 2 frame_cap) -- it sizes the generator's grids and,
-        with window, is what the number of rounds is taken from: ceil(max_len / window); a longer utterance raises AS_STATUS_CAPACITY."""
+        with window, is what the number of rounds is taken from: ceil(max_len / window); a longer utterance raises AS_STATUS_CAPACITY.
+        master (a master.Master at the output's rate): every utterance brought to its loudness target in LUFS and held under its
+        true-peak ceiling on the device, as the chain's last stage (`_back_end`); its report is self.last_master_report."""
         single, phonemes, ref_mel, features, token_prosody = self._lists(phonemes, ref_mel, features, token_prosody)
         req = dict(ref_mel=ref_mel, features=features, voice=voice, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth,
                    fit=fit, forced_durations=forced_durations)
-        return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len)
+        return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len, master=master)
 
-    def _wav(self, single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=None, max_len=None):
+    def _wav(self, single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=None, max_len=None, master=None):
         """synthesis_wav on lists: req = packed_inputs' keyword arguments"""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         rs, marker = self._out_resampler(sample_rate), self._marker(marks, sample_rate)
+        if master is not None:
+            self._check_master(master, sample_rate)
         if frame_cap is not None:
             frame_cap = int(frame_cap)
             if req["forced_durations"] is not None:
@@ -734,7 +757,7 @@ class ArtSpeech:
         if max_len is not None and frame_cap is None:
             raise ValueError("max_len goes with frame_cap (without it the frame counts are read back and every stage is sized by them)")
         res, out, off, _, m = self._chain(self.packed_inputs(phonemes, **req), frame_cap, pcm16, sample_rate, marker, window=window,
-                                          max_len=max_len)
+                                          max_len=max_len, master=master)
         hop = self._hop()
         with torch.cuda.device(self.device):
             if frame_cap is None:
@@ -754,19 +777,21 @@ class ArtSpeech:
     @torch.no_grad()
     def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
                             token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False, fit=None, window=None,
-                            max_len=None):
+                            max_len=None, master=None):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
         attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
         device, with the library's own filter); sample_rate: the rate of the returned samples (synthesis_wav).  Loading / trimming the
         file and espeak stay with the caller.  trim_db (None: the wave as it came): the silent ends of ref_wave are cut on the device
         before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity).  fit, window,
-        max_len: as synthesis_wav takes them."""
+        max_len, master: as synthesis_wav takes them."""
         single, phonemes, waves, features, token_prosody = self._lists(phonemes, ref_wave, features, token_prosody)
         req = dict(ref_mel=self._wave_mels(waves, ref_rate, trim_db), features=features, voice=None, prosody=prosody,
                    token_prosody=token_prosody, token_smooth=token_smooth, fit=fit, forced_durations=forced_durations)
         if self.generator is not None:
-            return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len)
+            return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len, master=master)
+        if master is not None:
+            raise RuntimeError("master works on samples: attach_vocoder(h, checkpoint) first")
         if frame_cap is not None:
             raise RuntimeError("frame_cap runs the acoustic model and the generator as one chain: attach_vocoder(h, checkpoint, runtime=True) first")
         if marks is not None and marks is not False:
@@ -775,7 +800,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_paragraph(self, sentences, ref_mel=None, voice=None, prosody=None, pause_ms=None, joiner=None, sample_rate=None, pcm16=False,
-                            frame_cap=None, features=None, max_tokens=None, marks=False, fit=None, window=None, max_len=None):
+                            frame_cap=None, features=None, max_tokens=None, marks=False, fit=None, window=None, max_len=None, master=None):
         """A paragraph as ONE stream: `sentences` is a list of phoneme strings, or one string that text.split_sentences cuts (max_tokens:
         its limit per piece).  The sentences run as one batch through the chain above (the acoustic model and the generator, with frame_cap
         with no read-back in between; the resampler when sample_rate is given), then through join.Joiner on the device -- every sentence
@@ -791,7 +816,10 @@ class ArtSpeech:
         fit: a Fit whose utterances are the sentences -- Fit.whole([2.0, 3.5, None]) gives every sentence its slot (subtitles) on the
         vocoder's clock, before the joiner trims and spaces them.
         window (mel frames, a runtime vocoder): the generator in rounds of that many frames per sentence (`_back_end`); max_len (with
-        frame_cap): the mel frames the longest sentence may have, as synthesis_wav takes it."""
+        frame_cap): the mel frames the longest sentence may have, as synthesis_wav takes it.
+        master (a master.Master at the output's rate): the joined stream brought to its loudness target in LUFS (integrated over the
+        whole stream, pauses gated out) and held under its true-peak ceiling, behind the joiner on the device; no length changes, so
+        piece and the marks hold as they are.  Its report is self.last_master_report."""
         from .join import Joiner
         from .text import PAUSE_SCALE, split_sentences
         if self.generator is None:
@@ -800,6 +828,8 @@ class ArtSpeech:
         if joiner is None:
             joiner = Joiner(rate, device=self.device, **({} if pause_ms is None else {"pause_ms": pause_ms}))
         self._check_joiner(joiner, sample_rate)
+        if master is not None:
+            self._check_master(master, sample_rate)
         pause = joiner.cfg.gap if pause_ms is None else joiner.samples(pause_ms)
         if isinstance(sentences, str):
             sentences, classes = split_sentences(sentences, max_tokens)
@@ -815,7 +845,7 @@ class ArtSpeech:
         marker = self._marker(marks, sample_rate)
         inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody, fit=fit)
         res, stream, out_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, sample_rate, marker,
-                                                     join=joiner, gaps=gaps, window=window,
+                                                     join=joiner, gaps=gaps, window=window, master=master,
                                                      **({} if frame_cap is None else {"max_len": max_len}))
         with torch.cuda.device(self.device):
             _, stream = self._read_back(stream, out_off, "synthesis_paragraph")     # the one synchronisation: the length, then the stream
@@ -834,7 +864,8 @@ class ArtSpeech:
         utterance has frames; the chunks of an utterance, concatenated, are its synthesis_wav(window=) samples bit for bit.
         `rounds_launched` counts the vocoder rounds issued so far; it lives on this object and every call sets it to 0, so two streams of
         one ArtSpeech that are consumed in turns share it: it is a figure for one stream at a time.  24 kHz generator output only:
-        sample_rate, a joiner or marks raise ValueError (a streaming resampler and joiner need state of their own)."""
+        sample_rate, a joiner or marks raise ValueError (a streaming resampler and joiner need state of their own).  There is no master=
+        either: integrated loudness is a figure of the whole stream, which does not exist while its first rounds leave."""
         if sample_rate not in (None, SAMPLE_RATE) or joiner is not None or (marks is not None and marks is not False):
             raise ValueError("synthesis_stream hands out the generator's own 24 kHz samples: no sample_rate, joiner or marks")
         if self.generator is None or not self.generator.runtime:

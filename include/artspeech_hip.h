@@ -1078,6 +1078,77 @@ int as_join_f32(const as_join_cfg* cfg, int B, const as_join_io* io, void* ws, s
 int as_join_measure_f32(const as_join_cfg* cfg, int B, const as_join_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
 int as_join_host(const as_join_cfg* cfg, int B, const as_join_io* io);
 
+/* ---- mastering: programme loudness and a true-peak limiter (csrc/master.hip; the rule: csrc/master_rule.h) --------
+ * The last stage of the sample back end: G packed streams are brought to a programme loudness (ITU-R BS.1770: K-weighted, gated) and held
+ * under a true-peak ceiling by a look-ahead limiter.  No length changes: offsets, pieces and speech marks stay valid as they are.
+ * The rule, per stream x[0 .. n) at cfg->rate Hz (zeros beyond its ends, never a neighbour's samples).  K-weighting: the shelf and the
+ * high pass of BS.1770 designed in double for the rate by the bilinear transform (at 48 kHz the standard's table), rounded once to fp32,
+ * each in transposed direct form II.  The recurrence is cut into chunks of P = 512 samples from the stream's OWN first sample: every chunk
+ * filtered from the zero state gives its final state f_j; S_0 = 0, S_{j+1} = T S_j + f_j with T the P-step transition matrix (double,
+ * rounded once); every chunk is filtered again from S_j.  hop = rate / 10; e_i = the sum of squares of the filter's output over hop i;
+ * block i = hops i .. i + 3, z_i = (e_i + .. + e_{i+3}) / (4 hop), complete blocks only; a stream shorter than one block has ONE block,
+ * z = sum / n.  Gates: z_i > abs_gate (10^((-70 + 0.691) / 10)), then z_i > 0.1 x the mean of the absolutely gated z; power = the mean of
+ * the z that pass both (0: none passes the absolute gate); the loudness is -0.691 + 10 log10(power) LUFS (computed by the caller: the rule
+ * has no logarithm).  Gain: g = min(sqrt(target_power / power), max_gain), 1 when power == 0 or target_power == 0 (loudness off;
+ * target_power = 10^((LUFS + 0.691) / 10)).  True peak: the resampler's own prototype for L = 4, M = 1 (64 taps per phase),
+ * p[n] = max(|g x[n]|, |g d_j[n]|, j = 0..3), d_j = phase j at sample n.  Limiter (ceiling > 0; A = lookahead samples, 1..512):
+ * r[n] = min(1, ceiling / p[n]), 1 outside the stream; c[k] = min r[k .. k + A]; s[n] = (c[n - A] + .. + c[n]) / (A + 1);
+ * y[n] = (g x[n]) s[n].  Hence |y[n]| <= ceiling (1 + 2^-14); y = g x bit for bit where nothing within +-A samples is over the ceiling; no
+ * delay; the gain is not raised again behind the limiter, so the loudness of a limited stream may sit a little under the target, and the
+ * TRUE peak of y may pass the ceiling by a few hundredths of a dB.  Every order of operations is fixed by master_rule.h: a
+ * stream in a batch gives the bits of the same stream alone, and the device gives the bits of as_master_host.  Loudness and ceiling off:
+ * the output is the input bit for bit.  An empty stream writes nothing; its report is power 0, gain 1, peak 0, floor 1.
+ * as_master_io: in_off DEVICE int32 [G + 1] (in_off[0] = 0; an as_join_f32 or as_resample_f32 out_off, an as_vocoder_cap.sample_off, or
+ * prefix sums), x DEVICE [in_cap]; outputs, each in_cap samples at the offsets of the input: y fp32 and / or pcm (as_conv_post_pcm_f32's
+ * rule on the fp32 value: a NaN stores 0 and raises AS_STATUS_F16_RANGE), samples in [in_off[G], in_cap) are 0; report DEVICE [G]
+ * (optional for as_master_f32): power, gain, peak = max p[n], floor = min s[n], blocks, gated = the blocks that passed both gates.
+ * as_master_design_host   no GPU: the ten coefficients in double (b0 b1 b2 a1 a2 of the shelf, then of the high pass), T [4][4] as the
+ *                         kernels use it (the P-th power, in double, of the one-step state matrix of the fp32 coefficients, rounded
+ *                         once), P and hop; each pointer may be NULL.
+ * as_master_create        validates the cfg and designs the filters and the oversampler's phase table on the host.  The handle is
+ *                         immutable and holds no device memory (the tables travel as kernel arguments): any number of calls, streams,
+ *                         threads and devices may share it, and it is created without a GPU.
+ * as_master_f32           at most five launches sized by in_cap (filter, carry, refilter with hop energies, gates with gain and report,
+ *                         limiter with the stores); loudness off: the report's initialisation and the limiter.  Nothing is read back,
+ *                         uploaded or allocated and no call synchronises: every call, the first included, can be captured into a hipGraph
+ *                         and replayed with other offsets and samples.  in_off[G] > in_cap: AS_STATUS_CAPACITY (the layout is cut there,
+ *                         nothing is read or stored out of bounds).  With loudness off the report's power, blocks and gated are 0.
+ *                         y == x is refused (AS_EINVAL): a tile's halo lies in its neighbours' outputs, and a second launch is not spent
+ *                         on it.
+ * as_master_measure_f32   the meter: the report only -- the loudness whatever target_power says, gain = what WOULD be applied, peak = the
+ *                         true peak of g x, floor 1; y and pcm are not read.
+ * as_master_host          the same rule on HOST arrays (every pointer of io is a host pointer; no GPU, no workspace): io->y or io->pcm
+ *                         given: the stage (y == x is allowed here); neither: the meter.  AS_EDEVICE: a NaN went to pcm; AS_EINVAL also for
+ *                         offsets that do not ascend from 0 to <= in_cap.
+ * AS_EINVAL before anything is launched: m, io, ws, in_off or x NULL, both outputs NULL (measure: report NULL), G outside [1, 65535], in_cap
+ * outside [1, 2^30]; from as_master_create and as_master_host: rate outside [8000, 192000], lookahead outside [1, 512] with ceiling > 0, a
+ * negative or non-finite float.  AS_ENOSPC: ws_bytes below as_master_workspace_bytes(G, in_cap, cfg) (0 for arguments it refuses).
+ * AS_EDEVICE while a status bit is set. */
+typedef struct as_master_cfg {
+    int32_t rate;                  /* samples per second of the streams */
+    float target_power, abs_gate, max_gain;   /* linear; target_power 0: loudness off */
+    float ceiling;                 /* linear; 0: limiter off */
+    int32_t lookahead;             /* samples */
+} as_master_cfg;
+typedef struct as_master_report {
+    float power, gain, peak, floor;
+    int32_t blocks, gated;
+} as_master_report;
+typedef struct as_master_io {
+    const int32_t* in_off; int32_t in_cap;
+    const float* x;
+    float* y; int16_t* pcm;
+    as_master_report* report;
+} as_master_io;
+typedef struct as_master as_master;
+int as_master_design_host(int rate, double* biquads10, float* carry16, int32_t* P, int32_t* hop);
+int as_master_create(const as_master_cfg* cfg, as_master** out);
+int as_master_destroy(as_master* m);
+size_t as_master_workspace_bytes(int G, int in_cap, const as_master_cfg* cfg);
+int as_master_f32(const as_master* m, int G, const as_master_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_master_measure_f32(const as_master* m, int G, const as_master_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_master_host(const as_master_cfg* cfg, int G, const as_master_io* io);
+
 /* ---- speech marks (csrc/marks.hip; the rule: csrc/marks_rule.h) ---------------------------------------------------
  * When every token is spoken in the samples the caller receives, and the twelve tracks the predictors hand the decoder (F0, N, EMA 0..9)
  * retimed onto an animation clock of fps_num / fps_den frames per second of those samples -- behind the duration rounding, the hop, the
