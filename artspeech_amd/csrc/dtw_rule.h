@@ -32,28 +32,20 @@
 #include <cstdint>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define DTW_HD __host__ __device__
-#else
-#define DTW_HD
-#endif
+#include "rule_math.h"
 
 namespace dtw_rule {
+
+using rule_math::add;           // one rounding each, on either side
+using rule_math::div;
+using rule_math::finite;
+using rule_math::mul;
 
 constexpr int MAX_C = 128, MAX_T = 4096, MAX_DUR = 16384;
 constexpr int DIAG = 0, UP = 1, LEFT = 2;                     // the predecessor: (i-1, j-1), (i-1, j), (i, j-1)
 constexpr int TRACKS = 12, ROW_DIM = 25, ROW_DUR = 0, ROW_GAIN = 1, ROW_OFFSET = 13, N_STRENGTH = 13;      // AS_PROSODY_*; strength: timing, then the tracks
 
-// one rounding each, on either side
-DTW_HD inline float add(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fadd_rn(a, b);
-#else
-    return a + b;
-#endif
-}
-DTW_HD inline float sub(float a, float b)
+RULE_HD inline float sub(float a, float b)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __fsub_rn(a, b);
@@ -61,31 +53,14 @@ DTW_HD inline float sub(float a, float b)
     return a - b;
 #endif
 }
-DTW_HD inline float mul(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fmul_rn(a, b);
-#else
-    return a * b;
-#endif
-}
-DTW_HD inline float div(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fdiv_rn(a, b);
-#else
-    return a / b;
-#endif
-}
-DTW_HD inline bool finite(float x) { return fabsf(x) <= FLT_MAX; }
-DTW_HD inline float inf() { return HUGE_VALF; }
+RULE_HD inline float inf() { return HUGE_VALF; }
 
 // ---- spans -------------------------------------------------------------------------------------------------------------------------
 struct Span {
     int32_t start, len;
     bool over;                     // cut at the leading dimension or at the capacity
 };
-DTW_HD inline Span span(int32_t off0, int32_t off1, int mult, int ld, int cap)
+RULE_HD inline Span span(int32_t off0, int32_t off1, int mult, int ld, int cap)
 {
     long long s = (long long)off0 * mult, e = (long long)off1 * mult;
     bool over = false;
@@ -106,7 +81,7 @@ DTW_HD inline Span span(int32_t off0, int32_t off1, int mult, int ld, int cap)
 
 // ---- cost --------------------------------------------------------------------------------------------------------------------------
 // the fp32 sum of x[0 .. n) at stride 1 in ascending order, divided by fp32(n); 0 for n < 1
-DTW_HD inline float mean(const float* x, int n)
+RULE_HD inline float mean(const float* x, int n)
 {
     if (n < 1) return 0.f;
     float acc = 0.f;
@@ -114,14 +89,14 @@ DTW_HD inline float mean(const float* x, int n)
     return div(acc, (float)n);
 }
 // what a frame's bin contributes: the value, or the value less its side's mean
-DTW_HD inline float centred(float v, float m) { return sub(v, m); }
-DTW_HD inline float cost_acc(float a, float b, float acc)
+RULE_HD inline float centred(float v, float m) { return sub(v, m); }
+RULE_HD inline float cost_acc(float a, float b, float acc)
 {
     const float d = sub(a, b);
     return fmaf(d, d, acc);
 }
 // c(i, j) from the two packed sides (a_i, b_j: the frames' first bins; lda, ldb: the stride between bins); ma / mb NULL: not centred
-DTW_HD inline float cost(const float* a_i, size_t lda, const float* b_j, size_t ldb, int C, const float* ma, const float* mb)
+RULE_HD inline float cost(const float* a_i, size_t lda, const float* b_j, size_t ldb, int C, const float* ma, const float* mb)
 {
     float acc = 0.f;
     for (int k = 0; k < C; ++k) {
@@ -136,7 +111,7 @@ struct Step {
     float d;
     int code;
 };
-DTW_HD inline Step step(float c, float diag, float up, float left)
+RULE_HD inline Step step(float c, float diag, float up, float left)
 {
     float m = diag;
     int code = DIAG;
@@ -150,14 +125,14 @@ DTW_HD inline Step step(float c, float diag, float up, float left)
     }
     return Step{add(c, m), code};
 }
-DTW_HD inline Step origin(float c) { return Step{c, DIAG}; }
+RULE_HD inline Step origin(float c) { return Step{c, DIAG}; }
 // the decision the walk follows at (i, j): never out of the lattice (a lattice of NaNs, decision words that were never written)
-DTW_HD inline int guard(int code, int i, int j) { return i <= 0 ? LEFT : j <= 0 ? UP : code > LEFT ? DIAG : code; }
+RULE_HD inline int guard(int code, int i, int j) { return i <= 0 ? LEFT : j <= 0 ? UP : code > LEFT ? DIAG : code; }
 
 // decisions are kept 2 bits per cell, 16 columns of a row per 32-bit word
 constexpr int CELLS_PER_WORD = 16;
-DTW_HD inline int words_per_row(int Ty) { return (Ty + CELLS_PER_WORD - 1) / CELLS_PER_WORD; }
-DTW_HD inline int code_of(uint32_t word, int j) { return (int)((word >> (2 * (j & (CELLS_PER_WORD - 1)))) & 3u); }
+RULE_HD inline int words_per_row(int Ty) { return (Ty + CELLS_PER_WORD - 1) / CELLS_PER_WORD; }
+RULE_HD inline int code_of(uint32_t word, int j) { return (int)((word >> (2 * (j & (CELLS_PER_WORD - 1)))) & 3u); }
 
 // the whole warp of one utterance on the host; c(i, j) is asked for once per cell.  Every output may be NULL; rows gets t_y entries, cols t_x.
 template <class Cost>
@@ -194,7 +169,7 @@ inline void align(Cost c, int t_x, int t_y, int32_t* rows, int32_t* cols, float*
 
 // ---- transfer ----------------------------------------------------------------------------------------------------------------------
 // the first j in [0, n) with rows[j] >= v, else n (rows ascends over [0, n))
-DTW_HD inline int first_at_least(const int32_t* rows, int n, long long v)
+RULE_HD inline int first_at_least(const int32_t* rows, int n, long long v)
 {
     int lo = 0, hi = n;
     while (lo < hi) {
@@ -204,29 +179,29 @@ DTW_HD inline int first_at_least(const int32_t* rows, int n, long long v)
     }
     return lo;
 }
-DTW_HD inline int frames_of(int32_t dur_i) { return dur_i > 0 ? dur_i : 0; }
-DTW_HD inline int half_frames(int E) { return (E + 1) >> 1; }
-DTW_HD inline int target(int H_k, int H_before)
+RULE_HD inline int frames_of(int32_t dur_i) { return dur_i > 0 ? dur_i : 0; }
+RULE_HD inline int half_frames(int E) { return (E + 1) >> 1; }
+RULE_HD inline int target(int H_k, int H_before)
 {
     const int t = H_k - H_before;
     return t < 1 ? 1 : t > MAX_DUR ? MAX_DUR : t;
 }
 // the duration scale that makes the model's clamp(rint(duration * q), 1, 16384) come out as t; *miss: no such fp32 q was found (q = 1)
-DTW_HD inline float scale(int t, float duration, bool* miss)
+RULE_HD inline float scale(int t, float duration, bool* miss)
 {
     const float q = div((float)t, duration);
     *miss = !finite(q) || rintf(mul(duration, q)) != (float)t;
     return *miss ? 1.f : q;
 }
 // row of the recording's feat12 that holds prosody track c (F0, N, EMA0..9): the energy is row 0 there, F0 row 1
-DTW_HD inline int feat_row(int c) { return c == 0 ? 1 : c == 1 ? 0 : c; }
-DTW_HD inline float offset(float strength, const float* rec, int n_rec, const float* syn, int n_syn)
+RULE_HD inline int feat_row(int c) { return c == 0 ? 1 : c == 1 ? 0 : c; }
+RULE_HD inline float offset(float strength, const float* rec, int n_rec, const float* syn, int n_syn)
 {
     if (n_rec < 1 || n_syn < 1) return 0.f;
     return mul(strength, sub(mean(rec, n_rec), mean(syn, n_syn)));
 }
 // the synthesised columns of a token, cut at the utterance's span of n columns
-DTW_HD inline void syn_range(long long s_k, long long s_next, int n, int* lo, int* hi)
+RULE_HD inline void syn_range(long long s_k, long long s_next, int n, int* lo, int* hi)
 {
     const long long a = 2 * s_k, e = 2 * s_next;
     *lo = (int)(a < n ? a : n);

@@ -33,11 +33,7 @@
 #include <algorithm>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define DURATION_FIT_HD __host__ __device__
-#else
-#define DURATION_FIT_HD
-#endif
+#include "rule_math.h"
 
 namespace duration_fit {
 
@@ -46,27 +42,27 @@ constexpr int64_t T_MAX = (int64_t)D_MAX * MAX_COUNT;
 constexpr uint64_t KEY_INF = ~(uint64_t)0;
 static_assert((1 << IDX_BITS) == MAX_COUNT, "a key holds the token's place in its span in IDX_BITS bits");
 
-DURATION_FIT_HD inline bool finite_v(float v) { return fabsf(v) <= 3.0e38f; }
+RULE_HD inline bool finite_v(float v) { return fabsf(v) <= 3.0e38f; }
 
 // the durations kernel's rule (csrc/elementwise.hip): round half to even, clamp; *fin false: AS_STATUS_F16_RANGE
-DURATION_FIT_HD inline int32_t plain(float v, bool* fin)
+RULE_HD inline int32_t plain(float v, bool* fin)
 {
     *fin = finite_v(v);
     const float r = *fin ? rintf(v) : 1.f;
     return (int32_t)(r < 1.f ? 1.f : fminf(r, (float)D_MAX));
 }
 
-DURATION_FIT_HD inline int64_t weight(float v)
+RULE_HD inline int64_t weight(float v)
 {
     if (!finite_v(v)) v = 1.f;
     return (int64_t)llrintf(fminf(fmaxf(v, 0.00390625f), (float)D_MAX) * 65536.f);
 }
 
 // the controlled duration of a token without per-token controls: the predictor's value times its utterance's scale (pros NULL: as it is)
-DURATION_FIT_HD inline float controlled(float duration, bool has_utt, float utt_scale) { return has_utt ? duration * utt_scale : duration; }
+RULE_HD inline float controlled(float duration, bool has_utt, float utt_scale) { return has_utt ? duration * utt_scale : duration; }
 
 // the utterance of packed token i: the last b < B with tok_off[b] <= i
-DURATION_FIT_HD inline int utterance_of(const int32_t* tok_off, int B, int i)
+RULE_HD inline int utterance_of(const int32_t* tok_off, int B, int i)
 {
     int lo = 0, hi = B - 1;
     while (hi > lo) {
@@ -78,7 +74,7 @@ DURATION_FIT_HD inline int utterance_of(const int32_t* tok_off, int B, int i)
 }
 
 // span s against the tokens and the span before it (the structural conditions: one false voids the whole fit)
-DURATION_FIT_HD inline bool structure_ok(const int32_t* span_tok, int s, int64_t n_tokens)
+RULE_HD inline bool structure_ok(const int32_t* span_tok, int s, int64_t n_tokens)
 {
     const int64_t first = span_tok[2 * s], count = span_tok[2 * s + 1];
     if (first < 0 || count < 1 || first + count > n_tokens) return false;
@@ -86,7 +82,7 @@ DURATION_FIT_HD inline bool structure_ok(const int32_t* span_tok, int s, int64_t
 }
 
 // a structurally sound span that this launch can take and that lies inside one utterance
-DURATION_FIT_HD inline bool span_ok(int32_t first, int32_t count, int max_count, const int32_t* tok_off, int B)
+RULE_HD inline bool span_ok(int32_t first, int32_t count, int max_count, const int32_t* tok_off, int B)
 {
     if (count > max_count || count > MAX_COUNT) return false;
     const int b = utterance_of(tok_off, B, first);
@@ -94,18 +90,18 @@ DURATION_FIT_HD inline bool span_ok(int32_t first, int32_t count, int max_count,
 }
 
 // what the free tokens share and whether they can: n free tokens, T' frames
-DURATION_FIT_HD inline bool share_ok(int64_t n, int64_t Tp) { return n == 0 ? Tp == 0 : (Tp >= n && Tp <= T_MAX); }
+RULE_HD inline bool share_ok(int64_t n, int64_t Tp) { return n == 0 ? Tp == 0 : (Tp >= n && Tp <= T_MAX); }
 
 // sort keys: ascending (u, place in the span) for the pinned prefix; descending rem, ascending place for the bonuses
-DURATION_FIT_HD inline uint64_t key_weight(int64_t u, int j) { return ((uint64_t)u << IDX_BITS) | (uint64_t)j; }
-DURATION_FIT_HD inline uint64_t key_rem(int64_t rem, int64_t Ustar, int j) { return ((uint64_t)(Ustar - 1 - rem) << IDX_BITS) | (uint64_t)j; }
-DURATION_FIT_HD inline int key_place(uint64_t key) { return (int)(key & (MAX_COUNT - 1)); }
-DURATION_FIT_HD inline int64_t key_value(uint64_t key) { return (int64_t)(key >> IDX_BITS); }
+RULE_HD inline uint64_t key_weight(int64_t u, int j) { return ((uint64_t)u << IDX_BITS) | (uint64_t)j; }
+RULE_HD inline uint64_t key_rem(int64_t rem, int64_t Ustar, int j) { return ((uint64_t)(Ustar - 1 - rem) << IDX_BITS) | (uint64_t)j; }
+RULE_HD inline int key_place(uint64_t key) { return (int)(key & (MAX_COUNT - 1)); }
+RULE_HD inline int64_t key_value(uint64_t key) { return (int64_t)(key >> IDX_BITS); }
 
 // the k-th smallest free token (weight u_k, P_k = the weights before it) needs no pin once the k before it are pinned
-DURATION_FIT_HD inline bool unpinned(int64_t u_k, int64_t P_k, int64_t k, int64_t U, int64_t Tp) { return u_k * (Tp - k) >= U - P_k; }
+RULE_HD inline bool unpinned(int64_t u_k, int64_t P_k, int64_t k, int64_t U, int64_t Tp) { return u_k * (Tp - k) >= U - P_k; }
 
-DURATION_FIT_HD inline void quotient(int64_t u, int64_t R, int64_t Ustar, int64_t* q, int64_t* rem)
+RULE_HD inline void quotient(int64_t u, int64_t R, int64_t Ustar, int64_t* q, int64_t* rem)
 {
     const int64_t p = u * R;
     *q = p / Ustar;
@@ -113,7 +109,7 @@ DURATION_FIT_HD inline void quotient(int64_t u, int64_t R, int64_t Ustar, int64_
 }
 
 // the stretch a span received, in units of 2^-16 (a valid span's is below 2^22: d <= 16384 and u >= 2^8)
-DURATION_FIT_HD inline int32_t scale_q16(int64_t R, int64_t Ustar) { return Ustar > 0 ? (int32_t)((R << 16) / Ustar) : 0; }
+RULE_HD inline int32_t scale_q16(int64_t R, int64_t Ustar) { return Ustar > 0 ? (int32_t)((R << 16) / Ustar) : 0; }
 
 // One span, serially (host only).  v, lock, d: the span's own tokens [count]; d holds the plain durations on entry and keeps them if the
 // span is void (false).  *scale: scale_q16, or 0.

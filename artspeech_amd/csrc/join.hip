@@ -2,14 +2,14 @@
 // pauses between them, by the rule of join_rule.h.  THREE launches per call, none of which synchronises, allocates or reads back:
 //
 //   measure    the grid is ceil(in_cap / span) + B workgroups (span = a whole number of blocks, about 2048 samples; the host knows no
-//              length): every workgroup derives the utterances' block and workgroup counts from the DEVICE offsets by a block scan and finds
-//              its utterance and its run of blocks; a wave takes one block at a time -- lane l the samples 4 l .. 4 l + 3, + 256, ... as
+//              length): every workgroup finds its utterance and its run of blocks from the DEVICE offsets (packed_streams.h: find_job over
+//              the utterances' block and workgroup counts); a wave takes one block at a time -- lane l the samples 4 l .. 4 l + 3, + 256, ... as
 //              16-byte loads that need 4-byte alignment only (utterance starts are no better aligned), one fused multiply-add chain per lane
 //              and the halving tree of the rule -- and stores (ss, pk) into the block table.  A sample that is not finite raises
 //              AS_STATUS_F16_RANGE.
 //   reduce     one wave per utterance over its rows of the block table: top, the active blocks, k0, k1, A (lane = chain), C, peak, the gain
 //              and the kept range [s0, s1) go to the workspace (as_join_measure_f32 stops here and stores them as piece / gain).
-//   write      the layout-scan scheme of resample_kernel: every workgroup scans the utterances' kept lengths -- a maximum scan carries the
+//   write      find_job's scheme with a position loop of its own: every workgroup scans the utterances' kept lengths -- a maximum scan carries the
 //              stream of the last non-empty piece (it says whether a piece is the first of its stream, i.e. whether its gap counts), a sum
 //              scan the samples, the piece tiles and the zero tiles in front of each piece -- and the thread whose chunk holds workgroup
 //              w's tile publishes it.  Tiles of 2048 outputs never straddle pieces; the workgroups behind the last piece tile write the
@@ -20,6 +20,7 @@
 #include "common.h"
 #include "artspeech_hip.h"
 #include "join_rule.h"
+#include "packed_streams.h"
 #include <cstring>
 #include <vector>
 
@@ -28,6 +29,9 @@
 namespace {
 
 namespace jr = join_rule;
+namespace ps = packed_streams;
+using rule_math::round16;
+using rule_math::rule_cfg;
 
 constexpr int THREADS = 256, WAVES = THREADS / AS_WAVE, TILE = 2048, SPAN = 2048;
 constexpr int MAX_CAP = 1 << 30;                // of in_cap and out_cap: tile and block counts stay inside 32 bits
@@ -37,86 +41,20 @@ typedef short s4v __attribute__((ext_vector_type(4)));
 
 static_assert(sizeof(jr::Cfg) == sizeof(as_join_cfg) && sizeof(jr::Piece) == sizeof(as_join_piece), "join_rule.h restates the public structs");
 
-__device__ __forceinline__ int len_at(const int* in_off, int in_cap, int b, int* first)
-{
-    const int a = min(max(in_off[b], 0), in_cap), e = min(max(in_off[b + 1], 0), in_cap);
-    *first = a;
-    return max(e - a, 0);
-}
-
-// inclusive block scans over THREADS values (s: the caller's shared array)
-template <int N>
-__device__ __forceinline__ void scan_sum(long long (*s)[THREADS], int t)       // s[N][THREADS], the N scans in step
-{
-    __syncthreads();
-    for (int off = 1; off < THREADS; off <<= 1) {
-        long long v[N];
-#pragma unroll
-        for (int j = 0; j < N; ++j) v[j] = t >= off ? s[j][t - off] : 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < N; ++j) s[j][t] += v[j];
-        __syncthreads();
-    }
-}
-__device__ __forceinline__ void scan_max(int* s, int t)
-{
-    __syncthreads();
-    for (int off = 1; off < THREADS; off <<= 1) {
-        const int v = t >= off ? s[t - off] : -1;
-        __syncthreads();
-        s[t] = max(s[t], v);
-        __syncthreads();
-    }
-}
-
 __global__ void __launch_bounds__(THREADS)
 join_measure_kernel(jr::Cfg c, int nblk, int B, const int* __restrict__ in_off, int in_cap, const float* __restrict__ x, float* __restrict__ ss,
                     float* __restrict__ pk, long long nb_cap, unsigned* __restrict__ status)
 {
-    __shared__ long long s_sum[2][THREADS];
-    long long* const s_blk = s_sum[0];
-    long long* const s_wg = s_sum[1];
-    __shared__ long long s_job_blk;
-    __shared__ int s_job[3];                        // the utterance's first sample, its length, the workgroup's first block in it
-    __shared__ int s_found;
-
     const int t = threadIdx.x;
-    const long long w = blockIdx.x;
-    if (t == 0) s_found = 0;
-    const int per = (B + THREADS - 1) / THREADS, lo = min(t * per, B), hi = min(lo + per, B);
-    long long local_blk = 0, local_wg = 0;
-    for (int b = lo; b < hi; ++b) {
-        int first;
-        const int K = jr::n_blocks(len_at(in_off, in_cap, b, &first), c.frame);
-        local_blk += K;
-        local_wg += (K + nblk - 1) / nblk;
-    }
-    s_blk[t] = local_blk;
-    s_wg[t] = local_wg;
-    scan_sum<2>(s_sum, t);
-    {
-        long long bp = s_blk[t] - local_blk, wp = s_wg[t] - local_wg;
-        for (int b = lo; b < hi; ++b) {
-            int first;
-            const int n = len_at(in_off, in_cap, b, &first), K = jr::n_blocks(n, c.frame), wgs = (K + nblk - 1) / nblk;
-            if (w >= wp && w < wp + wgs) {
-                s_job_blk = bp;
-                s_job[0] = first;
-                s_job[1] = n;
-                s_job[2] = (int)(w - wp) * nblk;
-                s_found = 1;
-            }
-            bp += K;
-            wp += wgs;
-        }
-    }
-    if (w == 0 && t == 0 && (s_blk[THREADS - 1] > nb_cap || in_off[B] > in_cap)) as_status_raise(status, AS_STATUS_CAPACITY);
-    __syncthreads();
-    if (!s_found) return;
+    // an utterance's items are its workgroups of nblk blocks, its rows its blocks
+    auto blocks = [&](int n) { return jr::n_blocks(n, c.frame); };
+    ps::Job<long long, long long> job;
+    const bool found = ps::find_job<THREADS>(B, in_off, in_cap, (long long)blockIdx.x, [&](int, int K) { return (K + nblk - 1) / nblk; }, blocks, &job);
+    if (blockIdx.x == 0 && t == 0 && (job.rows > nb_cap || in_off[B] > in_cap)) as_status_raise(status, AS_STATUS_CAPACITY);
+    if (!found) return;
 
-    const int first = s_job[0], n = s_job[1], k_first = s_job[2], K = jr::n_blocks(n, c.frame);
-    const long long base = s_job_blk;
+    const int first = job.first, n = job.n, k_first = job.idx * nblk, K = job.own;
+    const long long base = job.base;
     const int wv = t / AS_WAVE, lane = t % AS_WAVE;
     for (int kk = wv; kk < nblk; kk += WAVES) {
         const int k = k_first + kk;
@@ -157,14 +95,9 @@ join_reduce_kernel(jr::Cfg c, int B, const int* __restrict__ in_off, int in_cap,
                    float* __restrict__ gain)
 {
     const int b = blockIdx.x, lane = threadIdx.x;
-    long long base = 0;
-    for (int j = lane; j < b; j += AS_WAVE) {
-        int first;
-        base += jr::n_blocks(len_at(in_off, in_cap, j, &first), c.frame);
-    }
-    base = as_wave_sum(base);
+    const long long base = ps::rows_before(b, in_off, in_cap, lane, [&](int n) { return jr::n_blocks(n, c.frame); });
     int first;
-    const int n = len_at(in_off, in_cap, b, &first);
+    const int n = ps::len_at(in_off, in_cap, b, &first);
     const int K = (int)max(min((long long)jr::n_blocks(n, c.frame), nb_cap - base), 0LL);      // (more blocks than the table holds: AS_STATUS_CAPACITY was raised)
     const float* s = ss + base;
     const float* p = pk + base;
@@ -213,15 +146,7 @@ __device__ __forceinline__ void emit(float* __restrict__ y, short* __restrict__ 
     const uintptr_t a = (y ? reinterpret_cast<uintptr_t>(y) >> 2 : reinterpret_cast<uintptr_t>(pcm) >> 1) + (uintptr_t)o_base;
     const int head = min((int)((4 - (a & 3)) & 3), cnt), nv = (cnt - head) >> 2;
     const bool pcm_vec = pcm && (((reinterpret_cast<uintptr_t>(pcm) >> 1) + (uintptr_t)o_base + head) & 3) == 0;
-    auto put = [&](int i) {
-        const float v = one(i);
-        if (y) y[o_base + i] = v;
-        if (pcm) {
-            bool nan;
-            pcm[o_base + i] = (short)as_pcm16(v, &nan);
-            if (nan) as_status_raise(status, AS_STATUS_F16_RANGE);
-        }
-    };
+    auto put = [&](int i) { ps::put(one(i), o_base + i, y, pcm, status); };
     if (t < head) put(t);
     for (int v = t; v < nv; v += THREADS) {
         const int i = head + 4 * v;
@@ -255,10 +180,7 @@ join_write_kernel(jr::Cfg c, int B, const int* __restrict__ in_off, int in_cap, 
                   const float* __restrict__ ws_g, int out_cap, float* __restrict__ y, short* __restrict__ pcm, int* __restrict__ out_off,
                   jr::Piece* __restrict__ piece, float* __restrict__ gain, unsigned* __restrict__ status)
 {
-    __shared__ long long s_sum[3][THREADS];
-    long long* const s_a = s_sum[0];
-    long long* const s_til = s_sum[1];
-    long long* const s_zer = s_sum[2];
+    __shared__ long long s_a[THREADS], s_til[THREADS], s_zer[THREADS];
     __shared__ int s_lg[THREADS];
     __shared__ long long s_job_o;                   // piece tile: the piece's first output; zero tile: the run's first output
     __shared__ long long s_job_e;                   // zero tile: the run's end
@@ -274,7 +196,7 @@ join_write_kernel(jr::Cfg c, int B, const int* __restrict__ in_off, int in_cap, 
     // the kept range of utterance b, held inside the utterance whatever the workspace says
     auto range = [&](int b, int* src, int* s0) {
         int first;
-        const int n = len_at(in_off, in_cap, b, &first);
+        const int n = ps::len_at(in_off, in_cap, b, &first);
         const int a = min(max(ws_s0[b], 0), n), e = min(max(ws_s1[b], a), n);
         *src = first + a;
         *s0 = a;
@@ -288,7 +210,7 @@ join_write_kernel(jr::Cfg c, int B, const int* __restrict__ in_off, int in_cap, 
         if (range(b, &src, &s0) > 0) lg_local = jr::group_of(b, B, G, group_off);
     }
     s_lg[t] = lg_local;
-    scan_max(s_lg, t);
+    ps::scan_max<THREADS>(t, s_lg);
     const int lg_in = t > 0 ? s_lg[t - 1] : -1, lg_all = s_lg[THREADS - 1];
 
     // ---- samples, piece tiles and zero tiles per chunk (a zero run's length does not depend on what stands in front of it)
@@ -310,7 +232,7 @@ join_write_kernel(jr::Cfg c, int B, const int* __restrict__ in_off, int in_cap, 
     s_a[t] = local_a;
     s_til[t] = local_til;
     s_zer[t] = local_zer;
-    scan_sum<3>(s_sum, t);
+    ps::scan_sum<THREADS>(t, s_a, s_til, s_zer);
     const long long total_a = s_a[THREADS - 1], total_til = s_til[THREADS - 1], total_zer = s_zer[THREADS - 1];
 
     // ---- positions: publish the workgroup's tile; workgroup 0 stores the tables
@@ -394,14 +316,6 @@ join_write_kernel(jr::Cfg c, int B, const int* __restrict__ in_off, int in_cap, 
     emit(y, pcm, o_base, cnt, status, t, one, four);
 }
 
-jr::Cfg rule_cfg(const as_join_cfg* cfg)
-{
-    jr::Cfg c;
-    std::memcpy(&c, cfg, sizeof(c));
-    return c;
-}
-
-size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 long long table_blocks(int B, int in_cap, int frame) { return (long long)in_cap / frame + B + 1; }
 
 struct Workspace {
@@ -428,7 +342,7 @@ int blocks_per_group(int frame) { return SPAN / frame > 1 ? SPAN / frame : 1; }
 // what both device entry points refuse before anything is launched
 int check(const as_join_cfg* cfg, int B, const as_join_io* io, const void* ws, size_t ws_bytes, bool joins)
 {
-    if (!cfg || !io || !ws || B < 1 || io->G < 1 || !io->in_off || !io->x || io->in_cap < 1 || !jr::cfg_ok(rule_cfg(cfg))) return AS_EINVAL;
+    if (!cfg || !io || !ws || B < 1 || io->G < 1 || !io->in_off || !io->x || io->in_cap < 1 || !jr::cfg_ok(rule_cfg<jr::Cfg>(cfg))) return AS_EINVAL;
     if (joins && ((!io->y && !io->pcm) || io->out_cap < 1 || io->out_cap > MAX_CAP)) return AS_EINVAL;
     if (io->in_cap > MAX_CAP) return AS_EINVAL;
     if (!joins && !io->piece) return AS_EINVAL;
@@ -461,7 +375,7 @@ extern "C" int as_join_measure_f32(const as_join_cfg* cfg, int B, const as_join_
 {
     const int rc = check(cfg, B, io, ws, ws_bytes, false);
     if (rc != AS_OK) return rc;
-    const jr::Cfg c = rule_cfg(cfg);
+    const jr::Cfg c = rule_cfg<jr::Cfg>(cfg);
     hipStream_t s = (hipStream_t)stream;
     AsProfScope prof__(AS_FILE_CLS, 2.0 * io->in_cap, 4.0 * io->in_cap, s, "join_measure");
     launch_measure(c, B, io, carve(ws, B, io->in_cap, c.frame), true, s);
@@ -473,7 +387,7 @@ extern "C" int as_join_f32(const as_join_cfg* cfg, int B, const as_join_io* io, 
 {
     const int rc = check(cfg, B, io, ws, ws_bytes, true);
     if (rc != AS_OK) return rc;
-    const jr::Cfg c = rule_cfg(cfg);
+    const jr::Cfg c = rule_cfg<jr::Cfg>(cfg);
     const Workspace k = carve(ws, B, io->in_cap, c.frame);
     hipStream_t s = (hipStream_t)stream;
     // bytes: every input twice, every output once
@@ -491,13 +405,13 @@ extern "C" int as_join_f32(const as_join_cfg* cfg, int B, const as_join_io* io, 
 
 extern "C" int as_join_host(const as_join_cfg* cfg, int B, const as_join_io* io)
 {
-    if (!cfg || !io || B < 1 || io->G < 1 || !io->in_off || !io->x || io->in_cap < 1 || !jr::cfg_ok(rule_cfg(cfg))) return AS_EINVAL;
+    if (!cfg || !io || B < 1 || io->G < 1 || !io->in_off || !io->x || io->in_cap < 1 || !jr::cfg_ok(rule_cfg<jr::Cfg>(cfg))) return AS_EINVAL;
     const bool joins = io->y || io->pcm;
     if (joins ? io->out_cap < 1 : !io->piece) return AS_EINVAL;
     if (io->in_off[0] != 0 || io->in_off[B] > io->in_cap) return AS_EINVAL;
     for (int b = 0; b < B; ++b)
         if (io->in_off[b + 1] < io->in_off[b]) return AS_EINVAL;
-    const jr::Cfg c = rule_cfg(cfg);
+    const jr::Cfg c = rule_cfg<jr::Cfg>(cfg);
     std::vector<int32_t> s0(B), s1(B);
     std::vector<float> g(B), ss, pk;
     bool good = true;

@@ -25,15 +25,20 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define JOIN_HD __host__ __device__
-#else
-#define JOIN_HD
-#endif
+#include "rule_math.h"
 
 namespace join_rule {
 
+using rule_math::add;           // one rounding each, on either side
+using rule_math::cut;
+using rule_math::div;
+using rule_math::finite;
+using rule_math::group_of;      // the stream an utterance belongs to
+using rule_math::mul;
+using rule_math::tree64;        // the halving tree over the 64 chains
+
 constexpr int CHAINS = 64, MIN_FRAME = 16, MAX_FRAME = 4096;
+static_assert(CHAINS == 64, "the chains are added by tree64");
 
 struct Cfg {                    // as_join_cfg, field for field
     int32_t frame;
@@ -49,32 +54,9 @@ struct Decision {
     float top, A, peak, gain;
 };
 
-// one rounding each, on either side
-JOIN_HD inline float mul(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fmul_rn(a, b);
-#else
-    return a * b;
-#endif
-}
-JOIN_HD inline float add(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fadd_rn(a, b);
-#else
-    return a + b;
-#endif
-}
-JOIN_HD inline float div(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fdiv_rn(a, b);
-#else
-    return a / b;
-#endif
-}
-JOIN_HD inline float root(float a)
+// (not master_rule's root: on gfx950 __fsqrt_rn is the bare v_sqrt_f32, within 1 ulp, where sqrtf adds the correction step; the joiner's
+// bits on the device are those of this form, and changing them is not a refactoring)
+RULE_HD inline float root(float a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __fsqrt_rn(a);
@@ -82,8 +64,7 @@ JOIN_HD inline float root(float a)
     return sqrtf(a);
 #endif
 }
-JOIN_HD inline float sq_acc(float x, float acc) { return fmaf(x, x, acc); }
-JOIN_HD inline bool finite(float x) { return fabsf(x) <= FLT_MAX; }
+RULE_HD inline float sq_acc(float x, float acc) { return fmaf(x, x, acc); }
 
 inline bool cfg_ok(const Cfg& c)
 {
@@ -92,22 +73,14 @@ inline bool cfg_ok(const Cfg& c)
            ok(c.target_rms) && ok(c.peak_ceiling) && ok(c.max_gain);
 }
 
-JOIN_HD inline int n_blocks(int n, int F) { return n <= 0 ? 0 : (int)(((long long)n + F - 1) / F); }
-JOIN_HD inline int block_cnt(int n, int F, int k)
+RULE_HD inline int n_blocks(int n, int F) { return n <= 0 ? 0 : (int)(((long long)n + F - 1) / F); }
+RULE_HD inline int block_cnt(int n, int F, int k)
 {
     const long long r = (long long)n - (long long)k * F;
     return r < F ? (int)r : F;
 }
-JOIN_HD inline int sample_chain(int i) { return (i >> 2) & (CHAINS - 1); }
-JOIN_HD inline int block_chain(int k) { return k & (CHAINS - 1); }
-
-// the halving tree over 64 partial sums: the result is v[0]
-JOIN_HD inline float tree64(float* v)
-{
-    for (int o = CHAINS / 2; o > 0; o >>= 1)
-        for (int l = 0; l < o; ++l) v[l] = add(v[l], v[l + o]);
-    return v[0];
-}
+RULE_HD inline int sample_chain(int i) { return (i >> 2) & (CHAINS - 1); }
+RULE_HD inline int block_chain(int k) { return k & (CHAINS - 1); }
 
 // one block on the host: its sum of squares in the order of the rule, its peak; false: a sample is not finite
 inline bool block_measure(const float* x, int cnt, float* ss, float* pk)
@@ -126,12 +99,12 @@ inline bool block_measure(const float* x, int cnt, float* ss, float* pk)
     return good;
 }
 
-JOIN_HD inline float mean_square(float ss, int cnt) { return div(ss, (float)cnt); }
-JOIN_HD inline float threshold(const Cfg& c, float top) { return mul(c.trim_ratio, top); }
-JOIN_HD inline bool active(const Cfg& c, float ms, float thr) { return !(c.trim_ratio > 0.f) || (ms > 0.f && ms >= thr); }
+RULE_HD inline float mean_square(float ss, int cnt) { return div(ss, (float)cnt); }
+RULE_HD inline float threshold(const Cfg& c, float top) { return mul(c.trim_ratio, top); }
+RULE_HD inline bool active(const Cfg& c, float ms, float thr) { return !(c.trim_ratio > 0.f) || (ms > 0.f && ms >= thr); }
 
 // [s0, s1) from the first and last active block (k0 < 0: none)
-JOIN_HD inline void kept(const Cfg& c, int n, int k0, int k1, int32_t* s0, int32_t* s1)
+RULE_HD inline void kept(const Cfg& c, int n, int k0, int k1, int32_t* s0, int32_t* s1)
 {
     if (k0 < 0 || n <= 0) {
         *s0 = *s1 = 0;
@@ -142,7 +115,7 @@ JOIN_HD inline void kept(const Cfg& c, int n, int k0, int k1, int32_t* s0, int32
     *s1 = (int32_t)(b < n ? b : n);
 }
 
-JOIN_HD inline float gain(const Cfg& c, float A, int C, float peak)
+RULE_HD inline float gain(const Cfg& c, float A, int C, float peak)
 {
     if (!(c.target_rms > 0.f) || !(A > 0.f)) return 1.f;
     const float rms = root(div(A, (float)C));
@@ -180,36 +153,23 @@ inline Decision decide(const Cfg& c, int n, const float* ss, const float* pk)
     return d;
 }
 
-JOIN_HD inline int fade_len(const Cfg& c, int m) { return c.fade < m / 2 ? c.fade : m / 2; }
-JOIN_HD inline float weight(int i, int m, int f)
+RULE_HD inline int fade_len(const Cfg& c, int m) { return c.fade < m / 2 ? c.fade : m / 2; }
+RULE_HD inline float weight(int i, int m, int f)
 {
     if (i < f) return div(add((float)i, 0.5f), (float)f);
     if (i >= m - f) return div(add((float)(m - 1 - i), 0.5f), (float)f);
     return 1.f;
 }
-JOIN_HD inline float sample(float x, float g, float w) { return mul(mul(x, g), w); }
+RULE_HD inline float sample(float x, float g, float w) { return mul(mul(x, g), w); }
 
-// the stream utterance b belongs to: the number of inner cuts group_off[1 .. G) at or below b (cuts are read clamped to [0, B]; NULL: one
-// stream over everything)
-JOIN_HD inline int group_of(int b, int B, int G, const int32_t* group_off)
-{
-    if (!group_off) return 0;
-    int g = 0;
-    for (int j = 1; j < G; ++j) {
-        const int cut = group_off[j] < 0 ? 0 : group_off[j] > B ? B : group_off[j];
-        g += cut <= b;
-    }
-    return g;
-}
-JOIN_HD inline int gap_of(const Cfg& c, const int32_t* gap, int b)
+RULE_HD inline int gap_of(const Cfg& c, const int32_t* gap, int b)
 {
     const int v = gap ? gap[b] : c.gap;
     return v > 0 ? v : 0;
 }
 // first output of a piece: the streams in front of it, its stream's lead, the pieces and gaps in front of it (`before`), its own gap
-JOIN_HD inline long long piece_start(const Cfg& c, int g, long long before, int pre) { return (long long)g * ((long long)c.lead + c.tail) + c.lead + before + pre; }
-JOIN_HD inline long long stream_start(const Cfg& c, int g, long long before) { return (long long)g * ((long long)c.lead + c.tail) + before; }
-JOIN_HD inline int32_t cut(long long v, long long cap) { return (int32_t)(v < cap ? v : cap); }
+RULE_HD inline long long piece_start(const Cfg& c, int g, long long before, int pre) { return (long long)g * ((long long)c.lead + c.tail) + c.lead + before + pre; }
+RULE_HD inline long long stream_start(const Cfg& c, int g, long long before) { return (long long)g * ((long long)c.lead + c.tail) + before; }
 
 // where everything lands, on the host: s0 / s1 [B] are the kept ranges.  Returns the samples the streams need; out_off [G + 1] and piece [B]
 // (each may be NULL) are cut at out_cap.

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "artspeech_hip.h"
 #include "marks_rule.h"
+#include "packed_streams.h"
 #include <cstring>
 #include <vector>
 
@@ -23,23 +24,14 @@
 namespace {
 
 namespace mr = marks_rule;
+namespace ps = packed_streams;
+using rule_math::round16;
+using rule_math::rule_cfg;
 
 constexpr int THREADS = 256;
 
 static_assert(sizeof(mr::Cfg) == sizeof(as_marks_cfg) && sizeof(mr::Piece) == sizeof(as_join_piece), "marks_rule.h restates the public structs");
 static_assert(sizeof(mr::Utt) == 32, "pieces_of strides over the table in 32-bit words");
-
-// inclusive block scan over THREADS values
-__device__ __forceinline__ void scan_sum(long long* s, int t)
-{
-    __syncthreads();
-    for (int off = 1; off < THREADS; off <<= 1) {
-        const long long v = t >= off ? s[t - off] : 0;
-        __syncthreads();
-        s[t] += v;
-        __syncthreads();
-    }
-}
 
 struct Tables {
     mr::Utt* utt;               // [B]
@@ -47,7 +39,6 @@ struct Tables {
     int32_t* ao;                // [Gs + 1] anim_off
     size_t bytes;
 };
-size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 Tables carve(void* ws, int B)
 {
     const size_t streams = (size_t)(B > mr::MAX_G ? B : mr::MAX_G) + 1, tab = round16(sizeof(mr::Utt) * (size_t)B), off = round16(4 * streams);
@@ -85,7 +76,7 @@ marks_layout_kernel(mr::Cfg c, int B, const int* __restrict__ frame_off, long lo
                 local += mr::utt_len(c, W, &fine);
             }
             s_sum[t] = local;
-            scan_sum(s_sum, t);
+            ps::scan_sum<THREADS>(t, s_sum);
         }
         long long before = piece ? 0 : s_sum[t] - local;
         for (int b = lo; b < hi; ++b) {
@@ -128,7 +119,7 @@ marks_layout_kernel(mr::Cfg c, int B, const int* __restrict__ frame_off, long lo
         long long local = 0;
         for (int g = lo; g < hi; ++g) local += frames_of(g);
         s_sum[t] = local;
-        scan_sum(s_sum, t);
+        ps::scan_sum<THREADS>(t, s_sum);
         long long before = s_sum[t] - local;
         for (int g = lo; g < hi; ++g) {
             const int v = mr::cut(before, anim_cap);
@@ -164,7 +155,7 @@ marks_token_kernel(mr::Cfg c, int n_tokens, const int* __restrict__ tok_off, con
     long long local = 0;
     for (int k = lo; k < hi; ++k) local += mr::dur(dur_i[k]);
     s_sum[t] = local;
-    scan_sum(s_sum, t);
+    ps::scan_sum<THREADS>(t, s_sum);
     long long e = s_sum[t] - local;
     for (int k = lo; k < hi; ++k) {
         const long long d = mr::dur(dur_i[k]);
@@ -197,17 +188,10 @@ marks_tracks_kernel(mr::Cfg c, int B, int Gs, const mr::Utt* __restrict__ utt, c
     if (active) active[t] = on ? 1 : 0;
 }
 
-mr::Cfg rule_cfg(const as_marks_cfg* cfg)
-{
-    mr::Cfg c;
-    std::memcpy(&c, cfg, sizeof(c));
-    return c;
-}
-
 // what the device and the host entry point refuse alike
 int check(const as_marks_cfg* cfg, int B, int n_tokens, const as_marks_io* io)
 {
-    if (!cfg || !io || !mr::cfg_ok(rule_cfg(cfg)) || !io->frame_off) return AS_EINVAL;
+    if (!cfg || !io || !mr::cfg_ok(rule_cfg<mr::Cfg>(cfg)) || !io->frame_off) return AS_EINVAL;
     const bool wants_frames = io->tracks || io->active;
     if (!io->marks && !wants_frames && !io->anim_off) return AS_EINVAL;
     if (!mr::args_ok(B, n_tokens, io->piece != nullptr, io->G, io->anim_cap)) return AS_EINVAL;
@@ -227,7 +211,7 @@ mr::Src source(const as_marks_io* io) { return mr::Src{io->tracks ? io->F0 : nul
 
 extern "C" size_t as_marks_workspace_bytes(int B, int n_tokens, const as_marks_cfg* cfg)
 {
-    if (!cfg || !mr::cfg_ok(rule_cfg(cfg)) || !mr::args_ok(B, n_tokens, false, 1, 0)) return 0;
+    if (!cfg || !mr::cfg_ok(rule_cfg<mr::Cfg>(cfg)) || !mr::args_ok(B, n_tokens, false, 1, 0)) return 0;
     return carve(nullptr, B).bytes;
 }
 
@@ -238,7 +222,7 @@ extern "C" int as_marks_f32(const as_marks_cfg* cfg, int B, int n_tokens, const 
     if (!ws) return AS_EINVAL;
     if (ws_bytes < as_marks_workspace_bytes(B, n_tokens, cfg)) return AS_ENOSPC;
     if (as_status_peek()) return AS_EDEVICE;
-    const mr::Cfg c = rule_cfg(cfg);
+    const mr::Cfg c = rule_cfg<mr::Cfg>(cfg);
     const Tables k = carve(ws, B);
     const int Gs = io->piece ? io->G : B;
     hipStream_t s = (hipStream_t)stream;
@@ -265,7 +249,7 @@ extern "C" int as_marks_host(const as_marks_cfg* cfg, int B, int n_tokens, const
 {
     const int rc = check(cfg, B, n_tokens, io);
     if (rc != AS_OK) return rc;
-    const mr::Cfg c = rule_cfg(cfg);
+    const mr::Cfg c = rule_cfg<mr::Cfg>(cfg);
     const int Gs = io->piece ? io->G : B;
     std::vector<mr::Utt> utt((size_t)B);
     std::vector<int32_t> so((size_t)Gs + 1), ao((size_t)Gs + 1);

@@ -49,13 +49,12 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define MARKS_HD __host__ __device__
-#else
-#define MARKS_HD
-#endif
+#include "rule_math.h"
 
 namespace marks_rule {
+
+using rule_math::cut;
+using rule_math::group_of;      // the stream an utterance belongs to (with pieces)
 
 constexpr int TRACKS = 12, MAX_G = 4096, MAX_B = 1 << 20;
 constexpr int64_t MAX_HOP = 1 << 16, MAX_LM = 1 << 12, MAX_RATE = 1 << 20, MAX_FPS = 1 << 16, MAX_POS = 1 << 30, MAX_FRAMES = 1 << 24;
@@ -78,7 +77,7 @@ struct Pick {
     float w;
 };
 
-MARKS_HD inline int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+RULE_HD inline int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 inline bool cfg_ok(const Cfg& c)
 {
@@ -90,36 +89,29 @@ inline bool args_ok(int B, int n_tokens, bool with_piece, int G, int64_t anim_ca
     return B >= 1 && B <= MAX_B && n_tokens >= 0 && n_tokens <= MAX_POS && anim_cap >= 0 && anim_cap <= MAX_POS && (!with_piece || (G >= 1 && G <= MAX_G));
 }
 
-MARKS_HD inline int64_t frame_cap(bool tracks, int32_t ld_pred)
+RULE_HD inline int64_t frame_cap(bool tracks, int32_t ld_pred)
 {
     const int64_t h = ld_pred / 2;
     return !tracks ? MAX_FRAMES : h < MAX_FRAMES ? (h > 0 ? h : 0) : MAX_FRAMES;
 }
 // the columns of utterance b; false: frame_off had to be clamped
-MARKS_HD inline bool columns(const int32_t* frame_off, int b, int64_t fcap, int32_t* col0, int32_t* W)
+RULE_HD inline bool columns(const int32_t* frame_off, int b, int64_t fcap, int32_t* col0, int32_t* W)
 {
     const int64_t f0 = clampi(frame_off[b], 0, fcap), f1 = clampi(frame_off[b + 1], f0, fcap);
     *col0 = (int32_t)(2 * f0);
     *W = (int32_t)(2 * (f1 - f0));
     return f0 == frame_off[b] && f1 == frame_off[b + 1];
 }
-MARKS_HD inline int64_t r(const Cfg& c, int64_t p) { return (p * c.L + c.M - 1) / c.M; }
-MARKS_HD inline int64_t utt_len(const Cfg& c, int32_t W, bool* ok)
+RULE_HD inline int64_t r(const Cfg& c, int64_t p) { return (p * c.L + c.M - 1) / c.M; }
+RULE_HD inline int64_t utt_len(const Cfg& c, int32_t W, bool* ok)
 {
     const int64_t n = r(c, (int64_t)c.hop * W);
     *ok = n <= MAX_POS;
     return n <= MAX_POS ? n : MAX_POS;
 }
-MARKS_HD inline int group_of(int b, int B, int G, const int32_t* group_off)
-{
-    if (!group_off) return 0;
-    int g = 0;
-    for (int j = 1; j < G; ++j) g += clampi(group_off[j], 0, B) <= b;
-    return g;
-}
-MARKS_HD inline int64_t stream_pos(int32_t v) { return clampi(v, 0, MAX_POS); }
+RULE_HD inline int64_t stream_pos(int32_t v) { return clampi(v, 0, MAX_POS); }
 // stream g of out_off: [*s, *e); false: out_off had to be changed
-MARKS_HD inline bool stream_of(const int32_t* out_off, int g, int32_t* s, int32_t* e)
+RULE_HD inline bool stream_of(const int32_t* out_off, int g, int32_t* s, int32_t* e)
 {
     const int64_t a = stream_pos(out_off[g]), z = stream_pos(out_off[g + 1]);
     *s = (int32_t)a;
@@ -127,7 +119,7 @@ MARKS_HD inline bool stream_of(const int32_t* out_off, int g, int32_t* s, int32_
     return a == out_off[g] && z == out_off[g + 1] && z >= a;
 }
 // an utterance of n samples placed by a piece inside its stream [s, e); false: the piece had to be changed
-MARKS_HD inline bool place(const Piece& p, int64_t n, int32_t s, int32_t e, Utt* u)
+RULE_HD inline bool place(const Piece& p, int64_t n, int32_t s, int32_t e, Utt* u)
 {
     const int64_t os = clampi(p.out_start, s, e), oe = clampi(p.out_end, os, e), ss = clampi(p.src_start, 0, n), se = clampi(p.src_end, ss, n);
     const int64_t m = oe - os < se - ss ? oe - os : se - ss;
@@ -138,7 +130,7 @@ MARKS_HD inline bool place(const Piece& p, int64_t n, int32_t s, int32_t e, Utt*
     return os == p.out_start && oe == p.out_end && ss == p.src_start && se == p.src_end && oe - os == se - ss;
 }
 // no piece: the utterance is its own stream at the prefix sum `before`
-MARKS_HD inline bool place_alone(int64_t before, int64_t n, Utt* u)
+RULE_HD inline bool place_alone(int64_t before, int64_t n, Utt* u)
 {
     const int64_t os = before < MAX_POS ? before : MAX_POS, oe = before + n < MAX_POS ? before + n : MAX_POS;
     u->out_start = (int32_t)os;
@@ -147,31 +139,30 @@ MARKS_HD inline bool place_alone(int64_t before, int64_t n, Utt* u)
     u->src_end = (int32_t)(oe - os);
     return before + n <= MAX_POS;
 }
-MARKS_HD inline int32_t dur(int32_t d) { return d > 0 ? d : 0; }
-MARKS_HD inline void token_range(const int32_t* tok_off, int b, int n_tokens, int32_t* t0, int32_t* t1)
+RULE_HD inline int32_t dur(int32_t d) { return d > 0 ? d : 0; }
+RULE_HD inline void token_range(const int32_t* tok_off, int b, int n_tokens, int32_t* t0, int32_t* t1)
 {
     const int64_t a = clampi(tok_off[b], 0, n_tokens);
     *t0 = (int32_t)a;
     *t1 = (int32_t)clampi(tok_off[b + 1], a, n_tokens);
 }
 // the boundary at e half-rate frames from the utterance's start (e >= 0; cut at the utterance's own frames)
-MARKS_HD inline int32_t mark(const Cfg& c, const Utt& u, int64_t e)
+RULE_HD inline int32_t mark(const Cfg& c, const Utt& u, int64_t e)
 {
     const int64_t half = u.W / 2;
     e = e < half ? e : half;
     return u.out_start + (int32_t)clampi(r(c, 2 * (int64_t)c.hop * e) - u.src_start, 0, (int64_t)u.out_end - u.out_start);
 }
-MARKS_HD inline int64_t stream_frames(const Cfg& c, int64_t len)
+RULE_HD inline int64_t stream_frames(const Cfg& c, int64_t len)
 {
     return len <= 0 ? 0 : ((len - 1) * c.fps_num) / ((int64_t)c.rate * c.fps_den) + 1;
 }
-MARKS_HD inline int32_t cut(int64_t v, int64_t cap) { return (int32_t)(v < cap ? v : cap); }
 
-MARKS_HD inline int64_t frame_q(const Cfg& c, int32_t s, int64_t m) { return m * c.fps_den * c.rate + (int64_t)s * c.fps_num; }
-MARKS_HD inline int64_t col_den(const Cfg& c) { return (int64_t)c.fps_num * c.L * c.hop; }
+RULE_HD inline int64_t frame_q(const Cfg& c, int32_t s, int64_t m) { return m * c.fps_den * c.rate + (int64_t)s * c.fps_num; }
+RULE_HD inline int64_t col_den(const Cfg& c) { return (int64_t)c.fps_num * c.L * c.hop; }
 
 // the two columns and the weight at A / D - 1/2 of an utterance of W > 0 columns
-MARKS_HD inline Pick pick(int64_t A, int64_t D, int32_t W)
+RULE_HD inline Pick pick(int64_t A, int64_t D, int32_t W)
 {
     const int64_t n2 = 2 * A - D, d2 = 2 * D;
     if (n2 < 0) return Pick{0, 0, 0.f};
@@ -181,15 +172,15 @@ MARKS_HD inline Pick pick(int64_t A, int64_t D, int32_t W)
     w = w < 0.f ? 0.f : w > 1.f ? 1.f : w;
     return Pick{(int32_t)j, (int32_t)j + 1, w};
 }
-MARKS_HD inline const float* row(const Src& s, int c) { return c == 0 ? s.F0 : c == 1 ? s.N : s.EMA + (size_t)(c - 2) * s.ld; }
-MARKS_HD inline float value(const Src& s, int c, const Utt& u, const Pick& p)
+RULE_HD inline const float* row(const Src& s, int c) { return c == 0 ? s.F0 : c == 1 ? s.N : s.EMA + (size_t)(c - 2) * s.ld; }
+RULE_HD inline float value(const Src& s, int c, const Utt& u, const Pick& p)
 {
     const float* v = row(s, c) + u.col0;
     const float v0 = v[p.j0];
     return fmaf(p.w, v[p.j1] - v0, v0);
 }
-MARKS_HD inline bool empty(const Utt& u) { return u.out_end <= u.out_start; }
-MARKS_HD inline float gap_weight(int64_t Q, int64_t num, int32_t oe_a, int32_t os_c)
+RULE_HD inline bool empty(const Utt& u) { return u.out_end <= u.out_start; }
+RULE_HD inline float gap_weight(int64_t Q, int64_t num, int32_t oe_a, int32_t os_c)
 {
     if (os_c <= oe_a) return 0.f;
     float w = (float)((double)(Q - (int64_t)oe_a * num) / (double)(((int64_t)os_c - oe_a) * num));
@@ -197,7 +188,7 @@ MARKS_HD inline float gap_weight(int64_t Q, int64_t num, int32_t oe_a, int32_t o
 }
 
 // Frame m of the stream [s, ..) whose pieces are utt[lo .. hi): out[c] for the twelve tracks (src.F0 == NULL: not computed); returns `active`.
-MARKS_HD inline bool frame(const Cfg& c, const Utt* utt, int lo, int hi, int32_t s, int64_t m, const Src& src, const float* scale, const float* offset,
+RULE_HD inline bool frame(const Cfg& c, const Utt* utt, int lo, int hi, int32_t s, int64_t m, const Src& src, const float* scale, const float* offset,
                            float* out)
 {
     const int64_t num = c.fps_num, Q = frame_q(c, s, m), D = col_den(c);
@@ -245,7 +236,7 @@ MARKS_HD inline bool frame(const Cfg& c, const Utt* utt, int lo, int hi, int32_t
 }
 
 // the first index in [0, n) of the ascending table v with v[i] >= key (n when there is none)
-MARKS_HD inline int lower_bound(const int32_t* v, int n, int key, int stride)
+RULE_HD inline int lower_bound(const int32_t* v, int n, int key, int stride)
 {
     int a = 0, e = n;
     while (a < e) {
@@ -256,7 +247,7 @@ MARKS_HD inline int lower_bound(const int32_t* v, int n, int key, int stride)
     return a;
 }
 // the stream of animation column t: the last g in [0, G) with anim_off[g] <= t (t < anim_off[G])
-MARKS_HD inline int stream_at(const int32_t* anim_off, int G, int32_t t)
+RULE_HD inline int stream_at(const int32_t* anim_off, int G, int32_t t)
 {
     int a = 0, e = G;                                   // the first g with anim_off[g] > t
     while (a < e) {
@@ -267,7 +258,7 @@ MARKS_HD inline int stream_at(const int32_t* anim_off, int G, int32_t t)
     return a - 1;
 }
 // the pieces of stream g: utt[*lo .. *hi) (grp ascends with b)
-MARKS_HD inline void pieces_of(const Utt* utt, int B, int g, int* lo, int* hi)
+RULE_HD inline void pieces_of(const Utt* utt, int B, int g, int* lo, int* hi)
 {
     *lo = lower_bound(&utt[0].grp, B, g, (int)(sizeof(Utt) / sizeof(int32_t)));
     *hi = lower_bound(&utt[0].grp, B, g + 1, (int)(sizeof(Utt) / sizeof(int32_t)));

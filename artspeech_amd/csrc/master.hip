@@ -1,7 +1,7 @@
 // Mastering (include/artspeech_hip.h: as_master_f32): G packed streams brought to a programme loudness (ITU-R BS.1770, K-weighted and
 // gated) and held under a true-peak ceiling by a look-ahead limiter, by the rule of master_rule.h.  At most FIVE launches per call, none of
 // which synchronises, allocates or reads back; the stream lengths exist on the device only, so every grid is sized by in_cap and every
-// workgroup finds its work from the DEVICE offsets by a block scan (find_job, the scheme of resample.hip and join.hip):
+// workgroup finds its work from the DEVICE offsets (packed_streams.h: find_job, rows_before):
 //
 //   filter     a wave takes up to 64 consecutive chunks of ONE stream, a lane per chunk; the samples go through LDS 32 per chunk at a time
 //              so that the global loads are coalesced (a lane's own chunk lies 2 KiB from its neighbour's).  Every chunk is filtered from
@@ -22,6 +22,7 @@
 #include "common.h"
 #include "artspeech_hip.h"
 #include "master_rule.h"
+#include "packed_streams.h"
 #include <cstring>
 #include <new>
 #include <vector>
@@ -31,90 +32,16 @@
 namespace {
 
 namespace mr = master_rule;
+namespace ps = packed_streams;
+using rule_math::round16;
+using rule_math::rule_cfg;
+using Job = ps::Job<long long, long long>;
 
 constexpr int TILE = 2048, LIM_THREADS = 256, SUB = 32;
 constexpr int MAX_CAP = 1 << 30;
 constexpr int SPAN = TILE + 2 * mr::MAX_LOOK + 2 * mr::OS_J + 4, RSPAN = TILE + 2 * mr::MAX_LOOK;
 
 static_assert(sizeof(mr::Cfg) == sizeof(as_master_cfg) && sizeof(mr::Report) == sizeof(as_master_report), "master_rule.h restates the public structs");
-
-__device__ __forceinline__ int len_at(const int* in_off, int in_cap, int b, int* first)
-{
-    const int a = min(max(in_off[b], 0), in_cap), e = min(max(in_off[b + 1], 0), in_cap);
-    *first = a;
-    return max(e - a, 0);
-}
-
-struct Job {
-    int first, n, idx;          // the stream's first sample and length, the workgroup's index among the stream's workgroups
-    long long base;             // the table rows of the streams in front of it
-    long long items, rows;      // totals over all streams
-};
-
-// workgroup w's stream: a stream of n samples takes items(n) workgroups and rows(n) rows of a table.  false: w lies behind the last item.
-template <int TH, class Items, class Rows>
-__device__ __forceinline__ bool find_job(int G, const int* __restrict__ in_off, int in_cap, long long w, Items items, Rows rows, Job* job)
-{
-    __shared__ long long s_sum[2][TH];
-    __shared__ long long s_base;
-    __shared__ int s_job[3];
-    __shared__ int s_found;
-    const int t = threadIdx.x;
-    if (t == 0) s_found = 0;
-    const int per = (G + TH - 1) / TH, lo = min(t * per, G), hi = min(lo + per, G);
-    long long li = 0, lr = 0;
-    for (int b = lo; b < hi; ++b) {
-        int first;
-        const int n = len_at(in_off, in_cap, b, &first);
-        li += items(n);
-        lr += rows(n);
-    }
-    s_sum[0][t] = li;
-    s_sum[1][t] = lr;
-    __syncthreads();
-    for (int off = 1; off < TH; off <<= 1) {
-        const long long a = t >= off ? s_sum[0][t - off] : 0, c = t >= off ? s_sum[1][t - off] : 0;
-        __syncthreads();
-        s_sum[0][t] += a;
-        s_sum[1][t] += c;
-        __syncthreads();
-    }
-    long long ip = s_sum[0][t] - li, rp = s_sum[1][t] - lr;
-    for (int b = lo; b < hi; ++b) {
-        int first;
-        const int n = len_at(in_off, in_cap, b, &first);
-        const long long it = items(n);
-        if (w >= ip && w < ip + it) {
-            s_base = rp;
-            s_job[0] = first;
-            s_job[1] = n;
-            s_job[2] = (int)(w - ip);
-            s_found = 1;
-        }
-        ip += it;
-        rp += rows(n);
-    }
-    __syncthreads();
-    job->first = s_job[0];
-    job->n = s_job[1];
-    job->idx = s_job[2];
-    job->base = s_base;
-    job->items = s_sum[0][TH - 1];
-    job->rows = s_sum[1][TH - 1];
-    return s_found != 0;
-}
-
-// the table rows in front of stream b, by one wave
-template <class Rows>
-__device__ __forceinline__ long long rows_before(int b, const int* __restrict__ in_off, int in_cap, int lane, Rows rows)
-{
-    long long base = 0;
-    for (int j = lane; j < b; j += AS_WAVE) {
-        int first;
-        base += rows(len_at(in_off, in_cap, j, &first));
-    }
-    return as_wave_sum(base);
-}
 
 // SECOND false: every chunk from the zero state, its final state to fin.  true: from S[chunk], the two hop segments to seg.
 template <bool SECOND>
@@ -124,8 +51,8 @@ master_filter_kernel(mr::Filter f, int hop, int G, const int* __restrict__ in_of
 {
     __shared__ float tile[AS_WAVE][SUB + 1];
     Job job;
-    const bool found = find_job<AS_WAVE>(G, in_off, in_cap, blockIdx.x, [](int n) { return (mr::n_chunks(n) + AS_WAVE - 1) / AS_WAVE; },
-                                         [](int n) { return mr::n_chunks(n); }, &job);
+    const bool found = ps::find_job<AS_WAVE>(G, in_off, in_cap, (long long)blockIdx.x, [](int, int K) { return (K + AS_WAVE - 1) / AS_WAVE; },
+                                             [](int n) { return mr::n_chunks(n); }, &job);
     if (blockIdx.x == 0 && threadIdx.x == 0 && (job.rows > nc_cap || in_off[G] > in_cap)) as_status_raise(status, AS_STATUS_CAPACITY);
     if (!found) return;
 
@@ -175,9 +102,9 @@ master_carry_kernel(mr::Filter f, const int* __restrict__ in_off, int in_cap, co
 {
     __shared__ float4 s_in[AS_WAVE], s_out[AS_WAVE];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const long long base = rows_before(b, in_off, in_cap, lane, [](int n) { return mr::n_chunks(n); });
+    const long long base = ps::rows_before(b, in_off, in_cap, lane, [](int n) { return mr::n_chunks(n); });
     int first;
-    const int n = len_at(in_off, in_cap, b, &first);
+    const int n = ps::len_at(in_off, in_cap, b, &first);
     const int K = (int)max(min((long long)mr::n_chunks(n), nc_cap - base), 0LL);
     float st[4] = {0.f, 0.f, 0.f, 0.f};
     for (int j0 = 0; j0 < K; j0 += AS_WAVE) {
@@ -211,10 +138,10 @@ master_gate_kernel(mr::Cfg c, int hop, const int* __restrict__ in_off, int in_ca
         if (lane == 0 && report) report[b] = mr::Report{0.f, 1.f, 0.f, 1.f, 0, 0};
         return;
     }
-    const long long base_c = rows_before(b, in_off, in_cap, lane, [](int n) { return mr::n_chunks(n); });
-    const long long base_h = rows_before(b, in_off, in_cap, lane, [hop](int n) { return mr::n_hops(n, hop); });
+    const long long base_c = ps::rows_before(b, in_off, in_cap, lane, [](int n) { return mr::n_chunks(n); });
+    const long long base_h = ps::rows_before(b, in_off, in_cap, lane, [hop](int n) { return mr::n_hops(n, hop); });
     int first;
-    const int n = len_at(in_off, in_cap, b, &first);
+    const int n = ps::len_at(in_off, in_cap, b, &first);
     const int K = (int)max(min((long long)mr::n_chunks(n), nc_cap - base_c), 0LL);
     const int NH = (int)max(min((long long)mr::n_hops(n, hop), nh_cap - base_h), 0LL);
     float* e = e_tab + base_h;
@@ -278,19 +205,12 @@ master_limit_kernel(mr::Cfg c, mr::Taps taps, int G, const int* __restrict__ in_
 
     const int t = threadIdx.x;
     Job job;
-    auto tiles = [](int n) { return (n + TILE - 1) / TILE; };
-    const bool found = find_job<LIM_THREADS>(G, in_off, in_cap, blockIdx.x, tiles, [](int) { return 1; }, &job);
+    auto tiles = [](int n, int) { return (n + TILE - 1) / TILE; };
+    const bool found = ps::find_job<LIM_THREADS>(G, in_off, in_cap, (long long)blockIdx.x, tiles, [](int) { return 1; }, &job);
     if (blockIdx.x == 0 && t == 0 && in_off[G] > in_cap) as_status_raise(status, AS_STATUS_CAPACITY);
     if (!found) {
-        // behind the last tile: the filler [in_off[G], in_cap), one tile's width per workgroup
-        if (!WRITE) return;
-        const long long idx = (long long)blockIdx.x - job.items;
-        if (idx < 0) return;
-        const long long z0 = (long long)min(max(in_off[G], 0), in_cap) + idx * TILE, z1 = min(z0 + TILE, (long long)in_cap);
-        for (long long o = z0 + t; o < z1; o += LIM_THREADS) {
-            if (y) y[o] = 0.f;
-            if (pcm) pcm[o] = 0;
-        }
+        // the filler [in_off[G], in_cap)
+        if (WRITE) ps::fill_tail<LIM_THREADS>(y, pcm, min(max(in_off[G], 0), in_cap), in_cap, (long long)blockIdx.x - job.items, TILE, t);
         return;
     }
 
@@ -356,13 +276,7 @@ master_limit_kernel(mr::Cfg c, mr::Taps taps, int G, const int* __restrict__ in_
             }
             const float xv = s_x[i + A + mr::OS_J];
             const float v = limit ? mr::sample(xv, g, s) : mr::mul(g, xv);
-            const long long o = (long long)job.first + t0 + i;
-            if (y) y[o] = v;
-            if (pcm) {
-                bool nan;
-                pcm[o] = (short)as_pcm16(v, &nan);
-                if (nan) as_status_raise(status, AS_STATUS_F16_RANGE);
-            }
+            ps::put(v, (long long)job.first + t0 + i, y, pcm, status);
         }
     }
 
@@ -389,14 +303,6 @@ master_limit_kernel(mr::Cfg c, mr::Taps taps, int G, const int* __restrict__ in_
     }
 }
 
-mr::Cfg rule_cfg(const as_master_cfg* cfg)
-{
-    mr::Cfg c;
-    std::memcpy(&c, cfg, sizeof(c));
-    return c;
-}
-
-size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 long long chunk_rows(int G, int in_cap) { return (long long)in_cap / mr::P + G + 1; }
 long long hop_rows(int G, int in_cap, int hop) { return (long long)in_cap / hop + G + 1; }
 
@@ -475,10 +381,10 @@ extern "C" int as_master_create(const as_master_cfg* cfg, as_master** out)
 {
     if (!out) return AS_EINVAL;
     *out = nullptr;
-    if (!cfg || !mr::cfg_ok(rule_cfg(cfg))) return AS_EINVAL;
+    if (!cfg || !mr::cfg_ok(rule_cfg<mr::Cfg>(cfg))) return AS_EINVAL;
     as_master* m = new (std::nothrow) as_master();
     if (!m) return (int)hipErrorOutOfMemory;
-    m->c = rule_cfg(cfg);
+    m->c = rule_cfg<mr::Cfg>(cfg);
     mr::design(m->c.rate, &m->f, nullptr);
     mr::design_taps(&m->taps);
     *out = m;
@@ -538,13 +444,13 @@ extern "C" int as_master_measure_f32(const as_master* m, int G, const as_master_
 
 extern "C" int as_master_host(const as_master_cfg* cfg, int G, const as_master_io* io)
 {
-    if (!cfg || !io || !io->in_off || !io->x || G < 1 || G > mr::MAX_G || io->in_cap < 1 || io->in_cap > MAX_CAP || !mr::cfg_ok(rule_cfg(cfg))) return AS_EINVAL;
+    if (!cfg || !io || !io->in_off || !io->x || G < 1 || G > mr::MAX_G || io->in_cap < 1 || io->in_cap > MAX_CAP || !mr::cfg_ok(rule_cfg<mr::Cfg>(cfg))) return AS_EINVAL;
     const bool writes = io->y || io->pcm;
     if (!writes && !io->report) return AS_EINVAL;
     if (io->in_off[0] != 0 || io->in_off[G] > io->in_cap) return AS_EINVAL;
     for (int b = 0; b < G; ++b)
         if (io->in_off[b + 1] < io->in_off[b]) return AS_EINVAL;
-    const mr::Cfg c = rule_cfg(cfg);
+    const mr::Cfg c = rule_cfg<mr::Cfg>(cfg);
     mr::Filter f;
     mr::Taps* taps = new (std::nothrow) mr::Taps();
     if (!taps) return (int)hipErrorOutOfMemory;

@@ -37,19 +37,20 @@
 #include <vector>
 
 #include "resample_rule.h"
-
-#if defined(__HIPCC__)
-#define MASTER_HD __host__ __device__
-#else
-#define MASTER_HD
-#endif
+#include "rule_math.h"
 
 namespace master_rule {
+
+using rule_math::add;           // one rounding each, on either side
+using rule_math::div;
+using rule_math::mul;
+using rule_math::tree64;        // the halving tree over the 64 chains
 
 constexpr int P = 512, CHAINS = 64;
 constexpr int OS = 4, OS_H = 128, OS_J = 32, TAB_STRIDE = 68;      // the oversampler: phases, half length, taps reach x[n +- OS_J], row stride
 constexpr int MIN_RATE = 8000, MAX_RATE = 192000, MAX_LOOK = 512, MAX_G = 65535;
 static_assert(MIN_RATE / 10 >= P, "a chunk meets at most two hops");
+static_assert(CHAINS == 64, "the chains are added by tree64");
 
 struct Cfg {                    // as_master_cfg, field for field
     int32_t rate;
@@ -68,33 +69,8 @@ struct Taps {
     float h[OS][TAB_STRIDE];    // resample_rule's phase table for L = 4: h[p][j + OS_J] = the tap of phase p at x[n + j]
 };
 
-// one rounding each, on either side
-MASTER_HD inline float mul(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fmul_rn(a, b);
-#else
-    return a * b;
-#endif
-}
-MASTER_HD inline float add(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fadd_rn(a, b);
-#else
-    return a + b;
-#endif
-}
-MASTER_HD inline float div(float a, float b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fdiv_rn(a, b);
-#else
-    return a / b;
-#endif
-}
 // (sqrtf on the device too: hipcc rounds it correctly by default, whereas __fsqrt_rn is the hardware's approximate square root)
-MASTER_HD inline float root(float a) { return sqrtf(a); }
+RULE_HD inline float root(float a) { return sqrtf(a); }
 
 inline bool cfg_ok(const Cfg& c)
 {
@@ -171,7 +147,7 @@ inline void design_taps(Taps* t)
 }
 
 // ---- the filters
-MASTER_HD inline float kw_step(const float* q, float* s, float v)
+RULE_HD inline float kw_step(const float* q, float* s, float v)
 {
     const float o1 = fmaf(q[0], v, s[0]);
     s[0] = fmaf(-q[3], o1, fmaf(q[1], v, s[1]));
@@ -181,22 +157,22 @@ MASTER_HD inline float kw_step(const float* q, float* s, float v)
     s[3] = fmaf(-q[9], o2, mul(q[7], o1));
     return o2;
 }
-MASTER_HD inline void carry(const float* T, const float* S, const float* f, float* out)
+RULE_HD inline void carry(const float* T, const float* S, const float* f, float* out)
 {
     for (int i = 0; i < 4; ++i)
         out[i] = fmaf(T[4 * i + 3], S[3], fmaf(T[4 * i + 2], S[2], fmaf(T[4 * i + 1], S[1], fmaf(T[4 * i], S[0], f[i]))));
 }
 
-MASTER_HD inline int n_chunks(int n) { return n <= 0 ? 0 : (n + P - 1) / P; }
-MASTER_HD inline int chunk_cnt(int n, int j) { return n - j * P < P ? n - j * P : P; }
-MASTER_HD inline int n_hops(int n, int hop) { return n <= 0 ? 0 : (n + hop - 1) / hop; }
-MASTER_HD inline int n_blocks(int n, int hop) { return n <= 0 ? 0 : n < 4 * hop ? 1 : n / hop - 3; }
-MASTER_HD inline int chunk_hop(int j, int hop) { return (j * P) / hop; }
+RULE_HD inline int n_chunks(int n) { return n <= 0 ? 0 : (n + P - 1) / P; }
+RULE_HD inline int chunk_cnt(int n, int j) { return n - j * P < P ? n - j * P : P; }
+RULE_HD inline int n_hops(int n, int hop) { return n <= 0 ? 0 : (n + hop - 1) / hop; }
+RULE_HD inline int n_blocks(int n, int hop) { return n <= 0 ? 0 : n < 4 * hop ? 1 : n / hop - 3; }
+RULE_HD inline int chunk_hop(int j, int hop) { return (j * P) / hop; }
 // samples of chunk j in its first hop (the rest lies in the next one)
-MASTER_HD inline int chunk_cut(int j, int hop) { return (chunk_hop(j, hop) + 1) * hop - j * P; }
+RULE_HD inline int chunk_cut(int j, int hop) { return (chunk_hop(j, hop) + 1) * hop - j * P; }
 
 // hop i from the segment table seg[chunk][2] of its stream (K chunks)
-MASTER_HD inline float hop_energy(const float* seg, int K, int i, int hop, int n)
+RULE_HD inline float hop_energy(const float* seg, int K, int i, int hop, int n)
 {
     const long long last = (long long)(i + 1) * hop - 1;
     const int j0 = (int)(((long long)i * hop) / P), j1 = (int)((last < n - 1 ? last : n - 1) / P);
@@ -206,7 +182,7 @@ MASTER_HD inline float hop_energy(const float* seg, int K, int i, int hop, int n
 }
 
 // block i of a stream with nb blocks from its hop energies
-MASTER_HD inline float block_power(const float* e, int i, int nb, int n, int hop)
+RULE_HD inline float block_power(const float* e, int i, int nb, int n, int hop)
 {
     if (n < 4 * hop) {
         float a = 0.f;
@@ -215,15 +191,9 @@ MASTER_HD inline float block_power(const float* e, int i, int nb, int n, int hop
     }
     return div(add(add(add(e[i], e[i + 1]), e[i + 2]), e[i + 3]), (float)(4 * hop));
 }
-MASTER_HD inline int block_chain(int i) { return i & (CHAINS - 1); }
-MASTER_HD inline float tree64(float* v)
-{
-    for (int o = CHAINS / 2; o > 0; o >>= 1)
-        for (int l = 0; l < o; ++l) v[l] = add(v[l], v[l + o]);
-    return v[0];
-}
-MASTER_HD inline float rel_gate(float sum, int count) { return mul(0.1f, div(sum, (float)count)); }
-MASTER_HD inline float gain(const Cfg& c, float power)
+RULE_HD inline int block_chain(int i) { return i & (CHAINS - 1); }
+RULE_HD inline float rel_gate(float sum, int count) { return mul(0.1f, div(sum, (float)count)); }
+RULE_HD inline float gain(const Cfg& c, float power)
 {
     if (!(c.target_power > 0.f) || !(power > 0.f)) return 1.f;
     const float g = root(div(c.target_power, power));
@@ -264,7 +234,7 @@ inline void gate(const Cfg& c, int n, int hop, const float* e, Report* r)
 
 // ---- true peak and limiter
 // xs stands at sample n of a stream padded with zeros
-MASTER_HD inline float true_peak(const float* tab, const float* xs, float g)
+RULE_HD inline float true_peak(const float* tab, const float* xs, float g)
 {
     float p = fabsf(mul(g, xs[0]));
     for (int ph = 0; ph < OS; ++ph) {
@@ -274,13 +244,13 @@ MASTER_HD inline float true_peak(const float* tab, const float* xs, float g)
     }
     return p;
 }
-MASTER_HD inline float reduction(float ceiling, float p)
+RULE_HD inline float reduction(float ceiling, float p)
 {
     const float q = div(ceiling, p);
     return q < 1.f ? q : 1.f;
 }
-MASTER_HD inline float smooth(float sum, int A) { return div(sum, (float)(A + 1)); }
-MASTER_HD inline float sample(float x, float g, float s) { return mul(mul(g, x), s); }
+RULE_HD inline float smooth(float sum, int A) { return div(sum, (float)(A + 1)); }
+RULE_HD inline float sample(float x, float g, float s) { return mul(mul(g, x), s); }
 
 inline int pcm16(float w) { return w != w ? 0 : (int)fmaxf(-32768.f, fminf(32767.f, rintf(32767.f * w))); }
 

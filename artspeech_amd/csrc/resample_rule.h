@@ -20,11 +20,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define RESAMPLE_HD __host__ __device__
-#else
-#define RESAMPLE_HD
-#endif
+#include "rule_math.h"
 
 namespace resample_rule {
 
@@ -84,15 +80,15 @@ inline void design(const Ratio& r, float* taps)
     delete[] h;
 }
 
-RESAMPLE_HD inline int64_t out_len(int64_t n_in, int L, int M) { return n_in <= 0 ? 0 : (n_in * L + M - 1) / M; }
+RULE_HD inline int64_t out_len(int64_t n_in, int L, int M) { return n_in <= 0 ? 0 : (n_in * L + M - 1) / M; }
 
 // the phase table's columns: j = J0 .. J1
-RESAMPLE_HD inline int table_j0(int L, int H) { return -(H / L); }
-RESAMPLE_HD inline int table_j1(int L, int H) { return (H + L - 1) / L; }
-RESAMPLE_HD inline int table_taps(int L, int H) { return table_j1(L, H) - table_j0(L, H) + 1; }
+RULE_HD inline int table_j0(int L, int H) { return -(H / L); }
+RULE_HD inline int table_j1(int L, int H) { return (H + L - 1) / L; }
+RULE_HD inline int table_taps(int L, int H) { return table_j1(L, H) - table_j0(L, H) + 1; }
 // the taps of phase p: j = jlo .. jhi
-RESAMPLE_HD inline int phase_jlo(int p, int L, int H) { return -((H - p) / L); }
-RESAMPLE_HD inline int phase_jhi(int p, int L, int H) { return (H + p) / L; }
+RULE_HD inline int phase_jlo(int p, int L, int H) { return -((H - p) / L); }
+RULE_HD inline int phase_jhi(int p, int L, int H) { return (H + p) / L; }
 
 // table [L][stride >= T] from the prototype
 inline void table_fill(const Ratio& r, const float* taps, int stride, float* table)
@@ -107,7 +103,7 @@ inline void table_fill(const Ratio& r, const float* taps, int stride, float* tab
 
 // one output: row[j] = the phase's tap for input xs[j] (both pointers stand at j = 0, i.e. at table column -J0 and at input k = c);
 // xs holds zeros outside the utterance
-RESAMPLE_HD inline float dot(const float* row, const float* xs, int jlo, int jhi)
+RULE_HD inline float dot(const float* row, const float* xs, int jlo, int jhi)
 {
     float acc = 0.f;
     for (int j = jlo; j <= jhi; ++j) acc = fmaf(row[j], xs[j], acc);

@@ -22,11 +22,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define TOKEN_PROSODY_HD __host__ __device__
-#else
-#define TOKEN_PROSODY_HD
-#endif
+#include "rule_math.h"
 
 namespace token_prosody {
 
@@ -38,7 +34,7 @@ struct Pick {
 };
 
 // the control points of full-rate column j, which token k covers (2 start[k] <= j < 2 start[k + 1]), in the utterance of tokens first .. last
-TOKEN_PROSODY_HD inline Pick pick(int smooth, int64_t j, int32_t k, int32_t first, int32_t last, const int32_t* start)
+RULE_HD inline Pick pick(int smooth, int64_t j, int32_t k, int32_t first, int32_t last, const int32_t* start)
 {
     Pick p{k, k, 0.f};
     if (!smooth) return p;
@@ -53,7 +49,7 @@ TOKEN_PROSODY_HD inline Pick pick(int smooth, int64_t j, int32_t k, int32_t firs
 }
 
 // parameter `col` of the rows [tokens][ld] at the picked place
-TOKEN_PROSODY_HD inline float param(const Pick& p, const float* rows, int ld, int col)
+RULE_HD inline float param(const Pick& p, const float* rows, int ld, int col)
 {
     const float qa = rows[(size_t)p.a * ld + col];
     if (p.a == p.b) return qa;
@@ -61,10 +57,10 @@ TOKEN_PROSODY_HD inline float param(const Pick& p, const float* rows, int ld, in
     return fmaf(p.w, qb - qa, qa);
 }
 
-TOKEN_PROSODY_HD inline float apply(float gain, float x, float offset) { return fmaf(gain, x, offset); }
+RULE_HD inline float apply(float gain, float x, float offset) { return fmaf(gain, x, offset); }
 
 // a predicted duration under a token's scale and, has_utt, its utterance's (two roundings)
-TOKEN_PROSODY_HD inline float scale_duration(float duration, float token_scale, bool has_utt, float utt_scale)
+RULE_HD inline float scale_duration(float duration, float token_scale, bool has_utt, float utt_scale)
 {
     float v = duration * token_scale;
     if (has_utt) v = v * utt_scale;

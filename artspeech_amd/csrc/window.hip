@@ -15,6 +15,7 @@
 #include "common.h"
 #include "artspeech_hip.h"
 #include "window_rule.h"
+#include "packed_streams.h"
 #include <algorithm>
 
 #define AS_FILE_CLS AS_CLS_OTHER
@@ -97,17 +98,6 @@ window_gather_kernel(const Geo g, const float* __restrict__ mel, int ld_mel, int
     }
 }
 
-// one sample to wherever it goes
-__device__ __forceinline__ void put(float v, size_t j, float* __restrict__ wav, short* __restrict__ pcm, unsigned* status)
-{
-    if (wav) wav[j] = v;
-    if (pcm) {
-        bool nan;
-        pcm[j] = (short)as_pcm16(v, &nan);
-        if (nan) as_status_raise(status, AS_STATUS_F16_RANGE);
-    }
-}
-
 // zeros over [a, e) of wav and / or pcm by the workgroups of the filler's grid columns (column `col` of `cols`)
 __device__ void zero_fill(float* __restrict__ wav, short* __restrict__ pcm, long long a, long long e, int col, int cols)
 {
@@ -183,7 +173,7 @@ window_stitch_kernel(const Geo g, int hop, const float* __restrict__ wwav, int l
     // the scalar head and tail (everything, where the three sides sit differently inside their groups of four)
     for (int i = blockIdx.y * THREADS + t; i < head + (n - tail0); i += gridDim.y * THREADS) {
         const int j = i < head ? i : tail0 + (i - head);
-        put(src[j], j, dw, dp, status);
+        packed_streams::put(src[j], j, dw, dp, status);
     }
 }
 

@@ -25,12 +25,7 @@
 #include <cstdint>
 
 #include "artspeech_hip.h"
-
-#if defined(__HIPCC__)
-#define WINDOW_HD __host__ __device__
-#else
-#define WINDOW_HD
-#endif
+#include "rule_math.h"
 
 // the receptive-field radius in units of 1 / hop of a frame (samples at the output rate), from the configuration alone; *hop_out: hop.
 // -1: a configuration outside the struct's own limits (the caller checks what as_vocoder_create checks)
@@ -80,9 +75,9 @@ struct Win {                    // a round's window of one utterance, in mel fra
     int32_t s0, s1, skip, count;
 };
 
-WINDOW_HD inline long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : v > hi ? hi : v; }
+RULE_HD inline long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : v > hi ? hi : v; }
 
-WINDOW_HD inline Utt utterance(const int32_t* off, int b, int B, int mult, int cap, int max_len)
+RULE_HD inline Utt utterance(const int32_t* off, int b, int B, int mult, int cap, int max_len)
 {
     const long long o = clampll((long long)off[b] * mult, 0, cap);
     long long e = clampll((long long)off[b + 1] * mult, 0, cap);
@@ -95,15 +90,15 @@ WINDOW_HD inline Utt utterance(const int32_t* off, int b, int B, int mult, int c
     return u;
 }
 // the laid-out frames of the whole batch: where the filler starts
-WINDOW_HD inline int32_t total(const int32_t* off, int B, int mult, int cap)
+RULE_HD inline int32_t total(const int32_t* off, int B, int mult, int cap)
 {
     const long long o = clampll((long long)off[B - 1] * mult, 0, cap), e = clampll((long long)off[B] * mult, 0, cap);
     return (int32_t)(e < o ? o : e);
 }
 
-WINDOW_HD inline int n_rounds(int max_len, int core) { return max_len <= 0 ? 0 : (int)(((long long)max_len + core - 1) / core); }
+RULE_HD inline int n_rounds(int max_len, int core) { return max_len <= 0 ? 0 : (int)(((long long)max_len + core - 1) / core); }
 
-WINDOW_HD inline Win window(int n, int w, int core, int halo)
+RULE_HD inline Win window(int n, int w, int core, int halo)
 {
     const long long c0 = (long long)w * core;
     if (c0 >= n) return Win{n, n, 0, 0};
