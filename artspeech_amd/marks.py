@@ -14,7 +14,7 @@ from fractions import Fraction
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, stage
 
 TRACK_NAMES = ("F0", "energy") + tuple(f"EMA{i}" for i in range(10))
 
@@ -61,7 +61,7 @@ class Marker:
             if not 1 <= v <= top:
                 raise ValueError(f"Marker: {name} = {v} lies outside [1, {top}]")
         self.rate, self.fps, self.physical = int(rate), Fraction(num, den), bool(physical)
-        self._ws = {}                   # (device index, B, n_tokens) -> workspace tensor: the same one at every call, as a captured graph needs
+        self._ws = stage.Workspaces()   # keyed by (B, n_tokens)
         self._affine = {}
 
     def anim_cap(self, samples, G=1):
@@ -77,15 +77,24 @@ class Marker:
             self._affine[key] = (torch.from_numpy(s).to(dev), torch.from_numpy(o).to(dev))
         return self._affine[key]
 
-    def _workspace(self, dev, B, n_tokens):
-        key = (dev.index, B, n_tokens)
-        ws = self._ws.get(key)
-        if ws is None:
-            n = _lib.lib().as_marks_workspace_bytes(B, n_tokens, ctypes.byref(self.cfg))
-            if n == 0:
-                raise ValueError("Marker: B must be at least 1")
-            ws = self._ws[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-        return ws
+    def _fill(self, r, what, tok_off, dur_i, frame_off, tracks=None, anim_cap=0, piece=None, groups=None, out_off=None, scale=None, offset=None,
+              marks=True):
+        """The one as_marks_io of forward_packed and host, under the array rule r (stage.Device / stage.Host) -> (io, B, n_tokens, dict(marks,
+        tracks, active, anim_off) as r allocated them).  tracks: (F0, N, EMA, ld_pred) as the caller checked them, with anim_cap; piece, groups,
+        out_off, scale and offset are taken as the caller made them."""
+        tok_off, dur_i, frame_off = (r.need(a, stage.I32, what, name) for name, a in (("tok_off", tok_off), ("dur_i", dur_i), ("frame_off", frame_off)))
+        B, n_tokens = r.count(frame_off) - 1, r.count(dur_i)
+        G = B if piece is None else r.count(out_off) - 1
+        res = dict(marks=r.empty((max(n_tokens, 1), 2), stage.I32) if marks else None, tracks=None, active=None, anim_off=r.empty(G + 1, stage.I32))
+        io = _lib.MarksIO(tok_off=r.at(tok_off), dur_i=r.at(dur_i), frame_off=r.at(frame_off), scale=r.at(scale), offset=r.at(offset),
+                          marks=r.at(res["marks"]), anim_off=r.at(res["anim_off"]))
+        if tracks is not None:
+            res["tracks"], res["active"] = r.empty((12, anim_cap), stage.F32), r.empty(anim_cap, stage.U8)
+            io.F0, io.N, io.EMA, io.ld_pred = r.at(tracks[0]), r.at(tracks[1]), r.at(tracks[2]), tracks[3]
+            io.tracks, io.ld_tracks, io.anim_cap, io.active = r.at(res["tracks"]), anim_cap, anim_cap, r.at(res["active"])
+        if piece is not None:
+            io.piece, io.G, io.out_off, io.group_off = r.at(piece), G, r.at(out_off), r.at(groups)
+        return io, B, n_tokens, res
 
     def forward_packed(self, tok_off, dur_i, frame_off, F0=None, N=None, EMA=None, piece=None, groups=None, out_off=None, anim_cap=None,
                        scale=None, offset=None, marks=True):
@@ -95,43 +104,28 @@ class Marker:
         from Joiner.forward_packed, or none of them: every utterance is a stream of its own.  -> dict(marks int32 [n_tokens][2] or None,
         tracks fp32 [12][anim_cap] or None, active uint8 [anim_cap] or None, anim_off int32 [G + 1]).  More frames than anim_cap, or
         inconsistent offsets: the AS_STATUS_CAPACITY bit (as_device_status)."""
-        if not torch.cuda.is_available():
-            raise _lib.HipLibraryError("the HIP path needs a GPU: torch.cuda.is_available() is False (no CPU fallback)")
-        for name, t in (("tok_off", tok_off), ("dur_i", dur_i), ("frame_off", frame_off)):
-            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"forward_packed: {name} must be a contiguous int32 tensor on the GPU")
-        dev = frame_off.device
-        B, n_tokens = frame_off.numel() - 1, dur_i.numel()
-        want_tracks = F0 is not None
-        if want_tracks and (anim_cap is None or int(anim_cap) < 1):
-            raise ValueError("forward_packed: tracks need anim_cap (Marker.anim_cap)")
+        dev = stage.device(frame_off.device)    # (the filler refuses a frame_off that is not on a GPU)
+        tracks = None
+        if F0 is not None:
+            if anim_cap is None or int(anim_cap) < 1:
+                raise ValueError("forward_packed: tracks need anim_cap (Marker.anim_cap)")
+            for t in (F0, N, EMA):
+                if t.dtype != torch.float32 or t.stride(-1) != 1 or t.shape[-1] != F0.shape[-1]:
+                    raise ValueError("forward_packed: F0, N and EMA are fp32 rows of one width")
+            if not EMA.is_contiguous():
+                raise ValueError("forward_packed: EMA must be contiguous [10][ld]")
+            tracks = (F0, N, EMA, int(F0.shape[-1]))
+        if tracks is None or scale is None:     # (physical units go with tracks, and scale with offset)
+            scale = offset = None
         if piece is not None and out_off is None:
             raise ValueError("forward_packed: piece goes with the out_off of the same join")
-        G = B if piece is None else out_off.numel() - 1
+        io, B, n_tokens, res = self._fill(stage.Device(dev), "forward_packed", tok_off, dur_i, frame_off, tracks, int(anim_cap or 0), piece, groups,
+                                          out_off, scale, offset, marks)
+        if piece is not None:
+            res["_keep"] = (piece, out_off, groups)
         with torch.cuda.device(dev):
-            io = _lib.MarksIO(tok_off=_lib.ptr(tok_off), dur_i=_lib.ptr(dur_i), frame_off=_lib.ptr(frame_off))
-            res = dict(marks=None, tracks=None, active=None, anim_off=torch.empty(G + 1, dtype=torch.int32, device=dev))
-            io.anim_off = _lib.ptr(res["anim_off"])
-            if marks:
-                res["marks"] = torch.empty((max(n_tokens, 1), 2), dtype=torch.int32, device=dev)
-                io.marks = _lib.ptr(res["marks"])
-            if want_tracks:
-                cap = int(anim_cap)
-                for t in (F0, N, EMA):
-                    if t.dtype != torch.float32 or t.stride(-1) != 1 or t.shape[-1] != F0.shape[-1]:
-                        raise ValueError("forward_packed: F0, N and EMA are fp32 rows of one width")
-                if not EMA.is_contiguous():
-                    raise ValueError("forward_packed: EMA must be contiguous [10][ld]")
-                res["tracks"] = torch.empty((12, cap), dtype=torch.float32, device=dev)
-                res["active"] = torch.empty(cap, dtype=torch.uint8, device=dev)
-                io.F0, io.N, io.EMA, io.ld_pred = _lib.ptr(F0), _lib.ptr(N), _lib.ptr(EMA), int(F0.shape[-1])
-                io.tracks, io.ld_tracks, io.anim_cap, io.active = _lib.ptr(res["tracks"]), cap, cap, _lib.ptr(res["active"])
-                if scale is not None:
-                    io.scale, io.offset = _lib.ptr(scale), _lib.ptr(offset)
-            if piece is not None:
-                io.piece, io.G, io.out_off, io.group_off = _lib.ptr(piece), G, _lib.ptr(out_off), _lib.ptr(groups)
-                res["_keep"] = (piece, out_off, groups)
-            ws = self._workspace(dev, B, n_tokens)
+            ws = self._ws.get(dev, (B, n_tokens), lambda: _lib.lib().as_marks_workspace_bytes(B, n_tokens, ctypes.byref(self.cfg)),
+                              "Marker: B must be at least 1")
             _lib.check(_lib.lib().as_marks_f32(ctypes.byref(self.cfg), B, n_tokens, ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()),
                        "as_marks_f32")
         return res
@@ -140,35 +134,27 @@ class Marker:
              offset=None):
         """the same rule on host arrays (as_marks_host; no GPU): -> dict(marks, tracks, active, anim_off) as numpy arrays, tracks and
         active cut to anim_off[-1].  anim_cap None: what anim_cap() says for the streams at hand."""
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
-        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-        tok_off, dur_i, frame_off, piece, groups, out_off = (i32(a) for a in (tok_off, dur_i, frame_off, piece, groups, out_off))
-        F0, N, EMA, scale, offset = (f32(a) for a in (F0, N, EMA, scale, offset))
-        B, n_tokens = frame_off.size - 1, dur_i.size
-        G = B if piece is None else out_off.size - 1
-        at = lambda a: None if a is None else a.ctypes.data
-        io = _lib.MarksIO(tok_off=at(tok_off), dur_i=at(dur_i), frame_off=at(frame_off), piece=at(piece), G=G, group_off=at(groups), out_off=at(out_off),
-                          scale=at(scale), offset=at(offset))
-        marks = np.full((max(n_tokens, 1), 2), -1, np.int32)
-        anim_off = np.empty(G + 1, np.int32)
-        io.marks, io.anim_off = at(marks), at(anim_off)
-        tracks = active = None
+        r = stage.Host()
+        frame_off, piece, groups, out_off = (r.need(a, stage.I32) for a in (frame_off, piece, groups, out_off))
+        F0, N, EMA, scale, offset = (r.need(a, stage.F32) for a in (F0, N, EMA, scale, offset))
+        tracks = None
         exact = anim_cap is None
         if F0 is not None:
             if exact:
                 c = self.cfg
                 total = int(out_off[-1]) if piece is not None else sum(-((-c.hop * 2 * int(f) * c.L) // c.M) for f in np.diff(frame_off))
-                anim_cap = self.anim_cap(total, G)
-            ld = F0.reshape(-1).size
-            if N.reshape(-1).size != ld or EMA.size != 10 * ld:
+                anim_cap = self.anim_cap(total, frame_off.size - 1 if piece is None else out_off.size - 1)
+            tracks = (F0, N, EMA, F0.size)
+            if N.size != F0.size or EMA.size != 10 * F0.size:
                 raise ValueError("Marker.host: F0 [ld], N [ld] and EMA [10][ld] of one width")
-            tracks, active = np.empty((12, anim_cap), np.float32), np.empty(anim_cap, np.uint8)
-            io.F0, io.N, io.EMA, io.ld_pred = at(F0), at(N), at(EMA), ld
-            io.tracks, io.ld_tracks, io.anim_cap, io.active = at(tracks), anim_cap, anim_cap, at(active)
+        io, B, n_tokens, res = self._fill(r, "host", tok_off, dur_i, frame_off, tracks, anim_cap, piece, groups, out_off, scale, offset)
+        res["marks"].fill(-1)
         _lib.check(_lib.lib().as_marks_host(ctypes.byref(self.cfg), B, n_tokens, ctypes.byref(io)), "as_marks_host")
         if tracks is not None and exact:
-            tracks, active = tracks[:, : anim_off[-1]], active[: anim_off[-1]]
-        return dict(marks=marks[:n_tokens], tracks=tracks, active=active, anim_off=anim_off)
+            n = res["anim_off"][-1]
+            res["tracks"], res["active"] = res["tracks"][:, :n], res["active"][:n]
+        res["marks"] = res["marks"][:n_tokens]
+        return res
 
 
 def kept_symbols(cleaner, text):

@@ -13,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, stage
 
 LUFS_OFFSET = -0.691            # BS.1770: loudness = -0.691 + 10 log10(power)
 ABS_GATE_LUFS = -70.0
@@ -99,80 +99,50 @@ class Master:
         _lib.check(_lib.lib().as_master_create(ctypes.byref(self.cfg), ctypes.byref(h)), "as_master_create")
         self._h = h
         self.device = None if device is None else torch.device(device)
-        self._ws = {}                   # (device index, G, in_cap) -> workspace tensor: the same one at every call, as a captured graph needs
+        self._ws = stage.Workspaces()   # keyed by (G, in_cap)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:      # (None: the interpreter is shutting down)
             _lib.lib().as_master_destroy(h)
 
-    def _dev(self):
-        if not torch.cuda.is_available():
-            raise _lib.HipLibraryError("the HIP path needs a GPU: torch.cuda.is_available() is False (no CPU fallback)")
-        if self.device is None or self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
+    def _fill(self, r, what, x, off, pcm=False, wav=True, measure=False):
+        """The one as_master_io of forward_packed, measure and host, under the array rule r (stage.Device / stage.Host) -> (io, G, n, the
+        outputs y, p16, report as r allocated them); n: the samples of x.  measure: the report alone."""
+        x, off = r.need(x, stage.F32, what, "x", vector=True), r.need(off, stage.I32, what, "off", vector=True)
+        G, n = r.count(off) - 1, r.count(x)
+        y, p16 = (None, None) if measure else stage.samples(r, n, wav, pcm, what)
+        rep = r.empty((G, 6), stage.F32)
+        return _lib.MasterIO(in_off=r.at(off), in_cap=n, x=r.at(x), y=r.at(y), pcm=r.at(p16), report=r.at(rep)), G, n, (y, p16, rep)
 
-    def _workspace(self, dev, G, in_cap):
-        key = (dev.index, G, in_cap)
-        ws = self._ws.get(key)
-        if ws is None:
-            n = _lib.lib().as_master_workspace_bytes(G, in_cap, ctypes.byref(self.cfg))
-            if n == 0:
-                raise ValueError("Master: 1 .. 65535 streams and 1 .. 2^30 samples")
-            ws = self._ws[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-        return ws
-
-    @staticmethod
-    def _check(x, off, what):
-        if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or x.dim() != 1:
-            raise ValueError(f"{what}: x must be a contiguous float32 vector on the GPU")
-        if off.dtype != torch.int32 or not off.is_cuda or not off.is_contiguous() or off.dim() != 1:
-            raise ValueError(f"{what}: off must be a contiguous int32 vector on the GPU")
+    def _run(self, fn, what, x, off, **kw):
+        """as_master_f32 / as_master_measure_f32 on the current stream"""
+        dev = self.device = stage.device(self.device)
+        with torch.cuda.device(dev):
+            io, G, n, out = self._fill(stage.Device(dev), what, x, off, **kw)
+            ws = self._ws.get(dev, (G, n), lambda: _lib.lib().as_master_workspace_bytes(G, n, ctypes.byref(self.cfg)),
+                              "Master: 1 .. 65535 streams and 1 .. 2^30 samples")
+            _lib.check(getattr(_lib.lib(), fn)(self._h, G, ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()), fn)
+        return out
 
     def forward_packed(self, x, off, pcm=False, wav=True):
         """x: fp32 device samples [in_cap], stream g = x[off[g] : off[g + 1]] with off a DEVICE int32 [G + 1] (a joiner's or resampler's
         out_off, a vocoder's sample_off) -> (y fp32 [in_cap] or None, pcm int16 [in_cap] or None, Report) at the same offsets.  At most
         five launches on the current stream; nothing is read, uploaded or synchronised: the call can be captured with whatever produced x
         and off.  Samples in [off[G], in_cap) are 0; off[G] > in_cap raises the AS_STATUS_CAPACITY bit (as_device_status)."""
-        if not (wav or pcm):
-            raise ValueError("forward_packed: at least one of wav and pcm")
-        dev = self._dev()
-        self._check(x, off, "forward_packed")
-        G = off.numel() - 1
-        with torch.cuda.device(dev):
-            y = torch.empty(x.numel(), dtype=torch.float32, device=dev) if wav else None
-            p16 = torch.empty(x.numel(), dtype=torch.int16, device=dev) if pcm else None
-            rep = torch.empty(G, 6, dtype=torch.float32, device=dev)
-            ws = self._workspace(dev, G, x.numel())
-            io = _lib.MasterIO(in_off=_lib.ptr(off), in_cap=x.numel(), x=_lib.ptr(x), y=_lib.ptr(y), pcm=_lib.ptr(p16), report=_lib.ptr(rep))
-            _lib.check(_lib.lib().as_master_f32(self._h, G, ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()), "as_master_f32")
+        y, p16, rep = self._run("as_master_f32", "forward_packed", x, off, pcm=pcm, wav=wav)
         return y, p16, Report(rep)
 
     def measure(self, x, off):
         """the meter alone (as_master_measure_f32) -> Report on the device: the loudness of every stream (whether or not this Master has a
         target), the gain that WOULD be applied, the true peak behind that gain; floor is 1"""
-        dev = self._dev()
-        self._check(x, off, "measure")
-        G = off.numel() - 1
-        with torch.cuda.device(dev):
-            rep = torch.empty(G, 6, dtype=torch.float32, device=dev)
-            ws = self._workspace(dev, G, x.numel())
-            io = _lib.MasterIO(in_off=_lib.ptr(off), in_cap=x.numel(), x=_lib.ptr(x), report=_lib.ptr(rep))
-            _lib.check(_lib.lib().as_master_measure_f32(self._h, G, ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()), "as_master_measure_f32")
-        return Report(rep)
+        return Report(self._run("as_master_measure_f32", "measure", x, off, measure=True)[2])
 
     def host(self, x, off, pcm=False, measure=False):
         """the same rule on host arrays (as_master_host; no GPU): -> (y, pcm or None, Report) as numpy arrays; measure: (None, None, Report)"""
-        x = np.ascontiguousarray(x, np.float32)
-        off = np.ascontiguousarray(off, np.int32)
-        G = off.size - 1
-        xs = x if x.size else np.zeros(1, np.float32)
-        y = None if measure else np.empty(xs.size, np.float32)
-        p16 = np.empty(xs.size, np.int16) if pcm and not measure else None
-        rep = np.empty((G, 6), np.float32)
-        at = lambda a: None if a is None else a.ctypes.data
-        io = _lib.MasterIO(in_off=at(off), in_cap=xs.size, x=at(xs), y=at(y), pcm=at(p16), report=at(rep))
+        r = stage.Host()
+        x = r.need(x, stage.F32)
+        io, G, _, (y, p16, rep) = self._fill(r, "host", x if x.size else np.zeros(1, np.float32), off, pcm, measure=measure)
         rc = _lib.lib().as_master_host(ctypes.byref(self.cfg), G, ctypes.byref(io))
         if rc != _lib.AS_EDEVICE:               # (AS_EDEVICE: a NaN went to pcm -- it stored 0, as on the device)
             _lib.check(rc, "as_master_host")

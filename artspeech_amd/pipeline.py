@@ -33,7 +33,7 @@ import math
 import numpy as np
 import torch
 
-from . import models
+from . import models, stage
 from .fit import Fit
 from .text import TextCleaner
 from .weights import DEFAULT_STATS, load_distribution
@@ -452,7 +452,7 @@ class ArtSpeech:
             if join is not None:
                 G = 1 if groups is None else len(groups) - 1
                 if groups is not None:
-                    groups = join._i32(groups, dev, G + 1, "groups")                   # (the joiner and the marker read ONE device copy)
+                    groups = stage.Device(dev).values_i32(groups, G + 1, "forward_packed", "groups")  # (the joiner and the marker read ONE device copy)
                 if join_cap is None:                                                    # what always suffices: every sample kept, every gap in place
                     if torch.is_tensor(gaps):
                         raise ValueError("gaps on the device: name join_cap, the samples of room for the joined streams")

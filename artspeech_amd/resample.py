@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, stage
 
 _HANDLES = {}                   # (device index, in_rate, out_rate) -> as_resampler*
 
@@ -36,7 +36,7 @@ def design(in_rate, out_rate, taps=False):
     if not taps:
         return L.value, M.value, H.value
     h = np.empty(2 * H.value + 1, np.float32)
-    _lib.check(lib.as_resample_design_host(int(in_rate), int(out_rate), None, None, None, h.ctypes.data, h.size), "as_resample_design_host")
+    _lib.check(lib.as_resample_design_host(int(in_rate), int(out_rate), None, None, None, stage.Host.at(h), h.size), "as_resample_design_host")
     return L.value, M.value, H.value, h
 
 
@@ -50,30 +50,19 @@ class Resampler:
         """samples an utterance of n samples becomes: ceil(n L / M)"""
         return -((-int(n) * self.L) // self.M) if n > 0 else 0
 
-    def _dev(self):
-        if not torch.cuda.is_available():
-            raise _lib.HipLibraryError("the HIP path needs a GPU: torch.cuda.is_available() is False (no CPU fallback)")
-        if self.device is None or self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
-
     def forward_packed(self, x, in_off, out_cap, pcm=False, wav=True):
         """x: fp32 device samples [in_cap] (or [1][in_cap]), utterance b = x[in_off[b] : in_off[b + 1]] with in_off a DEVICE int32 [B + 1]
         (in_off[0] = 0) -> (y fp32 [out_cap] or None, pcm int16 [out_cap] or None, out_off device int32 [B + 1]).  One launch on the current
         stream; no host value is read and nothing synchronises: the call can be captured with whatever produced x and in_off.  Samples in
         [out_off[B], out_cap) are 0; more output than out_cap raises the AS_STATUS_CAPACITY bit (as_device_status)."""
-        if not (wav or pcm):
-            raise ValueError("forward_packed: at least one of wav and pcm")
-        dev = self._dev()
-        if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
-            raise ValueError("forward_packed: x must be a contiguous float32 tensor on the GPU")
-        if in_off.dtype != torch.int32 or not in_off.is_cuda or not in_off.is_contiguous() or in_off.dim() != 1:
-            raise ValueError("forward_packed: in_off must be a contiguous int32 vector on the GPU")
+        dev = self.device = stage.device(self.device)
+        r = stage.Device(dev)
+        r.need(x, stage.F32, "forward_packed", "x")
+        r.need(in_off, stage.I32, "forward_packed", "in_off", vector=True)
         B, out_cap = in_off.numel() - 1, int(out_cap)
         with torch.cuda.device(dev):
-            y = torch.empty(out_cap, dtype=torch.float32, device=dev) if wav else None
-            p16 = torch.empty(out_cap, dtype=torch.int16, device=dev) if pcm else None
-            out_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+            y, p16 = stage.samples(r, out_cap, wav, pcm)
+            out_off = r.empty(B + 1, stage.I32)
             _lib.check(_lib.lib().as_resample_f32(_handle(dev, self.in_rate, self.out_rate), B, _lib.ptr(in_off), x.numel(), _lib.ptr(x), out_cap,
                                                   _lib.ptr(y), _lib.ptr(p16), _lib.ptr(out_off), _lib.stream()), "as_resample_f32")
         return y, p16, out_off
@@ -81,7 +70,7 @@ class Resampler:
     def __call__(self, wave, pcm=False):
         """One wave (1-D tensor / array) or a list of them, lengths known here -> the resampled wave(s) on the device (pcm=True: int16).
         The offsets are uploaded by this call."""
-        dev = self._dev()
+        dev = self.device = stage.device(self.device)
         single = not isinstance(wave, (list, tuple))
         waves = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in ([wave] if single else wave)]
         lens = [int(w.numel()) for w in waves]

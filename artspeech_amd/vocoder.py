@@ -19,7 +19,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, stage
 from .ops import ACT_LRELU, ACT_NONE, ACT_TANH, layout, taps_1d
 from .synth import hash_tensor
 from .weights import fold_state_dict
@@ -150,28 +150,47 @@ class Generator:
         self.halo = L.as_vocoder_halo(voc)                 # mel frames a window needs on either side (csrc/window_rule.h)
         return self
 
-    def _forward_runtime(self, mel_p, lay, wav=True, pcm=False):
-        """as_vocoder_forward on the current stream.  The workspace is kept and only ever grows: a graph captured from this generator
-        stays valid as long as no larger geometry has been run since."""
+    def _library_call(self, what, fn, slot, plan, mel_p, wav, pcm, lay=None, off=None, mult=0, cap=0, max_len=0, out=None):
+        """The one call into the library's generator behind forward_packed (runtime=True), forward_packed_cap and forward_packed_windowed:
+        the checks, as_vocoder_io (and as_vocoder_cap), the outputs (or out=) and the workspace -> (wav, sample_off or None, pcm).
+        fn: the library's function; slot: the attribute that keeps ITS workspace, which only ever grows; plan(B), asked after the checks ->
+        (the bytes fn needs, the error text for 0 bytes, the geometry fn takes in front of its io -- None: the as_vocoder_cap of off, mult,
+        cap, max_len -- and what it takes between the io and the workspace).  lay: host widths (as_vocoder_forward) instead of a capacity."""
+        if not self.runtime:
+            raise ValueError(f"{what} needs Generator(runtime=True)")
         if self._voc is None:
             raise RuntimeError("no weights loaded: call load_state_dict first")
         if not (wav or pcm):
-            raise ValueError("forward_packed: at least one of wav and pcm")
+            raise ValueError(f"{what}: at least one of wav and pcm")
+        r = stage.Device(self.device)
+        B = lay.B if lay is not None else r.need(off, stage.I32, what, "off").numel() - 1
+        with torch.cuda.device(self.device):
+            need, bad, geometry, extra = plan(B)
+            if need == 0:
+                raise _lib.HipLibraryError(bad)
+            ws = getattr(self, slot)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                setattr(self, slot, ws)
+            if out is not None:
+                out_w, sample_off, out_p = out
+            else:
+                out_w, out_p = stage.samples(r, cap * self.hop if lay is None else max(lay.N * self.hop, 1), wav, pcm, what, lead=(1,))
+                sample_off = r.empty(B + 1, stage.I32) if lay is None else None
+            io = _lib.VocoderIO(mel=ops._p(mel_p), ld_mel=ops._ld(mel_p), wav=ops._p(out_w), pcm=ops._p(out_p))
+            if geometry is None:
+                geometry = ctypes.byref(_lib.VocoderCap(off=off.data_ptr(), mult=int(mult), cap=cap, max_len=max_len, sample_off=sample_off.data_ptr()))
+            _lib.check(fn(self._voc, self._plan, B, geometry, ctypes.byref(io), *extra, ws.data_ptr(), ws.numel(), _lib.stream()), fn.__name__)
+        return out_w, sample_off, out_p
+
+    def _forward_runtime(self, mel_p, lay, wav=True, pcm=False):
+        """as_vocoder_forward on the current stream.  The workspace is kept and only ever grows: a graph captured from this generator
+        stays valid as long as no larger geometry has been run since."""
         L = _lib.lib()
-        B = lay.B
-        lens = (ctypes.c_int32 * B)(*lay.widths_host)
-        need = L.as_vocoder_workspace_bytes(self._voc, self._plan, B, lens)
-        if need == 0:
-            raise _lib.HipLibraryError("as_vocoder_workspace_bytes: invalid geometry (an utterance beyond AS_META_MAX_W samples?)")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        n = lay.N * self.hop
-        io = _lib.VocoderIO()
-        out_w = torch.empty((1, max(n, 1)), dtype=torch.float32, device=self.device) if wav else None
-        out_p = torch.empty(max(n, 1), dtype=torch.int16, device=self.device) if pcm else None
-        io.mel, io.ld_mel, io.wav, io.pcm = ops._p(mel_p), ops._ld(mel_p), ops._p(out_w), ops._p(out_p)
-        _lib.check(L.as_vocoder_forward(self._voc, self._plan, B, lens, ctypes.byref(io), self._ws.data_ptr(), self._ws.numel(), _lib.stream()),
-                   "as_vocoder_forward")
+        lens = (ctypes.c_int32 * lay.B)(*lay.widths_host)
+        bad = "as_vocoder_workspace_bytes: invalid geometry (an utterance beyond AS_META_MAX_W samples?)"
+        out_w, _, out_p = self._library_call("forward_packed", L.as_vocoder_forward, "_ws", lambda B: (
+            L.as_vocoder_workspace_bytes(self._voc, self._plan, B, lens), bad, lens, ()), mel_p, wav, pcm, lay=lay)
         lay_w = lay.scaled(self.hop)
         return (out_w, lay_w, out_p) if pcm else (out_w, lay_w)
 
@@ -182,32 +201,12 @@ class Generator:
         read, nothing synchronises: the call can be captured with whatever produced `off` and `mel_p`.  Returns (wav [1][300 cap] or None,
         sample_off device int32 [B + 1]) and, with pcm=True, the int16 samples [300 cap]: utterance b is [sample_off[b], sample_off[b + 1]),
         the samples behind the last utterance are 0.  More frames than room raises the AS_STATUS_CAPACITY bit (as_device_status)."""
-        if not self.runtime:
-            raise ValueError("forward_packed_cap needs Generator(runtime=True)")
-        if self._voc is None:
-            raise RuntimeError("no weights loaded: call load_state_dict first")
-        if not (wav or pcm):
-            raise ValueError("forward_packed_cap: at least one of wav and pcm")
-        if off.dtype != torch.int32 or not off.is_cuda or not off.is_contiguous():
-            raise ValueError("forward_packed_cap: off must be a contiguous int32 tensor on the GPU")
         L = _lib.lib()
-        B, cap, max_len = off.numel() - 1, int(cap), int(max_len or 0)
-        with torch.cuda.device(self.device):
-            need = L.as_vocoder_cap_workspace_bytes(self._voc, self._plan, B, cap, max_len)
-            if need == 0:
-                raise _lib.HipLibraryError("as_vocoder_cap_workspace_bytes: invalid capacity (max_len > cap, or an utterance beyond AS_META_MAX_W samples?)")
-            if self._ws_cap is None or self._ws_cap.numel() < need:
-                self._ws_cap = torch.empty(need, dtype=torch.uint8, device=self.device)
-            n = cap * self.hop
-            out_w = torch.empty((1, n), dtype=torch.float32, device=self.device) if wav else None
-            out_p = torch.empty(n, dtype=torch.int16, device=self.device) if pcm else None
-            sample_off = torch.empty(B + 1, dtype=torch.int32, device=self.device)
-            io, g = _lib.VocoderIO(), _lib.VocoderCap()
-            io.mel, io.ld_mel, io.wav, io.pcm = ops._p(mel_p), ops._ld(mel_p), ops._p(out_w), ops._p(out_p)
-            g.off, g.mult, g.cap, g.max_len, g.sample_off = off.data_ptr(), int(mult), cap, max_len, sample_off.data_ptr()
-            _lib.check(L.as_vocoder_forward_cap(self._voc, self._plan, B, ctypes.byref(g), ctypes.byref(io), self._ws_cap.data_ptr(),
-                                                self._ws_cap.numel(), _lib.stream()), "as_vocoder_forward_cap")
-        return (out_w, sample_off, out_p) if pcm else (out_w, sample_off)
+        cap, max_len = int(cap), int(max_len or 0)
+        bad = "as_vocoder_cap_workspace_bytes: invalid capacity (max_len > cap, or an utterance beyond AS_META_MAX_W samples?)"
+        res = self._library_call("forward_packed_cap", L.as_vocoder_forward_cap, "_ws_cap", lambda B: (
+            L.as_vocoder_cap_workspace_bytes(self._voc, self._plan, B, cap, max_len), bad, None, ()), mel_p, wav, pcm, None, off, mult, cap, max_len)
+        return res if pcm else res[:2]
 
     def forward_packed_windowed(self, mel_p, off, mult, cap, core, max_len=None, halo=None, pcm=False, wav=True, rounds=None, out=None):
         """forward_packed_cap in rounds of `core` mel frames per utterance (as_vocoder_forward_windowed; csrc/window_rule.h): the same
@@ -217,39 +216,20 @@ class Generator:
         grows: a graph captured from this call stays valid as long as no larger (B, core, halo) has been run since.
         rounds = (round0, n): only those rounds (n = 0: every round from round0 on); round 0 also writes the filler's zeros and sample_off.
         out = (wav, sample_off, pcm) of an earlier call: the buffers to write into (rounds in pieces)."""
-        if not self.runtime:
-            raise ValueError("forward_packed_windowed needs Generator(runtime=True)")
-        if self._voc is None:
-            raise RuntimeError("no weights loaded: call load_state_dict first")
-        if not (wav or pcm):
-            raise ValueError("forward_packed_windowed: at least one of wav and pcm")
-        if off.dtype != torch.int32 or not off.is_cuda or not off.is_contiguous():
-            raise ValueError("forward_packed_windowed: off must be a contiguous int32 tensor on the GPU")
         L = _lib.lib()
-        B, cap, max_len = off.numel() - 1, int(cap), int(max_len or 0)
-        wc = _lib.WindowCfg(int(core), -1 if halo is None else int(halo), self.hop)
-        round0, n_rounds = (0, 0) if rounds is None else (int(rounds[0]), int(rounds[1]))
-        if round0 < 0 or n_rounds < 0:
-            raise ValueError("forward_packed_windowed: rounds = (first round >= 0, count >= 0)")
-        with torch.cuda.device(self.device):
-            need = L.as_vocoder_windowed_workspace_bytes(self._voc, self._plan, B, ctypes.byref(wc))
-            if need == 0:
-                raise _lib.HipLibraryError("as_vocoder_windowed_workspace_bytes: invalid window (core < 1, halo < -1, or a window beyond AS_META_MAX_W samples?)")
-            if self._ws_win is None or self._ws_win.numel() < need:
-                self._ws_win = torch.empty(need, dtype=torch.uint8, device=self.device)
-            n = cap * self.hop
-            if out is not None:
-                out_w, sample_off, out_p = out
-            else:
-                out_w = torch.empty((1, n), dtype=torch.float32, device=self.device) if wav else None
-                out_p = torch.empty(n, dtype=torch.int16, device=self.device) if pcm else None
-                sample_off = torch.empty(B + 1, dtype=torch.int32, device=self.device)
-            io, g = _lib.VocoderIO(), _lib.VocoderCap()
-            io.mel, io.ld_mel, io.wav, io.pcm = ops._p(mel_p), ops._ld(mel_p), ops._p(out_w), ops._p(out_p)
-            g.off, g.mult, g.cap, g.max_len, g.sample_off = off.data_ptr(), int(mult), cap, max_len, sample_off.data_ptr()
-            _lib.check(L.as_vocoder_forward_windowed(self._voc, self._plan, B, ctypes.byref(g), ctypes.byref(io), ctypes.byref(wc), round0, n_rounds,
-                                                     self._ws_win.data_ptr(), self._ws_win.numel(), _lib.stream()), "as_vocoder_forward_windowed")
-        return (out_w, sample_off, out_p) if pcm else (out_w, sample_off)
+
+        def window(B):                              # (after the checks: without weights there is no hop)
+            wc = _lib.WindowCfg(int(core), -1 if halo is None else int(halo), self.hop)
+            round0, n_rounds = (0, 0) if rounds is None else (int(rounds[0]), int(rounds[1]))
+            if round0 < 0 or n_rounds < 0:
+                raise ValueError("forward_packed_windowed: rounds = (first round >= 0, count >= 0)")
+            return (L.as_vocoder_windowed_workspace_bytes(self._voc, self._plan, B, ctypes.byref(wc)),
+                    "as_vocoder_windowed_workspace_bytes: invalid window (core < 1, halo < -1, or a window beyond AS_META_MAX_W samples?)",
+                    None, (ctypes.byref(wc), round0, n_rounds))
+
+        res = self._library_call("forward_packed_windowed", L.as_vocoder_forward_windowed, "_ws_win", window, mel_p, wav, pcm, None, off, mult,
+                                 int(cap), int(max_len or 0), out)
+        return res if pcm else res[:2]
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd, strict=False):
