@@ -101,6 +101,7 @@ _SIGNATURES.update({
     "as_relpos_attention_image_lds_bytes": (c_i, [c_i]),
     "as_bilstm_f32": (c_i, [c_p, c_i, c_p, c_i, c_i, c_p]),
     "as_bilstm_cluster_bytes": (ctypes.c_size_t, [c_i, c_i]),
+    "as_bilstm_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, ctypes.c_size_t]),
     "as_bilstm_cluster_f32": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, ctypes.c_size_t, c_p]),
     "as_interleave_phases_f32": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
     "as_mean3_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p]),

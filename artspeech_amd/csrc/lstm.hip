@@ -18,6 +18,7 @@
 #define AS_FILE_CLS AS_CLS_LSTM
 
 #define NB 2
+#define CL_P 4                                     /* workgroups of a cluster (bilstm_cluster_kernel below) */
 
 // exp and reciprocal via the hardware v_exp_f32 / v_rcp_f32 (1 ulp; ~1e-7 abs on the bounded gate outputs, the test bound is 2e-5).
 // Not __frcp_rn: the correctly rounded reciprocal is a ten-instruction division sequence, five of them on every step's critical path.
@@ -439,12 +440,31 @@ bilstm_quad1_kernel(const LstmJobs jobs, const int* __restrict__ col_off, int B)
     }
 }
 
+// Which kernel a launch takes: the ONE place that decides (as_bilstm_f32 and as_bilstm_cluster_f32 switch on it; host only, so the tests
+// assert that a shape reaches the kernel it is meant for).  has_xchg / xchg_bytes: the exchange buffer as_bilstm_cluster_f32 was given.
+extern "C" int as_bilstm_plan(int n_jobs, int B, int H, int max_len, int has_xchg, size_t xchg_bytes)
+{
+    if (n_jobs <= 0 || n_jobs > AS_MAX_LSTM_JOBS || B < 0 || H <= 0 || (4 * H) % 64 || 4 * H > 1024 || H % 8) return AS_EINVAL;
+    // one utterance per cluster while every cluster fits the chip at once, else two; beyond that (or without an exchange buffer, or
+    // another width, or lengths past the tag's step field) the single-workgroup kernels
+    const long c1 = (long)n_jobs * 2 * B, c2 = (long)n_jobs * 2 * ((B + 1) / 2);
+    const int nbu = c1 * CL_P <= 256 ? 1 : (c2 * CL_P <= 256 ? 2 : 0);
+    const char* mode = getenv("AS_LSTM_CLUSTER");                        // experiments: "0" = never, "1" / "2" = utterances per cluster
+    const int use = mode ? atoi(mode) : nbu;
+    if (H == 256 && has_xchg && B > 0 && (use == 1 || use == 2) && max_len > 0 && max_len < (1 << 17) && (use == 1 ? c1 : c2) * CL_P <= 256 &&
+        xchg_bytes >= as_bilstm_cluster_bytes(n_jobs, B))
+        return use == 1 ? AS_LSTM_PLAN_CLUSTER1 : AS_LSTM_PLAN_CLUSTER2;
+    // one utterance per workgroup while all the recurrences fit the chip together
+    if ((H == 64 || H == 128) && (long)n_jobs * 2 * B <= 512) return AS_LSTM_PLAN_QUAD1;
+    if (H == 16 || H == 32 || H == 64 || H == 128) return AS_LSTM_PLAN_QUAD;
+    return H == 256 ? AS_LSTM_PLAN_BIG : AS_LSTM_PLAN_STREAM;
+}
+
 extern "C" int as_bilstm_f32(const BiLstmJob* jobs_host, int n_jobs, const int32_t* col_off, int B, int H,
                              as_stream_t stream)
 {
-    if (!jobs_host || n_jobs <= 0 || n_jobs > AS_MAX_LSTM_JOBS || !col_off || B < 0 || H <= 0 || (4 * H) % 64 ||
-        4 * H > 1024 || H % 8)
-        return AS_EINVAL;
+    const int plan = as_bilstm_plan(n_jobs, B, H, 0, 0, 0);
+    if (!jobs_host || !col_off || plan < 0) return AS_EINVAL;
     LstmJobs jobs;
     for (int i = 0; i < AS_MAX_LSTM_JOBS; ++i) jobs.j[i] = jobs_host[i < n_jobs ? i : 0];
     for (int i = 0; i < n_jobs; ++i)
@@ -453,21 +473,22 @@ extern "C" int as_bilstm_f32(const BiLstmJob* jobs_host, int n_jobs, const int32
     const size_t smem = sizeof(float) * ((size_t)2 * H * NB + (size_t)4 * H * NB);
     const dim3 grid(as_cdiv(B, NB), 2, n_jobs), block(4 * H);
     AsProfScope prof__(AS_FILE_CLS, 0, 0, (hipStream_t)stream);
-    // one utterance per workgroup while all the recurrences fit the chip together
-    const bool single = (H == 64 || H == 128) && (long)n_jobs * 2 * B <= 512;
-    if (single) {
+    switch (plan) {
+    case AS_LSTM_PLAN_QUAD1: {
         const dim3 g1(B, 2, n_jobs);
         if (H == 64) hipLaunchKernelGGL(bilstm_quad1_kernel<64>, g1, block, 0, (hipStream_t)stream, jobs, col_off, B);
         else hipLaunchKernelGGL(bilstm_quad1_kernel<128>, g1, block, 0, (hipStream_t)stream, jobs, col_off, B);
-        AS_CHECK_LAUNCH();
-        return AS_OK;
+        break;
     }
-    switch (H) {
-    case 16: hipLaunchKernelGGL(bilstm_quad_kernel<16>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
-    case 32: hipLaunchKernelGGL(bilstm_quad_kernel<32>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
-    case 64: hipLaunchKernelGGL(bilstm_quad_kernel<64>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
-    case 128: hipLaunchKernelGGL(bilstm_quad_kernel<128>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
-    case 256: {
+    case AS_LSTM_PLAN_QUAD:
+        switch (H) {
+        case 16: hipLaunchKernelGGL(bilstm_quad_kernel<16>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
+        case 32: hipLaunchKernelGGL(bilstm_quad_kernel<32>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
+        case 64: hipLaunchKernelGGL(bilstm_quad_kernel<64>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
+        default: hipLaunchKernelGGL(bilstm_quad_kernel<128>, grid, block, 0, (hipStream_t)stream, jobs, col_off, B); break;
+        }
+        break;
+    case AS_LSTM_PLAN_BIG: {
         constexpr int KREG = 32, KLDS = 36;
         const size_t sm_big = smem + sizeof(float) * (size_t)KLDS * 1024;
         AS_LDS_OPT_IN((bilstm_big_kernel<256, KREG, KLDS>), (int)sm_big);   // (+ 16 bytes static: 160 KB would be refused)
@@ -501,7 +522,6 @@ extern "C" int as_bilstm_f32(const BiLstmJob* jobs_host, int n_jobs, const int32
 // order, so every poll is bounded (~1 s) and a poll that gives up RAISES AS_STATUS_LSTM_TIMEOUT (as_device_status): the launch still
 // ends, its output is void, and the module entry points return AS_EDEVICE until the status is cleared.
 // ---------------------------------------------------------------------------------------------------
-#define CL_P 4
 #define CL_REGION_WORDS 1032                       /* 1 header word + 2 slots x 256 units x 2 utterances, padded to 8 KB + 64 B */
 static __device__ __forceinline__ float dpp_add8(float v)
 {
@@ -689,20 +709,14 @@ extern "C" int as_bilstm_cluster_f32(const BiLstmJob* jobs_host, int n_jobs, con
 {
     if (!jobs_host || n_jobs <= 0 || n_jobs > AS_MAX_LSTM_JOBS || !col_off || B < 0 || H <= 0) return AS_EINVAL;
     if (B == 0) return AS_OK;
-    // one utterance per cluster while every cluster fits the chip at once, else two; beyond that (or without an exchange buffer, or
-    // another width, or lengths past the tag's step field) the single-workgroup kernels
-    const long c1 = (long)n_jobs * 2 * B, c2 = (long)n_jobs * 2 * ((B + 1) / 2);
-    const int nbu = c1 * CL_P <= 256 ? 1 : (c2 * CL_P <= 256 ? 2 : 0);
-    const char* mode = getenv("AS_LSTM_CLUSTER");                        // experiments: "0" = never, "1" / "2" = utterances per cluster
-    const int use = mode ? atoi(mode) : nbu;
-    if (H != 256 || !xchg || use <= 0 || use > 2 || max_len <= 0 || max_len >= (1 << 17) || (use == 1 ? c1 : c2) * CL_P > 256 ||
-        xchg_bytes < as_bilstm_cluster_bytes(n_jobs, B))
-        return as_bilstm_f32(jobs_host, n_jobs, col_off, B, H, stream);
+    const int plan = as_bilstm_plan(n_jobs, B, H, max_len, xchg != nullptr, xchg_bytes);
+    if (plan != AS_LSTM_PLAN_CLUSTER1 && plan != AS_LSTM_PLAN_CLUSTER2) return as_bilstm_f32(jobs_host, n_jobs, col_off, B, H, stream);
+    const int use = plan == AS_LSTM_PLAN_CLUSTER1 ? 1 : 2;
     LstmJobs jobs;
     for (int i = 0; i < AS_MAX_LSTM_JOBS; ++i) jobs.j[i] = jobs_host[i < n_jobs ? i : 0];
     for (int i = 0; i < n_jobs; ++i)
         if (!jobs.j[i].gx_tm || !jobs.j[i].whh_t || !jobs.j[i].out || jobs.j[i].ldg < 8 * H) return AS_EINVAL;
-    const int ncl = (int)(use == 1 ? c1 : c2);
+    const int ncl = n_jobs * 2 * (use == 1 ? B : (B + 1) / 2);
     const dim3 grid(8 * CL_P * as_cdiv(ncl, 8)), block(512);
     unsigned* status = as_status_words_device();
     AsProfScope prof__(AS_FILE_CLS, 0, 0, (hipStream_t)stream);

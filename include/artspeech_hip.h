@@ -528,6 +528,18 @@ size_t as_bilstm_cluster_bytes(int n_jobs, int B);
 int as_bilstm_cluster_f32(const BiLstmJob* jobs_host, int n_jobs, const int32_t* col_off, int B, int H, int max_len, void* xchg,
                           size_t xchg_bytes, as_stream_t stream);
 
+/* The kernel a launch takes, decided in one place (host only, no device needed): what as_bilstm_f32 (has_xchg = 0) and
+ * as_bilstm_cluster_f32 (has_xchg = xchg != NULL) run for these arguments, or AS_EINVAL for an n_jobs / B / H they refuse.
+ *   QUAD1    H = 64 / 128, one utterance per workgroup, while n_jobs * 2 * B <= 512
+ *   QUAD     H = 16 / 32 / 64 / 128, two utterances per workgroup
+ *   BIG      H = 256 in one workgroup;  STREAM  every other H divisible by 16 (W_hh streamed from L2)
+ *   CLUSTER1 / CLUSTER2  H = 256 over clusters of four workgroups, one / two utterances per cluster: needs the exchange buffer
+ *            (xchg_bytes >= as_bilstm_cluster_bytes), 0 < max_len < 2^17 and at most 64 clusters; AS_LSTM_CLUSTER in the environment
+ *            ("0" / "1" / "2") overrides the choice between never / one / two. */
+enum { AS_LSTM_PLAN_QUAD1 = 0, AS_LSTM_PLAN_QUAD = 1, AS_LSTM_PLAN_BIG = 2, AS_LSTM_PLAN_STREAM = 3, AS_LSTM_PLAN_CLUSTER1 = 4,
+       AS_LSTM_PLAN_CLUSTER2 = 5 };
+int as_bilstm_plan(int n_jobs, int B, int H, int max_len, int has_xchg, size_t xchg_bytes);
+
 /* test hooks: member `drop_member` (0..3; -1 = none) of every cluster exits at once and a poll gives up after spin_limit tries
  * (0 = default), so that the failure path can be exercised in milliseconds */
 int as_bilstm_cluster_test_hooks(int drop_member, int spin_limit);

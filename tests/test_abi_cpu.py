@@ -68,6 +68,7 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     # entry points added in round 2: the same contract (AS_EINVAL = -1 before anything touches a device)
     assert L.as_bilstm_cluster_f32(None, 1, None, 1, 256, 40, None, 0, None) == -1
     assert L.as_bilstm_cluster_bytes(0, 4) == 0 and L.as_bilstm_cluster_bytes(1, 32) > 0
+    assert L.as_bilstm_plan(0, 1, 128, 40, 0, 0) == -1 and L.as_bilstm_plan(1, 1, 24, 40, 0, 0) == -1 and L.as_bilstm_plan(1, 1, 128, 40, 0, 0) == 0
     assert L.as_relpos_attention_image_f32(None, 0, None, 0, 512, 4, 4, None, None, None, None, 0, None, 1, 40, None, 0, None, None) == -1
     assert L.as_adain_image_f32(None, None) == -1
     assert L.as_model_create(None, 0, None, None) == -1
