@@ -528,7 +528,8 @@ size_t as_bilstm_cluster_bytes(int n_jobs, int B);
 int as_bilstm_cluster_f32(const BiLstmJob* jobs_host, int n_jobs, const int32_t* col_off, int B, int H, int max_len, void* xchg,
                           size_t xchg_bytes, as_stream_t stream);
 
-/* The kernel a launch takes, decided in one place (host only, no device needed): what as_bilstm_f32 (has_xchg = 0) and
+/* The kernel a launch takes, decided in one place (csrc/lstm_rule.h: host only, no device needed; the same header gives the launch's
+ * geometry and the cluster kernels' id, word and tag arithmetic): what as_bilstm_f32 (has_xchg = 0) and
  * as_bilstm_cluster_f32 (has_xchg = xchg != NULL) run for these arguments, or AS_EINVAL for an n_jobs / B / H they refuse.
  *   QUAD1    H = 64 / 128, one utterance per workgroup, while n_jobs * 2 * B <= 512
  *   QUAD     H = 16 / 32 / 64 / 128, two utterances per workgroup

@@ -1,5 +1,5 @@
 """Float64 per-step ("teacher-forced") references and per-element error bounds of the LSTM recurrences of csrc/lstm.hip -- bilstm_quad_kernel,
-bilstm_quad1_kernel, bilstm_kernel<0>, bilstm_big_kernel, bilstm_cluster_kernel -- and of lstm_step0_kernel (csrc/conformer.hip), an fp32
+bilstm_quad1_kernel, bilstm_stream_kernel, bilstm_big_kernel, bilstm_cluster_kernel -- and of lstm_step0_kernel (csrc/conformer.hip), an fp32
 emulation of their arithmetic with plantable defects, and the cases the recurrence tests run (test infrastructure:
 tests/test_lstm_bound_gpu.py launches these cases, tests/test_lstm_bound_cpu.py emulates them).  CPU only; nothing of artspeech_amd is
 imported.
@@ -207,7 +207,7 @@ def _tanh32(x, quad1):
 
 
 def _dot32(h, W, x, order):
-    """h [J][2][b][H], W [J][2][H][4H], x [J][2][b][4H] fp32 -> x + h W in the order "seq" (ascending k on top of x: bilstm_kernel,
+    """h [J][2][b][H], W [J][2][H][4H], x [J][2][b][4H] fp32 -> x + h W in the order "seq" (ascending k on top of x: bilstm_stream_kernel,
     bilstm_big_kernel) or "split4" / "split8" (that many partial sums over consecutive k, added pairwise, then x: the quad and cluster
     kernels)"""
     H = h.shape[-1]

@@ -67,7 +67,7 @@ def test_plan_edges(monkeypatch):
 @pytest.mark.parametrize("mode,want", [("0", ["big", "big", "big"]), ("1", ["cluster1", "cluster1", "big"]),
                                        ("2", ["cluster2", "cluster2", "cluster2"]), ("3", ["big", "big", "big"])])
 def test_plan_environment(monkeypatch, mode, want):
-    """AS_LSTM_CLUSTER, read inside the rule: B = 5, 32, 33 (one utterance per cluster no longer fits at 33)"""
+    """AS_LSTM_CLUSTER, read by the library for the rule: B = 5, 32, 33 (one utterance per cluster no longer fits at 33)"""
     monkeypatch.setenv("AS_LSTM_CLUSTER", mode)
     assert [_plan(1, B, 256, xchg=True) for B in (5, 32, 33)] == want
     assert _plan(1, 5, 256) == "big" and _plan(1, 5, 128, xchg=True) == "quad1"

@@ -1,4 +1,4 @@
-"""GPU: every recurrence kernel of csrc/lstm.hip -- bilstm_quad_kernel<16 / 32 / 64 / 128>, bilstm_quad1_kernel<64 / 128>, bilstm_kernel<0>,
+"""GPU: every recurrence kernel of csrc/lstm.hip -- bilstm_quad_kernel<16 / 32 / 64 / 128>, bilstm_quad1_kernel<64 / 128>, bilstm_stream_kernel,
 bilstm_big_kernel, bilstm_cluster_kernel<1 / 2> -- and lstm_step0_kernel against float64, step by step from the kernel's own h(t-1), with
 the per-element bound of oracle/lstm_ref.py.  ops.bilstm is called with gx handed in (the GEMM has its own bound tests); every case first
 asserts that as_bilstm_plan names the kernel it is meant for.  One to four jobs, odd and even batches, empty utterances in either place
@@ -17,7 +17,7 @@ from artspeech_amd import _lib, ops
 pytestmark = pytest.mark.gpu
 
 KERNELS = ("quad16", "quad32", "quad64", "quad128", "quad1_64", "quad1_128", "stream48", "stream80", "stream240", "big", "cluster1", "cluster2")
-REGION_WORDS = 1032                                 # csrc/lstm.hip CL_REGION_WORDS: 8-byte words of one cluster's exchange region
+REGION_WORDS = 1032                                 # csrc/lstm_rule.h REGION_WORDS: 8-byte words of one cluster's exchange region
 WORST = {}
 
 
