@@ -365,6 +365,34 @@ _SIGNATURES.update({
 })
 
 
+class CueCfg(ctypes.Structure):
+    """as_cue_cfg (include/artspeech_hip.h): the cue tracks' rule in samples and linear values"""
+    _fields_ = [("min_gap", ctypes.c_int32), ("fade", ctypes.c_int32), ("tail", ctypes.c_int32), ("track_len", ctypes.c_int32),
+                ("attack", ctypes.c_int32), ("hold", ctypes.c_int32), ("release", ctypes.c_int32), ("depth", ctypes.c_float),
+                ("bed_gain", ctypes.c_float)]
+
+
+class CueReport(ctypes.Structure):
+    """as_cue_report"""
+    _fields_ = [("pos", ctypes.c_int32), ("late", ctypes.c_int32), ("cut", ctypes.c_int32), ("track", ctypes.c_int32)]
+
+
+class CueIO(ctypes.Structure):
+    """as_cue_io: DEVICE pointers (as_cue_host: host pointers)"""
+    _fields_ = [("in_off", c_p), ("in_cap", ctypes.c_int32), ("x", c_p), ("G", ctypes.c_int32), ("group_off", c_p),
+                ("start", c_p), ("limit", c_p), ("gain", c_p), ("piece_in", c_p),
+                ("out_cap", ctypes.c_int32), ("y", c_p), ("pcm", c_p), ("out_off", c_p), ("piece", c_p), ("report", c_p),
+                ("bed", c_p), ("bed_n", ctypes.c_int32), ("mix_cap", ctypes.c_int32), ("mix", c_p), ("mix_pcm", c_p), ("mix_off", c_p)]
+
+
+_pCC, _pCIO = ctypes.POINTER(CueCfg), ctypes.POINTER(CueIO)
+_SIGNATURES.update({
+    "as_cue_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, _pCC]),
+    "as_cue_f32": (c_i, [_pCC, c_i, _pCIO, c_p, c_sz, c_p]),
+    "as_cue_host": (c_i, [_pCC, c_i, _pCIO]),
+})
+
+
 class FitC(ctypes.Structure):
     """as_fit (as_plan_set_fit, as_fit_durations_f32: DEVICE pointers; as_fit_host: host pointers): spans of tokens and their targets"""
     _fields_ = [("span_tok", c_p), ("span_frames", c_p), ("lock", c_p), ("n_spans", ctypes.c_int32), ("max_count", ctypes.c_int32)]

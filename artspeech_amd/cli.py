@@ -40,6 +40,14 @@ mark), ``.srt`` or ``.vtt`` (subtitles) -- and ``--tracks-out PATH.npz`` the pit
 In rounds: ``--window-ms MS`` (with ``--vocoder-runtime``) runs the generator of any of the chains above in rounds of MS milliseconds of audio
 per utterance (as_vocoder_forward_windowed: the same samples, a workspace that does not grow with the length), and ``--stream`` writes
 ``--out`` as the rounds arrive (pipeline.ArtSpeech.synthesis_stream; ``--out -``: raw 16-bit PCM at 24 kHz on stdout).
+
+A cue sheet: ``--cues FILE.srt|.vtt`` takes the place of ``--phonemes``: every cue's text is a phoneme string, spoken at the cue's start on
+one timeline (cues.read_cues; a leading ``NAME: `` picks the track, one per name in order of first appearance; a line that would run past
+its cue's end is cut there with a fade, ``--fit-cues`` speaks it in its slot instead: pipeline.Fit).  ``--bed WAV`` (any rate the
+resampler takes; resampled on the device) lies under the speech, lowered by ``--duck-db DB`` under every line, over ``--attack-ms`` in front
+of it and ``--release-ms`` behind it.  ``--out`` is the mix (mastered by ``--lufs`` / ``--true-peak-db``), ``--stems-out PREFIX`` also
+writes PREFIX0.wav, PREFIX1.wav, ... one per track, ``--marks`` the subtitles at the PLACED times (cues.Cues, as_cue_f32;
+pipeline.ArtSpeech.synthesis_cues).  Not with ``--paragraph``, ``--like-wav``, ``--stream``, ``--fit``, ``--fit-seconds`` or ``--emphasis``.
 """
 import argparse
 import json
@@ -87,7 +95,7 @@ def write_wav(path, x, sr=24000):
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", help="Configs/config.yaml of the reference (model_params, stats_path, pretrained_model)")
-    ap.add_argument("--phonemes", required=True, help="the phoneme string espeak produces for the text (test.py:94-95)")
+    ap.add_argument("--phonemes", help="the phoneme string espeak produces for the text (test.py:94-95); required unless --cues is given")
     ref = ap.add_mutually_exclusive_group(required=True)
     ref.add_argument("--ref-wav", help="reference utterance, mono PCM wav (another rate than 24 kHz is resampled on the device)")
     ref.add_argument("--voice", help="a voice saved with --save-voice (in place of --ref-wav)")
@@ -132,6 +140,15 @@ def build_parser():
     ap.add_argument("--marks-fps", metavar="N[/D]", help="the animation clock of --tracks-out, frames per second (default 60; 30000/1001 is exact)")
     ap.add_argument("--tracks-out", metavar="PATH.npz", help="also write F0, energy and the ten articulator tracks, retimed onto --out at "
                     "--marks-fps frames per second, in physical units (as_marks_f32)")
+    ap.add_argument("--cues", metavar="FILE.srt|.vtt", help="a cue sheet in place of --phonemes: every cue's text is a phoneme string, spoken at "
+                    "the cue's start (as_cue_f32); a leading 'NAME: ' picks the track")
+    ap.add_argument("--bed", metavar="WAV", help="with --cues: the music-and-effects bed under the speech, mono PCM wav of any rate the resampler "
+                    "takes (resampled on the device)")
+    ap.add_argument("--duck-db", type=float, metavar="DB", help="with --bed: lower the bed by DB under every line (default: not at all)")
+    ap.add_argument("--attack-ms", type=float, metavar="MS", help="with --bed: the bed falls over MS in front of a line (default 50)")
+    ap.add_argument("--release-ms", type=float, metavar="MS", help="with --bed: the bed rises again over MS behind a line and its hold (default 300)")
+    ap.add_argument("--fit-cues", action="store_true", help="with --cues: every line is spoken in its cue's slot (to 25 ms) instead of being cut at its end")
+    ap.add_argument("--stems-out", metavar="PREFIX", help="with --cues: also write every track alone, PREFIX0.wav, PREFIX1.wav, ...")
     ap.add_argument("--jdc", help="Utils/JDC/bst.t7")
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
     ap.add_argument("--vocoder-config", help="Vocoder/config.json")
@@ -153,6 +170,8 @@ def build_parser():
 def parse_args(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
+    if (a.phonemes is None) == (a.cues is None):
+        ap.error("one of --phonemes and --cues is required" if a.cues is None else "--cues takes the place of --phonemes: one of them")
     if a.save_voice and not a.ref_wav:
         ap.error("--save-voice needs --ref-wav (the voice is computed from it)")
     if a.out_rate < 1:
@@ -216,6 +235,20 @@ def parse_args(argv=None):
         ap.error("--marks, --marks-fps and --tracks-out: not with --like-wav")
     if a.with_marks and a.stream:
         ap.error("--marks, --marks-fps and --tracks-out: not with --stream")
+    if a.cues is not None:
+        if not a.cues.lower().endswith((".srt", ".vtt")):
+            ap.error("--cues reads .srt or .vtt")
+        if a.paragraph or a.like_wav or a.stream or a.with_fit or a.emphasis:
+            ap.error("--cues places whole lines on a timeline: not with --paragraph (--pause-ms, --trim-db, --level-db), --like-wav, --stream, "
+                     "--fit, --fit-seconds or --emphasis")
+    elif a.bed or a.fit_cues or a.stems_out:
+        ap.error("--bed, --fit-cues and --stems-out need --cues")
+    if (a.duck_db is not None or a.attack_ms is not None or a.release_ms is not None) and not a.bed:
+        ap.error("--duck-db, --attack-ms and --release-ms shape the bed: they need --bed")
+    for name in ("duck_db", "attack_ms", "release_ms"):
+        v = getattr(a, name)
+        if v is not None and not (math.isfinite(v) and v >= 0):
+            ap.error(f"--{name.replace('_', '-')} takes 0 or more")
     if a.out == "-" and not a.stream:
         ap.error("--out - (raw PCM to stdout) needs --stream")
     try:
@@ -287,6 +320,40 @@ def master_of(a, rate):
     return Master(rate, lufs=a.lufs, true_peak_db=-1.0 if a.true_peak_db is None else a.true_peak_db, **kw)
 
 
+def cues_of(a, rate):
+    """the cues.Cues of the parsed arguments at the output's rate"""
+    from .cues import Cues
+    kw = {k: v for k, v in (("duck_db", a.duck_db), ("attack_ms", a.attack_ms), ("release_ms", a.release_ms)) if v is not None}
+    return Cues(rate, **kw)
+
+
+def cue_sheet_out(a, tts, lines):
+    """--cues: the lines as one timeline -> --out (the mix), --stems-out, --marks"""
+    from .resample import resampler
+    bed = None
+    if a.bed:
+        wave_in, bed_rate = read_wav_any(a.bed)
+        rs = resampler(bed_rate, a.out_rate, tts.device)
+        bed = torch.from_numpy(wave_in) if rs is None else rs(wave_in)                # (another rate: resampled on the device)
+    master = master_of(a, a.out_rate)
+    res = tts.synthesis_cues(lines, voice=voice_of(a, tts), prosody=a.prosody, cues=cues_of(a, a.out_rate), bed=bed, sample_rate=a.out_rate,
+                             pcm16=a.pcm16 and (master is not None or not a.stems_out), frame_cap=a.frame_cap, master=master,
+                             marks=marker_for(a, tts), fit_slots=a.fit_cues, stems=bool(a.stems_out))
+    mix, report, rest = res[0], res[1], list(res[2:])
+    write_wav(a.out, mix.numpy(), sr=a.out_rate)
+    print(f"{a.out}: {mix.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {len(lines)} lines")
+    for ln, (p, late, cut, g) in zip(lines, report.tolist()):
+        print(f"  track {g}: the line of {ln.start_s:.3f} s at {p / float(a.out_rate):.3f} s"
+              + (f", {late / float(a.out_rate):.3f} s late" if late else "") + (f", {cut} samples cut" if cut else ""))
+    if a.stems_out:
+        for g, stem in enumerate(rest.pop(0)):
+            write_wav(f"{a.stems_out}{g}.wav", stem.numpy(), sr=a.out_rate)
+        print(f"{a.stems_out}0.wav ..: {g + 1} tracks")
+    if a.with_marks:
+        write_marks(a, rest[-1], level="sentence")
+    print_master(a, tts)
+
+
 def print_master(a, tts):
     """one line per stream from the stage's report: the loudness that was measured, the gain, the true peak in front of the limiter and
     the deepest reduction"""
@@ -326,10 +393,10 @@ def voice_of(a, tts):
     return voice
 
 
-def write_marks(a, sm):
+def write_marks(a, sm, level=None):
     """the files --marks and --tracks-out name, from a marks.SpeechMarks"""
     if a.marks is not None:
-        sm.save(a.marks, level="sentence" if a.paragraph else "word")
+        sm.save(a.marks, level=level or ("sentence" if a.paragraph else "word"))
         print(f"{a.marks}: {len(sm.sentences)} sentences, {len(sm.words)} words, {len(sm.tokens)} tokens")
     if a.tracks_out is not None:
         sm.save_tracks(a.tracks_out)
@@ -407,6 +474,13 @@ def token_prosody_of(a, tts):
 
 def main(argv=None):
     ap, a = parse_args(argv)
+    lines = None
+    if a.cues:
+        from .cues import read_cues
+        try:
+            lines = read_cues(a.cues)
+        except (OSError, ValueError) as e:
+            ap.error(f"--cues: {e}")
 
     from . import ema as E, jdc as J, synth, vocoder as V
     from .pipeline import ArtSpeech
@@ -436,6 +510,9 @@ def main(argv=None):
             tok["fit"] = fit_of(a, tts)
     except ValueError as e:
         ap.error(f"--fit-seconds / --fit: {e}")
+    if lines is not None:
+        cue_sheet_out(a, tts, lines)
+        return 0
     if a.stream:
         n = stream_out(a, tts, tts.synthesis_stream(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, frame_cap=a.frame_cap, window=a.window,
                                                     pcm16=True, **tok))

@@ -225,6 +225,7 @@ class ArtSpeech:
         self.textcleaner = TextCleaner()
         self.device = dev
         self.generator = None                       # test.py:119-125: the HiFi-GAN generator (attach_vocoder)
+        self.last_cues = None                       # the dict of the last call's cue stage (`_back_end`), on the device
         self.last_master_report = None              # the master.Report of the last call with master= (`_back_end`), on the device
         self._record(None, None)
 
@@ -401,8 +402,8 @@ class ArtSpeech:
         return res
 
     def _back_end(self, inputs, res, frame_cap=None, max_len=None, pcm16=False, rs=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marker=None, window=None, master=None):
-        """generator -> [resampler rs] -> [joiner join] -> [master] -> [marks] behind `_forward`'s result, on the current stream; between the stages
+                  marker=None, window=None, master=None, cues=None, cue_sheet=None, bed=None, cue_cap=None, mix_cap=None):
+        """generator -> [resampler rs] -> [joiner join] -> [cues] -> [master] -> [marks] behind `_forward`'s result, on the current stream; between the stages
         travel packed fp32 samples and a device offset table [B + 1].  Two regimes: frame_cap None -- the host knows the frame counts
         (res["frames2"]) and every stage gets exactly the room its samples need; frame_cap=N -- only the device knows them (res["frame_off"]),
         the generator writes 300 * 2 N samples and the resampler gets out_len(that) + B; no host value is read and, with groups and gaps
@@ -415,12 +416,20 @@ class ArtSpeech:
         the joiner -- or behind the resampler or the generator when those are absent -- on the offsets the chain already has, which it
         leaves as they are: the marker sees the same offsets.  When present it is the last stage of samples and it alone writes the int16
         of pcm16; its master.Report (on the device) is kept as self.last_master_report.  master=None issues exactly the launches of before.
+        cues (a cues.Cues at the rate of the samples it receives) with cue_sheet (dict(group_off, start, limit, gain) as cues.sheet gives
+        them, in batch order; lists are uploaded, device tensors are taken as they are): every utterance is placed at its start on its
+        track (as_cue_f32).  A joiner in front of it runs with ONE GROUP PER UTTERANCE (it trims, levels and fades; groups and gaps are not
+        taken, its lead and tail must be 0) and hands its piece table on.  bed (fp32 device samples) or mix_cap: the tracks are mixed over
+        the ducked bed (mix_cap True: a mix, with the default room), and the mix with its mix_off [2] is what travels on -- to the master, and back to the caller; else the stems with
+        their out_off [G + 1].  cue_cap / mix_cap None: what always suffices, which needs the starts as a list.  The marker gets the stage's
+        piece table, tracks and the STEMS' out_off: marks are positions in the stems' buffer.  The stage's dict (Cues.forward_packed) is
+        kept as self.last_cues.  cues=None issues exactly the launches of before.
         -> (samples fp32 or int16, off [B + 1] -- behind a joiner out_off [G + 1] --, piece [B][4] or None, Marker.forward_packed's dict or
         None), all on the device."""
         from .models import layout
         gen, dev = self.generator, torch.device(self.device)
         B = res["frame_off"].numel() - 1
-        last = "master" if master is not None else "join" if join is not None else "rs" if rs is not None else "gen"
+        last = "master" if master is not None else "cues" if cues is not None else "join" if join is not None else "rs" if rs is not None else "gen"
         with torch.cuda.device(self.device):
             p = pcm16 and last == "gen"
             if window is not None and not gen.runtime:
@@ -449,6 +458,14 @@ class ArtSpeech:
                 y, p16, off = rs.forward_packed(x, off, room, pcm=p, wav=not p)
                 out = x = p16 if p else y
             piece = None
+            if join is not None and cues is not None:
+                if groups is not None or gaps is not None or join.cfg.lead or join.cfg.tail:
+                    raise ValueError("a joiner in front of cues runs with one group per utterance: no groups, no gaps, lead_ms = tail_ms = 0")
+                if "_cue_join_groups" not in inputs:                                    # (uploaded by the first, eager call: a captured one finds it)
+                    inputs["_cue_join_groups"] = torch.arange(B + 1, dtype=torch.int32).to(self.device)
+                groups = inputs["_cue_join_groups"]
+                if join_cap is None:
+                    join_cap = join.out_cap(x.numel(), B, B, 0)
             if join is not None:
                 G = 1 if groups is None else len(groups) - 1
                 if groups is not None:
@@ -460,6 +477,31 @@ class ArtSpeech:
                 p = pcm16 and last == "join"
                 y, p16, off, piece, _ = join.forward_packed(x, off, join_cap, groups=groups, gaps=gaps, pcm=p, wav=not p)
                 out = x = p16 if p else y
+            marks_off = off
+            if cues is not None:
+                if cue_sheet is None:
+                    raise ValueError("cues go with a cue_sheet (cues.sheet): group_off, start, limit, gain")
+                r, starts = stage.Device(dev), cue_sheet["start"]
+                G = len(cue_sheet["group_off"]) - 1
+                mixes = bed is not None or mix_cap is not None
+                if mix_cap is True:                                                     # (a mix, of whatever always suffices)
+                    mix_cap = None
+                if (cue_cap is None or (mixes and mix_cap is None)) and torch.is_tensor(starts):
+                    raise ValueError("starts on the device: name cue_cap (and mix_cap with a mix), the samples of room for the tracks")
+                if cue_cap is None:
+                    cue_cap = cues.out_cap(x.numel(), starts, G)
+                if mixes and mix_cap is None:
+                    mix_cap = cues.out_cap(x.numel(), starts, 1)
+                groups = r.values_i32(cue_sheet["group_off"], G + 1, "forward_packed", "group_off")   # (the stage and the marker read ONE device copy)
+                gain = cue_sheet.get("gain")
+                if gain is not None and not torch.is_tensor(gain):
+                    gain = torch.from_numpy(np.ascontiguousarray(gain, np.float32)).to(dev)
+                p = pcm16 and last == "cues"
+                o = self.last_cues = cues.forward_packed(x, off, starts, cue_cap, groups=groups, limit=cue_sheet.get("limit"), gain=gain, piece=piece,
+                                                         bed=bed, mix_cap=mix_cap if mixes else None, pcm=p, wav=not p)
+                piece, marks_off = o["piece"], o["out_off"]
+                x, off = (o["mix_pcm" if p else "mix"], o["mix_off"]) if mixes else (o["pcm" if p else "y"], o["out_off"])
+                out = x
             if master is not None:
                 y, p16, self.last_master_report = master.forward_packed(x, off, pcm=pcm16, wav=not pcm16)
                 out = p16 if pcm16 else y
@@ -468,9 +510,10 @@ class ArtSpeech:
                 if "_tok_off" not in inputs:                                            # (uploaded by the first, eager call: a captured one finds it)
                     inputs["_tok_off"] = torch.tensor(np.concatenate([[0], np.cumsum(inputs["tok_lens"])]), dtype=torch.int32).to(self.device)
                 scale, offset = marker.affine(_stats24(self), dev) if marker.physical else (None, None)
-                G = B if piece is None else off.numel() - 1
+                G = B if piece is None else marks_off.numel() - 1
+                room = out.numel() if cues is None else int(cue_cap)
                 m = marker.forward_packed(inputs["_tok_off"], res["dur_i"], res["frame_off"], res["F0"], res["N"], res["EMA"], piece=piece,
-                                          groups=groups, out_off=None if piece is None else off, anim_cap=marker.anim_cap(out.numel(), G),
+                                          groups=groups, out_off=None if piece is None else marks_off, anim_cap=marker.anim_cap(room, G),
                                           scale=scale, offset=offset)
         return out, off, piece, m
 
@@ -490,7 +533,7 @@ class ArtSpeech:
                                            **stages)
 
     def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marks=None, window=None, master=None):
+                  marks=None, window=None, master=None, cues=None, cue_sheet=None, bed=None, cue_cap=None, mix_cap=None):
         """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
         then the capacity vocoder on its frame_off and mel (`_chain`).  `inputs` = packed_inputs(...).  Every call with the same inputs dict
         reuses the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
@@ -513,14 +556,22 @@ class ArtSpeech:
         so name max_len, the mel frames the longest utterance may have, with it.
         master (a master.Master at the rate of the samples): the last stage of samples (`_back_end`) -- every stream of the result brought
         to its loudness target and held under its true-peak ceiling, at the same offsets; the chain stays capturable, and the stage's
-        Report is self.last_master_report (a device tensor: reading it synchronises).  master=None issues exactly the launches of before."""
+        Report is self.last_master_report (a device tensor: reading it synchronises).  master=None issues exactly the launches of before.
+        cues (a cues.Cues at the rate of the samples) with cue_sheet, bed, cue_cap, mix_cap (`_back_end`): every utterance is placed at
+        its start on its track, behind a joiner of one group per utterance when join is given; the call returns (mix [mix_cap], mix_off
+        [2], piece [B][4]) with a bed or a mix_cap, else (stems [cue_cap], out_off [G + 1], piece); the stage's whole dict is
+        self.last_cues.  With the sheet on the device and the capacities named the chain stays capturable; cues=None issues exactly the
+        launches of before."""
         if join is not None:
             self._check_joiner(join, sample_rate)
+        if cues is not None and cues.rate != (SAMPLE_RATE if sample_rate is None else int(sample_rate)):
+            raise ValueError(f"the cues count their milliseconds at {cues.rate} Hz, the samples they are given are at another rate")
         if master is not None:
             self._check_master(master, sample_rate)
         _, out, off, piece, m = self._chain(inputs, frame_cap, pcm16, sample_rate, self._marker(marks, sample_rate), max_len=max_len, join=join,
-                                            groups=groups, gaps=gaps, join_cap=join_cap, window=window, master=master)
-        ret = (out, off) if join is None else (out, off, piece)
+                                            groups=groups, gaps=gaps, join_cap=join_cap, window=window, master=master, cues=cues, cue_sheet=cue_sheet,
+                                            bed=bed, cue_cap=cue_cap, mix_cap=mix_cap)
+        ret = (out, off) if join is None and cues is None else (out, off, piece)
         return ret if m is None else ret + (m,)
 
     def _read_back(self, samples, off, what):
@@ -853,6 +904,79 @@ class ArtSpeech:
             sm = None if marker is None else self._speech_marks(marker, sentences, m, piece=piece.tolist())
         self._record(None if frame_cap is not None else list(res["frames2"]), res)
         return (stream, piece) if marker is None else (stream, piece, sm)
+
+    @torch.no_grad()
+    def synthesis_cues(self, lines, ref_mel=None, voice=None, prosody=None, cues=None, bed=None, sample_rate=None, pcm16=False, frame_cap=None,
+                       joiner=None, master=None, marks=False, fit_slots=False, stems=False):
+        """A cue sheet as ONE timeline: `lines` is a list of cues.Line (start_s, phonemes, end_s, track, voice, gain_db) in any order.  The
+        lines run as one batch through the chain above, then through the joiner with one group per line (trim, level, fade-in; joiner None:
+        Joiner(rate)), then through cues.Cues on the device (cues None: Cues(rate)): every line placed at its start on its track, cut with
+        a fade where its end_s says so, the tracks mixed over `bed` (1-D fp32 samples at the output's rate, or None) ducked under the
+        speech; master (a master.Master) masters the mix.  One reference or one voice serves every line unless lines name their own
+        (Line.voice; `voice` then serves the lines that name none).  fit_slots: every line with an end is spoken in its slot -- a
+        whole-utterance Fit target of max(floor((end - start) * 40), 1) half-rate frames.  ONE synchronisation: the mix's length is read, the
+        status checked, then the mix and whatever else was asked for (the report and pieces, the stems, the marks) are copied back.
+        Returns (mix 1-D fp32 or int16, report int32 [B][4] = position, late, cut, track per line, in the order of `lines`), then, when
+        asked for, stems (a list of 1-D fp32 tensors, one per track), piece int32 [B][4] in the order of `lines` (positions in the packed
+        stems; returned with stems or marks) and a marks.SpeechMarks whose utterances stand in the sheet's order (cues.sheet(lines)["order"])
+        and whose positions count from the first sample of each line's track."""
+        from . import cues as cue_mod
+        from .join import Joiner
+        from .marks import SpeechMarks, kept_symbols
+        if self.generator is None:
+            raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
+        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        lines = [ln if isinstance(ln, cue_mod.Line) else cue_mod.Line(*ln) for ln in lines]
+        sh = cue_mod.sheet(lines, rate)
+        order = sh["order"]
+        ordered = [lines[i] for i in order]
+        B = len(ordered)
+        if stems and pcm16 and master is None:
+            raise ValueError("synthesis_cues: without a master the cue stage writes the int16 itself and keeps no fp32 stems; ask for one of stems and pcm16")
+        if cues is None:
+            cues = cue_mod.Cues(rate, device=self.device)
+        if joiner is None:
+            joiner = Joiner(rate, device=self.device)
+        self._check_joiner(joiner, sample_rate)
+        if master is not None:
+            self._check_master(master, sample_rate)
+        if any(ln.voice is not None for ln in ordered):
+            voice = [ln.voice if ln.voice is not None else voice for ln in ordered]
+            if any(v is None for v in voice):
+                raise ValueError("synthesis_cues: some lines name a voice and the others have none to fall back on")
+        if ref_mel is not None and not isinstance(ref_mel, (list, tuple)):
+            ref_mel = [ref_mel] * B
+        fit = None
+        if fit_slots and any(ln.end_s is not None for ln in ordered):
+            fit = Fit.whole([None if ln.end_s is None else max(int(math.floor((ln.end_s - ln.start_s) * 40)), 1) for ln in ordered], frames=True)
+        phonemes = [ln.phonemes for ln in ordered]
+        marker = self._marker(marks, sample_rate)
+        if bed is not None:
+            bed = torch.as_tensor(bed, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+        inputs = self.packed_inputs(phonemes, ref_mel, None, voice, prosody, fit=fit)
+        res, mix, mix_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, sample_rate, marker, join=joiner,
+                                                  master=master, cues=cues, cue_sheet=sh, bed=bed, mix_cap=True)
+        o = self.last_cues
+        with torch.cuda.device(self.device):
+            _, mix = self._read_back(mix, mix_off, "synthesis_cues")                   # the one synchronisation: the length, then the mix
+            report, piece = o["report"].cpu(), piece.cpu()
+            back = lambda rows: rows[torch.argsort(torch.tensor(order))]                # rows in the order of `lines`
+            ret = (mix, back(report))
+            out_off = o["out_off"].cpu().tolist()
+            if stems:
+                y = o["y"][: out_off[-1]].cpu()
+                ret += ([y[out_off[g]: out_off[g + 1]] for g in range(len(out_off) - 1)],)
+            if stems or marker is not None:
+                ret += (back(piece),)
+            if marker is not None:
+                syms = [kept_symbols(self.textcleaner, p) for p in phonemes]
+                n = int(m["anim_off"][-1])
+                origin = [out_off[int(report[b, 3])] for b in range(B)]
+                ret += (SpeechMarks(marker.rate, marker.fps, syms, m["marks"].cpu().numpy()[: sum(len(s) for s in syms)],
+                                    [(int(p[0]), int(p[1])) for p in piece.tolist()], origin, m["tracks"][:, :n].cpu().numpy(),
+                                    m["active"][:n].cpu().numpy(), m["anim_off"].cpu().numpy()),)
+        self._record(None if frame_cap is not None else list(res["frames2"]), res)
+        return ret
 
     def synthesis_stream(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, frame_cap=None,
                          token_prosody=None, token_smooth=False, fit=None, window=64, pcm16=True, sample_rate=None, joiner=None, marks=False):

@@ -1222,6 +1222,70 @@ size_t as_marks_workspace_bytes(int B, int n_tokens, const as_marks_cfg* cfg);
 int as_marks_f32(const as_marks_cfg* cfg, int B, int n_tokens, const as_marks_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
 int as_marks_host(const as_marks_cfg* cfg, int B, int n_tokens, const as_marks_io* io);
 
+/* ---- cue tracks: pieces at absolute times, mixed over a ducked bed (csrc/cues.hip; the rule: csrc/cue_rule.h) ------
+ * The joiner lays pieces out back to back; this stage puts every piece AT A TIME on one of G tracks (a speaker each, say), and can mix the
+ * tracks over a music-and-effects bed that is ducked under the speech.  Its stems are packed streams with an out_off (as_master_f32 takes
+ * them as they are), its piece table is an as_join_piece table (as_marks_f32 takes it with the same G, group_off and out_off).
+ * The rule.  Piece b = x[in_off[b] .. in_off[b + 1]) (read clamped to [0, in_cap]), n_b samples; group_off [G + 1] cuts the B pieces into G
+ * tracks as the joiner's does (inner cuts clamped to [0, B]; NULL: everything on track 0).  Layout, per track in batch order, E = 0 the
+ * running end, any = "a non-empty piece has been placed": s_b = max(start[b], 0); p_b = max(s_b, E + (any ? min_gap : 0)); m_b = n_b, cut to
+ * max(limit[b] - p_b, 0) with a limit (limit given and limit[b] > 0) and to max(track_len - p_b, 0) with track_len > 0; cut_b = n_b - m_b,
+ * late_b = p_b - s_b.  m_b > 0: the piece lies at [p_b, p_b + m_b), E = p_b + m_b, any is set; else it lies nowhere, E stays, and piece[b] has
+ * out_start = out_end = E (a track's pieces ascend).  A track is track_len samples long when track_len > 0, else E + tail, and 0 without a
+ * placed piece; out_off = the prefix sums.  Samples: y[out_off[g] + p_b + i] = (x_b[i] gain[b]) w_b(i) for i < m_b (gain NULL: 1); w_b = 1 but
+ * for a piece with cut_b > 0, whose last f = min(fade, m_b) samples take w = ((m_b - 1 - i) + 0.5) / f.  Everything else of a track is 0, and
+ * so is [out_off[G], out_cap).  piece[b] = {out_off[g] + p_b, out_off[g] + p_b + m_b, src0, src0 + m_b} with src0 = piece_in[b].src_start
+ * (piece_in: the as_join_piece table of a joiner run with one group per utterance, whose output x is; NULL: 0); report[b] = {p_b, late_b,
+ * cut_b, g}.  Mix (mix or mix_pcm given; G <= 64): T = the longest track; speech(t) = the tracks' samples added in ascending track order
+ * from 0.f (0 behind a track's end); cover c(t) = the maximum over placed pieces of r_b(t), e_b = p_b + m_b: 1 on [p_b, e_b + hold),
+ * (t - (p_b - attack) + 1) / (attack + 1) on [p_b - attack, p_b), (e_b + hold + release - t) / (release + 1) on [e_b + hold, e_b + hold + release),
+ * else 0; k = 1 - depth; duck(t) = fmaf(-k, c(t), 1); mix(t) = bed(t) (bed_gain duck(t)) + speech(t) with bed(t) = bed[t] for t < bed_n, else 0
+ * (no bed: 0); mix_off = {0, T}; [T, mix_cap) is 0.  depth is the bed's linear gain at full duck: 1 = no ducking.  Every fp32 operation has
+ * one rounding in the order cue_rule.h fixes: a track alone gives the bits of the same track in a batch, the device those of as_cue_host.
+ * as_cue_io: DEVICE pointers.  in_off [B + 1], x [in_cap], start [B]; optional group_off [G + 1], limit [B], gain [B], piece_in [B], bed
+ * [bed_n].  Outputs, each optional, at least one of y, pcm, mix, mix_pcm: y fp32 / pcm (as_conv_post_pcm_f32's rule on the fp32 value: a NaN
+ * stores 0 and raises AS_STATUS_F16_RANGE) [out_cap], out_off [G + 1], piece [B], report [B]; mix / mix_pcm [mix_cap], mix_off [2].
+ * as_cue_f32            at most three launches (layout, write, mix), sized by B, out_cap and mix_cap: nothing is read back, uploaded or
+ *                       allocated and no call synchronises -- every call, the first included, can be captured into a hipGraph and replayed
+ *                       with other offsets, starts and samples.  The tracks need more than out_cap, T > mix_cap, in_off[B] > in_cap, or a
+ *                       position beyond 2^30: AS_STATUS_CAPACITY (the layout is cut there, nothing is read or stored out of bounds; that
+ *                       call's output is void).  y == x and mix == bed are refused.  With a mix and no y the stems go to the workspace.
+ * as_cue_host           the same rule on HOST arrays (every pointer of io is a host pointer; no GPU, no workspace).  AS_ENOSPC where the
+ *                       device raises AS_STATUS_CAPACITY; AS_EDEVICE: a NaN went to pcm; AS_EINVAL also for offsets that do not ascend from
+ *                       0 to <= in_cap.
+ * AS_EINVAL before anything is launched: cfg, io, ws, in_off, x or start NULL; no sample output; B outside [1, 65536]; G outside [1, 4096],
+ * or above 64 with a mix; in_cap, out_cap (mix_cap with a mix) outside [1, 2^30]; min_gap, fade, tail, attack, hold, release outside
+ * [0, 2^20]; track_len outside [0, 2^30]; depth outside [0, 1]; bed_gain negative or not finite; bed_n < 0 with a bed.  AS_ENOSPC: ws_bytes
+ * below as_cue_workspace_bytes(B, G, in_cap, out_cap, mix_cap, cfg) (mix_cap 0: no mix; 0 for arguments it refuses).  AS_EDEVICE while a
+ * status bit is set. */
+typedef struct as_cue_cfg {
+    int32_t min_gap, fade, tail;   /* samples: between two pieces of a track, the fade-out of a cut piece, behind a track's last piece */
+    int32_t track_len;             /* samples; 0: as long as needed */
+    int32_t attack, hold, release; /* samples: the duck's ramp down, its hold behind a piece and its ramp up */
+    float depth, bed_gain;         /* linear: the bed's gain at full duck (1: no ducking), the bed's gain */
+} as_cue_cfg;
+typedef struct as_cue_report {
+    int32_t pos, late, cut, track; /* p_b, late_b, cut_b, g */
+} as_cue_report;
+typedef struct as_cue_io {
+    const int32_t* in_off; int32_t in_cap;
+    const float* x;
+    int32_t G; const int32_t* group_off;
+    const int32_t* start; const int32_t* limit; const float* gain; const as_join_piece* piece_in;
+    int32_t out_cap;
+    float* y; int16_t* pcm;
+    int32_t* out_off;
+    as_join_piece* piece;
+    as_cue_report* report;
+    const float* bed; int32_t bed_n;
+    int32_t mix_cap;
+    float* mix; int16_t* mix_pcm;
+    int32_t* mix_off;
+} as_cue_io;
+size_t as_cue_workspace_bytes(int B, int G, int in_cap, int out_cap, int mix_cap, const as_cue_cfg* cfg);
+int as_cue_f32(const as_cue_cfg* cfg, int B, const as_cue_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_cue_host(const as_cue_cfg* cfg, int B, const as_cue_io* io);
+
 /* ---- prosody transfer (csrc/dtw.hip, csrc/dtw_rule.h) -------------------------------------------------------------
  * Speak a sentence the way a recording of it was spoken: synthesise it once (pass A), warp pass A's mel onto the recording's log-mel
  * (dynamic time warping, frame by frame), turn the warp into one prosody row per token (as_plan_set_token_prosody's rows: a duration scale
