@@ -393,6 +393,35 @@ _SIGNATURES.update({
 })
 
 
+class RoomCfg(ctypes.Structure):
+    """as_room_cfg (include/artspeech_hip.h): the ring-out behind every stream, in samples"""
+    _fields_ = [("tail", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class RoomIO(ctypes.Structure):
+    """as_room_io: DEVICE pointers (as_room_host: host pointers)"""
+    _fields_ = [("in_off", c_p), ("in_cap", ctypes.c_int32), ("x", c_p), ("K", ctypes.c_int32), ("ir_off", c_p), ("ir_cap", ctypes.c_int32),
+                ("h", c_p), ("room", c_p), ("send", c_p), ("dry", c_p), ("delay", c_p),
+                ("out_cap", ctypes.c_int32), ("y", c_p), ("pcm", c_p), ("out_off", c_p),
+                ("B", ctypes.c_int32), ("group_off", c_p), ("piece_in", c_p), ("piece", c_p),
+                ("mix_in", c_p), ("mix_off", c_p), ("mix_cap", ctypes.c_int32), ("mix", c_p), ("mix_pcm", c_p)]
+
+
+class RoomDesign(ctypes.Structure):
+    """as_room_design"""
+    _fields_ = [("rate", ctypes.c_int32), ("rt60_ms", ctypes.c_int32), ("damping", ctypes.c_float), ("seed", ctypes.c_uint32)]
+
+
+_pRC, _pRIO, _pRD = ctypes.POINTER(RoomCfg), ctypes.POINTER(RoomIO), ctypes.POINTER(RoomDesign)
+_SIGNATURES.update({
+    "as_room_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, _pRC]),
+    "as_room_f32": (c_i, [_pRC, c_i, _pRIO, c_p, c_sz, c_p]),
+    "as_room_host": (c_i, [_pRC, c_i, _pRIO]),
+    "as_room_design_host": (c_i, [_pRD, c_p, ctypes.c_int32, c_p]),
+    "as_room_geometry": (c_i, [c_p, c_p]),
+})
+
+
 class FitC(ctypes.Structure):
     """as_fit (as_plan_set_fit, as_fit_durations_f32: DEVICE pointers; as_fit_host: host pointers): spans of tokens and their targets"""
     _fields_ = [("span_tok", c_p), ("span_frames", c_p), ("lock", c_p), ("n_spans", ctypes.c_int32), ("max_count", ctypes.c_int32)]

@@ -48,6 +48,12 @@ resampler takes; resampled on the device) lies under the speech, lowered by ``--
 of it and ``--release-ms`` behind it.  ``--out`` is the mix (mastered by ``--lufs`` / ``--true-peak-db``), ``--stems-out PREFIX`` also
 writes PREFIX0.wav, PREFIX1.wav, ... one per track, ``--marks`` the subtitles at the PLACED times (cues.Cues, as_cue_f32;
 pipeline.ArtSpeech.synthesis_cues).  Not with ``--paragraph``, ``--like-wav``, ``--stream``, ``--fit``, ``--fit-seconds`` or ``--emphasis``.
+
+A room: ``--reverb-ms 600`` designs one whose response falls by 60 dB in 600 ms (``--reverb-damping``: how dark), ``--ir-wav WAV`` reads a
+measured one; ``--reverb-db`` is the wet signal's gain (default -12), ``--predelay-ms`` its delay, ``--reverb-tail-ms`` makes ``--out`` that
+much longer for the ring-out.  The convolution runs on the device in front of the master (room.Rooms, as_room_f32).  With ``--cues`` every
+track is sent to the room and returns to the mix; ``--track-reverb-db 0:-12,1:-30`` sets single tracks' sends.  Not with ``--stream`` or
+``--like-wav``.
 """
 import argparse
 import json
@@ -149,6 +155,17 @@ def build_parser():
     ap.add_argument("--release-ms", type=float, metavar="MS", help="with --bed: the bed rises again over MS behind a line and its hold (default 300)")
     ap.add_argument("--fit-cues", action="store_true", help="with --cues: every line is spoken in its cue's slot (to 25 ms) instead of being cut at its end")
     ap.add_argument("--stems-out", metavar="PREFIX", help="with --cues: also write every track alone, PREFIX0.wav, PREFIX1.wav, ...")
+    ap.add_argument("--reverb-ms", type=float, metavar="MS", help="put --out in a designed room whose response falls by 60 dB in MS milliseconds "
+                    "(room.Room; convolution reverb on the device, as_room_f32), in front of --lufs / --true-peak-db")
+    ap.add_argument("--ir-wav", metavar="WAV", help="in place of --reverb-ms: a measured impulse response -- a hall, a telephone, a radio -- mono PCM "
+                    "wav of any rate the resampler takes; cut at 2^17 taps and scaled to unit energy")
+    ap.add_argument("--reverb-db", type=float, metavar="DB", help="with --reverb-ms / --ir-wav: the wet signal's gain (default -12)")
+    ap.add_argument("--reverb-damping", type=float, metavar="D", help="with --reverb-ms: how dark the room is, 0 .. 0.95 (default 0.3)")
+    ap.add_argument("--predelay-ms", type=float, metavar="MS", help="with --reverb-ms / --ir-wav: the wet signal starts MS later (default 0)")
+    ap.add_argument("--reverb-tail-ms", type=float, metavar="MS", help="with --reverb-ms / --ir-wav: --out is MS longer, room for the ring-out "
+                    "(default 0; not with --cues, whose mix has the timeline's length)")
+    ap.add_argument("--track-reverb-db", metavar="TRACK:DB,...", help="with --cues and --reverb-ms / --ir-wav: the send of single tracks, e.g. "
+                    "0:-12,1:-30 (tracks that are not named take --reverb-db)")
     ap.add_argument("--jdc", help="Utils/JDC/bst.t7")
     ap.add_argument("--ema", help="Utils/EMA/200000.pth.tar")
     ap.add_argument("--vocoder-config", help="Vocoder/config.json")
@@ -249,6 +266,34 @@ def parse_args(argv=None):
         v = getattr(a, name)
         if v is not None and not (math.isfinite(v) and v >= 0):
             ap.error(f"--{name.replace('_', '-')} takes 0 or more")
+    a.with_reverb = a.reverb_ms is not None or a.ir_wav is not None
+    if a.reverb_ms is not None and a.ir_wav is not None:
+        ap.error("--reverb-ms designs a room, --ir-wav reads one: one of them")
+    given = [n for n in ("reverb_db", "reverb_damping", "predelay_ms", "reverb_tail_ms", "track_reverb_db") if getattr(a, n) is not None]
+    if given and not a.with_reverb:
+        ap.error(f"--{given[0].replace('_', '-')} needs --reverb-ms or --ir-wav")
+    if a.with_reverb and (a.stream or a.like_wav):
+        ap.error("--reverb-ms and --ir-wav: not with --stream (a room's history crosses the rounds) or --like-wav")
+    if a.reverb_ms is not None and not (math.isfinite(a.reverb_ms) and 1 <= a.reverb_ms <= 3600000):
+        ap.error("--reverb-ms takes 1 ms or more")
+    if a.reverb_damping is not None and (a.ir_wav is not None or not 0 <= a.reverb_damping <= 0.95):
+        ap.error("--reverb-damping shapes the designed room of --reverb-ms and lies in [0, 0.95]")
+    if a.reverb_db is not None and not math.isfinite(a.reverb_db):
+        ap.error("--reverb-db takes a finite gain in dB")
+    for name in ("predelay_ms", "reverb_tail_ms"):
+        v = getattr(a, name)
+        if v is not None and not (math.isfinite(v) and 0 <= v * a.out_rate / 1000.0 <= (1 << 20)):
+            ap.error(f"--{name.replace('_', '-')} takes 0 ms or more, at most 2^20 samples")
+    if a.reverb_tail_ms and a.cues is not None:
+        ap.error("--reverb-tail-ms: not with --cues (the reverb returns to the mix, which has the timeline's length)")
+    if a.reverb_tail_ms and a.with_marks and not a.paragraph:
+        ap.error("--reverb-tail-ms moves the utterances: with --marks it needs --paragraph")
+    if a.track_reverb_db is not None and a.cues is None:
+        ap.error("--track-reverb-db names the tracks of --cues")
+    try:
+        a.track_sends = track_sends(a.track_reverb_db)
+    except ValueError as e:
+        ap.error(str(e))
     if a.out == "-" and not a.stream:
         ap.error("--out - (raw PCM to stdout) needs --stream")
     try:
@@ -320,6 +365,52 @@ def master_of(a, rate):
     return Master(rate, lufs=a.lufs, true_peak_db=-1.0 if a.true_peak_db is None else a.true_peak_db, **kw)
 
 
+def track_sends(spec):
+    """--track-reverb-db "0:-12,1:-30" -> {0: -12.0, 1: -30.0} ({} for None)"""
+    sends = {}
+    for item in ([] if spec is None else spec.split(",")):
+        try:
+            g, db = item.split(":")
+            g, db = int(g), float(db)
+        except ValueError:
+            raise ValueError(f"--track-reverb-db takes TRACK:DB pairs, not {item!r}") from None
+        if g < 0 or g in sends or not math.isfinite(db):
+            raise ValueError(f"--track-reverb-db: {item!r} names a negative track, a track twice or a gain that is not finite")
+        sends[g] = db
+    return sends
+
+
+def rooms_of(a, rate, device=None):
+    """the room.Rooms of the parsed arguments at the output's rate -- one room, designed (--reverb-ms) or read (--ir-wav) --, or None"""
+    from .room import Room, Rooms
+    if not a.with_reverb:
+        return None
+    if a.ir_wav is not None:
+        wave_in, ir_rate = read_wav_any(a.ir_wav)
+        r = Room.from_wave(wave_in, ir_rate, rate, device)
+    else:
+        r = Room(rate, a.reverb_ms, damping=0.3 if a.reverb_damping is None else a.reverb_damping)
+    return Rooms(rate, [r], tail_ms=a.reverb_tail_ms or 0.0, device=device)
+
+
+def room_sheet_of(a):
+    """the room sheet of the parsed arguments: every stream in room 0 at --reverb-db behind --predelay-ms; None without a room"""
+    if not a.with_reverb:
+        return None
+    return dict(room=0, send_db=-12.0 if a.reverb_db is None else a.reverb_db, dry_db=0.0, predelay_ms=a.predelay_ms or 0.0)
+
+
+def track_rooms_of(a, lines):
+    """--cues: {track: (room 0, send, predelay)} for every track of the sheet, --track-reverb-db where it names the track; None without a room"""
+    if not a.with_reverb:
+        return None
+    sh = room_sheet_of(a)
+    G = max(ln.track for ln in lines) + 1
+    if any(g >= G for g in a.track_sends):
+        raise ValueError(f"--track-reverb-db names track {max(a.track_sends)}: the sheet has tracks 0 .. {G - 1}")
+    return {g: (0, a.track_sends.get(g, sh["send_db"]), sh["predelay_ms"]) for g in range(G)}
+
+
 def cues_of(a, rate):
     """the cues.Cues of the parsed arguments at the output's rate"""
     from .cues import Cues
@@ -338,7 +429,8 @@ def cue_sheet_out(a, tts, lines):
     master = master_of(a, a.out_rate)
     res = tts.synthesis_cues(lines, voice=voice_of(a, tts), prosody=a.prosody, cues=cues_of(a, a.out_rate), bed=bed, sample_rate=a.out_rate,
                              pcm16=a.pcm16 and (master is not None or not a.stems_out), frame_cap=a.frame_cap, master=master,
-                             marks=marker_for(a, tts), fit_slots=a.fit_cues, stems=bool(a.stems_out))
+                             marks=marker_for(a, tts), fit_slots=a.fit_cues, stems=bool(a.stems_out),
+                             **({"rooms": rooms_of(a, a.out_rate, tts.device), "track_rooms": track_rooms_of(a, lines)} if a.with_reverb else {}))
     mix, report, rest = res[0], res[1], list(res[2:])
     write_wav(a.out, mix.numpy(), sr=a.out_rate)
     print(f"{a.out}: {mix.numel() / float(a.out_rate):.2f} s of audio at {a.out_rate} Hz from {len(lines)} lines")
@@ -511,8 +603,13 @@ def main(argv=None):
     except ValueError as e:
         ap.error(f"--fit-seconds / --fit: {e}")
     if lines is not None:
+        try:
+            track_rooms_of(a, lines)
+        except ValueError as e:
+            ap.error(str(e))
         cue_sheet_out(a, tts, lines)
         return 0
+    room = {"rooms": rooms_of(a, a.out_rate, tts.device), "room_sheet": room_sheet_of(a)} if a.with_reverb else {}
     if a.stream:
         n = stream_out(a, tts, tts.synthesis_stream(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, frame_cap=a.frame_cap, window=a.window,
                                                     pcm16=True, **tok))
@@ -521,7 +618,7 @@ def main(argv=None):
     if a.paragraph:
         audio, piece, *sm = tts.synthesis_paragraph(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, joiner=joiner_of(a, a.out_rate),
                                                     pcm16=a.pcm16, frame_cap=a.frame_cap, sample_rate=a.out_rate, marks=marker_for(a, tts),
-                                                    window=a.window, master=master_of(a, a.out_rate))
+                                                    window=a.window, master=master_of(a, a.out_rate), **room)
         if sm:
             write_marks(a, sm[0])
         write_wav(a.out, audio.numpy(), sr=a.out_rate)
@@ -538,14 +635,14 @@ def main(argv=None):
               f"{int(info['misses'].sum())} token(s) kept their own duration")
     elif a.voice:
         audio = tts.synthesis_wav(a.phonemes, voice=voice_of(a, tts), prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap,
-                                  sample_rate=a.out_rate, marks=marker_for(a, tts), window=a.window, master=master_of(a, a.out_rate), **tok)
+                                  sample_rate=a.out_rate, marks=marker_for(a, tts), window=a.window, master=master_of(a, a.out_rate), **room, **tok)
     else:
         if a.save_voice:
             voice_of(a, tts)                                           # (written; the synthesis below starts from the wave itself)
         wave_in, ref_rate = read_wav_any(a.ref_wav)
         audio = tts.synthesis_from_wave(a.phonemes, wave_in, prosody=a.prosody, pcm16=a.pcm16, frame_cap=a.frame_cap, ref_rate=ref_rate,
                                         sample_rate=a.out_rate, trim_db=a.trim_ref_db,
-                                        marks=marker_for(a, tts), window=a.window, master=master_of(a, a.out_rate), **tok)
+                                        marks=marker_for(a, tts), window=a.window, master=master_of(a, a.out_rate), **room, **tok)
     if a.with_marks:
         audio, sm = audio
         write_marks(a, sm)

@@ -226,6 +226,7 @@ class ArtSpeech:
         self.device = dev
         self.generator = None                       # test.py:119-125: the HiFi-GAN generator (attach_vocoder)
         self.last_cues = None                       # the dict of the last call's cue stage (`_back_end`), on the device
+        self.last_rooms = None                      # the dict of the last call's rooms stage (`_back_end`), on the device
         self.last_master_report = None              # the master.Report of the last call with master= (`_back_end`), on the device
         self._record(None, None)
 
@@ -402,8 +403,9 @@ class ArtSpeech:
         return res
 
     def _back_end(self, inputs, res, frame_cap=None, max_len=None, pcm16=False, rs=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marker=None, window=None, master=None, cues=None, cue_sheet=None, bed=None, cue_cap=None, mix_cap=None):
-        """generator -> [resampler rs] -> [joiner join] -> [cues] -> [master] -> [marks] behind `_forward`'s result, on the current stream; between the stages
+                  marker=None, window=None, master=None, cues=None, cue_sheet=None, bed=None, cue_cap=None, mix_cap=None, rooms=None,
+                  room_sheet=None, room_cap=None):
+        """generator -> [resampler rs] -> [joiner join] -> [cues] -> [rooms] -> [master] -> [marks] behind `_forward`'s result, on the current stream; between the stages
         travel packed fp32 samples and a device offset table [B + 1].  Two regimes: frame_cap None -- the host knows the frame counts
         (res["frames2"]) and every stage gets exactly the room its samples need; frame_cap=N -- only the device knows them (res["frame_off"]),
         the generator writes 300 * 2 N samples and the resampler gets out_len(that) + B; no host value is read and, with groups and gaps
@@ -424,12 +426,20 @@ class ArtSpeech:
         their out_off [G + 1].  cue_cap / mix_cap None: what always suffices, which needs the starts as a list.  The marker gets the stage's
         piece table, tracks and the STEMS' out_off: marks are positions in the stems' buffer.  The stage's dict (Cues.forward_packed) is
         kept as self.last_cues.  cues=None issues exactly the launches of before.
+        rooms (a room.Rooms at the rate of the samples it receives) with room_sheet (dict(room, send_db, dry_db, predelay_ms), each one
+        value or one per stream -- per track behind cues --; device tensors are taken as they are, in the library's units: room int32,
+        send and dry linear fp32, predelay int32 samples): convolution reverb (as_room_f32) between cues and master.  Behind a cue MIX it
+        runs in return mode: the cue stage writes fp32 stems and mix, every track's wet signal is added to the mix, which travels on (dry_db
+        is not used: the mix is the dry signal).  Else in streams mode on the offsets the chain has: every non-empty stream grows by the
+        bank's tail, the offsets and the piece table that travel on are the stage's own, room_cap (None: what always suffices) is its
+        room; marks with a tail need a piece table (a joiner or cues in front).  The stage's dict is kept as self.last_rooms.  With the
+        sheet on the device the chain stays capturable; rooms=None issues exactly the launches of before.
         -> (samples fp32 or int16, off [B + 1] -- behind a joiner out_off [G + 1] --, piece [B][4] or None, Marker.forward_packed's dict or
         None), all on the device."""
         from .models import layout
         gen, dev = self.generator, torch.device(self.device)
         B = res["frame_off"].numel() - 1
-        last = "master" if master is not None else "cues" if cues is not None else "join" if join is not None else "rs" if rs is not None else "gen"
+        last = "master" if master is not None else "rooms" if rooms is not None else "cues" if cues is not None else "join" if join is not None else "rs" if rs is not None else "gen"
         with torch.cuda.device(self.device):
             p = pcm16 and last == "gen"
             if window is not None and not gen.runtime:
@@ -502,6 +512,31 @@ class ArtSpeech:
                 piece, marks_off = o["piece"], o["out_off"]
                 x, off = (o["mix_pcm" if p else "mix"], o["mix_off"]) if mixes else (o["pcm" if p else "y"], o["out_off"])
                 out = x
+            marks_room = None if cues is None else int(cue_cap)
+            if rooms is not None:
+                sh = dict(room_sheet or {})
+                sheet = dict(room=sh.get("room", 0), send_db=sh.get("send_db", -12.0), predelay_ms=sh.get("predelay_ms", 0.0))
+                p = pcm16 and last == "rooms"
+                if cues is not None and mixes:                                          # a send on the mix: the stems' wet signals return to it
+                    o = self.last_rooms = rooms.return_to(x, off, self.last_cues["y"], self.last_cues["out_off"], pcm=p, wav=not p, **sheet)
+                    out = x = o["mix_pcm" if p else "mix"]
+                else:
+                    if marker is not None and rooms.tail and piece is None:
+                        raise ValueError("rooms with a tail move every stream: marks then need a piece table (a joiner or cues in front of the rooms)")
+                    G = off.numel() - 1
+                    if piece is not None and groups is None:                            # (one joined stream: every piece is its own)
+                        if "_room_groups" not in inputs:                                # (uploaded by the first, eager call: a captured one finds it)
+                            inputs["_room_groups"] = torch.tensor([0, piece.shape[0]], dtype=torch.int32).to(self.device)
+                        groups = inputs["_room_groups"]
+                    if room_cap is None:
+                        room_cap = rooms.out_cap(x.numel(), G)
+                    o = self.last_rooms = rooms.forward_packed(x, off, dry_db=sh.get("dry_db", 0.0), out_cap=room_cap, pcm=p, wav=not p, piece=piece,
+                                                               groups=None if piece is None else groups, **sheet)
+                    out = x = o["pcm" if p else "y"]
+                    off = o["out_off"]
+                    if piece is not None:
+                        piece, marks_off = o["piece"], off
+                    marks_room = int(room_cap)
             if master is not None:
                 y, p16, self.last_master_report = master.forward_packed(x, off, pcm=pcm16, wav=not pcm16)
                 out = p16 if pcm16 else y
@@ -511,7 +546,7 @@ class ArtSpeech:
                     inputs["_tok_off"] = torch.tensor(np.concatenate([[0], np.cumsum(inputs["tok_lens"])]), dtype=torch.int32).to(self.device)
                 scale, offset = marker.affine(_stats24(self), dev) if marker.physical else (None, None)
                 G = B if piece is None else marks_off.numel() - 1
-                room = out.numel() if cues is None else int(cue_cap)
+                room = out.numel() if marks_room is None else marks_room
                 m = marker.forward_packed(inputs["_tok_off"], res["dur_i"], res["frame_off"], res["F0"], res["N"], res["EMA"], piece=piece,
                                           groups=groups, out_off=None if piece is None else marks_off, anim_cap=marker.anim_cap(room, G),
                                           scale=scale, offset=offset)
@@ -533,7 +568,8 @@ class ArtSpeech:
                                            **stages)
 
     def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marks=None, window=None, master=None, cues=None, cue_sheet=None, bed=None, cue_cap=None, mix_cap=None):
+                  marks=None, window=None, master=None, cues=None, cue_sheet=None, bed=None, cue_cap=None, mix_cap=None, rooms=None,
+                  room_sheet=None, room_cap=None):
         """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
         then the capacity vocoder on its frame_off and mel (`_chain`).  `inputs` = packed_inputs(...).  Every call with the same inputs dict
         reuses the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
@@ -561,6 +597,11 @@ class ArtSpeech:
         its start on its track, behind a joiner of one group per utterance when join is given; the call returns (mix [mix_cap], mix_off
         [2], piece [B][4]) with a bed or a mix_cap, else (stems [cue_cap], out_off [G + 1], piece); the stage's whole dict is
         self.last_cues.  With the sheet on the device and the capacities named the chain stays capturable; cues=None issues exactly the
+        launches of before.
+        rooms (a room.Rooms at the rate of the samples) with room_sheet and room_cap (`_back_end`): convolution reverb between cues and
+        master -- per stream (the offsets, and the pieces behind a joiner or cues, that the call returns are the stage's own: every
+        non-empty stream grows by the bank's tail) or, behind a cue mix, as a send of every track on the mix; the stage's dict is
+        self.last_rooms.  With the sheet on the device and room_cap named the chain stays capturable; rooms=None issues exactly the
         launches of before."""
         if join is not None:
             self._check_joiner(join, sample_rate)
@@ -568,9 +609,10 @@ class ArtSpeech:
             raise ValueError(f"the cues count their milliseconds at {cues.rate} Hz, the samples they are given are at another rate")
         if master is not None:
             self._check_master(master, sample_rate)
+        self._check_rooms(rooms, sample_rate)
         _, out, off, piece, m = self._chain(inputs, frame_cap, pcm16, sample_rate, self._marker(marks, sample_rate), max_len=max_len, join=join,
                                             groups=groups, gaps=gaps, join_cap=join_cap, window=window, master=master, cues=cues, cue_sheet=cue_sheet,
-                                            bed=bed, cue_cap=cue_cap, mix_cap=mix_cap)
+                                            bed=bed, cue_cap=cue_cap, mix_cap=mix_cap, **self._room_stage(rooms, room_sheet, room_cap))
         ret = (out, off) if join is None and cues is None else (out, off, piece)
         return ret if m is None else ret + (m,)
 
@@ -668,6 +710,20 @@ class ArtSpeech:
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if master.rate != rate:
             raise ValueError(f"the master's filters are designed for {master.rate} Hz, the samples it is given are at {rate} Hz")
+
+    def _check_rooms(self, rooms, sample_rate):
+        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        if rooms is not None and rooms.rate != rate:
+            raise ValueError(f"the rooms' responses are sampled at {rooms.rate} Hz, the samples they are given are at {rate} Hz")
+
+    @staticmethod
+    def _room_stage(rooms, room_sheet=None, room_cap=None):
+        """`_back_end`'s keywords of the rooms stage: none at all without rooms (a call without them is the call of before)"""
+        if rooms is None:
+            if room_sheet is not None or room_cap is not None:
+                raise ValueError("room_sheet and room_cap go with rooms")
+            return {}
+        return dict(rooms=rooms, room_sheet=room_sheet, room_cap=room_cap)
 
     def _hop(self):
         """samples per mel frame of the attached generator: the product of its up-sampling rates (300)"""
@@ -769,7 +825,7 @@ class ArtSpeech:
     @torch.no_grad()
     def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
                       frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False, fit=None, window=None,
-                      max_len=None, master=None):
+                      max_len=None, master=None, rooms=None, room_sheet=None):
         """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
         (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
         generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the chain's last kernel.
@@ -788,19 +844,25 @@ class ArtSpeech:
         max_len (with frame_cap): the mel frames the longest utterance may have (None: 2 frame_cap) -- it sizes the generator's grids and,
         with window, is what the number of rounds is taken from: ceil(max_len / window); a longer utterance raises AS_STATUS_CAPACITY.
         master (a master.Master at the output's rate): every utterance brought to its loudness target in LUFS and held under its
-        true-peak ceiling on the device, as the chain's last stage (`_back_end`); its report is self.last_master_report."""
+        true-peak ceiling on the device, as the chain's last stage (`_back_end`); its report is self.last_master_report.
+        rooms (a room.Rooms at the output's rate) with room_sheet (dict(room, send_db, dry_db, predelay_ms), one value or one per
+        utterance): convolution reverb on every utterance in front of the master (`_back_end`); every row is longer by the bank's tail
+        (marks then raise ValueError: they need a piece table)."""
         single, phonemes, ref_mel, features, token_prosody = self._lists(phonemes, ref_mel, features, token_prosody)
         req = dict(ref_mel=ref_mel, features=features, voice=voice, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth,
                    fit=fit, forced_durations=forced_durations)
-        return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len, master=master)
+        return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len, master=master, rooms=rooms,
+                         room_sheet=room_sheet)
 
-    def _wav(self, single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=None, max_len=None, master=None):
+    def _wav(self, single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=None, max_len=None, master=None, rooms=None, room_sheet=None):
         """synthesis_wav on lists: req = packed_inputs' keyword arguments"""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
         rs, marker = self._out_resampler(sample_rate), self._marker(marks, sample_rate)
         if master is not None:
             self._check_master(master, sample_rate)
+        self._check_rooms(rooms, sample_rate)
+        tail = 0 if rooms is None else rooms.tail
         if frame_cap is not None:
             frame_cap = int(frame_cap)
             if req["forced_durations"] is not None:
@@ -808,15 +870,17 @@ class ArtSpeech:
         if max_len is not None and frame_cap is None:
             raise ValueError("max_len goes with frame_cap (without it the frame counts are read back and every stage is sized by them)")
         res, out, off, _, m = self._chain(self.packed_inputs(phonemes, **req), frame_cap, pcm16, sample_rate, marker, window=window,
-                                          max_len=max_len, master=master)
+                                          max_len=max_len, master=master, **self._room_stage(rooms, room_sheet))
         hop = self._hop()
         with torch.cuda.device(self.device):
             if frame_cap is None:
                 frames = list(res["frames2"])
                 off = self._sample_off(frames, rs)                          # every utterance a stream of its own at these prefix sums
+                if tail:                                                    # (the rooms' rule: a non-empty stream grows by the tail)
+                    off = [0] + np.cumsum([n + tail if n > 0 else 0 for n in np.diff(off).tolist()]).tolist()
             else:
                 off, out = self._read_back(out, off, f"synthesis_wav(frame_cap={frame_cap})")
-                lens = [off[b + 1] - off[b] for b in range(len(off) - 1)]
+                lens = [max(off[b + 1] - off[b] - tail, 0) for b in range(len(off) - 1)]
                 # (mel frames, whatever the sample rate: n = ceil(hop f L / M) samples came from f = ceil(n M / L) // hop frames)
                 frames = [n // hop for n in lens] if rs is None else [-((-n * rs.M) // rs.L) // hop for n in lens]
             wav = self._rows(out, off)                                      # (under a capacity: on the host)
@@ -828,21 +892,24 @@ class ArtSpeech:
     @torch.no_grad()
     def synthesis_from_wave(self, phonemes, ref_wave, features=None, forced_durations=None, prosody=None, pcm16=False, frame_cap=None,
                             token_prosody=None, token_smooth=False, ref_rate=24000, sample_rate=None, trim_db=None, marks=False, fit=None, window=None,
-                            max_len=None, master=None):
+                            max_len=None, master=None, rooms=None, room_sheet=None):
         """test.py:94-116 from the phonemizer's output and the (already loaded, trimmed) reference wave on: [resampler ->] log-mel front
         end -> [JDCNet, EMA_Predictor] -> acoustic model -> generator [-> resampler].  Returns the samples (mel frames if no vocoder is
         attached).  ref_rate: the rate of ref_wave (test.py:105-106 resamples to 24 kHz with librosa; here resample.Resampler does, on the
         device, with the library's own filter); sample_rate: the rate of the returned samples (synthesis_wav).  Loading / trimming the
         file and espeak stay with the caller.  trim_db (None: the wave as it came): the silent ends of ref_wave are cut on the device
         before anything else (_trim_ref: the library's own block rule in the spirit of test.py:101, not librosa parity).  fit, window,
-        max_len, master: as synthesis_wav takes them."""
+        max_len, master, rooms, room_sheet: as synthesis_wav takes them."""
         single, phonemes, waves, features, token_prosody = self._lists(phonemes, ref_wave, features, token_prosody)
         req = dict(ref_mel=self._wave_mels(waves, ref_rate, trim_db), features=features, voice=None, prosody=prosody,
                    token_prosody=token_prosody, token_smooth=token_smooth, fit=fit, forced_durations=forced_durations)
         if self.generator is not None:
-            return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len, master=master)
+            return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len, master=master, rooms=rooms,
+                             room_sheet=room_sheet)
         if master is not None:
             raise RuntimeError("master works on samples: attach_vocoder(h, checkpoint) first")
+        if rooms is not None:
+            raise RuntimeError("rooms work on samples: attach_vocoder(h, checkpoint) first")
         if frame_cap is not None:
             raise RuntimeError("frame_cap runs the acoustic model and the generator as one chain: attach_vocoder(h, checkpoint, runtime=True) first")
         if marks is not None and marks is not False:
@@ -851,7 +918,8 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_paragraph(self, sentences, ref_mel=None, voice=None, prosody=None, pause_ms=None, joiner=None, sample_rate=None, pcm16=False,
-                            frame_cap=None, features=None, max_tokens=None, marks=False, fit=None, window=None, max_len=None, master=None):
+                            frame_cap=None, features=None, max_tokens=None, marks=False, fit=None, window=None, max_len=None, master=None,
+                            rooms=None, room_sheet=None):
         """A paragraph as ONE stream: `sentences` is a list of phoneme strings, or one string that text.split_sentences cuts (max_tokens:
         its limit per piece).  The sentences run as one batch through the chain above (the acoustic model and the generator, with frame_cap
         with no read-back in between; the resampler when sample_rate is given), then through join.Joiner on the device -- every sentence
@@ -870,7 +938,10 @@ class ArtSpeech:
         frame_cap): the mel frames the longest sentence may have, as synthesis_wav takes it.
         master (a master.Master at the output's rate): the joined stream brought to its loudness target in LUFS (integrated over the
         whole stream, pauses gated out) and held under its true-peak ceiling, behind the joiner on the device; no length changes, so
-        piece and the marks hold as they are.  Its report is self.last_master_report."""
+        piece and the marks hold as they are.  Its report is self.last_master_report.
+        rooms (a room.Rooms at the output's rate) with room_sheet (dict(room, send_db, dry_db, predelay_ms) of the one stream): the joined
+        stream in a room, behind the joiner and in front of the master; the stream is longer by the bank's tail, piece and the marks are
+        those of the stage (moved with the stream: here not at all)."""
         from .join import Joiner
         from .text import PAUSE_SCALE, split_sentences
         if self.generator is None:
@@ -881,6 +952,7 @@ class ArtSpeech:
         self._check_joiner(joiner, sample_rate)
         if master is not None:
             self._check_master(master, sample_rate)
+        self._check_rooms(rooms, sample_rate)
         pause = joiner.cfg.gap if pause_ms is None else joiner.samples(pause_ms)
         if isinstance(sentences, str):
             sentences, classes = split_sentences(sentences, max_tokens)
@@ -896,7 +968,7 @@ class ArtSpeech:
         marker = self._marker(marks, sample_rate)
         inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody, fit=fit)
         res, stream, out_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, sample_rate, marker,
-                                                     join=joiner, gaps=gaps, window=window, master=master,
+                                                     join=joiner, gaps=gaps, window=window, master=master, **self._room_stage(rooms, room_sheet),
                                                      **({} if frame_cap is None else {"max_len": max_len}))
         with torch.cuda.device(self.device):
             _, stream = self._read_back(stream, out_off, "synthesis_paragraph")     # the one synchronisation: the length, then the stream
@@ -907,7 +979,7 @@ class ArtSpeech:
 
     @torch.no_grad()
     def synthesis_cues(self, lines, ref_mel=None, voice=None, prosody=None, cues=None, bed=None, sample_rate=None, pcm16=False, frame_cap=None,
-                       joiner=None, master=None, marks=False, fit_slots=False, stems=False):
+                       joiner=None, master=None, marks=False, fit_slots=False, stems=False, rooms=None, track_rooms=None):
         """A cue sheet as ONE timeline: `lines` is a list of cues.Line (start_s, phonemes, end_s, track, voice, gain_db) in any order.  The
         lines run as one batch through the chain above, then through the joiner with one group per line (trim, level, fade-in; joiner None:
         Joiner(rate)), then through cues.Cues on the device (cues None: Cues(rate)): every line placed at its start on its track, cut with
@@ -919,7 +991,10 @@ class ArtSpeech:
         Returns (mix 1-D fp32 or int16, report int32 [B][4] = position, late, cut, track per line, in the order of `lines`), then, when
         asked for, stems (a list of 1-D fp32 tensors, one per track), piece int32 [B][4] in the order of `lines` (positions in the packed
         stems; returned with stems or marks) and a marks.SpeechMarks whose utterances stand in the sheet's order (cues.sheet(lines)["order"])
-        and whose positions count from the first sample of each line's track."""
+        and whose positions count from the first sample of each line's track.
+        rooms (a room.Rooms at the output's rate) with track_rooms = {track: (room, send_db)} (or (room, send_db, predelay_ms); a track
+        that is not named stays dry): every named track's wet signal is added to the mix behind the cue stage and in front of the master
+        (as_room_f32's return mode), ringing on behind the track's last line up to the end of the mix; the stems stay dry."""
         from . import cues as cue_mod
         from .join import Joiner
         from .marks import SpeechMarks, kept_symbols
@@ -931,8 +1006,19 @@ class ArtSpeech:
         order = sh["order"]
         ordered = [lines[i] for i in order]
         B = len(ordered)
-        if stems and pcm16 and master is None:
+        if stems and pcm16 and master is None and rooms is None:
             raise ValueError("synthesis_cues: without a master the cue stage writes the int16 itself and keeps no fp32 stems; ask for one of stems and pcm16")
+        self._check_rooms(rooms, sample_rate)
+        room_sheet = None
+        if rooms is not None:
+            G = len(sh["group_off"]) - 1
+            named = {int(k): tuple(v) for k, v in (track_rooms or {}).items()}
+            if any(not 0 <= k < G or len(v) not in (2, 3) for k, v in named.items()):
+                raise ValueError(f"synthesis_cues: track_rooms names tracks 0 .. {G - 1} with (room, send_db) or (room, send_db, predelay_ms)")
+            room_sheet = dict(room=[named[g][0] if g in named else None for g in range(G)], send_db=[named[g][1] if g in named else None for g in range(G)],
+                              predelay_ms=[named[g][2] if g in named and len(named[g]) == 3 else 0.0 for g in range(G)])
+        elif track_rooms is not None:
+            raise ValueError("synthesis_cues: track_rooms go with rooms")
         if cues is None:
             cues = cue_mod.Cues(rate, device=self.device)
         if joiner is None:
@@ -955,7 +1041,7 @@ class ArtSpeech:
             bed = torch.as_tensor(bed, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
         inputs = self.packed_inputs(phonemes, ref_mel, None, voice, prosody, fit=fit)
         res, mix, mix_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, sample_rate, marker, join=joiner,
-                                                  master=master, cues=cues, cue_sheet=sh, bed=bed, mix_cap=True)
+                                                  master=master, cues=cues, cue_sheet=sh, bed=bed, mix_cap=True, **self._room_stage(rooms, room_sheet))
         o = self.last_cues
         with torch.cuda.device(self.device):
             _, mix = self._read_back(mix, mix_off, "synthesis_cues")                   # the one synchronisation: the length, then the mix
@@ -979,7 +1065,8 @@ class ArtSpeech:
         return ret
 
     def synthesis_stream(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, frame_cap=None,
-                         token_prosody=None, token_smooth=False, fit=None, window=64, pcm16=True, sample_rate=None, joiner=None, marks=False):
+                         token_prosody=None, token_smooth=False, fit=None, window=64, pcm16=True, sample_rate=None, joiner=None, marks=False,
+                         rooms=None):
         """synthesis_wav whose samples leave while later ones are still being made: a Python generator over the rounds of the windowed
         vocoder (Generator.forward_packed_windowed).  ONE acoustic call (under frame_cap, or with known frame counts), ONE read-back of the
         B + 1 frame offsets -- the one synchronisation of the acoustic side, and when the device status is checked --, then the generator's
@@ -989,9 +1076,10 @@ class ArtSpeech:
         `rounds_launched` counts the vocoder rounds issued so far; it lives on this object and every call sets it to 0, so two streams of
         one ArtSpeech that are consumed in turns share it: it is a figure for one stream at a time.  24 kHz generator output only:
         sample_rate, a joiner or marks raise ValueError (a streaming resampler and joiner need state of their own).  There is no master=
-        either: integrated loudness is a figure of the whole stream, which does not exist while its first rounds leave."""
-        if sample_rate not in (None, SAMPLE_RATE) or joiner is not None or (marks is not None and marks is not False):
-            raise ValueError("synthesis_stream hands out the generator's own 24 kHz samples: no sample_rate, joiner or marks")
+        either: integrated loudness is a figure of the whole stream, which does not exist while its first rounds leave.  rooms raise
+        ValueError as a resampler does: a room's history crosses the rounds."""
+        if sample_rate not in (None, SAMPLE_RATE) or joiner is not None or (marks is not None and marks is not False) or rooms is not None:
+            raise ValueError("synthesis_stream hands out the generator's own 24 kHz samples: no sample_rate, joiner, marks or rooms")
         if self.generator is None or not self.generator.runtime:
             raise RuntimeError("synthesis_stream needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
         if int(window) < 1:

@@ -1286,6 +1286,76 @@ size_t as_cue_workspace_bytes(int B, int G, int in_cap, int out_cap, int mix_cap
 int as_cue_f32(const as_cue_cfg* cfg, int B, const as_cue_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
 int as_cue_host(const as_cue_cfg* cfg, int B, const as_cue_io* io);
 
+/* ---- rooms: convolution reverb on packed streams and as a send on a mix (csrc/room.hip; the rule: csrc/room_rule.h) ----
+ * A bank of K impulse responses -- designed rooms, measured rooms, a telephone's or a radio's FIR -- laid over G packed streams, each stream
+ * with its own response, send, dry gain and predelay; or, over the stems and the mix of as_cue_f32, added to the mix as a send.
+ * The rule.  Stream g = x[in_off[g] .. in_off[g + 1]) (read clamped to [0, in_cap]), n_g samples; response k = h[ir_off[k] .. ir_off[k + 1])
+ * (clamped to [0, ir_cap]), L_k taps, cut at 2^17 (AS_STATUS_CAPACITY); L_k = 0 is a wet signal of 0.  Per stream, DEVICE arrays [G] read when
+ * the call RUNS: room[g] an index into the bank (< 0: dry only; >= K: dry only and AS_STATUS_BAD_LAYOUT), send[g] the linear wet gain, dry[g]
+ * (NULL: 1), delay[g] the predelay in samples (NULL: 0; clamped to [0, 2^20]).  Wet signal, for every t >= 0: acc = 0.f; for k = 0 .. L - 1
+ * ASCENDING, j = t - delay - k, 0 <= j < n_g: acc = fmaf(h[k], x_g[j], acc); c_g(t) = acc -- one rounding per tap, one order, never a
+ * neighbour's sample: a stream alone gives the bits it has in a batch, the device those of as_room_host.  A non-finite tap is the caller's
+ * error (the output is then not finite; nothing is read or stored out of bounds).
+ * Streams mode (mix_in NULL): output stream g has m_g = n_g + cfg->tail samples (0 for an empty stream), out_off = the prefix sums;
+ * y_g[t] = fmaf(send_g, c_g(t), dry_g xz_g(t)), xz = x inside the stream and 0 in the tail; without a valid room y_g[t] = dry_g xz_g(t);
+ * [out_off[G], out_cap) is 0.  tail = 0, every room negative, dry NULL: the output is the input bit for bit.  piece (optional): without
+ * piece_in piece[g] = {out_off[g], out_off[g] + n_g, 0, n_g}; with piece_in [B] and group_off [G + 1] (a joiner's or the cue stage's table
+ * of the streams) every piece of stream g has out_start / out_end moved by out_off[g] - (stream g's first input sample), src_* as they
+ * were -- what as_marks_f32 needs to stay valid under a tail.  y == x is refused: a tile's history lies in its neighbour's output.
+ * Return mode (mix_in given; the streams are stems on ONE timeline from 0, as as_cue_f32 writes them; G <= 64): T = clamp(mix_off[1], 0,
+ * mix_cap), read on the device; for t < T: a = mix_in[t], for g ascending with a valid room a = fmaf(send_g, c_g(t), a), mix[t] = a -- a
+ * stem rings on behind its own end up to T; [T, mix_cap) is 0.  dry, tail, out_off and piece are not used; y or pcm are refused;
+ * mix == mix_in is allowed.
+ * as_room_io: DEVICE pointers.  Outputs fp32 and / or 16-bit PCM (as_conv_post_pcm_f32's rule on the fp32 value: a NaN stores 0 and raises
+ * AS_STATUS_F16_RANGE).
+ * as_room_f32           at most two launches, sized by out_cap or by G and mix_cap -- streams mode: the samples, whose job search is the
+ *                       layout, and the pieces with a piece_in; return mode: the stems' wet signals into the workspace (G rows of mix_cap
+ *                       samples: every stem's tiles run side by side), then their sum onto the mix in ascending order.  Nothing is read
+ *                       back, uploaded or allocated and no call synchronises -- every call, the first included,
+ *                       can be captured into a hipGraph and replayed with other offsets, samples, taps, rooms and sends.  The streams need
+ *                       more than out_cap, in_off[G] > in_cap or mix_off[1] > mix_cap: AS_STATUS_CAPACITY (the layout is cut there, nothing
+ *                       is read or stored out of bounds; that call's output is void).
+ * as_room_host          the same rule on HOST arrays (every pointer of io is a host pointer; no GPU, no workspace).  AS_ENOSPC where the
+ *                       device raises AS_STATUS_CAPACITY; AS_EDEVICE: a NaN went to pcm, or a room index was >= K.
+ * as_room_design_host   host only: a room from four numbers, in double, rounded once.  Ls = rt60_ms rate / 1000, L = clamp(ceil(Ls), 1, 2^17);
+ *                       u(k) = int32(lowbias32(seed 0x9E3779B9 + k)) / 2^31; v[k] = u(k) exp(-ln(1000) k / Ls); w[k] = (1 - damping) v[k] +
+ *                       damping w[k - 1]; h = w / sqrt(sum w^2) -- unit energy, so that a send in dB means something.  *n_taps = L; h NULL
+ *                       asks for the length only; AS_ENOSPC: h_cap < L; AS_EINVAL: rate outside [1, 768000], rt60_ms outside [1, 3600000],
+ *                       damping outside [0, 0.95].
+ * as_room_geometry      the sample kernel's tile (outputs of one stream per workgroup) and chunk (taps staged at a time).
+ * AS_EINVAL before anything is launched: cfg, io, ws, in_off, x, ir_off, h, room or send NULL; no sample output; both modes' outputs; mix
+ * outputs without mix_in or the reverse; y == x; G outside [1, 65535], or above 64 in return mode; K outside [1, 4096]; in_cap, ir_cap,
+ * out_cap (streams mode), mix_cap (return mode) outside [1, 2^30]; tail outside [0, 2^20]; piece_in without group_off or with B outside
+ * [1, 65536]; mix_in without mix_off.  AS_ENOSPC: ws_bytes below as_room_workspace_bytes(G, in_cap, out_cap, mix_cap, cfg) (the capacity of
+ * the mode that is not used: 0; returns 0 for arguments it refuses).  AS_EDEVICE while a status bit is set. */
+typedef struct as_room_cfg {
+    int32_t tail, reserved;        /* samples behind every stream for the ring-out (streams mode); 0 */
+} as_room_cfg;
+typedef struct as_room_io {
+    const int32_t* in_off; int32_t in_cap;
+    const float* x;
+    int32_t K; const int32_t* ir_off; int32_t ir_cap;
+    const float* h;
+    const int32_t* room; const float* send; const float* dry; const int32_t* delay;
+    int32_t out_cap;
+    float* y; int16_t* pcm;
+    int32_t* out_off;
+    int32_t B; const int32_t* group_off; const as_join_piece* piece_in;
+    as_join_piece* piece;
+    const float* mix_in; const int32_t* mix_off; int32_t mix_cap;
+    float* mix; int16_t* mix_pcm;
+} as_room_io;
+typedef struct as_room_design {
+    int32_t rate, rt60_ms;         /* samples per second; the time the response takes to fall by 60 dB */
+    float damping;                 /* the one-pole low-pass on the noise: 0 white .. 0.95 dark */
+    uint32_t seed;
+} as_room_design;
+size_t as_room_workspace_bytes(int G, int in_cap, int out_cap, int mix_cap, const as_room_cfg* cfg);
+int as_room_f32(const as_room_cfg* cfg, int G, const as_room_io* io, void* ws, size_t ws_bytes, as_stream_t stream);
+int as_room_host(const as_room_cfg* cfg, int G, const as_room_io* io);
+int as_room_design_host(const as_room_design* d, float* h, int32_t h_cap, int32_t* n_taps);
+int as_room_geometry(int32_t* tile, int32_t* chunk);
+
 /* ---- prosody transfer (csrc/dtw.hip, csrc/dtw_rule.h) -------------------------------------------------------------
  * Speak a sentence the way a recording of it was spoken: synthesise it once (pass A), warp pass A's mel onto the recording's log-mel
  * (dynamic time warping, frame by frame), turn the warp into one prosody row per token (as_plan_set_token_prosody's rows: a duration scale
