@@ -102,6 +102,7 @@ class Cues:
                         gain=r.at(gain), piece_in=r.at(piece), out_cap=out_cap, y=r.at(o["y"]), pcm=r.at(o["pcm"]), out_off=r.at(o["out_off"]),
                         piece=r.at(o["piece"]), report=r.at(o["report"]), bed=r.at(bed), bed_n=0 if bed is None else r.count(bed),
                         mix_cap=int(mix_cap) if mixes else 0, mix=r.at(o["mix"]), mix_pcm=r.at(o["mix_pcm"]), mix_off=r.at(o["mix_off"]))
+        io.keep = (x, off, start, limit, groups, gain, piece, bed)      # (what was uploaded here lives as long as the struct that points at it)
         return io, B, G, r.count(x), o
 
     def forward_packed(self, x, off, start, out_cap, groups=None, limit=None, gain=None, piece=None, bed=None, mix_cap=None, pcm=False, wav=True):

@@ -74,6 +74,7 @@ class Joiner:
         piece, gain = r.empty((B, 4), stage.I32), r.empty(B, stage.F32)
         io = _lib.JoinIO(in_off=r.at(in_off), in_cap=r.count(x), x=r.at(x), G=G, group_off=r.at(groups), gap=r.at(gaps), out_cap=out_cap or 0,
                          y=r.at(y), pcm=r.at(p16), out_off=r.at(out_off), piece=r.at(piece), gain=r.at(gain))
+        io.keep = (x, in_off, groups, gaps)     # (groups and gaps may have been uploaded here: they live as long as the struct that points at them)
         return io, B, (y, p16, out_off, piece, gain)
 
     def forward_packed(self, x, in_off, out_cap, groups=None, gaps=None, pcm=False, wav=True):

@@ -22,10 +22,10 @@ proportional to what the predictor and the controls above ask for.
 
 How a call runs.  Every public call turns "one utterance or lists" into lists at its first lines (``_lists``); everything private takes
 lists.  ``packed_inputs`` is the one place where a request becomes the tensors of ArtsSpeech.forward_packed, ``_forward`` the one call of
-the acoustic model (it returns the result dict), and ``_back_end`` the one chain behind it -- generator -> [resampler] -> [joiner] ->
-[marks] on packed samples and a device offset table -- whether the frame counts were read back or only a capacity is known
-(``_chain``: both regimes; ``chain_cap``: the capturable one).  ``_last_frames`` / ``_last_aux`` are records for the caller, written
-once at the end of a public call (``_record``); nothing in the library reads them.
+the acoustic model (it returns the result dict), and chain.py the one chain behind it -- the generator and one step per stage on packed
+samples and a device offset table -- whether the frame counts were read back or only a capacity is known (``_chain``: both regimes;
+``chain_cap``: the capturable one).  A public call says what it wants there once, as a chain.Stages (``_stages``).  ``_last_frames`` /
+``_last_aux`` are records for the caller, written once at the end of a public call (``_record``); nothing in the library reads them.
 """
 import json
 import math
@@ -33,12 +33,11 @@ import math
 import numpy as np
 import torch
 
-from . import models, stage
+from . import chain, models, stage
+from .chain import SAMPLE_RATE, out_rate
 from .fit import Fit
 from .text import TextCleaner
 from .weights import DEFAULT_STATS, load_distribution
-
-SAMPLE_RATE = 24000             # of the log-mel front end and of the generator (test.py:105-106, Vocoder/config.json)
 
 
 class Voice:
@@ -225,9 +224,9 @@ class ArtSpeech:
         self.textcleaner = TextCleaner()
         self.device = dev
         self.generator = None                       # test.py:119-125: the HiFi-GAN generator (attach_vocoder)
-        self.last_cues = None                       # the dict of the last call's cue stage (`_back_end`), on the device
-        self.last_rooms = None                      # the dict of the last call's rooms stage (`_back_end`), on the device
-        self.last_master_report = None              # the master.Report of the last call with master= (`_back_end`), on the device
+        self.last_cues = None                       # the dict of the last call's cue stage (chain.py), on the device
+        self.last_rooms = None                      # the dict of the last call's rooms stage (chain.py), on the device
+        self.last_master_report = None              # the master.Report of the last call with master= (chain.py), on the device
         self._record(None, None)
 
     def attach_pitch_extractor(self, checkpoint=None):
@@ -402,227 +401,65 @@ class ArtSpeech:
         res["tok_lens"] = inputs["tok_lens"]
         return res
 
-    def _back_end(self, inputs, res, frame_cap=None, max_len=None, pcm16=False, rs=None, join=None, groups=None, gaps=None, join_cap=None,
-                  marker=None, window=None, master=None, cues=None, cue_sheet=None, bed=None, cue_cap=None, mix_cap=None, rooms=None,
-                  room_sheet=None, room_cap=None):
-        """generator -> [resampler rs] -> [joiner join] -> [cues] -> [rooms] -> [master] -> [marks] behind `_forward`'s result, on the current stream; between the stages
-        travel packed fp32 samples and a device offset table [B + 1].  Two regimes: frame_cap None -- the host knows the frame counts
-        (res["frames2"]) and every stage gets exactly the room its samples need; frame_cap=N -- only the device knows them (res["frame_off"]),
-        the generator writes 300 * 2 N samples and the resampler gets out_len(that) + B; no host value is read and, with groups and gaps
-        on the device (or None), nothing is uploaded: the call can be captured.  Decided here and nowhere else: the LAST stage writes the
-        int16 samples of pcm16, every stage before it fp32; the marker is told the size of the buffer its marks point into; and
-        window=frames (a runtime vocoder) makes the generator's windowed call (Generator.forward_packed_windowed: rounds of `window` mel
-        frames per utterance, a workspace that does not grow with the capacity) take the place of the one-piece call -- the stages behind
-        it see the same offsets and, within the generator's bound, the same samples; window=None issues exactly the launches of before.
-        master (a master.Master at the rate of the samples it receives): the loudness gain and the true-peak limiter (as_master_f32) behind
-        the joiner -- or behind the resampler or the generator when those are absent -- on the offsets the chain already has, which it
-        leaves as they are: the marker sees the same offsets.  When present it is the last stage of samples and it alone writes the int16
-        of pcm16; its master.Report (on the device) is kept as self.last_master_report.  master=None issues exactly the launches of before.
-        cues (a cues.Cues at the rate of the samples it receives) with cue_sheet (dict(group_off, start, limit, gain) as cues.sheet gives
-        them, in batch order; lists are uploaded, device tensors are taken as they are): every utterance is placed at its start on its
-        track (as_cue_f32).  A joiner in front of it runs with ONE GROUP PER UTTERANCE (it trims, levels and fades; groups and gaps are not
-        taken, its lead and tail must be 0) and hands its piece table on.  bed (fp32 device samples) or mix_cap: the tracks are mixed over
-        the ducked bed (mix_cap True: a mix, with the default room), and the mix with its mix_off [2] is what travels on -- to the master, and back to the caller; else the stems with
-        their out_off [G + 1].  cue_cap / mix_cap None: what always suffices, which needs the starts as a list.  The marker gets the stage's
-        piece table, tracks and the STEMS' out_off: marks are positions in the stems' buffer.  The stage's dict (Cues.forward_packed) is
-        kept as self.last_cues.  cues=None issues exactly the launches of before.
-        rooms (a room.Rooms at the rate of the samples it receives) with room_sheet (dict(room, send_db, dry_db, predelay_ms), each one
-        value or one per stream -- per track behind cues --; device tensors are taken as they are, in the library's units: room int32,
-        send and dry linear fp32, predelay int32 samples): convolution reverb (as_room_f32) between cues and master.  Behind a cue MIX it
-        runs in return mode: the cue stage writes fp32 stems and mix, every track's wet signal is added to the mix, which travels on (dry_db
-        is not used: the mix is the dry signal).  Else in streams mode on the offsets the chain has: every non-empty stream grows by the
-        bank's tail, the offsets and the piece table that travel on are the stage's own, room_cap (None: what always suffices) is its
-        room; marks with a tail need a piece table (a joiner or cues in front).  The stage's dict is kept as self.last_rooms.  With the
-        sheet on the device the chain stays capturable; rooms=None issues exactly the launches of before.
-        -> (samples fp32 or int16, off [B + 1] -- behind a joiner out_off [G + 1] --, piece [B][4] or None, Marker.forward_packed's dict or
-        None), all on the device."""
-        from .models import layout
-        gen, dev = self.generator, torch.device(self.device)
-        B = res["frame_off"].numel() - 1
-        last = "master" if master is not None else "rooms" if rooms is not None else "cues" if cues is not None else "join" if join is not None else "rs" if rs is not None else "gen"
-        with torch.cuda.device(self.device):
-            p = pcm16 and last == "gen"
-            if window is not None and not gen.runtime:
-                raise RuntimeError("window needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
-            if frame_cap is None and window is None:
-                # (the packed mel as forward_packed wrote it; the operator-level generator always writes fp32 too)
-                wav, lay_w, *pcm = gen.forward_packed(res["mel"], layout(res["frames2"], gen.device), pcm=p)
-                x, off = wav.reshape(-1)[: max(lay_w.N, 1)], lay_w.col_off
-            else:
-                if frame_cap is None:                                       # (the host knows the lengths: the capacity is their sum)
-                    lay = layout(res["frames2"], gen.device)
-                    lay_w = lay.scaled(gen.hop)
-                    geo = (lay.col_off, 1, max(lay.N, 1))
-                    max_len = max(lay.max_w, 1)
-                else:
-                    geo = (res["frame_off"], 2, 2 * frame_cap)
-                if window is not None:
-                    wav, off, *pcm = gen.forward_packed_windowed(res["mel"], *geo, window, max_len=max_len, pcm=p, wav=not p)
-                else:
-                    wav, off, *pcm = gen.forward_packed_cap(res["mel"], *geo, max_len=max_len, pcm=p, wav=not p)
-                x = None if p else wav[0]
-            out = pcm[0] if p else x
-            if rs is not None:
-                p = pcm16 and last == "rs"
-                room = max(sum(rs.out_len(n) for n in lay_w.widths_host), 1) if frame_cap is None else rs.out_len(x.numel()) + B
-                y, p16, off = rs.forward_packed(x, off, room, pcm=p, wav=not p)
-                out = x = p16 if p else y
-            piece = None
-            if join is not None and cues is not None:
-                if groups is not None or gaps is not None or join.cfg.lead or join.cfg.tail:
-                    raise ValueError("a joiner in front of cues runs with one group per utterance: no groups, no gaps, lead_ms = tail_ms = 0")
-                if "_cue_join_groups" not in inputs:                                    # (uploaded by the first, eager call: a captured one finds it)
-                    inputs["_cue_join_groups"] = torch.arange(B + 1, dtype=torch.int32).to(self.device)
-                groups = inputs["_cue_join_groups"]
-                if join_cap is None:
-                    join_cap = join.out_cap(x.numel(), B, B, 0)
-            if join is not None:
-                G = 1 if groups is None else len(groups) - 1
-                if groups is not None:
-                    groups = stage.Device(dev).values_i32(groups, G + 1, "forward_packed", "groups")  # (the joiner and the marker read ONE device copy)
-                if join_cap is None:                                                    # what always suffices: every sample kept, every gap in place
-                    if torch.is_tensor(gaps):
-                        raise ValueError("gaps on the device: name join_cap, the samples of room for the joined streams")
-                    join_cap = join.out_cap(x.numel(), B, G, None if gaps is None else max(max(int(v) for v in gaps), 0))
-                p = pcm16 and last == "join"
-                y, p16, off, piece, _ = join.forward_packed(x, off, join_cap, groups=groups, gaps=gaps, pcm=p, wav=not p)
-                out = x = p16 if p else y
-            marks_off = off
-            if cues is not None:
-                if cue_sheet is None:
-                    raise ValueError("cues go with a cue_sheet (cues.sheet): group_off, start, limit, gain")
-                r, starts = stage.Device(dev), cue_sheet["start"]
-                G = len(cue_sheet["group_off"]) - 1
-                mixes = bed is not None or mix_cap is not None
-                if mix_cap is True:                                                     # (a mix, of whatever always suffices)
-                    mix_cap = None
-                if (cue_cap is None or (mixes and mix_cap is None)) and torch.is_tensor(starts):
-                    raise ValueError("starts on the device: name cue_cap (and mix_cap with a mix), the samples of room for the tracks")
-                if cue_cap is None:
-                    cue_cap = cues.out_cap(x.numel(), starts, G)
-                if mixes and mix_cap is None:
-                    mix_cap = cues.out_cap(x.numel(), starts, 1)
-                groups = r.values_i32(cue_sheet["group_off"], G + 1, "forward_packed", "group_off")   # (the stage and the marker read ONE device copy)
-                gain = cue_sheet.get("gain")
-                if gain is not None and not torch.is_tensor(gain):
-                    gain = torch.from_numpy(np.ascontiguousarray(gain, np.float32)).to(dev)
-                p = pcm16 and last == "cues"
-                o = self.last_cues = cues.forward_packed(x, off, starts, cue_cap, groups=groups, limit=cue_sheet.get("limit"), gain=gain, piece=piece,
-                                                         bed=bed, mix_cap=mix_cap if mixes else None, pcm=p, wav=not p)
-                piece, marks_off = o["piece"], o["out_off"]
-                x, off = (o["mix_pcm" if p else "mix"], o["mix_off"]) if mixes else (o["pcm" if p else "y"], o["out_off"])
-                out = x
-            marks_room = None if cues is None else int(cue_cap)
-            if rooms is not None:
-                sh = dict(room_sheet or {})
-                sheet = dict(room=sh.get("room", 0), send_db=sh.get("send_db", -12.0), predelay_ms=sh.get("predelay_ms", 0.0))
-                p = pcm16 and last == "rooms"
-                if cues is not None and mixes:                                          # a send on the mix: the stems' wet signals return to it
-                    o = self.last_rooms = rooms.return_to(x, off, self.last_cues["y"], self.last_cues["out_off"], pcm=p, wav=not p, **sheet)
-                    out = x = o["mix_pcm" if p else "mix"]
-                else:
-                    if marker is not None and rooms.tail and piece is None:
-                        raise ValueError("rooms with a tail move every stream: marks then need a piece table (a joiner or cues in front of the rooms)")
-                    G = off.numel() - 1
-                    if piece is not None and groups is None:                            # (one joined stream: every piece is its own)
-                        if "_room_groups" not in inputs:                                # (uploaded by the first, eager call: a captured one finds it)
-                            inputs["_room_groups"] = torch.tensor([0, piece.shape[0]], dtype=torch.int32).to(self.device)
-                        groups = inputs["_room_groups"]
-                    if room_cap is None:
-                        room_cap = rooms.out_cap(x.numel(), G)
-                    o = self.last_rooms = rooms.forward_packed(x, off, dry_db=sh.get("dry_db", 0.0), out_cap=room_cap, pcm=p, wav=not p, piece=piece,
-                                                               groups=None if piece is None else groups, **sheet)
-                    out = x = o["pcm" if p else "y"]
-                    off = o["out_off"]
-                    if piece is not None:
-                        piece, marks_off = o["piece"], off
-                    marks_room = int(room_cap)
-            if master is not None:
-                y, p16, self.last_master_report = master.forward_packed(x, off, pcm=pcm16, wav=not pcm16)
-                out = p16 if pcm16 else y
-            m = None
-            if marker is not None:
-                if "_tok_off" not in inputs:                                            # (uploaded by the first, eager call: a captured one finds it)
-                    inputs["_tok_off"] = torch.tensor(np.concatenate([[0], np.cumsum(inputs["tok_lens"])]), dtype=torch.int32).to(self.device)
-                scale, offset = marker.affine(_stats24(self), dev) if marker.physical else (None, None)
-                G = B if piece is None else marks_off.numel() - 1
-                room = out.numel() if marks_room is None else marks_room
-                m = marker.forward_packed(inputs["_tok_off"], res["dur_i"], res["frame_off"], res["F0"], res["N"], res["EMA"], piece=piece,
-                                          groups=groups, out_off=None if piece is None else marks_off, anim_cap=marker.anim_cap(room, G),
-                                          scale=scale, offset=offset)
-        return out, off, piece, m
+    def _stages(self, sample_rate, marks=None, **want):
+        """THE place where a public call's keywords become a chain.Stages, checked, with the resampler and the marker of sample_rate / marks"""
+        st = chain.Stages(**want).check(out_rate(sample_rate))
+        st.rs, st.marker = self._out_resampler(sample_rate), self._marker(marks, sample_rate)
+        return st
 
-    def _chain(self, inputs, frame_cap, pcm16, sample_rate, marker, **stages):
-        """tokens -> samples: `_forward` then `_back_end` (stages: its max_len / join / groups / gaps / join_cap / master), in either regime.
-        frame_cap None: the frame counts are read back between the two (the one host read; the result has everything `aux` has);
-        frame_cap=N: no host value is read, and every call with the same inputs dict reuses the acoustic model's output tensors
-        (inputs["_out"]).  -> (res, samples, off, piece, marks)"""
+    def _back_end(self, inputs, res, st, frame_cap=None, pcm16=False):
+        """chain.run behind `_forward`'s result on the current stream: the stages of `st` (a chain.Stages) in either regime, their uploads
+        under stage.Device, last_cues / last_rooms / last_master_report written here -> (samples, off, piece or None, marks or None)"""
+        with torch.cuda.device(self.device):
+            s = chain.State(stage.Device(torch.device(self.device)), self.generator, inputs, res, frame_cap, self, lambda: _stats24(self))
+            return chain.run(s, st, pcm16)
+
+    def _chain(self, inputs, frame_cap, pcm16, st):
+        """tokens -> samples: `_forward` then `_back_end` with the stages `st` -> (res, samples, off, piece, marks).  frame_cap None: the frame
+        counts are read back between the two (the one host read); N: none is, and the acoustic model reuses its outputs in inputs["_out"]."""
         if frame_cap is not None and (self.generator is None or not self.generator.runtime):
             raise RuntimeError("frame_cap needs a runtime vocoder: attach_vocoder(h, checkpoint, runtime=True)")
+        more = dict(aux=True) if frame_cap is None else dict(frame_cap=frame_cap, out=inputs.setdefault("_out", {}), tracks=st.marker is not None)
         with torch.cuda.device(self.device):
-            if frame_cap is None:
-                res = self._forward(inputs, aux=True)
-            else:
-                res = self._forward(inputs, frame_cap=frame_cap, out=inputs.setdefault("_out", {}), tracks=marker is not None)
-            return (res,) + self._back_end(inputs, res, frame_cap=frame_cap, pcm16=pcm16, rs=self._out_resampler(sample_rate), marker=marker,
-                                           **stages)
+            res = self._forward(inputs, **more)
+            return (res,) + self._back_end(inputs, res, st, frame_cap, pcm16)
 
     def chain_cap(self, inputs, frame_cap, pcm16=False, max_len=None, sample_rate=None, join=None, groups=None, gaps=None, join_cap=None,
                   marks=None, window=None, master=None, cues=None, cue_sheet=None, bed=None, cue_cap=None, mix_cap=None, rooms=None,
                   room_sheet=None, room_cap=None):
         """tokens -> samples under a frame capacity, on the current stream, with no host value read in between: forward_packed(frame_cap=)
-        then the capacity vocoder on its frame_off and mel (`_chain`).  `inputs` = packed_inputs(...).  Every call with the same inputs dict
-        reuses the acoustic model's output tensors; the whole call can be captured (after one eager call has sized the workspaces) and replayed
-        with other token / voice / prosody contents of the same geometry.  -> (samples [300 * 2 frame_cap], sample_off [B + 1]), both on the
-        device.  sample_rate (other than None / 24000): the generator writes fp32 and resample.Resampler(24000, sample_rate) runs on its
-        device sample_off on the same stream -> (samples [ceil(600 frame_cap L / M) + B], out_off [B + 1]); still no host value, still capturable.
-        join (a join.Joiner at the rate of the samples; groups / gaps / join_cap as Joiner.forward_packed takes them; join_cap None: what
-        always suffices, which needs the gaps as a list or None): the joiner runs on the device offsets the chain already has -- sample_off,
-        or the resampler's out_off -- on the same stream, and the call returns (stream [join_cap] fp32 or int16, out_off [G + 1], piece
-        [B][4]) instead; with groups and gaps as device tensors (or None) the chain stays capturable.
-        marks (a marks.Marker for this chain: its rate, the resampler's ratio, the generator's hop): the acoustic model also hands out
-        F0 / N / EMA and as_marks_f32 runs on the same stream behind the joiner -- or behind the resampler or the generator when there is
-        none -- on the device durations, offsets and pieces the chain already has; the call returns what it returns without marks and, as
-        one more entry, the dict of Marker.forward_packed (marks [sum tok_lens][2], tracks [12][anim_cap], active, anim_off), all on the
-        device.  The chain stays capturable (after one eager call, which also uploads the token offsets); marks=None issues exactly the
-        launches of before.
-        window (mel frames; None: the one-piece generator, exactly the launches of before): the generator runs in rounds of `window` frames
-        per utterance (`_back_end`): same offsets, same samples within its bound, and its workspace no longer grows with frame_cap.  The
-        call issues ceil(max_len / window) rounds -- max_len None: ceil(2 frame_cap / window), most of them past every utterance's end --,
-        so name max_len, the mel frames the longest utterance may have, with it.
-        master (a master.Master at the rate of the samples): the last stage of samples (`_back_end`) -- every stream of the result brought
-        to its loudness target and held under its true-peak ceiling, at the same offsets; the chain stays capturable, and the stage's
-        Report is self.last_master_report (a device tensor: reading it synchronises).  master=None issues exactly the launches of before.
-        cues (a cues.Cues at the rate of the samples) with cue_sheet, bed, cue_cap, mix_cap (`_back_end`): every utterance is placed at
-        its start on its track, behind a joiner of one group per utterance when join is given; the call returns (mix [mix_cap], mix_off
-        [2], piece [B][4]) with a bed or a mix_cap, else (stems [cue_cap], out_off [G + 1], piece); the stage's whole dict is
-        self.last_cues.  With the sheet on the device and the capacities named the chain stays capturable; cues=None issues exactly the
-        launches of before.
-        rooms (a room.Rooms at the rate of the samples) with room_sheet and room_cap (`_back_end`): convolution reverb between cues and
-        master -- per stream (the offsets, and the pieces behind a joiner or cues, that the call returns are the stage's own: every
-        non-empty stream grows by the bank's tail) or, behind a cue mix, as a send of every track on the mix; the stage's dict is
-        self.last_rooms.  With the sheet on the device and room_cap named the chain stays capturable; rooms=None issues exactly the
-        launches of before."""
-        if join is not None:
-            self._check_joiner(join, sample_rate)
-        if cues is not None and cues.rate != (SAMPLE_RATE if sample_rate is None else int(sample_rate)):
-            raise ValueError(f"the cues count their milliseconds at {cues.rate} Hz, the samples they are given are at another rate")
-        if master is not None:
-            self._check_master(master, sample_rate)
-        self._check_rooms(rooms, sample_rate)
-        _, out, off, piece, m = self._chain(inputs, frame_cap, pcm16, sample_rate, self._marker(marks, sample_rate), max_len=max_len, join=join,
-                                            groups=groups, gaps=gaps, join_cap=join_cap, window=window, master=master, cues=cues, cue_sheet=cue_sheet,
-                                            bed=bed, cue_cap=cue_cap, mix_cap=mix_cap, **self._room_stage(rooms, room_sheet, room_cap))
+        then the chain of chain.py on its frame_off and mel; each stage's contract is its step's docstring there, and a stage that is None
+        takes no part.  `inputs` = packed_inputs(...): every call with the same dict reuses the acoustic model's output tensors and the
+        chain's few uploads.  The whole call can be captured (after one eager call) and replayed with other token / voice / prosody contents
+        of the same geometry, as long as every list below is a device tensor or None and every capacity a list would have sized is named.
+        -> (samples [300 * 2 frame_cap] fp32, int16 with pcm16, sample_off [B + 1]), on the device as everything returned.  With
+        sample_rate (other than None / 24000): (samples [ceil(600 frame_cap L / M) + B], out_off [B + 1]) behind resample.Resampler;
+        join (a join.Joiner; groups, gaps, join_cap as Joiner.forward_packed takes them): (streams [join_cap], out_off [G + 1], piece [B][4]);
+        cues (a cues.Cues) with cue_sheet, bed, cue_cap, mix_cap, behind a joiner of one group per utterance when join is given: (mix
+        [mix_cap], mix_off [2], piece) with a bed or a mix_cap, else (stems [cue_cap], out_off [G + 1], piece), the whole dict in last_cues;
+        rooms (a room.Rooms) with room_sheet, room_cap: reverb per stream -- the offsets and pieces returned are the stage's own -- or as a
+        send on a cue mix, its dict in last_rooms; master (a master.Master): the same offsets, its Report in last_master_report (a device
+        tensor: reading it synchronises); marks (True or a marks.Marker for this chain): one more entry, Marker.forward_packed's dict.
+        max_len: the mel frames the longest utterance may have (None: 2 frame_cap); window (mel frames): the generator in rounds, its
+        workspace no longer grows with frame_cap -- ceil(max_len / window) rounds, so name max_len with it.  join_cap, cue_cap, mix_cap
+        (True), room_cap None: what always suffices.  join, cues, rooms and master count time at the rate of the samples returned."""
+        st = self._stages(sample_rate, marks, max_len=max_len, join=join, groups=groups, gaps=gaps, join_cap=join_cap, window=window, master=master,
+                          cues=cues, cue_sheet=cue_sheet, bed=bed, cue_cap=cue_cap, mix_cap=mix_cap, rooms=rooms, room_sheet=room_sheet, room_cap=room_cap)
+        _, out, off, piece, m = self._chain(inputs, frame_cap, pcm16, st)
         ret = (out, off) if join is None and cues is None else (out, off, piece)
         return ret if m is None else ret + (m,)
 
-    def _read_back(self, samples, off, what):
-        """the one synchronisation of a chain whose lengths only the device knows: the offsets first, then the status check, then the
-        samples in front of the last offset -> (off as a host list, those samples on the host)"""
+    def _checked(self, t, head, tail="; results since then are invalid"):
+        """THE status-checked read-back: device offsets or spans as a host list (the copy synchronises), then the status check"""
         from . import _lib
-        off = off.cpu().tolist()
+        host = t.cpu().tolist()
         if _lib.lib().as_device_status(0):
-            raise _lib.HipLibraryError(f"{what} failed: a kernel reported {_lib.device_status()} (as_device_status); results since then are invalid")
+            raise _lib.HipLibraryError(f"{head}: a kernel reported {_lib.device_status()} (as_device_status){tail}")
+        return host
+
+    def _read_back(self, samples, off, what):
+        """the one synchronisation of a chain whose lengths only the device knows -> (off as a host list, the samples in front of off[-1])"""
+        off = self._checked(off, f"{what} failed")
         return off, samples[: off[-1]].cpu()
 
     def _sample_off(self, frames2, rs):
@@ -670,7 +507,6 @@ class ArtSpeech:
         the last.  This is the library's own block rule in the spirit of test.py:101 (librosa.effects.trim(top_db=30): frames of 2048
         samples every 512, RMS against the peak frame); it is NOT librosa parity -- the frames, the hop and the margin differ, and
         nothing here pins librosa's result.  Returns device tensors."""
-        from . import _lib
         from .join import Joiner
         single = not isinstance(ref_wave, (list, tuple))
         waves = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in ([ref_wave] if single else ref_wave)]
@@ -679,14 +515,12 @@ class ArtSpeech:
             raise ValueError("trim_db: an empty reference wave")
         with torch.cuda.device(self.device):
             x = torch.cat([w.to(self.device) for w in waves]).contiguous()
-            off = np.concatenate([[0], np.cumsum(lens)])
-            kept, _ = Joiner(rate, trim_db=trim_db, keep_ms=self.REF_KEEP_MS, device=self.device).measure(x, torch.tensor(off, dtype=torch.int32).to(self.device))
-            kept = kept.cpu().tolist()
-            if _lib.lib().as_device_status(0):
-                raise _lib.HipLibraryError(f"trim_db: a kernel reported {_lib.device_status()} (as_device_status): a sample of the reference is not finite")
+            off = chain.prefix_i32(stage.Device(torch.device(self.device)), lens)
+            kept, _ = Joiner(rate, trim_db=trim_db, keep_ms=self.REF_KEEP_MS, device=self.device).measure(x, off)
+            kept = self._checked(kept, "trim_db", ": a sample of the reference is not finite")
         if any(e <= s for s, e in kept):
             raise ValueError("trim_db: a reference wave is silent throughout")
-        out = [x[int(off[b]) + s: int(off[b]) + e] for b, (s, e) in enumerate(kept)]
+        out = [w[s:e] for w, (s, e) in zip(x.split(lens), kept)]
         return out[0] if single else out
 
     def _ref_at_24k(self, ref_wave, rate):
@@ -700,31 +534,7 @@ class ArtSpeech:
         from .resample import resampler
         return resampler(SAMPLE_RATE, sample_rate, self.device)
 
-    # ------------------------------------------------------------------ joiner and marks
-    def _check_joiner(self, join, sample_rate):
-        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
-        if join.rate != rate:
-            raise ValueError(f"the joiner counts its milliseconds at {join.rate} Hz, the samples it is given are at {rate} Hz")
-
-    def _check_master(self, master, sample_rate):
-        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
-        if master.rate != rate:
-            raise ValueError(f"the master's filters are designed for {master.rate} Hz, the samples it is given are at {rate} Hz")
-
-    def _check_rooms(self, rooms, sample_rate):
-        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
-        if rooms is not None and rooms.rate != rate:
-            raise ValueError(f"the rooms' responses are sampled at {rooms.rate} Hz, the samples they are given are at {rate} Hz")
-
-    @staticmethod
-    def _room_stage(rooms, room_sheet=None, room_cap=None):
-        """`_back_end`'s keywords of the rooms stage: none at all without rooms (a call without them is the call of before)"""
-        if rooms is None:
-            if room_sheet is not None or room_cap is not None:
-                raise ValueError("room_sheet and room_cap go with rooms")
-            return {}
-        return dict(rooms=rooms, room_sheet=room_sheet, room_cap=room_cap)
-
+    # ------------------------------------------------------------------ marks
     def _hop(self):
         """samples per mel frame of the attached generator: the product of its up-sampling rates (300)"""
         return int(np.prod([int(u) for u in self.generator.h["upsample_rates"]]))
@@ -735,8 +545,7 @@ class ArtSpeech:
         from .marks import Marker
         if self.generator is None:
             raise RuntimeError("marks time the samples: attach_vocoder(h, checkpoint) first")
-        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
-        return Marker(rate, fps=fps, hop=self._hop(), resampler=self._out_resampler(sample_rate), physical=physical)
+        return Marker(out_rate(sample_rate), fps=fps, hop=self._hop(), resampler=self._out_resampler(sample_rate), physical=physical)
 
     def _marker(self, marks, sample_rate):
         """synthesis_*'s `marks` argument -> a marks.Marker for samples at sample_rate, or None: True makes one at 60 frames per second, a
@@ -750,18 +559,17 @@ class ArtSpeech:
             raise TypeError("marks: True, False or a marks.Marker")
         if self.generator is None:
             raise RuntimeError("marks time the samples: attach_vocoder(h, checkpoint) first")
-        rs = self._out_resampler(sample_rate)
-        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        rs, rate = self._out_resampler(sample_rate), out_rate(sample_rate)
         want = (self._hop(), 1, 1, rate) if rs is None else (self._hop(), rs.L, rs.M, rate)
         have = (marks.cfg.hop, marks.cfg.L, marks.cfg.M, marks.cfg.rate)
         if have != want:
             raise ValueError(f"the marker describes a chain of (hop, L, M, rate) = {have}, the samples it is to mark come from {want}")
         return marks
 
-    def _speech_marks(self, marker, phonemes, m, piece=None, stream_off=None):
-        """the device results of the chain's marker (`_back_end`) -> marks.SpeechMarks (copies them to the host).  piece (host [B][4]): the
-        utterances lie in joined streams, positions are absolute; stream_off (host [B + 1]): every utterance is a stream of its own,
-        positions count from its own first sample"""
+    def _speech_marks(self, marker, phonemes, m, piece=None, stream_off=None, origin=None):
+        """the device results of the chain's marker (chain.py) -> marks.SpeechMarks (copies them to the host).  piece (host [B][4]): the
+        utterances lie in joined streams, positions are absolute -- or count from origin [B], when given; stream_off (host [B + 1]): every
+        utterance is a stream of its own, positions count from its own first sample"""
         from .marks import SpeechMarks, kept_symbols
         syms = [kept_symbols(self.textcleaner, p) for p in phonemes]
         anim_off = m["anim_off"].cpu().numpy()
@@ -769,7 +577,7 @@ class ArtSpeech:
         marks_h = m["marks"].cpu().numpy()[: sum(len(s) for s in syms)]
         tracks, active = m["tracks"][:, :n].cpu().numpy(), m["active"][:n].cpu().numpy()
         if piece is not None:
-            spans, origin = [(int(p[0]), int(p[1])) for p in piece], None
+            spans = [(int(p[0]), int(p[1])) for p in piece]
         else:
             spans, origin = [(int(stream_off[b]), int(stream_off[b + 1])) for b in range(len(syms))], [int(v) for v in stream_off[:-1]]
         return SpeechMarks(marker.rate, marker.fps, syms, marks_h, spans, origin, tracks, active, anim_off)
@@ -826,9 +634,8 @@ class ArtSpeech:
     def synthesis_wav(self, phonemes, ref_mel=None, features=None, forced_durations=None, voice=None, prosody=None, pcm16=False,
                       frame_cap=None, token_prosody=None, token_smooth=False, sample_rate=None, marks=False, fit=None, window=None,
                       max_len=None, master=None, rooms=None, room_sheet=None):
-        """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames]
-        (one utterance: 1-D), samples beyond an utterance's own length are zero.  The packed mel goes straight into the
-        generator: no padding is ever synthesised.  pcm16=True: int16 samples, converted by the chain's last kernel.
+        """test.py:113-116: mel from the acoustic model, then ``generator(mel).squeeze()`` -> [B, 300 * frames] (one utterance: 1-D), samples
+        beyond an utterance's own length are zero.  No padding is ever synthesised.  pcm16=True: int16 samples, by the chain's last kernel.
         frame_cap=N (predicted durations, a runtime vocoder): room for N half-rate frames, all utterances together -- the acoustic model
         hands its device frame_off and mel straight to the generator on the same stream (chain_cap): no host value is read between the
         tokens and the samples, then ONE copy brings the sample offsets and the samples back.
@@ -840,37 +647,31 @@ class ArtSpeech:
         token and word is spoken, in samples and seconds from the start of its own utterance's row, and F0, energy and the articulators
         on the animation clock (as_marks_f32 on the device results the call already has, read back with the samples).
         fit: a Fit (fit.py) -- Fit.whole(s) gives every utterance rint(40 s) * 600 samples at 24 kHz, spans give their tokens an exact time.
-        window (mel frames, a runtime vocoder): the generator in rounds of that many frames per utterance (`_back_end`).
-        max_len (with frame_cap): the mel frames the longest utterance may have (None: 2 frame_cap) -- it sizes the generator's grids and,
-        with window, is what the number of rounds is taken from: ceil(max_len / window); a longer utterance raises AS_STATUS_CAPACITY.
-        master (a master.Master at the output's rate): every utterance brought to its loudness target in LUFS and held under its
-        true-peak ceiling on the device, as the chain's last stage (`_back_end`); its report is self.last_master_report.
-        rooms (a room.Rooms at the output's rate) with room_sheet (dict(room, send_db, dry_db, predelay_ms), one value or one per
-        utterance): convolution reverb on every utterance in front of the master (`_back_end`); every row is longer by the bank's tail
-        (marks then raise ValueError: they need a piece table)."""
+        The stages behind the generator are chain.py's, each described at its step.  window (mel frames, a runtime vocoder): the generator
+        in rounds of that many frames per utterance.  max_len (with frame_cap): the mel frames the longest utterance may have (None: 2
+        frame_cap); with window there are ceil(max_len / window) rounds; a longer utterance raises AS_STATUS_CAPACITY.  master (a
+        master.Master at the output's rate): every utterance brought to its loudness target in LUFS and held under its true-peak ceiling;
+        its report is self.last_master_report.  rooms (a room.Rooms at the output's rate) with room_sheet (dict(room, send_db, dry_db,
+        predelay_ms), one value or one per utterance): convolution reverb on every utterance in front of the master; every row is longer
+        by the bank's tail (marks then raise ValueError: they need a piece table)."""
         single, phonemes, ref_mel, features, token_prosody = self._lists(phonemes, ref_mel, features, token_prosody)
         req = dict(ref_mel=ref_mel, features=features, voice=voice, prosody=prosody, token_prosody=token_prosody, token_smooth=token_smooth,
                    fit=fit, forced_durations=forced_durations)
-        return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len, master=master, rooms=rooms,
-                         room_sheet=room_sheet)
-
-    def _wav(self, single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=None, max_len=None, master=None, rooms=None, room_sheet=None):
-        """synthesis_wav on lists: req = packed_inputs' keyword arguments"""
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
-        rs, marker = self._out_resampler(sample_rate), self._marker(marks, sample_rate)
-        if master is not None:
-            self._check_master(master, sample_rate)
-        self._check_rooms(rooms, sample_rate)
-        tail = 0 if rooms is None else rooms.tail
+        st = self._stages(sample_rate, marks, window=window, max_len=max_len, master=master, rooms=rooms, room_sheet=room_sheet)
+        return self._wav(single, phonemes, req, st, pcm16, frame_cap)
+
+    def _wav(self, single, phonemes, req, st, pcm16, frame_cap):
+        """synthesis_wav on lists: req = packed_inputs' keyword arguments, st = the call's stages"""
+        rs, marker, tail = st.rs, st.marker, 0 if st.rooms is None else st.rooms.tail
         if frame_cap is not None:
             frame_cap = int(frame_cap)
             if req["forced_durations"] is not None:
                 raise ValueError("frame_cap goes with predicted durations (no forced_durations)")
-        if max_len is not None and frame_cap is None:
+        if st.max_len is not None and frame_cap is None:
             raise ValueError("max_len goes with frame_cap (without it the frame counts are read back and every stage is sized by them)")
-        res, out, off, _, m = self._chain(self.packed_inputs(phonemes, **req), frame_cap, pcm16, sample_rate, marker, window=window,
-                                          max_len=max_len, master=master, **self._room_stage(rooms, room_sheet))
+        res, out, off, _, m = self._chain(self.packed_inputs(phonemes, **req), frame_cap, pcm16, st)
         hop = self._hop()
         with torch.cuda.device(self.device):
             if frame_cap is None:
@@ -904,8 +705,8 @@ class ArtSpeech:
         req = dict(ref_mel=self._wave_mels(waves, ref_rate, trim_db), features=features, voice=None, prosody=prosody,
                    token_prosody=token_prosody, token_smooth=token_smooth, fit=fit, forced_durations=forced_durations)
         if self.generator is not None:
-            return self._wav(single, phonemes, req, pcm16, frame_cap, sample_rate, marks, window=window, max_len=max_len, master=master, rooms=rooms,
-                             room_sheet=room_sheet)
+            st = self._stages(sample_rate, marks, window=window, max_len=max_len, master=master, rooms=rooms, room_sheet=room_sheet)
+            return self._wav(single, phonemes, req, st, pcm16, frame_cap)
         if master is not None:
             raise RuntimeError("master works on samples: attach_vocoder(h, checkpoint) first")
         if rooms is not None:
@@ -934,25 +735,18 @@ class ArtSpeech:
         as_marks_f32 behind the joiner, read back with the stream.
         fit: a Fit whose utterances are the sentences -- Fit.whole([2.0, 3.5, None]) gives every sentence its slot (subtitles) on the
         vocoder's clock, before the joiner trims and spaces them.
-        window (mel frames, a runtime vocoder): the generator in rounds of that many frames per sentence (`_back_end`); max_len (with
-        frame_cap): the mel frames the longest sentence may have, as synthesis_wav takes it.
-        master (a master.Master at the output's rate): the joined stream brought to its loudness target in LUFS (integrated over the
-        whole stream, pauses gated out) and held under its true-peak ceiling, behind the joiner on the device; no length changes, so
-        piece and the marks hold as they are.  Its report is self.last_master_report.
-        rooms (a room.Rooms at the output's rate) with room_sheet (dict(room, send_db, dry_db, predelay_ms) of the one stream): the joined
-        stream in a room, behind the joiner and in front of the master; the stream is longer by the bank's tail, piece and the marks are
-        those of the stage (moved with the stream: here not at all)."""
+        window, max_len: as synthesis_wav takes them, per sentence.  master (a master.Master at the output's rate): the joined stream
+        brought to its loudness target in LUFS (integrated over the whole stream, pauses gated out) and held under its true-peak ceiling,
+        behind the joiner; no length changes, so piece and the marks hold as they are.  Its report is self.last_master_report.  rooms (a
+        room.Rooms at the output's rate) with room_sheet (dict(room, send_db, dry_db, predelay_ms) of the one stream): the joined stream
+        in a room, behind the joiner and in front of the master; the stream is longer by the bank's tail, piece and the marks are those
+        of the stage (moved with the stream: here not at all)."""
         from .join import Joiner
         from .text import PAUSE_SCALE, split_sentences
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
-        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if joiner is None:
-            joiner = Joiner(rate, device=self.device, **({} if pause_ms is None else {"pause_ms": pause_ms}))
-        self._check_joiner(joiner, sample_rate)
-        if master is not None:
-            self._check_master(master, sample_rate)
-        self._check_rooms(rooms, sample_rate)
+            joiner = Joiner(out_rate(sample_rate), device=self.device, **({} if pause_ms is None else {"pause_ms": pause_ms}))
         pause = joiner.cfg.gap if pause_ms is None else joiner.samples(pause_ms)
         if isinstance(sentences, str):
             sentences, classes = split_sentences(sentences, max_tokens)
@@ -965,17 +759,15 @@ class ArtSpeech:
             raise ValueError("synthesis_paragraph: nothing to say")
         if ref_mel is not None and not isinstance(ref_mel, (list, tuple)):
             ref_mel, features = [ref_mel] * B, None if features is None else [features] * B
-        marker = self._marker(marks, sample_rate)
+        st = self._stages(sample_rate, marks, join=joiner, gaps=gaps, window=window, max_len=max_len, master=master, rooms=rooms, room_sheet=room_sheet)
         inputs = self.packed_inputs(sentences, ref_mel, features, voice, prosody, fit=fit)
-        res, stream, out_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, sample_rate, marker,
-                                                     join=joiner, gaps=gaps, window=window, master=master, **self._room_stage(rooms, room_sheet),
-                                                     **({} if frame_cap is None else {"max_len": max_len}))
+        res, stream, out_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, st)
         with torch.cuda.device(self.device):
             _, stream = self._read_back(stream, out_off, "synthesis_paragraph")     # the one synchronisation: the length, then the stream
             piece = piece.cpu()
-            sm = None if marker is None else self._speech_marks(marker, sentences, m, piece=piece.tolist())
+            sm = None if st.marker is None else self._speech_marks(st.marker, sentences, m, piece=piece.tolist())
         self._record(None if frame_cap is not None else list(res["frames2"]), res)
-        return (stream, piece) if marker is None else (stream, piece, sm)
+        return (stream, piece) if st.marker is None else (stream, piece, sm)
 
     @torch.no_grad()
     def synthesis_cues(self, lines, ref_mel=None, voice=None, prosody=None, cues=None, bed=None, sample_rate=None, pcm16=False, frame_cap=None,
@@ -997,10 +789,9 @@ class ArtSpeech:
         (as_room_f32's return mode), ringing on behind the track's last line up to the end of the mix; the stems stay dry."""
         from . import cues as cue_mod
         from .join import Joiner
-        from .marks import SpeechMarks, kept_symbols
         if self.generator is None:
             raise RuntimeError("no vocoder attached: call attach_vocoder(h, checkpoint) first")
-        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        rate = out_rate(sample_rate)
         lines = [ln if isinstance(ln, cue_mod.Line) else cue_mod.Line(*ln) for ln in lines]
         sh = cue_mod.sheet(lines, rate)
         order = sh["order"]
@@ -1008,7 +799,6 @@ class ArtSpeech:
         B = len(ordered)
         if stems and pcm16 and master is None and rooms is None:
             raise ValueError("synthesis_cues: without a master the cue stage writes the int16 itself and keeps no fp32 stems; ask for one of stems and pcm16")
-        self._check_rooms(rooms, sample_rate)
         room_sheet = None
         if rooms is not None:
             G = len(sh["group_off"]) - 1
@@ -1023,9 +813,6 @@ class ArtSpeech:
             cues = cue_mod.Cues(rate, device=self.device)
         if joiner is None:
             joiner = Joiner(rate, device=self.device)
-        self._check_joiner(joiner, sample_rate)
-        if master is not None:
-            self._check_master(master, sample_rate)
         if any(ln.voice is not None for ln in ordered):
             voice = [ln.voice if ln.voice is not None else voice for ln in ordered]
             if any(v is None for v in voice):
@@ -1036,12 +823,11 @@ class ArtSpeech:
         if fit_slots and any(ln.end_s is not None for ln in ordered):
             fit = Fit.whole([None if ln.end_s is None else max(int(math.floor((ln.end_s - ln.start_s) * 40)), 1) for ln in ordered], frames=True)
         phonemes = [ln.phonemes for ln in ordered]
-        marker = self._marker(marks, sample_rate)
         if bed is not None:
             bed = torch.as_tensor(bed, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+        st = self._stages(sample_rate, marks, join=joiner, master=master, cues=cues, cue_sheet=sh, bed=bed, mix_cap=True, rooms=rooms, room_sheet=room_sheet)
         inputs = self.packed_inputs(phonemes, ref_mel, None, voice, prosody, fit=fit)
-        res, mix, mix_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, sample_rate, marker, join=joiner,
-                                                  master=master, cues=cues, cue_sheet=sh, bed=bed, mix_cap=True, **self._room_stage(rooms, room_sheet))
+        res, mix, mix_off, piece, m = self._chain(inputs, None if frame_cap is None else int(frame_cap), pcm16, st)
         o = self.last_cues
         with torch.cuda.device(self.device):
             _, mix = self._read_back(mix, mix_off, "synthesis_cues")                   # the one synchronisation: the length, then the mix
@@ -1052,15 +838,10 @@ class ArtSpeech:
             if stems:
                 y = o["y"][: out_off[-1]].cpu()
                 ret += ([y[out_off[g]: out_off[g + 1]] for g in range(len(out_off) - 1)],)
-            if stems or marker is not None:
+            if stems or st.marker is not None:
                 ret += (back(piece),)
-            if marker is not None:
-                syms = [kept_symbols(self.textcleaner, p) for p in phonemes]
-                n = int(m["anim_off"][-1])
-                origin = [out_off[int(report[b, 3])] for b in range(B)]
-                ret += (SpeechMarks(marker.rate, marker.fps, syms, m["marks"].cpu().numpy()[: sum(len(s) for s in syms)],
-                                    [(int(p[0]), int(p[1])) for p in piece.tolist()], origin, m["tracks"][:, :n].cpu().numpy(),
-                                    m["active"][:n].cpu().numpy(), m["anim_off"].cpu().numpy()),)
+            if st.marker is not None:                                                      # (positions from the first sample of each line's track)
+                ret += (self._speech_marks(st.marker, phonemes, m, piece=piece.tolist(), origin=[out_off[int(report[b, 3])] for b in range(B)]),)
         self._record(None if frame_cap is not None else list(res["frames2"]), res)
         return ret
 
@@ -1094,21 +875,14 @@ class ArtSpeech:
 
     @torch.no_grad()
     def _stream(self, inputs, frame_cap, core, pcm16):
-        from . import _lib
-        from .models import layout
         gen, hop = self.generator, self._hop()
         with torch.cuda.device(self.device):
+            res = self._forward(inputs, aux=True) if frame_cap is None else self._forward(inputs, frame_cap=frame_cap, out=inputs.setdefault("_out", {}))
+            (off_dev, mult, cap), _ = chain.geometry(res, frame_cap, gen.device)
             if frame_cap is None:
-                res = self._forward(inputs, aux=True)
-                lay = layout(res["frames2"], gen.device)
-                off_dev, mult, cap, lens = lay.col_off, 1, max(lay.N, 1), [int(f) for f in res["frames2"]]
+                lens = [int(f) for f in res["frames2"]]
             else:
-                res = self._forward(inputs, frame_cap=frame_cap, out=inputs.setdefault("_out", {}))
-                off_dev, mult, cap = res["frame_off"], 2, 2 * frame_cap
-                off = off_dev.cpu().tolist()                                # the one synchronisation: the offsets, then the status
-                if _lib.lib().as_device_status(0):
-                    raise _lib.HipLibraryError(f"synthesis_stream(frame_cap={frame_cap}) failed: a kernel reported {_lib.device_status()} "
-                                               "(as_device_status); results since then are invalid")
+                off = self._checked(off_dev, f"synthesis_stream(frame_cap={frame_cap}) failed")     # the one synchronisation
                 lens = [mult * (off[b + 1] - off[b]) for b in range(len(off) - 1)]
             self._record(lens, res)
             first = np.concatenate([[0], np.cumsum(lens)]).tolist()
@@ -1203,8 +977,7 @@ class ArtSpeech:
                 _, f0_p, ema_p = pack_reference(mels, f0_raw, ema_raw, ml, dev)
                 feat12 = ops.ref_features(rec_p, f0_p, ema_p, Nr, torch.tensor(_stats24(net), dtype=torch.float32, device=dev),
                                           torch.empty((12, Nr), dtype=torch.float32, device=dev))
-            rec_off = torch.tensor(np.concatenate([[0], np.cumsum(ml)]), dtype=torch.int32).to(dev)
-            tok_off = torch.tensor(np.concatenate([[0], np.cumsum(kw["tok_lens"])]), dtype=torch.int32).to(dev)
+            rec_off, tok_off = (chain.prefix_i32(stage.Device(dev), n) for n in (ml, kw["tok_lens"]))
             a = self._forward(kw, aux=True)                                          # pass A (reads its frame counts back)
             Tx, Ty = max(max(a["frames2"]), 1), max(ml)
             if Tx > mimic.MAX_T or Ty > mimic.MAX_T:
@@ -1218,8 +991,8 @@ class ArtSpeech:
             info = dict(rows=rows, target_dur=target, misses=misses, total=total, dur_a=a["dur_i"], dur_b=b_out["dur_i"],
                         duration=a["duration"], tok_off=tok_off, token_rows=trows, syn_frames=syn_frames, rec_frames=ml)
             if use_vocoder:
-                rs = self._out_resampler(sample_rate)
-                out = self._rows(self._back_end(kw, b_out, pcm16=pcm16, rs=rs, window=window)[0], self._sample_off(frames, rs))
+                st = self._stages(sample_rate, window=window)
+                out = self._rows(self._back_end(kw, b_out, st, pcm16=pcm16)[0], self._sample_off(frames, st.rs))
             else:
                 out = unpack(b_out["mel"], layout(frames, dev))
         self._record(frames, b_out)
